@@ -23,6 +23,12 @@ Prints ONE JSON line on rank 0.  value = candidate frames scored / s over all ra
 is scored each time it contributes a confidence to the searcher: g*g per grid call + 1 per
 verification call.  Weights are seeded synthetic OWL-ViT-B/32 (no checkpoint
 offline), data synthetic.
+
+A plain run does only what that line's headline needs: set up, warm up, time --steps searches, write
+--dump-outputs DIR (the last timed search's results as .npy; the same arguments give the same inputs),
+print the line.  --full adds everything else, all of it after the timed region: the single-search
+latency, the oracle replay of the timed keyframes, config.grid4, config.drop_in, config.other_configs
+and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -125,6 +131,16 @@ def parse():
                          "host cores (about 25-40 s at configs[1]; OWL-ViT backend, single-video workload); cpu_baseline.value is then the measured one "
                          "and the sampled extrapolation stays beside it; sample = the bounded sample only (rounds 1-4)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget for the CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything the headline figure does not need, after the timed region: the single-search latency, the oracle "
+                         "replay of the timed keyframes (config.keyframes_verified), config.grid4, config.drop_in, config.other_configs and the CPU "
+                         "baseline.  The --no-* options above switch single parts of it off.  Without --full a run sets up, warms up, times "
+                         "--steps searches, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the last timed search returned to its caller (rank 0) as DIR/<name>.npy: "
+                         "keyframe_timestamps (float64 [K]), keyframes (the K frames, float32 [K, H, W, 3]; a fixed seeded sample of "
+                         "its elements when the whole would pass 64 MB), score_distribution and keyframe_distribution (the searcher's "
+                         "score_distribution and P, float64 [nframes]).  The same arguments give the same inputs, run after run")
     args = ap.parse_args()
     if args.lockstep <= 0:
         args.lockstep = 24 if args.heuristic == "yolo" else 8
@@ -148,14 +164,15 @@ def run_group(heuristic, items, g, k=8):
 
 def run_groups(heuristic, groups, g, k=8):
     """Lock-step groups of independent (video, question) searches, the groups alternating on the GPU
-    (tstar_amd.lockstep.search_lockstep_groups); per group [(searcher, time_stamps)]."""
+    (tstar_amd.lockstep.search_lockstep_groups); per group [(searcher, time_stamps, keyframes)]."""
     from tstar_amd.lockstep import search_lockstep_groups
     sss = [[make_searcher(heuristic, it, g, k) for it in items] for items in groups]
     if len(sss) == 1 and len(sss[0]) == 1:
         s_ = sss[0][0]
-        return [[(s_, s_.search()[1])]]
+        frames, ts = s_.search()
+        return [[(s_, ts, frames)]]
     res = search_lockstep_groups(sss)
-    return [[(s_, r[1]) for s_, r in zip(ss, rr)] for ss, rr in zip(sss, res)]
+    return [[(s_, r[1], r[0]) for s_, r in zip(ss, rr)] for ss, rr in zip(sss, res)]
 
 
 def verify_keyframes(heuristic, item, g, k, timed_keyframes):
@@ -182,6 +199,29 @@ def verify_keyframes(heuristic, item, g, k, timed_keyframes):
                 "iterations": len(log), "verification_calls": int(sum(len(it["verify"]) for it in ref.trace))}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what the last timed search handed its caller, as float32 / float64 .npy files (rank 0).  ``last`` is one entry of
+    run_many's result, (searcher, time_stamps, seconds, keyframes).  The searcher's state arrays are read after the timed region (a caller
+    reads them the same way once search() has returned).  Keyframes past DUMP_MAX_BYTES are cut to a fixed seeded sample of elements."""
+    s_, ts, _, frames = last
+    arrays = {"keyframe_timestamps": np.asarray(ts, dtype=np.float64),
+              "score_distribution": np.asarray(s_.score_distribution, dtype=np.float64),
+              "keyframe_distribution": np.asarray(s_.P, dtype=np.float64)}
+    budget = (DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values())) // 4
+    kf = np.asarray(frames).reshape(-1)
+    if kf.size > budget:
+        kf = kf[np.sort(np.random.RandomState(0).randint(0, kf.size, budget))]
+    else:
+        kf = np.asarray(frames)
+    arrays["keyframes"] = kf.astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def grid4_record(heuristic, store, nframes, k):
     """The reference's DEFAULT configuration (TStarFramework.py:34-35: grid 4x4, 16 frames per iteration, <= 63 iterations
     per video) on the same video and question, outside the driver-timed region: one search ALONE (the latency a single
@@ -202,12 +242,12 @@ def grid4_record(heuristic, store, nframes, k):
     dt = time.perf_counter() - t0
     grp = [x for gr in grps for x in gr]
     nv = len(grp)
-    frames = sum(s_.frames_scored for s_, _ in grp)
+    frames = sum(s_.frames_scored for s_, *_ in grp)
     return {"grid": "4x4 (16 frames/iter, the reference default)", "lockstep16_frames_per_s": frames / dt, "lockstep16_sec_per_video": dt / nv,
             "lockstep16_videos": nv, "lockstep16_groups_alternating": 2,
             "solo_sec_per_video": t_solo, "solo_frames_per_s": solo[0][0].frames_scored / t_solo,
-            "grid_calls_per_video": sum(s_.iterations for s_, _ in grp) / nv,
-            "verify_calls_per_video": sum(s_.detector_calls - s_.iterations for s_, _ in grp) / nv,
+            "grid_calls_per_video": sum(s_.iterations for s_, *_ in grp) / nv,
+            "verify_calls_per_video": sum(s_.detector_calls - s_.iterations for s_, *_ in grp) / nv,
             "solo_bound": "kernel throughput at small batch: per iteration a B ~ 9.5 verification forward (M ~ 5500: 146-186 TFLOP/s algorithmic on its GEMMs, "
                           "~0.62 ms an image against 0.55 ms in the lock-step bench) and a B = 1 grid forward (M = 577: 120-456 wave tiles per GEMM for 1024 SIMDs, "
                           "2.06 ms alone), 63 iterations, 670 detector images.  Round 5 ran them back to back on one stream (593 ms of kernels in a 580 ms "
@@ -605,7 +645,8 @@ def other_configs():
            and not k.startswith("TSTAR_")}
     for name, flags in runs.items():
         t1 = time.perf_counter()
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "1", "--no-cpu-baseline", "--no-grid4", "--no-other-configs", "--no-drop-in"] + flags
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-grid4", "--no-other-configs",
+               "--no-drop-in"] + flags
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -732,7 +773,7 @@ def main():
         torch.cuda.synchronize()
 
     def run_many(items):
-        """Run one search per item, `conc` lock-step groups at a time; returns per-search (searcher, timestamps, seconds)."""
+        """Run one search per item, `conc` lock-step groups at a time; returns per-search (searcher, timestamps, seconds, keyframes)."""
         q = queue.Queue()
         L = max(1, min(args.lockstep, 31))
         PL = max(1, args.pipeline)
@@ -760,8 +801,8 @@ def main():
                         t1 = time.perf_counter()
                         grps = run_groups(heuristics[w], sd, g, args.search_nframes)
                         torch.cuda.synchronize()
-                        for j, (s_, ts_) in enumerate([x for grp in grps for x in grp]):
-                            out[i + j] = (s_, ts_, time.perf_counter() - t1)
+                        for j, (s_, ts_, fr_) in enumerate([x for grp in grps for x in grp]):
+                            out[i + j] = (s_, ts_, time.perf_counter() - t1, fr_)
             except Exception as e:                      # surface worker failures in the main thread
                 errs.append(e)
 
@@ -784,9 +825,9 @@ def main():
     items = [make_item(k * world + rank, 2025 + k * world + rank) for k in range(args.steps)]
     warm_items = [dict(items[w % len(items)], seed=10_000 + rank * 1000 + w) for w in range(n_warm)] if items else []
     run_many(warm_items)
-    # latency of ONE search running alone (the "sec/video to 8 keyframes" half of the metric, untimed):
+    # latency of ONE search running alone (the "sec/video to 8 keyframes" half of the metric, untimed; --full only):
     solo_latency = None
-    if n_warm > 0 and items:
+    if args.full and n_warm > 0 and items:
         # a search alone runs other batch shapes than a lock-step group (its own verification batches): one untimed run
         # first, like the warm-up of the groups, so that the figure carries no first-use cost
         run_group(heuristics[0], [dict(items[0], seed=19_000 + rank)], g, args.search_nframes)
@@ -909,9 +950,11 @@ def main():
                                         "weight planes global -> VGPR in fragment order a full K step ahead, software-pipelined per wave)"), BF16_MFMA_PEAK_TFLOPS, 6.0
     else:
         gemm_kernel, peak, exec_mult = "gemm_f32_kernel (v_mfma_f32_32x32x2_f32)", FP32_MFMA_PEAK_TFLOPS, 1.0
-    # post-run parity check of the keyframes this run produced (rank 0, step 0): solo re-run + oracle replay, untimed
+    if rank == 0 and args.dump_outputs and res:
+        dump_outputs(args.dump_outputs, res[-1])
+    # post-run parity check of the keyframes this run produced (rank 0, step 0): solo re-run + oracle replay, untimed (--full)
     verified, verify_detail = None, None
-    if rank == 0 and not args.no_verify and items:
+    if rank == 0 and args.full and not args.no_verify and items:
         verified, verify_detail = verify_keyframes(heuristics[0], items[0], g, args.search_nframes, keys[0])
     wl_name = {"single": "configs[1]", "haystack": "configs[2] shape (weak scaling: --steps items per rank)",
                "haystack32": "configs[2]"}[workload]
@@ -1007,15 +1050,16 @@ def main():
             out["roofline"].pop("attention_kernel", None)
             out["roofline"]["peak_note"] = "f32 VALU spec peak (v_pk_fma_f32 rate); a tiled f32 VALU GEMM sustains about a third of it on this part (MI355X guide: 52 TFLOP/s)"
         g4rec = None
-        if world == 1 and not args.no_grid4 and args.heuristic == "owl" and workload == "single" and g != 4:
+        full = world == 1 and args.full                      # the records below are not the headline's: --full only
+        if full and not args.no_grid4 and args.heuristic == "owl" and workload == "single" and g != 4:
             g4rec = grid4_record(heuristics[0], shared_store, args.nframes, args.search_nframes)
             out["config"]["grid4"] = g4rec
-        if world == 1 and not args.no_drop_in and args.heuristic == "owl" and workload == "single":
+        if full and not args.no_drop_in and args.heuristic == "owl" and workload == "single":
             try:
                 out["config"]["drop_in"] = drop_in_record(shared_store, args.search_nframes)
             except Exception as e:                                  # an extra record must never take the headline line down
                 out["config"]["drop_in"] = {"error": repr(e)}
-        if (world == 1 and not args.no_other_configs and args.heuristic == "owl" and args.weights == "f32x3" and workload == "single"
+        if (full and not args.no_other_configs and args.heuristic == "owl" and args.weights == "f32x3" and workload == "single"
                 and args.nframes == N_FRAMES and g == 16 and args.search_nframes == 8):
             out["config"]["other_configs"] = other_configs()
             # the native-f32 figure of the same workload beside the headline (what rounds 1-4 reported as `value`)
@@ -1024,7 +1068,7 @@ def main():
                 out["config"]["f32_native"] = {"value": nat[0]["value"], "unit": nat[0]["unit"], "ms_per_step": nat[0]["ms_per_step"],
                                                "roofline_frac_of_157.3_TFLOPs": nat[0]["roofline"]["frac"], "keyframes_verified": nat[0]["keyframes_verified"],
                                                "headline_over_native": out["value"] / nat[0]["value"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             stats_ = {"grid_calls": grid_calls / args.steps, "verify_calls": verify_calls / args.steps, "grid4": g4rec}
             out["cpu_baseline"] = cpu_baseline_yolo(args, stats_) if args.heuristic == "yolo" else cpu_baseline(args, stats_)
             if args.cpu_baseline == "full" and args.heuristic == "owl" and workload == "single":

@@ -246,11 +246,42 @@ def test_bench_gpus2_over_rccl():
     assert len(two["config"]["host_cpu_sec_per_video_by_rank"]) == 2
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: one JSON line with the headline keys and
+    none of the --full records, and DIR holds what the last timed search returned to its caller (float32 / float64, 64 MB at most):
+    its keyframe time stamps (= the last gathered keyframe row), the K frames, the searcher's score and keyframe distributions.
+    Two runs with the same arguments write the same arrays."""
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        runs.append((_bench_line([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                                 dict(os.environ)), out))
+    d, out = runs[0]
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config", "roofline"):
+        assert k in d, k
+    c = d["config"]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["value"] > 1000
+    assert "frames scored/sec" in d["metric"] and "3 bf16 terms" in d["dtype"]
+    assert abs(d["ms_per_step"] * 1e-3 - c["sec_per_video"]) < 1e-9 and len(c["gathered_keyframes"]) == 3
+    assert "cpu_baseline" not in d and not {"grid4", "drop_in", "other_configs", "f32_native"} & set(c)
+    assert c["keyframes_verified"] is None and c["single_search_alone_latency_sec"] is None
+    names = ("keyframe_timestamps", "keyframes", "score_distribution", "keyframe_distribution")
+    assert sorted(p.name for p in out.iterdir()) == sorted(n + ".npy" for n in names)
+    arrs = {n: np.load(out / (n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    assert [int(t) for t in arrs["keyframe_timestamps"]] == c["gathered_keyframes"][-1]
+    kf = arrs["keyframes"]
+    assert kf.shape == (8, 360, 640, 3) and kf.dtype == np.float32 and kf.min() >= 0 and kf.max() <= 255 and np.array_equal(kf, np.round(kf))
+    assert arrs["score_distribution"].shape == arrs["keyframe_distribution"].shape == (3600,) and arrs["score_distribution"].max() > 0
+    for n in names:
+        assert np.array_equal(arrs[n], np.load(runs[1][1] / (n + ".npy"))), n
+
+
 def test_bench_line_contract():
-    """`python bench.py --steps K --warmup W` as the driver runs it at N = 1: exactly one JSON line on stdout with the
+    """`python bench.py --full --steps K --warmup W` at N = 1: exactly one JSON line on stdout with the
     contract's keys, the roofline and cpu_baseline objects, self-consistent figures (value = frames / time, the time shares
     below 1, achieved below the peak) and the keyframes of the timed region verified through the oracle."""
-    d = _bench_line([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-seconds", "3", "--no-grid4"],
+    d = _bench_line([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "3", "--no-grid4"],
                     dict(os.environ))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):

@@ -727,6 +727,30 @@ def test_bench_traffic_is_only_quoted_for_the_same_launch_population(tmp_path):
     assert bench.match_traffic(pop16, 1.3e9, "yolo_pmc_conv_traffic", str(d)) == (None, None, None, "no PMC collection under profiles/")
 
 
+def test_bench_dump_outputs_stays_within_64_mb(tmp_path):
+    """bench.dump_outputs: float32 / float64 files only, 64 MB in all; keyframes that would pass that (K = 32 frames at 360x640) are cut
+    to the same seeded sample of elements every time, small ones are written whole."""
+    import types
+    import bench
+    rs = np.random.RandomState(1)
+    s_ = types.SimpleNamespace(score_distribution=rs.random_sample(14400), P=rs.random_sample(14400))
+    big = rs.randint(0, 256, (32, 360, 640, 3)).astype(np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), (s_, [float(t) for t in range(32)], 0.1, big))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["keyframe_distribution.npy", "keyframe_timestamps.npy", "keyframes.npy", "score_distribution.npy"]
+    arrs = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= (64 << 20) + 4 * 256      # + the .npy headers
+    assert arrs["keyframes.npy"].dtype == np.float32 and arrs["keyframes.npy"].ndim == 1 and arrs["keyframes.npy"].size < big.size
+    assert np.array_equal(arrs["score_distribution.npy"], s_.score_distribution) and np.array_equal(arrs["keyframe_timestamps.npy"], np.arange(32.0))
+    for f in files:
+        assert np.array_equal(arrs[f], np.load(tmp_path / "b" / f)), f
+    small = big[:8]
+    bench.dump_outputs(str(tmp_path / "c"), (s_, [1.0] * 8, 0.1, small))
+    assert np.array_equal(np.load(tmp_path / "c" / "keyframes.npy"), small.astype(np.float32))
+
+
 def test_bench_self_spawn_command(monkeypatch):
     """`python bench.py --gpus N` typed without a launcher (WORLD_SIZE unset) starts its own ranks: the command is the driver's
     (torch.distributed.run, one process per GPU, rendezvous on 127.0.0.1, the user's flags passed through), launcher variables of

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 cd /tmp
 PY="python $ROOT/bench.py"
 rm -rf /tmp/prof_yolo
-rocprofv3 --kernel-trace --stats -d /tmp/prof_yolo -o kt -- $PY --heuristic yolo --steps 48 --warmup 1 --no-cpu-baseline --no-verify --no-other-configs > "$OUT/${TAG}_bench_yolo_under_rocprofv3.json" 2> "$OUT/rocprof_yolo.err"
+rocprofv3 --kernel-trace --stats -d /tmp/prof_yolo -o kt -- $PY --full --heuristic yolo --steps 48 --warmup 1 --no-cpu-baseline --no-verify --no-other-configs > "$OUT/${TAG}_bench_yolo_under_rocprofv3.json" 2> "$OUT/rocprof_yolo.err"
 DBY=$(find /tmp/prof_yolo -name '*.db' | head -1)
 python $ROOT/tools/rocpd_stats.py "$DBY" --timed-region "$OUT/${TAG}_bench_yolo_under_rocprofv3.json" --check > "$OUT/${TAG}_yolo_rocprofv3_kernel_stats_timed_region.md" \
     || echo "collect_yolo_profiles: the kernel trace does NOT reproduce the bench line's conv launch average / count" >&2
@@ -34,5 +34,5 @@ timeout 700 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/prof_yolo5 -o pmc 
 python $ROOT/tools/rocpd_traffic.py "$(find /tmp/prof_yolo4 -name '*.db' | head -1)" "$(find /tmp/prof_yolo5 -name '*.db' | head -1)" "conv_valu|conv_sw|conv_halo" \
     "rocprofv3 --kernel-trace --pmc <COUNTER> -- python bench.py --heuristic yolo --steps 48 --warmup 0 --no-cpu-baseline --no-verify --no-other-configs (tools/collect_yolo_profiles.sh)" "$OUT/pmc_pass_yolo_FETCH_SIZE.json" > "$OUT/${TAG}_yolo_pmc_conv_traffic.json"
 cp "$OUT/${TAG}_yolo_pmc_conv_traffic.json" "$ROOT/profiles/${TAG}_yolo_pmc_conv_traffic.json"
-$PY --heuristic yolo --steps 48 --warmup 1 > "$OUT/${TAG}_bench_yolo.json" 2>> "$OUT/bench_yolo.err"
+$PY --full --heuristic yolo --steps 48 --warmup 1 > "$OUT/${TAG}_bench_yolo.json" 2>> "$OUT/bench_yolo.err"
 ls -la "$OUT" | grep yolo
