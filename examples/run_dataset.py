@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--lockstep", type=int, default=16)
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default="./output/tstar_results.json")
+    ap.add_argument("--owl-model", default="google/owlvit-base-patch32",
+                    help="OWL-ViT checkpoint (name or directory; B/32 or B/16); seeded synthetic B/32 weights when none is on disk")
     args = ap.parse_args()
 
     import torch
@@ -54,7 +56,8 @@ def main():
 
     items = [{"video_path": f"synthetic://n={args.nframes},seed={100 + i}", "targets": QUESTIONS[i % 4][0],
               "cues": QUESTIONS[i % 4][1]} for i in range(args.items)]
-    heuristic = initialize_heuristic("owl-vit", synthetic_seed=0, max_batch=64, device=f"cuda:{local}")
+    heuristic = initialize_heuristic("owl-vit", model_name_or_path=args.owl_model, synthetic_seed=0, max_batch=64,
+                                     device=f"cuda:{local}")
     mine = shard_items(len(items), world, rank)
     rows, dists = [], {}
     # two lock-step groups alternate on the GPU: one group's host bookkeeping runs under the other's verification batch

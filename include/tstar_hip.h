@@ -90,6 +90,19 @@ typedef struct tstar_owl tstar_owl;
 int tstar_owl_create(tstar_owl** out, const float* h_vision_blob, size_t n_vision,
                      const float* h_text_blob, size_t n_text, const float* h_norm_lut, int max_batch,
                      int weights_mode);
+/* Added entries (tstar_abi_version() stays 3).  The same for a vision tower of patch geometry (image_size, patch_size):
+ * (768, 32) = OWL-ViT B/32 (what tstar_owl_create builds: 24 x 24 = 576 patches, 577 tokens) or (768, 16) = B/16
+ * (48 x 48 = 2304 patches, 2305 tokens, patch-embed K = 768); every other geometry is refused before anything is
+ * allocated.  Both share every width (vision 768 / 3072 / 12 layers / 12 heads, the text tower, projection 512).  The
+ * vision blob holds tstar_owl_vision_blob_floats_ex(image_size, patch_size) floats.  A forward runs in chunks of at most
+ * 1024 images at B/32 and 256 at B/16 (no chunk holds more token rows than B/32's 1024 images, so every activation
+ * workspace stays below 2^31 elements); a larger max_batch is accepted and its batches are scored chunk by chunk. */
+int tstar_owl_create_ex(tstar_owl** out, int image_size, int patch_size, const float* h_vision_blob, size_t n_vision,
+                        const float* h_text_blob, size_t n_text, const float* h_norm_lut, int max_batch, int weights_mode);
+/* floats of a vision blob of that geometry (0 if it is not supported) */
+size_t tstar_owl_vision_blob_floats_ex(int image_size, int patch_size);
+/* np, the detections per image of the handle's geometry (576 at B/32, 2304 at B/16; -1 for a NULL handle) */
+int tstar_owl_num_patches(tstar_owl* h);
 int tstar_owl_destroy(tstar_owl* h);
 
 /* Replaces the text half of processor(...)+model(...) that the reference recomputes on every
@@ -122,16 +135,17 @@ int tstar_owl_get_query_embeds(tstar_owl* h, int query_set, float* h_out, int Q,
  * detection->grid-cell loop of TStarSearcher.imageGridScoreFunction
  * (interface_searcher.py:129-150) for B images of identical size in one call.
  *   d_images      u8  [B,H,W,3] RGB (the grid image, or a verification frame)
+ * np = tstar_owl_num_patches(h): 576 for a B/32 handle, 2304 for B/16; detections come in patch order.
  *   h_image_query_set  i32 [B] (host) query set of every image, or NULL (all images use set 0)
- *   d_scores      f32 [B,576]   sigmoid(max_q logit)            (dense: not thresholded)
- *   d_labels      i32 [B,576]   argmax_q logit
- *   d_boxes_xyxy  f32 [B,576,4] pixels of the passed image
+ *   d_scores      f32 [B,np]    sigmoid(max_q logit)            (dense: not thresholded)
+ *   d_labels      i32 [B,np]    argmax_q logit
+ *   d_boxes_xyxy  f32 [B,np,4]  pixels of the passed image
  *   d_cell_conf   f64 [B,rows*cols]  max over detections with score > 0.005 of
  *                                    float64(score) * class_weight[label], row-major cells; 0 if none
  *   d_cell_mask   u32 [B,rows*cols]  bit q set <=> a kept detection with label q fell in the cell
  *   d_n_kept      i32 [B]       number of detections with score > 0.005 (may be NULL)
- *   d_logits      f32 [B,576,Q] raw logits (may be NULL; needs the same Q for every image)
- *   d_boxes_cxcywh f32 [B,576,4] pred_boxes (may be NULL)
+ *   d_logits      f32 [B,np,Q]  raw logits (may be NULL; needs the same Q for every image)
+ *   d_boxes_cxcywh f32 [B,np,4] pred_boxes (may be NULL)
  */
 int tstar_owl_score(tstar_owl* h, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
                     const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
@@ -151,9 +165,10 @@ int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B,
                          float* d_boxes_cxcywh, void* stream);
 
 /* Diagnostics for parity tests: the preprocessed 768x768 u8 image of the LAST chunk's image 0
- * (after bicubic) and its patch-embed A operand can be read back. */
+ * (after bicubic) and its patch-embed A operand can be read back.  d_out_patches is [B*np, 3*P*P] for the handle's
+ * patch size P: [B*576, 3072] at B/32, [B*2304, 768] at B/16 (row b*np + (y/P)*G + x/P, column c*P*P + (y%P)*P + x%P). */
 int tstar_owl_debug_preprocess(tstar_owl* h, const uint8_t* d_images, int B, int H, int W,
-                               uint8_t* d_out_u8 /* [B,768,768,3] */, float* d_out_patches /* [B*576,3072] */,
+                               uint8_t* d_out_u8 /* [B,768,768,3] */, float* d_out_patches /* [B*np,3*P*P] */,
                                void* stream);
 
 /* ------------------------------------------------------------------ second detector backend: YOLO-World (D13)
@@ -299,6 +314,10 @@ int tstar_ssim_pairwise(const uint8_t* d_gt, int G, const uint8_t* d_pred, int P
  * device: paints the 1-px box of every kept detection (score > 0.005) of image b -- d_boxes_xyxy [B,576,4] and
  * d_scores [B,576] as written by tstar_owl_score -- onto d_images u8 [B,H,W,3] in place. */
 int tstar_draw_boxes(uint8_t* d_images, int B, int H, int W, const float* d_boxes_xyxy, const float* d_scores, void* stream);
+/* The same for np detections per image (d_boxes_xyxy [B,np,4], d_scores [B,np]; np = tstar_owl_num_patches of the handle
+ * that scored them).  Added entry; tstar_draw_boxes is this with np = 576. */
+int tstar_draw_boxes_np(uint8_t* d_images, int B, int H, int W, const float* d_boxes_xyxy, const float* d_scores, int np,
+                        void* stream);
 
 /* ------------------------------------------------------------------ kernel-level diagnostics
  * (used by tests/ and bench.py to check and time individual kernels) */

@@ -26,6 +26,9 @@ SIGNATURES = {
     "tstar_owl_vision_blob_floats": (_sz, []),
     "tstar_owl_text_blob_floats": (_sz, []),
     "tstar_owl_create": (_i, [C.POINTER(_vp), _vp, _sz, _vp, _sz, _vp, _i, _i]),
+    "tstar_owl_create_ex": (_i, [C.POINTER(_vp), _i, _i, _vp, _sz, _vp, _sz, _vp, _i, _i]),
+    "tstar_owl_vision_blob_floats_ex": (_sz, [_i, _i]),
+    "tstar_owl_num_patches": (_i, [_vp]),
     "tstar_owl_destroy": (_i, [_vp]),
     "tstar_owl_set_queries": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),
     "tstar_owl_set_queries_many": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -76,6 +79,7 @@ SIGNATURES = {
     "tstar_gemm_f32x3_pre": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tstar_layernorm_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "tstar_draw_boxes": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "tstar_draw_boxes_np": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "tstar_attention_split": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "tstar_attention_x3": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "tstar_attention_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),

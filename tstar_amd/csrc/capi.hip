@@ -1,5 +1,5 @@
 // C ABI of libtstar_hip.so (include/tstar_hip.h): handle management and the
-// OWL-ViT-B/32 forward orchestration over the hand-written gfx950 kernels.
+// OWL-ViT (B/32, B/16) forward orchestration over the hand-written gfx950 kernels.
 #include "../../include/tstar_hip.h"
 #include "common.h"
 #include "heads.h"
@@ -83,8 +83,10 @@ struct tstar_owl {
     VisionW vw{};
     TextW tw{};
     bool has_text = false, has_vision = false;
+    OwlGeom geom{};                                                  // patch geometry of the vision tower (B/32 or B/16)
     float* d_lut = nullptr;
     int max_batch = 0;
+    int chunk_cap = 0;                                               // images per forward chunk: min(max_batch, owl_chunk_limit(geom))
     size_t mpad = 0;
     // activation workspaces (per chunk of `cap` images).  Lane 0 is the handle's own (max_batch images, allocated at creation; the
     // text tower runs in it).  Lane 1 is a SMALL second one, allocated on first use (tstar_owl_score_lane): a forward that runs in it
@@ -160,9 +162,16 @@ static int upload_blob(const float* h_blob, size_t n_expected_check, float** d_o
     return TSTAR_OK;
 }
 
-static size_t vision_floats() {
-    size_t n = 0; VisionW w; map_vision(w, [&](size_t k) -> const float* { n += k; return nullptr; }); return n;
+static size_t vision_floats(const OwlGeom& g) {
+    size_t n = 0; VisionW w; map_vision(w, g, [&](size_t k) -> const float* { n += k; return nullptr; }); return n;
 }
+
+// Images per forward chunk.  B/16 has four times B/32's tokens per image; a chunk is capped so that it never holds more
+// rows than B/32's largest chunk (1024 images x 577 tokens, the row range every kernel of the forward already runs at):
+// 1024 images at B/32, 256 at B/16 (590080 rows; hid [Mp, 3072] = 1.81e9 floats).  Every workspace then stays below 2^31
+// elements, so the kernels' 32-bit element offsets (the wide GEMM epilogue's among them) cannot wrap; checked at creation.
+static int owl_chunk_limit(const OwlGeom& g) { return 1024 * V_NP / g.np; }
+static size_t lane_rows(int cap, const OwlGeom& g) { return round_up((size_t)cap * g.ntok, 128); }
 static size_t text_floats() {
     size_t n = 0; TextW w; map_text(w, [&](size_t k) -> const float* { n += k; return nullptr; }); return n;
 }
@@ -231,14 +240,15 @@ static int preprocess_chunk(tstar_owl* h, tstar_owl::Lane& L, const uint8_t* d_i
         L.tmp_u8_bytes = need;
     }
     RC(resample_h_u8(d_images, L.tmp_u8, B, H, W, *th, s));
-    RC(resample_v_normalize_patchify(L.tmp_u8, out_patches, out_u8, B, H, *tv, h->d_lut, s));
+    RC(resample_v_normalize_patchify(L.tmp_u8, out_patches, out_u8, B, H, *tv, h->d_lut, h->geom.patch, s));
     return TSTAR_OK;
 }
 
 // One activation workspace for forward chunks of up to `cap` images: x, xn, att [Mp, 768], qkv [Mp, 2304], hid [Mp, 3072] with
-// Mp = roundup(cap * 577, 128); zero-filled (rows past M are read by the last GEMM tile of a launch).
-static hipError_t alloc_lane(tstar_owl::Lane& L, int cap) {
-    const size_t mp = round_up((size_t)cap * V_NTOK, 128);
+// Mp = roundup(cap * ntok, 128) (ntok 577 at B/32, 2305 at B/16); zero-filled (rows past M are read by the last GEMM tile of a
+// launch).  hid also holds the patch-embed A operand [cap * np, 3 P^2] (3072 or 768 columns: fits either way).
+static hipError_t alloc_lane(tstar_owl::Lane& L, int cap, const OwlGeom& g) {
+    const size_t mp = lane_rows(cap, g);
     hipError_t e = hipSuccess;
     auto alloc = [&](float** p, size_t n) { if (e == hipSuccess) { e = hipMalloc(p, n * sizeof(float)); if (e == hipSuccess) e = hipMemset(*p, 0, n * sizeof(float)); } };
     alloc(&L.x, mp * V_D); alloc(&L.xn, mp * V_D); alloc(&L.qkv, mp * 3 * V_D); alloc(&L.att, mp * V_D); alloc(&L.hid, mp * V_FF);
@@ -255,13 +265,22 @@ extern "C" {
 
 const char* tstar_last_error(void) { return g_err.c_str(); }
 int tstar_abi_version(void) { return 3; }
-size_t tstar_owl_vision_blob_floats(void) { return vision_floats(); }
+size_t tstar_owl_vision_blob_floats(void) { return vision_floats(OwlGeom{}); }
 size_t tstar_owl_text_blob_floats(void) { return text_floats(); }
+size_t tstar_owl_vision_blob_floats_ex(int image_size, int patch_size) {
+    OwlGeom g;
+    if (!owl_geom(image_size, patch_size, &g)) { set_error("tstar_owl_vision_blob_floats_ex: unsupported geometry (image 768, patch 32 or 16)"); return 0; }
+    return vision_floats(g);
+}
+int tstar_owl_num_patches(tstar_owl* h) {
+    if (!h) { set_error("tstar_owl_num_patches: null handle"); return -1; }
+    return h->geom.np;
+}
 
 static int make_bf16_copies(tstar_owl* h, int mode) {
     struct Mat { const float* w; int n, k; };
     std::vector<Mat> mats;
-    mats.push_back({h->vw.patch_w, V_D, V_PATCH_K});
+    mats.push_back({h->vw.patch_w, V_D, h->geom.patch_k});
     auto layer = [&](const LayerW& l, int d, int ff) {
         mats.push_back({l.qkv_w, 3 * d, d}); mats.push_back({l.out_w, d, d});
         mats.push_back({l.fc1_w, ff, d}); mats.push_back({l.fc2_w, d, ff});
@@ -304,6 +323,14 @@ static int make_bf16_copies(tstar_owl* h, int mode) {
 
 int tstar_owl_create(tstar_owl** out, const float* h_vision_blob, size_t n_vision, const float* h_text_blob,
                      size_t n_text, const float* h_norm_lut, int max_batch, int weights_mode) {
+    return tstar_owl_create_ex(out, 768, 32, h_vision_blob, n_vision, h_text_blob, n_text, h_norm_lut, max_batch, weights_mode);
+}
+
+int tstar_owl_create_ex(tstar_owl** out, int image_size, int patch_size, const float* h_vision_blob, size_t n_vision,
+                        const float* h_text_blob, size_t n_text, const float* h_norm_lut, int max_batch, int weights_mode) {
+    OwlGeom geom;
+    TSTAR_REQUIRE(owl_geom(image_size, patch_size, &geom),
+                  "tstar_owl_create_ex: unsupported geometry; supported: image 768 with patch 32 (B/32) or 16 (B/16)");
     TSTAR_REQUIRE(out && (h_vision_blob || h_text_blob), "tstar_owl_create: null argument");
     TSTAR_REQUIRE(!h_vision_blob || h_norm_lut, "tstar_owl_create: the vision tower needs the normalisation LUT");
     TSTAR_REQUIRE(h_vision_blob || weights_mode == TSTAR_WEIGHTS_F32, "tstar_owl_create: a text-only handle runs in float32");
@@ -316,10 +343,14 @@ int tstar_owl_create(tstar_owl** out, const float* h_vision_blob, size_t n_visio
         set_error("tstar_owl_create: no HIP device visible (this library has no CPU path)");
         return TSTAR_ERR_HIP;
     }
+    const int chunk_cap = max_batch < owl_chunk_limit(geom) ? max_batch : owl_chunk_limit(geom);
+    TSTAR_REQUIRE(lane_rows(chunk_cap, geom) * V_FF < (size_t(1) << 31),
+                  "tstar_owl_create: a forward chunk's workspace would reach 2^31 elements");
     tstar_owl* h = new tstar_owl();
+    h->geom = geom;
     int rc = TSTAR_OK;
     if (h_vision_blob) {               // NULL: a text-only handle (CLIP text features for the YOLO-World backend)
-        rc = upload_blob(h_vision_blob, n_vision, &h->d_vision, [&](auto&& take) { map_vision(h->vw, take); });
+        rc = upload_blob(h_vision_blob, n_vision, &h->d_vision, [&](auto&& take) { map_vision(h->vw, h->geom, take); });
         if (rc) { delete h; return rc; }
         h->has_vision = true;
     }
@@ -329,10 +360,11 @@ int tstar_owl_create(tstar_owl** out, const float* h_vision_blob, size_t n_visio
         h->has_text = true;
     }
     h->max_batch = max_batch;
-    h->mpad = round_up((size_t)max_batch * V_NTOK, 128);
+    h->chunk_cap = chunk_cap;
+    h->mpad = lane_rows(chunk_cap, geom);
     hipError_t e = hipSuccess;
     auto alloc = [&](float** p, size_t n) { if (e == hipSuccess) { e = hipMalloc(p, n * sizeof(float)); if (e == hipSuccess) e = hipMemset(*p, 0, n * sizeof(float)); } };
-    e = alloc_lane(h->lane[0], max_batch);
+    e = alloc_lane(h->lane[0], chunk_cap, geom);
     alloc(&h->d_lut, 768);
     constexpr int NSQ = TSTAR_OWL_MAX_SETS * TSTAR_OWL_MAX_QUERIES;
     alloc(&h->q_raw, (size_t)NSQ * PROJ); alloc(&h->qn, (size_t)NSQ * PROJ);
@@ -558,10 +590,10 @@ int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B,
         // lane 1: allocated on first use (a one-off, like the resample tables) for forward chunks of min(max_batch, max(TSTAR_OWL_AUX_BATCH, B))
         // images, and grown when a larger batch arrives (the device is drained first)
         int need = B > TSTAR_OWL_AUX_BATCH ? B : TSTAR_OWL_AUX_BATCH;
-        if (need > h->max_batch) need = h->max_batch;
+        if (need > h->chunk_cap) need = h->chunk_cap;
         if (!L.x || L.cap < need) {
             if (L.x) { TSTAR_HIP_CHECK(hipDeviceSynchronize()); free_lane(L); }      // (rare: whichever stream used the smaller workspace last)
-            const hipError_t e = alloc_lane(L, need);
+            const hipError_t e = alloc_lane(L, need, h->geom);
             if (e != hipSuccess) {
                 free_lane(L);
                 set_error(std::string("tstar_owl_score_lane: workspace allocation failed: ") + hipGetErrorString(e));
@@ -589,18 +621,20 @@ int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B,
         TSTAR_HIP_CHECK(hipMemcpyAsync(L.d_image_set, h_image_query_set, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
     }
     const int ncell = grid_rows * grid_cols;
+    const OwlGeom& G = h->geom;
+    const int NP = G.np, NTOK = G.ntok, PK = G.patch_k;
     for (int b0 = 0; b0 < B; b0 += L.cap) {
         const int Bc = (B - b0) < L.cap ? (B - b0) : L.cap;
-        const int M = Bc * V_NTOK, MP = Bc * V_NP;
+        const int M = Bc * NTOK, MP = Bc * NP;
         RC(preprocess_chunk(h, L, d_images + (size_t)b0 * H * W * 3, Bc, H, W, nullptr, L.hid, s));
-        GemmArgs pg = mk_gemm(h, L.hid, h->vw.patch_w, L.x, nullptr, nullptr, MP, V_D, V_PATCH_K, V_PATCH_K, V_D, ACT_NONE);
-        pg.pos = h->vw.pos_emb; pg.patch_np = V_NP;
+        GemmArgs pg = mk_gemm(h, L.hid, h->vw.patch_w, L.x, nullptr, nullptr, MP, V_D, PK, PK, V_D, ACT_NONE);
+        pg.pos = h->vw.pos_emb; pg.patch_np = NP;
         RC(gemm_f32(pg, s));
-        RC(write_cls_rows(L.x, h->vw.class_emb, h->vw.pos_emb, Bc, V_NTOK, V_D, s));
+        RC(write_cls_rows(L.x, h->vw.class_emb, h->vw.pos_emb, Bc, NTOK, V_D, s));
         RC(layernorm_f32(L.x, L.x, h->vw.pre_ln_w, h->vw.pre_ln_b, M, V_D, s));
-        RC(run_encoder(h, L, h->vw.layers, V_LAYERS, Bc, V_NTOK, V_D, V_FF, V_HEADS, 0, nullptr, s));
+        RC(run_encoder(h, L, h->vw.layers, V_LAYERS, Bc, NTOK, V_D, V_FF, V_HEADS, 0, nullptr, s));
         float* feats = L.xn;
-        RC(merge_cls_ln(L.x, feats, h->vw.post_ln_w, h->vw.post_ln_b, h->vw.det_ln_w, h->vw.det_ln_b, Bc, V_NTOK, V_D, s));
+        RC(merge_cls_ln(L.x, feats, h->vw.post_ln_w, h->vw.post_ln_b, h->vw.det_ln_w, h->vw.det_ln_b, Bc, NTOK, V_D, s));
         float* cls = L.att;      // [MP, 512]
         float* bh1 = L.qkv;      // [MP, 768]
         float* bh2 = L.hid;      // [MP, 768]
@@ -611,16 +645,16 @@ int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B,
         a.feats = feats; a.cls = cls; a.boxh = bh2; a.qn = h->qn; a.qmask = h->qmask;
         a.shift_w = h->vw.shift_w; a.shift_b = h->vw.shift_b; a.scale_w = h->vw.scale_w; a.scale_b = h->vw.scale_b;
         a.box2_w = h->vw.box2_w; a.box2_b = h->vw.box2_b; a.box_bias = h->vw.box_bias;
-        a.scores = d_scores + (size_t)b0 * V_NP;
-        a.labels = d_labels + (size_t)b0 * V_NP;
-        a.xyxy = d_boxes_xyxy + (size_t)b0 * V_NP * 4;
-        a.logits = d_logits ? d_logits + (size_t)b0 * V_NP * q_uniform : nullptr;
+        a.scores = d_scores + (size_t)b0 * NP;
+        a.labels = d_labels + (size_t)b0 * NP;
+        a.xyxy = d_boxes_xyxy + (size_t)b0 * NP * 4;
+        a.logits = d_logits ? d_logits + (size_t)b0 * NP * q_uniform : nullptr;
         a.image_set = h_image_query_set ? L.d_image_set + b0 : nullptr;
         a.setQ = h->d_setQ;
-        a.cxcywh = d_boxes_cxcywh ? d_boxes_cxcywh + (size_t)b0 * V_NP * 4 : nullptr;
-        a.rows = MP; a.np = V_NP; a.Q = q_uniform; a.img_w = W; a.img_h = H;
+        a.cxcywh = d_boxes_cxcywh ? d_boxes_cxcywh + (size_t)b0 * NP * 4 : nullptr;
+        a.rows = MP; a.np = NP; a.Q = q_uniform; a.img_w = W; a.img_h = H;
         RC(detect_rows(a, s));
-        RC(cell_reduce(a.scores, a.labels, a.xyxy, h->qweight, a.image_set, Bc, V_NP, W, H, grid_rows, grid_cols, 0.005f,
+        RC(cell_reduce(a.scores, a.labels, a.xyxy, h->qweight, a.image_set, Bc, NP, W, H, grid_rows, grid_cols, 0.005f,
                        d_cell_conf + (size_t)b0 * ncell, d_cell_mask + (size_t)b0 * ncell,
                        d_n_kept ? d_n_kept + b0 : nullptr, s));
     }
@@ -776,6 +810,12 @@ int tstar_attention_f32(const float* d_qkv, float* d_out, int B, int T, int head
 int tstar_draw_boxes(uint8_t* d_images, int B, int H, int W, const float* d_boxes_xyxy, const float* d_scores, void* stream) {
     TSTAR_REQUIRE(d_images && d_boxes_xyxy && d_scores, "tstar_draw_boxes: null argument");
     return draw_boxes(d_images, B, H, W, d_boxes_xyxy, d_scores, V_NP, 0.005f, (hipStream_t)stream);
+}
+
+int tstar_draw_boxes_np(uint8_t* d_images, int B, int H, int W, const float* d_boxes_xyxy, const float* d_scores, int np, void* stream) {
+    TSTAR_REQUIRE(d_images && d_boxes_xyxy && d_scores, "tstar_draw_boxes_np: null argument");
+    TSTAR_REQUIRE(np >= 1, "tstar_draw_boxes_np: np must be positive");
+    return draw_boxes(d_images, B, H, W, d_boxes_xyxy, d_scores, np, 0.005f, (hipStream_t)stream);
 }
 
 int tstar_attention_x3(const float* d_qkv, float* d_out, int B, int T, int heads, void* stream) {

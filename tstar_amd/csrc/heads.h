@@ -45,9 +45,9 @@ void free_table(ResampleTable* t);
 
 // u8 [B,H,W,3] -> u8 [B,H,OW,3]   (Pillow 8bpc horizontal pass)
 int resample_h_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const ResampleTable& t, hipStream_t s);
-// u8 [B,H,768,3] -> vertical pass -> LUT normalise -> im2col f32 [B*576, 3072]
+// u8 [B,H,768,3] -> vertical pass -> LUT normalise -> im2col f32 [B*np, 3*patch^2] (patch 32: [B*576, 3072]; 16: [B*2304, 768])
 int resample_v_normalize_patchify(const uint8_t* in, float* out, uint8_t* out_u8, int B, int H, const ResampleTable& t,
-                                  const float* lut, hipStream_t s);
+                                  const float* lut, int patch, hipStream_t s);
 
 // OpenCV-style fixed-point bilinear resize (11-bit coefficients), gather by frame index.
 // mode 0: frames[idx[i]] (H,W) -> out[i] (oh,ow)

@@ -1,4 +1,4 @@
-// Device-side view of the OWL-ViT-B/32 parameter blobs.  Entry order mirrors
+// Device-side view of the OWL-ViT parameter blobs (B/32 and B/16).  Entry order mirrors
 // tstar_amd/weights.py vision_spec()/text_spec() one to one; the host blob is packed,
 // the device copy pads every entry to 64 floats so all rows stay 16-byte aligned.
 #pragma once
@@ -6,8 +6,21 @@
 
 namespace tstar {
 
+// B/32 numbers (the default geometry); a handle's own geometry is an OwlGeom
 constexpr int V_D = 768, V_FF = 3072, V_LAYERS = 12, V_HEADS = 12, V_NP = 576, V_NTOK = 577, V_PATCH_K = 3072;
 constexpr int T_D = 512, T_FF = 2048, T_LAYERS = 12, T_HEADS = 8, T_LEN = 16, T_VOCAB = 49408, PROJ = 512;
+
+// Patch geometry of the vision tower: every supported checkpoint shares the widths above and differs only here.
+struct OwlGeom {
+    int image = 768, patch = 32, grid = 24, np = V_NP, ntok = V_NTOK, patch_k = V_PATCH_K;
+};
+// the geometry of (image_size, patch_size), or false when it is not supported (B/32 and B/16: image 768, patch 32 / 16)
+inline bool owl_geom(int image_size, int patch_size, OwlGeom* g) {
+    if (image_size != 768 || (patch_size != 32 && patch_size != 16)) return false;
+    g->image = image_size; g->patch = patch_size; g->grid = image_size / patch_size;
+    g->np = g->grid * g->grid; g->ntok = g->np + 1; g->patch_k = 3 * patch_size * patch_size;
+    return true;
+}
 
 struct LayerW {
     const float *ln1_w, *ln1_b, *qkv_w, *qkv_b, *out_w, *out_b, *ln2_w, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
@@ -39,10 +52,10 @@ void map_layer(LayerW& l, int d, int ff, Take&& take) {
 }
 
 template <class Take>
-void map_vision(VisionW& w, Take&& take) {
-    w.patch_w = take((size_t)V_D * V_PATCH_K);
+void map_vision(VisionW& w, const OwlGeom& g, Take&& take) {
+    w.patch_w = take((size_t)V_D * g.patch_k);
     w.class_emb = take(V_D);
-    w.pos_emb = take((size_t)V_NTOK * V_D);
+    w.pos_emb = take((size_t)g.ntok * V_D);
     w.pre_ln_w = take(V_D); w.pre_ln_b = take(V_D);
     for (int i = 0; i < V_LAYERS; ++i) map_layer(w.layers[i], V_D, V_FF, take);
     w.post_ln_w = take(V_D); w.post_ln_b = take(V_D);
@@ -53,7 +66,7 @@ void map_vision(VisionW& w, Take&& take) {
     w.box0_w = take((size_t)V_D * V_D); w.box0_b = take(V_D);
     w.box1_w = take((size_t)V_D * V_D); w.box1_b = take(V_D);
     w.box2_w = take((size_t)4 * V_D); w.box2_b = take(4);
-    w.box_bias = take((size_t)V_NP * 4);
+    w.box_bias = take((size_t)g.np * 4);
 }
 
 template <class Take>

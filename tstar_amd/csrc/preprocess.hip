@@ -133,16 +133,21 @@ int resample_h_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const Re
 }
 
 // in u8 [B,H,768,3]; vertical pass to 768 rows; LUT normalise; write the patch-embed
-// A operand: row = b*576 + (y/32)*24 + x/32, col = c*1024 + (y%32)*32 + x%32.
+// A operand for patch size P (grid G = 768 / P, np = G^2 patches per image, K = 3 P^2):
+// row = b*np + (y/P)*G + x/P, col = c*P^2 + (y%P)*P + x%P  (P = 32: b*576 + (y/32)*24 + x/32, c*1024 + (y%32)*32 + x%32).
 // One thread per (b, y, x); x fastest -> 32 consecutive threads write 128 contiguous bytes per channel.
 // Round 6: FOUR consecutive x per thread (12 source bytes = three dwords per tap and row instead of twelve byte loads, the products on the
-// full-rate v_mad_i32_i24 -- |k| <= 2^22, pixels <= 255: the same 32-bit values --, one float4 store per channel: 4 | 32, so the four stay in
-// one patch row), the normalisation LUT in LDS.  Same integers, same LUT entries: bit-exact (tests/test_gpu_detector.py::test_preprocess_*).
+// full-rate v_mad_i32_i24 -- |k| <= 2^22, pixels <= 255: the same 32-bit values --, one float4 store per channel: 4 | P, so the four stay in
+// one patch row, 16-byte aligned), the normalisation LUT in LDS.  Same integers, same LUT entries: bit-exact
+// (tests/test_gpu_detector.py::test_preprocess_*; P = 16: tests/test_gpu_owl_b16.py).
+template <int P>
 __global__ __launch_bounds__(256) void resample_v_patchify_kernel(const uint8_t* __restrict__ in, float* __restrict__ out,
                                                                   uint8_t* __restrict__ out_u8, int H, int ksize,
                                                                   const int* __restrict__ bounds,
                                                                   const int* __restrict__ coefs,
                                                                   const float* __restrict__ lut, size_t total4) {
+    static_assert(P == 32 || P == 16, "patch sizes 32 and 16");
+    constexpr int SH = P == 32 ? 5 : 4, G = 768 / P, NP = G * G, PP = P * P, K = 3 * PP;
     __shared__ float slut[768];
     for (int i = threadIdx.x; i < 768; i += 256) slut[i] = lut[i];
     __syncthreads();
@@ -177,23 +182,27 @@ __global__ __launch_bounds__(256) void resample_v_patchify_kernel(const uint8_t*
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[j][c] = clip8(s[j][c]);
     if (out_u8) store_px4_bytes(out_u8 + ((b * 768 + y) * 768 + x) * 3, v);
-    const size_t row = b * 576 + (size_t)(y >> 5) * 24 + (x >> 5);
-    float* o = out + row * 3072 + (y & 31) * 32 + (x & 31);
+    const size_t row = b * NP + (size_t)(y >> SH) * G + (x >> SH);
+    float* o = out + row * K + (y & (P - 1)) * P + (x & (P - 1));
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         f32x4 q;
 #pragma unroll
         for (int j = 0; j < 4; ++j) q[j] = slut[c * 256 + v[j][c]];
-        *reinterpret_cast<f32x4*>(o + c * 1024) = q;
+        *reinterpret_cast<f32x4*>(o + c * PP) = q;
     }
 }
 
 int resample_v_normalize_patchify(const uint8_t* in, float* out, uint8_t* out_u8, int B, int H, const ResampleTable& t,
-                                  const float* lut, hipStream_t s) {
+                                  const float* lut, int patch, hipStream_t s) {
     TSTAR_REQUIRE(t.in_size == H && t.out_size == 768, "resample_v: table must map H -> 768");
+    TSTAR_REQUIRE(patch == 32 || patch == 16, "resample_v: patch size must be 32 or 16");
     const size_t total4 = (size_t)B * 768 * 192;                        // four consecutive x per thread
-    hipLaunchKernelGGL(resample_v_patchify_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, in, out,
-                       out_u8, H, t.ksize, t.d_bounds, t.d_coefs, lut, total4);
+    const dim3 grid((unsigned)((total4 + 255) / 256));
+    if (patch == 32)
+        hipLaunchKernelGGL(resample_v_patchify_kernel<32>, grid, dim3(256), 0, s, in, out, out_u8, H, t.ksize, t.d_bounds, t.d_coefs, lut, total4);
+    else
+        hipLaunchKernelGGL(resample_v_patchify_kernel<16>, grid, dim3(256), 0, s, in, out, out_u8, H, t.ksize, t.d_bounds, t.d_coefs, lut, total4);
     TSTAR_HIP_CHECK(hipGetLastError());
     return TSTAR_OK;
 }

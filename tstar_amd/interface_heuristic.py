@@ -70,8 +70,17 @@ class HeuristicInterface:
 class OWLInterface(HeuristicInterface):
     def __init__(self, model_name_or_path: str = "google/owlvit-base-patch32", device: str = "cuda",
                  max_batch: Optional[int] = None, synthetic_seed: Optional[int] = None, state_dict: Optional[Dict] = None,
-                 weights_dtype: Optional[str] = None, allow_standin_tokenizer: Optional[bool] = None):
+                 weights_dtype: Optional[str] = None, allow_standin_tokenizer: Optional[bool] = None,
+                 patch_size: Optional[int] = None):
         """``device`` must be a HIP device (default "cuda" as in the reference, :201).
+
+        Supported checkpoints: OWL-ViT B/32 (``google/owlvit-base-patch32``, the default) and B/16
+        (``google/owlvit-base-patch16``).  The geometry comes from the checkpoint (its config.json, cross-checked against the
+        tensor shapes; ``weights.geometry_of_checkpoint``) or from the shapes of a given ``state_dict``; any other geometry
+        (L/14, OWLv2, ...) raises ValueError before anything is allocated on the device.  ``patch_size`` (32 or 16) chooses
+        the geometry of SYNTHETIC weights (default 32); given together with real weights it must agree with them.  The
+        geometry is kept as ``self.geometry`` (``weights.OwlGeometry``); ``inference_detector`` returns
+        ``self.geometry.npatch`` detections (patch order) when every patch passes the threshold.
 
         Under an UNCHANGED ``TStarFramework`` the heuristic is built by ``initialize_heuristic(heuristic_type)`` without keyword
         arguments (TStarFramework.py:171-187, 207), so the three arguments a deployment chooses can also come from the environment
@@ -108,20 +117,29 @@ class OWLInterface(HeuristicInterface):
         dev = torch.device(device)
         if dev.index is not None:
             torch.cuda.set_device(dev.index)
+        if patch_size is not None:
+            W.geometry_for_patch(int(patch_size))                  # an unsupported value fails here, whatever the weights
         if state_dict is None:
             ckpt = W.find_pretrained(model_name_or_path)
             if ckpt is not None:
+                geometry = W.geometry_of_checkpoint(ckpt)          # before the weights are read or anything is allocated
                 state_dict = W.load_safetensors_state_dict(ckpt)
                 self.weights_source = ckpt
             elif synthetic_seed is not None:
-                state_dict = W.synthetic_state_dict(int(synthetic_seed))
+                geometry = W.geometry_for_patch(32 if patch_size is None else int(patch_size))
+                state_dict = W.synthetic_state_dict(int(synthetic_seed), geometry=geometry)
                 self.weights_source = f"synthetic(seed={int(synthetic_seed)})"
             else:
                 raise FileNotFoundError(
                     f"no local checkpoint for {model_name_or_path!r} (offline); pass synthetic_seed=<int> "
-                    "for seeded synthetic OWL-ViT-B/32 weights or state_dict=<HF state dict>")
+                    "for seeded synthetic OWL-ViT weights (B/32, or B/16 with patch_size=16) or state_dict=<HF state dict>")
         else:
+            geometry = W.geometry_of_state_dict(state_dict)
             self.weights_source = "state_dict"
+        if patch_size is not None and int(patch_size) != geometry.patch_size:
+            raise ValueError(f"patch_size={int(patch_size)} disagrees with the weights of {self.weights_source!r}, which are "
+                             f"{geometry.name} (patch {geometry.patch_size})")
+        self.geometry = geometry
         if allow_standin_tokenizer is None:
             allow_standin_tokenizer = self.weights_source.startswith("synthetic(")
         self.allow_standin_tokenizer = bool(allow_standin_tokenizer)
@@ -129,8 +147,8 @@ class OWLInterface(HeuristicInterface):
             state_dict = W.round_weights_to_bf16(state_dict)
         self.weights_dtype = weights_dtype
         self.model_name_or_path = model_name_or_path
-        self.scorer = OwlScorer(W.pack_blob(state_dict, W.vision_spec()), W.pack_blob(state_dict, W.text_spec()),
-                                max_batch=max_batch, weights_mode=weights_dtype)
+        self.scorer = OwlScorer(W.pack_blob(state_dict, W.vision_spec(geometry)), W.pack_blob(state_dict, W.text_spec()),
+                                max_batch=max_batch, weights_mode=weights_dtype, patch_size=geometry.patch_size)
         self.device = device
         self.texts = ["couch", "table", "woman"]      # as the reference leaves it before reparameterisation (:203)
         self.detections_inbatch: List[Detections] = []
@@ -231,8 +249,9 @@ class OWLInterface(HeuristicInterface):
         boxes = r.boxes[start:start + count].contiguous()
         scores = r.scores[start:start + count].contiguous()
         lib = _lib.load()
-        _lib.check(lib.tstar_draw_boxes(d_images.data_ptr(), count, int(d_images.shape[1]), int(d_images.shape[2]),
-                                        boxes.data_ptr(), scores.data_ptr(), _lib.stream_ptr()), "tstar_draw_boxes")
+        _lib.check(lib.tstar_draw_boxes_np(d_images.data_ptr(), count, int(d_images.shape[1]), int(d_images.shape[2]),
+                                           boxes.data_ptr(), scores.data_ptr(), int(boxes.shape[1]), _lib.stream_ptr()),
+                   "tstar_draw_boxes_np")
         imgs = d_images.cpu().numpy()
         s, bx, lab = scores.cpu().numpy(), boxes.cpu().numpy(), r.labels[start:start + count].cpu().numpy()
         dets = []
@@ -465,9 +484,11 @@ def draw_boxes(image: np.ndarray, det: Detections, color=(255, 64, 64)) -> np.nd
 
 
 def initialize_heuristic(heuristic_type: str = "owl-vit", **kwargs) -> HeuristicInterface:
-    """Factory with the reference's signature (TStarFramework.py:171-187)."""
+    """Factory with the reference's signature (TStarFramework.py:171-187).  ``model_name_or_path=`` overrides the OWL-ViT
+    checkpoint (default ``google/owlvit-base-patch32``; B/16 checkpoints are supported too)."""
     if heuristic_type == "owl-vit":
-        return OWLInterface(model_name_or_path="google/owlvit-base-patch32", **kwargs)
+        kwargs.setdefault("model_name_or_path", "google/owlvit-base-patch32")
+        return OWLInterface(**kwargs)
     if heuristic_type == "yolo-World":
         # the paths the reference hard-codes (TStarFramework.py:181-182); the checkpoint is used when it exists
         config_path = "./YOLO-World/configs/pretrain/yolo_world_v2_xl_vlpan_bn_2e-3_100e_4x8gpus_obj365v1_goldg_train_lvis_minival.py"

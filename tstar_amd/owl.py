@@ -37,10 +37,10 @@ def normalize_lut() -> np.ndarray:
 
 @dataclass
 class ScoreResult:
-    """Device tensors produced by one tstar_owl_score call."""
-    scores: "object"       # f32 [B,576]
-    labels: "object"       # i32 [B,576]
-    boxes: "object"        # f32 [B,576,4] xyxy pixels
+    """Device tensors produced by one tstar_owl_score call (np = 576 at B/32, 2304 at B/16)."""
+    scores: "object"       # f32 [B,np]
+    labels: "object"       # i32 [B,np]
+    boxes: "object"        # f32 [B,np,4] xyxy pixels
     cell_conf: "object"    # f64 [B,rows*cols]
     cell_mask: "object"    # i32 view of u32 [B,rows*cols]
     n_kept: "object"       # i32 [B]
@@ -49,15 +49,17 @@ class ScoreResult:
 
 
 class OwlScorer:
-    """One OWL-ViT-B/32 scorer resident on the current HIP device."""
+    """One OWL-ViT scorer (B/32, or B/16 with ``patch_size=16``) resident on the current HIP device."""
 
     WEIGHTS_MODES = {"f32": 0, "bf16": 1, "bf16_exact": 3, "f32x3": 4}      # TSTAR_WEIGHTS_* of include/tstar_hip.h
 
     def __init__(self, vision_blob: Optional[np.ndarray], text_blob: Optional[np.ndarray] = None, max_batch: int = 32,
-                 weights_mode: str = "f32"):
+                 weights_mode: str = "f32", patch_size: int = 32):
         """``vision_blob=None`` gives a text-only handle: ``set_queries`` / ``get_query_embeds`` work (the CLIP text
-        features of the YOLO-World backend), ``score`` raises."""
+        features of the YOLO-World backend), ``score`` raises.  ``patch_size``: 32 (B/32) or 16 (B/16); the vision blob is
+        packed with ``weights.vision_spec`` of that geometry."""
         import torch
+        self.geometry = W.geometry_for_patch(patch_size)           # ValueError before anything touches the device
         if not torch.cuda.is_available():
             raise _lib.TStarHipError("OwlScorer needs a HIP device (torch.cuda.is_available() is False); "
                                      "tstar_amd has no CPU path")
@@ -73,23 +75,26 @@ class OwlScorer:
             text_blob = np.ascontiguousarray(text_blob, dtype=np.float32)
         lut = normalize_lut()
         h = C.c_void_p()
-        rc = self._lib.tstar_owl_create(
-            C.byref(h), None if vision_blob is None else vision_blob.ctypes.data, 0 if vision_blob is None else vision_blob.size,
+        rc = self._lib.tstar_owl_create_ex(
+            C.byref(h), self.geometry.image_size, self.geometry.patch_size,
+            None if vision_blob is None else vision_blob.ctypes.data, 0 if vision_blob is None else vision_blob.size,
             None if text_blob is None else text_blob.ctypes.data, 0 if text_blob is None else text_blob.size,
             lut.ctypes.data, int(max_batch), self.WEIGHTS_MODES[weights_mode])
         _lib.check(rc, "tstar_owl_create")
         self._h = h
+        self.num_patches = int(self._lib.tstar_owl_num_patches(h))   # detections per image: 576 (B/32) or 2304 (B/16)
         self.max_batch = int(max_batch)
         self.Qs = {}                # query-set slot -> number of queries
         self._pending = {}          # slot -> (ids, mask, weights) recorded by set_queries(lazy=True), installed on first use
         self.device = torch.device("cuda", torch.cuda.current_device())
 
     @classmethod
-    def synthetic(cls, seed: int = 0, max_batch: int = 32, with_text: bool = True):
-        sd = W.synthetic_state_dict(seed, "both" if with_text else "vision")
-        vb = W.pack_blob(sd, W.vision_spec())
+    def synthetic(cls, seed: int = 0, max_batch: int = 32, with_text: bool = True, patch_size: int = 32):
+        g = W.geometry_for_patch(patch_size)
+        sd = W.synthetic_state_dict(seed, "both" if with_text else "vision", geometry=g)
+        vb = W.pack_blob(sd, W.vision_spec(g))
         tb = W.pack_blob(sd, W.text_spec()) if with_text else None
-        return cls(vb, tb, max_batch)
+        return cls(vb, tb, max_batch, patch_size=patch_size)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -208,10 +213,11 @@ class OwlScorer:
         B, H, Wd, _ = images.shape
         dev = images.device
         ncell = grid_rows * grid_cols
+        npatch = self.num_patches
         r = ScoreResult(
-            scores=torch.empty((B, W.NPATCH), dtype=torch.float32, device=dev),
-            labels=torch.empty((B, W.NPATCH), dtype=torch.int32, device=dev),
-            boxes=torch.empty((B, W.NPATCH, 4), dtype=torch.float32, device=dev),
+            scores=torch.empty((B, npatch), dtype=torch.float32, device=dev),
+            labels=torch.empty((B, npatch), dtype=torch.int32, device=dev),
+            boxes=torch.empty((B, npatch, 4), dtype=torch.float32, device=dev),
             cell_conf=torch.empty((B, ncell), dtype=torch.float64, device=dev),
             cell_mask=torch.empty((B, ncell), dtype=torch.int32, device=dev),
             n_kept=torch.empty((B,), dtype=torch.int32, device=dev),
@@ -227,8 +233,8 @@ class OwlScorer:
             qs = {self.Qs.get(int(v), 0) for v in (sets if sets is not None else [0])}
             if len(qs) != 1:
                 raise ValueError("score: raw logits need the same query count for every image")
-            r.logits = torch.empty((B, W.NPATCH, qs.pop()), dtype=torch.float32, device=dev)
-            r.boxes_cxcywh = torch.empty((B, W.NPATCH, 4), dtype=torch.float32, device=dev)
+            r.logits = torch.empty((B, npatch, qs.pop()), dtype=torch.float32, device=dev)
+            r.boxes_cxcywh = torch.empty((B, npatch, 4), dtype=torch.float32, device=dev)
         rc = self._lib.tstar_owl_score_lane(
             self._h, int(lane), images.data_ptr(), B, H, Wd, grid_rows, grid_cols,
             None if sets is None else sets.ctypes.data, r.scores.data_ptr(), r.labels.data_ptr(), r.boxes.data_ptr(), r.cell_conf.data_ptr(),
@@ -242,7 +248,7 @@ class OwlScorer:
         images = images.contiguous()
         B, H, Wd, _ = images.shape
         u8 = torch.empty((B, 768, 768, 3), dtype=torch.uint8, device=images.device)
-        pat = torch.empty((B * W.NPATCH, 3 * W.PATCH * W.PATCH), dtype=torch.float32, device=images.device)
+        pat = torch.empty((B * self.num_patches, self.geometry.patch_k), dtype=torch.float32, device=images.device)
         rc = self._lib.tstar_owl_debug_preprocess(self._h, images.data_ptr(), B, H, Wd, u8.data_ptr(),
                                                   pat.data_ptr(), _lib.stream_ptr())
         _lib.check(rc, "tstar_owl_debug_preprocess")

@@ -1,10 +1,10 @@
-"""OWL-ViT-B/32 parameter sets for the HIP scorer.
+"""OWL-ViT-B/32 and B/16 parameter sets for the HIP scorer.
 
-The reference loads ``google/owlvit-base-patch32`` through HF transformers
-(/root/reference/TStar/interface_heuristic.py:207-210, TStarFramework.py:176).
-The HIP library takes ONE flat little-endian float32 blob whose layout is
-fixed by ``vision_spec()`` / ``text_spec()`` below (mirrored entry by entry in
-``tstar_amd/csrc/owl_weights.h``).  This module
+The reference loads ``google/owlvit-base-patch32`` (or whatever checkpoint it is
+given) through HF transformers (/root/reference/TStar/interface_heuristic.py:207-210,
+TStarFramework.py:176).  The HIP library takes ONE flat little-endian float32 blob
+whose layout is fixed by ``vision_spec()`` / ``text_spec()`` below (mirrored entry
+by entry in ``tstar_amd/csrc/owl_weights.h``).  This module
 
 * builds that blob from a HF-style ``state_dict`` (names as in
   ``transformers/models/owlvit/modeling_owlvit.py``), either real weights found
@@ -17,11 +17,18 @@ fixed by ``vision_spec()`` / ``text_spec()`` below (mirrored entry by entry in
   and class-head shift/scale scaled by 0.01 so scores do not saturate
   (SURVEY.md 8c caveat (c)).
 
+Two vision geometries are supported (``OwlGeometry``): B/32 (the default
+everywhere; the module-level constants below are its numbers) and B/16.  They
+share every width; only the patch grid, and with it the token count, the
+patch-embedding matrix, the position table and ``box_bias``, differ.
+
 No torch import at module import time; numpy only.
 """
 from __future__ import annotations
 
+import json
 import os
+from dataclasses import dataclass
 from typing import Dict, List, Tuple
 
 import numpy as np
@@ -48,6 +55,49 @@ LN_EPS = 1e-5
 Spec = List[Tuple[str, Tuple[int, ...], Tuple[str, ...]]]
 
 
+@dataclass(frozen=True)
+class OwlGeometry:
+    """Patch geometry of an OWL-ViT vision tower.  Every supported checkpoint shares the widths above (vision 768 / 3072,
+    12 layers, 12 heads; the same text tower; projection 512): only the patch grid differs."""
+    image_size: int
+    patch_size: int
+
+    @property
+    def grid(self) -> int:
+        return self.image_size // self.patch_size
+
+    @property
+    def npatch(self) -> int:
+        return self.grid * self.grid
+
+    @property
+    def ntok(self) -> int:
+        return self.npatch + 1
+
+    @property
+    def patch_k(self) -> int:
+        return 3 * self.patch_size * self.patch_size
+
+    @property
+    def name(self) -> str:
+        return f"B/{self.patch_size}"
+
+
+B32 = OwlGeometry(768, 32)     # google/owlvit-base-patch32: grid 24, 576 patches, T = 577 (the default everywhere)
+B16 = OwlGeometry(768, 16)     # google/owlvit-base-patch16: grid 48, 2304 patches, T = 2305
+SUPPORTED = (B32, B16)
+SUPPORTED_TEXT = ("OWL-ViT B/32 and B/16 (image 768, patch 32 or 16; vision 768 wide, MLP 3072, 12 layers, 12 heads; "
+                  "text 512 wide, MLP 2048, 12 layers, 8 heads; projection 512)")
+
+
+def geometry_for_patch(patch_size: int) -> OwlGeometry:
+    """The supported geometry with this patch size (image 768); ValueError otherwise."""
+    for g in SUPPORTED:
+        if g.patch_size == patch_size:
+            return g
+    raise ValueError(f"patch_size {patch_size!r} is not supported; supported: {SUPPORTED_TEXT}")
+
+
 def _layer_spec(prefix: str, d: int, ff: int) -> Spec:
     p = prefix
     return [
@@ -66,13 +116,14 @@ def _layer_spec(prefix: str, d: int, ff: int) -> Spec:
     ]
 
 
-def vision_spec() -> Spec:
+def vision_spec(geometry: OwlGeometry = B32) -> Spec:
     """(blob entry name, shape, HF state_dict names concatenated along dim 0)."""
+    g = geometry
     vm = "owlvit.vision_model."
     s: Spec = [
-        ("patch_w", (V_D, 3 * PATCH * PATCH), (vm + "embeddings.patch_embedding.weight",)),
+        ("patch_w", (V_D, g.patch_k), (vm + "embeddings.patch_embedding.weight",)),
         ("class_emb", (V_D,), (vm + "embeddings.class_embedding",)),
-        ("pos_emb", (NTOK, V_D), (vm + "embeddings.position_embedding.weight",)),
+        ("pos_emb", (g.ntok, V_D), (vm + "embeddings.position_embedding.weight",)),
         ("pre_ln_w", (V_D,), (vm + "pre_layernorm.weight",)),
         ("pre_ln_b", (V_D,), (vm + "pre_layernorm.bias",)),
     ]
@@ -95,7 +146,7 @@ def vision_spec() -> Spec:
         ("box1_b", (V_D,), ("box_head.dense1.bias",)),
         ("box2_w", (4, V_D), ("box_head.dense2.weight",)),
         ("box2_b", (4,), ("box_head.dense2.bias",)),
-        ("box_bias", (NPATCH, 4), ("box_bias",)),
+        ("box_bias", (g.npatch, 4), ("box_bias",)),
     ]
     return s
 
@@ -120,25 +171,26 @@ def spec_size(spec: Spec) -> int:
     return int(sum(int(np.prod(shape)) for _, shape, _ in spec))
 
 
-def compute_box_bias() -> np.ndarray:
-    """box_bias buffer, restated from modeling_owlvit.py:1072-1104.
+def compute_box_bias(geometry: OwlGeometry = B32) -> np.ndarray:
+    """box_bias buffer, restated from modeling_owlvit.py:1072-1104 (``compute_box_bias(G, G)``).
 
-    xy = ((col+1)/24, (row+1)/24); bias = log(v+1e-4) - log1p(-v+1e-4); size
-    entries use v = 1/24.  Row-major over the 24x24 patch grid.  Uses torch
-    float32 ops (as HF does) so the buffer is bit-identical to the one HF
-    builds at model init; torch is imported lazily.
+    xy = ((col+1)/G, (row+1)/G); bias = log(v+1e-4) - log1p(-v+1e-4); size
+    entries use v = 1/G, G = the patch grid (24 at B/32, 48 at B/16).  Row-major
+    over the G x G patch grid.  Uses torch float32 ops (as HF does) so the buffer
+    is bit-identical to the one HF builds at model init; torch is imported lazily.
     """
     import torch
-    xs = torch.arange(1, GRID + 1, dtype=torch.float32)
+    G = geometry.grid
+    xs = torch.arange(1, G + 1, dtype=torch.float32)
     xx, yy = torch.meshgrid(xs, xs, indexing="xy")
     coords = torch.stack((xx, yy), dim=-1)
-    coords[..., 0] /= GRID
-    coords[..., 1] /= GRID
+    coords[..., 0] /= G
+    coords[..., 1] /= G
     coords = torch.clip(coords.view(-1, 2), 0.0, 1.0)
     cb = torch.log(coords + 1e-4) - torch.log1p(-coords + 1e-4)
     size = torch.full_like(cb, 1.0)
-    size[..., 0] /= GRID
-    size[..., 1] /= GRID
+    size[..., 0] /= G
+    size[..., 1] /= G
     sb = torch.log(size + 1e-4) - torch.log1p(-size + 1e-4)
     return torch.cat([cb, sb], dim=-1).numpy().astype(np.float32)
 
@@ -167,8 +219,8 @@ def _std_for(name: str, shape: Tuple[int, ...]) -> float:
     return 0.02
 
 
-def synthetic_state_dict(seed: int = 0, towers: str = "both") -> Dict[str, np.ndarray]:
-    """Seeded synthetic OWL-ViT-B/32 parameters keyed by HF state_dict names.
+def synthetic_state_dict(seed: int = 0, towers: str = "both", geometry: OwlGeometry = B32) -> Dict[str, np.ndarray]:
+    """Seeded synthetic OWL-ViT parameters (B/32 unless ``geometry`` says otherwise) keyed by HF state_dict names.
 
     Drawn from ONE ``RandomState(seed)`` stream in spec order (vision first),
     so the text tower does not depend on whether the vision tower was built:
@@ -179,10 +231,10 @@ def synthetic_state_dict(seed: int = 0, towers: str = "both") -> Dict[str, np.nd
     def fill(spec: Spec, rs: np.random.RandomState) -> None:
         for _, _, hf_names in spec:
             for hf in hf_names:
-                shape = _hf_shape(hf)
+                shape = _hf_shape(hf, geometry)
                 n = int(np.prod(shape))
                 if hf == "box_bias":
-                    out[hf] = compute_box_bias()
+                    out[hf] = compute_box_bias(geometry)
                     continue
                 # unit-variance uniform: (u - 0.5) * sqrt(12); the legacy
                 # random_sample stream is frozen and ~30x faster than gauss
@@ -198,30 +250,32 @@ def synthetic_state_dict(seed: int = 0, towers: str = "both") -> Dict[str, np.nd
                 out[hf] = x
 
     if towers in ("both", "vision"):
-        fill(vision_spec(), np.random.RandomState(seed))
+        fill(vision_spec(geometry), np.random.RandomState(seed))
     if towers in ("both", "text"):
         fill(text_spec(), np.random.RandomState(seed + 1))
     return out
 
 
-_HF_SHAPES: Dict[str, Tuple[int, ...]] = {}
+_HF_SHAPES: Dict[OwlGeometry, Dict[str, Tuple[int, ...]]] = {}
 
 
-def _hf_shape(hf: str) -> Tuple[int, ...]:
-    if not _HF_SHAPES:
-        for spec in (vision_spec(), text_spec()):
+def _hf_shape(hf: str, geometry: OwlGeometry = B32) -> Tuple[int, ...]:
+    shapes = _HF_SHAPES.get(geometry)
+    if shapes is None:
+        shapes = _HF_SHAPES[geometry] = {}
+        for spec in (vision_spec(geometry), text_spec()):
             for _, shape, hf_names in spec:
                 k = len(hf_names)
                 for h in hf_names:
                     if h.endswith("patch_embedding.weight"):
-                        _HF_SHAPES[h] = (V_D, 3, PATCH, PATCH)
+                        shapes[h] = (V_D, 3, geometry.patch_size, geometry.patch_size)
                     elif h.startswith("class_head.logit_s") and h.endswith("weight"):
-                        _HF_SHAPES[h] = (1, V_D)
+                        shapes[h] = (1, V_D)
                     elif k > 1:
-                        _HF_SHAPES[h] = (shape[0] // k,) + tuple(shape[1:])
+                        shapes[h] = (shape[0] // k,) + tuple(shape[1:])
                     else:
-                        _HF_SHAPES[h] = tuple(shape)
-    return _HF_SHAPES[hf]
+                        shapes[h] = tuple(shape)
+    return shapes[hf]
 
 
 def to_bf16_values(a: np.ndarray) -> np.ndarray:
@@ -242,11 +296,15 @@ def round_weights_to_bf16(sd: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
 
 
 def pack_blob(sd: Dict[str, np.ndarray], spec: Spec) -> np.ndarray:
-    """Concatenate ``sd`` entries into the flat f32 blob the C ABI expects."""
+    """Concatenate ``sd`` entries into the flat f32 blob the C ABI expects.  ``box_bias`` is a non-persistent buffer in
+    transformers 5.x (not in the state dict): when it is missing it is computed for the spec's patch grid."""
     parts = []
     for name, shape, hf_names in spec:
         if name == "box_bias" and "box_bias" not in sd:
-            arr = compute_box_bias()
+            g = next((g for g in SUPPORTED if g.npatch == shape[0]), None)
+            if g is None:
+                raise ValueError(f"weight box_bias: no supported geometry has {shape[0]} patches")
+            arr = compute_box_bias(g)
         else:
             arr = np.concatenate([np.asarray(sd[h], dtype=np.float32).reshape(-1) for h in hf_names])
         if arr.size != int(np.prod(shape)):
@@ -291,3 +349,77 @@ def load_safetensors_state_dict(path: str) -> Dict[str, np.ndarray]:
     from safetensors.numpy import load_file
     sd = load_file(path)
     return {k: np.asarray(v, dtype=np.float32) for k, v in sd.items()}
+
+
+# ---- checkpoint geometry ----------------------------------------------------------------------------------------------
+# configuration_owlvit.py defaults: a key that a config.json leaves out holds these values
+_VISION_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, image_size=768,
+                        patch_size=32)
+_TEXT_DEFAULTS = dict(hidden_size=512, intermediate_size=2048, num_hidden_layers=12, num_attention_heads=8)
+_VISION_FIXED = dict(hidden_size=V_D, intermediate_size=V_FF, num_hidden_layers=V_LAYERS, num_attention_heads=V_HEADS)
+_TEXT_FIXED = dict(hidden_size=T_D, intermediate_size=T_FF, num_hidden_layers=T_LAYERS, num_attention_heads=T_HEADS)
+_PATCH_KEY = "owlvit.vision_model.embeddings.patch_embedding.weight"
+_POS_KEY = "owlvit.vision_model.embeddings.position_embedding.weight"
+
+
+def geometry_of_config(cfg: dict) -> OwlGeometry:
+    """The geometry an OWL-ViT ``config.json`` (as a dict) describes; ValueError (naming what was found and what is
+    supported) for anything but B/32 and B/16."""
+    mt = cfg.get("model_type", "owlvit")
+    if mt != "owlvit":
+        raise ValueError(f"config model_type {mt!r} is not supported (OWLv2 and other families are out of scope); "
+                         f"supported: {SUPPORTED_TEXT}")
+    vc = dict(_VISION_DEFAULTS, **{k: v for k, v in (cfg.get("vision_config") or {}).items() if k in _VISION_DEFAULTS})
+    tc = dict(_TEXT_DEFAULTS, **{k: v for k, v in (cfg.get("text_config") or {}).items() if k in _TEXT_DEFAULTS})
+    proj = cfg.get("projection_dim", PROJ)
+    found = (f"vision hidden {vc['hidden_size']}, MLP {vc['intermediate_size']}, {vc['num_hidden_layers']} layers, "
+             f"{vc['num_attention_heads']} heads, image {vc['image_size']}, patch {vc['patch_size']}; text hidden {tc['hidden_size']}, "
+             f"MLP {tc['intermediate_size']}, {tc['num_hidden_layers']} layers, {tc['num_attention_heads']} heads; projection {proj}")
+    ok = all(vc[k] == v for k, v in _VISION_FIXED.items()) and all(tc[k] == v for k, v in _TEXT_FIXED.items()) and proj == PROJ
+    g = OwlGeometry(int(vc["image_size"]), int(vc["patch_size"]))
+    if not ok or g not in SUPPORTED:
+        raise ValueError(f"unsupported OWL-ViT geometry ({found}); supported: {SUPPORTED_TEXT}")
+    return g
+
+
+def geometry_of_state_dict(shapes) -> OwlGeometry:
+    """The geometry the vision tensors' shapes imply: ``patch_embedding`` [768, 3, P, P] and ``position_embedding``
+    [(768 / P)^2 + 1, 768].  ``shapes``: HF name -> shape or array (a state dict works)."""
+    shapes = {k: tuple(getattr(v, "shape", v)) for k, v in shapes.items() if k in (_PATCH_KEY, _POS_KEY)}
+    pe, pos = shapes.get(_PATCH_KEY), shapes.get(_POS_KEY)
+    if pe is None or pos is None:
+        raise ValueError(f"no {_PATCH_KEY} / {_POS_KEY}: not an OWL-ViT detector state dict")
+    if len(pe) != 4 or pe[0] != V_D or pe[1] != 3 or pe[2] != pe[3]:
+        raise ValueError(f"patch_embedding has shape {list(pe)}; supported: {SUPPORTED_TEXT}")
+    for g in SUPPORTED:
+        if g.patch_size == pe[2]:
+            if pos != (g.ntok, V_D):
+                raise ValueError(f"position_embedding has shape {list(pos)}; patch {pe[2]} wants [{g.ntok}, {V_D}]")
+            return g
+    raise ValueError(f"patch_embedding has shape {list(pe)} (patch {pe[2]}); supported: {SUPPORTED_TEXT}")
+
+
+def geometry_of_checkpoint(path: str) -> OwlGeometry:
+    """Geometry of a local checkpoint (a directory or its ``model.safetensors``): ``config.json`` next to the weights
+    (``vision_config`` / ``text_config`` / ``projection_dim``) cross-checked against the tensor shapes, which are read from
+    the safetensors header alone.  A disagreement or an unsupported geometry raises ValueError; without a config.json the
+    shapes decide."""
+    st = os.path.join(path, "model.safetensors") if os.path.isdir(path) else path
+    cfg_path = os.path.join(os.path.dirname(st), "config.json")
+    g_cfg = None
+    if os.path.isfile(cfg_path):
+        with open(cfg_path) as f:
+            g_cfg = geometry_of_config(json.load(f))
+    if not os.path.isfile(st):
+        if g_cfg is None:
+            raise ValueError(f"{path!r} holds neither model.safetensors nor config.json")
+        return g_cfg
+    from safetensors import safe_open
+    with safe_open(st, framework="numpy") as f:
+        keys = set(f.keys())
+        shapes = {k: tuple(f.get_slice(k).get_shape()) for k in (_PATCH_KEY, _POS_KEY) if k in keys}
+    g_w = geometry_of_state_dict(shapes)
+    if g_cfg is not None and g_cfg != g_w:
+        raise ValueError(f"config.json says {g_cfg.name} (image {g_cfg.image_size}, patch {g_cfg.patch_size}) but the weights are "
+                         f"{g_w.name}: patch_embedding {list(shapes[_PATCH_KEY])}, position_embedding {list(shapes[_POS_KEY])}")
+    return g_w
