@@ -348,6 +348,13 @@ int tstar_gemm_f32x3(const float* d_A, const float* d_W, float* d_C, const float
 int tstar_pack_f32x3(const float* d_W, void* d_Wp, int N, int K, void* stream);
 int tstar_gemm_f32x3_pre(const float* d_A, const void* d_Wp, float* d_C, const float* d_bias, const float* d_residual,
                          int M, int N, int K, int act, int tile_cfg, void* stream);
+/* The tile plan the GEMM launcher makes for a problem (an added entry; tstar_abi_version() stays 3).  Pure integer arithmetic: needs no
+ * GPU and launches nothing.  weights_mode: a TSTAR_WEIGHTS_* value; ldc and patch_np (0 = none) as the launch passes them (the patch
+ * embedding writes token rows: ldc = N, patch_np = patches per image); tile_cfg as above; has_packed_w2: the two-term mode's
+ * fragment-packed weight plane exists.  plan4 = { kind, m_split, blocks, dynamic LDS bytes per block }; kind 0 / 1 / 2 = a pure grid of
+ * 128x128 / 64x128 / 64x64 tiles, 3 = hybrid (rows [0, m_split) in 128x128 tiles, the rest 64x128), 4 = wide (128x256 + 64x128 tail),
+ * 5 = wide with the weights streamed global -> VGPR.  TSTAR_ERR_ARG where tstar_gemm_* would refuse the same arguments. */
+int tstar_gemm_plan(int weights_mode, int M, int N, int ldc, int patch_np, int tile_cfg, int has_packed_w2, int* plan4);
 int tstar_layernorm_f32(const float* d_x, float* d_y, const float* d_w, const float* d_b, int rows, int D, void* stream);
 /* qkv [B*T, 3*heads*64] -> out [B*T, heads*64]; mode 0 full, 1 causal + key mask u8 [B,T] */
 int tstar_attention_f32(const float* d_qkv, float* d_out, int B, int T, int heads, int mode,

@@ -29,6 +29,38 @@ def test_blob_layout_matches_library():
     assert lib.tstar_owl_text_blob_floats() == W.spec_size(W.text_spec())
 
 
+def test_gemm_plan_matches_recorded_table(golden_dir):
+    """The GEMM tile policy (plan_gemm through tstar_gemm_plan: pure integers, no GPU) against plans recorded from the launcher
+    that preceded it: which tile, m_split, block count and dynamic LDS, row by row.  A threshold moved by one fails here
+    (tried on every threshold of pick_cfg and of the wide rule, each way: e.g. pick_cfg's 200 -> 201 fails 10 rows, the f32x3
+    rule's 400 -> 399 fails 2)."""
+    import ctypes as C
+    from tstar_amd import _lib
+    lib = _lib.load()
+    weights_mode = {"f32": 0, "bf16_2t": 1, "bf16_exact": 3, "f32x3": 4}          # TSTAR_WEIGHTS_*
+    out = (C.c_int * 4)()
+    rows, pairs = 0, set()
+    for line in open(os.path.join(golden_dir, "gemm_plan_table.txt")):
+        if line.startswith("#"):
+            continue
+        f = line.split()
+        mode, (wq, M, N, ldc, np_, cfg, kind, m_split, blocks, lds) = f[0], map(int, f[1:])
+        rc = lib.tstar_gemm_plan(weights_mode[mode], M, N, ldc, np_, cfg, wq, out)
+        got = (-1, 0, 0, 0) if rc else tuple(out)
+        assert rc in (0, 1) and got == (kind, m_split, blocks, lds), (line, rc, got)
+        rows += 1
+        pairs.add((mode, kind))
+    assert rows >= 3000
+    # refusals (tile_cfg 6), the three grids and the hybrid launch in every mode; wide in two modes, VGPR-streamed weights in one
+    kinds = {"f32": range(-1, 4), "bf16_exact": range(-1, 4), "f32x3": range(-1, 5), "bf16_2t": range(-1, 6)}
+    assert pairs == {(m, k) for m, ks in kinds.items() for k in ks}
+    # outside the named tile_cfg values: refused, as gemm_f32() refuses them
+    for cfg in (-2, 7, 15):
+        assert lib.tstar_gemm_plan(4, 9232, 768, 768, 0, cfg, 0, out) == 1
+    assert lib.tstar_gemm_plan(2, 9232, 768, 768, 0, -1, 0, out) == 1             # the retired weights mode
+    assert lib.tstar_gemm_plan(0, 9232, 192, 192, 0, -1, 0, out) == 1             # N % 128
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():

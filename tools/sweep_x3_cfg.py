@@ -1,5 +1,5 @@
 """The f32x3 GEMM tile (gemm_tile_x3, round 5) on the shapes of a forward at batch B: every pure tile shape, the hybrid launches and
-the wide (128x256) launch against the launcher's automatic choice.  Data behind launch_mode<4>'s policy (csrc/gemm_f32.hip).
+the wide (128x256) launch against the launcher's automatic choice.  Data behind plan_gemm's f32x3 rule (csrc/gemm_f32.hip).
     python tools/sweep_x3_cfg.py [B ...]"""
 import os
 import sys

@@ -194,7 +194,7 @@ static GemmArgs mk_gemm(const tstar_owl* h, const float* A, const float* W, floa
                         int M, int N, int K, int lda, int ldc, int act) {
     GemmArgs g{};
     g.A = A; g.W = W; g.Wb = h ? h->bf16_of(W) : nullptr; g.Wp = h ? h->packed_of(W) : nullptr; g.Wq = h ? h->w2_of(W) : nullptr; g.C = C; g.bias = bias; g.res = res; g.pos = nullptr;
-    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.act = act; g.patch_np = 0; g.tile_cfg = -1; g.m_split = 0;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.act = act; g.patch_np = 0; g.tile_cfg = TILE_AUTO; g.m_split = 0;
     g.a_terms = h && h->weights_mode == TSTAR_WEIGHTS_BF16 ? 2 : 0;      // bf16 weights: two-term activations unless the exact mode is asked for
     return g;
 }
@@ -307,7 +307,7 @@ static int make_bf16_copies(tstar_owl* h, int mode) {
             h->wb[m.w] = p;
             rc = convert_f32_to_bf16(m.w, p, nullptr, n, 0);
             static const bool w2v_off = getenv("TSTAR_W2V_OFF") != nullptr;           // same-session A/Bs: every layer on the LDS tile
-            if (!rc && mode == TSTAR_WEIGHTS_BF16 && m.n == 768 && m.k % 32 == 0 && !w2v_off) {       // per-shape dispatch (gemm_f32.hip launch_mode)
+            if (!rc && mode == TSTAR_WEIGHTS_BF16 && m.n == 768 && m.k % 32 == 0 && !w2v_off) {       // per-shape dispatch (gemm_f32.hip plan_gemm)
                 void* q = nullptr;
                 TSTAR_HIP_CHECK(hipMalloc(&q, n * sizeof(__bf16)));
                 h->wq[m.w] = q;
@@ -794,6 +794,16 @@ int tstar_gemm_f32x3_pre(const float* d_A, const void* d_Wp, float* d_C, const f
     g.Wp = d_Wp;
     g.tile_cfg = tile_cfg;
     return gemm_f32(g, (hipStream_t)stream);
+}
+
+int tstar_gemm_plan(int weights_mode, int M, int N, int ldc, int patch_np, int tile_cfg, int has_packed_w2, int* plan4) {
+    TSTAR_REQUIRE(plan4, "tstar_gemm_plan: null argument");
+    const int wmode = weights_mode == TSTAR_WEIGHTS_F32 ? GEMM_W_F32 : weights_mode == TSTAR_WEIGHTS_BF16 ? GEMM_W_BF16_2T :
+                      weights_mode == TSTAR_WEIGHTS_BF16_EXACT ? GEMM_W_BF16_EXACT : weights_mode == TSTAR_WEIGHTS_F32X3 ? GEMM_W_F32X3 : -1;
+    const GemmPlan p = plan_gemm(wmode, M, N, ldc, patch_np, tile_cfg, has_packed_w2 != 0);
+    if (p.error) { set_error(p.error); return TSTAR_ERR_ARG; }
+    plan4[0] = p.kind; plan4[1] = p.m_split; plan4[2] = p.blocks; plan4[3] = p.lds_bytes;
+    return TSTAR_OK;
 }
 
 int tstar_layernorm_f32(const float* d_x, float* d_y, const float* d_w, const float* d_b, int rows, int D, void* stream) {

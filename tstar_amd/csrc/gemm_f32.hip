@@ -12,7 +12,7 @@
 //  * 128x128x32 block tile, 256 threads = 4 waves (2x2), each wave 64x64 =
 //    2x2 MFMA tiles (64 accumulator VGPRs).  2 blocks per CU so one block's
 //    MFMA stream covers the other's barrier / LDS-write bubbles.  Two smaller
-//    tile shapes (64x128, 64x64) share the code; the launcher (pick_cfg) uses
+//    tile shapes (64x128, 64x64) share the code; the launcher (plan_gemm) uses
 //    them for grids under one wave of 128x128 tiles and, from one full wave
 //    on, launches whole waves of 128x128 tiles followed by a 64x128 tail
 //    (the hybrid kernel), so the last wave is quantised at half a tile.
@@ -1044,9 +1044,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w2_wide_kernel(GemmArgs g) {
 }
 
 // dynamic LDS of one block: double-buffered operand tiles
-template <int WMODE>
-constexpr int lds_bytes(int bm, int bn) {
-    return WMODE == 4 ? 2 * 3 * bm * 64 : WMODE == 3 ? 2 * (2 * bm + bn) * 64 : WMODE == 1 ? 2 * (3 * bm + bn) * 64 : 2 * (bm + bn) * LDS_LD * 4;
+static constexpr int lds_bytes(int wmode, int bm, int bn) {
+    return wmode == GEMM_W_F32X3 ? 2 * 3 * bm * 64 : wmode == GEMM_W_BF16_2T ? 2 * (2 * bm + bn) * 64 : wmode == GEMM_W_BF16_EXACT ? 2 * (3 * bm + bn) * 64 : 2 * (bm + bn) * LDS_LD * 4;
 }
 
 // algorithmic HBM bytes of one launch: A and W read once, C written once, residual read once, bias / position rows
@@ -1054,49 +1053,6 @@ static double gemm_algorithmic_bytes(const GemmArgs& g) {
     const double wbytes = g.Wp ? 6.0 : g.Wb ? 2.0 : 4.0;                // f32x3: three bf16 planes; bf16 weights: one term
     return 4.0 * g.M * g.K + wbytes * g.N * g.K + 4.0 * g.M * g.N * (g.res ? 2.0 : 1.0) + (g.bias ? 4.0 * g.N : 0.0) +
            (g.pos ? 4.0 * (g.patch_np + 1) * g.N : 0.0);
-}
-
-template <class CF, int WMODE, int ACT, bool HAS_BIAS, bool HAS_RES, bool PATCH>
-static int launch_cfg(const GemmArgs& g, hipStream_t stream) {
-    constexpr int lds = lds_bytes<WMODE>(CF::BM, CF::BN);
-    auto kern = gemm_f32_kernel<CF, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>;
-    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
-    const int nwg = cdiv(g.M, CF::BM) * (g.N / CF::BN);
-    const bool prof = prof_enabled();
-    if (prof) prof_start(PROF_GEMM, stream, 2.0 * g.M * g.N * g.K, gemm_algorithmic_bytes(g));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, stream, g);
-    if (prof) prof_stop(PROF_GEMM, stream);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    return TSTAR_OK;
-}
-
-template <int WMODE, int ACT, bool HAS_BIAS, bool HAS_RES, bool PATCH>
-static int launch_hybrid(const GemmArgs& g, hipStream_t stream) {
-    constexpr int lds = lds_bytes<WMODE>(128, 128);
-    auto kern = gemm_f32_hybrid_kernel<WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>;
-    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
-    const int nt = g.N / 128;
-    const int nwg = (g.m_split / 128) * nt + cdiv(g.M - g.m_split, 64) * nt;
-    const bool prof = prof_enabled();
-    if (prof) prof_start(PROF_GEMM, stream, 2.0 * g.M * g.N * g.K, gemm_algorithmic_bytes(g));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, stream, g);
-    if (prof) prof_stop(PROF_GEMM, stream);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    return TSTAR_OK;
-}
-
-template <int WMODE, int ACT, bool HAS_BIAS, bool HAS_RES, bool PATCH, bool VW = false>
-static int launch_wide(const GemmArgs& g, hipStream_t stream) {
-    constexpr int lds = lds_bytes<WMODE>(128, 256);       // (VW: the wide tile needs 32 KB, the 64x128 tail tile of the same kernel this much)
-    auto kern = gemm_bf16w2_wide_kernel<WMODE, ACT, HAS_BIAS, HAS_RES, PATCH, VW>;
-    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), lds)) return rc;
-    const int nwg = (g.m_split / 128) * (g.N / 256) + cdiv(g.M - g.m_split, 64) * (g.N / 128);
-    const bool prof = prof_enabled();
-    if (prof) prof_start(PROF_GEMM, stream, 2.0 * g.M * g.N * g.K, gemm_algorithmic_bytes(g));
-    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), lds, stream, g);
-    if (prof) prof_stop(PROF_GEMM, stream);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    return TSTAR_OK;
 }
 
 // Tile choice, calibrated on MI355X (tools/sweep_small_m.py for launches under two waves of 128x128 tiles -- the
@@ -1113,14 +1069,14 @@ static int launch_wide(const GemmArgs& g, hipStream_t stream) {
 //    the chip idle for up to half a tile time (fc1 at B = 5: 91 -> 109 TFLOP/s);
 //  * from two waves on, as many whole 512-block waves of 128x128 tiles as fit, the remaining rows as 64x128 tiles, which
 //    arrive last and fill the tail at half the granularity (never worse than a pure grid, up to +15 %).
-// Returns 0/1/2 for a pure grid, or 3 for the hybrid launch with *m_split set.
+// Returns a pure grid, or GEMM_HYBRID with *m_split set.
 static int pick_cfg(int M, int N, int* m_split) {
     *m_split = 0;
     const int nt = N / 128;
     const int mt = cdiv(M, 128);
     const int b128 = mt * nt;
-    if (b128 <= 200) return 2;                               // 64x64
-    if (b128 <= 256) return 1;                               // 64x128
+    if (b128 <= 200) return GEMM_GRID_64;
+    if (b128 <= 256) return GEMM_GRID_64N;
     if (b128 < 410 || (b128 >= 512 && b128 < 1024)) {
         int n_big = mt / 2;
         if (b128 < 410) {
@@ -1128,78 +1084,107 @@ static int pick_cfg(int M, int N, int* m_split) {
             if (fill > n_big) n_big = fill;
         }
         if (n_big > mt - 1) n_big = mt - 1;
-        if (n_big < 1) return 1;
+        if (n_big < 1) return GEMM_GRID_64N;
         *m_split = n_big * 128;
-        return 3;
+        return GEMM_HYBRID;
     }
-    if (b128 < 512) return 0;                                // 128x128
+    if (b128 < 512) return GEMM_GRID_128;
     const int big_rows = ((b128 / 512) * 512 / nt) * 128;    // rows covered by whole waves of 128x128 tiles
-    if (big_rows >= M) return 0;
+    if (big_rows >= M) return GEMM_GRID_128;
     *m_split = big_rows;
-    return 3;
+    return GEMM_HYBRID;
 }
 
-template <int WMODE, int ACT, bool HAS_BIAS, bool HAS_RES, bool PATCH>
-static int launch_mode(const GemmArgs& g, hipStream_t stream) {
-    const int forced = g.tile_cfg;                           // -1 = auto
-    if constexpr (WMODE == 3 || WMODE == 4) {
+GemmPlan plan_gemm(int wmode, int M, int N, int ldc, int patch_np, int tile_cfg, bool has_wq) {
+    auto refuse = [](const char* msg) { return GemmPlan{0, 0, 0, 0, msg}; };
+    if (wmode != GEMM_W_F32 && wmode != GEMM_W_BF16_EXACT && wmode != GEMM_W_BF16_2T && wmode != GEMM_W_F32X3) return refuse("gemm_f32: unknown weight mode");
+    if (M <= 0 || N <= 0) return refuse("gemm_f32: empty problem");
+    if (N % 128 != 0) return refuse("gemm_f32: N must be a multiple of 128");
+    if (!((tile_cfg >= TILE_AUTO && tile_cfg <= TILE_WIDE_VW) || tile_cfg >= TILE_HYBRID_N)) return refuse("gemm_f32: tile_cfg must be -1..6 (or 16 + big row tiles)");
+    const int forced = tile_cfg;
+    const int nt = N / 128;
+    auto wide = [&](int kind, int m_split) {
+        return GemmPlan{kind, m_split, (m_split / 128) * (N / 256) + cdiv(M - m_split, 64) * nt, lds_bytes(wmode, 128, 256), nullptr};   // (GEMM_WIDE_VW: the wide tile needs 32 KB, the 64x128 tail tile of the same kernel this much)
+    };
+    if (wmode == GEMM_W_BF16_2T || wmode == GEMM_W_F32X3) {
         // two-term mode (and the f32x3 mode, whose 128x256 tile measures 6-7 % above its 128x128 one: 197-201 vs 184-188 TFLOP/s): from one wave (512) of 128x256 tiles on, whole waves of them; the remaining full panels are wide
         // too when they make more than half a wave (a 64x128 tile of this mode is LDS-bound and runs at ~0.7 of the wide
         // tile's rate: three rounds of them cost more than one round of wide tiles -- tools/bench_gemm_bf16.py: out-proj
         // at B = 64, 864 wide tiles: 410 all wide vs 384 with a narrow tail), else they and the ragged rows go out as
-        // 64x128 tiles that fill the tail (tile_cfg 4 forces every full 128-row panel wide; 5 forces the wide tile OFF)
-        if (g.N % 256 == 0 && forced != 5 && (forced == -1 || forced == 4 || forced == 6)) {
-            const int ntw = g.N / 256, mt = g.M / 128;       // full 128-row panels only
+        // 64x128 tiles that fill the tail (TILE_WIDE forces every full 128-row panel wide; TILE_NO_WIDE forces the wide tile OFF)
+        if (N % 256 == 0 && (forced == TILE_AUTO || forced == TILE_WIDE || forced == TILE_WIDE_VW)) {
+            const int ntw = N / 256, mt = M / 128;           // full 128-row panels only
             const long long bw = (long long)mt * ntw;
             int big = 0;
-            if (forced == 4 || forced == 6) big = mt;
+            if (forced == TILE_WIDE || forced == TILE_WIDE_VW) big = mt;
             else if (bw >= 512) big = (bw % 512) > 256 ? mt : (int)(((bw / 512) * 512) / ntw);
             // f32x3, under one wave of wide tiles (tools/sweep_x3_cfg.py, profiles/r05_x3_cfg_sweep.log): the wide tile still wins when its
             // blocks nearly fill the 512 slots (>= 400: fc1 at B = 8 195 -> 216, qkv at B = 10 190 -> 212 TFLOP/s) or when every block gets
             // a CU to itself (192..256: out-proj / fc2 at B = 16 +5 / +7 %); in between (a full CU pair next to single ones) it loses
-            else if (WMODE == 4 && (bw >= 400 || (bw >= 192 && bw <= 256))) big = mt;
-            const bool fits32 = ((long long)(g.M + g.M / (g.patch_np > 0 ? g.patch_np : g.M) + 1) * g.ldc) < (1ll << 32);   // the wide epilogue's offsets
+            else if (wmode == GEMM_W_F32X3 && (bw >= 400 || (bw >= 192 && bw <= 256))) big = mt;
+            const bool fits32 = ((long long)(M + M / (patch_np > 0 ? patch_np : M) + 1) * ldc) < (1ll << 32);   // the wide epilogue's offsets
             if (big > 0 && fits32) {
-                GemmArgs h = g;
-                h.m_split = big * 128;
-                if constexpr (WMODE == 3) {
-                    // round 6, per-shape dispatch: with a fragment-packed plane at hand the wide tiles of the N = 768 layers (out-proj, fc2,
-                    // patch embedding, box head) stream their weights global -> VGPR (+12 ... +20 % there; +-3 % on the wide layers, which
-                    // keep the LDS tile).  Same bits either way.  tile_cfg 6 forces this tile on every full panel of any N (tests).
-                    if (g.Wq && (forced == 6 || (forced == -1 && g.N == 768))) return launch_wide<3, ACT, HAS_BIAS, HAS_RES, PATCH, true>(h, stream);
-                }
-                TSTAR_REQUIRE(forced != 6, "gemm_f32: tile_cfg 6 needs the two-term mode with a fragment-packed weight plane (Wq)");
-                return launch_wide<WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(h, stream);
+                // round 6, per-shape dispatch: with a fragment-packed plane at hand the wide tiles of the N = 768 layers (out-proj, fc2,
+                // patch embedding, box head) stream their weights global -> VGPR (+12 ... +20 % there; +-3 % on the wide layers, which
+                // keep the LDS tile).  Same bits either way.  TILE_WIDE_VW forces this tile on every full panel of any N (tests).
+                if (wmode == GEMM_W_BF16_2T && has_wq && (forced == TILE_WIDE_VW || (forced == TILE_AUTO && N == 768))) return wide(GEMM_WIDE_VW, big * 128);
+                if (forced == TILE_WIDE_VW) return refuse("gemm_f32: tile_cfg 6 needs the two-term mode with a fragment-packed weight plane (Wq)");
+                return wide(GEMM_WIDE, big * 128);
             }
         }
     }
+    if (forced == TILE_WIDE_VW) return refuse("gemm_f32: tile_cfg 6 (two-term wide tile, weights global -> VGPR) needs N % 256 == 0, at least one full 128-row panel and a packed plane");
     int m_split = 0;
-    TSTAR_REQUIRE(forced != 6, "gemm_f32: tile_cfg 6 (two-term wide tile, weights global -> VGPR) needs N % 256 == 0, at least one full 128-row panel and a packed plane");
-    int cfg = (forced >= 0 && forced <= 3) || forced >= 16 ? forced : pick_cfg(g.M, g.N, &m_split);
-    if (forced == 3) {                                       // forced hybrid: half of the row tiles big
-        m_split = (cdiv(g.M, 128) / 2) * 128;
-        if (m_split == 0) cfg = 1;
-    } else if (forced >= 16) {                               // diagnostic: hybrid with (forced - 16) big row tiles
-        m_split = (forced - 16) * 128;
-        if (m_split > (g.M / 128) * 128) m_split = (g.M / 128) * 128;
-        cfg = m_split == 0 ? 1 : 3;
+    int kind = (forced >= TILE_128 && forced <= TILE_HYBRID) || forced >= TILE_HYBRID_N ? forced : pick_cfg(M, N, &m_split);   // TILE_128 .. TILE_HYBRID are the GemmKind numbers
+    if (forced == TILE_HYBRID) {                             // forced hybrid: half of the row tiles big
+        m_split = (cdiv(M, 128) / 2) * 128;
+        if (m_split == 0) kind = GEMM_GRID_64N;
+    } else if (forced >= TILE_HYBRID_N) {                    // diagnostic: hybrid with (forced - 16) big row tiles
+        const long long want = (long long)(forced - TILE_HYBRID_N) * 128, full = (long long)(M / 128) * 128;
+        m_split = (int)(want < full ? want : full);
+        kind = m_split == 0 ? GEMM_GRID_64N : GEMM_HYBRID;
     }
-    if (cfg == 3) {
-        GemmArgs h = g;
-        h.m_split = m_split;
-        return launch_hybrid<WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(h, stream);
+    if (kind == GEMM_HYBRID) return GemmPlan{kind, m_split, (m_split / 128) * nt + cdiv(M - m_split, 64) * nt, lds_bytes(wmode, 128, 128), nullptr};
+    const int bm = kind == GEMM_GRID_128 ? 128 : 64, bn = kind == GEMM_GRID_64 ? 64 : 128;
+    return GemmPlan{kind, 0, cdiv(M, bm) * (N / bn), lds_bytes(wmode, bm, bn), nullptr};
+}
+
+// every GEMM kernel of this file: one GemmArgs by value, 256 threads
+static int launch_gemm(void (*kern)(GemmArgs), const GemmPlan& p, const GemmArgs& g, hipStream_t stream) {
+    if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kern), p.lds_bytes)) return rc;
+    const bool prof = prof_enabled();
+    if (prof) prof_start(PROF_GEMM, stream, 2.0 * g.M * g.N * g.K, gemm_algorithmic_bytes(g));
+    hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(256), p.lds_bytes, stream, g);
+    if (prof) prof_stop(PROF_GEMM, stream);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    return TSTAR_OK;
+}
+
+template <int WMODE, int ACT, bool HAS_BIAS, bool HAS_RES, bool PATCH>
+static int launch_mode(const GemmArgs& g0, hipStream_t stream) {
+    const GemmPlan p = plan_gemm(WMODE, g0.M, g0.N, g0.ldc, g0.patch_np, g0.tile_cfg, g0.Wq != nullptr);
+    if (p.error) { set_error(p.error); return TSTAR_ERR_ARG; }
+    GemmArgs g = g0;
+    g.m_split = p.m_split;
+    void (*kern)(GemmArgs) = nullptr;
+    switch (p.kind) {
+        case GEMM_WIDE_VW: if constexpr (WMODE == GEMM_W_BF16_2T) kern = gemm_bf16w2_wide_kernel<GEMM_W_BF16_2T, ACT, HAS_BIAS, HAS_RES, PATCH, true>; break;
+        case GEMM_WIDE: if constexpr (WMODE == GEMM_W_BF16_2T || WMODE == GEMM_W_F32X3) kern = gemm_bf16w2_wide_kernel<WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>; break;
+        case GEMM_HYBRID: kern = gemm_f32_hybrid_kernel<WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>; break;
+        case GEMM_GRID_128: kern = gemm_f32_kernel<Cfg128, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>; break;
+        case GEMM_GRID_64N: kern = gemm_f32_kernel<Cfg64N, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>; break;
+        case GEMM_GRID_64: kern = gemm_f32_kernel<Cfg64, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>; break;
     }
-    if (cfg == 0) return launch_cfg<Cfg128, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
-    if (cfg == 1) return launch_cfg<Cfg64N, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
-    return launch_cfg<Cfg64, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
+    TSTAR_REQUIRE(kern != nullptr, "gemm_f32: the plan names a tile that this weight mode does not have");
+    return launch_gemm(kern, p, g, stream);
 }
 
 template <int ACT, bool HAS_BIAS, bool HAS_RES, bool PATCH>
 static int launch_one(const GemmArgs& g, hipStream_t stream) {
-    if (g.Wp) return launch_mode<4, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
-    if (g.Wb && g.a_terms == 2) return launch_mode<3, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
-    if (g.Wb) return launch_mode<1, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
-    return launch_mode<0, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
+    if (g.Wp) return launch_mode<GEMM_W_F32X3, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
+    if (g.Wb && g.a_terms == 2) return launch_mode<GEMM_W_BF16_2T, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
+    if (g.Wb) return launch_mode<GEMM_W_BF16_EXACT, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
+    return launch_mode<GEMM_W_F32, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
 }
 
 // rows of a super-panel (tile_mn): TSTAR_GEMM_GM overrides the default for A/B runs (1 = the panel-major order of rounds 1-3)
@@ -1212,10 +1197,8 @@ int gemm_f32(const GemmArgs& g0, hipStream_t stream) {
     GemmArgs g = g0;
     if (g.group_m <= 0) g.group_m = default_group_m();
     TSTAR_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "gemm_f32: empty problem");
-    TSTAR_REQUIRE(g.N % 128 == 0, "gemm_f32: N must be a multiple of 128");
     TSTAR_REQUIRE(g.K % BK == 0, "gemm_f32: K must be a multiple of 32");
     TSTAR_REQUIRE(g.lda % 4 == 0 && g.K % 4 == 0, "gemm_f32: rows must be 16-byte aligned");
-    TSTAR_REQUIRE((g.tile_cfg >= -1 && g.tile_cfg <= 6) || g.tile_cfg >= 16, "gemm_f32: tile_cfg must be -1..6 (or 16 + big row tiles)");
     const bool bias = g.bias != nullptr, res = g.res != nullptr, patch = g.pos != nullptr;
     if (patch) {
         TSTAR_REQUIRE(!bias && !res && g.act == ACT_NONE && g.patch_np > 0, "gemm_f32: patch epilogue takes no bias/res/act");

@@ -19,13 +19,56 @@ struct GemmArgs {
     int M, N, K, lda, ldc;
     int act;             // ACT_*
     int patch_np;        // patches per image (576) for the patch-embed epilogue
-    int tile_cfg;        // (4 / 5: wide tile forced on / off; 6: the two-term wide tile with weights global -> VGPR forced)  -1 auto; 0 = 128x128, 1 = 64x128, 2 = 64x64 block tile, 3 = hybrid 128x128 + 64x128 tail (half/half); 16 + n = hybrid with n big row tiles (diagnostic)
+    int tile_cfg;        // a GemmTileCfg value (below); crosses the C ABI as int
     int m_split;         // hybrid launch: rows [0, m_split) use 128-row tiles (set by the launcher)
     int group_m;         // row panels per super-panel of the tile order (gemm_f32.hip tile_mn); 0 = the library's default
     int a_terms;         // bf16-weight tile (Wb set): 2 = activations as two round-to-nearest bf16 terms (2 MFMA
                          // products per algorithmic product); anything else = the exact three-term split
 };
 int gemm_f32(const GemmArgs& g, hipStream_t stream);
+
+// GemmArgs::tile_cfg.  The numbers are fixed: the diagnostic C entry points, the tests and tools/sweep_*.py pass them as int.
+enum GemmTileCfg {
+    TILE_AUTO = -1,       // the launcher's choice (plan_gemm)
+    TILE_128 = 0,         // pure grid of 128x128 block tiles
+    TILE_64N = 1,         // pure grid of 64x128 block tiles
+    TILE_64 = 2,          // pure grid of 64x64 block tiles
+    TILE_HYBRID = 3,      // 128x128 tiles on the first half of the row tiles + 64x128 tail
+    TILE_WIDE = 4,        // two-term bf16 / f32x3 modes: the 128x256 tile forced on every full 128-row panel
+    TILE_NO_WIDE = 5,     // two-term bf16 / f32x3 modes: the 128x256 tile forced off
+    TILE_WIDE_VW = 6,     // two-term bf16 mode: the 128x256 tile with weights global -> VGPR forced on every full panel
+    TILE_HYBRID_N = 16,   // 16 + n: hybrid with n big row tiles (diagnostic, tile-policy sweeps)
+};
+
+// How a launch reads its weights; the values are the WMODE template argument of the kernels.
+enum GemmWeightMode {
+    GEMM_W_F32 = 0,       // native f32 MFMA
+    GEMM_W_BF16_EXACT = 1,// bf16 weights, activations split exactly into three bf16 terms
+    GEMM_W_BF16_2T = 3,   // bf16 weights, activations as two round-to-nearest bf16 terms
+    GEMM_W_F32X3 = 4,     // fragment-packed three-plane weights, six products
+};
+
+enum GemmKind {
+    GEMM_GRID_128 = 0,    // pure grid of 128x128 tiles
+    GEMM_GRID_64N = 1,    // pure grid of 64x128 tiles
+    GEMM_GRID_64 = 2,     // pure grid of 64x64 tiles
+    GEMM_HYBRID = 3,      // rows [0, m_split) in 128x128 tiles, the rest in 64x128 tiles
+    GEMM_WIDE = 4,        // rows [0, m_split) in 128x256 tiles, the rest in 64x128 tiles
+    GEMM_WIDE_VW = 5,     // the same with the wide tiles' weights streamed global -> VGPR (needs GemmArgs::Wq)
+};
+
+// What one launch does.  error != null: the arguments are refused (TSTAR_ERR_ARG) and the other fields mean nothing.
+struct GemmPlan {
+    int kind;             // GemmKind
+    int m_split;          // GemmArgs::m_split of the launch (0 for a pure grid)
+    int blocks;           // grid size
+    int lds_bytes;        // dynamic LDS per block
+    const char* error;
+};
+
+// The tile policy: pure integer arithmetic, no HIP call, no global state (tests/test_host_logic.py pins it on a host without a GPU).
+// has_wq: a fragment-packed two-term plane (GemmArgs::Wq) exists.
+GemmPlan plan_gemm(int wmode, int M, int N, int ldc, int patch_np, int tile_cfg, bool has_wq);
 
 // Wb[i] = bfloat16(W[i]) (round to nearest even); n elements.  With Wlo != null also Wlo[i] = bfloat16(W[i] - Wb[i]).
 int convert_f32_to_bf16(const float* W, __bf16* Wb, __bf16* Wlo, size_t n, hipStream_t s);
