@@ -6,9 +6,11 @@ groups, the keyframe indices are all-gathered (RCCL) and rank 0 writes the refer
 
 Grounding (question -> target / cue objects) is a remote VLM call in the reference and is out of scope
 here: every item carries its objects.  Videos are synthetic:// URLs (BASELINE configs[2]: the real
-LV-Haystack split needs network).
+LV-Haystack split needs network) unless --videos names files: anything tstar_amd.video.open_video reads --
+a Motion-JPEG .avi, a .mjpeg stream, a folder of .jpg frames (--video-fps for the latter two), .y4m, ...
 
   python examples/run_dataset.py --items 8 --out /tmp/results.json
+  python examples/run_dataset.py --videos clips/a.avi clips/b_frames/ --video-fps 1
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_dataset.py --items 32
 """
 import argparse
@@ -34,6 +36,10 @@ def main():
     ap.add_argument("--out", default="./output/tstar_results.json")
     ap.add_argument("--owl-model", default="google/owlvit-base-patch32",
                     help="OWL-ViT checkpoint (name or directory; B/32 or B/16); seeded synthetic B/32 weights when none is on disk")
+    ap.add_argument("--videos", nargs="+", default=None,
+                    help="video files / JPEG frame folders to search instead of synthetic videos (one item each; overrides --items)")
+    ap.add_argument("--video-fps", type=float, default=None,
+                    help="frame rate of JPEG frame folders (default 1) and .mjpeg streams (default 25) among --videos")
     args = ap.parse_args()
 
     import torch
@@ -54,8 +60,17 @@ def main():
         _shard.PREFER_RCCL = os.environ.get("TSTAR_BENCH_BACKEND", "nccl") == "nccl"
         dist.init_process_group("gloo")
 
-    items = [{"video_path": f"synthetic://n={args.nframes},seed={100 + i}", "targets": QUESTIONS[i % 4][0],
-              "cues": QUESTIONS[i % 4][1]} for i in range(args.items)]
+    paths = args.videos if args.videos else [f"synthetic://n={args.nframes},seed={100 + i}" for i in range(args.items)]
+    items = [{"video_path": p, "targets": QUESTIONS[i % 4][0], "cues": QUESTIONS[i % 4][1]} for i, p in enumerate(paths)]
+
+    def video_of(i):
+        """What the searcher opens: the path itself, or the store when the rate has to be passed along."""
+        p = items[i]["video_path"]
+        if args.video_fps is not None and (os.path.isdir(p) or p.lower().endswith((".mjpeg", ".mjpg"))):
+            from tstar_amd.video import open_video
+            return open_video(p, fps=args.video_fps)
+        return p
+
     heuristic = initialize_heuristic("owl-vit", model_name_or_path=args.owl_model, synthetic_seed=0, max_batch=64,
                                      device=f"cuda:{local}")
     mine = shard_items(len(items), world, rank)
@@ -64,7 +79,7 @@ def main():
     L = max(1, min(args.lockstep, 31))
     for g0 in range(0, len(mine), 2 * L):
         groups = [mine[g1:g1 + L] for g1 in range(g0, min(g0 + 2 * L, len(mine)), L)]
-        sss = [[TStarSearcher(items[i]["video_path"], heuristic, list(items[i]["targets"]), list(items[i]["cues"]),
+        sss = [[TStarSearcher(video_of(i), heuristic, list(items[i]["targets"]), list(items[i]["cues"]),
                               search_nframes=args.search_nframes, image_grid_shape=(args.grid, args.grid),
                               search_budget=1000, confidence_threshold=0.6,
                               rng=np.random.RandomState(item_seed(args.seed, i)), keep_visual_history=False) for i in group]

@@ -221,6 +221,36 @@ int tstar_frames_resize(const uint8_t* d_video, int N, int H, int W, const int32
  * device -> the resident NV12 store layout u8 [n, H*3/2, W] the ingest kernels read.  Replaces the decode half of
  * read_frame_batch (interface_searcher.py:157-169) for such files. */
 int tstar_i420_to_nv12(const uint8_t* d_i420, int n, int H, int W, uint8_t* d_nv12, void* stream);
+/* Decode front end for JPEG frames (Motion-JPEG AVI / .mjpeg streams, folders of .jpg): replaces the decode half of
+ * read_frame_batch (interface_searcher.py:157-169) for such files.  Baseline / extended sequential Huffman, 8-bit, one
+ * interleaved scan, grayscale or YCbCr with luma sampling 1x1, 2x1 or 2x2 (hs, vs) and chroma 1x1.  The entropy stage runs
+ * on the host (serial per scan), everything after it on the device; the result is byte-equal to libjpeg-turbo's default
+ * decode (accurate integer IDCT, fancy upsampling).  The host entries touch no HIP state and work without a device.
+ *
+ * Frame status / return value of tstar_jpeg_probe: 0 decodable here, 1 malformed or truncated, 2 a JPEG this decoder does
+ * not cover (progressive, arithmetic, CMYK, other sampling: hand it to a general decoder), 3 geometry differs from the batch.
+ * Layouts for a geometry (W, H, ncomp, hs, vs): coefficients int16 [blocks][64] in natural order, component after
+ * component, block-raster within the component, padded to whole MCUs; tables u16 [3][64] per frame, natural order. */
+/* Header walk: info5 = {W, H, ncomp, hs, vs}. */
+int tstar_jpeg_probe(const uint8_t* data, size_t len, int32_t* info5);
+/* One past the EOI of the JPEG starting at data[pos], by walking marker segments and the stuffed entropy data; 0 if broken. */
+size_t tstar_jpeg_frame_end(const uint8_t* data, size_t len, size_t pos);
+/* out2 = {blocks per frame, bytes of the per-frame plane workspace}. */
+int tstar_jpeg_sizes(int W, int H, int ncomp, int hs, int vs, size_t* out2);
+/* Threads a batch uses: min(16, CPUs the process may run on, asked when > 0). */
+int tstar_jpeg_threads(int asked);
+/* Entropy-decode n independent frames on a thread pool into caller memory (pinned for the device path): coef int16
+ * [n][blocks][64], quant u16 [n][3][64], status i32 [n].  Returns 0 when every frame decoded, else TSTAR_ERR_STATE with the
+ * first failing frame's message in tstar_last_error(); never reads or writes outside the given buffers. */
+int tstar_jpeg_entropy_batch(const uint8_t* const* datas, const size_t* lens, int n, int W, int H, int ncomp, int hs, int vs,
+                             int16_t* coef, uint16_t* quant, int threads, int32_t* status);
+/* Scalar host reference of tstar_jpeg_reconstruct (same integers): rgb u8 [n,H,W,3] in host memory. */
+int tstar_jpeg_reconstruct_host(const int16_t* coef, const uint16_t* quant, int n, int W, int H, int ncomp, int hs, int vs,
+                                uint8_t* rgb, int threads);
+/* Device stage: dequantise + inverse DCT + range limit -> u8 planes (d_planes: n * plane-workspace bytes), then chroma
+ * upsampling + YCbCr -> RGB into d_rgb u8 [n,H,W,3] (typically store[s0 : s0 + n]).  d_coef / d_quant 16-byte aligned. */
+int tstar_jpeg_reconstruct(const int16_t* d_coef, const uint16_t* d_quant, int n, int W, int H, int ncomp, int hs, int vs,
+                           uint8_t* d_planes, uint8_t* d_rgb, void* stream);
 /* Native-resolution RGB u8 [n,H,W,3] of NV12 frames (the keyframes pop_frames hands back, :379-380). */
 int tstar_nv12_to_rgb(const uint8_t* d_video, int N, int H, int W, const int32_t* d_frame_idx, int n,
                       uint8_t* d_out, void* stream);

@@ -48,6 +48,13 @@ SIGNATURES = {
     "tstar_frames_resize": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     "tstar_i420_to_nv12": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "tstar_nv12_to_rgb": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "tstar_jpeg_probe": (_i, [_vp, _sz, _vp]),
+    "tstar_jpeg_frame_end": (_sz, [_vp, _sz, _sz]),
+    "tstar_jpeg_sizes": (_i, [_i, _i, _i, _i, _i, _vp]),
+    "tstar_jpeg_threads": (_i, [_i]),
+    "tstar_jpeg_entropy_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "tstar_jpeg_reconstruct_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i]),
+    "tstar_jpeg_reconstruct": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tstar_searcher_create": (_i, [C.POINTER(_vp), _i, C.c_double, C.c_double]),
     "tstar_searcher_destroy": (_i, [_vp]),
     "tstar_searcher_apply_grid": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

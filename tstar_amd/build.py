@@ -38,8 +38,13 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (set HIPCC)")
 
 
+# HIP-free host sources that are part of libtstar_hip.so (hipcc compiles them as plain C++)
+HOST_SOURCES = ("jpeg_host.cpp",)
+HOST_FLAGS = ["-x", "c++", "-O3", "-std=c++20", "-fPIC", "-Wall", "-pthread"]
+
+
 def sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    return sorted([f for f in os.listdir(CSRC) if f.endswith(".hip")] + list(HOST_SOURCES))
 
 
 def _newest_header() -> float:
@@ -56,11 +61,14 @@ def build(force: bool = False, verbose: bool = True) -> str:
     objs = []
     for src in sources():
         sp = os.path.join(CSRC, src)
-        op = os.path.join(OBJ, src[:-4] + ".o")
+        op = os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
         objs.append(op)
         stale = force or not os.path.exists(op) or os.path.getmtime(op) < max(os.path.getmtime(sp), hdr)
         if stale:
-            jobs.append([hipcc] + FLAGS + PER_FILE.get(src, []) + ["-c", sp, "-o", op])
+            if src in HOST_SOURCES:
+                jobs.append([hipcc] + HOST_FLAGS + ["-c", sp, "-o", op])
+            else:
+                jobs.append([hipcc] + FLAGS + PER_FILE.get(src, []) + ["-c", sp, "-o", op])
 
     def run(cmd):
         if verbose:

@@ -3,6 +3,7 @@
 #include "../../include/tstar_hip.h"
 #include "common.h"
 #include "heads.h"
+#include "jpeg_host.h"
 #include "kernels.h"
 #include "owl_weights.h"
 #include <math.h>
@@ -695,6 +696,13 @@ int tstar_nv12_to_rgb(const uint8_t* d_video, int N, int H, int W, const int32_t
 int tstar_i420_to_nv12(const uint8_t* d_i420, int n, int H, int W, uint8_t* d_nv12, void* stream) {
     TSTAR_REQUIRE(d_i420 && d_nv12 && d_i420 != d_nv12, "tstar_i420_to_nv12: null or aliased argument");
     return i420_to_nv12_u8(d_i420, n, H, W, d_nv12, (hipStream_t)stream);
+}
+
+int tstar_jpeg_reconstruct(const int16_t* d_coef, const uint16_t* d_quant, int n, int W, int H, int ncomp, int hs, int vs,
+                           uint8_t* d_planes, uint8_t* d_rgb, void* stream) {
+    TSTAR_REQUIRE(d_coef && d_quant && d_planes && d_rgb, "tstar_jpeg_reconstruct: null argument");
+    const JpegGeom g{W, H, ncomp, hs, vs};
+    return jpeg_reconstruct_u8(d_coef, d_quant, n, g, d_planes, d_rgb, (hipStream_t)stream);
 }
 
 int tstar_gemm_f32(const float* d_A, const float* d_W, float* d_C, const float* d_bias, const float* d_residual, int M,

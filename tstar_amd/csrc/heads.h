@@ -60,5 +60,10 @@ int frames_to_grid_u8(const uint8_t* video, int H, int W, const int* d_idx, int 
 int i420_to_nv12_u8(const uint8_t* in, int n, int H, int W, uint8_t* out, hipStream_t s);
 // frames[idx[i]] NV12 [H*3/2, W] -> RGB u8 [n,H,W,3] (BT.601 limited range, nearest chroma)
 int nv12_to_rgb_u8(const uint8_t* video, int H, int W, const int* d_idx, int n, uint8_t* out, hipStream_t s);
+// jpeg.hip: n frames of coefficient blocks [n][g.blocks()][64] + tables u16 [n][3][64] -> RGB u8 [n,H,W,3]; planes is a
+// workspace of n * g.plane_bytes() bytes (layouts in jpeg_host.h)
+struct JpegGeom;
+int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const JpegGeom& g, uint8_t* planes, uint8_t* rgb,
+                        hipStream_t s);
 
 }  // namespace tstar

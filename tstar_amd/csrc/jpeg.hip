@@ -1,0 +1,175 @@
+// Baseline JPEG decode front end, device half: the coefficient blocks the host entropy stage (jpeg_host.cpp) produced
+// -> RGB u8 frames in the resident store.  Two kernels per chunk of frames of one geometry:
+//   jpeg_idct_kernel   dequantise + libjpeg's accurate integer IDCT + range limit -> u8 component planes (whole blocks)
+//   jpeg_color_kernel  "fancy" chroma upsampling + YCbCr -> RGB, written straight into store[s0 : s0 + n]
+// The integers are those of jpeg_math.h (shared with the host reference), so the result is byte-equal to libjpeg-turbo.
+// Traffic per picture sample: 2 B of coefficients in, 1 B of plane out and in again, 1 B of RGB out.
+#include "common.h"
+#include "heads.h"
+#include "jpeg_host.h"
+#include "jpeg_math.h"
+
+namespace tstar {
+
+namespace {
+
+constexpr int kBlocksPerWg = 32;       // 256 threads: 8 lanes per 8x8 block, 8 blocks per wave
+constexpr int kRowPitch = 9;           // LDS dwords per block row: with 72 per block, every access below is bank-conflict-free
+constexpr int kBlockPitch = 72;
+
+// One workgroup = 32 consecutive blocks of one component (block-raster order, frame after frame).
+//   load   lane (block, r) reads coefficient row r as one 16-byte vector -- a wave reads 1 KiB contiguous -- and the matching
+//          quantiser row, multiplies, and parks the products in LDS;
+//   pass 1 lane (block, c) transforms column c in registers and writes it back in place;
+//   pass 2 lane (r, block) transforms row r, limits the range and stores 8 pixels as one 8-byte vector; the 8 lanes of a
+//          row r cover 64 contiguous bytes of the plane when the blocks are neighbours.
+// LDS word of element (row k, col c) of block b: b * 72 + k * 9 + c.  Bank = that mod 64: for a fixed k (pass 1: lanes
+// (b, c)) 8b + c + 9k is distinct over the 64 lanes of a wave; for a fixed c (load / pass 2: lanes (b, r)) 8(b + r) + r + c
+// is distinct too.
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restrict__ coef, size_t coef_frame_stride,
+                                                        const uint16_t* __restrict__ quant, uint8_t* __restrict__ planes,
+                                                        size_t plane_frame_stride, int nblk, int bw, size_t total_blocks) {
+    __shared__ uint32_t ws[kBlocksPerWg * kBlockPitch];
+    const int t = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * kBlocksPerWg;
+    {
+        const int bl = t >> 3, r = t & 7;
+        const size_t gb = base + bl;
+        if (gb < total_blocks) {
+            const size_t f = gb / nblk, g = gb % nblk;
+            const uint4 cv = *reinterpret_cast<const uint4*>(coef + f * coef_frame_stride + g * 64 + r * 8);
+            const uint4 qv = *reinterpret_cast<const uint4*>(quant + f * 192 + r * 8);
+            const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
+            uint32_t* dst = ws + bl * kBlockPitch + r * kRowPitch;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int c0 = (int16_t)(cw[k] & 0xffff), c1 = (int16_t)(cw[k] >> 16);
+                dst[2 * k] = (uint32_t)(c0 * (int)(qw[k] & 0xffff));
+                dst[2 * k + 1] = (uint32_t)(c1 * (int)(qw[k] >> 16));
+            }
+        }
+    }
+    __syncthreads();
+    {
+        const int bl = t >> 3, c = t & 7;
+        uint32_t* col = ws + bl * kBlockPitch + c;
+        uint32_t x[8];
+        int32_t o[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = col[k * kRowPitch];
+        jpegmath::idct8(x, o, 11);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) col[k * kRowPitch] = (uint32_t)o[k];
+    }
+    __syncthreads();
+    {
+        const int lane = t & 63, bl = (t >> 6) * 8 + (lane & 7), r = lane >> 3;
+        const size_t gb = base + bl;
+        if (gb < total_blocks) {
+            const uint32_t* row = ws + bl * kBlockPitch + r * kRowPitch;
+            uint32_t x[8];
+            int32_t o[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = row[k];
+            jpegmath::idct8(x, o, 18);
+            uint2 px;
+            px.x = (uint32_t)jpegmath::range_limit(o[0]) | ((uint32_t)jpegmath::range_limit(o[1]) << 8) |
+                   ((uint32_t)jpegmath::range_limit(o[2]) << 16) | ((uint32_t)jpegmath::range_limit(o[3]) << 24);
+            px.y = (uint32_t)jpegmath::range_limit(o[4]) | ((uint32_t)jpegmath::range_limit(o[5]) << 8) |
+                   ((uint32_t)jpegmath::range_limit(o[6]) << 16) | ((uint32_t)jpegmath::range_limit(o[7]) << 24);
+            const size_t f = gb / nblk, g = gb % nblk;
+            const size_t by = g / bw, bx = g % bw;
+            *reinterpret_cast<uint2*>(planes + f * plane_frame_stride + (by * 8 + r) * ((size_t)bw * 8) + bx * 8) = px;
+        }
+    }
+}
+
+struct ColorArgs {
+    size_t plane_frame_stride, off1, off2;       // byte offsets of the Cb / Cr planes inside a frame's planes
+    int pitch0, pitch1, W, H, ncomp, hs, vs, cw, ch;
+};
+
+// Four consecutive pixels of the chunk (flat index over [n, H, W]) per lane -> 12 bytes = three dword stores.  A chroma
+// sample is read by the (up to four) pixels it feeds from L1 / L2; HBM sees every plane byte once.
+// DWORDS = false: the byte-store form for a destination that is not 4-byte aligned (odd W * H * s0).
+template <bool DWORDS>
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restrict__ planes, ColorArgs a, uint8_t* __restrict__ rgb,
+                                                         size_t total_px) {
+    const size_t q = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (q >= total_px) return;
+    const size_t per = (size_t)a.W * a.H;
+    size_t f = q / per;
+    const size_t rem = q % per;
+    int y = (int)(rem / a.W), x = (int)(rem % a.W);
+    const int npx = total_px - q < 4 ? (int)(total_px - q) : 4;
+    uint32_t px[4] = {0, 0, 0, 0};                                 // R | G << 8 | B << 16 of each pixel, kept in registers
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j < npx) {
+            const uint8_t* fp = planes + f * a.plane_frame_stride;
+            const int yy = fp[(size_t)y * a.pitch0 + x];
+            uint8_t t[3] = {(uint8_t)yy, (uint8_t)yy, (uint8_t)yy};
+            if (a.ncomp == 3) {
+                const int cb = jpegmath::upsample_at(fp + a.off1, a.pitch1, a.cw, a.ch, a.hs, a.vs, x, y);
+                const int cr = jpegmath::upsample_at(fp + a.off2, a.pitch1, a.cw, a.ch, a.hs, a.vs, x, y);
+                jpegmath::ycc_to_rgb(yy, cb, cr, t);
+            }
+            px[j] = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16);
+            if (++x == a.W) {
+                x = 0;
+                if (++y == a.H) { y = 0; ++f; }
+            }
+        }
+    }
+    uint8_t* dst = rgb + q * 3;
+    if (DWORDS && npx == 4) {
+        uint32_t* d4 = reinterpret_cast<uint32_t*>(dst);
+        d4[0] = px[0] | (px[1] << 24);
+        d4[1] = (px[1] >> 8) | (px[2] << 16);
+        d4[2] = (px[2] >> 16) | (px[3] << 8);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < npx) {
+                dst[3 * j] = (uint8_t)px[j];
+                dst[3 * j + 1] = (uint8_t)(px[j] >> 8);
+                dst[3 * j + 2] = (uint8_t)(px[j] >> 16);
+            }
+    }
+}
+
+}  // namespace
+
+int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const JpegGeom& g, uint8_t* planes, uint8_t* rgb,
+                        hipStream_t s) {
+    TSTAR_REQUIRE(n > 0 && g.valid(), "jpeg_reconstruct_u8: n <= 0 or unsupported geometry");
+    TSTAR_REQUIRE((uintptr_t)coef % 16 == 0 && (uintptr_t)quant % 16 == 0 && (uintptr_t)planes % 8 == 0,
+                  "jpeg_reconstruct_u8: coefficient / table buffers need 16-byte, the plane workspace 8-byte alignment");
+    const size_t blocks = g.blocks();
+    TSTAR_REQUIRE(blocks * (size_t)n / kBlocksPerWg + 1 < 0x7fffffffull && (size_t)n * g.W * g.H / 1024 + 1 < 0x7fffffffull,
+                  "jpeg_reconstruct_u8: chunk too large for one launch");
+    for (int c = 0; c < g.ncomp; ++c) {
+        const int nblk = g.bw(c) * g.bh(c);
+        const size_t total = (size_t)nblk * n;
+        hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((total + kBlocksPerWg - 1) / kBlocksPerWg)), dim3(256), 0, s,
+                           coef + g.block_offset(c) * 64, blocks * 64, quant + 64 * c, planes + g.block_offset(c) * 64,
+                           g.plane_bytes(), nblk, g.bw(c), total);
+        TSTAR_HIP_CHECK(hipGetLastError());
+    }
+    ColorArgs a;
+    a.plane_frame_stride = g.plane_bytes();
+    a.off1 = g.ncomp == 3 ? g.block_offset(1) * 64 : 0;
+    a.off2 = g.ncomp == 3 ? g.block_offset(2) * 64 : 0;
+    a.pitch0 = g.bw(0) * 8;
+    a.pitch1 = g.ncomp == 3 ? g.bw(1) * 8 : 0;
+    a.W = g.W; a.H = g.H; a.ncomp = g.ncomp; a.hs = g.hs; a.vs = g.vs;
+    a.cw = g.cw(1); a.ch = g.ch(1);
+    const size_t total_px = (size_t)n * g.W * g.H;
+    const dim3 grid((unsigned)((total_px + 1023) / 1024));
+    if ((uintptr_t)rgb % 4 == 0) hipLaunchKernelGGL(jpeg_color_kernel<true>, grid, dim3(256), 0, s, planes, a, rgb, total_px);
+    else hipLaunchKernelGGL(jpeg_color_kernel<false>, grid, dim3(256), 0, s, planes, a, rgb, total_px);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    return TSTAR_OK;
+}
+
+}  // namespace tstar

@@ -1,0 +1,68 @@
+// Baseline JPEG decode front end, host half (HIP-free: also compiled alone by the CPU sanitizer build).
+//
+// Split of the work (DESIGN.md "JPEG decode stage"): the entropy stage below turns one JPEG into int16 coefficient
+// blocks + quantisation tables; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB are data-parallel and
+// run either in jpeg.hip (device) or in jpeg_reconstruct_host (the scalar reference, same integers).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace tstar {
+
+// status of one frame (also the return value of the single-frame calls)
+enum {
+    JPEG_OK = 0,
+    JPEG_MALFORMED = 1,      // broken or truncated stream: an error, never a partial picture
+    JPEG_UNCOVERED = 2,      // a JPEG this decoder does not cover (progressive, arithmetic, CMYK / RGB, other sampling) or does
+                             // not vouch for (stray bytes or no EOI after the last block, a block beyond the energy bound)
+    JPEG_GEOMETRY = 3,       // decodable, but width / height / components / sampling differ from the batch's geometry
+};
+
+// Geometry shared by every frame of a batch.  hs, vs: luma sampling factors (1x1, 2x1 or 2x2; chroma is always 1x1).
+struct JpegGeom {
+    int W, H, ncomp, hs, vs;
+    int mcux() const { return (W + 8 * hs - 1) / (8 * hs); }
+    int mcuy() const { return (H + 8 * vs - 1) / (8 * vs); }
+    // blocks per row / column of component c, padded to whole MCUs
+    int bw(int c) const { return mcux() * (c == 0 ? hs : 1); }
+    int bh(int c) const { return mcuy() * (c == 0 ? vs : 1); }
+    // true (unpadded) sample size of component c: ceil(W * h_c / hmax)
+    int cw(int c) const { return c == 0 ? W : (W + hs - 1) / hs; }
+    int ch(int c) const { return c == 0 ? H : (H + vs - 1) / vs; }
+    size_t blocks() const {
+        size_t b = 0;
+        for (int c = 0; c < ncomp; ++c) b += (size_t)bw(c) * bh(c);
+        return b;
+    }
+    size_t block_offset(int c) const {
+        size_t b = 0;
+        for (int k = 0; k < c; ++k) b += (size_t)bw(k) * bh(k);
+        return b;
+    }
+    size_t plane_bytes() const { return blocks() * 64; }          // u8 planes of whole blocks
+    // Subsampled chroma at most 2 samples wide (W <= 4) is excluded: libjpeg replicates such rows instead of running the
+    // triangle filter, and frames that small go to the general decoder.
+    bool valid() const {
+        return W > 0 && H > 0 && W <= 16384 && H <= 16384 && (ncomp == 1 || ncomp == 3) &&
+               ((hs == 1 && vs == 1) || (ncomp == 3 && hs == 2 && (vs == 1 || vs == 2) && cw(1) > 2));
+    }
+};
+
+// Header walk only.  JPEG_OK: *g filled.  JPEG_UNCOVERED: g->W, g->H filled when a frame header was seen (else 0).
+int jpeg_probe(const uint8_t* data, size_t len, JpegGeom* g, char* err, size_t errlen);
+
+// Entropy-decode one frame of geometry g: coef int16 [g.blocks()][64] (natural order, component after component,
+// block-raster within the component, padded to whole MCUs), quant u16 [3][64] (natural order; unused rows zero).
+int jpeg_entropy(const uint8_t* data, size_t len, const JpegGeom& g, int16_t* coef, uint16_t* quant, char* err, size_t errlen);
+
+// Byte offset one past the EOI of the JPEG that starts at data[pos] (found by walking marker segments and the stuffed
+// entropy data), or 0 when the stream is broken / ends first.
+size_t jpeg_frame_end(const uint8_t* data, size_t len, size_t pos);
+
+// Scalar reference of the device stage: coefficients + tables -> RGB u8 [H][W][3].  scratch: g.plane_bytes() bytes.
+void jpeg_reconstruct_host(const JpegGeom& g, const int16_t* coef, const uint16_t* quant, uint8_t* scratch, uint8_t* rgb);
+
+// threads a batch may use: min(16, CPUs this process is allowed to run on); `asked` > 0 lowers it further
+int jpeg_thread_allowance(int asked);
+
+}  // namespace tstar

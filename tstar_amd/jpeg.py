@@ -1,0 +1,456 @@
+"""JPEG decode front end: Motion-JPEG AVI, raw .mjpeg streams, folders / lists of JPEG frames -> the resident store.
+
+Replaces the decode half of read_frame_batch (reference interface_searcher.py:157-169) for intra-only JPEG video.
+Only the raw frames the searcher can ever ask for (int(sec * fps) for every logical second, :360) are read from disk.
+Each is entropy-decoded on a host thread pool (tstar_jpeg_entropy_batch: serial per scan, so it stays on the CPU) into
+pinned memory; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB run as HIP kernels (tstar_jpeg_reconstruct)
+straight into the store, the copy and kernels of one chunk overlapping the entropy decode of the next.  The result is
+byte-equal to Pillow / libjpeg-turbo.  Frames the kernels do not cover (progressive, arithmetic, CMYK, unusual sampling)
+are decoded by Pillow and copied in; ``FrameStore.decode_stats`` says how many frames went which way.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import mmap
+import os
+import re
+import struct
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+JPEG_EXT = (".jpg", ".jpeg")
+MJPEG_EXT = (".mjpeg", ".mjpg")
+OK, MALFORMED, UNCOVERED, GEOMETRY = 0, 1, 2, 3
+
+
+class NotMotionJpeg(ValueError):
+    """An AVI whose video stream is another codec: open_video may still hand it to decord / cv2 where a host has them."""
+
+
+def natural_key(name: str):
+    """f2.jpg sorts before f10.jpg: digit runs compare as numbers."""
+    return [(0, int(p), "") if p.isdigit() else (1, 0, p.lower()) for p in re.split(r"(\d+)", name) if p]
+
+
+# ------------------------------------------------------------------------------------------------ sources
+class JpegFrames:
+    """Random access to the JPEG bytes of a stream's raw frames."""
+
+    def __init__(self, name: str, fps: float, n_frames: int):
+        self.name, self.fps, self.n_frames = name, float(fps), int(n_frames)
+        if not self.fps > 0:
+            raise ValueError(f"Cannot open video file: {name} (frame rate {fps!r} is not positive)")
+
+    def read(self, i: int) -> bytes:
+        raise NotImplementedError
+
+    def label(self, i: int) -> str:
+        return f"{self.name} frame {i}"
+
+    def close(self) -> None:
+        pass
+
+
+class JpegList(JpegFrames):
+    """A list of file paths and / or ``bytes`` objects, one JPEG each."""
+
+    def __init__(self, items: Sequence, fps: float = 1.0, name: str = "<jpeg list>"):
+        super().__init__(name, fps, len(items))
+        self.items = list(items)
+
+    def read(self, i):
+        it = self.items[i]
+        if isinstance(it, (bytes, bytearray, memoryview)):
+            return bytes(it)
+        with open(it, "rb") as f:
+            return f.read()
+
+    def label(self, i):
+        it = self.items[i]
+        return f"{self.name}[{i}]" if isinstance(it, (bytes, bytearray, memoryview)) else str(it)
+
+
+def jpeg_folder(path: str, fps: float = 1.0) -> JpegList:
+    names = sorted((f for f in os.listdir(path) if f.lower().endswith(JPEG_EXT)), key=natural_key)
+    if not names:
+        raise ValueError(f"Cannot open video file: {path} (the folder holds no .jpg / .jpeg files)")
+    return JpegList([os.path.join(path, f) for f in names], fps, name=path)
+
+
+class _Mapped(JpegFrames):
+    """Frames as (offset, size) byte ranges of one memory-mapped file."""
+
+    def __init__(self, path, fps, ranges, fh, mm):
+        super().__init__(path, fps, len(ranges))
+        self.ranges, self._fh, self._mm = ranges, fh, mm
+
+    def read(self, i):
+        off, size = self.ranges[i]
+        return self._mm[off:off + size]
+
+    def close(self):
+        self._mm.close()
+        self._fh.close()
+
+
+def _map_file(path):
+    if not os.path.isfile(path) or os.path.getsize(path) == 0:
+        raise ValueError(f"Cannot open video file: {path}")
+    fh = open(path, "rb")
+    return fh, mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ)
+
+
+def mjpeg_stream(path: str, fps: float = 25.0) -> _Mapped:
+    """Concatenated JPEGs.  Frame boundaries come from walking each frame's marker segments and stuffed entropy data
+    (tstar_jpeg_frame_end), not from searching for FFD8: thumbnails inside APPn segments carry their own SOI / EOI."""
+    from . import _lib
+    lib = _lib.load()
+    fh, mm = _map_file(path)
+    try:
+        buf = np.frombuffer(mm, dtype=np.uint8)
+        base, size = buf.ctypes.data, len(mm)
+        ranges, pos = [], 0
+        while pos < size:
+            if mm[pos] != 0xFF:                       # padding between frames (some writers align them)
+                nxt = mm.find(b"\xff\xd8", pos)
+                if nxt < 0 and ranges and not mm[pos:].strip(b"\x00"):
+                    break                             # zero padding after the last frame
+                if nxt < 0 or mm[pos:nxt].strip(b"\x00"):
+                    raise ValueError(f"Cannot open video file: {path} (bytes that are no JPEG at offset {pos})")
+                pos = nxt
+            end = lib.tstar_jpeg_frame_end(base, size, pos)
+            if end == 0:
+                raise ValueError(f"Cannot open video file: {path} (frame {len(ranges)} at offset {pos} is broken or truncated)")
+            ranges.append((pos, end - pos))
+            pos = end
+        del buf
+        if not ranges:
+            raise ValueError(f"Cannot open video file: {path} (no JPEG frame)")
+        return _Mapped(path, fps, ranges, fh, mm)
+    except Exception:
+        try:
+            mm.close()
+        except BufferError:
+            pass
+        fh.close()
+        raise
+
+
+def _riff_chunks(mm, start, end):
+    """(fourcc, data offset, data size) of the chunks in [start, end); sizes are clipped to the enclosing range."""
+    p = start
+    while p + 8 <= end:
+        cid, size = mm[p:p + 4], struct.unpack_from("<I", mm, p + 4)[0]
+        if p + 8 + size > end:
+            size = end - p - 8                        # a truncated last chunk: what is there
+        yield cid, p + 8, size
+        p += 8 + size + (size & 1)
+
+
+def avi_mjpeg(path: str) -> _Mapped:
+    """An AVI (RIFF) file whose video stream is Motion-JPEG.  Rate and stream number from ``strh`` / ``avih``, the frames'
+    byte ranges from ``idx1`` when present, else by walking the ``movi`` list.  A zero-length video chunk (a dropped frame)
+    repeats the previous one.  OpenDML files (``AVIX`` extension segments, above 1 GiB) are refused by name."""
+    fh, mm = _map_file(path)
+
+    def bad(why):
+        return ValueError(f"Cannot open video file: {path} ({why})")
+
+    try:
+        size = len(mm)
+        if size < 12 or mm[0:4] != b"RIFF" or mm[8:12] != b"AVI ":
+            raise bad("not a RIFF AVI file")
+        riff_end = min(size, 8 + struct.unpack_from("<I", mm, 4)[0])
+        if riff_end + 12 <= size and mm[riff_end:riff_end + 4] == b"RIFF" and mm[riff_end + 8:riff_end + 12] == b"AVIX":
+            raise bad("OpenDML AVI with AVIX extension segments is not supported")
+        usec, vstream, rate, scale, fourcc, movi, idx1, n_streams = 0, None, 0, 0, None, None, None, 0
+        for cid, off, sz in _riff_chunks(mm, 12, riff_end):
+            if cid == b"LIST" and sz >= 4 and mm[off:off + 4] == b"hdrl":
+                for c2, o2, s2 in _riff_chunks(mm, off + 4, off + sz):
+                    if c2 == b"avih" and s2 >= 4:
+                        usec = struct.unpack_from("<I", mm, o2)[0]
+                    elif c2 == b"LIST" and s2 >= 4 and mm[o2:o2 + 4] == b"strl":
+                        kind, handler, sc, rt, comp = None, b"", 0, 0, None
+                        for c3, o3, s3 in _riff_chunks(mm, o2 + 4, o2 + s2):
+                            if c3 == b"strh" and s3 >= 28:
+                                kind, handler = mm[o3:o3 + 4], mm[o3 + 4:o3 + 8]
+                                sc, rt = struct.unpack_from("<II", mm, o3 + 20)
+                            elif c3 == b"strf" and s3 >= 20:
+                                comp = mm[o3 + 16:o3 + 20]
+                        if kind == b"vids" and vstream is None:
+                            vstream, scale, rate, fourcc = n_streams, sc, rt, (comp if comp is not None else handler)
+                        n_streams += 1
+            elif cid == b"LIST" and sz >= 4 and mm[off:off + 4] == b"movi":
+                movi = (off, sz)
+            elif cid == b"idx1":
+                idx1 = (off, sz)
+        if vstream is None or movi is None:
+            raise bad("no video stream or no movi list")
+        if fourcc.upper() != b"MJPG":
+            raise NotMotionJpeg(f"Cannot open video file: {path} (video codec {fourcc.decode('latin-1')!r}: only Motion-JPEG "
+                                f"('MJPG') AVI is decoded here)")
+        fps = rate / scale if rate and scale else (1e6 / usec if usec else 0.0)
+        if not fps > 0:
+            raise bad("no frame rate in strh / avih")
+        ids = (b"%02ddc" % vstream, b"%02ddb" % vstream)
+        ranges: List = []
+
+        def add(off, sz):
+            if sz == 0:
+                if ranges:
+                    ranges.append(ranges[-1])         # dropped frame: the previous picture stays on screen
+            else:
+                ranges.append((off, sz))
+
+        movi_off, movi_sz = movi
+        if idx1 is not None and idx1[1] >= 16:
+            entries = [struct.unpack_from("<4sIII", mm, idx1[0] + 16 * k) for k in range(idx1[1] // 16)]
+            # offsets count from the 'movi' fourcc (the usual reading) or from the start of the file (some muxers): take
+            # the one under which the first entry lands on a chunk header carrying its own id
+            rel = None
+            for cand in (movi_off, 0):
+                o = cand + entries[0][2]
+                if o + 8 <= size and mm[o:o + 4] == entries[0][0]:
+                    rel = cand
+                    break
+            if rel is None:
+                raise bad("idx1 offsets point at no chunk")
+            for cid, _flags, o, sz in entries:
+                if cid in ids:
+                    o += rel
+                    if o + 8 + sz > size or mm[o:o + 4] != cid:
+                        raise bad(f"idx1 entry for frame {len(ranges)} points outside the file or at another chunk")
+                    add(o + 8, sz)
+        else:
+            def walk(start, end):
+                for cid, o, sz in _riff_chunks(mm, start, end):
+                    if cid == b"LIST" and sz >= 4 and mm[o:o + 4] == b"rec ":
+                        walk(o + 4, o + sz)
+                    elif cid in ids:
+                        add(o, sz)
+            walk(movi_off + 4, movi_off + movi_sz)
+        if not ranges:
+            raise bad("the video stream holds no frame")
+        return _Mapped(path, fps, ranges, fh, mm)
+    except Exception:
+        mm.close()
+        fh.close()
+        raise
+
+
+def open_source(video, fps: Optional[float] = None) -> Optional[JpegFrames]:
+    """The JPEG source ``video`` names, or None when it is none of: a folder of .jpg / .jpeg files, a list of paths /
+    bytes, a .mjpeg / .mjpg stream, an .avi file."""
+    if isinstance(video, JpegFrames):
+        return video
+    if isinstance(video, (list, tuple)):
+        return JpegList(video, 1.0 if fps is None else fps)
+    if not isinstance(video, (str, os.PathLike)):
+        return None
+    path = os.fspath(video)
+    if os.path.isdir(path):
+        return jpeg_folder(path, 1.0 if fps is None else fps)
+    low = path.lower()
+    if low.endswith(MJPEG_EXT):
+        return mjpeg_stream(path, 25.0 if fps is None else fps)
+    if low.endswith(".avi"):
+        if fps is not None:
+            raise ValueError(f"Cannot open video file: {path} (an AVI carries its own frame rate; fps= is for frame folders and .mjpeg streams)")
+        return avi_mjpeg(path)
+    return None
+
+
+# ------------------------------------------------------------------------------------------------ decode
+def probe(data: bytes):
+    """(status, (W, H, ncomp, hs, vs), message)."""
+    from . import _lib
+    lib = _lib.load()
+    info = (C.c_int32 * 5)()
+    rc = lib.tstar_jpeg_probe(data, len(data), info)
+    msg = lib.tstar_last_error().decode() if rc else ""
+    return rc, tuple(info), msg
+
+
+def _sizes(geom):
+    from . import _lib
+    out = (C.c_size_t * 2)()
+    _lib.check(_lib.load().tstar_jpeg_sizes(*geom, out), "tstar_jpeg_sizes")
+    return int(out[0]), int(out[1])
+
+
+def entropy_batch(datas: Sequence[bytes], geom, coef: np.ndarray, quant: np.ndarray, threads: int = 0):
+    """Entropy-decode ``datas`` into coef int16 [>= n, blocks * 64] / quant uint16 [>= n, 192] -> (status int32 [n], message)."""
+    from . import _lib
+    lib = _lib.load()
+    n = len(datas)
+    blocks, _ = _sizes(geom)
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size >= n * blocks * 64
+    assert quant.dtype == np.uint16 and quant.flags.c_contiguous and quant.size >= n * 192
+    ptrs = (C.c_char_p * n)(*datas)
+    lens = (C.c_size_t * n)(*[len(d) for d in datas])
+    status = np.full(n, -1, dtype=np.int32)
+    rc = lib.tstar_jpeg_entropy_batch(ptrs, lens, n, *geom, coef.ctypes.data, quant.ctypes.data, threads, status.ctypes.data)
+    if rc not in (0, 3):
+        _lib.check(rc, "tstar_jpeg_entropy_batch")
+    return status, (lib.tstar_last_error().decode() if rc else "")
+
+
+def _pillow_rgb(data: bytes, label: str) -> np.ndarray:
+    import io
+    from PIL import Image
+    try:
+        with Image.open(io.BytesIO(data)) as im:
+            return np.array(im.convert("RGB"), dtype=np.uint8)
+    except Exception as e:
+        raise ValueError(f"Cannot open video file: {label} ({e})")
+
+
+def decode_host(datas: Sequence[bytes], threads: int = 0) -> np.ndarray:
+    """JPEG bytes -> uint8 [n,H,W,3] through the host path alone (entropy stage + scalar reference of the kernels); every
+    frame must be one the decoder covers, of the first frame's geometry.  Raises ValueError naming the frame otherwise."""
+    from . import _lib
+    datas = list(datas)
+    rc, geom, msg = probe(datas[0])
+    if rc:
+        raise ValueError(f"JPEG frame 0: {msg}")
+    blocks, _ = _sizes(geom)
+    n = len(datas)
+    coef = np.empty((n, blocks * 64), dtype=np.int16)
+    quant = np.empty((n, 192), dtype=np.uint16)
+    status, msg = entropy_batch(datas, geom, coef, quant, threads)
+    if status.any():
+        raise ValueError(f"JPEG {msg}")
+    W, H = geom[0], geom[1]
+    out = np.empty((n, H, W, 3), dtype=np.uint8)
+    _lib.check(_lib.load().tstar_jpeg_reconstruct_host(coef.ctypes.data, quant.ctypes.data, n, *geom, out.ctypes.data, threads),
+               "tstar_jpeg_reconstruct_host")
+    return out
+
+
+def wanted_frames(n_frames: int, fps: float):
+    """Raw frame of every logical second (interface_searcher.py:360)."""
+    return [int(sec * fps) for sec in range(int(n_frames / fps))]
+
+
+def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None, threads: int = 0):
+    """Decode the wanted frames of ``src`` into a FrameStore (RGB u8 [N,H,W,3] on ``device``)."""
+    import torch
+    from . import _lib
+    from .video import FrameStore
+    lib = _lib.load()
+    want = wanted_frames(src.n_frames, src.fps)
+    if not want:
+        raise ValueError(f"Cannot open video file: {src.name} (shorter than one second)")
+    on_gpu = not str(device).startswith("cpu")
+
+    # the first wanted frame fixes the picture size; the first frame the kernels cover fixes the device geometry
+    first = src.read(want[0])
+    rc, info, msg = probe(first)
+    if rc == MALFORMED:
+        raise ValueError(f"Cannot open video file: {src.label(want[0])} ({msg})")
+    if rc == OK:
+        W, H = info[0], info[1]
+    else:
+        H, W = _pillow_rgb(first, src.label(want[0])).shape[:2]
+    n_sec = len(want)
+    store = torch.empty((n_sec, H, W, 3), dtype=torch.uint8, device=device)
+    stats = {"device": 0, "host": 0, "pillow": 0}
+    geom = None
+    bufs = None
+    side = torch.cuda.Stream(device=device) if on_gpu else None
+    done = [None, None]
+
+    def alloc(g):
+        blocks, plane_bytes = _sizes(g)
+        c = chunk if chunk else max(1, min(64, (48 << 20) // (blocks * 128)))
+        c = min(c, n_sec)
+        b = {"chunk": c, "blocks": blocks}
+        if on_gpu:
+            b["coef"] = [torch.empty((c, blocks * 64), dtype=torch.int16).pin_memory() for _ in range(2)]
+            b["quant"] = [torch.empty((c, 192), dtype=torch.int16).pin_memory() for _ in range(2)]
+            b["d_coef"] = [torch.empty((c, blocks * 64), dtype=torch.int16, device=device) for _ in range(2)]
+            b["d_quant"] = [torch.empty((c, 192), dtype=torch.int16, device=device) for _ in range(2)]
+            b["planes"] = torch.empty((c, plane_bytes), dtype=torch.uint8, device=device)   # one: the side stream runs chunks in order
+        else:
+            b["coef"] = [torch.empty((c, blocks * 64), dtype=torch.int16)]
+            b["quant"] = [torch.empty((c, 192), dtype=torch.int16)]
+        return b
+
+    s0, ci = 0, 0
+    step = chunk if chunk else None
+    try:
+        while s0 < n_sec:
+            if geom is None:
+                # no covered frame seen yet: look one frame ahead at a time (each goes to Pillow until one is covered)
+                data = first if s0 == 0 else src.read(want[s0])
+                rc, info, msg = probe(data)
+                if rc == OK:
+                    if (info[0], info[1]) != (W, H):
+                        raise ValueError(f"Cannot open video file: {src.label(want[s0])} is {info[0]}x{info[1]}, the first frame is {W}x{H}")
+                    geom = info
+                    bufs = alloc(geom)
+                    step = bufs["chunk"]
+                    continue
+                if rc == MALFORMED:
+                    raise ValueError(f"Cannot open video file: {src.label(want[s0])} ({msg})")
+                arr = _pillow_rgb(data, src.label(want[s0]))
+                if arr.shape != (H, W, 3):
+                    raise ValueError(f"Cannot open video file: {src.label(want[s0])} is {arr.shape[1]}x{arr.shape[0]}, the first frame is {W}x{H}")
+                store[s0].copy_(torch.from_numpy(arr))
+                stats["pillow"] += 1
+                s0 += 1
+                continue
+            idx = want[s0:s0 + step]
+            n = len(idx)
+            b = ci & 1 if on_gpu else 0
+            if on_gpu and done[b] is not None:
+                done[b].synchronize()                     # the pinned buffers' previous copy has left
+            datas = [first if (s0 + j == 0) else src.read(fi) for j, fi in enumerate(idx)]
+            coef, quant = bufs["coef"][b], bufs["quant"][b]
+            status, _ = entropy_batch(datas, geom, coef.numpy(), quant.numpy().view(np.uint16), threads)
+            fallback = []
+            for j in np.nonzero(status)[0]:
+                j = int(j)
+                label = src.label(idx[j])
+                if status[j] == MALFORMED:
+                    one_c = np.empty((1, bufs["blocks"] * 64), dtype=np.int16)
+                    _, m = entropy_batch([datas[j]], geom, one_c, np.empty((1, 192), dtype=np.uint16), 1)
+                    raise ValueError(f"Cannot open video file: {label} ({m.split(': ', 2)[-1]})")
+                if status[j] == GEOMETRY:
+                    _, inf, _ = probe(datas[j])
+                    if (inf[0], inf[1]) != (W, H):
+                        raise ValueError(f"Cannot open video file: {label} is {inf[0]}x{inf[1]}, the first frame is {W}x{H}")
+                arr = _pillow_rgb(datas[j], label)          # uncovered, or covered sampling other than the batch's: exact, on the host
+                if arr.shape != (H, W, 3):
+                    raise ValueError(f"Cannot open video file: {label} is {arr.shape[1]}x{arr.shape[0]}, the first frame is {W}x{H}")
+                fallback.append((j, arr))
+            if on_gpu:
+                with torch.cuda.stream(side):
+                    bufs["d_coef"][b][:n].copy_(coef[:n], non_blocking=True)
+                    bufs["d_quant"][b][:n].copy_(quant[:n], non_blocking=True)
+                    _lib.check(lib.tstar_jpeg_reconstruct(bufs["d_coef"][b].data_ptr(), bufs["d_quant"][b].data_ptr(), n, *geom,
+                                                          bufs["planes"].data_ptr(), store[s0:s0 + n].data_ptr(), side.cuda_stream),
+                               "tstar_jpeg_reconstruct")
+                    done[b] = torch.cuda.Event()
+                    done[b].record(side)
+                    for j, arr in fallback:               # after the kernels, which wrote whatever the stale coefficients gave into these slots
+                        store[s0 + j].copy_(torch.from_numpy(arr))
+            else:
+                out = store[s0:s0 + n].numpy()
+                _lib.check(lib.tstar_jpeg_reconstruct_host(coef.data_ptr(), quant.data_ptr(), n, *geom, out.ctypes.data, threads),
+                           "tstar_jpeg_reconstruct_host")
+                for j, arr in fallback:
+                    out[j] = arr
+            stats["device" if on_gpu else "host"] += n - len(fallback)
+            stats["pillow"] += len(fallback)
+            s0 += n
+            ci += 1
+    finally:
+        # also on the way out with an error: the side stream may still be writing the previous chunk into the store, the
+        # planes and the staged coefficients, and the allocator must not hand those blocks out before it is done
+        if side is not None:
+            side.synchronize()
+    st = FrameStore(store, src.fps, src.n_frames, name=src.name)
+    st.decode_stats = stats
+    return st

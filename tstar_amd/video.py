@@ -8,8 +8,10 @@ frame count (:60-65).  Here a video is decoded ONCE into a uint8 tensor
 outside the hot path (SURVEY.md 8f "next" row 3): raw 4:2:0 files (YUV4MPEG2) are
 read and repacked on the device here (``load_y4m``); the compressed sequences Pillow
 decodes in this image (animated GIF / WebP, AVIF sequences = AV1) go through
-``load_pillow_sequence``; other compressed files need decord or cv2 on the host
-(rocDecode / FFmpeg are not in this build), synthetic videos need nothing.
+``load_pillow_sequence``; Motion-JPEG (.avi / .mjpeg) and folders or lists of JPEG frames are
+entropy-decoded on the host and reconstructed by HIP kernels (``tstar_amd.jpeg``); other compressed
+files need decord or cv2 on the host (rocDecode / FFmpeg are not in this build), synthetic videos
+need nothing.
 """
 from __future__ import annotations
 
@@ -80,6 +82,7 @@ class FrameStore:
         self.raw_total_frames = int(raw_total_frames if raw_total_frames is not None
                                     else round(frames.shape[0] * self.raw_fps))
         self.name = name
+        self.decode_stats = None      # JPEG sources: {"device": n, "host": n, "pillow": n} frames decoded by each path
 
     @property
     def num_seconds(self) -> int:
@@ -159,12 +162,12 @@ def synthetic_video_nv12(n_frames: int = 3600, H: int = 360, W: int = 640, seed:
     return FrameStore(out, raw_fps, None, name=f"synthetic://n={n_frames},h={H},w={W},seed={seed},fmt=nv12", fmt="nv12")
 
 
-def load_video_frames(video, num_frames: int = 8) -> np.ndarray:
+def load_video_frames(video, num_frames: int = 8, fps: Optional[float] = None) -> np.ndarray:
     """The grounder's uniform frame loader (/root/reference/TStar/utilites.py:40-81): frames at raw
     indices floor(i * total / num_frames), RGB uint8 [n,H,W,3] -- served from the resident store (the
-    stored frame nearest in time to each raw index when raw_fps != 1)."""
+    stored frame nearest in time to each raw index when raw_fps != 1).  ``fps``: as ``open_video``."""
     import math
-    st = open_video(video)
+    st = open_video(video) if fps is None else open_video(video, fps=fps)
     total = st.raw_total_frames
     if total == 0:
         raise ValueError("Video has zero frames or could not retrieve frame count.")
@@ -336,12 +339,27 @@ def load_pillow_sequence(path: str, device: str = "cuda", chunk: int = 64) -> Fr
 _SYN = re.compile(r"^synthetic://")
 
 
-def open_video(video, device: str = "cuda") -> FrameStore:
-    """``video``: a FrameStore, a ``synthetic://n=..,h=..,w=..,seed=..,fps=..`` URL, or a file path
-    (decoded at native rate through decord, else cv2; both absent -> ValueError like the
-    reference's ``Cannot open video file`` at interface_searcher.py:61-62)."""
+def open_video(video, device: str = "cuda", fps: Optional[float] = None) -> FrameStore:
+    """``video``: a FrameStore, a ``synthetic://n=..,h=..,w=..,seed=..,fps=..`` URL, a folder of .jpg / .jpeg frames or a
+    list of JPEG paths / bytes (``fps`` frames per second, default 1), a .mjpeg / .mjpg stream (``fps`` default 25), a
+    Motion-JPEG .avi, or another file path (.y4m, the Pillow sequences; else decoded at native rate through decord, else
+    cv2; both absent -> ValueError like the reference's ``Cannot open video file`` at interface_searcher.py:61-62)."""
     if isinstance(video, FrameStore):
         return video
+    other_codec = None
+    if not (isinstance(video, str) and _SYN.match(video)):
+        from . import jpeg
+        try:
+            src = jpeg.open_source(video, fps)
+        except jpeg.NotMotionJpeg as e:               # an AVI with another codec: decord / cv2 below, where a host has them
+            src, other_codec = None, e
+        if src is not None:
+            try:
+                return jpeg.load_jpeg(src, device)
+            finally:
+                src.close()
+    if fps is not None:
+        raise ValueError("open_video: fps= applies to JPEG frame folders / lists and .mjpeg streams only")
     if isinstance(video, str) and _SYN.match(video):
         kv = dict(p.split("=") for p in video[len("synthetic://"):].split(",") if p)
         if kv.get("fmt", "rgb") == "nv12":
@@ -374,6 +392,8 @@ def open_video(video, device: str = "cuda") -> FrameStore:
     try:
         import cv2  # type: ignore
     except ImportError:
+        if other_codec is not None:
+            raise other_codec
         raise ValueError(f"Cannot open video file: {video} (neither decord nor cv2 is importable; "
                          "pass a tstar_amd.video.FrameStore or a synthetic:// URL)")
     cap = cv2.VideoCapture(video)
