@@ -202,6 +202,16 @@ int tstar_yolo_detect(tstar_yolo* h, const uint8_t* d_images, int B, int H, int 
                       const int32_t* h_image_query_set, float score_threshold, int max_dets, float* d_det_scores,
                       int32_t* d_det_labels, float* d_det_boxes, int32_t* d_n_det, double* d_cell_conf, uint32_t* d_cell_mask,
                       float* d_dense_scores, float* d_dense_boxes, void* stream);
+/* Diagnostic (an added entry; tstar_abi_version() stays 3): the tail of tstar_yolo_detect -- DFL decode + contrastive scores + candidate
+ * collection per head level, the nms_pre cut / sort / class-aware NMS / wrapper threshold / top-k, the dense copies and the
+ * cell loop; the same launch sequence, one internal function -- on caller-supplied head tensors instead of the network's:
+ * HOST arrays of n_levels DEVICE pointers, level l holding the embedding f32 [B * size_l^2, 512] and the DFL logits
+ * f32 [B * size_l^2, 64] (side * 16 + bin; sides left, top, right, bottom), rows in image-major, row-major anchor order.
+ * n_levels must equal the handle's; H, W only set the letterbox geometry and the clamp.  Everything else as in detect. */
+int tstar_yolo_postprocess(tstar_yolo* h, const float* const* d_level_embed, const float* const* d_level_dfl, int n_levels, int B, int H,
+                           int W, int grid_rows, int grid_cols, const int32_t* h_image_query_set, float score_threshold, int max_dets,
+                           float* d_det_scores, int32_t* d_det_labels, float* d_det_boxes, int32_t* d_n_det, double* d_cell_conf,
+                           uint32_t* d_cell_mask, float* d_dense_scores, float* d_dense_boxes, void* stream);
 
 /* ------------------------------------------------------------------ ingest (S1-S3, S8) */
 /* The resident decoded video d_video is u8 [N,H,W,3] RGB (nv12 = 0) or NV12 u8 [N, H*3/2, W] (nv12 = 1:

@@ -138,3 +138,52 @@ def test_round3_entry_points_validate_their_arguments(env):
     assert n.value == 2 and fl.value == 2 * 2.0 * 256 * 128 * 64
     assert by.value == 2 * (4.0 * 256 * 64 + 2.0 * 128 * 64 + 4.0 * 256 * 128)            # A (f32) + W (bf16) + C, per launch
     assert lib.tstar_comm_available() == 0                                                # torch's RCCL is loadable on a GPU box
+
+
+def test_yolo_postprocess_argument_validation(env):
+    """tstar_yolo_postprocess checks what tstar_yolo_detect checks, plus its own level arrays."""
+    L, lib, _ = env
+    from tstar_amd import yolo_world as Y
+    from tstar_amd.yolo import YoloDetector
+    det = YoloDetector(Y.synthetic_state_dict(2, "s"), "s", max_batch=1)
+    t = np.zeros((2, 512), np.float32)
+    t[0, 0] = t[1, 1] = 1.0
+    emb = [torch.zeros((n * n, 512), device="cuda") for n in (80, 40, 20)]
+    dfl = [torch.zeros((n * n, 64), device="cuda") for n in (80, 40, 20)]
+    with pytest.raises(L.TStarHipError, match="no text features installed"):
+        det.postprocess(emb, dfl, 1, 640, 640)
+    det.set_text_feats(t, [1.0, 0.5])
+    for bad, msg in ((dict(max_dets=301), "max_dets must be in 1..300"),
+                     (dict(grid_rows=100, grid_cols=100), "1..4096 cells"), (dict(image_sets=[64]), "query_set must be in 0..63"),
+                     (dict(image_sets=[5]), "no text features installed")):
+        with pytest.raises(L.TStarHipError, match=msg):
+            det.postprocess(emb, dfl, 1, 640, 640, **bad)
+    with pytest.raises(L.TStarHipError, match="outside the letterbox geometry"):
+        det.postprocess(emb, dfl, 1, 2, 4000)
+    with pytest.raises(ValueError, match="one slot per image"):
+        det.postprocess(emb, dfl, 1, 640, 640, image_sets=[0, 0])
+    with pytest.raises(ValueError, match="level tensors"):
+        det.postprocess(emb, [dfl[0], dfl[1], dfl[2][:-16]], 1, 640, 640)
+    with pytest.raises(ValueError, match="per head level"):
+        det.postprocess(emb[:2], dfl[:2], 1, 640, 640)
+    # the C entry itself: null arguments, a wrong level count, a null level tensor
+    out = [torch.zeros(4, device="cuda") for _ in range(3)] + [torch.zeros(1, dtype=torch.int32, device="cuda")]
+    pe = (C.c_void_p * 3)(*[e.data_ptr() for e in emb])
+    pd = (C.c_void_p * 3)(*[d.data_ptr() for d in dfl])
+    tail = (1, 640, 640, 1, 1, None, C.c_float(0.12), 1, out[0].data_ptr(), out[3].data_ptr(), out[1].data_ptr(), out[3].data_ptr(), None, None, None, None, None)
+    assert lib.tstar_yolo_postprocess(det._h, None, pd, 3, *tail) == 1 and b"null argument" in lib.tstar_last_error()
+    assert lib.tstar_yolo_postprocess(None, pe, pd, 3, *tail) == 1
+    assert lib.tstar_yolo_postprocess(det._h, pe, pd, 2, *tail) == 1 and b"n_levels" in lib.tstar_last_error()
+    hole = (C.c_void_p * 3)(emb[0].data_ptr(), None, emb[2].data_ptr())
+    assert lib.tstar_yolo_postprocess(det._h, hole, pd, 3, *tail) == 1 and b"null level tensor" in lib.tstar_last_error()
+    zero = list(tail)
+    zero[7] = 0
+    assert lib.tstar_yolo_postprocess(det._h, pe, pd, 3, *zero) == 1 and b"max_dets must be in 1..300" in lib.tstar_last_error()
+    labels = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ok = list(tail)
+    ok[9] = labels.data_ptr()
+    assert lib.tstar_yolo_postprocess(det._h, pe, pd, 3, *ok) == 0                          # still healthy afterwards
+    r = det.postprocess(emb, dfl, 1, 640, 640)
+    torch.cuda.synchronize()
+    assert int(r.n_kept[0]) == 0 and int(r.labels[0, -1]) == -1
+    det.close()

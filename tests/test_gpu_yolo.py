@@ -32,7 +32,7 @@ def yolo():
     return dict(det=det, sd=sd, txt=txt)
 
 
-@pytest.mark.parametrize("H,W,rows,cols,B", [(380, 800, 4, 4, 3), (285, 600, 1, 1, 2), (1520, 3200, 16, 16, 1), (360, 640, 1, 1, 1)])
+@pytest.mark.parametrize("H,W,rows,cols,B", [(380, 800, 4, 4, 3), (285, 600, 1, 1, 2), (1520, 3200, 16, 16, 1), (360, 640, 1, 1, 1), (800, 380, 4, 4, 1)])
 def test_detector_vs_oracle(yolo, H, W, rows, cols, B):
     from oracle import yolo_ref as R, searcher_ref as S
     imgs = np.stack([GU.detector_test_image(50 + b, H, W) for b in range(B)])
@@ -68,6 +68,34 @@ def test_detector_vs_oracle(yolo, H, W, rows, cols, B):
             for nme in names[cell]:
                 want |= 1 << [t[0] for t in texts].index(nme)
             assert mask[cell] == want
+
+
+@pytest.mark.parametrize("thr,max_dets", [(0.0005, 300), (0.12, 300)])
+def test_wide_open_wrapper_through_the_forward(yolo, thr, max_dets):
+    """The public path with the wrapper's knobs at their far ends, teacher-forced against the LITERAL statement of the
+    post-process (tests/yolo_post_util.py: no shortcut at the wrapper threshold or at 300).  With score_threshold = 0.0005
+    every candidate of the synthetic detector passes it: more than 16384 keys, the global-memory sort of sort_nms_kernel, and
+    more than 30000, the nms_pre cut, through the real forward.  max_dets = 300 is the ABI's limit."""
+    import yolo_post_util as U
+    from oracle import yolo_ref as R
+    H, W = 380, 800
+    imgs = np.stack([GU.detector_test_image(50 + b, H, W) for b in range(2)])
+    r = yolo["det"].detect(torch.from_numpy(imgs).cuda(), 4, 4, score_threshold=thr, max_dets=max_dets, want_dense=True)
+    torch.cuda.synchronize()
+    dsc, dbx = r.dense_scores.cpu().numpy(), r.dense_boxes.cpu().numpy()
+    for b in range(2):
+        lit = U.literal_select(dsc[b], dbx[b], (H, W), wrapper_thr=thr, max_dets=max_dets)
+        assert U.same_selection(lit, R.select(dsc[b], dbx[b], (H, W), wrapper_thr=thr, max_dets=max_dets))
+        reach = U.reach(lit, thr)
+        print(f"threshold {thr} image {b}: {reach}")
+        if thr < 0.001:
+            assert reach["candidates"] > 30000 and reach["above"] > 16384
+        n = int(r.n_kept[b])
+        assert n == len(lit["scores"]) and n > 50
+        assert np.array_equal(r.scores[b, :n].cpu().numpy(), lit["scores"])
+        assert np.array_equal(r.labels[b, :n].cpu().numpy(), lit["labels"])
+        assert np.array_equal(r.boxes[b, :n].cpu().numpy(), lit["xyxy"])
+        assert (r.labels[b, n:].cpu().numpy() == -1).all() and (r.scores[b, n:].cpu().numpy() == 0).all()
 
 
 @pytest.mark.parametrize("scale", ["s", "m", "x", "xl"])

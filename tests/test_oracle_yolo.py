@@ -118,3 +118,76 @@ def test_nms_and_selection_semantics():
     assert r["anchors"].tolist() == [1, 2, 3]
     r = R.select(sc, boxes, (8, 8))                                  # clamp to the image
     assert r["xyxy"].max() <= 8
+
+
+def _params():
+    import yolo_post_util as U
+    return U.level_params(Y.synthetic_state_dict(2, "s"))
+
+
+def test_literal_decode_statements_agree_on_exact_inputs():
+    """One-hot and equal-weight DFL logits decode to exact integers in float64 and in the float32 statement alike; the crafted
+    boxes of the nms_pre scenario are where its docstring says."""
+    import yolo_post_util as U
+    sc = U.scenario_cut()
+    p = _params()
+    e, d = U.embeds_from_logits(sc["logits"][:1], p), U.dfl_levels(sc["dfl"][:1])
+    s64, b64 = U.decode_f64(e, d, p, 640, 640, 4)
+    s32, b32 = U.decode_f32(e, d, p, 640, 640, 4)
+    assert np.array_equal(b64, b32.astype(np.float64)) and np.abs(s64 - s32).max() < 1e-6
+    assert b32[U.CUT_P].tolist() == [204, 204, 664, 664] and b32[U.CUT_Q].tolist() == [-464, -464, 16, 16]
+    assert b32[U.CUT_PIN, 2] == 667 and b32.max() == 756 and b32[U.CUT_BIG[0], 2] == 756
+
+
+@pytest.mark.parametrize("name", ["few", "cut", "fallback", "greedy", "ties", "classes", "cells"])
+def test_literal_selection_equals_the_oracle_selection(name):
+    """oracle.yolo_ref.select stops the greedy pass at the wrapper threshold and at 300 survivors (the kernel's shortcuts); the
+    literal statement (tests/yolo_post_util.py) does neither.  Bit-equal detections on every crafted scenario of the GPU
+    post-process tests, from dense float32 scores / boxes of the float32 statement, at the scenario's own threshold and
+    max_dets and at the wrapper defaults of the other regime (a threshold below score_thr; top-50)."""
+    import yolo_post_util as U
+    from oracle import yolo_ref as R
+    sc = U.SCENARIOS[name]()
+    p = _params()
+    B = sc["logits"].shape[0]
+    full = 0
+    for b in range(B):
+        ds, db = U.scenario_dense_f32(sc, p, b)
+        runs = [(sc["thr"], sc["max_dets"])]
+        if name in ("few", "ties", "classes"):
+            runs += [(0.0005, 300), (0.12, 50)]
+        for thr, md in runs:
+            lit = U.literal_select(ds, db, (sc["H"], sc["W"]), wrapper_thr=thr, max_dets=md)
+            sel = R.select(ds, db, (sc["H"], sc["W"]), wrapper_thr=thr, max_dets=md)
+            assert U.same_selection(lit, sel), (name, b, thr, md)
+            assert lit["n_candidates"] == sel["n_candidates"]
+            full += lit["n_sorted"]
+    print(name, "candidates through the literal pass:", full)
+
+
+def test_crafted_scenarios_reach_their_paths_on_the_cpu():
+    """The reach each scenario is built for, from the float32 statement (the GPU tests assert the same from read-back data)."""
+    import yolo_post_util as U
+    from oracle import yolo_ref as R
+    p = _params()
+    sc = U.scenario_cut()
+    for b in range(2):
+        ds, db = U.scenario_dense_f32(sc, p, b)
+        lit = U.literal_select(ds, db, (640, 640), max_dets=300)
+        assert lit["n_candidates"] == (33600, 33597)[b] and lit["off_unit"] == 668.0 and db.max() == U.CUT_MAX[b]
+        want = [(U.CUT_P, 0), (U.CUT_PIN, 0)] if b == 0 else [(U.CUT_P, 0), (U.CUT_P2, 2), (U.CUT_Q2, 3), (U.CUT_PIN, 0)]
+        assert [(int(a), int(c)) for a, c in zip(lit["anchors"], lit["labels"])] == want
+        nocut = R.select(ds, db, (640, 640), max_dets=300, nms_pre=10 ** 9)
+        assert (U.CUT_Q, 1) in [(int(a), int(c)) for a, c in zip(nocut["anchors"], nocut["labels"])]
+    assert lit["sorted_scores"][29999] == lit["sorted_scores"][29003] < lit["sorted_scores"][29002] and np.count_nonzero(ds == lit["sorted_scores"][29999]) == 1993
+    assert (int(lit["sorted_anchors"][29999]), int(lit["sorted_labels"][29999])) == (U.CUT_LAST, 3) and db[U.CUT_LAST, 3] == 667
+    for n_pre, missing in ((29999, (U.CUT_Q2, 3)), (30001, None)):                # the cut off by one either way changes the detections
+        off = U.literal_select(ds, db, (640, 640), max_dets=300, nms_pre=n_pre)
+        got = [(int(a), int(c)) for a, c in zip(off["anchors"], off["labels"])]
+        assert got != want and (missing is None or missing not in got) and (missing is not None or (U.CUT_Q, 1) in got)
+    sc = U.scenario_greedy()
+    for b in range(2):
+        ds, db = U.scenario_dense_f32(sc, p, b)
+        lit = U.literal_select(ds, db, (640, 640), max_dets=300)
+        r = U.reach(lit, 0.12)
+        assert r["survivors"] == 300 and r["survivors_available"] == 400 and r["examined"] > 2000 and r["above"] <= 16384, r

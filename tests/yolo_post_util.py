@@ -1,0 +1,438 @@
+"""Helpers of the YOLO post-process tests (tests/test_oracle_yolo.py on the CPU, tests/test_gpu_yolo_postprocess.py on the GPU).
+
+* ``literal_select``: mmyolo's ``predict_by_feat`` tail + the reference wrapper in the published order and with NO shortcut
+  (``oracle.yolo_ref.select`` shares the kernel's shortcuts: it stops the greedy pass at the wrapper threshold and at 300).
+* ``decode_f64``: the DFL expectation / box decode / un-letterbox / sigmoid score in float64.
+* crafted head outputs: every scenario is a dict of class logits [B, 8400, Q] and DFL logits [B, 8400, 64] built from
+  seeds; ``embeds_from_logits`` turns the class logits into the embedding the head kernel reads when the installed text
+  features are the first Q standard basis vectors of R^512 (<E[row], e_k> = E[row, k] exactly).
+"""
+import numpy as np
+
+from tstar_amd import yolo_world as Y
+
+SIZES = tuple(Y.IMG_SIZE // s for s in Y.STRIDES)                    # 80, 40, 20
+BASE = (0, SIZES[0] ** 2, SIZES[0] ** 2 + SIZES[1] ** 2)            # first anchor of each level
+A = sum(s * s for s in SIZES)                                        # 8400
+OFF = -100.0                                                         # class logit of "no candidate": expf overflows, score exactly 0
+HOT = 200.0                                                          # DFL logit of a chosen bin next to zeros: expf(-200) is 0 in float32
+
+
+def anchor(level, x, y):
+    return BASE[level] + y * SIZES[level] + x
+
+
+def level_of(a):
+    return int(np.searchsorted(np.asarray(BASE), a, side="right") - 1)
+
+
+def level_params(sd):
+    """Per level (exp(logit_scale), bias) as the layer program stores them: float32."""
+    out = []
+    for i in range(3):
+        c = f"bbox_head.head_module.cls_contrasts.{i}."
+        out.append((np.float32(np.exp(np.float32(sd[c + "logit_scale"]))), np.float32(np.asarray(sd[c + "bias"]))))
+    return out
+
+
+def basis_text(Q):
+    t = np.zeros((Q, Y.TEXT_DIM), np.float32)
+    t[np.arange(Q), np.arange(Q)] = 1.0
+    return t
+
+
+def embeds_from_logits(logits, params):
+    """logits [B, A, Q] -> per level float32 [B * size^2, 512] with E[row, k] = (logit - bias_l) / exp(logit_scale_l)."""
+    B, _, Q = logits.shape
+    out = []
+    for l, (ls, bias) in enumerate(params):
+        n = SIZES[l] ** 2
+        e = np.zeros((B, n, Y.TEXT_DIM), np.float32)
+        e[:, :, :Q] = ((logits[:, BASE[l]:BASE[l] + n].astype(np.float64) - float(bias)) / float(ls)).astype(np.float32)
+        out.append(e.reshape(B * n, Y.TEXT_DIM))
+    return out
+
+
+def dfl_levels(dfl):
+    """dfl [B, A, 64] -> per level [B * size^2, 64]."""
+    B = dfl.shape[0]
+    return [np.ascontiguousarray(dfl[:, BASE[l]:BASE[l] + SIZES[l] ** 2].reshape(B * SIZES[l] ** 2, 64), dtype=np.float32) for l in range(3)]
+
+
+def onehot_dfl(bins):
+    """bins int [..., 4] (left, top, right, bottom) -> DFL logits [..., 64]: the distance is exactly bin * stride."""
+    bins = np.asarray(bins)
+    d = np.zeros(bins.shape[:-1] + (64,), np.float32)
+    idx = np.arange(4) * 16 + bins
+    np.put_along_axis(d, idx, HOT, axis=-1)
+    return d
+
+
+def set_bins(dfl_row, side, bins):
+    """Equal weight on a power-of-two number of distinct bins: the distance is exactly mean(bins) * stride."""
+    assert len(set(bins)) == len(bins) and len(bins) in (1, 2, 4, 8)
+    dfl_row[side * 16:side * 16 + 16] = 0.0
+    dfl_row[side * 16 + np.asarray(bins)] = HOT
+
+
+def bins_with_sum(total, k=8):
+    """k distinct bins of 0..15 whose sum is ``total``."""
+    b = list(range(k))
+    rest = total - sum(b)
+    assert rest >= 0
+    for i in range(k - 1, -1, -1):
+        up = min(rest, 15 - (k - 1 - i) - b[i])
+        b[i] += up
+        rest -= up
+    assert rest == 0 and len(set(b)) == k and max(b) <= 15, (total, k)
+    return b
+
+
+# ----------------------------------------------------------------------------- float64 / float32 statements of the decode
+def _priors():
+    pts, strd = [], []
+    for size, s in zip(SIZES, Y.STRIDES):
+        ys, xs = np.meshgrid(np.arange(size, dtype=np.float64), np.arange(size, dtype=np.float64), indexing="ij")
+        pts.append(np.stack([(xs.reshape(-1) + 0.5) * s, (ys.reshape(-1) + 0.5) * s], 1))
+        strd.append(np.full(size * size, float(s)))
+    return np.concatenate(pts), np.concatenate(strd)
+
+
+def decode_f64(embeds, dfl, params, H, W, Q):
+    """One image: embeds / dfl per level [size^2, 512] / [size^2, 64] (float32 data) -> (scores [A, Q], boxes [A, 4]) in
+    float64: softmax expectation over the 16 bins of each side times the stride, point priors at (i + 0.5) * stride,
+    minus the letterbox padding, divided by the scale factor; sigmoid(E[:, k] * exp(logit_scale) + bias)."""
+    g = Y.letterbox_geometry(H, W)
+    top, _, left, _ = g["pad"]
+    sfw, sfh = g["scale_factor"]
+    pri, strd = _priors()
+    r = np.concatenate([d.astype(np.float64) for d in dfl]).reshape(A, 4, 16)
+    r = np.exp(r - r.max(-1, keepdims=True))
+    dist = (r * np.arange(16.0)).sum(-1) / r.sum(-1) * strd[:, None]
+    boxes = np.stack([(pri[:, 0] - dist[:, 0] - left) / sfw, (pri[:, 1] - dist[:, 1] - top) / sfh,
+                      (pri[:, 0] + dist[:, 2] - left) / sfw, (pri[:, 1] + dist[:, 3] - top) / sfh], 1)
+    logit = np.concatenate([e[:, :Q].astype(np.float64) * float(ls) + float(b) for e, (ls, b) in zip(embeds, params)])
+    with np.errstate(over="ignore"):
+        scores = 1.0 / (1.0 + np.exp(-logit))
+    return scores, boxes
+
+
+def decode_f32(embeds, dfl, params, H, W, Q):
+    """The same quantities through the oracle's float32 torch statement (yolo_ref.head's softmax expectation and
+    yolo_ref.dense_decode)."""
+    import torch
+    from oracle import yolo_ref as R
+    g = Y.letterbox_geometry(H, W)
+    levels = []
+    for e, d, (ls, b), size in zip(embeds, dfl, params, SIZES):
+        lg = torch.from_numpy(np.ascontiguousarray(e[:, :Q])) * torch.tensor(ls) + torch.tensor(b)
+        dist = torch.from_numpy(np.ascontiguousarray(d)).reshape(size * size, 4, 16).softmax(2).matmul(torch.arange(16, dtype=torch.float32))
+        levels.append((lg.t().reshape(Q, size, size), dist.t().reshape(4, size, size)))
+    return R.dense_decode(levels, dict(pad=g["pad"], scale_factor=g["scale_factor"]))
+
+
+# ----------------------------------------------------------------------------- the literal selection
+def literal_select(sc, boxes, ori_hw, wrapper_thr=0.12, max_dets=50, score_thr=0.001, nms_pre=30000, iou_thr=0.7, max_per_img=300):
+    """mmyolo ``predict_by_feat`` after the decode (multi_label) and the reference wrapper, step by step as published:
+    every (anchor, class) pair with score > score_thr in (anchor, class) order; stable sort by descending score; the first
+    nms_pre; mmcv batched_nms (boxes + label * (largest coordinate of those + 1), float32; greedy over ALL of them,
+    IoU > iou_thr strict); the first max_per_img; clamp to the image; then the wrapper: score > wrapper_thr, the first
+    max_dets.  Besides the detections it reports what the pass went through (ranks are positions in the sorted list):
+    ``keep_ranks`` of every survivor, and per candidate the lowest / highest survivor index that suppresses it (-1: none)."""
+    sc = np.asarray(sc, dtype=np.float32)
+    boxes = np.asarray(boxes, dtype=np.float32)
+    a, k = np.nonzero(sc > np.float32(score_thr))
+    v = sc[a, k]
+    n_cand = len(v)
+    o = np.argsort(-v, kind="stable")[:nms_pre]
+    a, k, v = a[o], k[o], v[o]
+    b = boxes[a]
+    n = len(v)
+    sup_lo, sup_hi = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
+    keep = []
+    unit = np.float32(0)
+    if n:
+        unit = b.max() + np.float32(1)
+        ob = b + (k.astype(np.float32) * unit)[:, None]
+        area = (ob[:, 2] - ob[:, 0]) * (ob[:, 3] - ob[:, 1])
+        kb, ka = np.empty((n, 4), np.float32), np.empty(n, np.float32)
+        thr = np.float32(iou_thr)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for i in range(n):
+                m = len(keep)
+                if m:
+                    iw = np.maximum(np.minimum(ob[i, 2], kb[:m, 2]) - np.maximum(ob[i, 0], kb[:m, 0]), np.float32(0))
+                    ih = np.maximum(np.minimum(ob[i, 3], kb[:m, 3]) - np.maximum(ob[i, 1], kb[:m, 1]), np.float32(0))
+                    inter = iw * ih
+                    hit = np.flatnonzero(inter / (area[i] + ka[:m] - inter) > thr)
+                    if len(hit):
+                        sup_lo[i], sup_hi[i] = hit[0], hit[-1]
+                        continue
+                kb[m] = ob[i]
+                ka[m] = area[i]
+                keep.append(i)
+    keep_ranks = np.asarray(keep, dtype=np.int64)
+    kept = keep_ranks[:max_per_img]
+    kb_, kv, kk, kan = b[kept].copy(), v[kept], k[kept], a[kept]
+    kb_[:, 0::2] = np.clip(kb_[:, 0::2], 0, ori_hw[1])
+    kb_[:, 1::2] = np.clip(kb_[:, 1::2], 0, ori_hw[0])
+    m = kv > np.float32(wrapper_thr)
+    kb_, kv, kk, kan = kb_[m], kv[m], kk[m], kan[m]
+    t = np.argsort(-kv, kind="stable")[:max_dets]
+    return dict(xyxy=kb_[t].astype(np.float32), scores=kv[t].astype(np.float32), labels=kk[t].astype(np.int64), anchors=kan[t].astype(np.int64),
+                n_candidates=int(n_cand), n_sorted=int(n), sorted_scores=v, sorted_anchors=a, sorted_labels=k, off_unit=float(unit),
+                keep_ranks=keep_ranks, sup_lo=sup_lo, sup_hi=sup_hi)
+
+
+def reach(lit, wrapper_thr):
+    """What the kernel's path sees of one image, derived from the literal pass: candidates, candidates above the wrapper
+    threshold inside the cut, how many of those the one-wave greedy pass examines before it stops (threshold or 300
+    survivors), survivors among them."""
+    above = int(np.count_nonzero(lit["sorted_scores"] > np.float32(wrapper_thr)))
+    kr = lit["keep_ranks"][lit["keep_ranks"] < above]
+    examined = above if len(kr) < 300 else int(kr[299]) + 1
+    return dict(candidates=lit["n_candidates"], above=above, examined=examined, survivors=int(min(len(kr), 300)), survivors_available=int(len(kr)))
+
+
+def same_selection(x, y):
+    return all(np.array_equal(x[f], y[f]) for f in ("xyxy", "scores", "labels", "anchors"))
+
+
+# ----------------------------------------------------------------------------- crafted scenarios
+def _blank(B, Q):
+    return np.full((B, A, Q), OFF, np.float64), np.zeros((B, A, 4), np.int64)
+
+
+def _grouped_bins(group):
+    """Bins that give every anchor of a (group[l] x group[l]) block of level l the same box: the block's extent minus half
+    a stride on each side.  -> bins [A, 4], slot [A] (a number shared by the anchors with equal boxes)."""
+    bins, slot, nslot = np.zeros((A, 4), np.int64), np.zeros(A, np.int64), 0
+    for l, size in enumerate(SIZES):
+        g = group[l]
+        ys, xs = np.divmod(np.arange(size * size), size)
+        bx, by = xs % g, ys % g
+        bins[BASE[l]:BASE[l] + size * size] = np.stack([bx, by, g - 1 - bx, g - 1 - by], 1)
+        per = -(-size // g)
+        slot[BASE[l]:BASE[l] + size * size] = nslot + (ys // g) * per + xs // g
+        nslot += per * per
+    return bins, slot
+
+
+def scenario_few():
+    """Real-checkpoint regime: image 0 about two thousand candidates, image 1 none at all, image 2 five hundred candidates
+    with none above the wrapper threshold."""
+    rs = np.random.RandomState(11)
+    lg, bins = _blank(3, 4)
+    bins[:] = rs.randint(0, 7, size=bins.shape)
+    idx = rs.choice(A * 4, 2000, replace=False)
+    lg[0].reshape(-1)[idx] = rs.uniform(-6.5, 3.0, 2000)
+    idx = rs.choice(A * 4, 500, replace=False)
+    lg[2].reshape(-1)[idx] = rs.uniform(-6.5, -2.1, 500)
+    return dict(name="few", logits=lg, dfl=onehot_dfl(bins), H=640, W=640, Q=4, thr=0.12, max_dets=100, grid=(4, 4))
+
+
+CUT_P, CUT_Q, CUT_PIN = anchor(2, 10, 10), anchor(2, 0, 0), anchor(0, 79, 10)
+CUT_BIG, CUT_MAX = (anchor(0, 79, 79), anchor(0, 70, 76)), (756, 732)
+CUT_LAST, CUT_P2, CUT_Q2 = anchor(0, 69, 76), anchor(0, 79, 79), anchor(0, 0, 0)
+
+
+def scenario_cut():
+    """33600 (33597) candidates per image, a handful above the wrapper threshold.  Class-0 box P = [204, 664]^2 and class-1 box
+    Q = [-464, 16]^2 with a lower score: Q + unit overlaps P (IoU 0.92) only when the offset unit is 668, the largest
+    coordinate among the 30000 KEPT candidates (667) plus one.  The anchor with the largest coordinate of all, CUT_BIG, is
+    cut, and with its coordinate in the unit (757 / 733) the IoU is below 0.53 and Q would be kept.
+    Image 0: distinct scores; CUT_BIG's four candidates are the lowest; anchor CUT_PIN holds the 667.
+    Image 1: a group of 1993 bit-equal scores (one level, one logit) straddles rank 30000 and (anchor, class) order decides
+    who is cut: the LAST kept candidate (rank 29999; anchor CUT_LAST, class 3) is the only one that holds the 667, the FIRST
+    cut one (rank 30000; CUT_BIG, class 0) holds the 732.  A second pair, class-2 P2 = [628, 664]^2 and class-3
+    Q2 = [-37, 4]^2, is kept apart by the unit 668 (IoU 0.58) and would merge at 665, the unit without rank 29999 (IoU 0.77)."""
+    rs = np.random.RandomState(12)
+    lg, bins = _blank(2, 4)
+    bins[:] = rs.randint(0, 2, size=bins.shape)
+    lg[0] = rs.permutation(A * 4).reshape(A, 4) / (A * 4.0) * 2.5 - 5.7           # distinct, scores 0.0033 .. 0.039
+    lg[0, CUT_BIG[0]] = [-6.86, -6.85, -6.84, -6.83]                               # scores 0.00105 .. 0.00108: the four lowest
+    lg[1] = rs.uniform(-5.5, -3.2, (A, 4))
+    lg[1, BASE[1]:BASE[1] + 650] = rs.uniform(-6.8, -6.3, (650, 4))                # the bottom
+    tie0 = CUT_LAST - 249
+    lg[1, tie0:tie0 + 500] = -6.0                                                  # the bit-equal group, anchors tie0 .. tie0 + 499
+    lg[1, CUT_LAST, :3] = OFF
+    for b in range(2):
+        bins[b, CUT_BIG[b]] = [0, 0, 15, 15]
+    lg[:, CUT_P, 0], lg[:, CUT_P, 1:] = 3.0, -5.0
+    lg[:, CUT_Q, 1], lg[:, CUT_Q, 0], lg[:, CUT_Q, 2:] = 2.0, -5.0, -5.0
+    lg[:, CUT_PIN, 0] = 1.0
+    lg[1, CUT_P2], lg[1, CUT_Q2] = -5.0, -5.0
+    lg[1, CUT_P2, 2], lg[1, CUT_Q2, 3] = 2.5, 2.2
+    bins[:, CUT_Q] = [15, 15, 0, 0]                                                # [-464, -464, 16, 16]
+    bins[1, CUT_P2], bins[1, CUT_Q2] = [1, 1, 0, 0], [0, 0, 0, 0]
+    # image 1: exactly 29999 - (tie members before (CUT_LAST, 3)) scores above the tie group
+    need = int(np.count_nonzero(lg[1] > -6.0)) + 4 * (CUT_LAST - tie0) - 29999
+    spare = lg[1, BASE[2] + 100:BASE[2] + 300].reshape(-1)                         # level 2, away from P and Q
+    assert 0 <= need < spare.size
+    spare[:need] = -6.5
+    lg[1, BASE[2] + 100:BASE[2] + 300] = spare.reshape(200, 4)
+    order = np.argsort(-lg[1].reshape(-1), kind="stable")
+    assert divmod(int(order[29999]), 4) == (CUT_LAST, 3) and divmod(int(order[30000]), 4) == (CUT_BIG[1], 0)
+    dfl = onehot_dfl(bins)
+    for b in range(2):
+        for side, total in ((0, 33), (1, 33), (2, 82), (3, 82)):                   # 336 - 4 * 33 = 204, 336 + 4 * 82 = 664
+            set_bins(dfl[b, CUT_P], side, bins_with_sum(total))
+    set_bins(dfl[0, CUT_PIN], 2, bins_with_sum(31))                                # x1 = 636 + 31 = 667
+    set_bins(dfl[1, CUT_LAST], 3, bins_with_sum(55))                               # y1 = 612 + 55 = 667
+    for side in (2, 3):
+        set_bins(dfl[1, CUT_P2], side, bins_with_sum(28))                          # 636 - 8 = 628, 636 + 28 = 664
+    for side in (0, 1):
+        set_bins(dfl[1, CUT_Q2], side, bins_with_sum(41))                          # 4 - 41 = -37
+    return dict(name="cut", logits=lg, dfl=dfl, H=640, W=640, Q=4, thr=0.12, max_dets=300, grid=(4, 4))
+
+
+def scenario_fallback():
+    """Q = 32, more than 16384 candidates above the wrapper threshold: image 0 all 268800 candidates with about 40000 above
+    (cut and fallback combine), image 1 80000 candidates (not near a power of two) with about 20000 above, all in
+    three classes whose boxes repeat so that fewer than 300 survive and the greedy pass walks the whole sorted list, image 2
+    about 25000 candidates (no cut) with about 20000 above."""
+    rs = np.random.RandomState(13)
+    lg, _ = _blank(3, 32)
+    bins, _ = _grouped_bins((16, 8, 4))
+    lg[0] = rs.uniform(-6.5, -2.2, (A, 32))
+    hi = rs.choice(A * 32, 40000, replace=False)
+    lg[0].reshape(-1)[hi] = rs.uniform(-1.8, 4.0, 40000)
+    cls = [5, 17, 31]
+    for b, n_low in ((1, 80000), (2, 0)):
+        sub = np.full((A, 3), -4.0)
+        sub.reshape(-1)[:] = rs.uniform(-6.0, -2.2, A * 3)
+        top = rs.choice(A * 3, 20000, replace=False)
+        sub.reshape(-1)[top] = rs.uniform(-1.8, 4.0, 20000)
+        lg[b][:, cls] = sub
+        if n_low:
+            others = np.setdiff1d(np.arange(32), cls)
+            low = rs.choice(A * 29, n_low - A * 3, replace=False)
+            blk = np.full(A * 29, OFF)
+            blk[low] = rs.uniform(-6.5, -2.2, len(low))
+            lg[b][:, others] = blk.reshape(A, 29)
+    lg[2][rs.choice(A, 67, replace=False)[:, None], cls] = OFF                     # n = 24999
+    return dict(name="fallback", logits=lg, dfl=onehot_dfl(np.broadcast_to(bins, (3, A, 4))), H=640, W=640, Q=32, thr=0.12, max_dets=300,
+                grid=(4, 4))
+
+
+def scenario_greedy():
+    """The rank order is laid out by hand (logits fall by 1e-3 per rank): 400 (box, class) slots -- the 100 blocks of 8 x 8
+    level-0 anchors, whose 64 members decode to one box, times 4 classes -- become survivors one after the other, each
+    followed by duplicates (other members of slots that already survived): one of its own slot (suppressed by a survivor of
+    the same 64-candidate fetch), one of slot s // 2, every eighth time one of slot 0 (a survivor fetched long before) and a
+    few of random earlier slots (survivor indices beyond 64, 128, 256).  Thousands of candidates are examined before 300
+    survive; 400 could.  A few thousand background candidates below the wrapper threshold sit on levels 1 and 2."""
+    B = 2
+    lg, _ = _blank(B, 4)
+    bins, slot = _grouped_bins((8, 4, 2))
+    members = [np.flatnonzero(slot[:BASE[1]] == s) for s in range(100)]
+    for b in range(B):
+        rs = np.random.RandomState(14 + b)
+        ndup = (7, 4)[b]
+        order = rs.permutation(400)                                                # slot number -> (block, class)
+        used = np.zeros(400, np.int64)
+        seq = []
+
+        def take(si):
+            if used[si] >= 64:
+                return
+            blk, c = divmod(int(order[si]), 4)
+            seq.append((members[blk][used[si]], c))
+            used[si] += 1
+
+        for s in range(400):
+            take(s)
+            take(s)
+            take(s // 2)
+            if s % 8 == 0 and s:
+                take(0)
+            for e in rs.randint(0, s + 1, ndup):
+                take(int(e))
+        for r, (an, c) in enumerate(seq):
+            lg[b, an, c] = 4.0 - 1e-3 * r                                          # > -0.5: scores 0.38 .. 0.98
+        bg = rs.choice((A - BASE[1]) * 4, 3000, replace=False)
+        lg[b, BASE[1]:].reshape(-1)[bg] = rs.uniform(-6.5, -2.2, 3000)
+    return dict(name="greedy", logits=lg, dfl=onehot_dfl(np.broadcast_to(bins, (B, A, 4))), H=640, W=640, Q=4, thr=0.12, max_dets=300, grid=(4, 4))
+
+
+TIE_IOU = dict(A0=(anchor(0, 5, 10), 0), B0=(anchor(0, 4, 10), 0), C0=(anchor(0, 3, 10), 0),
+               A2=(anchor(0, 5, 30), 2), B2=(anchor(0, 4, 30), 2), C2=(anchor(0, 3, 30), 2),
+               Z0=(anchor(0, 40, 50), 1), Z1=(anchor(0, 40, 51), 1))
+
+
+def scenario_ties():
+    """Image 0: 20 distinct leaders, then 400 bit-equal scores (level 0, one logit; 100 anchors with disjoint 8 x 8 boxes times
+    4 classes) that straddle max_dets = 50 and the 300 cap, then candidates between 0.001 and the wrapper threshold and some
+    between 0.0005 and 0.001 (never candidates, whatever the wrapper threshold).  Image 1: integer boxes with IoU exactly
+    0.7 (kept: the comparison is strict) and 0.8 (suppressed) against a leader, once for label 0 and once for label 2 (offset
+    added); two zero-width boxes that overlap (0 / 0 is no suppression); the same low-score filler."""
+    rs = np.random.RandomState(15)
+    lg, bins = _blank(2, 4)
+    bins[:, :, 2:] = 1                                                             # [px, py, px + s, py + s]: disjoint from the neighbours
+    ties = [anchor(0, 2 * i % 80, 4 + 2 * (2 * i // 80)) for i in range(100)]
+    lg[0, ties] = 1.0
+    lead = [anchor(1, 2 * i, 30) for i in range(20)]
+    lg[0, lead, 0] = 3.0 - 0.05 * np.arange(20)
+    for b in range(2):
+        rows = np.arange(BASE[2], A)
+        lg[b, rows] = rs.uniform(-6.5, -2.2, (len(rows), 4))                       # 0.0015 .. 0.0998
+        lg[b, rows[:50], 3] = -7.2                                                 # 0.00075
+    for name, (bn, sc) in dict(A=((5, 2, 5, 2), 2.0), B=((4, 2, 3, 2), 1.5), C=((3, 2, 5, 2), 1.2)).items():
+        for suffix in "02":
+            an, c = TIE_IOU[name + suffix]
+            bins[1, an] = bn                                                       # A [4, 84], B [4, 60], C [4, 68] wide, equal rows
+            lg[1, an, c] = sc
+    for name in ("Z0", "Z1"):
+        an, c = TIE_IOU[name]
+        bins[1, an] = [0, 3, 0, 3]
+        lg[1, an, c] = 0.5
+    return dict(name="ties", logits=lg, dfl=onehot_dfl(bins), H=640, W=640, Q=4, thr=0.12, max_dets=300, grid=(4, 4), tie_logit=1.0)
+
+
+def scenario_classes():
+    """Three query sets in one batch: Q = 32 (image 0), Q = 4 (image 1), Q = 1 (image 2).  Logits are laid out for 32 classes;
+    an image only sees the first Q columns.  Anchor (level 1, 7, 7) scores high in EVERY class: identical boxes, all kept."""
+    rs = np.random.RandomState(16)
+    lg, bins = _blank(3, 32)
+    bins[:] = rs.randint(0, 5, size=bins.shape)
+    for b in range(3):
+        idx = rs.choice(A * 32, 6000, replace=False)
+        lg[b].reshape(-1)[idx] = rs.uniform(-6.5, 3.0, 6000)
+        lg[b, anchor(1, 7, 7)] = 4.0 + 0.01 * np.arange(32)
+    return dict(name="classes", logits=lg, dfl=onehot_dfl(bins), H=640, W=640, Q=(32, 4, 1), thr=0.12, max_dets=300, grid=(4, 4))
+
+
+CELL_WEIGHTS = (1.0 / 3.0, 0.7, 0.1, 0.9)
+
+
+def scenario_cells():
+    """360 x 640 (140 rows of padding above and below, scale 1): more than 300 disjoint boxes (300 detections); boxes in the
+    padding that lie outside the image before the clamp; a box centred exactly on x = 160, y = 180 (a border of the 4 x 4
+    and of the 16 x 16 grid) and one far larger than the image, clamped on all four sides."""
+    rs = np.random.RandomState(17)
+    B = 2
+    lg, bins = _blank(B, 4)
+    bins[:, :, 2:] = 1
+    for b in range(B):
+        pick = rs.choice(BASE[1], 420, replace=False)                              # level 0, anywhere: rows < 17.5 or > 62.5 decode outside
+        lg[b, pick, rs.randint(0, 4, 420)] = rs.uniform(-1.0, 4.0, 420)
+        an = anchor(0, 19, 39)                                                     # px 156, py 316 - 140
+        bins[b, an] = [1, 1 + b, 2, 2 + b]                                         # x [148, 172], y [168, 192] / [160, 200]: centre (160, 180)
+        lg[b, an, 1] = 5.0
+        an = anchor(2, 10, 10)
+        bins[b, an] = [15, 15, 15, 15]                                             # [-144, -284, 816, 676]: clamped on all four sides
+        lg[b, an, 2] = 4.5
+    return dict(name="cells", logits=lg, dfl=onehot_dfl(bins), H=360, W=640, Q=4, thr=0.12, max_dets=300, grid=(4, 4))
+
+
+SCENARIOS = dict(few=scenario_few, cut=scenario_cut, fallback=scenario_fallback, greedy=scenario_greedy, ties=scenario_ties,
+                 classes=scenario_classes, cells=scenario_cells)
+
+
+def scenario_dense_f32(sc, params, b, Q=None):
+    """Dense float32 scores / boxes of image b of a scenario through the float32 statement (the CPU tests' stand-in for the
+    kernel's dense outputs)."""
+    Q = Q or (sc["Q"] if isinstance(sc["Q"], int) else sc["Q"][b])
+    e = embeds_from_logits(sc["logits"][b:b + 1, :, :Q], params)
+    d = dfl_levels(sc["dfl"][b:b + 1])
+    return decode_f32(e, d, params, sc["H"], sc["W"], Q)

@@ -44,6 +44,7 @@ SIGNATURES = {
     "tstar_yolo_set_text_feats": (_i, [_vp, _i, _vp, _vp, _i, _vp]),
     "tstar_yolo_set_class_weights": (_i, [_vp, _i, _vp, _i, _vp]),
     "tstar_yolo_detect": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tstar_yolo_postprocess": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tstar_frames_to_grid": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     "tstar_frames_resize": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     "tstar_i420_to_nv12": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -1492,25 +1492,30 @@ static int run_program(tstar_yolo* h, int B, const int* d_image_set, hipStream_t
     return TSTAR_OK;
 }
 
-int tstar_yolo_detect(tstar_yolo* h, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
-                      const int32_t* h_image_query_set, float score_threshold, int max_dets, float* d_det_scores,
-                      int32_t* d_det_labels, float* d_det_boxes, int32_t* d_n_det, double* d_cell_conf, uint32_t* d_cell_mask,
-                      float* d_dense_scores, float* d_dense_boxes, void* stream) {
-    TSTAR_REQUIRE(h && d_images && d_det_scores && d_det_labels && d_det_boxes && d_n_det, "tstar_yolo_detect: null argument");
-    TSTAR_REQUIRE(B >= 1 && H >= 2 && W >= 2, "tstar_yolo_detect: empty batch or image");
-    TSTAR_REQUIRE(max_dets >= 1 && max_dets <= YOLO_MAX_PER_IMG, "tstar_yolo_detect: max_dets must be in 1..300");
-    TSTAR_REQUIRE(!d_cell_conf == !d_cell_mask, "tstar_yolo_detect: cell_conf and cell_mask go together");
-    TSTAR_REQUIRE(!d_cell_conf || (grid_rows >= 1 && grid_cols >= 1 && grid_rows * grid_cols <= 4096), "tstar_yolo_detect: grid must have 1..4096 cells");
-    hipStream_t s = (hipStream_t)stream;
+}  // extern "C"
+
+// mmyolo test pipeline geometry: YOLOv5KeepRatioResize(640) then LetterResize(640, allow_scale_up=False, pad 114)
+struct YoloGeom { double ratio, sfw, sfh; int rw, rh, top, left; };
+
+// What tstar_yolo_detect and tstar_yolo_postprocess share before the first launch: argument checks, the per-image query
+// sets (uploaded to d_image_set), the candidate lists' capacity and the letterbox geometry of an H x W image.
+static int yolo_prepare(tstar_yolo* h, const char* fn, int B, int H, int W, int grid_rows, int grid_cols, const int32_t* h_image_query_set,
+                        int max_dets, const double* d_cell_conf, const uint32_t* d_cell_mask, const float* d_dense_scores, hipStream_t s,
+                        int* q_uniform_out, YoloGeom* g) {
+    const std::string f(fn);
+    TSTAR_REQUIRE(B >= 1 && H >= 2 && W >= 2, f + ": empty batch or image");
+    TSTAR_REQUIRE(max_dets >= 1 && max_dets <= YOLO_MAX_PER_IMG, f + ": max_dets must be in 1..300");
+    TSTAR_REQUIRE(!d_cell_conf == !d_cell_mask, f + ": cell_conf and cell_mask go together");
+    TSTAR_REQUIRE(!d_cell_conf || (grid_rows >= 1 && grid_cols >= 1 && grid_rows * grid_cols <= 4096), f + ": grid must have 1..4096 cells");
     int q_uniform = -1, q_max = 0;
     for (int b = 0; b < B; ++b) {
         const int set = h_image_query_set ? h_image_query_set[b] : 0;
-        YCHECK_SET(set, "tstar_yolo_detect");
-        if (h->Q[set] == 0) { set_error("tstar_yolo_detect: no text features installed in the requested query set (call tstar_yolo_set_text_feats first)"); return TSTAR_ERR_STATE; }
+        TSTAR_REQUIRE(set >= 0 && set < YOLO_SETS, f + ": query_set must be in 0..63");
+        if (h->Q[set] == 0) { set_error(f + ": no text features installed in the requested query set (call tstar_yolo_set_text_feats first)"); return TSTAR_ERR_STATE; }
         q_uniform = (b == 0 || q_uniform == h->Q[set]) ? h->Q[set] : 0;
         q_max = q_max > h->Q[set] ? q_max : h->Q[set];
     }
-    TSTAR_REQUIRE(!d_dense_scores || q_uniform > 0, "tstar_yolo_detect: dense scores need the same query count for every image");
+    TSTAR_REQUIRE(!d_dense_scores || q_uniform > 0, f + ": dense scores need the same query count for every image");
     if (h_image_query_set) {
         if (B > h->image_set_cap) {
             TSTAR_HIP_CHECK(hipStreamSynchronize(s));
@@ -1530,17 +1535,72 @@ int tstar_yolo_detect(tstar_yolo* h, const uint8_t* d_images, int B, int H, int 
         TSTAR_HIP_CHECK(hipMalloc(&h->d_cand, (size_t)h->max_batch * need_cap * sizeof(unsigned long long)));
         h->cand_cap = need_cap;
     }
-    // mmyolo test pipeline geometry: YOLOv5KeepRatioResize(640) then LetterResize(640, allow_scale_up=False, pad 114)
-    const double ratio = fmin(640.0 / (H > W ? H : W), 640.0 / (H < W ? H : W));
-    const int rw = ratio != 1.0 ? (int)(W * ratio) : W, rh = ratio != 1.0 ? (int)(H * ratio) : H;
-    TSTAR_REQUIRE(rw >= 1 && rh >= 1 && rw <= YOLO_IMG && rh <= YOLO_IMG, "tstar_yolo_detect: image shape outside the letterbox geometry");
-    const double sfw = (double)rw / W, sfh = (double)rh / H;
-    const int ph = YOLO_IMG - rh, pw = YOLO_IMG - rw;
+    g->ratio = fmin(640.0 / (H > W ? H : W), 640.0 / (H < W ? H : W));
+    g->rw = g->ratio != 1.0 ? (int)(W * g->ratio) : W; g->rh = g->ratio != 1.0 ? (int)(H * g->ratio) : H;
+    TSTAR_REQUIRE(g->rw >= 1 && g->rh >= 1 && g->rw <= YOLO_IMG && g->rh <= YOLO_IMG, f + ": image shape outside the letterbox geometry");
+    g->sfw = (double)g->rw / W; g->sfh = (double)g->rh / H;
     // LetterResize: top = int(round(padding_h // 2 - 0.1)) = padding_h // 2 (the -0.1 only breaks the .5 tie of a float half)
-    const int top = ph / 2, left = pw / 2;
+    g->top = (YOLO_IMG - g->rh) / 2; g->left = (YOLO_IMG - g->rw) / 2;
+    *q_uniform_out = q_uniform;
+    return TSTAR_OK;
+}
+
+// The post-process of images b0 .. b0 + Bc - 1 (one chunk, Bc <= max_batch) from the head tensors of the chunk: per level
+// E[l] [Bc * size_l^2, 512] and R[l] [Bc * size_l^2, 64].  The output pointers are those of the whole batch.
+static int yolo_tail(tstar_yolo* h, const float* const* E, const float* const* R, int b0, int Bc, int H, int W, const YoloGeom& g,
+                     const int* d_sets, int q_uniform, int grid_rows, int grid_cols, float score_threshold, int max_dets,
+                     float* d_det_scores, int32_t* d_det_labels, float* d_det_boxes, int32_t* d_n_det, double* d_cell_conf,
+                     uint32_t* d_cell_mask, float* d_dense_scores, float* d_dense_boxes, hipStream_t s) {
     // candidates exactly as mmyolo's predict_by_feat forms them (multi_label, score > score_thr = 0.001): the class-aware
     // NMS offsets depend on the largest coordinate among ALL of them, so the wrapper's 0.12 is not applied early
     const float cand_thr = YOLO_SCORE_THR;
+    TSTAR_HIP_CHECK(hipMemsetAsync(h->d_cand_count, 0, Bc * sizeof(int), s));
+    int anchor0 = 0;
+    for (size_t li = 0; li < h->levels.size(); ++li) {
+        const YoloLevel& l = h->levels[li];
+        DecodeArgs a{};
+        a.E = E[li]; a.R = R[li]; a.HW = l.size * l.size; a.Wl = l.size; a.stride = l.stride;
+        a.anchor0 = anchor0; a.n_anchor = h->n_anchor; a.logit_scale = l.logit_scale; a.bias = l.bias;
+        a.textn = h->d_textn; a.setQ = h->d_setQ; a.image_set = d_sets;
+        a.pad_left = (float)g.left; a.pad_top = (float)g.top; a.sf_w = (float)g.sfw; a.sf_h = (float)g.sfh; a.cand_thr = cand_thr;
+        a.boxes = h->d_boxes; a.cand = h->d_cand; a.cand_cap = h->cand_cap; a.cand_count = h->d_cand_count;
+        a.dense_scores = d_dense_scores ? d_dense_scores + (size_t)b0 * h->n_anchor * q_uniform : nullptr; a.dense_q = q_uniform;
+        const int rows = Bc * a.HW;
+        hipLaunchKernelGGL(head_decode_kernel, dim3(cdiv(rows, HD_APB)), dim3(256), 0, s, a, rows);
+        TSTAR_HIP_CHECK(hipGetLastError());
+        anchor0 += a.HW;
+    }
+    RC(ensure_dyn_lds(reinterpret_cast<const void*>(sort_nms_kernel), NMS_LDS_KEYS * 8));
+    hipLaunchKernelGGL(sort_nms_kernel, dim3(Bc), dim3(1024), (size_t)NMS_LDS_KEYS * 8, s, h->d_cand, h->cand_cap, h->d_cand_count, h->d_boxes, h->n_anchor,
+                       (float)W, (float)H, score_threshold, max_dets, d_det_scores + (size_t)b0 * max_dets, d_det_labels + (size_t)b0 * max_dets,
+                       d_det_boxes + (size_t)b0 * max_dets * 4, d_n_det + b0);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    if (d_dense_boxes)
+        TSTAR_HIP_CHECK(hipMemcpyAsync(d_dense_boxes + (size_t)b0 * h->n_anchor * 4, h->d_boxes, (size_t)Bc * h->n_anchor * 4 * sizeof(float),
+                                       hipMemcpyDeviceToDevice, s));
+    if (d_cell_conf) {
+        const int ncell = grid_rows * grid_cols;
+        hipLaunchKernelGGL(det_cells_kernel, dim3(Bc), dim3(64), (size_t)ncell * 12, s, d_det_scores + (size_t)b0 * max_dets,
+                           d_det_labels + (size_t)b0 * max_dets, d_det_boxes + (size_t)b0 * max_dets * 4, d_n_det + b0, max_dets,
+                           h->d_qweight, d_sets, W, H, grid_rows, grid_cols, d_cell_conf + (size_t)b0 * ncell, d_cell_mask + (size_t)b0 * ncell);
+        TSTAR_HIP_CHECK(hipGetLastError());
+    }
+    return TSTAR_OK;
+}
+
+extern "C" {
+
+int tstar_yolo_detect(tstar_yolo* h, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
+                      const int32_t* h_image_query_set, float score_threshold, int max_dets, float* d_det_scores,
+                      int32_t* d_det_labels, float* d_det_boxes, int32_t* d_n_det, double* d_cell_conf, uint32_t* d_cell_mask,
+                      float* d_dense_scores, float* d_dense_boxes, void* stream) {
+    TSTAR_REQUIRE(h && d_images && d_det_scores && d_det_labels && d_det_boxes && d_n_det, "tstar_yolo_detect: null argument");
+    hipStream_t s = (hipStream_t)stream;
+    int q_uniform = 0;
+    YoloGeom g{};
+    RC(yolo_prepare(h, "tstar_yolo_detect", B, H, W, grid_rows, grid_cols, h_image_query_set, max_dets, d_cell_conf, d_cell_mask, d_dense_scores, s,
+                    &q_uniform, &g));
+    const int rw = g.rw, rh = g.rh;
     // chunks of max_batch + one remainder.  Cutting a batch into near-equal chunks instead (156 -> 78 + 78 under a capacity of
     // 96) was measured and is WORSE than 76 + 76 + 4 (bench conv average 98.3 vs 100.5 TFLOP/s): the chunk size is chosen so
     // that the halo layers fill whole rounds of the chip's 768 workgroup slots (20 B workgroups on a 40x40 / 256-channel
@@ -1558,7 +1618,7 @@ int tstar_yolo_detect(tstar_yolo* h, const uint8_t* d_images, int B, int H, int 
                 TSTAR_HIP_CHECK(hipMalloc(&h->d_tmp_u8, need));
                 h->tmp_u8_bytes = need;
             }
-            if (ratio < 1.0) {
+            if (g.ratio < 1.0) {
                 const size_t total = (size_t)Bc * rh * rw;
                 hipLaunchKernelGGL(area_resize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, imgs, H, W, h->d_tmp_u8, rh, rw, total);
                 TSTAR_HIP_CHECK(hipGetLastError());
@@ -1569,42 +1629,41 @@ int tstar_yolo_detect(tstar_yolo* h, const uint8_t* d_images, int B, int H, int 
         }
         {
             const size_t total = (size_t)Bc * YOLO_IMG * YOLO_IMG;
-            hipLaunchKernelGGL(letterbox_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, packed_src, rh, rw, top, left,
+            hipLaunchKernelGGL(letterbox_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, packed_src, rh, rw, g.top, g.left,
                                h->bufs[h->input_buf], total);
             TSTAR_HIP_CHECK(hipGetLastError());
         }
         const int* d_sets = h_image_query_set ? h->d_image_set + b0 : nullptr;
         RC(run_program(h, Bc, d_sets, s));
-        TSTAR_HIP_CHECK(hipMemsetAsync(h->d_cand_count, 0, Bc * sizeof(int), s));
-        int anchor0 = 0;
-        for (const YoloLevel& l : h->levels) {
-            DecodeArgs a{};
-            a.E = h->bufs[l.e_buf]; a.R = h->bufs[l.r_buf]; a.HW = l.size * l.size; a.Wl = l.size; a.stride = l.stride;
-            a.anchor0 = anchor0; a.n_anchor = h->n_anchor; a.logit_scale = l.logit_scale; a.bias = l.bias;
-            a.textn = h->d_textn; a.setQ = h->d_setQ; a.image_set = d_sets;
-            a.pad_left = (float)left; a.pad_top = (float)top; a.sf_w = (float)sfw; a.sf_h = (float)sfh; a.cand_thr = cand_thr;
-            a.boxes = h->d_boxes; a.cand = h->d_cand; a.cand_cap = h->cand_cap; a.cand_count = h->d_cand_count;
-            a.dense_scores = d_dense_scores ? d_dense_scores + (size_t)b0 * h->n_anchor * q_uniform : nullptr; a.dense_q = q_uniform;
-            const int rows = Bc * a.HW;
-            hipLaunchKernelGGL(head_decode_kernel, dim3(cdiv(rows, HD_APB)), dim3(256), 0, s, a, rows);
-            TSTAR_HIP_CHECK(hipGetLastError());
-            anchor0 += a.HW;
+        const float* E[8]; const float* R[8];
+        for (size_t li = 0; li < h->levels.size(); ++li) { E[li] = h->bufs[h->levels[li].e_buf]; R[li] = h->bufs[h->levels[li].r_buf]; }
+        RC(yolo_tail(h, E, R, b0, Bc, H, W, g, d_sets, q_uniform, grid_rows, grid_cols, score_threshold, max_dets, d_det_scores, d_det_labels,
+                     d_det_boxes, d_n_det, d_cell_conf, d_cell_mask, d_dense_scores, d_dense_boxes, s));
+    }
+    return TSTAR_OK;
+}
+
+int tstar_yolo_postprocess(tstar_yolo* h, const float* const* d_level_embed, const float* const* d_level_dfl, int n_levels, int B, int H, int W,
+                           int grid_rows, int grid_cols, const int32_t* h_image_query_set, float score_threshold, int max_dets,
+                           float* d_det_scores, int32_t* d_det_labels, float* d_det_boxes, int32_t* d_n_det, double* d_cell_conf,
+                           uint32_t* d_cell_mask, float* d_dense_scores, float* d_dense_boxes, void* stream) {
+    TSTAR_REQUIRE(h && d_level_embed && d_level_dfl && d_det_scores && d_det_labels && d_det_boxes && d_n_det, "tstar_yolo_postprocess: null argument");
+    TSTAR_REQUIRE(n_levels == (int)h->levels.size(), "tstar_yolo_postprocess: n_levels must equal the number of head levels of the handle");
+    for (int l = 0; l < n_levels; ++l) TSTAR_REQUIRE(d_level_embed[l] && d_level_dfl[l], "tstar_yolo_postprocess: null level tensor");
+    hipStream_t s = (hipStream_t)stream;
+    int q_uniform = 0;
+    YoloGeom g{};
+    RC(yolo_prepare(h, "tstar_yolo_postprocess", B, H, W, grid_rows, grid_cols, h_image_query_set, max_dets, d_cell_conf, d_cell_mask, d_dense_scores,
+                    s, &q_uniform, &g));
+    for (int b0 = 0; b0 < B; b0 += h->max_batch) {                   // chunked like detect: d_boxes / d_cand hold max_batch images
+        const int Bc = (B - b0) < h->max_batch ? (B - b0) : h->max_batch;
+        const float* E[8]; const float* R[8];
+        for (int l = 0; l < n_levels; ++l) {
+            const size_t row0 = (size_t)b0 * h->levels[l].size * h->levels[l].size;
+            E[l] = d_level_embed[l] + row0 * YOLO_TEXT; R[l] = d_level_dfl[l] + row0 * 4 * YOLO_REG_MAX;
         }
-        RC(ensure_dyn_lds(reinterpret_cast<const void*>(sort_nms_kernel), NMS_LDS_KEYS * 8));
-        hipLaunchKernelGGL(sort_nms_kernel, dim3(Bc), dim3(1024), (size_t)NMS_LDS_KEYS * 8, s, h->d_cand, h->cand_cap, h->d_cand_count, h->d_boxes, h->n_anchor,
-                           (float)W, (float)H, score_threshold, max_dets, d_det_scores + (size_t)b0 * max_dets, d_det_labels + (size_t)b0 * max_dets,
-                           d_det_boxes + (size_t)b0 * max_dets * 4, d_n_det + b0);
-        TSTAR_HIP_CHECK(hipGetLastError());
-        if (d_dense_boxes)
-            TSTAR_HIP_CHECK(hipMemcpyAsync(d_dense_boxes + (size_t)b0 * h->n_anchor * 4, h->d_boxes, (size_t)Bc * h->n_anchor * 4 * sizeof(float),
-                                           hipMemcpyDeviceToDevice, s));
-        if (d_cell_conf) {
-            const int ncell = grid_rows * grid_cols;
-            hipLaunchKernelGGL(det_cells_kernel, dim3(Bc), dim3(64), (size_t)ncell * 12, s, d_det_scores + (size_t)b0 * max_dets,
-                               d_det_labels + (size_t)b0 * max_dets, d_det_boxes + (size_t)b0 * max_dets * 4, d_n_det + b0, max_dets,
-                               h->d_qweight, d_sets, W, H, grid_rows, grid_cols, d_cell_conf + (size_t)b0 * ncell, d_cell_mask + (size_t)b0 * ncell);
-            TSTAR_HIP_CHECK(hipGetLastError());
-        }
+        RC(yolo_tail(h, E, R, b0, Bc, H, W, g, h_image_query_set ? h->d_image_set + b0 : nullptr, q_uniform, grid_rows, grid_cols, score_threshold,
+                     max_dets, d_det_scores, d_det_labels, d_det_boxes, d_n_det, d_cell_conf, d_cell_mask, d_dense_scores, d_dense_boxes, s));
     }
     return TSTAR_OK;
 }

@@ -83,15 +83,8 @@ class YoloDetector:
         _lib.check(self._lib.tstar_yolo_set_class_weights(self._h, int(slot), w.ctypes.data, len(w), _lib.stream_ptr()),
                    "tstar_yolo_set_class_weights")
 
-    def detect(self, images, grid_rows: int = 1, grid_cols: int = 1, score_threshold: float = 0.12, max_dets: int = 50,
-               image_sets: Optional[Sequence[int]] = None, want_dense: bool = False, want_cells: bool = True) -> YoloResult:
-        """images: torch u8 cuda tensor [B,H,W,3] (RGB, as the searcher hands them to the reference)."""
+    def _outputs(self, B, dev, grid_rows, grid_cols, max_dets, image_sets, want_dense, want_cells, who):
         torch = self._torch
-        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
-            raise ValueError("detect: images must be a cuda uint8 tensor [B,H,W,3]")
-        images = images.contiguous()
-        B, H, W, _ = images.shape
-        dev = images.device
         r = YoloResult(scores=torch.empty((B, max_dets), dtype=torch.float32, device=dev),
                        labels=torch.empty((B, max_dets), dtype=torch.int32, device=dev),
                        boxes=torch.empty((B, max_dets, 4), dtype=torch.float32, device=dev),
@@ -103,17 +96,58 @@ class YoloDetector:
         if image_sets is not None:
             sets = np.ascontiguousarray(image_sets, dtype=np.int32)
             if sets.shape != (B,):
-                raise ValueError("detect: image_sets needs one slot per image")
+                raise ValueError(who + ": image_sets needs one slot per image")
         if want_dense:
             qs = {self.Qs.get(int(v), 0) for v in (sets if sets is not None else [0])}
             if len(qs) != 1:
-                raise ValueError("detect: dense scores need the same query count for every image")
+                raise ValueError(who + ": dense scores need the same query count for every image")
             r.dense_scores = torch.empty((B, self.n_anchor, qs.pop()), dtype=torch.float32, device=dev)
             r.dense_boxes = torch.empty((B, self.n_anchor, 4), dtype=torch.float32, device=dev)
+        return r, sets
+
+    def detect(self, images, grid_rows: int = 1, grid_cols: int = 1, score_threshold: float = 0.12, max_dets: int = 50,
+               image_sets: Optional[Sequence[int]] = None, want_dense: bool = False, want_cells: bool = True) -> YoloResult:
+        """images: torch u8 cuda tensor [B,H,W,3] (RGB, as the searcher hands them to the reference)."""
+        torch = self._torch
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
+            raise ValueError("detect: images must be a cuda uint8 tensor [B,H,W,3]")
+        images = images.contiguous()
+        B, H, W, _ = images.shape
+        dev = images.device
+        r, sets = self._outputs(B, dev, grid_rows, grid_cols, max_dets, image_sets, want_dense, want_cells, "detect")
         rc = self._lib.tstar_yolo_detect(self._h, images.data_ptr(), B, H, W, int(grid_rows), int(grid_cols),
                                          None if sets is None else sets.ctypes.data, float(score_threshold), int(max_dets),
                                          r.scores.data_ptr(), r.labels.data_ptr(), r.boxes.data_ptr(), r.n_kept.data_ptr(),
                                          _lib.ptr(r.cell_conf), _lib.ptr(r.cell_mask), _lib.ptr(r.dense_scores), _lib.ptr(r.dense_boxes),
                                          _lib.stream_ptr())
         _lib.check(rc, "tstar_yolo_detect")
+        return r
+
+    def postprocess(self, embeds, dfl, B: int, H: int, W: int, grid_rows: int = 1, grid_cols: int = 1, score_threshold: float = 0.12,
+                    max_dets: int = 50, image_sets: Optional[Sequence[int]] = None, want_dense: bool = False,
+                    want_cells: bool = True) -> YoloResult:
+        """Diagnostic: the tail of detect (tstar_yolo_postprocess) on caller-supplied head tensors.  embeds / dfl: one cuda
+        float32 tensor per head level, [B * size^2, 512] and [B * size^2, 64] (side * 16 + bin)."""
+        torch = self._torch
+        if len(embeds) != len(dfl):
+            raise ValueError("postprocess: one embedding and one DFL tensor per head level")
+        keep = []
+        if len(embeds) != len(Y.STRIDES) or B < 1:
+            raise ValueError("postprocess: one tensor pair per head level and at least one image")
+        for e, d, stride in zip(embeds, dfl, Y.STRIDES):
+            rows = B * (Y.IMG_SIZE // stride) ** 2
+            for t, c in ((e, Y.TEXT_DIM), (d, 4 * Y.REG_MAX)):
+                if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != (rows, c):
+                    raise ValueError("postprocess: level tensors must be cuda float32 [B*size^2, 512] and [B*size^2, 64]")
+            keep.append((e.contiguous(), d.contiguous()))
+        dev = keep[0][0].device
+        r, sets = self._outputs(B, dev, grid_rows, grid_cols, max_dets, image_sets, want_dense, want_cells, "postprocess")
+        pe = (C.c_void_p * len(keep))(*[e.data_ptr() for e, _ in keep])
+        pd = (C.c_void_p * len(keep))(*[d.data_ptr() for _, d in keep])
+        rc = self._lib.tstar_yolo_postprocess(self._h, pe, pd, len(keep), int(B), int(H), int(W), int(grid_rows), int(grid_cols),
+                                              None if sets is None else sets.ctypes.data, float(score_threshold), int(max_dets),
+                                              r.scores.data_ptr(), r.labels.data_ptr(), r.boxes.data_ptr(), r.n_kept.data_ptr(),
+                                              _lib.ptr(r.cell_conf), _lib.ptr(r.cell_mask), _lib.ptr(r.dense_scores), _lib.ptr(r.dense_boxes),
+                                              _lib.stream_ptr())
+        _lib.check(rc, "tstar_yolo_postprocess")
         return r
