@@ -395,6 +395,14 @@ int tstar_gemm_f32x3_pre(const float* d_A, const void* d_Wp, float* d_C, const f
  * 128x128 / 64x128 / 64x64 tiles, 3 = hybrid (rows [0, m_split) in 128x128 tiles, the rest 64x128), 4 = wide (128x256 + 64x128 tail),
  * 5 = wide with the weights streamed global -> VGPR.  TSTAR_ERR_ARG where tstar_gemm_* would refuse the same arguments. */
 int tstar_gemm_plan(int weights_mode, int M, int N, int ldc, int patch_np, int tile_cfg, int has_packed_w2, int* plan4);
+/* The launch plan tstar_frames_resize (op 0: n frames -> out_w x out_h = ow x oh) or tstar_frames_to_grid (op 1: n = grid_rows * grid_cols,
+ * ow x oh = the 200 x 95 cell) makes (an added entry; tstar_abi_version() stays 3).  Pure: needs no GPU and launches nothing.
+ * out_aligned4 / video_aligned4: the output / frame-store pointer is a multiple of 4; generic, nv12_lds, grid_px: the values of
+ * TSTAR_INGEST_GENERIC (default 0), TSTAR_NV12_LDS (default 1) and TSTAR_GRID_PX (default 1).  plan6 = { kind, pixels per lane, grid.x,
+ * grid.y, dynamic LDS bytes, LDS row pitch in dwords }; kind 0 = generic kernels, 1 = RGB fast path, 2 = NV12 per tap, 3 = NV12 through LDS
+ * (resize only).  TSTAR_ERR_ARG where the launchers refuse the same n / ow / oh. */
+int tstar_ingest_plan(int op, int nv12, int H, int W, int n, int ow, int oh, int out_aligned4, int video_aligned4, int generic,
+                      int nv12_lds, int grid_px, int* plan6);
 int tstar_layernorm_f32(const float* d_x, float* d_y, const float* d_w, const float* d_b, int rows, int D, void* stream);
 /* qkv [B*T, 3*heads*64] -> out [B*T, heads*64]; mode 0 full, 1 causal + key mask u8 [B,T] */
 int tstar_attention_f32(const float* d_qkv, float* d_out, int B, int T, int heads, int mode,

@@ -186,7 +186,7 @@ def nv12_to_rgb(frame: np.ndarray) -> np.ndarray:
     """NV12 uint8 [H*3/2, W] -> RGB uint8 [H,W,3]: BT.601 limited-range integer matrix, nearest chroma.
     PARITY UNPINNED (the reference receives RGB from decord/swscale and never sees NV12): this is the
     build's own definition of the NV12 ingest variant, mirrored by SrcNV12 in
-    tstar_amd/csrc/preprocess.hip."""
+    tstar_amd/csrc/ingest.hip."""
     H = frame.shape[0] * 2 // 3
     W = frame.shape[1]
     y = frame[:H].astype(np.int64) - 16

@@ -5,13 +5,44 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+# The shapes the tests below hand to the library.  library_shapes() restates the calls made from them, so that a test without a
+# GPU (tests/test_host_logic.py::test_every_ingest_kernel_form_is_gpu_tested) can ask the launch plan which kernel each one runs.
+GRID_RGB_G = [1, 4, 15]
+RESIZE_RGB_TARGETS = [(600, 285), (800, 380), (640, 360), (37, 11), (4, 3), (1, 5), (8, 2), (2, 1)]   # ow 4 / 1: one unit per row (magic_of(1))
+RANDOM_SOURCE_TARGETS = ((200, 95), (600, 285))
+# (2, 2): below the NV12 fast paths' W >= 4, the generic NV12 kernels
+NV12_CASES = [(360, 640, 4), (72, 128, 3), (90, 160, 1), (480, 854, 2), (36, 4, 2), (1080, 1920, 2), (2, 2, 1)]
+NV12_RESIZE_TARGETS = ((600, 285), (201, 97))
+
+
+def random_source_sizes():
+    rs = np.random.RandomState(77)
+    sizes = [(190, 400), (380, 800), (95, 200), (570, 1200), (285, 600), (2, 2), (2, 3), (1080, 1920)]
+    while len(sizes) < 20:
+        sizes.append((int(rs.randint(8, 1300)), int(rs.randint(8, 1300))))
+    return rs, sizes
+
+
+def library_shapes():
+    """(op, nv12, H, W, n, ow, oh) of the tstar_frames_resize (op 0) / tstar_frames_to_grid (op 1: n cells of 200x95) calls of
+    test_frames_to_grid_rgb, test_frames_resize_rgb, test_frames_resize_random_source_sizes,
+    test_nv12_store_matches_rgb_of_converted_frames and test_nv12_grid_random_full_range; torch allocations are 4-byte aligned."""
+    out = [(1, 0, 360, 640, g * g, 200, 95) for g in GRID_RGB_G]
+    out += [(0, 0, 360, 640, 3, ow, oh) for ow, oh in RESIZE_RGB_TARGETS]
+    for H, W in random_source_sizes()[1]:
+        out += [(0, 0, H, W, 2, ow, oh) for ow, oh in RANDOM_SOURCE_TARGETS] + [(1, 0, H, W, 1, 200, 95)]
+    out += [(1, 1, 360, 640, 16, 200, 95), (0, 1, 360, 640, 2, 600, 285)]
+    for H, W, g in NV12_CASES:
+        out += [(1, 1, H, W, g * g, 200, 95)] + [(0, 1, H, W, min(2, g * g), ow, oh) for ow, oh in NV12_RESIZE_TARGETS]
+    return out
+
 
 def _lib():
     from tstar_amd import _lib
     return _lib, _lib.load()
 
 
-@pytest.mark.parametrize("g", [1, 4, 15])
+@pytest.mark.parametrize("g", GRID_RGB_G)
 def test_frames_to_grid_rgb(g):
     from oracle import resize_ref as R
     from tstar_amd.video import synthetic_frames_numpy, synthetic_video
@@ -26,7 +57,7 @@ def test_frames_to_grid_rgb(g):
     assert np.array_equal(grid.cpu().numpy(), R.frames_to_grid(list(synthetic_frames_numpy(secs, N, seed=4)), g, g))
 
 
-@pytest.mark.parametrize("ow,oh", [(600, 285), (800, 380), (640, 360), (37, 11), (4, 3), (1, 5), (8, 2), (2, 1)])   # ow 4 / 1: one unit per row (magic_of(1))
+@pytest.mark.parametrize("ow,oh", RESIZE_RGB_TARGETS)
 def test_frames_resize_rgb(ow, oh):
     from oracle import resize_ref as R
     from tstar_amd.video import synthetic_frames_numpy, synthetic_video
@@ -46,23 +77,25 @@ def test_frames_resize_rgb(ow, oh):
 def test_frames_resize_random_source_sizes():
     """Random noise frames of 20 seeded random source sizes (upscales, strong decimation, odd sizes, exact 2x / 4x / 1x of
     the target) to the grid-cell (200x95) and verification (600x285) sizes: bit-exact against the oracle's cv2.resize
-    statement (at exactly 2x decimation, where cv2 switches to INTER_AREA, the two formulas coincide)."""
+    statement (at exactly 2x decimation, where cv2 switches to INTER_AREA, the two formulas coincide).  Each size also fills a
+    one-cell grid: the 2-pixel-wide sources are the only ones that reach the generic RGB grid kernel."""
     from oracle import resize_ref as R
     L, lib = _lib()
-    rs = np.random.RandomState(77)
-    sizes = [(190, 400), (380, 800), (95, 200), (570, 1200), (285, 600), (2, 2), (2, 3), (1080, 1920)]
-    while len(sizes) < 20:
-        sizes.append((int(rs.randint(8, 1300)), int(rs.randint(8, 1300))))
+    rs, sizes = random_source_sizes()
     for H, W in sizes:
         frames = rs.randint(0, 256, (2, H, W, 3), dtype=np.uint8)
         d = torch.from_numpy(frames).cuda()
         idx = torch.tensor([1, 0], dtype=torch.int32, device="cuda")
-        for ow, oh in ((200, 95), (600, 285)):
+        for ow, oh in RANDOM_SOURCE_TARGETS:
             out = torch.empty((2, oh, ow, 3), dtype=torch.uint8, device="cuda")
             L.check(lib.tstar_frames_resize(d.data_ptr(), 2, H, W, idx.data_ptr(), 2, ow, oh, out.data_ptr(), 0, None))
             torch.cuda.synchronize()
             for k, src in enumerate((1, 0)):
                 assert np.array_equal(out[k].cpu().numpy(), R.cv_bilinear_resize(frames[src], ow, oh)), (H, W, ow, oh)
+        grid = torch.empty((95, 200, 3), dtype=torch.uint8, device="cuda")
+        L.check(lib.tstar_frames_to_grid(d.data_ptr(), 2, H, W, idx.data_ptr(), 1, 1, grid.data_ptr(), 0, None))
+        torch.cuda.synchronize()
+        assert np.array_equal(grid.cpu().numpy(), R.frames_to_grid([frames[1]], 1, 1)), (H, W)
 
 
 def test_nv12_store_matches_rgb_of_converted_frames():
@@ -88,7 +121,7 @@ def test_nv12_store_matches_rgb_of_converted_frames():
     assert np.array_equal(out[1].cpu().numpy(), R.cv_bilinear_resize(rgb[1], 600, 285))
 
 
-@pytest.mark.parametrize("H,W,g", [(360, 640, 4), (72, 128, 3), (90, 160, 1), (480, 854, 2), (36, 4, 2), (1080, 1920, 2)])
+@pytest.mark.parametrize("H,W,g", NV12_CASES)
 def test_nv12_grid_random_full_range(H, W, g):
     """NV12 grid ingest on FULL-RANGE random bytes (the BT.601 conversion clips at both ends, which the synthetic video's
     limited-range content never reaches) and on sizes that exercise the window clamps at the right edge, the chroma-pair
@@ -109,7 +142,7 @@ def test_nv12_grid_random_full_range(H, W, g):
     assert np.array_equal(grid.cpu().numpy(), R.frames_to_grid(rgb, g, g)), (H, W, g)
     # the single-step resize on the same frames: 600x285 (4 pixels per lane) and an odd width (1 pixel per lane)
     m = min(2, len(order))
-    for ow, oh in ((600, 285), (201, 97)):
+    for ow, oh in NV12_RESIZE_TARGETS:
         out = torch.empty((m, oh, ow, 3), dtype=torch.uint8, device="cuda")
         L.check(lib.tstar_frames_resize(d.data_ptr(), n, H, W, idx.data_ptr(), m, ow, oh, out.data_ptr(), 1, None))
         torch.cuda.synchronize()

@@ -61,6 +61,73 @@ def test_gemm_plan_matches_recorded_table(golden_dir):
     assert lib.tstar_gemm_plan(0, 9232, 192, 192, 0, -1, 0, out) == 1             # N % 128
 
 
+def test_ingest_plan_matches_recorded_table(golden_dir):
+    """The ingest launch policy (plan_ingest through tstar_ingest_plan: pure, no GPU) against launches recorded from the launchers
+    that preceded it: kernel form, pixels per lane, grid, dynamic LDS bytes and LDS pitch, row by row.  A threshold moved by one
+    fails here.  Tried on plan_ingest, with the number of rows of the table that then differ:
+      n <= 65535: 65536 -> 351, 65534 -> 234.
+      frame bytes < 2^31: RGB frames are multiples of 3 bytes and even-sized NV12 frames of 6, so no frame has 2^31 - 1 or 2^31
+        bytes and +-1 changes nothing; the table holds the nearest ones (2^31 - 2, 2^31 + 1): -2 -> 6, +2 -> 6.
+      W >= 3: 2 -> 73, 4 -> 73.   ow >= 2: 1 -> 247, 3 -> 247.
+      units * ow < 2^32: + 1 -> 10 (1024 x 4096 is 2^32 exactly); - 1 -> 0 (2^32 - 1 is square-free, so only ow = 1 reaches it);
+        the bound moved to either side of the 4000x268 / 4000x269 pair -> 32 / 20.
+      four pixels per lane: ow % 4 -> % 2: 28, % 8: 26; ow >= 8 -> 9: 183 (5..7 are the same rule under ow % 4; 4 -> 183);
+        output alignment ignored -> 208; TSTAR_GRID_PX compared != 1 instead of == 4 -> 16, ignored -> 140; allowed on the NV12
+        grid -> 19.
+      NV12 through LDS: W % 4 -> % 2: 13, % 8: 31; H % 2 dropped: 52; ow % 4 -> % 2: 3, % 8: 18; ow >= 5: 15; either alignment
+        flag ignored: 28; TSTAR_NV12_LDS ignored: 36; offered to the grid: 45; made subject to TSTAR_INGEST_GENERIC: 36; region
+        bytes <= 65535: 3 (a 16x1020 source needs 65536 exactly); <= 65537 .. 65791: 0 (regions are multiples of 16 bytes and the
+        next one in the table is 65792); <= 65792: 3; pitch + 8 instead of + 4: 164.
+      NV12 per tap: W >= 5: 52 (3 and 2: 0, W is even and the shared W >= 3 holds); W <= 65533: 9, 65536: 9 (65534: 0, W is even);
+        W % 2 dropped: 162; H % 2 dropped: 423.
+      TSTAR_INGEST_GENERIC ignored: 386.   Grids: units + 256 instead of + 255: 28, generic: 2159.
+    Never binding, so no row can tell: units < 2^31 (implied by units * ow < 2^32 with ow >= 2; it keeps that product inside 64
+    bits), rows * column groups < 8192 (implied by the 64 KB bound: 4096 -> 0 rows, 4064 -> 6), frame bytes % 4 (implied by W % 4
+    and H % 2)."""
+    import ctypes as C
+    from tstar_amd import _lib
+    lib = _lib.load()
+    path = os.path.join(golden_dir, "ingest_plan_table.txt")
+    out = (C.c_int * 6)()
+    rows, forms, lds_refused_for_size = 0, set(), False
+    for line in open(path):
+        if line.startswith("#"):
+            continue
+        f = [int(v) for v in line.split()]
+        (op, nv12, H, W, n, ow, oh, oa, va, generic, lds_on, grid_px), want = f[:12], tuple(f[12:])
+        rc = lib.tstar_ingest_plan(*f[:12], out)
+        got = (-1, 0, 0, 0, 0, 0) if rc else tuple(out)
+        assert rc in (0, 1) and got == want, (line, rc, got)
+        rows += 1
+        forms.add((op, nv12, want[0], want[1]))
+        lds_refused_for_size |= (op == 0 and nv12 and lds_on and oa and va and 0 < n <= 65535 and W % 4 == 0 and H % 2 == 0 and ow % 4 == 0
+                                 and H * W * 3 // 2 < 2 ** 31 and want[0] == 2)
+    assert rows >= 1000 and os.path.getsize(path) < 512 * 1024
+    # every (op, format, kind, pixels per lane) the launchers could reach: refusals (-1), the generic kernels, the fast forms with
+    # 4 and 1 pixels per lane (the RGB grid's 4 only under TSTAR_GRID_PX=4, the NV12 grid always 1), NV12 through LDS (resize only)
+    rgb = {(-1, 0), (0, 1), (1, 1), (1, 4)}
+    assert forms == ({(0, 0) + k for k in rgb} | {(1, 0) + k for k in rgb} | {(0, 1) + k for k in {(-1, 0), (0, 1), (2, 1), (2, 4), (3, 4)}}
+                     | {(1, 1) + k for k in {(-1, 0), (0, 1), (2, 1)}})
+    assert lds_refused_for_size                     # e.g. 1080x1920 -> 200x95: the region of an 8 x 128 tile does not fit 64 KB
+    assert lib.tstar_ingest_plan(2, 0, 360, 640, 1, 200, 95, 1, 1, 0, 1, 1, out) == 1         # no such op
+
+
+def test_every_ingest_kernel_form_is_gpu_tested():
+    """The shapes tests/test_gpu_ingest.py hands to the library reach every kernel form the plan can choose without an override:
+    per op and format the generic kernels, the fast forms with 4 and 1 pixels per lane, NV12 through LDS."""
+    import ctypes as C
+    import test_gpu_ingest as G
+    from tstar_amd import _lib
+    lib = _lib.load()
+    out = (C.c_int * 6)()
+    forms = set()
+    for op, nv12, H, W, n, ow, oh in G.library_shapes():
+        assert lib.tstar_ingest_plan(op, nv12, H, W, n, ow, oh, 1, 1, 0, 1, 1, out) == 0
+        forms.add((op, nv12, out[0], out[1]))
+    assert forms == {(0, 0, 0, 1), (0, 0, 1, 1), (0, 0, 1, 4), (0, 1, 0, 1), (0, 1, 2, 1), (0, 1, 2, 4), (0, 1, 3, 4),
+                     (1, 0, 0, 1), (1, 0, 1, 1), (1, 1, 0, 1), (1, 1, 2, 1)}
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():

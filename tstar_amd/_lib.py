@@ -86,6 +86,7 @@ SIGNATURES = {
     "tstar_pack_f32x3": (_i, [_vp, _vp, _i, _i, _vp]),
     "tstar_gemm_f32x3_pre": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tstar_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "tstar_ingest_plan": (_i, [_i] * 12 + [C.POINTER(_i)]),
     "tstar_layernorm_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "tstar_draw_boxes": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "tstar_draw_boxes_np": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp]),

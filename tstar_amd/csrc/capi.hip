@@ -3,6 +3,7 @@
 #include "../../include/tstar_hip.h"
 #include "common.h"
 #include "heads.h"
+#include "ingest.h"
 #include "jpeg_host.h"
 #include "kernels.h"
 #include "owl_weights.h"
@@ -811,6 +812,15 @@ int tstar_gemm_plan(int weights_mode, int M, int N, int ldc, int patch_np, int t
     const GemmPlan p = plan_gemm(wmode, M, N, ldc, patch_np, tile_cfg, has_packed_w2 != 0);
     if (p.error) { set_error(p.error); return TSTAR_ERR_ARG; }
     plan4[0] = p.kind; plan4[1] = p.m_split; plan4[2] = p.blocks; plan4[3] = p.lds_bytes;
+    return TSTAR_OK;
+}
+
+int tstar_ingest_plan(int op, int nv12, int H, int W, int n, int ow, int oh, int out_aligned4, int video_aligned4, int generic, int nv12_lds,
+                      int grid_px, int* plan6) {
+    TSTAR_REQUIRE(plan6, "tstar_ingest_plan: null argument");
+    const IngestPlan p = plan_ingest(op, nv12 != 0, H, W, n, ow, oh, out_aligned4 != 0, video_aligned4 != 0, IngestOverrides{generic != 0, nv12_lds != 0, grid_px});
+    if (p.error) { set_error(p.error); return TSTAR_ERR_ARG; }
+    plan6[0] = p.kind; plan6[1] = p.px; plan6[2] = (int)p.grid_x; plan6[3] = (int)p.grid_y; plan6[4] = p.lds_bytes; plan6[5] = p.lds_pitch;
     return TSTAR_OK;
 }
 

@@ -49,6 +49,16 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return base + idx;
 }
 
+// 12 bytes of 4 consecutive RGB pixels -> three aligned dword stores (d dword-aligned: rows are multiples of 4 pixels;
+// byte stores of single channels were the resize kernel's limiter: 3 strided store instructions per pixel)
+__device__ __forceinline__ void store_px4(uint8_t* d, const unsigned (&v)[4][3]) {
+    uint3 o;
+    o.x = v[0][0] | (v[0][1] << 8) | (v[0][2] << 16) | (v[1][0] << 24);
+    o.y = v[1][1] | (v[1][2] << 8) | (v[2][0] << 16) | (v[2][1] << 24);
+    o.z = v[2][2] | (v[3][0] << 8) | (v[3][1] << 16) | (v[3][2] << 24);
+    *reinterpret_cast<uint3*>(d) = o;
+}
+
 }  // namespace tstar
 
 #define TSTAR_OK 0

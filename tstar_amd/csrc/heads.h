@@ -1,4 +1,4 @@
-// Launchers of heads.hip / preprocess.hip (internal).
+// Launchers of heads.hip / preprocess.hip / jpeg.hip (internal); the searcher ingest is ingest.h.
 #pragma once
 #include "common.h"
 
@@ -33,7 +33,7 @@ int cell_reduce(const float* scores, const int* labels, const float* xyxy, const
 // paint the kept detections' boxes (score > thr) on u8 images [B,H,W,3] in place; xyxy [B,np,4], scores [B,np]
 int draw_boxes(uint8_t* images, int B, int H, int W, const float* xyxy, const float* scores, int np, float thr, hipStream_t s);
 
-// ---- preprocess.hip ----
+// ---- preprocess.hip: the detector's bicubic pass ----
 // Pillow-compatible fixed-point resampling tables for one axis (host side).
 struct ResampleTable {
     int in_size = 0, out_size = 0, ksize = 0;
@@ -49,17 +49,6 @@ int resample_h_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const Re
 int resample_v_normalize_patchify(const uint8_t* in, float* out, uint8_t* out_u8, int B, int H, const ResampleTable& t,
                                   const float* lut, int patch, hipStream_t s);
 
-// OpenCV-style fixed-point bilinear resize (11-bit coefficients), gather by frame index.
-// mode 0: frames[idx[i]] (H,W) -> out[i] (oh,ow)
-int bilinear_gather_u8(const uint8_t* video, int H, int W, const int* d_idx, int n, int ow, int oh, uint8_t* out,
-                       int nv12, hipStream_t s);
-// frames[idx[i]] -> (4*ch x 4*cw) -> (ch x cw) -> tile (i / cols, i % cols) of grid [rows*ch, cols*cw, 3]
-int frames_to_grid_u8(const uint8_t* video, int H, int W, const int* d_idx, int rows, int cols, int cw, int ch,
-                      uint8_t* grid, int nv12, hipStream_t s);
-// n planar I420 frames [H*3/2*W bytes each: Y, U, V planes] -> NV12 [n, H*3/2, W]
-int i420_to_nv12_u8(const uint8_t* in, int n, int H, int W, uint8_t* out, hipStream_t s);
-// frames[idx[i]] NV12 [H*3/2, W] -> RGB u8 [n,H,W,3] (BT.601 limited range, nearest chroma)
-int nv12_to_rgb_u8(const uint8_t* video, int H, int W, const int* d_idx, int n, uint8_t* out, hipStream_t s);
 // jpeg.hip: n frames of coefficient blocks [n][g.blocks()][64] + tables u16 [n][3][64] -> RGB u8 [n,H,W,3]; planes is a
 // workspace of n * g.plane_bytes() bytes (layouts in jpeg_host.h)
 struct JpegGeom;

@@ -27,6 +27,7 @@
 #include "../../include/tstar_hip.h"
 #include "common.h"
 #include "heads.h"
+#include "ingest.h"
 #include "prof.h"
 #include <math.h>
 #include <stdlib.h>
