@@ -36,6 +36,9 @@ def main():
     ap.add_argument("--out", default="./output/tstar_results.json")
     ap.add_argument("--owl-model", default="google/owlvit-base-patch32",
                     help="OWL-ViT checkpoint (name or directory; B/32 or B/16); seeded synthetic B/32 weights when none is on disk")
+    ap.add_argument("--owl-input-size", default=None, metavar="HxW",
+                    help="detector input size, e.g. 448x768 (each side a multiple of the patch size; default: the checkpoint's 768x768, "
+                         "or TSTAR_INPUT_SIZE)")
     ap.add_argument("--videos", nargs="+", default=None,
                     help="video files / JPEG frame folders to search instead of synthetic videos (one item each; overrides --items)")
     ap.add_argument("--video-fps", type=float, default=None,
@@ -71,8 +74,14 @@ def main():
             return open_video(p, fps=args.video_fps)
         return p
 
+    owl_kw = {}
+    if args.owl_input_size is not None:
+        try:
+            owl_kw["input_size"] = tuple(int(v) for v in args.owl_input_size.lower().split("x"))
+        except ValueError:
+            ap.error(f"--owl-input-size must look like HEIGHTxWIDTH, not {args.owl_input_size!r}")
     heuristic = initialize_heuristic("owl-vit", model_name_or_path=args.owl_model, synthetic_seed=0, max_batch=64,
-                                     device=f"cuda:{local}")
+                                     device=f"cuda:{local}", **owl_kw)
     mine = shard_items(len(items), world, rank)
     rows, dists = [], {}
     # two lock-step groups alternate on the GPU: one group's host bookkeeping runs under the other's verification batch

@@ -101,7 +101,21 @@ int tstar_owl_create_ex(tstar_owl** out, int image_size, int patch_size, const f
                         const float* h_text_blob, size_t n_text, const float* h_norm_lut, int max_batch, int weights_mode);
 /* floats of a vision blob of that geometry (0 if it is not supported) */
 size_t tstar_owl_vision_blob_floats_ex(int image_size, int patch_size);
-/* np, the detections per image of the handle's geometry (576 at B/32, 2304 at B/16; -1 for a NULL handle) */
+/* Added entries (tstar_abi_version() stays 3).  The same for a handle that runs its checkpoint at the INPUT SIZE (input_h,
+ * input_w) pixels instead of the checkpoint's own 768 x 768 (HF: forward(..., interpolate_pos_encoding=True) behind an image
+ * processor of that size): images are resampled (Pillow bicubic) to input_h x input_w, the patch grid is gh x gw = input_h / P x
+ * input_w / P, np = gh gw detections and np + 1 tokens per image.  Each side must be a positive multiple of patch_size (32 or
+ * 16) and np at most 3600; anything else is refused before anything is allocated.  The size is fixed for the handle's life.
+ * The vision blob holds tstar_owl_vision_blob_floats_in(input_h, input_w, patch_size) floats: the layout of tstar_owl_create_ex
+ * with pos_emb [np + 1, 768] (the checkpoint's table resampled to gh x gw, row 0 kept) and box_bias [np, 4] (for the gh x gw
+ * grid) -- tstar_amd/weights.py pack_blob builds both as HF does.  (768, 768, P) is tstar_owl_create_ex(768, P): same bits.
+ * A forward chunk never holds more token rows than 1024 images of 577 tokens. */
+int tstar_owl_create_in(tstar_owl** out, int input_h, int input_w, int patch_size, const float* h_vision_blob, size_t n_vision,
+                        const float* h_text_blob, size_t n_text, const float* h_norm_lut, int max_batch, int weights_mode);
+/* floats of a vision blob for that input size (0 if it is not supported) */
+size_t tstar_owl_vision_blob_floats_in(int input_h, int input_w, int patch_size);
+/* np, the detections per image of the handle's geometry (576 at B/32, 2304 at B/16, gh x gw at another input size; -1 for a
+ * NULL handle) */
 int tstar_owl_num_patches(tstar_owl* h);
 int tstar_owl_destroy(tstar_owl* h);
 
@@ -164,11 +178,11 @@ int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B,
                          double* d_cell_conf, uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits,
                          float* d_boxes_cxcywh, void* stream);
 
-/* Diagnostics for parity tests: the preprocessed 768x768 u8 image of the LAST chunk's image 0
- * (after bicubic) and its patch-embed A operand can be read back.  d_out_patches is [B*np, 3*P*P] for the handle's
+/* Diagnostics for parity tests: the preprocessed u8 images (after bicubic; 768 x 768, or the handle's input_h x input_w)
+ * and their patch-embed A operand can be read back.  d_out_patches is [B*np, 3*P*P] for the handle's
  * patch size P: [B*576, 3072] at B/32, [B*2304, 768] at B/16 (row b*np + (y/P)*G + x/P, column c*P*P + (y%P)*P + x%P). */
 int tstar_owl_debug_preprocess(tstar_owl* h, const uint8_t* d_images, int B, int H, int W,
-                               uint8_t* d_out_u8 /* [B,768,768,3] */, float* d_out_patches /* [B*np,3*P*P] */,
+                               uint8_t* d_out_u8 /* [B,input_h,input_w,3] */, float* d_out_patches /* [B*np,3*P*P] */,
                                void* stream);
 
 /* ------------------------------------------------------------------ second detector backend: YOLO-World (D13)

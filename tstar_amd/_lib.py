@@ -28,6 +28,8 @@ SIGNATURES = {
     "tstar_owl_create": (_i, [C.POINTER(_vp), _vp, _sz, _vp, _sz, _vp, _i, _i]),
     "tstar_owl_create_ex": (_i, [C.POINTER(_vp), _i, _i, _vp, _sz, _vp, _sz, _vp, _i, _i]),
     "tstar_owl_vision_blob_floats_ex": (_sz, [_i, _i]),
+    "tstar_owl_create_in": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _i, _i]),
+    "tstar_owl_vision_blob_floats_in": (_sz, [_i, _i, _i]),
     "tstar_owl_num_patches": (_i, [_vp]),
     "tstar_owl_destroy": (_i, [_vp]),
     "tstar_owl_set_queries": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),

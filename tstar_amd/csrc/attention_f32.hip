@@ -18,6 +18,12 @@
 //    lane-local.
 //  * T = 32 n + 1 (577 = 576 patches + CLS): the straggler key is folded in after
 //    the block loop with VALU ops (tail_key) instead of a 19th, 97 % empty block.
+//    Every other T >= 1 (an input size other than 768 x 768: T = 337 at 448 x 768, 3601 at 3600 patches) runs
+//    ceil(T / 32) key tiles, the last one MASKED: its staged rows past T - 1 are copies of row T - 1 (the row
+//    index is clamped, so nothing behind the last image of the workspace is read), their scores are set to
+//    -inf and their probabilities are exp2(-inf) = 0 exactly; same loop, same single barrier per tile
+//    (tests/test_gpu_owl_input_size.py).  The query tail form (tail16) needs T = 128 n + 65, which implies
+//    T = 32 n + 1; other T use the generic last query block.
 //  * K/V tiles (32 keys) are staged global -> VGPR -> LDS, double-buffered, one
 //    barrier per tile; K rows are 64 floats with an XOR swizzle of the float4
 //    column (conflict-free ds_read_b128, 32 KB of LDS per workgroup),

@@ -18,7 +18,9 @@
 //  * LDS (16 KB per buffer, double buffered): K planes 2 x 32 x 128 B, 16-B chunks XOR-swizzled by
 //    (key >> 1) & 7; V^T planes 2 x 64 x 64 B, 8-B units XOR-swizzled by (d >> 2) & 7: fragment reads are
 //    conflict-free, staging writes at most 2-way (free for ds_write_b32).
-//  * T = 32 n + 1: the straggler key is folded in with VALU ops after the loop, as in attention_f32.hip.
+//  * T = 32 n + 1: the straggler key is folded in with VALU ops after the loop, as in attention_f32.hip.  Any other T
+//    runs ceil(T / 32) key tiles with the last one masked (rows past T - 1 staged as copies of row T - 1, scores -inf,
+//    probabilities exactly 0), as there.
 #include "common.h"
 #include "kernels.h"
 #include "prof.h"

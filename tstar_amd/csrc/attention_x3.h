@@ -19,6 +19,10 @@
 //    (80-B rows, keys permuted so that a lane's eight keys of a step are one 16-B chunk; V is transposed while staged) triple-buffered because tile t + 2 is
 //    written while tile t is read: 69 KB per workgroup, 2 workgroups per CU (256 registers per wave).
 //  * T = 32 n + 1 (577): the straggler key is folded in with f32 VALU ops after the loop (q rebuilt exactly from its terms).
+//    Any other T (337 at a 448 x 768 input, 3601 at 3600 patches) runs ceil(T / 32) key tiles, the last one masked in the peeled
+//    iterations (soft_piece 0): its rows past T - 1 are staged as ZEROS (the buffer resource ends at the image's last row, so
+//    nothing behind the last image of the workspace is read), their scores are set to -inf and their probabilities are
+//    exp2(-inf) = 0 exactly.  Same pipeline, one barrier per tile.
 //  * measured (B = 256, T = 577, 12 heads; tools/lab/attn_lab.hip, profiles/r05_attention_x3_lab.log, r05_attention_x3_counters.md):
 //    154 TFLOP/s algorithmic (0.92 PFLOP/s executed) against 120-125 for attention_f32_kernel, 147 vs 103 inside the bench; error
 //    against float64 below the f32 kernel's (tests/test_gpu_kernels.py::test_attention_x3).  Matrix pipe busy 0.51: the kernel is

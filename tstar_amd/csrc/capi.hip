@@ -110,7 +110,7 @@ struct tstar_owl {
     int *d_ids = nullptr, *d_eos = nullptr;
     uint8_t* d_kmask = nullptr;
     int seq_cap = TSTAR_OWL_MAX_QUERIES;                             // sequences the three staging buffers above hold
-    std::map<int, ResampleTable> tabs;   // in_size -> table to 768
+    std::map<std::pair<int, int>, ResampleTable> tabs;   // (in_size, out_size) -> table (out_size: the handle's input width / height)
     // weights_mode 1 / 3 (BASELINE config 5, bf16 weights; two-term / exact three-term activations): bfloat16 copy of every
     // GEMM weight matrix; weights_mode 4 (f32x3): every f32 matrix as three exact bf16 planes in MFMA-fragment order
     int weights_mode = TSTAR_WEIGHTS_F32;
@@ -168,23 +168,30 @@ static size_t vision_floats(const OwlGeom& g) {
     size_t n = 0; VisionW w; map_vision(w, g, [&](size_t k) -> const float* { n += k; return nullptr; }); return n;
 }
 
-// Images per forward chunk.  B/16 has four times B/32's tokens per image; a chunk is capped so that it never holds more
-// rows than B/32's largest chunk (1024 images x 577 tokens, the row range every kernel of the forward already runs at):
-// 1024 images at B/32, 256 at B/16 (590080 rows; hid [Mp, 3072] = 1.81e9 floats).  Every workspace then stays below 2^31
-// elements, so the kernels' 32-bit element offsets (the wide GEMM epilogue's among them) cannot wrap; checked at creation.
-static int owl_chunk_limit(const OwlGeom& g) { return 1024 * V_NP / g.np; }
-static size_t lane_rows(int cap, const OwlGeom& g) { return round_up((size_t)cap * g.ntok, 128); }
+// Images per forward chunk.  A chunk is capped so that it never holds more rows than B/32's largest chunk at 768 x 768 (1024
+// images x 577 tokens, the row range every kernel of the forward already runs at): 1024 images at B/32, 256 at B/16 (590080
+// rows; hid [Mp, 3072] = 1.81e9 floats), 164 at 3600 patches; 1024 (the max_batch limit) at every input with fewer tokens than
+// 577.  Every workspace then stays below 2^31 elements, so the kernels' 32-bit element offsets (the wide GEMM epilogue's
+// among them) cannot wrap; checked at creation.
+static int owl_chunk_limit(const OwlGeom& g) { const int n = 1024 * V_NTOK / g.ntok; return n < 1024 ? n : 1024; }
+// rows of a lane's workspaces: the chunk's tokens, and never fewer than the text tower's largest forward through
+// tstar_owl_set_queries (32 sequences of 16 tokens), which runs in lane 0 (a small input at a small max_batch has fewer tokens)
+static size_t lane_rows(int cap, const OwlGeom& g) {
+    const size_t rows = round_up((size_t)cap * g.ntok, 128), text_rows = (size_t)TSTAR_OWL_MAX_QUERIES * T_LEN;
+    return rows > text_rows ? rows : text_rows;
+}
 static size_t text_floats() {
     size_t n = 0; TextW w; map_text(w, [&](size_t k) -> const float* { n += k; return nullptr; }); return n;
 }
 
-static int get_table(tstar_owl* h, int in_size, ResampleTable** out, hipStream_t s) {
-    auto it = h->tabs.find(in_size);
+static int get_table(tstar_owl* h, int in_size, int out_size, ResampleTable** out, hipStream_t s) {
+    const auto key = std::make_pair(in_size, out_size);
+    auto it = h->tabs.find(key);
     if (it == h->tabs.end()) {
         ResampleTable t;
-        int rc = build_bicubic_table(&t, in_size, 768, s);
+        int rc = build_bicubic_table(&t, in_size, out_size, s);
         if (rc) return rc;
-        it = h->tabs.emplace(in_size, t).first;
+        it = h->tabs.emplace(key, t).first;
     }
     *out = &it->second;
     return TSTAR_OK;
@@ -231,9 +238,10 @@ static int run_encoder(tstar_owl* h, tstar_owl::Lane& L, const LayerW* layers, i
 static int preprocess_chunk(tstar_owl* h, tstar_owl::Lane& L, const uint8_t* d_images, int B, int H, int W, uint8_t* out_u8,
                             float* out_patches, hipStream_t s) {
     ResampleTable *th, *tv;
-    RC(get_table(h, W, &th, s));
-    RC(get_table(h, H, &tv, s));
-    const size_t need = (size_t)B * H * 768 * 3;
+    const OwlGeom& G = h->geom;
+    RC(get_table(h, W, G.in_w, &th, s));
+    RC(get_table(h, H, G.in_h, &tv, s));
+    const size_t need = (size_t)B * H * G.in_w * 3;
     if (need > L.tmp_u8_bytes) {
         TSTAR_HIP_CHECK(hipStreamSynchronize(s));
         if (L.tmp_u8) TSTAR_HIP_CHECK(hipFree(L.tmp_u8));
@@ -242,7 +250,7 @@ static int preprocess_chunk(tstar_owl* h, tstar_owl::Lane& L, const uint8_t* d_i
         L.tmp_u8_bytes = need;
     }
     RC(resample_h_u8(d_images, L.tmp_u8, B, H, W, *th, s));
-    RC(resample_v_normalize_patchify(L.tmp_u8, out_patches, out_u8, B, H, *tv, h->d_lut, h->geom.patch, s));
+    RC(resample_v_normalize_patchify(L.tmp_u8, out_patches, out_u8, B, H, G.in_w, *tv, h->d_lut, G.patch, s));
     return TSTAR_OK;
 }
 
@@ -272,6 +280,14 @@ size_t tstar_owl_text_blob_floats(void) { return text_floats(); }
 size_t tstar_owl_vision_blob_floats_ex(int image_size, int patch_size) {
     OwlGeom g;
     if (!owl_geom(image_size, patch_size, &g)) { set_error("tstar_owl_vision_blob_floats_ex: unsupported geometry (image 768, patch 32 or 16)"); return 0; }
+    return vision_floats(g);
+}
+size_t tstar_owl_vision_blob_floats_in(int input_h, int input_w, int patch_size) {
+    OwlGeom g;
+    if (!owl_geom_input(input_h, input_w, patch_size, &g)) {
+        set_error("tstar_owl_vision_blob_floats_in: unsupported input size (patch 32 or 16; each side a positive multiple of the patch size; at most 3600 patches)");
+        return 0;
+    }
     return vision_floats(g);
 }
 int tstar_owl_num_patches(tstar_owl* h) {
@@ -333,6 +349,15 @@ int tstar_owl_create_ex(tstar_owl** out, int image_size, int patch_size, const f
     OwlGeom geom;
     TSTAR_REQUIRE(owl_geom(image_size, patch_size, &geom),
                   "tstar_owl_create_ex: unsupported geometry; supported: image 768 with patch 32 (B/32) or 16 (B/16)");
+    return tstar_owl_create_in(out, geom.in_h, geom.in_w, patch_size, h_vision_blob, n_vision, h_text_blob, n_text, h_norm_lut, max_batch, weights_mode);
+}
+
+int tstar_owl_create_in(tstar_owl** out, int input_h, int input_w, int patch_size, const float* h_vision_blob, size_t n_vision,
+                        const float* h_text_blob, size_t n_text, const float* h_norm_lut, int max_batch, int weights_mode) {
+    OwlGeom geom;
+    TSTAR_REQUIRE(owl_geom_input(input_h, input_w, patch_size, &geom),
+                  "tstar_owl_create_in: unsupported input size; supported: patch 32 (B/32) or 16 (B/16), each side of the input a positive "
+                  "multiple of the patch size, at most 3600 patches");
     TSTAR_REQUIRE(out && (h_vision_blob || h_text_blob), "tstar_owl_create: null argument");
     TSTAR_REQUIRE(!h_vision_blob || h_norm_lut, "tstar_owl_create: the vision tower needs the normalisation LUT");
     TSTAR_REQUIRE(h_vision_blob || weights_mode == TSTAR_WEIGHTS_F32, "tstar_owl_create: a text-only handle runs in float32");

@@ -45,8 +45,9 @@ void free_table(ResampleTable* t);
 
 // u8 [B,H,W,3] -> u8 [B,H,OW,3]   (Pillow 8bpc horizontal pass)
 int resample_h_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const ResampleTable& t, hipStream_t s);
-// u8 [B,H,768,3] -> vertical pass -> LUT normalise -> im2col f32 [B*np, 3*patch^2] (patch 32: [B*576, 3072]; 16: [B*2304, 768])
-int resample_v_normalize_patchify(const uint8_t* in, float* out, uint8_t* out_u8, int B, int H, const ResampleTable& t,
+// u8 [B,H,OW,3] -> vertical pass to t.out_size rows -> LUT normalise -> im2col f32 [B*np, 3*patch^2] (768 x 768: patch 32
+// [B*576, 3072], patch 16 [B*2304, 768]); OW and t.out_size are multiples of the patch size
+int resample_v_normalize_patchify(const uint8_t* in, float* out, uint8_t* out_u8, int B, int H, int OW, const ResampleTable& t,
                                   const float* lut, int patch, hipStream_t s);
 
 // jpeg.hip: n frames of coefficient blocks [n][g.blocks()][64] + tables u16 [n][3][64] -> RGB u8 [n,H,W,3]; planes is a

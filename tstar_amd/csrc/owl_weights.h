@@ -10,16 +10,30 @@ namespace tstar {
 constexpr int V_D = 768, V_FF = 3072, V_LAYERS = 12, V_HEADS = 12, V_NP = 576, V_NTOK = 577, V_PATCH_K = 3072;
 constexpr int T_D = 512, T_FF = 2048, T_LAYERS = 12, T_HEADS = 8, T_LEN = 16, T_VOCAB = 49408, PROJ = 512;
 
-// Patch geometry of the vision tower: every supported checkpoint shares the widths above and differs only here.
+// Patch geometry of the vision tower: every supported checkpoint shares the widths above and differs only here.  image / grid
+// describe the CHECKPOINT (its position table is grid x grid); in_h x in_w is the input size of the RUN (a property of the
+// handle; the checkpoint's own 768 x 768 unless the handle was created with another one), gh x gw its patch grid, np = gh gw
+// the patches and ntok = np + 1 the tokens per image.
+constexpr int V_MAX_NP = 3600;
 struct OwlGeom {
     int image = 768, patch = 32, grid = 24, np = V_NP, ntok = V_NTOK, patch_k = V_PATCH_K;
+    int in_h = 768, in_w = 768, gh = 24, gw = 24;
 };
+// the run geometry of a (input_h, input_w) input at patch 32 / 16, or false when the size is not supported: each side a
+// positive multiple of the patch size, at most V_MAX_NP patches
+inline bool owl_geom_input(int input_h, int input_w, int patch_size, OwlGeom* g) {
+    if (patch_size != 32 && patch_size != 16) return false;
+    if (input_h <= 0 || input_w <= 0 || input_h % patch_size || input_w % patch_size) return false;
+    if ((long long)(input_h / patch_size) * (input_w / patch_size) > V_MAX_NP) return false;
+    g->image = 768; g->patch = patch_size; g->grid = 768 / patch_size;
+    g->in_h = input_h; g->in_w = input_w; g->gh = input_h / patch_size; g->gw = input_w / patch_size;
+    g->np = g->gh * g->gw; g->ntok = g->np + 1; g->patch_k = 3 * patch_size * patch_size;
+    return true;
+}
 // the geometry of (image_size, patch_size), or false when it is not supported (B/32 and B/16: image 768, patch 32 / 16)
 inline bool owl_geom(int image_size, int patch_size, OwlGeom* g) {
     if (image_size != 768 || (patch_size != 32 && patch_size != 16)) return false;
-    g->image = image_size; g->patch = patch_size; g->grid = image_size / patch_size;
-    g->np = g->grid * g->grid; g->ntok = g->np + 1; g->patch_k = 3 * patch_size * patch_size;
-    return true;
+    return owl_geom_input(image_size, image_size, patch_size, g);
 }
 
 struct LayerW {

@@ -1,6 +1,6 @@
 // Detector pre-processing kernels (byte work, HBM-bound; no MFMA):
 //
-//  * Pillow-compatible 8-bit BICUBIC resampling to 768x768, exactly as the HF
+//  * Pillow-compatible 8-bit BICUBIC resampling to 768x768 (or the handle's input size), exactly as the HF
 //    OWL-ViT image processor applies it to the grid image
 //    (/root/reference/TStar/interface_heuristic.py:234 -> HF
 //    image_processing_pil_owlvit.py:109-119 -> PIL.Image.resize(BICUBIC);
@@ -113,32 +113,37 @@ int resample_h_u8(const uint8_t* in, uint8_t* out, int B, int H, int W, const Re
     return TSTAR_OK;
 }
 
-// in u8 [B,H,768,3]; vertical pass to 768 rows; LUT normalise; write the patch-embed
-// A operand for patch size P (grid G = 768 / P, np = G^2 patches per image, K = 3 P^2):
-// row = b*np + (y/P)*G + x/P, col = c*P^2 + (y%P)*P + x%P  (P = 32: b*576 + (y/32)*24 + x/32, c*1024 + (y%32)*32 + x%32).
+// in u8 [B,H,OW,3]; vertical pass to OH rows; LUT normalise; write the patch-embed
+// A operand for patch size P (patch grid GH x GW = OH / P x OW / P, np = GH GW patches per image, K = 3 P^2):
+// row = b*np + (y/P)*GW + x/P, col = c*P^2 + (y%P)*P + x%P  (768 x 768, P = 32: b*576 + (y/32)*24 + x/32, c*1024 + (y%32)*32 + x%32).
 // One thread per (b, y, x); x fastest -> 32 consecutive threads write 128 contiguous bytes per channel.
 // Round 6: FOUR consecutive x per thread (12 source bytes = three dwords per tap and row instead of twelve byte loads, the products on the
 // full-rate v_mad_i32_i24 -- |k| <= 2^22, pixels <= 255: the same 32-bit values --, one float4 store per channel: 4 | P, so the four stay in
 // one patch row, 16-byte aligned), the normalisation LUT in LDS.  Same integers, same LUT entries: bit-exact
 // (tests/test_gpu_detector.py::test_preprocess_*; P = 16: tests/test_gpu_owl_b16.py).
-template <int P>
+// SQ768: the checkpoint's own 768 x 768 output with every extent a compile-time constant (the default input size); otherwise
+// the output size (OWr x OHr, both multiples of P, so 4 | OWr and the rows of 3 OWr bytes stay dword-aligned) comes at run time
+// (tests/test_gpu_owl_input_size.py).
+template <int P, bool SQ768>
 __global__ __launch_bounds__(256) void resample_v_patchify_kernel(const uint8_t* __restrict__ in, float* __restrict__ out,
-                                                                  uint8_t* __restrict__ out_u8, int H, int ksize,
+                                                                  uint8_t* __restrict__ out_u8, int H, int OWr, int OHr, int ksize,
                                                                   const int* __restrict__ bounds,
                                                                   const int* __restrict__ coefs,
                                                                   const float* __restrict__ lut, size_t total4) {
     static_assert(P == 32 || P == 16, "patch sizes 32 and 16");
-    constexpr int SH = P == 32 ? 5 : 4, G = 768 / P, NP = G * G, PP = P * P, K = 3 * PP;
+    constexpr int SH = P == 32 ? 5 : 4, PP = P * P, K = 3 * PP;
+    const int OW = SQ768 ? 768 : OWr, OH = SQ768 ? 768 : OHr;
+    const int GW = OW >> SH, NP = (OH >> SH) * GW, W4 = OW >> 2;
     __shared__ float slut[768];
     for (int i = threadIdx.x; i < 768; i += 256) slut[i] = lut[i];
     __syncthreads();
     const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= total4) return;
-    const int x = (int)(gid % 192) * 4;
-    const int y = (int)((gid / 192) % 768);
-    const size_t b = gid / (192 * 768);
+    const int x = (int)(gid % W4) * 4;
+    const int y = (int)((gid / W4) % OH);
+    const size_t b = gid / ((size_t)W4 * OH);
     const int ymin = bounds[y * 2], n = bounds[y * 2 + 1];
-    const uint8_t* src = in + ((b * H + ymin) * 768 + x) * 3;          // 12 bytes per tap row, dword-aligned (x % 4 == 0, rows of 2304 bytes)
+    const uint8_t* src = in + ((b * H + ymin) * OW + x) * 3;           // 12 bytes per tap row, dword-aligned (x % 4 == 0, rows of 3 OW bytes, 4 | OW)
     const int* k = coefs + (size_t)y * ksize;
     int s[4][3];
 #pragma unroll
@@ -147,7 +152,7 @@ __global__ __launch_bounds__(256) void resample_v_patchify_kernel(const uint8_t*
         for (int c = 0; c < 3; ++c) s[j][c] = 1 << 21;
     for (int i = 0; i < n; ++i) {
         const int kk = k[i];
-        const unsigned* p = reinterpret_cast<const unsigned*>(src + (size_t)i * 768 * 3);
+        const unsigned* p = reinterpret_cast<const unsigned*>(src + (size_t)i * OW * 3);
         const unsigned w[3] = {p[0], p[1], p[2]};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -162,8 +167,8 @@ __global__ __launch_bounds__(256) void resample_v_patchify_kernel(const uint8_t*
     for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[j][c] = clip8(s[j][c]);
-    if (out_u8) store_px4(out_u8 + ((b * 768 + y) * 768 + x) * 3, v);
-    const size_t row = b * NP + (size_t)(y >> SH) * G + (x >> SH);
+    if (out_u8) store_px4(out_u8 + ((b * OH + y) * OW + x) * 3, v);
+    const size_t row = b * NP + (size_t)(y >> SH) * GW + (x >> SH);
     float* o = out + row * K + (y & (P - 1)) * P + (x & (P - 1));
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -174,16 +179,19 @@ __global__ __launch_bounds__(256) void resample_v_patchify_kernel(const uint8_t*
     }
 }
 
-int resample_v_normalize_patchify(const uint8_t* in, float* out, uint8_t* out_u8, int B, int H, const ResampleTable& t,
+int resample_v_normalize_patchify(const uint8_t* in, float* out, uint8_t* out_u8, int B, int H, int OW, const ResampleTable& t,
                                   const float* lut, int patch, hipStream_t s) {
-    TSTAR_REQUIRE(t.in_size == H && t.out_size == 768, "resample_v: table must map H -> 768");
+    const int OH = t.out_size;
+    TSTAR_REQUIRE(t.in_size == H, "resample_v: table must map H -> the output height");
     TSTAR_REQUIRE(patch == 32 || patch == 16, "resample_v: patch size must be 32 or 16");
-    const size_t total4 = (size_t)B * 768 * 192;                        // four consecutive x per thread
+    TSTAR_REQUIRE(OW > 0 && OH > 0 && OW % patch == 0 && OH % patch == 0, "resample_v: the output size must be a positive multiple of the patch size");
+    const size_t total4 = (size_t)B * OH * (OW / 4);                    // four consecutive x per thread
     const dim3 grid((unsigned)((total4 + 255) / 256));
-    if (patch == 32)
-        hipLaunchKernelGGL(resample_v_patchify_kernel<32>, grid, dim3(256), 0, s, in, out, out_u8, H, t.ksize, t.d_bounds, t.d_coefs, lut, total4);
-    else
-        hipLaunchKernelGGL(resample_v_patchify_kernel<16>, grid, dim3(256), 0, s, in, out, out_u8, H, t.ksize, t.d_bounds, t.d_coefs, lut, total4);
+    const bool sq = OW == 768 && OH == 768;
+#define TSTAR_RV_LAUNCH(P, SQ) hipLaunchKernelGGL((resample_v_patchify_kernel<P, SQ>), grid, dim3(256), 0, s, in, out, out_u8, H, OW, OH, t.ksize, t.d_bounds, t.d_coefs, lut, total4)
+    if (patch == 32) { if (sq) TSTAR_RV_LAUNCH(32, true); else TSTAR_RV_LAUNCH(32, false); }
+    else { if (sq) TSTAR_RV_LAUNCH(16, true); else TSTAR_RV_LAUNCH(16, false); }
+#undef TSTAR_RV_LAUNCH
     TSTAR_HIP_CHECK(hipGetLastError());
     return TSTAR_OK;
 }

@@ -71,7 +71,7 @@ class OWLInterface(HeuristicInterface):
     def __init__(self, model_name_or_path: str = "google/owlvit-base-patch32", device: str = "cuda",
                  max_batch: Optional[int] = None, synthetic_seed: Optional[int] = None, state_dict: Optional[Dict] = None,
                  weights_dtype: Optional[str] = None, allow_standin_tokenizer: Optional[bool] = None,
-                 patch_size: Optional[int] = None):
+                 patch_size: Optional[int] = None, input_size=None):
         """``device`` must be a HIP device (default "cuda" as in the reference, :201).
 
         Supported checkpoints: OWL-ViT B/32 (``google/owlvit-base-patch32``, the default) and B/16
@@ -82,11 +82,20 @@ class OWLInterface(HeuristicInterface):
         geometry is kept as ``self.geometry`` (``weights.OwlGeometry``); ``inference_detector`` returns
         ``self.geometry.npatch`` detections (patch order) when every patch passes the threshold.
 
+        ``input_size=(height, width)``: the size every image is resampled to (Pillow bicubic) before the vision tower, fixed
+        for the heuristic's life; default the checkpoint's own 768 x 768.  Any other size is HF's
+        ``forward(..., interpolate_pos_encoding=True)`` behind an image processor of that ``size``: the position table is
+        resampled to the (height / patch) x (width / patch) grid and ``box_bias`` is built for it.  Each side must be a
+        positive multiple of the patch size and the grid may hold at most 3600 patches (ValueError otherwise, before anything
+        is allocated).  ``self.geometry`` then carries the size (``geometry.input_size``, ``geometry.npatch``) and compares
+        unequal to ``weights.B32`` / ``B16``; ``geometry.checkpoint`` is the checkpoint's own.
+
         Under an UNCHANGED ``TStarFramework`` the heuristic is built by ``initialize_heuristic(heuristic_type)`` without keyword
-        arguments (TStarFramework.py:171-187, 207), so the three arguments a deployment chooses can also come from the environment
+        arguments (TStarFramework.py:171-187, 207), so the four arguments a deployment chooses can also come from the environment
         -- read only when the keyword is not given: ``TSTAR_WEIGHTS_DTYPE`` (``weights_dtype``; default "f32"),
-        ``TSTAR_MAX_BATCH`` (``max_batch``; default 32) and ``TSTAR_SYNTHETIC_SEED`` (``synthetic_seed``; unset = no synthetic
-        weights: a missing checkpoint raises).
+        ``TSTAR_MAX_BATCH`` (``max_batch``; default 32), ``TSTAR_SYNTHETIC_SEED`` (``synthetic_seed``; unset = no synthetic
+        weights: a missing checkpoint raises) and ``TSTAR_INPUT_SIZE`` (``input_size`` as ``HEIGHTxWIDTH``, e.g. ``448x768``;
+        unset = the checkpoint's own size).
 
         Weights: ``state_dict`` (HF names) if given; else a local safetensors checkpoint of
         ``model_name_or_path`` if one exists on disk; else, only when ``synthetic_seed`` is not None,
@@ -119,14 +128,17 @@ class OWLInterface(HeuristicInterface):
             torch.cuda.set_device(dev.index)
         if patch_size is not None:
             W.geometry_for_patch(int(patch_size))                  # an unsupported value fails here, whatever the weights
+        input_size = W.resolve_input_size(input_size)              # a malformed TSTAR_INPUT_SIZE fails here
         if state_dict is None:
             ckpt = W.find_pretrained(model_name_or_path)
             if ckpt is not None:
                 geometry = W.geometry_of_checkpoint(ckpt)          # before the weights are read or anything is allocated
+                W.with_input_size(geometry, input_size)            # likewise
                 state_dict = W.load_safetensors_state_dict(ckpt)
                 self.weights_source = ckpt
             elif synthetic_seed is not None:
                 geometry = W.geometry_for_patch(32 if patch_size is None else int(patch_size))
+                W.with_input_size(geometry, input_size)
                 state_dict = W.synthetic_state_dict(int(synthetic_seed), geometry=geometry)
                 self.weights_source = f"synthetic(seed={int(synthetic_seed)})"
             else:
@@ -139,6 +151,7 @@ class OWLInterface(HeuristicInterface):
         if patch_size is not None and int(patch_size) != geometry.patch_size:
             raise ValueError(f"patch_size={int(patch_size)} disagrees with the weights of {self.weights_source!r}, which are "
                              f"{geometry.name} (patch {geometry.patch_size})")
+        geometry = W.with_input_size(geometry, input_size)
         self.geometry = geometry
         if allow_standin_tokenizer is None:
             allow_standin_tokenizer = self.weights_source.startswith("synthetic(")
@@ -147,8 +160,9 @@ class OWLInterface(HeuristicInterface):
             state_dict = W.round_weights_to_bf16(state_dict)
         self.weights_dtype = weights_dtype
         self.model_name_or_path = model_name_or_path
-        self.scorer = OwlScorer(W.pack_blob(state_dict, W.vision_spec(geometry)), W.pack_blob(state_dict, W.text_spec()),
-                                max_batch=max_batch, weights_mode=weights_dtype, patch_size=geometry.patch_size)
+        self.scorer = OwlScorer(W.pack_blob(state_dict, W.vision_spec(geometry), geometry), W.pack_blob(state_dict, W.text_spec()),
+                                max_batch=max_batch, weights_mode=weights_dtype, patch_size=geometry.patch_size,
+                                input_size=None if geometry == geometry.checkpoint else geometry.input_size)
         self.device = device
         self.texts = ["couch", "table", "woman"]      # as the reference leaves it before reparameterisation (:203)
         self.detections_inbatch: List[Detections] = []
@@ -485,7 +499,8 @@ def draw_boxes(image: np.ndarray, det: Detections, color=(255, 64, 64)) -> np.nd
 
 def initialize_heuristic(heuristic_type: str = "owl-vit", **kwargs) -> HeuristicInterface:
     """Factory with the reference's signature (TStarFramework.py:171-187).  ``model_name_or_path=`` overrides the OWL-ViT
-    checkpoint (default ``google/owlvit-base-patch32``; B/16 checkpoints are supported too)."""
+    checkpoint (default ``google/owlvit-base-patch32``; B/16 checkpoints are supported too); ``input_size=(height, width)``
+    overrides the detector's input size (default the checkpoint's 768 x 768; ``TSTAR_INPUT_SIZE=HxW`` when not given)."""
     if heuristic_type == "owl-vit":
         kwargs.setdefault("model_name_or_path", "google/owlvit-base-patch32")
         return OWLInterface(**kwargs)

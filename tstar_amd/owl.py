@@ -37,7 +37,7 @@ def normalize_lut() -> np.ndarray:
 
 @dataclass
 class ScoreResult:
-    """Device tensors produced by one tstar_owl_score call (np = 576 at B/32, 2304 at B/16)."""
+    """Device tensors produced by one tstar_owl_score call (np = 576 at B/32, 2304 at B/16; gh * gw at another input size)."""
     scores: "object"       # f32 [B,np]
     labels: "object"       # i32 [B,np]
     boxes: "object"        # f32 [B,np,4] xyxy pixels
@@ -54,12 +54,16 @@ class OwlScorer:
     WEIGHTS_MODES = {"f32": 0, "bf16": 1, "bf16_exact": 3, "f32x3": 4}      # TSTAR_WEIGHTS_* of include/tstar_hip.h
 
     def __init__(self, vision_blob: Optional[np.ndarray], text_blob: Optional[np.ndarray] = None, max_batch: int = 32,
-                 weights_mode: str = "f32", patch_size: int = 32):
+                 weights_mode: str = "f32", patch_size: int = 32, input_size=None):
         """``vision_blob=None`` gives a text-only handle: ``set_queries`` / ``get_query_embeds`` work (the CLIP text
         features of the YOLO-World backend), ``score`` raises.  ``patch_size``: 32 (B/32) or 16 (B/16); the vision blob is
-        packed with ``weights.vision_spec`` of that geometry."""
+        packed with ``weights.vision_spec`` of that geometry.  ``input_size=(height, width)``: the size images are resampled
+        to before the vision tower, fixed for the scorer's life (default: the checkpoint's own 768 x 768); the vision blob is
+        then ``pack_blob(sd, vision_spec(g), g)`` with ``g = weights.with_input_size(geometry, input_size)``, and ``score``
+        returns ``(height / patch) * (width / patch)`` detections per image."""
         import torch
-        self.geometry = W.geometry_for_patch(patch_size)           # ValueError before anything touches the device
+        # ValueError before anything touches the device
+        self.geometry = W.with_input_size(W.geometry_for_patch(patch_size), input_size)
         if not torch.cuda.is_available():
             raise _lib.TStarHipError("OwlScorer needs a HIP device (torch.cuda.is_available() is False); "
                                      "tstar_amd has no CPU path")
@@ -75,8 +79,8 @@ class OwlScorer:
             text_blob = np.ascontiguousarray(text_blob, dtype=np.float32)
         lut = normalize_lut()
         h = C.c_void_p()
-        rc = self._lib.tstar_owl_create_ex(
-            C.byref(h), self.geometry.image_size, self.geometry.patch_size,
+        rc = self._lib.tstar_owl_create_in(
+            C.byref(h), self.geometry.input_h, self.geometry.input_w, self.geometry.patch_size,
             None if vision_blob is None else vision_blob.ctypes.data, 0 if vision_blob is None else vision_blob.size,
             None if text_blob is None else text_blob.ctypes.data, 0 if text_blob is None else text_blob.size,
             lut.ctypes.data, int(max_batch), self.WEIGHTS_MODES[weights_mode])
@@ -89,12 +93,12 @@ class OwlScorer:
         self.device = torch.device("cuda", torch.cuda.current_device())
 
     @classmethod
-    def synthetic(cls, seed: int = 0, max_batch: int = 32, with_text: bool = True, patch_size: int = 32):
-        g = W.geometry_for_patch(patch_size)
+    def synthetic(cls, seed: int = 0, max_batch: int = 32, with_text: bool = True, patch_size: int = 32, input_size=None):
+        g = W.with_input_size(W.geometry_for_patch(patch_size), input_size)
         sd = W.synthetic_state_dict(seed, "both" if with_text else "vision", geometry=g)
-        vb = W.pack_blob(sd, W.vision_spec(g))
+        vb = W.pack_blob(sd, W.vision_spec(g), g)
         tb = W.pack_blob(sd, W.text_spec()) if with_text else None
-        return cls(vb, tb, max_batch, patch_size=patch_size)
+        return cls(vb, tb, max_batch, patch_size=patch_size, input_size=input_size)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -247,7 +251,7 @@ class OwlScorer:
         torch = self._torch
         images = images.contiguous()
         B, H, Wd, _ = images.shape
-        u8 = torch.empty((B, 768, 768, 3), dtype=torch.uint8, device=images.device)
+        u8 = torch.empty((B, self.geometry.input_h, self.geometry.input_w, 3), dtype=torch.uint8, device=images.device)
         pat = torch.empty((B * self.num_patches, self.geometry.patch_k), dtype=torch.float32, device=images.device)
         rc = self._lib.tstar_owl_debug_preprocess(self._h, images.data_ptr(), B, H, Wd, u8.data_ptr(),
                                                   pat.data_ptr(), _lib.stream_ptr())

@@ -29,7 +29,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -61,14 +61,42 @@ class OwlGeometry:
     12 layers, 12 heads; the same text tower; projection 512): only the patch grid differs."""
     image_size: int
     patch_size: int
+    # the input size of the RUN in pixels (height, width): a property of the detector handle, not of the checkpoint.  0 = the
+    # checkpoint's own image_size, so OwlGeometry(768, 32) == OwlGeometry(768, 32, 768, 768) == B32.  See with_input_size().
+    input_h: int = 0
+    input_w: int = 0
+
+    def __post_init__(self):
+        if not self.input_h:
+            object.__setattr__(self, "input_h", self.image_size)
+        if not self.input_w:
+            object.__setattr__(self, "input_w", self.image_size)
 
     @property
     def grid(self) -> int:
+        """Side of the CHECKPOINT's square patch grid (what its position table was trained on)."""
         return self.image_size // self.patch_size
 
     @property
+    def gh(self) -> int:
+        return self.input_h // self.patch_size
+
+    @property
+    def gw(self) -> int:
+        return self.input_w // self.patch_size
+
+    @property
+    def input_size(self) -> Tuple[int, int]:
+        return (self.input_h, self.input_w)
+
+    @property
+    def checkpoint(self) -> "OwlGeometry":
+        """The same checkpoint at its own input size."""
+        return OwlGeometry(self.image_size, self.patch_size)
+
+    @property
     def npatch(self) -> int:
-        return self.grid * self.grid
+        return self.gh * self.gw
 
     @property
     def ntok(self) -> int:
@@ -88,6 +116,46 @@ B16 = OwlGeometry(768, 16)     # google/owlvit-base-patch16: grid 48, 2304 patch
 SUPPORTED = (B32, B16)
 SUPPORTED_TEXT = ("OWL-ViT B/32 and B/16 (image 768, patch 32 or 16; vision 768 wide, MLP 3072, 12 layers, 12 heads; "
                   "text 512 wide, MLP 2048, 12 layers, 8 heads; projection 512)")
+
+
+MAX_NPATCH = 3600              # patches per image a run may ask for (T = 3601)
+INPUT_SIZE_RULE = (f"each side of the input size must be a positive multiple of the patch size, and the patch grid may hold at most "
+                   f"{MAX_NPATCH} patches")
+
+
+def with_input_size(geometry: OwlGeometry, input_size=None) -> OwlGeometry:
+    """``geometry`` run at ``input_size`` = (height, width) pixels; None keeps the checkpoint's own size.  ValueError, naming
+    the rule, for a size the detector does not run at -- before anything touches the device."""
+    g = geometry.checkpoint
+    if input_size is None:
+        return g
+    try:
+        h, w = input_size
+        ok = int(h) == h and int(w) == w
+        h, w = int(h), int(w)
+    except (TypeError, ValueError):
+        raise ValueError(f"input_size must be (height, width), not {input_size!r}") from None
+    P = g.patch_size
+    if not ok or h <= 0 or w <= 0 or h % P or w % P or (h // P) * (w // P) > MAX_NPATCH:
+        raise ValueError(f"input_size {input_size!r} is not supported at patch {P}: {INPUT_SIZE_RULE}")
+    return OwlGeometry(g.image_size, P, h, w)
+
+
+def input_size_from_env(name: str = "TSTAR_INPUT_SIZE"):
+    """(height, width) from ``TSTAR_INPUT_SIZE=HxW`` (e.g. ``448x768``), or None when it is unset / empty."""
+    v = os.environ.get(name)
+    if v is None or v.strip() == "":
+        return None
+    parts = v.strip().lower().split("x")
+    if len(parts) != 2 or not all(p.strip().isdigit() for p in parts):
+        raise ValueError(f"{name} must look like HEIGHTxWIDTH (e.g. 448x768), not {v!r}")
+    return int(parts[0]), int(parts[1])
+
+
+def resolve_input_size(input_size=None):
+    """The ``input_size`` keyword if it was given, else ``TSTAR_INPUT_SIZE``, else None: the environment is read only when the
+    keyword is absent, like the other deployment settings of ``OWLInterface``."""
+    return input_size if input_size is not None else input_size_from_env()
 
 
 def geometry_for_patch(patch_size: int) -> OwlGeometry:
@@ -172,27 +240,48 @@ def spec_size(spec: Spec) -> int:
 
 
 def compute_box_bias(geometry: OwlGeometry = B32) -> np.ndarray:
-    """box_bias buffer, restated from modeling_owlvit.py:1072-1104 (``compute_box_bias(G, G)``).
+    """box_bias buffer, restated from modeling_owlvit.py:1072-1104 (``compute_box_bias(gh, gw)``).
 
-    xy = ((col+1)/G, (row+1)/G); bias = log(v+1e-4) - log1p(-v+1e-4); size
-    entries use v = 1/G, G = the patch grid (24 at B/32, 48 at B/16).  Row-major
-    over the G x G patch grid.  Uses torch float32 ops (as HF does) so the buffer
-    is bit-identical to the one HF builds at model init; torch is imported lazily.
+    xy = ((col+1)/gw, (row+1)/gh); bias = log(v+1e-4) - log1p(-v+1e-4); size
+    entries use v = (1/gw, 1/gh); gh x gw = the run's patch grid (24 x 24 at B/32,
+    48 x 48 at B/16, 14 x 24 at B/32 run on 448 x 768).  Row-major over the patch
+    grid.  Uses torch float32 ops (as HF does) so the buffer is bit-identical to
+    the one HF builds; torch is imported lazily.
     """
     import torch
-    G = geometry.grid
-    xs = torch.arange(1, G + 1, dtype=torch.float32)
-    xx, yy = torch.meshgrid(xs, xs, indexing="xy")
+    gh, gw = geometry.gh, geometry.gw
+    xs = torch.arange(1, gw + 1, dtype=torch.float32)
+    ys = torch.arange(1, gh + 1, dtype=torch.float32)
+    xx, yy = torch.meshgrid(xs, ys, indexing="xy")
     coords = torch.stack((xx, yy), dim=-1)
-    coords[..., 0] /= G
-    coords[..., 1] /= G
+    coords[..., 0] /= gw
+    coords[..., 1] /= gh
     coords = torch.clip(coords.view(-1, 2), 0.0, 1.0)
     cb = torch.log(coords + 1e-4) - torch.log1p(-coords + 1e-4)
     size = torch.full_like(cb, 1.0)
-    size[..., 0] /= G
-    size[..., 1] /= G
+    size[..., 0] /= gw
+    size[..., 1] /= gh
     sb = torch.log(size + 1e-4) - torch.log1p(-size + 1e-4)
     return torch.cat([cb, sb], dim=-1).numpy().astype(np.float32)
+
+
+def interpolate_pos_emb(pos_emb: np.ndarray, geometry: OwlGeometry) -> np.ndarray:
+    """The checkpoint's position table [G*G + 1, 768] as the run's [gh*gw + 1, 768], with the statements of HF's
+    ``OwlViTVisionEmbeddings.interpolate_pos_encoding``: row 0 (CLS) kept, the G x G patch rows resampled to gh x gw with
+    ``torch.nn.functional.interpolate(mode="bicubic", align_corners=False)`` on the CPU.  At gh = gw = G the table is
+    returned unchanged, as HF does.  torch is imported lazily."""
+    g = geometry
+    G = g.grid
+    pos = np.ascontiguousarray(pos_emb, dtype=np.float32).reshape(G * G + 1, V_D)
+    if g.gh == G and g.gw == G:
+        return pos
+    import torch
+    t = torch.from_numpy(pos).unsqueeze(0)
+    cls, patch = t[:, :1], t[:, 1:]
+    patch = patch.reshape(1, G, G, V_D).permute(0, 3, 1, 2)
+    patch = torch.nn.functional.interpolate(patch, size=(g.gh, g.gw), mode="bicubic", align_corners=False)
+    patch = patch.permute(0, 2, 3, 1).reshape(1, -1, V_D)
+    return np.ascontiguousarray(torch.cat((cls, patch), dim=1)[0].numpy(), dtype=np.float32)
 
 
 def _std_for(name: str, shape: Tuple[int, ...]) -> float:
@@ -249,6 +338,7 @@ def synthetic_state_dict(seed: int = 0, towers: str = "both", geometry: OwlGeome
                     x = (x * np.float32(0.01)).astype(np.float32)
                 out[hf] = x
 
+    geometry = geometry.checkpoint
     if towers in ("both", "vision"):
         fill(vision_spec(geometry), np.random.RandomState(seed))
     if towers in ("both", "text"):
@@ -260,6 +350,7 @@ _HF_SHAPES: Dict[OwlGeometry, Dict[str, Tuple[int, ...]]] = {}
 
 
 def _hf_shape(hf: str, geometry: OwlGeometry = B32) -> Tuple[int, ...]:
+    geometry = geometry.checkpoint                  # a state dict holds the checkpoint's tables, whatever size it is run at
     shapes = _HF_SHAPES.get(geometry)
     if shapes is None:
         shapes = _HF_SHAPES[geometry] = {}
@@ -295,12 +386,22 @@ def round_weights_to_bf16(sd: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     return out
 
 
-def pack_blob(sd: Dict[str, np.ndarray], spec: Spec) -> np.ndarray:
+def pack_blob(sd: Dict[str, np.ndarray], spec: Spec, geometry: Optional[OwlGeometry] = None) -> np.ndarray:
     """Concatenate ``sd`` entries into the flat f32 blob the C ABI expects.  ``box_bias`` is a non-persistent buffer in
-    transformers 5.x (not in the state dict): when it is missing it is computed for the spec's patch grid."""
+    transformers 5.x (not in the state dict): when it is missing it is computed for the spec's patch grid.
+
+    ``geometry`` (with ``spec = vision_spec(geometry)``): a run at another input size than the checkpoint's.  ``pos_emb`` is
+    then the checkpoint's table resampled to the run's grid (``interpolate_pos_emb``) and ``box_bias`` is computed for that
+    grid (``compute_box_bias``), whatever the state dict holds: both are HF's own values under
+    ``interpolate_pos_encoding=True``, bit for bit."""
     parts = []
+    resized = geometry is not None and geometry != geometry.checkpoint
     for name, shape, hf_names in spec:
-        if name == "box_bias" and "box_bias" not in sd:
+        if resized and name == "pos_emb":
+            arr = interpolate_pos_emb(np.asarray(sd[hf_names[0]], dtype=np.float32), geometry)
+        elif resized and name == "box_bias":
+            arr = compute_box_bias(geometry)
+        elif name == "box_bias" and "box_bias" not in sd:
             g = next((g for g in SUPPORTED if g.npatch == shape[0]), None)
             if g is None:
                 raise ValueError(f"weight box_bias: no supported geometry has {shape[0]} patches")
