@@ -227,6 +227,35 @@ int tstar_yolo_postprocess(tstar_yolo* h, const float* const* d_level_embed, con
                            float* d_det_scores, int32_t* d_det_labels, float* d_det_boxes, int32_t* d_n_det, double* d_cell_conf,
                            uint32_t* d_cell_mask, float* d_dense_scores, float* d_dense_boxes, void* stream);
 
+/* Diagnostics (added entries; tstar_abi_version() stays 3): the layer ops of a handle on caller data.  A handle's program may be any op
+ * table tstar_yolo_create accepts (tests hand it crafted single-op programs); these entries run the code tstar_yolo_detect runs.
+ * tstar_yolo_buffer_copy copies B images' worth of floats (B * H * W * C of activation buffer `buf`, NHWC) between d_data (device) and the
+ * buffer: to_buffer != 0 writes the buffer, 0 reads it; 1 <= B <= max_batch, so the zero quad kept behind every buffer is out of reach.
+ * Enqueues only.
+ * tstar_yolo_run_ops runs the op table on the buffers as they stand (no preprocessing, no tail) for images 0 .. B - 1
+ * (1 <= B <= max_batch), with the per-image query sets of tstar_yolo_detect (read only when the program has attention layers);
+ * h_forms (host int32 [n_ops] or null) receives, per conv op, the kernel form that was launched (-1 for the other ops) -- the value the
+ * launcher switched on.  Synchronises. */
+#define TSTAR_YOLO_FORM_TILE64 0   /* LDS-tiled, 64 pixels x 64 channels per workgroup */
+#define TSTAR_YOLO_FORM_TILE128 1  /* LDS-tiled, 128 pixels x 64 channels */
+#define TSTAR_YOLO_FORM_WIDE 2     /* LDS-tiled, 128 pixels x 128 channels */
+#define TSTAR_YOLO_FORM_SW8 3      /* scalar weights, 8 pixels per lane */
+#define TSTAR_YOLO_FORM_SW4 4      /* scalar weights, 4 pixels per lane */
+#define TSTAR_YOLO_FORM_HALO_A16 5 /* halo tile, 8 x 40 patches, 16 channels per wave */
+#define TSTAR_YOLO_FORM_HALO_A8 6  /* halo tile, 8 x 40 patches, 8 channels per wave */
+#define TSTAR_YOLO_FORM_HALO_B16 7 /* halo tile, 16 x 20 patches over the row-stacked batch, 16 channels per wave */
+#define TSTAR_YOLO_FORM_HALO_B8 8  /* halo tile, 16 x 20 patches over the row-stacked batch, 8 channels per wave */
+#define TSTAR_YOLO_FORM_DIRECT 9   /* direct small-K form */
+int tstar_yolo_buffer_copy(tstar_yolo* h, int buf, float* d_data, int B, int to_buffer, void* stream);
+int tstar_yolo_run_ops(tstar_yolo* h, int B, const int32_t* h_image_query_set, int32_t* h_forms, void* stream);
+/* The launch plan of one conv op (pure: needs no GPU and launches nothing): a k x k / stride conv (pad k / 2) reading cin channels at
+ * src_off of an H x W x src_ld buffer, writing cout channels at dst_off of a dst_ld-channel buffer, for B images of a handle created with
+ * max_batch; mode 0 plain / 1 residual / 2 gate.  env_policy 0: the default policy; 1: with the TSTAR_YOLO_* overrides of this process (read
+ * once).  plan3 = { form, mt, nt }: mt x nt workgroups of 256 threads (direct form: mt blocks of nt threads).  TSTAR_ERR_ARG where the
+ * launcher refuses the layer. */
+int tstar_yolo_conv_plan(int cin, int src_ld, int src_off, int H, int W, int cout, int dst_ld, int dst_off, int ks, int stride, int mode, int B,
+                         int max_batch, int env_policy, int* plan3);
+
 /* ------------------------------------------------------------------ ingest (S1-S3, S8) */
 /* The resident decoded video d_video is u8 [N,H,W,3] RGB (nv12 = 0) or NV12 u8 [N, H*3/2, W] (nv12 = 1:
  * luma plane + interleaved half-resolution UV plane, converted on the fly, BT.601 limited range, nearest

@@ -61,6 +61,50 @@ def test_gemm_plan_matches_recorded_table(golden_dir):
     assert lib.tstar_gemm_plan(0, 9232, 192, 192, 0, -1, 0, out) == 1             # N % 128
 
 
+def test_yolo_conv_plan_matches_recorded_table(golden_dir):
+    """The YOLO conv launch policy (plan_conv through tstar_yolo_conv_plan: pure, no GPU) against the plans recorded for every conv
+    layer of the five published scales at B = 1, 2, 8, 16, 32 under the default policy: kernel form and grid, row by row.  The
+    rows were recorded from the new entry after it had been confirmed, row by row, against the launcher that preceded it (its
+    launches replaced by a recorder of kernel, grid and block).  Scale S is also re-derived from build_program here, so the
+    table cannot drift from the programs."""
+    import ctypes as C
+    from tstar_amd import _lib, yolo_world as Y
+    from tstar_amd.yolo import FORM_NAMES, conv_plan
+    lib = _lib.load()
+    out = (C.c_int * 3)()
+    rows, forms, by_scale = 0, set(), {}
+    for line in open(os.path.join(golden_dir, "yolo_conv_plan_table.txt")):
+        if line.startswith("#"):
+            continue
+        f = line.split()
+        args, want = [int(v) for v in f[1:14]], (f[14], int(f[15]), int(f[16]))
+        assert lib.tstar_yolo_conv_plan(*args, 0, out) == 0, line
+        assert (FORM_NAMES[out[0]], out[1], out[2]) == want, (line, tuple(out))
+        rows += 1
+        forms.add(want[0])
+        by_scale.setdefault(f[0], set()).add(tuple(args))
+    assert rows >= 2000 and set(by_scale) == {"s", "m", "l", "x", "xl"}
+    assert forms == {"tile64", "tile128", "wide", "sw8", "sw4", "halo_a16", "halo_a8", "direct"}   # 16 x 20 patches need B > 32 on 20-wide maps
+    prog = Y.build_program(Y.synthetic_state_dict(0, "s"), "s")
+    mine = set()
+    for B in (1, 2, 8, 16, 32):
+        for o in prog["ops"]:
+            if o[0] == Y.OP_CONV:
+                H, W, sld = (int(v) for v in prog["bufs"][o[1]])
+                mine.add((int(o[3]), sld, int(o[2]), H, W, int(o[6]), int(prog["bufs"][o[4]][2]), int(o[5]), int(o[7]), int(o[8]), int(o[12]), B, B))
+    assert mine == by_scale["s"]
+    # refusals: what launch_conv refuses, the plan refuses
+    with pytest.raises(_lib.TStarHipError, match="16-byte aligned"):
+        conv_plan(16, 16, 0, 8, 8, 6, 8, 0, 1, 1, 0, 1, 1)
+    with pytest.raises(_lib.TStarHipError, match="no fused residual"):
+        conv_plan(3, 3, 0, 8, 8, 16, 16, 0, 3, 1, 1, 1, 1)
+    with pytest.raises(_lib.TStarHipError, match="64 KB of LDS"):
+        conv_plan(8, 8, 0, 8, 8, 256, 256, 0, 3, 1, 0, 1, 1)
+    with pytest.raises(_lib.TStarHipError, match="not a conv op"):
+        conv_plan(16, 16, 0, 8, 8, 16, 16, 0, 5, 1, 0, 1, 1)
+    assert lib.tstar_yolo_conv_plan(16, 16, 0, 8, 8, 16, 16, 0, 1, 1, 0, 1, 1, 0, None) == 1
+
+
 def test_ingest_plan_matches_recorded_table(golden_dir):
     """The ingest launch policy (plan_ingest through tstar_ingest_plan: pure, no GPU) against launches recorded from the launchers
     that preceded it: kernel form, pixels per lane, grid, dynamic LDS bytes and LDS pitch, row by row.  A threshold moved by one

@@ -47,6 +47,9 @@ SIGNATURES = {
     "tstar_yolo_set_class_weights": (_i, [_vp, _i, _vp, _i, _vp]),
     "tstar_yolo_detect": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tstar_yolo_postprocess": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tstar_yolo_buffer_copy": (_i, [_vp, _i, _vp, _i, _i, _vp]),
+    "tstar_yolo_run_ops": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "tstar_yolo_conv_plan": (_i, [_i] * 14 + [C.POINTER(_i)]),
     "tstar_frames_to_grid": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp]),
     "tstar_frames_resize": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     "tstar_i420_to_nv12": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -694,18 +694,44 @@ static double conv_algorithmic_bytes(const ConvArgs& a) {
     return b;
 }
 
-static int launch_conv(const ConvArgs& a, hipStream_t s) {
-    TSTAR_REQUIRE(a.cout % 4 == 0 && a.dst_ld % 4 == 0 && a.dst_off % 4 == 0, "yolo conv: output channels must be 16-byte aligned");
+// The launch policy's environment overrides (defaults in the initialisers); read once per process by conv_policy_env().
+struct ConvPolicy {
+    int sw = -1, sw_min = 400, sw_p = 0;                                   // TSTAR_YOLO_SW, _SW_MIN, _SW_P
+    int halo = -1, halo_nch = 0, halo8_max = 600, halo8_min = 600;         // TSTAR_YOLO_HALO, _HALO_NCH, _HALO8_MAX, _HALO8_MIN
+    int tn = 0, tm = 0, tm_min = 512;                                      // TSTAR_YOLO_TN, _TM, _TM_MIN
+};
+
+static const ConvPolicy& conv_policy_env() {
+    static const ConvPolicy p = [] {
+        ConvPolicy q;
+        auto rd = [](const char* name, int& v) { const char* e = getenv(name); if (e) v = atoi(e); };
+        rd("TSTAR_YOLO_SW", q.sw); rd("TSTAR_YOLO_SW_MIN", q.sw_min); rd("TSTAR_YOLO_SW_P", q.sw_p);
+        rd("TSTAR_YOLO_HALO", q.halo); rd("TSTAR_YOLO_HALO_NCH", q.halo_nch); rd("TSTAR_YOLO_HALO8_MAX", q.halo8_max); rd("TSTAR_YOLO_HALO8_MIN", q.halo8_min);
+        rd("TSTAR_YOLO_TN", q.tn); rd("TSTAR_YOLO_TM", q.tm); rd("TSTAR_YOLO_TM_MIN", q.tm_min);
+        return q;
+    }();
+    return p;
+}
+
+// Which kernel a conv launches (TSTAR_YOLO_FORM_* in include/tstar_hip.h) and its grid: mt x nt workgroups of 256 threads; for the
+// direct form mt blocks of nt threads.  error != null: the launcher refuses the layer.
+struct ConvPlan { int form = -1, mt = 0, nt = 0; const char* error = nullptr; };
+
+// The per-layer policy: pure (dimensions, pointer PRESENCE and policy in, plan out; no HIP call), so it is testable without a GPU
+// (tstar_yolo_conv_plan).  Only a.wt != null, a.zoff and the integers of `a` are read.
+static ConvPlan plan_conv(const ConvArgs& a, const ConvPolicy& pol) {
+    ConvPlan p;
+    if (!(a.cout % 4 == 0 && a.dst_ld % 4 == 0 && a.dst_off % 4 == 0)) { p.error = "yolo conv: output channels must be 16-byte aligned"; return p; }
     const bool tiled = a.cin % CBK == 0 && a.src_ld % 4 == 0 && a.src_off % 4 == 0 && (a.ks == 1 || a.ks == 3);
     // scalar-weight form, chosen per layer from its size in 512-pixel x 64-channel blocks (per-layer timings of the L model
     // at B = 32, tools/rocpd_conv_align.py -> profiles/r02_yolo_conv_kernels_by_layer.md): >= 800 blocks: 4 pixels per lane
     // (256-pixel workgroups, 4 waves / SIMD); 400..799: 8 pixels per lane (one round of the chip's 512 two-per-CU slots);
     // below that the 128-pixel tiles of the tile kernel spread the layer over more CUs and win by up to 2x
-    static const int sw_env = [] { const char* e = getenv("TSTAR_YOLO_SW"); return e ? atoi(e) : -1; }();
+    const int sw_env = pol.sw;
     const long long sw_blocks = (long long)cdiv(a.M, 512) * cdiv(a.cout, SWN);
     const bool sw_ok = tiled && a.wt && a.cout % 16 == 0 && a.zoff != 0 && a.zoff < (1u << 30);   // byte offsets fit 32 bits
-    static const int sw_min = [] { const char* e = getenv("TSTAR_YOLO_SW_MIN"); return e ? atoi(e) : 400; }();
-    static const int sw_p_env = [] { const char* e = getenv("TSTAR_YOLO_SW_P"); return e ? atoi(e) : 0; }();
+    const int sw_min = pol.sw_min;
+    const int sw_p_env = pol.sw_p;
     // halo form of the scalar-weight kernel for 3x3 / stride-1 layers.  Patch 8 x 40 on maps that tile by it (the 160-, 80-
     // and 40-wide ones), 16 x 20 over the row-stacked batch on 20-wide maps (H >= 16; one zero row at image boundaries).
     // From 320 workgroups of 16-channel waves up that form beats both other kernels on every such layer (B = 32: 10-15 %
@@ -716,10 +742,10 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
     // input channels) and the tile kernel's many small workgroups win (B = 8, 40x40: 278 vs 426 us at 320 workgroups; B = 16,
     // 640: 440 vs 543) -- thresholds from profiles/r03_yolo_halo_forms_by_layer_*.md.  TSTAR_YOLO_HALO = 0 never / 2 always (when eligible);
     // TSTAR_YOLO_HALO_NCH = 8 / 16 forces the channel form.
-    static const int halo_env = [] { const char* e = getenv("TSTAR_YOLO_HALO"); return e ? atoi(e) : -1; }();
-    static const int nch_env = [] { const char* e = getenv("TSTAR_YOLO_HALO_NCH"); return e ? atoi(e) : 0; }();
-    static const int halo8_max = [] { const char* e = getenv("TSTAR_YOLO_HALO8_MAX"); return e ? atoi(e) : 600; }();
-    static const int halo8_min = [] { const char* e = getenv("TSTAR_YOLO_HALO8_MIN"); return e ? atoi(e) : 600; }();
+    const int halo_env = pol.halo;
+    const int nch_env = pol.halo_nch;
+    const int halo8_max = pol.halo8_max;
+    const int halo8_min = pol.halo8_min;
     const bool halo_3x3 = sw_ok && a.ks == 3 && a.stride == 1 && a.Ho == a.H && a.Wo == a.W;
     const bool halo_a = halo_3x3 && a.H % 8 == 0 && a.W % 40 == 0;                         // 8 x 40 patches, never across images
     const bool halo_b = halo_3x3 && !halo_a && a.W % 20 == 0 && a.H >= 16;                  // 16 x 20 patches over stacked rows
@@ -733,62 +759,75 @@ static int launch_conv(const ConvArgs& a, hipStream_t s) {
         else if (wgs8 >= halo8_min || halo_env > 1) halo_nch = 8;
     }
     if (halo_nch) {
-        const int mt = (int)halo_mt, nt = cdiv(a.cout, 4 * halo_nch);
-        const bool prof = prof_enabled();
-        if (prof) prof_start(PROF_CONV, s, 2.0 * a.M * a.cout * a.ks * a.ks * a.cin, conv_algorithmic_bytes(a));
-        const dim3 grid(mt * nt);
-        if (halo_a) {
-            if (halo_nch == 16) hipLaunchKernelGGL((conv_halo_kernel<8, 40, 16, false>), grid, dim3(256), 0, s, a, mt, nt);
-            else hipLaunchKernelGGL((conv_halo_kernel<8, 40, 8, false>), grid, dim3(256), 0, s, a, mt, nt);
-        } else {
-            if (halo_nch == 16) hipLaunchKernelGGL((conv_halo_kernel<16, 20, 16, true>), grid, dim3(256), 0, s, a, mt, nt);
-            else hipLaunchKernelGGL((conv_halo_kernel<16, 20, 8, true>), grid, dim3(256), 0, s, a, mt, nt);
-        }
-        if (prof) prof_stop(PROF_CONV, s);
+        p.mt = (int)halo_mt; p.nt = cdiv(a.cout, 4 * halo_nch);
+        p.form = halo_a ? (halo_nch == 16 ? TSTAR_YOLO_FORM_HALO_A16 : TSTAR_YOLO_FORM_HALO_A8) : (halo_nch == 16 ? TSTAR_YOLO_FORM_HALO_B16 : TSTAR_YOLO_FORM_HALO_B8);
     } else if (sw_ok && (sw_env < 0 ? sw_blocks >= sw_min : sw_env > 0)) {
         const int sw_p = sw_p_env ? sw_p_env : (sw_blocks >= 800 ? 4 : 8);
-        const int mt = cdiv(a.M, 64 * sw_p), nt = cdiv(a.cout, SWN);
-        const dim3 grid(mt * nt);
-        const bool prof = prof_enabled();
-        if (prof) prof_start(PROF_CONV, s, 2.0 * a.M * a.cout * a.ks * a.ks * a.cin, conv_algorithmic_bytes(a));
-        if (sw_p == 8) {
-            if (a.ks == 1) hipLaunchKernelGGL((conv_sw_kernel<1, 8>), grid, dim3(256), 0, s, a, mt, nt);
-            else hipLaunchKernelGGL((conv_sw_kernel<3, 8>), grid, dim3(256), 0, s, a, mt, nt);
-        } else {
-            if (a.ks == 1) hipLaunchKernelGGL((conv_sw_kernel<1, 4>), grid, dim3(256), 0, s, a, mt, nt);
-            else hipLaunchKernelGGL((conv_sw_kernel<3, 4>), grid, dim3(256), 0, s, a, mt, nt);
-        }
-        if (prof) prof_stop(PROF_CONV, s);
+        p.mt = cdiv(a.M, 64 * sw_p); p.nt = cdiv(a.cout, SWN);
+        p.form = sw_p == 8 ? TSTAR_YOLO_FORM_SW8 : TSTAR_YOLO_FORM_SW4;
     } else if (tiled) {
         // 128-channel tiles (8 x 8 outputs per lane) when the layer has the channels and enough pixels to fill the chip;
         // 64-pixel tiles (4 x 4 per lane) when 128-pixel tiles would leave CUs without a workgroup to overlap with
-        static const int tn_env = [] { const char* e = getenv("TSTAR_YOLO_TN"); return e ? atoi(e) : 0; }();
-        static const int tm_env = [] { const char* e = getenv("TSTAR_YOLO_TM"); return e ? atoi(e) : 0; }();
-        static const int tm_min = [] { const char* e = getenv("TSTAR_YOLO_TM_MIN"); return e ? atoi(e) : 512; }();
+        const int tn_env = pol.tn;
+        const int tm_env = pol.tm;
+        const int tm_min = pol.tm_min;
         const bool wide = tn_env ? tn_env == 8 : (a.cout % 128 == 0 && (long long)cdiv(a.M, 128) * (a.cout / 128) >= 512);
         const bool small = !wide && (tm_env ? tm_env == 4 : (long long)cdiv(a.M, 128) * cdiv(a.cout, 64) < tm_min);
-        const int mt = cdiv(a.M, small ? 64 : 128), nt = cdiv(a.cout, wide ? 128 : 64);
-        const dim3 grid(mt * nt);
-        const bool prof = prof_enabled();
-        if (prof) prof_start(PROF_CONV, s, 2.0 * a.M * a.cout * a.ks * a.ks * a.cin, conv_algorithmic_bytes(a));
-        if (a.ks == 1) {
-            if (wide) hipLaunchKernelGGL((conv_valu_kernel<1, 8, 8>), grid, dim3(256), 0, s, a, mt, nt);
-            else if (small) hipLaunchKernelGGL((conv_valu_kernel<1, 4, 4>), grid, dim3(256), 0, s, a, mt, nt);
-            else hipLaunchKernelGGL((conv_valu_kernel<1, 4, 8>), grid, dim3(256), 0, s, a, mt, nt);
-        } else {
-            if (wide) hipLaunchKernelGGL((conv_valu_kernel<3, 8, 8>), grid, dim3(256), 0, s, a, mt, nt);
-            else if (small) hipLaunchKernelGGL((conv_valu_kernel<3, 4, 4>), grid, dim3(256), 0, s, a, mt, nt);
-            else hipLaunchKernelGGL((conv_valu_kernel<3, 4, 8>), grid, dim3(256), 0, s, a, mt, nt);
-        }
-        if (prof) prof_stop(PROF_CONV, s);
+        p.mt = cdiv(a.M, small ? 64 : 128); p.nt = cdiv(a.cout, wide ? 128 : 64);
+        p.form = wide ? TSTAR_YOLO_FORM_WIDE : small ? TSTAR_YOLO_FORM_TILE64 : TSTAR_YOLO_FORM_TILE128;
     } else {
-        TSTAR_REQUIRE(a.mode == MODE_PLAIN, "yolo conv: the direct form has no fused residual / gate");
+        if (a.mode != MODE_PLAIN) { p.error = "yolo conv: the direct form has no fused residual / gate"; return p; }
         const int K = a.ks * a.ks * a.cin;
-        TSTAR_REQUIRE(a.cout % DCH == 0 && a.cout / DCH <= 256 && (size_t)K * a.cout * 4 <= 64 * 1024,
-                      "yolo conv: the direct (small-K) form needs cout % 16 == 0 and its weights in 64 KB of LDS");
+        if (!(a.cout % DCH == 0 && a.cout / DCH <= 256 && (size_t)K * a.cout * 4 <= 64 * 1024)) {
+            p.error = "yolo conv: the direct (small-K) form needs cout % 16 == 0 and its weights in 64 KB of LDS";
+            return p;
+        }
         const int ncg = a.cout / DCH, nthreads = (256 / ncg) * ncg, ppb = (nthreads / ncg) * DPIX;
-        hipLaunchKernelGGL(conv_direct_kernel, dim3(cdiv(a.M, ppb)), dim3(nthreads), (size_t)K * a.cout * 4, s, a);
+        p.mt = cdiv(a.M, ppb); p.nt = nthreads;
+        p.form = TSTAR_YOLO_FORM_DIRECT;
     }
+    return p;
+}
+
+// Launches the form plan_conv chose; *form_out (optional) receives it.
+static int launch_conv(const ConvArgs& a, hipStream_t s, int* form_out = nullptr) {
+    const ConvPlan p = plan_conv(a, conv_policy_env());
+    if (p.error) { set_error(p.error); return TSTAR_ERR_ARG; }
+    if (form_out) *form_out = p.form;
+    const int mt = p.mt, nt = p.nt;
+    const dim3 grid(mt * nt);
+    const bool prof = p.form != TSTAR_YOLO_FORM_DIRECT && prof_enabled();
+    if (prof) prof_start(PROF_CONV, s, 2.0 * a.M * a.cout * a.ks * a.ks * a.cin, conv_algorithmic_bytes(a));
+    switch (p.form) {
+    case TSTAR_YOLO_FORM_HALO_A16: hipLaunchKernelGGL((conv_halo_kernel<8, 40, 16, false>), grid, dim3(256), 0, s, a, mt, nt); break;
+    case TSTAR_YOLO_FORM_HALO_A8: hipLaunchKernelGGL((conv_halo_kernel<8, 40, 8, false>), grid, dim3(256), 0, s, a, mt, nt); break;
+    case TSTAR_YOLO_FORM_HALO_B16: hipLaunchKernelGGL((conv_halo_kernel<16, 20, 16, true>), grid, dim3(256), 0, s, a, mt, nt); break;
+    case TSTAR_YOLO_FORM_HALO_B8: hipLaunchKernelGGL((conv_halo_kernel<16, 20, 8, true>), grid, dim3(256), 0, s, a, mt, nt); break;
+    case TSTAR_YOLO_FORM_SW8:
+        if (a.ks == 1) hipLaunchKernelGGL((conv_sw_kernel<1, 8>), grid, dim3(256), 0, s, a, mt, nt);
+        else hipLaunchKernelGGL((conv_sw_kernel<3, 8>), grid, dim3(256), 0, s, a, mt, nt);
+        break;
+    case TSTAR_YOLO_FORM_SW4:
+        if (a.ks == 1) hipLaunchKernelGGL((conv_sw_kernel<1, 4>), grid, dim3(256), 0, s, a, mt, nt);
+        else hipLaunchKernelGGL((conv_sw_kernel<3, 4>), grid, dim3(256), 0, s, a, mt, nt);
+        break;
+    case TSTAR_YOLO_FORM_WIDE:
+        if (a.ks == 1) hipLaunchKernelGGL((conv_valu_kernel<1, 8, 8>), grid, dim3(256), 0, s, a, mt, nt);
+        else hipLaunchKernelGGL((conv_valu_kernel<3, 8, 8>), grid, dim3(256), 0, s, a, mt, nt);
+        break;
+    case TSTAR_YOLO_FORM_TILE64:
+        if (a.ks == 1) hipLaunchKernelGGL((conv_valu_kernel<1, 4, 4>), grid, dim3(256), 0, s, a, mt, nt);
+        else hipLaunchKernelGGL((conv_valu_kernel<3, 4, 4>), grid, dim3(256), 0, s, a, mt, nt);
+        break;
+    case TSTAR_YOLO_FORM_TILE128:
+        if (a.ks == 1) hipLaunchKernelGGL((conv_valu_kernel<1, 4, 8>), grid, dim3(256), 0, s, a, mt, nt);
+        else hipLaunchKernelGGL((conv_valu_kernel<3, 4, 8>), grid, dim3(256), 0, s, a, mt, nt);
+        break;
+    default:                                                                                // TSTAR_YOLO_FORM_DIRECT: mt blocks of nt threads
+        hipLaunchKernelGGL(conv_direct_kernel, dim3(mt), dim3(nt), (size_t)a.ks * a.ks * a.cin * a.cout * 4, s, a);
+        break;
+    }
+    if (prof) prof_stop(PROF_CONV, s);
     TSTAR_HIP_CHECK(hipGetLastError());
     return TSTAR_OK;
 }
@@ -1288,6 +1327,12 @@ struct tstar_yolo {
     unsigned long long* d_cand = nullptr; int cand_cap = 0;   // [max_batch, cand_cap]
 };
 
+// element offset of the zero quad behind a source buffer of max_batch images; 0 = beyond the 32-bit byte offsets of the scalar-weight forms
+static unsigned conv_zoff(int max_batch, int H, int W, int ld) {
+    const size_t zo = (size_t)max_batch * H * W * ld;
+    return zo < (1ull << 30) ? (unsigned)zo : 0;
+}
+
 #define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
 static size_t pow2_at_least(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; }
@@ -1334,6 +1379,7 @@ int tstar_yolo_create(tstar_yolo** out, const float* h_blob, size_t n_blob, cons
         YoloOp op; memcpy(op.w, h_ops + (size_t)i * op_words, sizeof(op.w));
         const int* w = op.w;
         bool ok = true;
+        const char* why = "";                                        // what the kernels cannot serve, where the op is otherwise well formed
         if (w[0] == OP_CONV) {
             ok = buf_ok(w[1]) && buf_ok(w[4]) && w[3] >= 1 && w[6] >= 1 && (w[7] == 1 || w[7] == 3) && (w[8] == 1 || w[8] == 2) &&
                  w[2] >= 0 && w[2] + w[3] <= h->buf_c[w[1]] && w[5] >= 0 && w[5] + w[6] <= h->buf_c[w[4]] && h->buf_c[w[4]] % 4 == 0 &&
@@ -1343,18 +1389,38 @@ int tstar_yolo_create(tstar_yolo** out, const float* h_blob, size_t n_blob, cons
                 const int Ho = (h->buf_h[w[1]] + 2 * (w[7] / 2) - w[7]) / w[8] + 1, Wo = (h->buf_w[w[1]] + 2 * (w[7] / 2) - w[7]) / w[8] + 1;
                 ok = Ho == h->buf_h[w[4]] && Wo == h->buf_w[w[4]];
             }
+            // what launch_conv would refuse at the first forward, or the kernels would get wrong silently: refused here instead
+            if (ok && (w[6] % 4 != 0 || w[5] % 4 != 0)) { ok = false; why = ": conv output channels and their offset must be multiples of 4"; }
+            if (ok && w[12] != MODE_PLAIN && w[12] != MODE_RESIDUAL && w[12] != MODE_ATTN_MUL) { ok = false; why = ": unknown conv mode"; }
+            if (ok && w[12] != MODE_PLAIN && (h->buf_h[w[13]] != h->buf_h[w[4]] || h->buf_w[w[13]] != h->buf_w[w[4]])) {
+                ok = false; why = ": the residual / gate buffer must have the output's map size";
+            }
+            if (ok && w[12] == MODE_RESIDUAL && (w[14] % 4 != 0 || h->buf_c[w[13]] % 4 != 0 || w[14] + w[6] > h->buf_c[w[13]])) {
+                ok = false; why = ": the residual channels must be 16-byte aligned and inside their buffer";
+            }
+            if (ok && w[12] == MODE_ATTN_MUL && (w[14] != 0 || w[6] % h->buf_c[w[13]] != 0)) {
+                ok = false; why = ": gated output channels must divide evenly among the heads of the gate buffer (read at offset 0)";
+            }
+            const bool tiled = w[3] % CBK == 0 && h->buf_c[w[1]] % 4 == 0 && w[2] % 4 == 0;
+            if (ok && !tiled && w[12] != MODE_PLAIN) { ok = false; why = ": the direct form (cin % 16 != 0 or unaligned input channels) has no fused residual / gate"; }
+            if (ok && !tiled && (w[6] % DCH != 0 || w[6] / DCH > 256 || (size_t)w[7] * w[7] * w[3] * w[6] * 4 > 64 * 1024)) {
+                ok = false; why = ": the direct form (cin % 16 != 0 or unaligned input channels) needs cout % 16 == 0 and its weights in 64 KB of LDS";
+            }
         } else if (w[0] == OP_POOL5) {
-            ok = buf_ok(w[1]) && w[4] == w[1] && w[3] % 4 == 0 && w[2] % 4 == 0 && w[5] % 4 == 0 && h->buf_c[w[1]] % 4 == 0 &&
+            ok = buf_ok(w[1]) && w[4] == w[1] && w[3] >= 4 && w[3] % 4 == 0 && w[2] % 4 == 0 && w[5] % 4 == 0 && h->buf_c[w[1]] % 4 == 0 &&
                  w[2] + w[3] <= h->buf_c[w[1]] && w[5] + w[3] <= h->buf_c[w[1]];
         } else if (w[0] == OP_UPCOPY) {
-            ok = buf_ok(w[1]) && buf_ok(w[4]) && (w[6] == 1 || w[6] == 2) && w[3] % 4 == 0 && w[2] % 4 == 0 && w[5] % 4 == 0 &&
+            ok = buf_ok(w[1]) && buf_ok(w[4]) && (w[6] == 1 || w[6] == 2) && w[3] >= 4 && w[3] % 4 == 0 && w[2] % 4 == 0 && w[5] % 4 == 0 &&
                  h->buf_c[w[1]] % 4 == 0 && h->buf_c[w[4]] % 4 == 0 && w[2] + w[3] <= h->buf_c[w[1]] &&
                  w[5] + w[3] <= h->buf_c[w[4]] && h->buf_h[w[1]] * w[6] == h->buf_h[w[4]] && h->buf_w[w[1]] * w[6] == h->buf_w[w[4]];
         } else if (w[0] == OP_ATTN) {
             ok = buf_ok(w[1]) && buf_ok(w[4]) && w[7] >= 0 && w[7] < n_guides && w[6] >= 1 && w[3] % w[6] == 0 && h->buf_c[w[4]] == w[6] &&
-                 w[2] + w[3] <= h->buf_c[w[1]];
+                 w[2] >= 0 && w[2] + w[3] <= h->buf_c[w[1]];
+            // attn_kernel takes embed and heads from the guide and writes one row of heads per source pixel
+            if (ok && (h_guides == nullptr || h_guides[w[7] * 5] != w[3] || h_guides[w[7] * 5 + 1] != w[6])) { ok = false; why = ": embed / heads differ from the op's attention layer"; }
+            if (ok && (h->buf_h[w[4]] != h->buf_h[w[1]] || h->buf_w[w[4]] != h->buf_w[w[1]])) { ok = false; why = ": the gate buffer must have the source's map size"; }
         } else ok = false;
-        if (!ok) { set_error("tstar_yolo_create: malformed op " + std::to_string(i)); return fail(TSTAR_ERR_ARG); }
+        if (!ok) { set_error("tstar_yolo_create: malformed op " + std::to_string(i) + why); return fail(TSTAR_ERR_ARG); }
         h->ops.push_back(op);
     }
     hipError_t e = hipMalloc(&h->d_blob, n_blob * sizeof(float));
@@ -1455,9 +1521,11 @@ int tstar_yolo_set_class_weights(tstar_yolo* h, int query_set, const double* h_c
     return TSTAR_OK;
 }
 
-static int run_program(tstar_yolo* h, int B, const int* d_image_set, hipStream_t s) {
+// h_forms (optional, one int per op): the kernel form every conv op launched (TSTAR_YOLO_FORM_*), -1 for the other ops
+static int run_program(tstar_yolo* h, int B, const int* d_image_set, hipStream_t s, int32_t* h_forms = nullptr) {
     for (size_t oi = 0; oi < h->ops.size(); ++oi) {
         const int* w = h->ops[oi].w;
+        if (h_forms) h_forms[oi] = -1;
         if (w[0] == OP_CONV) {
             ConvArgs a{};
             a.src = h->bufs[w[1]]; a.src_ld = h->buf_c[w[1]]; a.src_off = w[2]; a.cin = w[3]; a.H = h->buf_h[w[1]]; a.W = h->buf_w[w[1]];
@@ -1466,9 +1534,10 @@ static int run_program(tstar_yolo* h, int B, const int* d_image_set, hipStream_t
             a.mode = w[12];
             if (a.mode != MODE_PLAIN) { a.aux = h->bufs[w[13]]; a.aux_ld = h->buf_c[w[13]]; a.aux_off = w[14]; a.heads = h->buf_c[w[13]]; }
             a.M = B * a.Ho * a.Wo;
-            const size_t zo = (size_t)h->max_batch * a.H * a.W * a.src_ld;
-            a.zoff = zo < (1ull << 30) ? (unsigned)zo : 0;
-            RC(launch_conv(a, s));
+            a.zoff = conv_zoff(h->max_batch, a.H, a.W, a.src_ld);
+            int form = -1;
+            RC(launch_conv(a, s, &form));
+            if (h_forms) h_forms[oi] = form;
         } else if (w[0] == OP_POOL5) {
             const int H = h->buf_h[w[1]], W = h->buf_w[w[1]];
             const size_t total = (size_t)B * H * W * (w[3] / 4);
@@ -1498,6 +1567,30 @@ static int run_program(tstar_yolo* h, int B, const int* d_image_set, hipStream_t
 // mmyolo test pipeline geometry: YOLOv5KeepRatioResize(640) then LetterResize(640, allow_scale_up=False, pad 114)
 struct YoloGeom { double ratio, sfw, sfh; int rw, rh, top, left; };
 
+// The per-image query sets of a batch: checked against the installed text features and uploaded to d_image_set.
+static int yolo_query_sets(tstar_yolo* h, const std::string& f, int B, const int32_t* h_image_query_set, hipStream_t s, int* q_uniform_out, int* q_max_out) {
+    int q_uniform = -1, q_max = 0;
+    for (int b = 0; b < B; ++b) {
+        const int set = h_image_query_set ? h_image_query_set[b] : 0;
+        TSTAR_REQUIRE(set >= 0 && set < YOLO_SETS, f + ": query_set must be in 0..63");
+        if (h->Q[set] == 0) { set_error(f + ": no text features installed in the requested query set (call tstar_yolo_set_text_feats first)"); return TSTAR_ERR_STATE; }
+        q_uniform = (b == 0 || q_uniform == h->Q[set]) ? h->Q[set] : 0;
+        q_max = q_max > h->Q[set] ? q_max : h->Q[set];
+    }
+    if (h_image_query_set) {
+        if (B > h->image_set_cap) {
+            TSTAR_HIP_CHECK(hipStreamSynchronize(s));
+            if (h->d_image_set) TSTAR_HIP_CHECK(hipFree(h->d_image_set));
+            h->d_image_set = nullptr; h->image_set_cap = 0;
+            TSTAR_HIP_CHECK(hipMalloc(&h->d_image_set, (size_t)B * sizeof(int)));
+            h->image_set_cap = B;
+        }
+        TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_image_set, h_image_query_set, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    *q_uniform_out = q_uniform; *q_max_out = q_max;
+    return TSTAR_OK;
+}
+
 // What tstar_yolo_detect and tstar_yolo_postprocess share before the first launch: argument checks, the per-image query
 // sets (uploaded to d_image_set), the candidate lists' capacity and the letterbox geometry of an H x W image.
 static int yolo_prepare(tstar_yolo* h, const char* fn, int B, int H, int W, int grid_rows, int grid_cols, const int32_t* h_image_query_set,
@@ -1509,24 +1602,8 @@ static int yolo_prepare(tstar_yolo* h, const char* fn, int B, int H, int W, int 
     TSTAR_REQUIRE(!d_cell_conf == !d_cell_mask, f + ": cell_conf and cell_mask go together");
     TSTAR_REQUIRE(!d_cell_conf || (grid_rows >= 1 && grid_cols >= 1 && grid_rows * grid_cols <= 4096), f + ": grid must have 1..4096 cells");
     int q_uniform = -1, q_max = 0;
-    for (int b = 0; b < B; ++b) {
-        const int set = h_image_query_set ? h_image_query_set[b] : 0;
-        TSTAR_REQUIRE(set >= 0 && set < YOLO_SETS, f + ": query_set must be in 0..63");
-        if (h->Q[set] == 0) { set_error(f + ": no text features installed in the requested query set (call tstar_yolo_set_text_feats first)"); return TSTAR_ERR_STATE; }
-        q_uniform = (b == 0 || q_uniform == h->Q[set]) ? h->Q[set] : 0;
-        q_max = q_max > h->Q[set] ? q_max : h->Q[set];
-    }
+    RC(yolo_query_sets(h, f, B, h_image_query_set, s, &q_uniform, &q_max));
     TSTAR_REQUIRE(!d_dense_scores || q_uniform > 0, f + ": dense scores need the same query count for every image");
-    if (h_image_query_set) {
-        if (B > h->image_set_cap) {
-            TSTAR_HIP_CHECK(hipStreamSynchronize(s));
-            if (h->d_image_set) TSTAR_HIP_CHECK(hipFree(h->d_image_set));
-            h->d_image_set = nullptr; h->image_set_cap = 0;
-            TSTAR_HIP_CHECK(hipMalloc(&h->d_image_set, (size_t)B * sizeof(int)));
-            h->image_set_cap = B;
-        }
-        TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_image_set, h_image_query_set, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-    }
     // candidate lists: every (anchor, class) pair can qualify
     const int need_cap = (int)pow2_at_least((size_t)h->n_anchor * q_max);
     if (need_cap > h->cand_cap) {
@@ -1670,5 +1747,51 @@ int tstar_yolo_postprocess(tstar_yolo* h, const float* const* d_level_embed, con
 }
 
 int tstar_yolo_num_anchors(tstar_yolo* h) { return h ? h->n_anchor : 0; }
+
+int tstar_yolo_buffer_copy(tstar_yolo* h, int buf, float* d_data, int B, int to_buffer, void* stream) {
+    TSTAR_REQUIRE(h && d_data, "tstar_yolo_buffer_copy: null argument");
+    TSTAR_REQUIRE(buf >= 0 && buf < (int)h->bufs.size(), "tstar_yolo_buffer_copy: no such activation buffer");
+    TSTAR_REQUIRE(B >= 1 && B <= h->max_batch, "tstar_yolo_buffer_copy: B must be in 1..max_batch");
+    // B <= max_batch images: the zero quad behind the buffer's max_batch images is out of reach
+    const size_t bytes = (size_t)B * h->buf_h[buf] * h->buf_w[buf] * h->buf_c[buf] * sizeof(float);
+    TSTAR_HIP_CHECK(hipMemcpyAsync(to_buffer ? (void*)h->bufs[buf] : (void*)d_data, to_buffer ? (const void*)d_data : (const void*)h->bufs[buf], bytes,
+                                   hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return TSTAR_OK;
+}
+
+int tstar_yolo_run_ops(tstar_yolo* h, int B, const int32_t* h_image_query_set, int32_t* h_forms, void* stream) {
+    TSTAR_REQUIRE(h, "tstar_yolo_run_ops: null argument");
+    TSTAR_REQUIRE(B >= 1 && B <= h->max_batch, "tstar_yolo_run_ops: B must be in 1..max_batch");
+    hipStream_t s = (hipStream_t)stream;
+    if (!h->guides.empty()) {                                            // only the attention ops read the query sets
+        int q_uniform = 0, q_max = 0;
+        RC(yolo_query_sets(h, "tstar_yolo_run_ops", B, h_image_query_set, s, &q_uniform, &q_max));
+    }
+    RC(run_program(h, B, h_image_query_set && !h->guides.empty() ? h->d_image_set : nullptr, s, h_forms));
+    TSTAR_HIP_CHECK(hipStreamSynchronize(s));
+    return TSTAR_OK;
+}
+
+int tstar_yolo_conv_plan(int cin, int src_ld, int src_off, int H, int W, int cout, int dst_ld, int dst_off, int ks, int stride, int mode, int B,
+                         int max_batch, int env_policy, int* plan3) {
+    TSTAR_REQUIRE(plan3, "tstar_yolo_conv_plan: null argument");
+    TSTAR_REQUIRE(cin >= 1 && cout >= 1 && H >= 1 && W >= 1 && src_ld >= 1 && dst_ld >= 1 && src_off >= 0 && dst_off >= 0 && (ks == 1 || ks == 3) &&
+                  (stride == 1 || stride == 2) && B >= 1 && B <= max_batch && max_batch <= 1024,
+                  "tstar_yolo_conv_plan: not a conv op tstar_yolo_create accepts");
+    // the arguments run_program derives from an op of a handle with max_batch images per buffer (every conv op has a transposed matrix)
+    ConvArgs a{};
+    a.src_ld = src_ld; a.src_off = src_off; a.cin = cin; a.H = H; a.W = W;
+    a.dst_ld = dst_ld; a.dst_off = dst_off; a.cout = cout;
+    a.Ho = (H + 2 * (ks / 2) - ks) / stride + 1; a.Wo = (W + 2 * (ks / 2) - ks) / stride + 1;
+    a.ks = ks; a.stride = stride; a.mode = mode;
+    static const float wt_present = 0.f;
+    a.wt = &wt_present;
+    a.M = B * a.Ho * a.Wo;
+    a.zoff = conv_zoff(max_batch, a.H, a.W, a.src_ld);
+    const ConvPlan p = plan_conv(a, env_policy ? conv_policy_env() : ConvPolicy{});
+    if (p.error) { set_error(p.error); return TSTAR_ERR_ARG; }
+    plan3[0] = p.form; plan3[1] = p.mt; plan3[2] = p.nt;
+    return TSTAR_OK;
+}
 
 }  // extern "C"

@@ -15,6 +15,20 @@ from . import _lib
 from . import yolo_world as Y
 
 
+# kernel forms of a conv op (TSTAR_YOLO_FORM_* in include/tstar_hip.h)
+FORM_NAMES = ("tile64", "tile128", "wide", "sw8", "sw4", "halo_a16", "halo_a8", "halo_b16", "halo_b8", "direct")
+
+
+def conv_plan(cin, src_ld, src_off, H, W, cout, dst_ld, dst_off, ks, stride, mode, B, max_batch, env_policy=False):
+    """(form name, mt, nt) the conv launcher plans for one op (tstar_yolo_conv_plan; pure, needs no GPU).  ``env_policy``: apply
+    this process's TSTAR_YOLO_* overrides instead of the default policy."""
+    out = (C.c_int * 3)()
+    rc = _lib.load().tstar_yolo_conv_plan(int(cin), int(src_ld), int(src_off), int(H), int(W), int(cout), int(dst_ld), int(dst_off), int(ks),
+                                          int(stride), int(mode), int(B), int(max_batch), int(bool(env_policy)), out)
+    _lib.check(rc, "tstar_yolo_conv_plan")
+    return FORM_NAMES[out[0]], out[1], out[2]
+
+
 @dataclass
 class YoloResult:
     """Device tensors of one tstar_yolo_detect call (detections are sorted by descending score, padded to max_dets)."""
@@ -37,8 +51,8 @@ class YoloDetector:
             raise _lib.TStarHipError("YoloDetector needs a HIP device (torch.cuda.is_available() is False); tstar_amd has no CPU path")
         self._torch = torch
         self._lib = _lib.load()
-        prog = Y.build_program(state_dict, scale)
-        self.arch = prog["arch"]
+        prog = state_dict if scale is None else Y.build_program(state_dict, scale)
+        self.arch = prog.get("arch")
         self.conv_flops_per_image = Y.conv_flops(prog)
         blob = np.ascontiguousarray(prog["blob"], dtype=np.float32)
         ops = np.ascontiguousarray(prog["ops"], dtype=np.int32)
@@ -55,6 +69,50 @@ class YoloDetector:
         self.n_anchor = int(self._lib.tstar_yolo_num_anchors(h))
         self.Qs = {}
         self.device = torch.device("cuda", torch.cuda.current_device())
+        self.bufs = [tuple(int(v) for v in b) for b in bufs]
+        self.n_ops = int(ops.shape[0])
+
+    @classmethod
+    def from_program(cls, prog, max_batch: int = 16) -> "YoloDetector":
+        """A detector over a ready layer program: the dict ``yolo_world.build_program`` returns (blob, ops, bufs, guides, levels,
+        input_buf), e.g. one assembled with ``yolo_world.program_from_builder`` from crafted ops (diagnostics and tests)."""
+        return cls(prog, None, max_batch)
+
+    # ---- diagnostics: the layer ops on caller data (tstar_yolo_buffer_copy / tstar_yolo_run_ops)
+    def write_buffer(self, buf: int, data, B: int):
+        """Images 0 .. B-1 of activation buffer ``buf`` <- data (cuda float32, B * H * W * C elements, NHWC)."""
+        self._copy(buf, data, B, 1)
+
+    def read_buffer(self, buf: int, B: int):
+        """Images 0 .. B-1 of activation buffer ``buf`` as a cuda float32 tensor [B, H, W, C]."""
+        if not 0 <= int(buf) < len(self.bufs):
+            raise ValueError("read_buffer: no such activation buffer")
+        out = self._torch.empty((max(int(B), 0),) + self.bufs[int(buf)], dtype=self._torch.float32, device=self.device)
+        self._copy(buf, out, B, 0)
+        return out
+
+    def _copy(self, buf, t, B, to_buffer):
+        torch = self._torch
+        if not 0 <= int(buf) < len(self.bufs):
+            raise ValueError("buffer copy: no such activation buffer")
+        H, W, Cc = self.bufs[int(buf)]
+        if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.numel() != int(B) * H * W * Cc:
+            raise ValueError("buffer copy: data must be a contiguous cuda float32 tensor of B * H * W * C elements")
+        _lib.check(self._lib.tstar_yolo_buffer_copy(self._h, int(buf), t.data_ptr(), int(B), int(to_buffer), _lib.stream_ptr()),
+                   "tstar_yolo_buffer_copy")
+
+    def run_ops(self, B: int, image_sets: Optional[Sequence[int]] = None) -> np.ndarray:
+        """Run the op table on the buffers as they stand for images 0 .. B-1 (no preprocessing, no tail).  Returns int32 [n_ops]:
+        per conv op the kernel form launched (``FORM_NAMES``), -1 for the other ops."""
+        sets = None
+        if image_sets is not None:
+            sets = np.ascontiguousarray(image_sets, dtype=np.int32)
+            if sets.shape != (int(B),):
+                raise ValueError("run_ops: image_sets needs one slot per image")
+        forms = np.full(self.n_ops, -2, dtype=np.int32)
+        _lib.check(self._lib.tstar_yolo_run_ops(self._h, int(B), None if sets is None else sets.ctypes.data, forms.ctypes.data,
+                                                _lib.stream_ptr()), "tstar_yolo_run_ops")
+        return forms
 
     def close(self):
         if getattr(self, "_h", None):

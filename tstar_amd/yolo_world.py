@@ -316,12 +316,17 @@ def build_program(state_dict, scale: str = "l") -> Dict:
         B.conv(None, r2, 0, r, 0, act=ACT_NONE, raw=(state_dict[f"{h}reg_preds.{i}.2.weight"], state_dict[f"{h}reg_preds.{i}.2.bias"]))
         ls = float(np.exp(np.float32(state_dict[c + "logit_scale"])))            # x * logit_scale.exp() + bias
         levels.append([e, r, sz, STRIDES[i], B.put([ls, float(np.asarray(state_dict[c + "bias"]))]), 0, 0, 0])
+    return program_from_builder(B, levels, x, A)
+
+
+def program_from_builder(B: "_Builder", levels, input_buf: int, A=None) -> Dict:
+    """The program dict the library takes, from a builder's blob / ops / buffers / attention layers."""
     ops = np.zeros((len(B.ops), OP_WORDS), dtype=np.int32)
     for i, o in enumerate(B.ops):
         ops[i, :len(o)] = o
-    guides = np.array([[g["embed"], g["heads"], g["w_off"], g["b_off"], g["bias_off"]] for g in B.guides], dtype=np.int32)
+    guides = np.array([[g["embed"], g["heads"], g["w_off"], g["b_off"], g["bias_off"]] for g in B.guides], dtype=np.int32).reshape(-1, 5)
     return dict(blob=np.concatenate(B.blob).astype(np.float32), ops=ops, bufs=np.array(B.bufs, dtype=np.int32), guides=guides,
-                levels=np.array(levels, dtype=np.int32), arch=A, input_buf=x)
+                levels=np.array(levels, dtype=np.int32), arch=A, input_buf=input_buf)
 
 
 def conv_flops(prog) -> float:
