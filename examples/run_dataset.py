@@ -35,7 +35,8 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--out", default="./output/tstar_results.json")
     ap.add_argument("--owl-model", default="google/owlvit-base-patch32",
-                    help="OWL-ViT checkpoint (name or directory; B/32 or B/16); seeded synthetic B/32 weights when none is on disk")
+                    help="OWL-ViT or OWLv2 checkpoint (name or directory; OWL-ViT B/32 or B/16, OWLv2 B/16); when none is on disk, seeded "
+                         "synthetic weights: B/32, or OWLv2 B/16 for a name containing 'owlv2' (e.g. google/owlv2-base-patch16-ensemble)")
     ap.add_argument("--owl-input-size", default=None, metavar="HxW",
                     help="detector input size, e.g. 448x768 (each side a multiple of the patch size; default: the checkpoint's 768x768, "
                          "or TSTAR_INPUT_SIZE)")

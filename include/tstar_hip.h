@@ -116,6 +116,19 @@ int tstar_owl_create_in(tstar_owl** out, int input_h, int input_w, int patch_siz
 size_t tstar_owl_vision_blob_floats_in(int input_h, int input_w, int patch_size);
 /* np, the detections per image of the handle's geometry (576 at B/32, 2304 at B/16, gh x gw at another input size; -1 for a
  * NULL handle) */
+/* OWLv2 (an added entry; tstar_abi_version() stays 3).  tstar_owl_create_in for a model family: TSTAR_OWL_FAMILY_OWLVIT (0) IS
+ * tstar_owl_create_in.  TSTAR_OWL_FAMILY_OWLV2 (1): an OWLv2 B/16 handle (checkpoint image 960, patch 16; patch_size must be 16; the
+ * input size follows the same rule, default 960 x 960 = 3600 patches).  Its vision blob has the v2 layout -- the OWL-ViT layout followed
+ * by the objectness head: obj0_w [768,768], obj0_b [768], obj1_w [768,768], obj1_b [768], obj2_w [768], obj2_b [1] --
+ * tstar_owl_vision_blob_floats_family(1, ...) floats; its normalisation argument is mean[3], std[3] (float32) instead of the 3 x 256
+ * table: pre-processing is HF's Owlv2ImageProcessorPil in float (pad to a square, Gaussian anti-aliasing, linear zoom, clip, normalise),
+ * bit for bit; boxes are scaled by max(H, W) as HF's post-processing does.  Every refusal happens before anything is allocated. */
+#define TSTAR_OWL_FAMILY_OWLVIT 0
+#define TSTAR_OWL_FAMILY_OWLV2 1
+int tstar_owl_create_family(tstar_owl** out, int family, int input_h, int input_w, int patch_size, const float* h_vision_blob,
+                            size_t n_vision, const float* h_text_blob, size_t n_text, const float* h_norm, int max_batch,
+                            int weights_mode);
+size_t tstar_owl_vision_blob_floats_family(int family, int input_h, int input_w, int patch_size);
 int tstar_owl_num_patches(tstar_owl* h);
 int tstar_owl_destroy(tstar_owl* h);
 
@@ -178,9 +191,37 @@ int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B,
                          double* d_cell_conf, uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits,
                          float* d_boxes_cxcywh, void* stream);
 
+/* tstar_owl_score_lane with one more nullable output (an added entry): d_objectness f32 [B, np] = HF's objectness_logits of an OWLv2
+ * handle (the objectness head: two GELU layers through the handle's GEMM path, then a 768-dot).  Computed only when the pointer is
+ * non-NULL, after everything else, so no other output changes; TSTAR_ERR_ARG on an OWL-ViT handle.  NULL: tstar_owl_score_lane. */
+int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
+                             const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy,
+                             double* d_cell_conf, uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits,
+                             float* d_boxes_cxcywh, float* d_objectness, void* stream);
+
+/* OWLv2 pre-processing policy (added entries; pure: no GPU, nothing launched).  plan10 = { form, tile_h, tile_w, win_h, win_w, LDS bytes
+ * per workgroup, grid.x, grid.y, radius_y, radius_x } for a u8 image H x W resized to out_h x out_w (multiples of 16): form 0 = direct
+ * (no axis shrinks: four taps per output pixel straight from the source), 1 = filtered (a workgroup owns tile_h x tile_w output pixels and
+ * holds their source window, at most win_h x win_w samples, in LDS); radius = the Gaussian's radius per axis, -1 = the axis is skipped.
+ * TSTAR_ERR_ARG where a score call would refuse the same image: the window of the smallest tile must fit 160 KiB of LDS.
+ * tstar_owlv2_axis_window: the window [lo, lo + n) = lo_n2 of tile k of an axis (S = max(H, W) samples -> out, `tile` outputs per tile).
+ * tstar_owlv2_axis_tables: the float64 tables of an axis as the kernels read them: taps (i0, i1, t) per output index and the Gaussian's
+ * left half gw[radius - k] (k = distance from the centre; one entry 1.0 when the axis is skipped).
+ * tstar_owlv2_set_axis_weights: install the Gaussian's left half (n = radius + 1 float64 values, gw[radius - k] for distance k) of the axis
+ * (S -> out) of a handle, replacing the library's own (computed with libm's exp).  HF's processor computes them with numpy, whose exp can
+ * differ from libm's in the last bit; tstar_amd.owl.OwlScorer installs numpy's before the first image of a new (S, out), so its
+ * pre-processing has the processor's bits on the machine it runs on. */
+int tstar_owlv2_set_axis_weights(tstar_owl* h, int S, int out, const double* gw, int n);
+int tstar_owlv2_preprocess_plan(int H, int W, int out_h, int out_w, int* plan10);
+int tstar_owlv2_axis_window(int S, int out, int tile, int k, int radius, int* lo_n2);
+int tstar_owlv2_axis_tables(int S, int out, int32_t* i0, int32_t* i1, double* t, double* gw, int gw_cap);
+/* the form (0 / 1) of the last OWLv2 pre-processing launch of `lane`, -1 before the first */
+int tstar_owlv2_last_preprocess_form(tstar_owl* h, int lane);
+
 /* Diagnostics for parity tests: the preprocessed u8 images (after bicubic; 768 x 768, or the handle's input_h x input_w)
  * and their patch-embed A operand can be read back.  d_out_patches is [B*np, 3*P*P] for the handle's
  * patch size P: [B*576, 3072] at B/32, [B*2304, 768] at B/16 (row b*np + (y/P)*G + x/P, column c*P*P + (y%P)*P + x%P). */
+/* On an OWLv2 handle there is no u8 stage: d_out_u8 must be NULL (TSTAR_ERR_ARG otherwise); d_out_patches is [B*np, 768]. */
 int tstar_owl_debug_preprocess(tstar_owl* h, const uint8_t* d_images, int B, int H, int W,
                                uint8_t* d_out_u8 /* [B,input_h,input_w,3] */, float* d_out_patches /* [B*np,3*P*P] */,
                                void* stream);

@@ -30,6 +30,14 @@ SIGNATURES = {
     "tstar_owl_vision_blob_floats_ex": (_sz, [_i, _i]),
     "tstar_owl_create_in": (_i, [C.POINTER(_vp), _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _i, _i]),
     "tstar_owl_vision_blob_floats_in": (_sz, [_i, _i, _i]),
+    "tstar_owl_create_family": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _i, _i]),
+    "tstar_owl_vision_blob_floats_family": (_sz, [_i, _i, _i, _i]),
+    "tstar_owl_score_lane_obj": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tstar_owlv2_set_axis_weights": (_i, [_vp, _i, _i, _vp, _i]),
+    "tstar_owlv2_preprocess_plan": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
+    "tstar_owlv2_axis_window": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "tstar_owlv2_axis_tables": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i]),
+    "tstar_owlv2_last_preprocess_form": (_i, [_vp, _i]),
     "tstar_owl_num_patches": (_i, [_vp]),
     "tstar_owl_destroy": (_i, [_vp]),
     "tstar_owl_set_queries": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp]),

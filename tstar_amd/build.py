@@ -28,7 +28,8 @@ ARCH = "gfx950"
 # -ffp-contract=off on the searcher file keeps its float64 arithmetic bit-identical
 # to the numpy statement of the reference (no FMA contraction).
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]
-PER_FILE = {"searcher.hip": ["-ffp-contract=off"]}
+# likewise preprocess_v2.hip: its float64 filter / zoom sums (device) and tables (host) are scipy's bits only without contraction
+PER_FILE = {"searcher.hip": ["-ffp-contract=off"], "preprocess_v2.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

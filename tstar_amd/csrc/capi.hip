@@ -7,6 +7,7 @@
 #include "jpeg_host.h"
 #include "kernels.h"
 #include "owl_weights.h"
+#include "preprocess_v2.h"
 #include <math.h>
 #include <map>
 #include <mutex>
@@ -97,6 +98,8 @@ struct tstar_owl {
     struct Lane {
         float *x = nullptr, *xn = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr;
         uint8_t* tmp_u8 = nullptr; size_t tmp_u8_bytes = 0;
+        int* d_minmax = nullptr; int minmax_cap = 0;                 // OWLv2: per-image clip bounds of the pre-processing (two ints per image)
+        int v2_form = -1;                                            // OWLv2: form of the last pre-processing launch (OWLV2_FORM_*)
         int* d_image_set = nullptr; int image_set_cap = 0;
         int cap = 0;                                                 // images per forward chunk
     } lane[TSTAR_OWL_LANES];
@@ -111,6 +114,8 @@ struct tstar_owl {
     uint8_t* d_kmask = nullptr;
     int seq_cap = TSTAR_OWL_MAX_QUERIES;                             // sequences the three staging buffers above hold
     std::map<std::pair<int, int>, ResampleTable> tabs;   // (in_size, out_size) -> table (out_size: the handle's input width / height)
+    std::map<std::pair<int, int>, Owlv2AxisTable> tabs_v2;   // OWLv2: (square side, out_size) -> zoom taps + Gaussian weights of one axis
+    std::map<std::pair<int, int>, std::vector<double>> gw_v2;  // OWLv2: Gaussian weights installed by the caller (tstar_owlv2_set_axis_weights)
     // weights_mode 1 / 3 (BASELINE config 5, bf16 weights; two-term / exact three-term activations): bfloat16 copy of every
     // GEMM weight matrix; weights_mode 4 (f32x3): every f32 matrix as three exact bf16 planes in MFMA-fragment order
     int weights_mode = TSTAR_WEIGHTS_F32;
@@ -235,8 +240,45 @@ static int run_encoder(tstar_owl* h, tstar_owl::Lane& L, const LayerW* layers, i
     return TSTAR_OK;
 }
 
+static int get_table_v2(tstar_owl* h, int S, int out_size, Owlv2AxisTable** out) {
+    const auto key = std::make_pair(S, out_size);
+    auto it = h->tabs_v2.find(key);
+    if (it == h->tabs_v2.end()) {
+        Owlv2AxisTable t;
+        auto gw = h->gw_v2.find(key);
+        int rc = build_owlv2_axis_table(&t, S, out_size, gw == h->gw_v2.end() ? nullptr : &gw->second);
+        if (rc) return rc;
+        it = h->tabs_v2.emplace(key, t).first;
+    }
+    *out = &it->second;
+    return TSTAR_OK;
+}
+
+// OWLv2: pad to a square, Gaussian anti-aliasing, linear zoom, clip, normalise, im2col (preprocess_v2.hip); no u8 stage
+static int preprocess_chunk_v2(tstar_owl* h, tstar_owl::Lane& L, const uint8_t* d_images, int B, int H, int W, float* out_patches, hipStream_t s) {
+    const OwlGeom& G = h->geom;
+    const Owlv2Plan p = plan_owlv2_preprocess(H, W, G.in_h, G.in_w);      // refusals before a table is built
+    if (p.error) { set_error(p.error); return TSTAR_ERR_ARG; }
+    Owlv2AxisTable *ty, *tx;
+    const int S = H > W ? H : W;
+    RC(get_table_v2(h, S, G.in_h, &ty));
+    RC(get_table_v2(h, S, G.in_w, &tx));
+    if (B > L.minmax_cap) {
+        TSTAR_HIP_CHECK(hipStreamSynchronize(s));
+        if (L.d_minmax) TSTAR_HIP_CHECK(hipFree(L.d_minmax));
+        L.d_minmax = nullptr; L.minmax_cap = 0;
+        TSTAR_HIP_CHECK(hipMalloc(&L.d_minmax, (size_t)B * 2 * sizeof(int)));
+        L.minmax_cap = B;
+    }
+    return owlv2_preprocess(d_images, out_patches, L.d_minmax, B, H, W, G.in_h, G.in_w, *ty, *tx, h->d_lut, s, &L.v2_form);
+}
+
 static int preprocess_chunk(tstar_owl* h, tstar_owl::Lane& L, const uint8_t* d_images, int B, int H, int W, uint8_t* out_u8,
                             float* out_patches, hipStream_t s) {
+    if (h->geom.family == TSTAR_OWL_FAMILY_OWLV2) {
+        TSTAR_REQUIRE(!out_u8, "tstar_owl_debug_preprocess: an OWLv2 handle has no u8 stage (d_out_u8 must be NULL)");
+        return preprocess_chunk_v2(h, L, d_images, B, H, W, out_patches, s);
+    }
     ResampleTable *th, *tv;
     const OwlGeom& G = h->geom;
     RC(get_table(h, W, G.in_w, &th, s));
@@ -266,7 +308,7 @@ static hipError_t alloc_lane(tstar_owl::Lane& L, int cap, const OwlGeom& g) {
     return e;
 }
 static void free_lane(tstar_owl::Lane& L) {
-    void* ptrs[] = {L.x, L.xn, L.qkv, L.att, L.hid, L.tmp_u8, L.d_image_set};
+    void* ptrs[] = {L.x, L.xn, L.qkv, L.att, L.hid, L.tmp_u8, L.d_image_set, L.d_minmax};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     L = tstar_owl::Lane{};
 }
@@ -290,6 +332,15 @@ size_t tstar_owl_vision_blob_floats_in(int input_h, int input_w, int patch_size)
     }
     return vision_floats(g);
 }
+size_t tstar_owl_vision_blob_floats_family(int family, int input_h, int input_w, int patch_size) {
+    OwlGeom g;
+    if (!owl_geom_family(family, input_h, input_w, patch_size, &g)) {
+        set_error("tstar_owl_vision_blob_floats_family: unsupported family / input size (family 0: patch 32 or 16; family 1 (OWLv2): patch 16; each "
+                  "side a positive multiple of the patch size; at most 3600 patches)");
+        return 0;
+    }
+    return vision_floats(g);
+}
 int tstar_owl_num_patches(tstar_owl* h) {
     if (!h) { set_error("tstar_owl_num_patches: null handle"); return -1; }
     return h->geom.np;
@@ -307,6 +358,7 @@ static int make_bf16_copies(tstar_owl* h, int mode) {
     mats.push_back({h->vw.cls_w, PROJ, V_D});
     mats.push_back({h->vw.box0_w, V_D, V_D});
     mats.push_back({h->vw.box1_w, V_D, V_D});
+    if (h->vw.obj0_w) { mats.push_back({h->vw.obj0_w, V_D, V_D}); mats.push_back({h->vw.obj1_w, V_D, V_D}); }
     if (h->has_text) {
         for (int i = 0; i < T_LAYERS; ++i) layer(h->tw.layers[i], T_D, T_FF);
         mats.push_back({h->tw.text_proj, PROJ, T_D});
@@ -354,8 +406,16 @@ int tstar_owl_create_ex(tstar_owl** out, int image_size, int patch_size, const f
 
 int tstar_owl_create_in(tstar_owl** out, int input_h, int input_w, int patch_size, const float* h_vision_blob, size_t n_vision,
                         const float* h_text_blob, size_t n_text, const float* h_norm_lut, int max_batch, int weights_mode) {
+    return tstar_owl_create_family(out, TSTAR_OWL_FAMILY_OWLVIT, input_h, input_w, patch_size, h_vision_blob, n_vision, h_text_blob, n_text, h_norm_lut,
+                                   max_batch, weights_mode);
+}
+
+int tstar_owl_create_family(tstar_owl** out, int family, int input_h, int input_w, int patch_size, const float* h_vision_blob, size_t n_vision,
+                            const float* h_text_blob, size_t n_text, const float* h_norm_lut, int max_batch, int weights_mode) {
     OwlGeom geom;
-    TSTAR_REQUIRE(owl_geom_input(input_h, input_w, patch_size, &geom),
+    TSTAR_REQUIRE(family == TSTAR_OWL_FAMILY_OWLVIT || family == TSTAR_OWL_FAMILY_OWLV2, "tstar_owl_create_family: family must be 0 (OWL-ViT) or 1 (OWLv2)");
+    TSTAR_REQUIRE(family != TSTAR_OWL_FAMILY_OWLV2 || patch_size == 16, "tstar_owl_create_family: OWLv2 is supported at patch 16 (B/16) only");
+    TSTAR_REQUIRE(owl_geom_family(family, input_h, input_w, patch_size, &geom),
                   "tstar_owl_create_in: unsupported input size; supported: patch 32 (B/32) or 16 (B/16), each side of the input a positive "
                   "multiple of the patch size, at most 3600 patches");
     TSTAR_REQUIRE(out && (h_vision_blob || h_text_blob), "tstar_owl_create: null argument");
@@ -404,7 +464,14 @@ int tstar_owl_create_in(tstar_owl** out, int input_h, int input_w, int patch_siz
     if (e == hipSuccess) e = hipMalloc(&h->d_ids, TSTAR_OWL_MAX_QUERIES * T_LEN * sizeof(int));
     if (e == hipSuccess) e = hipMalloc(&h->d_eos, TSTAR_OWL_MAX_QUERIES * sizeof(int));
     if (e == hipSuccess) e = hipMalloc(&h->d_kmask, TSTAR_OWL_MAX_QUERIES * T_LEN);
-    if (e == hipSuccess && h_norm_lut) e = hipMemcpy(h->d_lut, h_norm_lut, 768 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && h_norm_lut && family == TSTAR_OWL_FAMILY_OWLVIT) e = hipMemcpy(h->d_lut, h_norm_lut, 768 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && h_norm_lut && family == TSTAR_OWL_FAMILY_OWLV2) {
+        // OWLv2: h_norm_lut is mean[3], std[3]; the device holds the rescale table float32(float64(u8) * (1 / 255)) | mean | std
+        float norm[262];
+        for (int u = 0; u < 256; ++u) norm[u] = (float)((double)u * (1.0 / 255.0));
+        for (int i = 0; i < 6; ++i) norm[256 + i] = h_norm_lut[i];
+        e = hipMemcpy(h->d_lut, norm, sizeof(norm), hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) {
         set_error(std::string("tstar_owl_create: workspace allocation failed: ") + hipGetErrorString(e));
         tstar_owl_destroy(h);
@@ -424,6 +491,7 @@ int tstar_owl_destroy(tstar_owl* h) {
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& L : h->lane) free_lane(L);
     for (auto& kv : h->tabs) free_table(&kv.second);
+    for (auto& kv : h->tabs_v2) free_owlv2_axis_table(&kv.second);
     for (auto& kv : h->wb) if (kv.second) (void)hipFree(kv.second);
     for (auto& kv : h->wp) if (kv.second) (void)hipFree(kv.second);
     for (auto& kv : h->wq) if (kv.second) (void)hipFree(kv.second);
@@ -605,12 +673,24 @@ int tstar_owl_score(tstar_owl* h, const uint8_t* d_images, int B, int H, int W, 
 int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
                          const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
                          uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_boxes_cxcywh, void* stream) {
+    return tstar_owl_score_lane_obj(h, lane, d_images, B, H, W, grid_rows, grid_cols, h_image_query_set, d_scores, d_labels, d_boxes_xyxy, d_cell_conf,
+                                    d_cell_mask, d_n_kept, d_logits, d_boxes_cxcywh, nullptr, stream);
+}
+
+int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
+                             const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
+                             uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_boxes_cxcywh, float* d_objectness, void* stream) {
     TSTAR_REQUIRE(h && d_images && d_scores && d_labels && d_boxes_xyxy && d_cell_conf && d_cell_mask,
                   "tstar_owl_score: null argument");
     TSTAR_REQUIRE(lane >= 0 && lane < TSTAR_OWL_LANES, "tstar_owl_score_lane: lane must be 0 or 1");
     TSTAR_REQUIRE(B >= 1 && H >= 1 && W >= 1, "tstar_owl_score: empty batch or image");
     TSTAR_REQUIRE(grid_rows >= 1 && grid_cols >= 1, "tstar_owl_score: grid must be at least 1x1");
     if (!h->has_vision) { set_error("tstar_owl_score: handle was created without vision weights (text-only)"); return TSTAR_ERR_STATE; }
+    TSTAR_REQUIRE(!d_objectness || h->geom.family == TSTAR_OWL_FAMILY_OWLV2, "tstar_owl_score_lane_obj: objectness needs an OWLv2 handle (OWL-ViT has no objectness head)");
+    if (h->geom.family == TSTAR_OWL_FAMILY_OWLV2) {          // refusals before anything is launched
+        const Owlv2Plan vp = plan_owlv2_preprocess(H, W, h->geom.in_h, h->geom.in_w);
+        if (vp.error) { set_error(vp.error); return TSTAR_ERR_ARG; }
+    }
     hipStream_t s = (hipStream_t)stream;
     auto& L = h->lane[lane];
     if (lane != 0) {
@@ -679,8 +759,16 @@ int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B,
         a.image_set = h_image_query_set ? L.d_image_set + b0 : nullptr;
         a.setQ = h->d_setQ;
         a.cxcywh = d_boxes_cxcywh ? d_boxes_cxcywh + (size_t)b0 * NP * 4 : nullptr;
-        a.rows = MP; a.np = NP; a.Q = q_uniform; a.img_w = W; a.img_h = H;
+        a.rows = MP; a.np = NP; a.Q = q_uniform;
+        // boxes are relative to the resized image (OWL-ViT) or to the padded square (OWLv2: HF's _scale_boxes multiplies by max(H, W))
+        const bool v2 = G.family == TSTAR_OWL_FAMILY_OWLV2;
+        a.box_sx = (float)(v2 ? (H > W ? H : W) : W); a.box_sy = (float)(v2 ? (H > W ? H : W) : H);
         RC(detect_rows(a, s));
+        if (d_objectness) {                                   // after detect_rows: feats is still whole, the heads' buffers are free
+            RC(gemm_f32(mk_gemm(h, feats, h->vw.obj0_w, bh1, h->vw.obj0_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
+            RC(gemm_f32(mk_gemm(h, bh1, h->vw.obj1_w, bh2, h->vw.obj1_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
+            RC(row_dot768(bh2, h->vw.obj2_w, h->vw.obj2_b, d_objectness + (size_t)b0 * NP, MP, s));
+        }
         RC(cell_reduce(a.scores, a.labels, a.xyxy, h->qweight, a.image_set, Bc, NP, W, H, grid_rows, grid_cols, 0.005f,
                        d_cell_conf + (size_t)b0 * ncell, d_cell_mask + (size_t)b0 * ncell,
                        d_n_kept ? d_n_kept + b0 : nullptr, s));
@@ -694,6 +782,52 @@ int tstar_owl_debug_preprocess(tstar_owl* h, const uint8_t* d_images, int B, int
     TSTAR_REQUIRE(B >= 1 && B <= h->max_batch, "tstar_owl_debug_preprocess: B must be in 1..max_batch");
     if (!h->has_vision) { set_error("tstar_owl_debug_preprocess: handle was created without vision weights (text-only)"); return TSTAR_ERR_STATE; }
     return preprocess_chunk(h, h->lane[0], d_images, B, H, W, d_out_u8, d_out_patches, (hipStream_t)stream);
+}
+
+int tstar_owlv2_last_preprocess_form(tstar_owl* h, int lane) {
+    if (!h || lane < 0 || lane >= TSTAR_OWL_LANES) { set_error("tstar_owlv2_last_preprocess_form: null handle or bad lane"); return -1; }
+    return h->lane[lane].v2_form;
+}
+
+int tstar_owlv2_set_axis_weights(tstar_owl* h, int S, int out, const double* gw, int n) {
+    TSTAR_REQUIRE(h && gw && S >= 2 && out >= 1, "tstar_owlv2_set_axis_weights: bad argument");
+    const Owlv2Axis a = owlv2_axis(S, out);
+    TSTAR_REQUIRE(n == (a.radius > 0 ? a.radius : 0) + 1, "tstar_owlv2_set_axis_weights: n must be the axis' radius + 1");
+    const auto key = std::make_pair(S, out);
+    auto it = h->tabs_v2.find(key);
+    if (it != h->tabs_v2.end()) {                            // a table built from other weights: drop it once the device is done with it
+        TSTAR_HIP_CHECK(hipDeviceSynchronize());
+        free_owlv2_axis_table(&it->second);
+        h->tabs_v2.erase(it);
+    }
+    h->gw_v2[key] = std::vector<double>(gw, gw + n);
+    return TSTAR_OK;
+}
+
+int tstar_owlv2_preprocess_plan(int H, int W, int out_h, int out_w, int* plan10) {
+    TSTAR_REQUIRE(plan10, "tstar_owlv2_preprocess_plan: null argument");
+    const Owlv2Plan p = plan_owlv2_preprocess(H, W, out_h, out_w);
+    if (p.error) { set_error(p.error); return TSTAR_ERR_ARG; }
+    const int v[10] = {p.form, p.tile_h, p.tile_w, p.win_h, p.win_w, p.lds_bytes, p.grid_x, p.grid_y, p.radius_y, p.radius_x};
+    for (int i = 0; i < 10; ++i) plan10[i] = v[i];
+    return TSTAR_OK;
+}
+
+int tstar_owlv2_axis_window(int S, int out, int tile, int k, int radius, int* lo_n2) {
+    TSTAR_REQUIRE(lo_n2 && S >= 2 && out >= 1 && tile >= 1 && k >= 0 && k * tile < out, "tstar_owlv2_axis_window: bad argument");
+    owlv2_axis_window(S, out, tile, k, radius, &lo_n2[0], &lo_n2[1]);
+    return TSTAR_OK;
+}
+
+int tstar_owlv2_axis_tables(int S, int out, int32_t* i0, int32_t* i1, double* t, double* gw, int gw_cap) {
+    TSTAR_REQUIRE(i0 && i1 && t && gw && S >= 2 && out >= 1, "tstar_owlv2_axis_tables: bad argument");
+    std::vector<int> a, b;
+    std::vector<double> tt, g;
+    owlv2_axis_host(S, out, a, b, tt, g);
+    TSTAR_REQUIRE((int)g.size() <= gw_cap, "tstar_owlv2_axis_tables: gw_cap is smaller than radius + 1");
+    for (int j = 0; j < out; ++j) { i0[j] = a[j]; i1[j] = b[j]; t[j] = tt[j]; }
+    for (size_t k = 0; k < g.size(); ++k) gw[k] = g[k];
+    return TSTAR_OK;
 }
 
 int tstar_frames_to_grid(const uint8_t* d_video, int N, int H, int W, const int32_t* d_frame_idx, int grid_rows,

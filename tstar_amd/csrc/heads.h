@@ -22,9 +22,13 @@ struct DetectRowsArgs {
     float* xyxy;           // [rows, 4] pixels of the passed image
     float* logits;         // [rows, Q] or null
     float* cxcywh;         // [rows, 4] or null
-    int rows, np, Q, img_w, img_h;   // Q: common query count (row stride of `logits`), 0 if the sets differ
+    int rows, np, Q;       // Q: common query count (row stride of `logits`), 0 if the sets differ
+    float box_sx, box_sy;  // pixels per unit of the relative boxes: (W, H) of the passed image for OWL-ViT, (max(H, W), max(H, W)) for OWLv2
 };
 int detect_rows(const DetectRowsArgs& a, hipStream_t s);
+
+// out[r] = dot(h[r, :768], w) + b[0]: the last layer of OWLv2's objectness head (one wave per row)
+int row_dot768(const float* h, const float* w, const float* b, float* out, int rows, hipStream_t s);
 
 int cell_reduce(const float* scores, const int* labels, const float* xyxy, const double* qweight, const int* image_set, int B, int np,
                 int img_w, int img_h, int grows, int gcols, float thr, double* cell_conf, uint32_t* cell_mask,

@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void detect_rows_kernel(DetectRowsArgs a) {
 
     if (lane == 0) {
         const float score = 1.0f / (1.0f + expf(-best));
-        const float fw = (float)a.img_w, fh = (float)a.img_h;
+        const float fw = a.box_sx, fh = a.box_sy;
         const float x0 = (bx[0] - 0.5f * bx[2]) * fw, y0 = (bx[1] - 0.5f * bx[3]) * fh;
         const float x1 = (bx[0] + 0.5f * bx[2]) * fw, y1 = (bx[1] + 0.5f * bx[3]) * fh;
         a.scores[row] = score;
@@ -123,6 +123,31 @@ __global__ __launch_bounds__(256) void detect_rows_kernel(DetectRowsArgs a) {
 int detect_rows(const DetectRowsArgs& a, hipStream_t s) {
     TSTAR_REQUIRE(a.rows > 0 && a.setQ, "detect_rows: empty problem");
     hipLaunchKernelGGL(detect_rows_kernel, dim3(cdiv(a.rows, 4)), dim3(256), 0, s, a);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    return TSTAR_OK;
+}
+
+// modeling_owlv2.py Owlv2ForObjectDetection.objectness_predictor: dense2 of the objectness head, [..., 0]
+__global__ __launch_bounds__(256) void row_dot768_kernel(const float* __restrict__ h, const float* __restrict__ w, const float* __restrict__ b,
+                                                         float* __restrict__ out, int rows) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float d = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(h + (size_t)row * 768 + (i * 64 + lane) * 4);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(w + (i * 64 + lane) * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d += x[e] * v[e];
+    }
+    d = wsum(d) + b[0];
+    if (lane == 0) out[row] = d;
+}
+
+int row_dot768(const float* h, const float* w, const float* b, float* out, int rows, hipStream_t s) {
+    TSTAR_REQUIRE(rows > 0 && h && w && b && out, "row_dot768: empty problem");
+    hipLaunchKernelGGL(row_dot768_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, h, w, b, out, rows);
     TSTAR_HIP_CHECK(hipGetLastError());
     return TSTAR_OK;
 }

@@ -18,6 +18,7 @@ constexpr int V_MAX_NP = 3600;
 struct OwlGeom {
     int image = 768, patch = 32, grid = 24, np = V_NP, ntok = V_NTOK, patch_k = V_PATCH_K;
     int in_h = 768, in_w = 768, gh = 24, gw = 24;
+    int family = 0;              // TSTAR_OWL_FAMILY_OWLVIT (0) or TSTAR_OWL_FAMILY_OWLV2 (1: image 960, patch 16, an objectness head)
 };
 // the run geometry of a (input_h, input_w) input at patch 32 / 16, or false when the size is not supported: each side a
 // positive multiple of the patch size, at most V_MAX_NP patches
@@ -28,6 +29,13 @@ inline bool owl_geom_input(int input_h, int input_w, int patch_size, OwlGeom* g)
     g->image = 768; g->patch = patch_size; g->grid = 768 / patch_size;
     g->in_h = input_h; g->in_w = input_w; g->gh = input_h / patch_size; g->gw = input_w / patch_size;
     g->np = g->gh * g->gw; g->ntok = g->np + 1; g->patch_k = 3 * patch_size * patch_size;
+    return true;
+}
+// the run geometry of a handle of `family`: 0 = OWL-ViT (owl_geom_input), 1 = OWLv2 B/16 (checkpoint image 960, patch 16 only)
+inline bool owl_geom_family(int family, int input_h, int input_w, int patch_size, OwlGeom* g) {
+    if (family == 0) return owl_geom_input(input_h, input_w, patch_size, g);
+    if (family != 1 || patch_size != 16 || !owl_geom_input(input_h, input_w, patch_size, g)) return false;
+    g->image = 960; g->grid = 60; g->family = 1;
     return true;
 }
 // the geometry of (image_size, patch_size), or false when it is not supported (B/32 and B/16: image 768, patch 32 / 16)
@@ -46,6 +54,7 @@ struct VisionW {
     const float *post_ln_w, *post_ln_b, *det_ln_w, *det_ln_b;
     const float *cls_w, *cls_b, *shift_w, *shift_b, *scale_w, *scale_b;
     const float *box0_w, *box0_b, *box1_w, *box1_b, *box2_w, *box2_b, *box_bias;
+    const float *obj0_w, *obj0_b, *obj1_w, *obj1_b, *obj2_w, *obj2_b;      // OWLv2 only (objectness_head), null otherwise
 };
 
 struct TextW {
@@ -81,6 +90,11 @@ void map_vision(VisionW& w, const OwlGeom& g, Take&& take) {
     w.box1_w = take((size_t)V_D * V_D); w.box1_b = take(V_D);
     w.box2_w = take((size_t)4 * V_D); w.box2_b = take(4);
     w.box_bias = take((size_t)g.np * 4);
+    if (g.family == 1) {
+        w.obj0_w = take((size_t)V_D * V_D); w.obj0_b = take(V_D);
+        w.obj1_w = take((size_t)V_D * V_D); w.obj1_b = take(V_D);
+        w.obj2_w = take(V_D); w.obj2_b = take(1);
+    }
 }
 
 template <class Take>

@@ -71,13 +71,20 @@ class OWLInterface(HeuristicInterface):
     def __init__(self, model_name_or_path: str = "google/owlvit-base-patch32", device: str = "cuda",
                  max_batch: Optional[int] = None, synthetic_seed: Optional[int] = None, state_dict: Optional[Dict] = None,
                  weights_dtype: Optional[str] = None, allow_standin_tokenizer: Optional[bool] = None,
-                 patch_size: Optional[int] = None, input_size=None):
+                 patch_size: Optional[int] = None, input_size=None, family: Optional[str] = None):
         """``device`` must be a HIP device (default "cuda" as in the reference, :201).
 
         Supported checkpoints: OWL-ViT B/32 (``google/owlvit-base-patch32``, the default) and B/16
-        (``google/owlvit-base-patch16``).  The geometry comes from the checkpoint (its config.json, cross-checked against the
-        tensor shapes; ``weights.geometry_of_checkpoint``) or from the shapes of a given ``state_dict``; any other geometry
-        (L/14, OWLv2, ...) raises ValueError before anything is allocated on the device.  ``patch_size`` (32 or 16) chooses
+        (``google/owlvit-base-patch16``), and OWLv2 B/16 (``google/owlv2-base-patch16``, ``-ensemble``, ``-finetuned``: image
+        960, patch 16).  The geometry, the model family included, comes from the checkpoint (its config.json, cross-checked
+        against the tensor names and shapes; ``weights.geometry_of_checkpoint``) or from the keys and shapes of a given
+        ``state_dict`` (``owlvit.*`` / ``owlv2.*``); any other geometry (L/14, OWLv2 at image 768, ...) raises ValueError before
+        anything is allocated on the device.  An OWLv2 heuristic pre-processes as HF's ``Owlv2ImageProcessorPil`` does (pad to a
+        square, Gaussian anti-aliasing, linear resize; bit for bit), scales boxes by max(H, W) as its post-processing does, and
+        ``self.scorer.score(..., objectness=True)`` returns HF's ``objectness_logits``; image-guided queries are not supported.
+        ``family`` ("owlvit" / "owlv2") chooses the family of SYNTHETIC weights; not given, it is ``TSTAR_OWL_FAMILY``, else
+        "owlv2" when ``model_name_or_path`` contains ``owlv2``, else "owlvit"; given together with real weights it must agree
+        with them.  ``patch_size`` (32 or 16) chooses
         the geometry of SYNTHETIC weights (default 32); given together with real weights it must agree with them.  The
         geometry is kept as ``self.geometry`` (``weights.OwlGeometry``); ``inference_detector`` returns
         ``self.geometry.npatch`` detections (patch order) when every patch passes the threshold.
@@ -126,7 +133,14 @@ class OWLInterface(HeuristicInterface):
         dev = torch.device(device)
         if dev.index is not None:
             torch.cuda.set_device(dev.index)
-        if patch_size is not None:
+        if family is None:
+            family = os.environ.get("TSTAR_OWL_FAMILY") or None
+        family_given = family is not None
+        if family is None:
+            family = "owlv2" if "owlv2" in str(model_name_or_path).lower() else "owlvit"
+        if family not in W.FAMILIES:
+            raise ValueError(f"family (or TSTAR_OWL_FAMILY) must be one of {W.FAMILIES}, not {family!r}")
+        if patch_size is not None and not (family == "owlv2" and family_given):
             W.geometry_for_patch(int(patch_size))                  # an unsupported value fails here, whatever the weights
         input_size = W.resolve_input_size(input_size)              # a malformed TSTAR_INPUT_SIZE fails here
         if state_dict is None:
@@ -137,22 +151,27 @@ class OWLInterface(HeuristicInterface):
                 state_dict = W.load_safetensors_state_dict(ckpt)
                 self.weights_source = ckpt
             elif synthetic_seed is not None:
-                geometry = W.geometry_for_patch(32 if patch_size is None else int(patch_size))
+                geometry = W.geometry_for_family(family, None if patch_size is None else int(patch_size))
                 W.with_input_size(geometry, input_size)
                 state_dict = W.synthetic_state_dict(int(synthetic_seed), geometry=geometry)
                 self.weights_source = f"synthetic(seed={int(synthetic_seed)})"
             else:
                 raise FileNotFoundError(
                     f"no local checkpoint for {model_name_or_path!r} (offline); pass synthetic_seed=<int> "
-                    "for seeded synthetic OWL-ViT weights (B/32, or B/16 with patch_size=16) or state_dict=<HF state dict>")
+                    "for seeded synthetic OWL-ViT weights (B/32, or B/16 with patch_size=16; OWLv2 B/16 with family='owlv2' or a "
+                    "model name containing 'owlv2') or state_dict=<HF state dict>")
         else:
             geometry = W.geometry_of_state_dict(state_dict)
             self.weights_source = "state_dict"
         if patch_size is not None and int(patch_size) != geometry.patch_size:
             raise ValueError(f"patch_size={int(patch_size)} disagrees with the weights of {self.weights_source!r}, which are "
                              f"{geometry.name} (patch {geometry.patch_size})")
+        if family_given and family != geometry.family:
+            raise ValueError(f"family={family!r} disagrees with the weights of {self.weights_source!r}, which are {geometry.name} "
+                             f"({geometry.family})")
         geometry = W.with_input_size(geometry, input_size)
         self.geometry = geometry
+        self.family = geometry.family
         if allow_standin_tokenizer is None:
             allow_standin_tokenizer = self.weights_source.startswith("synthetic(")
         self.allow_standin_tokenizer = bool(allow_standin_tokenizer)
@@ -160,9 +179,9 @@ class OWLInterface(HeuristicInterface):
             state_dict = W.round_weights_to_bf16(state_dict)
         self.weights_dtype = weights_dtype
         self.model_name_or_path = model_name_or_path
-        self.scorer = OwlScorer(W.pack_blob(state_dict, W.vision_spec(geometry), geometry), W.pack_blob(state_dict, W.text_spec()),
+        self.scorer = OwlScorer(W.pack_blob(state_dict, W.vision_spec(geometry), geometry), W.pack_blob(state_dict, W.text_spec(geometry)),
                                 max_batch=max_batch, weights_mode=weights_dtype, patch_size=geometry.patch_size,
-                                input_size=None if geometry == geometry.checkpoint else geometry.input_size)
+                                input_size=None if geometry == geometry.checkpoint else geometry.input_size, family=geometry.family)
         self.device = device
         self.texts = ["couch", "table", "woman"]      # as the reference leaves it before reparameterisation (:203)
         self.detections_inbatch: List[Detections] = []
@@ -499,7 +518,7 @@ def draw_boxes(image: np.ndarray, det: Detections, color=(255, 64, 64)) -> np.nd
 
 def initialize_heuristic(heuristic_type: str = "owl-vit", **kwargs) -> HeuristicInterface:
     """Factory with the reference's signature (TStarFramework.py:171-187).  ``model_name_or_path=`` overrides the OWL-ViT
-    checkpoint (default ``google/owlvit-base-patch32``; B/16 checkpoints are supported too); ``input_size=(height, width)``
+    checkpoint (default ``google/owlvit-base-patch32``; B/16 and OWLv2 B/16 checkpoints are supported too); ``input_size=(height, width)``
     overrides the detector's input size (default the checkpoint's 768 x 768; ``TSTAR_INPUT_SIZE=HxW`` when not given)."""
     if heuristic_type == "owl-vit":
         kwargs.setdefault("model_name_or_path", "google/owlvit-base-patch32")

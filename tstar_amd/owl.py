@@ -19,6 +19,29 @@ OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
+FAMILY_CODES = {"owlvit": 0, "owlv2": 1}                   # TSTAR_OWL_FAMILY_* of include/tstar_hip.h
+
+
+def owlv2_axis_radius(S: int, out: int) -> int:
+    """Radius of the anti-aliasing Gaussian HF's OWLv2 processor applies on an axis of S samples resized to ``out``
+    (image_processing_pil_owlv2.py resize -> scipy.ndimage.gaussian_filter1d); -1: sigma <= 1e-15, the axis is skipped."""
+    sigma = max(0.0, (S / out - 1) / 2)
+    return -1 if sigma <= 1e-15 else int(4.0 * sigma + 0.5)
+
+
+def owlv2_gaussian_half(S: int, out: int) -> np.ndarray:
+    """float64 [radius + 1]: the left half of scipy's ``_gaussian_kernel1d(sigma, 0, radius)`` for that axis, with scipy's own
+    numpy statements (so with numpy's exp and pairwise sum, as on the machine HF's processor would run on)."""
+    lw = owlv2_axis_radius(S, out)
+    if lw <= 0:
+        return np.ones(1, dtype=np.float64)
+    sigma = (S / out - 1) / 2
+    x = np.arange(-lw, lw + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[:lw + 1], dtype=np.float64)
+
+
 def normalize_lut() -> np.ndarray:
     """f32 [3,256]: value of (channel, u8) after HF rescale + normalize.
 
@@ -46,24 +69,28 @@ class ScoreResult:
     n_kept: "object"       # i32 [B]
     logits: "object" = None
     boxes_cxcywh: "object" = None
+    objectness: "object" = None   # f32 [B,np]: HF's objectness_logits (OWLv2 only, ``score(..., objectness=True)``)
 
 
 class OwlScorer:
-    """One OWL-ViT scorer (B/32, or B/16 with ``patch_size=16``) resident on the current HIP device."""
+    """One OWL-ViT scorer (B/32, or B/16 with ``patch_size=16``), or an OWLv2 B/16 scorer (``family="owlv2"``), resident on the
+    current HIP device."""
 
     WEIGHTS_MODES = {"f32": 0, "bf16": 1, "bf16_exact": 3, "f32x3": 4}      # TSTAR_WEIGHTS_* of include/tstar_hip.h
 
     def __init__(self, vision_blob: Optional[np.ndarray], text_blob: Optional[np.ndarray] = None, max_batch: int = 32,
-                 weights_mode: str = "f32", patch_size: int = 32, input_size=None):
+                 weights_mode: str = "f32", patch_size: Optional[int] = None, input_size=None, family: str = "owlvit"):
         """``vision_blob=None`` gives a text-only handle: ``set_queries`` / ``get_query_embeds`` work (the CLIP text
         features of the YOLO-World backend), ``score`` raises.  ``patch_size``: 32 (B/32) or 16 (B/16); the vision blob is
         packed with ``weights.vision_spec`` of that geometry.  ``input_size=(height, width)``: the size images are resampled
         to before the vision tower, fixed for the scorer's life (default: the checkpoint's own 768 x 768); the vision blob is
         then ``pack_blob(sd, vision_spec(g), g)`` with ``g = weights.with_input_size(geometry, input_size)``, and ``score``
-        returns ``(height / patch) * (width / patch)`` detections per image."""
+        returns ``(height / patch) * (width / patch)`` detections per image.  ``family="owlv2"``: an OWLv2 B/16 checkpoint (image
+        960, patch 16; blobs packed with the specs of ``weights.OWLV2_B16``): HF's float pre-processing, boxes scaled by
+        max(H, W), and ``score(..., objectness=True)``."""
         import torch
         # ValueError before anything touches the device
-        self.geometry = W.with_input_size(W.geometry_for_patch(patch_size), input_size)
+        self.geometry = W.with_input_size(W.geometry_for_family(family, patch_size), input_size)
         if not torch.cuda.is_available():
             raise _lib.TStarHipError("OwlScorer needs a HIP device (torch.cuda.is_available() is False); "
                                      "tstar_amd has no CPU path")
@@ -77,10 +104,13 @@ class OwlScorer:
             vision_blob = np.ascontiguousarray(vision_blob, dtype=np.float32)
         if text_blob is not None:
             text_blob = np.ascontiguousarray(text_blob, dtype=np.float32)
-        lut = normalize_lut()
+        if family == "owlv2":       # the float path normalises with (x - mean) / std itself
+            lut = np.ascontiguousarray(OPENAI_CLIP_MEAN + OPENAI_CLIP_STD, dtype=np.float32)
+        else:
+            lut = normalize_lut()
         h = C.c_void_p()
-        rc = self._lib.tstar_owl_create_in(
-            C.byref(h), self.geometry.input_h, self.geometry.input_w, self.geometry.patch_size,
+        rc = self._lib.tstar_owl_create_family(
+            C.byref(h), FAMILY_CODES[self.family], self.geometry.input_h, self.geometry.input_w, self.geometry.patch_size,
             None if vision_blob is None else vision_blob.ctypes.data, 0 if vision_blob is None else vision_blob.size,
             None if text_blob is None else text_blob.ctypes.data, 0 if text_blob is None else text_blob.size,
             lut.ctypes.data, int(max_batch), self.WEIGHTS_MODES[weights_mode])
@@ -93,12 +123,18 @@ class OwlScorer:
         self.device = torch.device("cuda", torch.cuda.current_device())
 
     @classmethod
-    def synthetic(cls, seed: int = 0, max_batch: int = 32, with_text: bool = True, patch_size: int = 32, input_size=None):
-        g = W.with_input_size(W.geometry_for_patch(patch_size), input_size)
+    def synthetic(cls, seed: int = 0, max_batch: int = 32, with_text: bool = True, patch_size: Optional[int] = None, input_size=None,
+                  family: str = "owlvit"):
+        g = W.with_input_size(W.geometry_for_family(family, patch_size), input_size)
         sd = W.synthetic_state_dict(seed, "both" if with_text else "vision", geometry=g)
         vb = W.pack_blob(sd, W.vision_spec(g), g)
-        tb = W.pack_blob(sd, W.text_spec()) if with_text else None
-        return cls(vb, tb, max_batch, patch_size=patch_size, input_size=input_size)
+        tb = W.pack_blob(sd, W.text_spec(g)) if with_text else None
+        return cls(vb, tb, max_batch, patch_size=patch_size, input_size=input_size, family=family)
+
+    @property
+    def family(self) -> str:
+        """"owlvit" or "owlv2": the geometry's."""
+        return self.geometry.family
 
     def close(self):
         if getattr(self, "_h", None):
@@ -203,11 +239,26 @@ class OwlScorer:
         return out
 
     # ---- scoring
+    def _prepare_v2(self, H: int, Wd: int):
+        """OWLv2: before the first image of a new size, install numpy's Gaussian weights of its two axes (the library's own come
+        from libm's exp, which can differ from numpy's in the last bit; HF's processor is numpy)."""
+        S = max(int(H), int(Wd))
+        done = self.__dict__.setdefault("_v2_axes", set())       # the (square side, output size) axes already installed
+        for out in (self.geometry.input_h, self.geometry.input_w):
+            if (S, out) in done or S < 2:
+                continue
+            if owlv2_axis_radius(S, out) > 0:
+                gw = owlv2_gaussian_half(S, out)
+                _lib.check(self._lib.tstar_owlv2_set_axis_weights(self._h, S, out, gw.ctypes.data, int(gw.size)),
+                           "tstar_owlv2_set_axis_weights")
+            done.add((S, out))
+
     def score(self, images, grid_rows: int, grid_cols: int, want_logits: bool = False,
-              image_sets: Optional[Sequence[int]] = None, lane: int = 0) -> ScoreResult:
+              image_sets: Optional[Sequence[int]] = None, lane: int = 0, objectness: bool = False) -> ScoreResult:
         """images: torch u8 cuda tensor [B,H,W,3] (contiguous); ``image_sets``: query-set slot per image
         (default: slot 0 for all).  ``lane``: activation workspace of the forward (tstar_owl_score_lane) -- 0 = the handle's own,
-        1 = the small second one: a call on lane 1 enqueued on ANOTHER stream may run beside a call on lane 0 (same results)."""
+        1 = the small second one: a call on lane 1 enqueued on ANOTHER stream may run beside a call on lane 0 (same results).
+        ``objectness=True`` (OWLv2 only): also ``r.objectness`` f32 [B,np], HF's ``objectness_logits``; no other output changes."""
         torch = self._torch
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
             raise ValueError("score: images must be a cuda uint8 tensor [B,H,W,3]")
@@ -239,21 +290,38 @@ class OwlScorer:
                 raise ValueError("score: raw logits need the same query count for every image")
             r.logits = torch.empty((B, npatch, qs.pop()), dtype=torch.float32, device=dev)
             r.boxes_cxcywh = torch.empty((B, npatch, 4), dtype=torch.float32, device=dev)
-        rc = self._lib.tstar_owl_score_lane(
+        if objectness:
+            if self.family != "owlv2":
+                raise ValueError("score: objectness needs an OWLv2 scorer (OWL-ViT has no objectness head)")
+            r.objectness = torch.empty((B, npatch), dtype=torch.float32, device=dev)
+        if self.family == "owlv2":
+            self._prepare_v2(H, Wd)
+        rc = self._lib.tstar_owl_score_lane_obj(
             self._h, int(lane), images.data_ptr(), B, H, Wd, grid_rows, grid_cols,
             None if sets is None else sets.ctypes.data, r.scores.data_ptr(), r.labels.data_ptr(), r.boxes.data_ptr(), r.cell_conf.data_ptr(),
             r.cell_mask.data_ptr(), r.n_kept.data_ptr(),
-            _lib.ptr(r.logits), _lib.ptr(r.boxes_cxcywh), _lib.stream_ptr())
+            _lib.ptr(r.logits), _lib.ptr(r.boxes_cxcywh), _lib.ptr(r.objectness), _lib.stream_ptr())
         _lib.check(rc, "tstar_owl_score")
         return r
 
     def debug_preprocess(self, images):
+        """(u8 images after the bicubic pass, patch-embed A operand); an OWLv2 scorer has no u8 stage: (None, A operand)."""
         torch = self._torch
         images = images.contiguous()
         B, H, Wd, _ = images.shape
+        if self.family == "owlv2":
+            self._prepare_v2(H, Wd)
+            pat = torch.empty((B * self.num_patches, self.geometry.patch_k), dtype=torch.float32, device=images.device)
+            rc = self._lib.tstar_owl_debug_preprocess(self._h, images.data_ptr(), B, H, Wd, None, pat.data_ptr(), _lib.stream_ptr())
+            _lib.check(rc, "tstar_owl_debug_preprocess")
+            return None, pat
         u8 = torch.empty((B, self.geometry.input_h, self.geometry.input_w, 3), dtype=torch.uint8, device=images.device)
         pat = torch.empty((B * self.num_patches, self.geometry.patch_k), dtype=torch.float32, device=images.device)
         rc = self._lib.tstar_owl_debug_preprocess(self._h, images.data_ptr(), B, H, Wd, u8.data_ptr(),
                                                   pat.data_ptr(), _lib.stream_ptr())
         _lib.check(rc, "tstar_owl_debug_preprocess")
         return u8, pat
+
+    def preprocess_form(self, lane: int = 0) -> int:
+        """OWLv2: the kernel form of the last pre-processing launch of ``lane`` (0 direct, 1 filtered; -1 before the first)."""
+        return int(self._lib.tstar_owlv2_last_preprocess_form(self._h, int(lane)))

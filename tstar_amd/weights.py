@@ -1,4 +1,4 @@
-"""OWL-ViT-B/32 and B/16 parameter sets for the HIP scorer.
+"""OWL-ViT-B/32 and B/16, and OWLv2-B/16, parameter sets for the HIP scorer.
 
 The reference loads ``google/owlvit-base-patch32`` (or whatever checkpoint it is
 given) through HF transformers (/root/reference/TStar/interface_heuristic.py:207-210,
@@ -17,10 +17,12 @@ by entry in ``tstar_amd/csrc/owl_weights.h``).  This module
   and class-head shift/scale scaled by 0.01 so scores do not saturate
   (SURVEY.md 8c caveat (c)).
 
-Two vision geometries are supported (``OwlGeometry``): B/32 (the default
+Two OWL-ViT vision geometries are supported (``OwlGeometry``): B/32 (the default
 everywhere; the module-level constants below are its numbers) and B/16.  They
 share every width; only the patch grid, and with it the token count, the
-patch-embedding matrix, the position table and ``box_bias``, differ.
+patch-embedding matrix, the position table and ``box_bias``, differ.  OWLv2 B/16
+(``OWLV2_B16``: image 960, patch 16) is a third geometry of the other FAMILY: the
+same widths, keys prefixed ``owlv2.`` and an ``objectness_head`` after the box head.
 
 No torch import at module import time; numpy only.
 """
@@ -65,6 +67,9 @@ class OwlGeometry:
     # checkpoint's own image_size, so OwlGeometry(768, 32) == OwlGeometry(768, 32, 768, 768) == B32.  See with_input_size().
     input_h: int = 0
     input_w: int = 0
+    # the model family: "owlvit" (keys ``owlvit.*``, Pillow bicubic pre-processing, boxes scaled by (W, H)) or "owlv2" (keys
+    # ``owlv2.*``, an objectness head, pad-to-square + float resize, boxes scaled by max(H, W))
+    family: str = "owlvit"
 
     def __post_init__(self):
         if not self.input_h:
@@ -92,7 +97,12 @@ class OwlGeometry:
     @property
     def checkpoint(self) -> "OwlGeometry":
         """The same checkpoint at its own input size."""
-        return OwlGeometry(self.image_size, self.patch_size)
+        return OwlGeometry(self.image_size, self.patch_size, family=self.family)
+
+    @property
+    def prefix(self) -> str:
+        """Prefix of the towers' HF state-dict keys."""
+        return self.family + "."
 
     @property
     def npatch(self) -> int:
@@ -108,14 +118,17 @@ class OwlGeometry:
 
     @property
     def name(self) -> str:
-        return f"B/{self.patch_size}"
+        return f"B/{self.patch_size}" if self.family == "owlvit" else f"OWLv2 B/{self.patch_size}"
 
 
 B32 = OwlGeometry(768, 32)     # google/owlvit-base-patch32: grid 24, 576 patches, T = 577 (the default everywhere)
 B16 = OwlGeometry(768, 16)     # google/owlvit-base-patch16: grid 48, 2304 patches, T = 2305
-SUPPORTED = (B32, B16)
+OWLV2_B16 = OwlGeometry(960, 16, family="owlv2")   # google/owlv2-base-patch16(-ensemble, -finetuned): grid 60, 3600 patches, T = 3601
+SUPPORTED = (B32, B16)                             # the OWL-ViT geometries (what ``patch_size=`` chooses between)
+FAMILIES = ("owlvit", "owlv2")
 SUPPORTED_TEXT = ("OWL-ViT B/32 and B/16 (image 768, patch 32 or 16; vision 768 wide, MLP 3072, 12 layers, 12 heads; "
-                  "text 512 wide, MLP 2048, 12 layers, 8 heads; projection 512)")
+                  "text 512 wide, MLP 2048, 12 layers, 8 heads; projection 512), and OWLv2 B/16 (image 960, patch 16, the same "
+                  "widths, plus the objectness head)")
 
 
 MAX_NPATCH = 3600              # patches per image a run may ask for (T = 3601)
@@ -138,7 +151,7 @@ def with_input_size(geometry: OwlGeometry, input_size=None) -> OwlGeometry:
     P = g.patch_size
     if not ok or h <= 0 or w <= 0 or h % P or w % P or (h // P) * (w // P) > MAX_NPATCH:
         raise ValueError(f"input_size {input_size!r} is not supported at patch {P}: {INPUT_SIZE_RULE}")
-    return OwlGeometry(g.image_size, P, h, w)
+    return OwlGeometry(g.image_size, P, h, w, g.family)
 
 
 def input_size_from_env(name: str = "TSTAR_INPUT_SIZE"):
@@ -166,6 +179,18 @@ def geometry_for_patch(patch_size: int) -> OwlGeometry:
     raise ValueError(f"patch_size {patch_size!r} is not supported; supported: {SUPPORTED_TEXT}")
 
 
+def geometry_for_family(family: str = "owlvit", patch_size: Optional[int] = None) -> OwlGeometry:
+    """The checkpoint geometry of ``family`` ("owlvit": B/32, or B/16 with ``patch_size=16``; "owlv2": B/16 at image 960);
+    ValueError for an unknown family or a patch size the family does not have."""
+    if family == "owlvit":
+        return geometry_for_patch(32 if patch_size is None else patch_size)
+    if family == "owlv2":
+        if patch_size is not None and int(patch_size) != OWLV2_B16.patch_size:
+            raise ValueError(f"patch_size {patch_size!r} is not supported for owlv2; supported: {SUPPORTED_TEXT}")
+        return OWLV2_B16
+    raise ValueError(f"family {family!r} is not supported (one of {FAMILIES}); supported: {SUPPORTED_TEXT}")
+
+
 def _layer_spec(prefix: str, d: int, ff: int) -> Spec:
     p = prefix
     return [
@@ -187,7 +212,7 @@ def _layer_spec(prefix: str, d: int, ff: int) -> Spec:
 def vision_spec(geometry: OwlGeometry = B32) -> Spec:
     """(blob entry name, shape, HF state_dict names concatenated along dim 0)."""
     g = geometry
-    vm = "owlvit.vision_model."
+    vm = g.prefix + "vision_model."
     s: Spec = [
         ("patch_w", (V_D, g.patch_k), (vm + "embeddings.patch_embedding.weight",)),
         ("class_emb", (V_D,), (vm + "embeddings.class_embedding",)),
@@ -216,11 +241,21 @@ def vision_spec(geometry: OwlGeometry = B32) -> Spec:
         ("box2_b", (4,), ("box_head.dense2.bias",)),
         ("box_bias", (g.npatch, 4), ("box_bias",)),
     ]
+    if g.family == "owlv2":                 # Owlv2ForObjectDetection.objectness_head: a box-head-shaped MLP with one output
+        s += [
+            ("obj0_w", (V_D, V_D), ("objectness_head.dense0.weight",)),
+            ("obj0_b", (V_D,), ("objectness_head.dense0.bias",)),
+            ("obj1_w", (V_D, V_D), ("objectness_head.dense1.weight",)),
+            ("obj1_b", (V_D,), ("objectness_head.dense1.bias",)),
+            ("obj2_w", (1, V_D), ("objectness_head.dense2.weight",)),
+            ("obj2_b", (1,), ("objectness_head.dense2.bias",)),
+        ]
     return s
 
 
-def text_spec() -> Spec:
-    tm = "owlvit.text_model."
+def text_spec(geometry: OwlGeometry = B32) -> Spec:
+    """The text tower's entries; only the key prefix depends on the geometry (its family)."""
+    tm = geometry.prefix + "text_model."
     s: Spec = [
         ("tok_emb", (VOCAB, T_D), (tm + "embeddings.token_embedding.weight",)),
         ("tpos_emb", (T_LEN, T_D), (tm + "embeddings.position_embedding.weight",)),
@@ -230,7 +265,7 @@ def text_spec() -> Spec:
     s += [
         ("final_ln_w", (T_D,), (tm + "final_layer_norm.weight",)),
         ("final_ln_b", (T_D,), (tm + "final_layer_norm.bias",)),
-        ("text_proj", (PROJ, T_D), ("owlvit.text_projection.weight",)),
+        ("text_proj", (PROJ, T_D), (geometry.prefix + "text_projection.weight",)),
     ]
     return s
 
@@ -303,7 +338,7 @@ def _std_for(name: str, shape: Tuple[int, ...]) -> float:
         return (d ** -0.5) * ((2 * layers) ** -0.5)
     if "text_projection" in name:
         return T_D ** -0.5
-    if name.startswith("class_head") or name.startswith("box_head"):
+    if name.startswith("class_head") or name.startswith("box_head") or name.startswith("objectness_head"):
         return 0.02
     return 0.02
 
@@ -342,7 +377,7 @@ def synthetic_state_dict(seed: int = 0, towers: str = "both", geometry: OwlGeome
     if towers in ("both", "vision"):
         fill(vision_spec(geometry), np.random.RandomState(seed))
     if towers in ("both", "text"):
-        fill(text_spec(), np.random.RandomState(seed + 1))
+        fill(text_spec(geometry), np.random.RandomState(seed + 1))
     return out
 
 
@@ -354,7 +389,7 @@ def _hf_shape(hf: str, geometry: OwlGeometry = B32) -> Tuple[int, ...]:
     shapes = _HF_SHAPES.get(geometry)
     if shapes is None:
         shapes = _HF_SHAPES[geometry] = {}
-        for spec in (vision_spec(geometry), text_spec()):
+        for spec in (vision_spec(geometry), text_spec(geometry)):
             for _, shape, hf_names in spec:
                 k = len(hf_names)
                 for h in hf_names:
@@ -402,7 +437,7 @@ def pack_blob(sd: Dict[str, np.ndarray], spec: Spec, geometry: Optional[OwlGeome
         elif resized and name == "box_bias":
             arr = compute_box_bias(geometry)
         elif name == "box_bias" and "box_bias" not in sd:
-            g = next((g for g in SUPPORTED if g.npatch == shape[0]), None)
+            g = geometry.checkpoint if geometry is not None else next((g for g in SUPPORTED + (OWLV2_B16,) if g.npatch == shape[0]), None)
             if g is None:
                 raise ValueError(f"weight box_bias: no supported geometry has {shape[0]} patches")
             arr = compute_box_bias(g)
@@ -453,58 +488,76 @@ def load_safetensors_state_dict(path: str) -> Dict[str, np.ndarray]:
 
 
 # ---- checkpoint geometry ----------------------------------------------------------------------------------------------
-# configuration_owlvit.py defaults: a key that a config.json leaves out holds these values
+# configuration_owlvit.py / configuration_owlv2.py defaults: a key that a config.json leaves out holds these values
 _VISION_DEFAULTS = dict(hidden_size=768, intermediate_size=3072, num_hidden_layers=12, num_attention_heads=12, image_size=768,
                         patch_size=32)
+_VISION_DEFAULTS_V2 = dict(_VISION_DEFAULTS, patch_size=16)
 _TEXT_DEFAULTS = dict(hidden_size=512, intermediate_size=2048, num_hidden_layers=12, num_attention_heads=8)
 _VISION_FIXED = dict(hidden_size=V_D, intermediate_size=V_FF, num_hidden_layers=V_LAYERS, num_attention_heads=V_HEADS)
 _TEXT_FIXED = dict(hidden_size=T_D, intermediate_size=T_FF, num_hidden_layers=T_LAYERS, num_attention_heads=T_HEADS)
-_PATCH_KEY = "owlvit.vision_model.embeddings.patch_embedding.weight"
-_POS_KEY = "owlvit.vision_model.embeddings.position_embedding.weight"
+_PATCH_SUFFIX = "vision_model.embeddings.patch_embedding.weight"
+_POS_SUFFIX = "vision_model.embeddings.position_embedding.weight"
+_PATCH_KEY = "owlvit." + _PATCH_SUFFIX
+_POS_KEY = "owlvit." + _POS_SUFFIX
+_GEOMETRY_KEYS = tuple(f + "." + k for f in FAMILIES for k in (_PATCH_SUFFIX, _POS_SUFFIX))
 
 
 def geometry_of_config(cfg: dict) -> OwlGeometry:
-    """The geometry an OWL-ViT ``config.json`` (as a dict) describes; ValueError (naming what was found and what is
-    supported) for anything but B/32 and B/16."""
+    """The geometry an OWL-ViT / OWLv2 ``config.json`` (as a dict) describes; ValueError (naming what was found and what is
+    supported) for anything but OWL-ViT B/32 and B/16 and OWLv2 B/16 at image 960."""
     mt = cfg.get("model_type", "owlvit")
-    if mt != "owlvit":
-        raise ValueError(f"config model_type {mt!r} is not supported (OWLv2 and other families are out of scope); "
-                         f"supported: {SUPPORTED_TEXT}")
-    vc = dict(_VISION_DEFAULTS, **{k: v for k, v in (cfg.get("vision_config") or {}).items() if k in _VISION_DEFAULTS})
+    if mt not in FAMILIES:
+        raise ValueError(f"config model_type {mt!r} is not supported (only owlvit and owlv2 are); supported: {SUPPORTED_TEXT}")
+    vdef = _VISION_DEFAULTS if mt == "owlvit" else _VISION_DEFAULTS_V2
+    vc = dict(vdef, **{k: v for k, v in (cfg.get("vision_config") or {}).items() if k in vdef})
     tc = dict(_TEXT_DEFAULTS, **{k: v for k, v in (cfg.get("text_config") or {}).items() if k in _TEXT_DEFAULTS})
     proj = cfg.get("projection_dim", PROJ)
     found = (f"vision hidden {vc['hidden_size']}, MLP {vc['intermediate_size']}, {vc['num_hidden_layers']} layers, "
              f"{vc['num_attention_heads']} heads, image {vc['image_size']}, patch {vc['patch_size']}; text hidden {tc['hidden_size']}, "
              f"MLP {tc['intermediate_size']}, {tc['num_hidden_layers']} layers, {tc['num_attention_heads']} heads; projection {proj}")
     ok = all(vc[k] == v for k, v in _VISION_FIXED.items()) and all(tc[k] == v for k, v in _TEXT_FIXED.items()) and proj == PROJ
-    g = OwlGeometry(int(vc["image_size"]), int(vc["patch_size"]))
-    if not ok or g not in SUPPORTED:
-        raise ValueError(f"unsupported OWL-ViT geometry ({found}); supported: {SUPPORTED_TEXT}")
+    try:
+        g = OwlGeometry(int(vc["image_size"]), int(vc["patch_size"]), family=mt)
+    except (TypeError, ValueError):
+        ok, g = False, None
+    if not ok or g not in (SUPPORTED if mt == "owlvit" else (OWLV2_B16,)):
+        raise ValueError(f"unsupported {'OWL-ViT' if mt == 'owlvit' else 'owlv2'} geometry ({found}); supported: {SUPPORTED_TEXT}")
     return g
+
+
+def family_of_state_dict(keys) -> str:
+    """"owlvit" or "owlv2" by the key prefix of the vision tower's patch embedding; ValueError when neither is there."""
+    keys = set(keys)
+    for f in FAMILIES:
+        if f + "." + _PATCH_SUFFIX in keys or f + "." + _POS_SUFFIX in keys:
+            return f
+    raise ValueError(f"no {_PATCH_KEY} / {_POS_KEY} (nor their owlv2.* forms): not an OWL-ViT / OWLv2 detector state dict")
 
 
 def geometry_of_state_dict(shapes) -> OwlGeometry:
     """The geometry the vision tensors' shapes imply: ``patch_embedding`` [768, 3, P, P] and ``position_embedding``
-    [(768 / P)^2 + 1, 768].  ``shapes``: HF name -> shape or array (a state dict works)."""
-    shapes = {k: tuple(getattr(v, "shape", v)) for k, v in shapes.items() if k in (_PATCH_KEY, _POS_KEY)}
-    pe, pos = shapes.get(_PATCH_KEY), shapes.get(_POS_KEY)
+    [(image / P)^2 + 1, 768]; the family comes from the key prefix (``owlvit.`` / ``owlv2.``).  ``shapes``: HF name -> shape or
+    array (a state dict works)."""
+    shapes = {k: tuple(getattr(v, "shape", v)) for k, v in shapes.items() if k in _GEOMETRY_KEYS}
+    fam = family_of_state_dict(shapes)
+    pe, pos = shapes.get(fam + "." + _PATCH_SUFFIX), shapes.get(fam + "." + _POS_SUFFIX)
     if pe is None or pos is None:
-        raise ValueError(f"no {_PATCH_KEY} / {_POS_KEY}: not an OWL-ViT detector state dict")
+        raise ValueError(f"no {fam}.{_PATCH_SUFFIX} / {fam}.{_POS_SUFFIX}: not an OWL-ViT / OWLv2 detector state dict")
     if len(pe) != 4 or pe[0] != V_D or pe[1] != 3 or pe[2] != pe[3]:
-        raise ValueError(f"patch_embedding has shape {list(pe)}; supported: {SUPPORTED_TEXT}")
-    for g in SUPPORTED:
+        raise ValueError(f"{fam} patch_embedding has shape {list(pe)}; supported: {SUPPORTED_TEXT}")
+    for g in (SUPPORTED if fam == "owlvit" else (OWLV2_B16,)):
         if g.patch_size == pe[2]:
             if pos != (g.ntok, V_D):
-                raise ValueError(f"position_embedding has shape {list(pos)}; patch {pe[2]} wants [{g.ntok}, {V_D}]")
+                raise ValueError(f"{fam} position_embedding has shape {list(pos)}; patch {pe[2]} wants [{g.ntok}, {V_D}]")
             return g
-    raise ValueError(f"patch_embedding has shape {list(pe)} (patch {pe[2]}); supported: {SUPPORTED_TEXT}")
+    raise ValueError(f"{fam} patch_embedding has shape {list(pe)} (patch {pe[2]}); supported: {SUPPORTED_TEXT}")
 
 
 def geometry_of_checkpoint(path: str) -> OwlGeometry:
     """Geometry of a local checkpoint (a directory or its ``model.safetensors``): ``config.json`` next to the weights
-    (``vision_config`` / ``text_config`` / ``projection_dim``) cross-checked against the tensor shapes, which are read from
-    the safetensors header alone.  A disagreement or an unsupported geometry raises ValueError; without a config.json the
-    shapes decide."""
+    (``model_type`` / ``vision_config`` / ``text_config`` / ``projection_dim``) cross-checked against the tensor names and
+    shapes, which are read from the safetensors header alone.  A disagreement or an unsupported geometry raises ValueError;
+    without a config.json the tensors decide."""
     st = os.path.join(path, "model.safetensors") if os.path.isdir(path) else path
     cfg_path = os.path.join(os.path.dirname(st), "config.json")
     g_cfg = None
@@ -518,9 +571,9 @@ def geometry_of_checkpoint(path: str) -> OwlGeometry:
     from safetensors import safe_open
     with safe_open(st, framework="numpy") as f:
         keys = set(f.keys())
-        shapes = {k: tuple(f.get_slice(k).get_shape()) for k in (_PATCH_KEY, _POS_KEY) if k in keys}
+        shapes = {k: tuple(f.get_slice(k).get_shape()) for k in _GEOMETRY_KEYS if k in keys}
     g_w = geometry_of_state_dict(shapes)
     if g_cfg is not None and g_cfg != g_w:
         raise ValueError(f"config.json says {g_cfg.name} (image {g_cfg.image_size}, patch {g_cfg.patch_size}) but the weights are "
-                         f"{g_w.name}: patch_embedding {list(shapes[_PATCH_KEY])}, position_embedding {list(shapes[_POS_KEY])}")
+                         f"{g_w.name}: " + ", ".join(f"{k} {list(v)}" for k, v in sorted(shapes.items())))
     return g_w
