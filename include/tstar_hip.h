@@ -226,6 +226,30 @@ int tstar_owl_debug_preprocess(tstar_owl* h, const uint8_t* d_images, int B, int
                                uint8_t* d_out_u8 /* [B,input_h,input_w,3] */, float* d_out_patches /* [B*np,3*P*P] */,
                                void* stream);
 
+/* Diagnostics for kernel tests of the detector TAIL (everything after the encoder): the launchers tstar_owl_score runs, with the
+ * same arguments, on caller-supplied device tensors.  Added entries (no ABI bump).
+ *
+ * tstar_owl_debug_heads: detect_rows on d_feats [B*np,768] (image feats after the detection LayerNorm), d_cls [B*np,512] (the class
+ * head's dense0 output) and d_boxh [B*np,768] (the box head after dense1 + GELU), with the handle's head weights, box_bias, installed
+ * query sets and masks; np = tstar_owl_num_patches(h).  (H, W): the image size the boxes are scaled to -- by (W, H) on an OWL-ViT
+ * handle, by max(H, W) on both axes on an OWLv2 handle.  h_image_query_set (host, [B]), d_logits [B*np,Q] (needs one Q for every
+ * image) and d_boxes_cxcywh [B*np,4] may be NULL.  d_obj_hidden [B*np,768] with d_objectness [B*np] (both or neither; OWLv2 handle
+ * only): row_dot768 with the handle's objectness dense2.  B in 1..max_batch. */
+int tstar_owl_debug_heads(tstar_owl* h, const float* d_feats, const float* d_cls, const float* d_boxh, int B, int H, int W,
+                          const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, float* d_logits,
+                          float* d_boxes_cxcywh, const float* d_obj_hidden, float* d_objectness, void* stream);
+/* write_cls_rows (when write_cls != 0: token row 0 of every image = class embedding + position row 0, in place) and then
+ * merge_cls_ln on d_x [B*ntok,768] (ntok = np + 1) with the handle's post-LayerNorm / detection-LayerNorm weights:
+ * d_feats [B*np,768] = LN_det(LN_post(x[b,1+p]) * LN_post(x[b,0])).  B in 1..max_batch. */
+int tstar_owl_debug_merge(tstar_owl* h, float* d_x, int B, int write_cls, float* d_feats, void* stream);
+/* cell_reduce without a handle: d_scores [B,np], d_labels [B,np] (0..31; rows with score <= thr are not read), d_boxes_xyxy [B,np,4]
+ * -> d_cell_conf f64 [B,rows*cols], d_cell_mask u32 [B,rows*cols], d_n_kept [B] exactly as tstar_owl_score writes them.
+ * h_weights: HOST float64 [n_sets,32] class weights; h_image_set: HOST [B] weight row of every image, or NULL (row 0).  W, H: the
+ * image size in pixels.  At most 4096 cells.  Synchronises the stream.  Box centres are >= 0 (a sigmoid times a size). */
+int tstar_cell_reduce(const float* d_scores, const int32_t* d_labels, const float* d_boxes_xyxy, const double* h_weights, int n_sets,
+                      const int32_t* h_image_set, int B, int np, int W, int H, int grid_rows, int grid_cols, float thr,
+                      double* d_cell_conf, uint32_t* d_cell_mask, int32_t* d_n_kept, void* stream);
+
 /* ------------------------------------------------------------------ second detector backend: YOLO-World (D13)
  * Replaces YoloWorldInterface (interface_heuristic.py:39-190; wired at TStarFramework.py:178-184) -- the mmdet test
  * pipeline (keep-ratio resize to 640, letterbox pad 114, /255, channel swap), model.test_step (YOLOv8 CSPDarknet,

@@ -140,6 +140,74 @@ def test_round3_entry_points_validate_their_arguments(env):
     assert lib.tstar_comm_available() == 0                                                # torch's RCCL is loadable on a GPU box
 
 
+def test_owl_tail_diagnostic_entries_validate_their_arguments(env):
+    """tstar_owl_debug_heads / tstar_owl_debug_merge / tstar_cell_reduce: one case per refusal; nothing is launched on a refusal and
+    the handle is healthy afterwards."""
+    L, lib, h = env
+    h.reparameterize_object_list(["couch"], [])
+    sc = h.scorer
+    sc.get_query_embeds()                                    # slot 0's recorded queries go through the text tower now
+    sc.set_query_embeds(np.eye(3, 512, dtype=np.float32), [1, 1, 1], [1.0, 0.5, 0.5], slot=1)      # a set of another size than slot 0's
+    st = torch.cuda.current_stream().cuda_stream
+    npatch, B = sc.num_patches, 2
+    f = torch.zeros((B * npatch, 768), device="cuda")
+    c = torch.zeros((B * npatch, 512), device="cuda")
+    x = torch.zeros((B * (npatch + 1), 768), device="cuda")
+    o = torch.full((B * npatch, 4), 7.0, device="cuda")
+    lab = torch.full((B * npatch,), 7, dtype=torch.int32, device="cuda")
+    big = torch.zeros((B * npatch, 32), device="cuda")
+    sco = torch.full((B * npatch,), 7.0, device="cuda")
+    held = []                                                # the host arrays the calls below point into
+
+    def sets(*v):
+        held.append(np.ascontiguousarray(v, dtype=np.int32))
+        return held[-1].ctypes.data
+
+    def heads(hd=sc._h, feats=f.data_ptr(), cls=c.data_ptr(), boxh=f.data_ptr(), b=B, H=95, W=200, s=None, scores=sco.data_ptr(), labels=lab.data_ptr(),
+              xyxy=o.data_ptr(), logits=None, cxcywh=None, oh=None, ob=None):
+        return lib.tstar_owl_debug_heads(hd, feats, cls, boxh, b, H, W, s, scores, labels, xyxy, logits, cxcywh, oh, ob, st)
+
+    for bad, code, msg in ((dict(hd=None), 1, b"null argument"), (dict(feats=None), 1, b"null argument"), (dict(cls=None), 1, b"null argument"),
+                           (dict(boxh=None), 1, b"null argument"), (dict(scores=None), 1, b"null argument"), (dict(labels=None), 1, b"null argument"),
+                           (dict(xyxy=None), 1, b"null argument"), (dict(b=0), 1, b"B must be in 1..max_batch"), (dict(b=3), 1, b"B must be in 1..max_batch"),
+                           (dict(H=0), 1, b"empty image"), (dict(s=sets(0, 64)), 1, b"query_set must be in 0..63"),
+                           (dict(s=sets(0, 9)), 3, b"no queries installed"), (dict(s=sets(0, 1), logits=big.data_ptr()), 1, b"same query count"),
+                           (dict(oh=f.data_ptr(), ob=o.data_ptr()), 1, b"objectness needs an OWLv2 handle"),
+                           (dict(oh=f.data_ptr()), 1, b"go together")):
+        assert heads(**bad) == code and msg in lib.tstar_last_error(), (bad, lib.tstar_last_error())
+    for args, msg in (((None, x.data_ptr(), B, 0, f.data_ptr()), b"null argument"), ((sc._h, None, B, 0, f.data_ptr()), b"null argument"),
+                      ((sc._h, x.data_ptr(), B, 0, None), b"null argument"), ((sc._h, x.data_ptr(), 0, 0, f.data_ptr()), b"B must be in 1..max_batch"),
+                      ((sc._h, x.data_ptr(), 3, 1, f.data_ptr()), b"B must be in 1..max_batch")):
+        assert lib.tstar_owl_debug_merge(*args, st) == 1 and msg in lib.tstar_last_error(), (args, lib.tstar_last_error())
+    torch.cuda.synchronize()
+    assert (o == 7.0).all() and (sco == 7.0).all() and (lab == 7).all() and not f.any() and not x.any()      # nothing ran
+    wts = np.full((2, 32), 0.5)
+    conf = torch.full((B, 4), -1.0, dtype=torch.float64, device="cuda")
+    mask = torch.full((B, 4), -1, dtype=torch.int32, device="cuda")
+    kept = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+    s1 = torch.full((B, npatch), 0.5, device="cuda")
+
+    def cells(scores=s1.data_ptr(), labels=lab.data_ptr(), xyxy=o.data_ptr(), w=wts.ctypes.data, n_sets=2, s=None, b=B, n=npatch, W=200, H=95, rows=2, cols=2,
+              cf=conf.data_ptr(), mk=mask.data_ptr(), kp=kept.data_ptr()):
+        return lib.tstar_cell_reduce(scores, labels, xyxy, w, n_sets, s, b, n, W, H, rows, cols, 0.005, cf, mk, kp, st)
+
+    for bad, msg in ((dict(scores=None), b"null argument"), (dict(labels=None), b"null argument"), (dict(xyxy=None), b"null argument"),
+                     (dict(w=None), b"null argument"), (dict(cf=None), b"null argument"), (dict(mk=None), b"null argument"), (dict(kp=None), b"null argument"),
+                     (dict(b=0), b"empty batch or image"), (dict(n=0), b"empty batch or image"), (dict(W=0), b"empty batch or image"),
+                     (dict(n_sets=0), b"n_sets must be in 1..64"), (dict(n_sets=65), b"n_sets must be in 1..64"), (dict(s=sets(0, 2)), b"image set out of range"),
+                     (dict(rows=0), b"1..4096 cells"), (dict(rows=1, cols=4097), b"1..4096 cells")):
+        assert cells(**bad) == 1 and msg in lib.tstar_last_error(), (bad, lib.tstar_last_error())
+    torch.cuda.synchronize()
+    assert (conf == -1.0).all() and (mask == -1).all() and (kept == -1).all()                    # nothing ran
+    # healthy afterwards: both weight rows, labels 7 everywhere, every box the point (7, 7) of cell 0
+    assert cells(s=sets(1, 0)) == 0
+    torch.cuda.synchronize()
+    assert kept.tolist() == [npatch, npatch] and conf[:, 0].tolist() == [0.25, 0.25] and (conf[:, 1:] == 0).all() and (mask[:, 0] == 1 << 7).all()
+    assert heads(cxcywh=big.data_ptr()) == 0 and lib.tstar_owl_debug_merge(sc._h, x.data_ptr(), B, 1, f.data_ptr(), st) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(o).all() and torch.isfinite(sco).all() and int(lab.max()) < sc.Q and torch.isfinite(f).all() and x[0].any() and not x[1].any()
+
+
 def test_yolo_postprocess_argument_validation(env):
     """tstar_yolo_postprocess checks what tstar_yolo_detect checks, plus its own level arrays."""
     L, lib, _ = env

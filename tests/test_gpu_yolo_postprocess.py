@@ -310,10 +310,13 @@ def test_classes_and_mixed_query_sets(env):
 
 
 def test_cells(env):
-    """Scenario 7 (see yolo_post_util.scenario_cells): 1 x 1, 4 x 4 and 16 x 16 grids over 300 detections, non-dyadic weights."""
+    """Scenario 7 (see yolo_post_util.scenario_cells): 1 x 1, 4 x 4 and 16 x 16 grids over 300 detections, non-dyadic weights; then
+    the scenario's grids of non-representable cells, (3, 7) and (14, 12): on the second the centre (160, 180) lies on a border of
+    both axes, where the cell is numpy 1.26's float64 floor_divide (row 6, column 2), not floor(c / cell) (row 7, column 3)."""
     sc = U.scenario_cells()
     dev = upload(sc, env["params"])
-    for grid in ((1, 1), (4, 4), (16, 16)):
+    assert U.cell_index_forms(160.0, 640, 12) == (2, 3) and U.cell_index_forms(180.0, 360, 14) == (6, 7)      # the case cannot go dead
+    for grid in ((1, 1), (4, 4), (16, 16)) + sc["border_grids"]:
         out = run(env, sc, dev, [0, 0], grid=grid)
         lits = check(out, sc, [0, 0], grid=grid)
         for b, lit in enumerate(lits):

@@ -408,7 +408,11 @@ CELL_WEIGHTS = (1.0 / 3.0, 0.7, 0.1, 0.9)
 def scenario_cells():
     """360 x 640 (140 rows of padding above and below, scale 1): more than 300 disjoint boxes (300 detections); boxes in the
     padding that lie outside the image before the clamp; a box centred exactly on x = 160, y = 180 (a border of the 4 x 4
-    and of the 16 x 16 grid) and one far larger than the image, clamped on all four sides."""
+    and of the 16 x 16 grid) and one far larger than the image, clamped on all four sides.
+    ``border_grids``: grids whose cells are NOT representable.  (3, 7): 640 / 7-pixel columns; no centre of this head can sit on one
+    of its borders (centres are multiples of 1/16, 640 k / 7 is one only at the clamped image edge), so it only checks that such a
+    grid runs and agrees.  (14, 12): 360 / 14-pixel rows and 640 / 12-pixel columns, and the centre (160, 180) IS on a border of
+    both: numpy 1.26's float64 floor_divide gives cell (row 6, column 2), floor(c / cell) gives (7, 3) (``cell_index_forms``)."""
     rs = np.random.RandomState(17)
     B = 2
     lg, bins = _blank(B, 4)
@@ -422,7 +426,14 @@ def scenario_cells():
         an = anchor(2, 10, 10)
         bins[b, an] = [15, 15, 15, 15]                                             # [-144, -284, 816, 676]: clamped on all four sides
         lg[b, an, 2] = 4.5
-    return dict(name="cells", logits=lg, dfl=onehot_dfl(bins), H=360, W=640, Q=4, thr=0.12, max_dets=300, grid=(4, 4))
+    return dict(name="cells", logits=lg, dfl=onehot_dfl(bins), H=360, W=640, Q=4, thr=0.12, max_dets=300, grid=(4, 4), border_grids=((3, 7), (14, 12)))
+
+
+def cell_index_forms(c, size, n):
+    """(numpy 1.26's cell index of centre c -- np.float32 // Python float is a float64 floor_divide --, floor(double(c) / cell size))
+    on an axis of ``size`` pixels cut into n cells, both clamped to n - 1."""
+    cell = size / n
+    return min(int(np.float64(np.float32(c)) // cell), n - 1), min(int(np.floor(np.float64(np.float32(c)) / cell)), n - 1)
 
 
 SCENARIOS = dict(few=scenario_few, cut=scenario_cut, fallback=scenario_fallback, greedy=scenario_greedy, ties=scenario_ties,

@@ -313,6 +313,50 @@ static void free_lane(tstar_owl::Lane& L) {
     L = tstar_owl::Lane{};
 }
 
+#define CHECK_SET(set, fn) TSTAR_REQUIRE((set) >= 0 && (set) < TSTAR_OWL_MAX_SETS, fn ": query_set must be in 0..63")
+
+// every image's query set is installed; *q_uniform = the common Q when every image uses one set size, else 0
+static int check_image_sets(const tstar_owl* h, const int32_t* h_image_query_set, int B, int* q_uniform) {
+    int qu = -1;
+    for (int b = 0; b < B; ++b) {
+        const int set = h_image_query_set ? h_image_query_set[b] : 0;
+        CHECK_SET(set, "tstar_owl_score");
+        if (h->Q[set] == 0) { set_error("tstar_owl_score: no queries installed in the requested query set (call tstar_owl_set_queries first)"); return TSTAR_ERR_STATE; }
+        qu = (b == 0 || qu == h->Q[set]) ? h->Q[set] : 0;
+    }
+    *q_uniform = qu;
+    return TSTAR_OK;
+}
+
+// the image -> set array of a call, copied into the lane's device staging (grown when a larger batch arrives)
+static int stage_image_sets(tstar_owl::Lane& L, const int32_t* h_image_query_set, int B, hipStream_t s) {
+    if (B > L.image_set_cap) {
+        TSTAR_HIP_CHECK(hipStreamSynchronize(s));
+        if (L.d_image_set) TSTAR_HIP_CHECK(hipFree(L.d_image_set));
+        L.d_image_set = nullptr; L.image_set_cap = 0;
+        TSTAR_HIP_CHECK(hipMalloc(&L.d_image_set, (size_t)B * sizeof(int)));
+        L.image_set_cap = B;
+    }
+    TSTAR_HIP_CHECK(hipMemcpyAsync(L.d_image_set, h_image_query_set, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    return TSTAR_OK;
+}
+
+// boxes are relative to the resized image (OWL-ViT) or to the padded square (OWLv2: HF's _scale_boxes multiplies by max(H, W))
+static void box_scale(const OwlGeom& G, int H, int W, float* sx, float* sy) {
+    const bool v2 = G.family == TSTAR_OWL_FAMILY_OWLV2;
+    *sx = (float)(v2 ? (H > W ? H : W) : W);
+    *sy = (float)(v2 ? (H > W ? H : W) : H);
+}
+
+// the part of DetectRowsArgs that is the handle's own: head weights, installed queries
+static DetectRowsArgs detect_args(const tstar_owl* h) {
+    DetectRowsArgs a{};
+    a.qn = h->qn; a.qmask = h->qmask; a.setQ = h->d_setQ;
+    a.shift_w = h->vw.shift_w; a.shift_b = h->vw.shift_b; a.scale_w = h->vw.scale_w; a.scale_b = h->vw.scale_b;
+    a.box2_w = h->vw.box2_w; a.box2_b = h->vw.box2_b; a.box_bias = h->vw.box_bias;
+    return a;
+}
+
 extern "C" {
 
 const char* tstar_last_error(void) { return g_err.c_str(); }
@@ -498,8 +542,6 @@ int tstar_owl_destroy(tstar_owl* h) {
     delete h;
     return TSTAR_OK;
 }
-
-#define CHECK_SET(set, fn) TSTAR_REQUIRE((set) >= 0 && (set) < TSTAR_OWL_MAX_SETS, fn ": query_set must be in 0..63")
 
 static int finish_queries(tstar_owl* h, int set, const uint8_t* h_mask, const double* h_w, int Q, hipStream_t s) {
     const size_t qo = (size_t)set * TSTAR_OWL_MAX_QUERIES;
@@ -710,23 +752,9 @@ int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, in
         }
     }
     int q_uniform = -1;                                   // the common Q when every image uses one set size
-    for (int b = 0; b < B; ++b) {
-        const int set = h_image_query_set ? h_image_query_set[b] : 0;
-        CHECK_SET(set, "tstar_owl_score");
-        if (h->Q[set] == 0) { set_error("tstar_owl_score: no queries installed in the requested query set (call tstar_owl_set_queries first)"); return TSTAR_ERR_STATE; }
-        q_uniform = (b == 0 || q_uniform == h->Q[set]) ? h->Q[set] : 0;
-    }
+    RC(check_image_sets(h, h_image_query_set, B, &q_uniform));
     TSTAR_REQUIRE(!d_logits || q_uniform > 0, "tstar_owl_score: raw logits need the same query count for every image");
-    if (h_image_query_set) {
-        if (B > L.image_set_cap) {
-            TSTAR_HIP_CHECK(hipStreamSynchronize(s));
-            if (L.d_image_set) TSTAR_HIP_CHECK(hipFree(L.d_image_set));
-            L.d_image_set = nullptr; L.image_set_cap = 0;
-            TSTAR_HIP_CHECK(hipMalloc(&L.d_image_set, (size_t)B * sizeof(int)));
-            L.image_set_cap = B;
-        }
-        TSTAR_HIP_CHECK(hipMemcpyAsync(L.d_image_set, h_image_query_set, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-    }
+    if (h_image_query_set) RC(stage_image_sets(L, h_image_query_set, B, s));
     const int ncell = grid_rows * grid_cols;
     const OwlGeom& G = h->geom;
     const int NP = G.np, NTOK = G.ntok, PK = G.patch_k;
@@ -748,21 +776,16 @@ int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, in
         RC(gemm_f32(mk_gemm(h, feats, h->vw.cls_w, cls, h->vw.cls_b, nullptr, MP, PROJ, V_D, V_D, PROJ, ACT_NONE), s));
         RC(gemm_f32(mk_gemm(h, feats, h->vw.box0_w, bh1, h->vw.box0_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
         RC(gemm_f32(mk_gemm(h, bh1, h->vw.box1_w, bh2, h->vw.box1_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
-        DetectRowsArgs a{};
-        a.feats = feats; a.cls = cls; a.boxh = bh2; a.qn = h->qn; a.qmask = h->qmask;
-        a.shift_w = h->vw.shift_w; a.shift_b = h->vw.shift_b; a.scale_w = h->vw.scale_w; a.scale_b = h->vw.scale_b;
-        a.box2_w = h->vw.box2_w; a.box2_b = h->vw.box2_b; a.box_bias = h->vw.box_bias;
+        DetectRowsArgs a = detect_args(h);
+        a.feats = feats; a.cls = cls; a.boxh = bh2;
         a.scores = d_scores + (size_t)b0 * NP;
         a.labels = d_labels + (size_t)b0 * NP;
         a.xyxy = d_boxes_xyxy + (size_t)b0 * NP * 4;
         a.logits = d_logits ? d_logits + (size_t)b0 * NP * q_uniform : nullptr;
         a.image_set = h_image_query_set ? L.d_image_set + b0 : nullptr;
-        a.setQ = h->d_setQ;
         a.cxcywh = d_boxes_cxcywh ? d_boxes_cxcywh + (size_t)b0 * NP * 4 : nullptr;
         a.rows = MP; a.np = NP; a.Q = q_uniform;
-        // boxes are relative to the resized image (OWL-ViT) or to the padded square (OWLv2: HF's _scale_boxes multiplies by max(H, W))
-        const bool v2 = G.family == TSTAR_OWL_FAMILY_OWLV2;
-        a.box_sx = (float)(v2 ? (H > W ? H : W) : W); a.box_sy = (float)(v2 ? (H > W ? H : W) : H);
+        box_scale(G, H, W, &a.box_sx, &a.box_sy);
         RC(detect_rows(a, s));
         if (d_objectness) {                                   // after detect_rows: feats is still whole, the heads' buffers are free
             RC(gemm_f32(mk_gemm(h, feats, h->vw.obj0_w, bh1, h->vw.obj0_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
@@ -782,6 +805,70 @@ int tstar_owl_debug_preprocess(tstar_owl* h, const uint8_t* d_images, int B, int
     TSTAR_REQUIRE(B >= 1 && B <= h->max_batch, "tstar_owl_debug_preprocess: B must be in 1..max_batch");
     if (!h->has_vision) { set_error("tstar_owl_debug_preprocess: handle was created without vision weights (text-only)"); return TSTAR_ERR_STATE; }
     return preprocess_chunk(h, h->lane[0], d_images, B, H, W, d_out_u8, d_out_patches, (hipStream_t)stream);
+}
+
+int tstar_owl_debug_heads(tstar_owl* h, const float* d_feats, const float* d_cls, const float* d_boxh, int B, int H, int W,
+                          const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, float* d_logits,
+                          float* d_boxes_cxcywh, const float* d_obj_hidden, float* d_objectness, void* stream) {
+    TSTAR_REQUIRE(h && d_feats && d_cls && d_boxh && d_scores && d_labels && d_boxes_xyxy, "tstar_owl_debug_heads: null argument");
+    TSTAR_REQUIRE(B >= 1 && B <= h->max_batch, "tstar_owl_debug_heads: B must be in 1..max_batch");
+    TSTAR_REQUIRE(H >= 1 && W >= 1, "tstar_owl_debug_heads: empty image");
+    if (!h->has_vision) { set_error("tstar_owl_debug_heads: handle was created without vision weights (text-only)"); return TSTAR_ERR_STATE; }
+    TSTAR_REQUIRE(!d_obj_hidden == !d_objectness, "tstar_owl_debug_heads: d_obj_hidden and d_objectness go together");
+    TSTAR_REQUIRE(!d_objectness || h->geom.family == TSTAR_OWL_FAMILY_OWLV2, "tstar_owl_debug_heads: objectness needs an OWLv2 handle (OWL-ViT has no objectness head)");
+    hipStream_t s = (hipStream_t)stream;
+    auto& L = h->lane[0];
+    int q_uniform = -1;
+    RC(check_image_sets(h, h_image_query_set, B, &q_uniform));
+    TSTAR_REQUIRE(!d_logits || q_uniform > 0, "tstar_owl_debug_heads: raw logits need the same query count for every image");
+    if (h_image_query_set) RC(stage_image_sets(L, h_image_query_set, B, s));
+    const int NP = h->geom.np;
+    DetectRowsArgs a = detect_args(h);
+    a.feats = d_feats; a.cls = d_cls; a.boxh = d_boxh;
+    a.scores = d_scores; a.labels = d_labels; a.xyxy = d_boxes_xyxy; a.logits = d_logits; a.cxcywh = d_boxes_cxcywh;
+    a.image_set = h_image_query_set ? L.d_image_set : nullptr;
+    a.rows = B * NP; a.np = NP; a.Q = q_uniform;
+    box_scale(h->geom, H, W, &a.box_sx, &a.box_sy);
+    RC(detect_rows(a, s));
+    if (d_objectness) RC(row_dot768(d_obj_hidden, h->vw.obj2_w, h->vw.obj2_b, d_objectness, B * NP, s));
+    return TSTAR_OK;
+}
+
+int tstar_owl_debug_merge(tstar_owl* h, float* d_x, int B, int write_cls, float* d_feats, void* stream) {
+    TSTAR_REQUIRE(h && d_x && d_feats, "tstar_owl_debug_merge: null argument");
+    TSTAR_REQUIRE(B >= 1 && B <= h->max_batch, "tstar_owl_debug_merge: B must be in 1..max_batch");
+    if (!h->has_vision) { set_error("tstar_owl_debug_merge: handle was created without vision weights (text-only)"); return TSTAR_ERR_STATE; }
+    hipStream_t s = (hipStream_t)stream;
+    if (write_cls) RC(write_cls_rows(d_x, h->vw.class_emb, h->vw.pos_emb, B, h->geom.ntok, V_D, s));
+    return merge_cls_ln(d_x, d_feats, h->vw.post_ln_w, h->vw.post_ln_b, h->vw.det_ln_w, h->vw.det_ln_b, B, h->geom.ntok, V_D, s);
+}
+
+int tstar_cell_reduce(const float* d_scores, const int32_t* d_labels, const float* d_boxes_xyxy, const double* h_weights, int n_sets,
+                      const int32_t* h_image_set, int B, int np, int W, int H, int grid_rows, int grid_cols, float thr,
+                      double* d_cell_conf, uint32_t* d_cell_mask, int32_t* d_n_kept, void* stream) {
+    TSTAR_REQUIRE(d_scores && d_labels && d_boxes_xyxy && h_weights && d_cell_conf && d_cell_mask && d_n_kept, "tstar_cell_reduce: null argument");
+    TSTAR_REQUIRE(B >= 1 && np >= 1 && W >= 1 && H >= 1, "tstar_cell_reduce: empty batch or image");
+    TSTAR_REQUIRE(n_sets >= 1 && n_sets <= TSTAR_OWL_MAX_SETS, "tstar_cell_reduce: n_sets must be in 1..64");
+    TSTAR_REQUIRE(grid_rows > 0 && grid_cols > 0 && grid_rows * grid_cols <= 4096, "tstar_cell_reduce: grid must have 1..4096 cells");
+    for (int b = 0; h_image_set && b < B; ++b)
+        TSTAR_REQUIRE(h_image_set[b] >= 0 && h_image_set[b] < n_sets, "tstar_cell_reduce: image set out of range");
+    hipStream_t s = (hipStream_t)stream;
+    double* d_w = nullptr;
+    int* d_set = nullptr;
+    TSTAR_HIP_CHECK(hipMalloc(&d_w, (size_t)n_sets * TSTAR_OWL_MAX_QUERIES * sizeof(double)));
+    hipError_t e = hipMemcpyAsync(d_w, h_weights, (size_t)n_sets * TSTAR_OWL_MAX_QUERIES * sizeof(double), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && h_image_set) {
+        e = hipMalloc(&d_set, (size_t)B * sizeof(int));
+        if (e == hipSuccess) e = hipMemcpyAsync(d_set, h_image_set, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s);
+    }
+    int rc = TSTAR_OK;
+    if (e == hipSuccess)
+        rc = cell_reduce(d_scores, d_labels, d_boxes_xyxy, d_w, d_set, B, np, W, H, grid_rows, grid_cols, thr, d_cell_conf, d_cell_mask, d_n_kept, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);           // the staging copies are freed below
+    (void)hipFree(d_w);
+    if (d_set) (void)hipFree(d_set);
+    if (!rc && e != hipSuccess) { set_error(std::string("tstar_cell_reduce: ") + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
+    return rc;
 }
 
 int tstar_owlv2_last_preprocess_form(tstar_owl* h, int lane) {

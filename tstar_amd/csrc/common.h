@@ -59,6 +59,16 @@ __device__ __forceinline__ void store_px4(uint8_t* d, const unsigned (&v)[4][3])
     *reinterpret_cast<uint3*>(d) = o;
 }
 
+// numpy's float64 floor_divide (npy_divmod: fmod-based) for a >= 0, b > 0 -- what `np.float32 // Python float` is under the
+// reference's pinned numpy 1.26.  floor(a / b) is NOT the same number when b is a rounded quotient (800 / 6) and a sits on a
+// multiple of it: 400.0 / 133.33333333333334 rounds to 3.0, while 400.0 holds only two whole 133.33333333333334s.
+__device__ __forceinline__ double np_floor_divide(double a, double b) {
+    const double mod = fmod(a, b);
+    const double div = (a - mod) / b;
+    const double f = floor(div);
+    return div - f > 0.5 ? f + 1.0 : f;
+}
+
 }  // namespace tstar
 
 #define TSTAR_OK 0

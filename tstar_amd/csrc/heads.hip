@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void cell_reduce_kernel(const float* __restric
             const f32x4 bb = *reinterpret_cast<const f32x4*>(xyxy + r * 4);
             const float cx = (bb[0] + bb[2]) * 0.5f;          // f32 add, exact halving
             const float cy = (bb[1] + bb[3]) * 0.5f;
-            int gx = (int)floor((double)cx / cw), gy = (int)floor((double)cy / ch);
+            int gx = (int)np_floor_divide((double)cx, cw), gy = (int)np_floor_divide((double)cy, ch);   // cx // grid_width (:141-142)
             gx = gx < gcols - 1 ? gx : gcols - 1;
             gy = gy < grows - 1 ? gy : grows - 1;
             gx = gx < 0 ? 0 : gx; gy = gy < 0 ? 0 : gy;

@@ -1285,7 +1285,7 @@ __global__ __launch_bounds__(64) void det_cells_kernel(const float* __restrict__
         const double conf = (double)det_scores[r] * qweight[lab];
         const float* bb = det_boxes + r * 4;
         const float cx = (bb[0] + bb[2]) * 0.5f, cy = (bb[1] + bb[3]) * 0.5f;
-        int gx = (int)floor((double)cx / cw), gy = (int)floor((double)cy / ch);
+        int gx = (int)np_floor_divide((double)cx, cw), gy = (int)np_floor_divide((double)cy, ch);
         gx = gx < gcols - 1 ? gx : gcols - 1; gy = gy < grows - 1 ? gy : grows - 1;
         gx = gx < 0 ? 0 : gx; gy = gy < 0 ? 0 : gy;
         atomicMax(&cbits[gy * gcols + gx], (unsigned long long)__double_as_longlong(conf));
