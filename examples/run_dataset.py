@@ -11,6 +11,7 @@ a Motion-JPEG .avi, a .mjpeg stream, a folder of .jpg frames (--video-fps for th
 
   python examples/run_dataset.py --items 8 --out /tmp/results.json
   python examples/run_dataset.py --videos clips/a.avi clips/b_frames/ --video-fps 1
+  python examples/run_dataset.py --query-image mug=shots/my_mug.png --query-image dog=shots/rex.jpg
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_dataset.py --items 32
 """
 import argparse
@@ -44,6 +45,9 @@ def main():
                     help="video files / JPEG frame folders to search instead of synthetic videos (one item each; overrides --items)")
     ap.add_argument("--video-fps", type=float, default=None,
                     help="frame rate of JPEG frame folders (default 1) and .mjpeg streams (default 25) among --videos")
+    ap.add_argument("--query-image", action="append", default=[], metavar="NAME=PATH",
+                    help="example image of an object (repeatable): every target / cue object called NAME is searched for by the "
+                         "image-guided query embedded from PATH instead of by its text")
     args = ap.parse_args()
 
     import torch
@@ -83,6 +87,14 @@ def main():
             ap.error(f"--owl-input-size must look like HEIGHTxWIDTH, not {args.owl_input_size!r}")
     heuristic = initialize_heuristic("owl-vit", model_name_or_path=args.owl_model, synthetic_seed=0, max_batch=64,
                                      device=f"cuda:{local}", **owl_kw)
+    query_images = {}
+    for spec in args.query_image:
+        name, sep, path = spec.partition("=")
+        if not sep or not name.strip() or not path:
+            ap.error(f"--query-image must look like NAME=PATH, not {spec!r}")
+        query_images[name.strip()] = path
+    if query_images:
+        heuristic.set_query_images(query_images)
     mine = shard_items(len(items), world, rank)
     rows, dists = [], {}
     # two lock-step groups alternate on the GPU: one group's host bookkeeping runs under the other's verification batch

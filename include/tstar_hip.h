@@ -250,6 +250,30 @@ int tstar_cell_reduce(const float* d_scores, const int32_t* d_labels, const floa
                       const int32_t* h_image_set, int B, int np, int W, int H, int grid_rows, int grid_cols, float thr,
                       double* d_cell_conf, uint32_t* d_cell_mask, int32_t* d_n_kept, void* stream);
 
+/* Image-guided (one-shot) queries (added entries; tstar_abi_version() stays 3): HF's image_guided_detection up to the query vector,
+ * OwlViTForObjectDetection.embed_image_query (Owlv2ForObjectDetection's is the same statements).  An example image is pre-processed
+ * and run through the vision tower exactly like a target image; with class_embeds [np,512] (the class head's dense0 output, not
+ * normalised) and pred_boxes [np,4] (cxcywh): IoU of every box with the unit box [0,0,1,1] in float32 (generalized IoU instead when
+ * EVERY IoU is 0), thr = max * 0.8, the selected rows are those with value >= thr; among them the one whose class embedding has the
+ * smallest dot product with the mean class embedding of ALL rows (lowest index on a tie) is the query: class_embeds[best].  Install it
+ * with tstar_owl_set_query_embeds (which normalises by ||.|| + 1e-6 as the class head does) with query mask 1.
+ *
+ * tstar_owl_embed_image_queries: d_images u8 [n,H,W,3] on the device -> HOST arrays h_embeds f32 [n,512], h_best i32 [n] (row of the
+ * chosen patch), h_boxes_cxcywh f32 [n,4] (its pred_box: the bits tstar_owl_score returns as d_boxes_cxcywh for that image),
+ * h_n_selected i32 [n], h_status i32 [n]: 0 = IoU, 1 = the GIoU fallback was used, 2 = empty selection (the largest GIoU is negative;
+ * HF produces no query for such an image): embedding and box zeros, best -1, and the call still returns TSTAR_OK.  Runs in lane 0 (as
+ * the text tower does; keep it ordered with lane-0 score calls) in chunks of the handle's chunk limit; OWL-ViT and OWLv2 handles,
+ * any input size, every weights mode; installed queries are not touched.  Refuses bad arguments before anything is launched.
+ * Synchronises the stream.
+ *
+ * tstar_image_query_select: the selection alone, without a handle, on caller tensors d_cls f32 [n*np,512] (16-byte aligned) and
+ * d_boxes_cxcywh f32 [n*np,4] (w, h >= 0, no NaN), np in 1..3600; the launcher tstar_owl_embed_image_queries calls.  One workgroup
+ * per image; image i reads rows i*np .. (i+1)*np - 1 and nothing else.  Synchronises the stream. */
+int tstar_owl_embed_image_queries(tstar_owl* h, const uint8_t* d_images, int n, int H, int W, float* h_embeds, int32_t* h_best,
+                                  float* h_boxes_cxcywh, int32_t* h_n_selected, int32_t* h_status, void* stream);
+int tstar_image_query_select(const float* d_cls, const float* d_boxes_cxcywh, int n, int np, float* h_embeds, int32_t* h_best,
+                             float* h_boxes_cxcywh, int32_t* h_n_selected, int32_t* h_status, void* stream);
+
 /* ------------------------------------------------------------------ second detector backend: YOLO-World (D13)
  * Replaces YoloWorldInterface (interface_heuristic.py:39-190; wired at TStarFramework.py:178-184) -- the mmdet test
  * pipeline (keep-ratio resize to 640, letterbox pad 114, /255, channel swap), model.test_step (YOLOv8 CSPDarknet,

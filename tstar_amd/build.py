@@ -29,7 +29,8 @@ ARCH = "gfx950"
 # to the numpy statement of the reference (no FMA contraction).
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]
 # likewise preprocess_v2.hip: its float64 filter / zoom sums (device) and tables (host) are scipy's bits only without contraction
-PER_FILE = {"searcher.hip": ["-ffp-contract=off"], "preprocess_v2.hip": ["-ffp-contract=off"]}
+# image_query.hip: the IoU / GIoU arithmetic selects torch's rows only as plain float32 operations
+PER_FILE = {"searcher.hip": ["-ffp-contract=off"], "preprocess_v2.hip": ["-ffp-contract=off"], "image_query.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

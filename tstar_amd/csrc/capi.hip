@@ -3,6 +3,7 @@
 #include "../../include/tstar_hip.h"
 #include "common.h"
 #include "heads.h"
+#include "image_query.h"
 #include "ingest.h"
 #include "jpeg_host.h"
 #include "kernels.h"
@@ -355,6 +356,34 @@ static DetectRowsArgs detect_args(const tstar_owl* h) {
     a.shift_w = h->vw.shift_w; a.shift_b = h->vw.shift_b; a.scale_w = h->vw.scale_w; a.scale_b = h->vw.scale_b;
     a.box2_w = h->vw.box2_w; a.box2_b = h->vw.box2_b; a.box_bias = h->vw.box_bias;
     return a;
+}
+
+// One forward chunk up to the head tensors, shared by scoring and the image-query embedding: pre-processing of either family,
+// patch embedding, the encoder in the handle's weight mode, merge_cls_ln, the class head's dense0 and the box head's two GELU
+// layers.  The tensors live in the lane's workspaces (L.x is free again on return).
+struct OwlHeadTensors {
+    float* feats;    // [Bc * np, 768]  L.xn
+    float* cls;      // [Bc * np, 512]  L.att
+    float* bh1;      // [Bc * np, 768]  L.qkv: the box head's first layer (free once bh2 is written)
+    float* bh2;      // [Bc * np, 768]  L.hid
+};
+static int owl_forward_heads(tstar_owl* h, tstar_owl::Lane& L, const uint8_t* d_images, int Bc, int H, int W, OwlHeadTensors* t, hipStream_t s) {
+    const OwlGeom& G = h->geom;
+    const int NP = G.np, NTOK = G.ntok, PK = G.patch_k;
+    const int M = Bc * NTOK, MP = Bc * NP;
+    RC(preprocess_chunk(h, L, d_images, Bc, H, W, nullptr, L.hid, s));
+    GemmArgs pg = mk_gemm(h, L.hid, h->vw.patch_w, L.x, nullptr, nullptr, MP, V_D, PK, PK, V_D, ACT_NONE);
+    pg.pos = h->vw.pos_emb; pg.patch_np = NP;
+    RC(gemm_f32(pg, s));
+    RC(write_cls_rows(L.x, h->vw.class_emb, h->vw.pos_emb, Bc, NTOK, V_D, s));
+    RC(layernorm_f32(L.x, L.x, h->vw.pre_ln_w, h->vw.pre_ln_b, M, V_D, s));
+    RC(run_encoder(h, L, h->vw.layers, V_LAYERS, Bc, NTOK, V_D, V_FF, V_HEADS, 0, nullptr, s));
+    t->feats = L.xn; t->cls = L.att; t->bh1 = L.qkv; t->bh2 = L.hid;
+    RC(merge_cls_ln(L.x, t->feats, h->vw.post_ln_w, h->vw.post_ln_b, h->vw.det_ln_w, h->vw.det_ln_b, Bc, NTOK, V_D, s));
+    RC(gemm_f32(mk_gemm(h, t->feats, h->vw.cls_w, t->cls, h->vw.cls_b, nullptr, MP, PROJ, V_D, V_D, PROJ, ACT_NONE), s));
+    RC(gemm_f32(mk_gemm(h, t->feats, h->vw.box0_w, t->bh1, h->vw.box0_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
+    RC(gemm_f32(mk_gemm(h, t->bh1, h->vw.box1_w, t->bh2, h->vw.box1_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
+    return TSTAR_OK;
 }
 
 extern "C" {
@@ -757,25 +786,13 @@ int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, in
     if (h_image_query_set) RC(stage_image_sets(L, h_image_query_set, B, s));
     const int ncell = grid_rows * grid_cols;
     const OwlGeom& G = h->geom;
-    const int NP = G.np, NTOK = G.ntok, PK = G.patch_k;
+    const int NP = G.np;
     for (int b0 = 0; b0 < B; b0 += L.cap) {
         const int Bc = (B - b0) < L.cap ? (B - b0) : L.cap;
-        const int M = Bc * NTOK, MP = Bc * NP;
-        RC(preprocess_chunk(h, L, d_images + (size_t)b0 * H * W * 3, Bc, H, W, nullptr, L.hid, s));
-        GemmArgs pg = mk_gemm(h, L.hid, h->vw.patch_w, L.x, nullptr, nullptr, MP, V_D, PK, PK, V_D, ACT_NONE);
-        pg.pos = h->vw.pos_emb; pg.patch_np = NP;
-        RC(gemm_f32(pg, s));
-        RC(write_cls_rows(L.x, h->vw.class_emb, h->vw.pos_emb, Bc, NTOK, V_D, s));
-        RC(layernorm_f32(L.x, L.x, h->vw.pre_ln_w, h->vw.pre_ln_b, M, V_D, s));
-        RC(run_encoder(h, L, h->vw.layers, V_LAYERS, Bc, NTOK, V_D, V_FF, V_HEADS, 0, nullptr, s));
-        float* feats = L.xn;
-        RC(merge_cls_ln(L.x, feats, h->vw.post_ln_w, h->vw.post_ln_b, h->vw.det_ln_w, h->vw.det_ln_b, Bc, NTOK, V_D, s));
-        float* cls = L.att;      // [MP, 512]
-        float* bh1 = L.qkv;      // [MP, 768]
-        float* bh2 = L.hid;      // [MP, 768]
-        RC(gemm_f32(mk_gemm(h, feats, h->vw.cls_w, cls, h->vw.cls_b, nullptr, MP, PROJ, V_D, V_D, PROJ, ACT_NONE), s));
-        RC(gemm_f32(mk_gemm(h, feats, h->vw.box0_w, bh1, h->vw.box0_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
-        RC(gemm_f32(mk_gemm(h, bh1, h->vw.box1_w, bh2, h->vw.box1_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
+        const int MP = Bc * NP;
+        OwlHeadTensors t;
+        RC(owl_forward_heads(h, L, d_images + (size_t)b0 * H * W * 3, Bc, H, W, &t, s));
+        float *feats = t.feats, *cls = t.cls, *bh1 = t.bh1, *bh2 = t.bh2;
         DetectRowsArgs a = detect_args(h);
         a.feats = feats; a.cls = cls; a.boxh = bh2;
         a.scores = d_scores + (size_t)b0 * NP;
@@ -869,6 +886,75 @@ int tstar_cell_reduce(const float* d_scores, const int32_t* d_labels, const floa
     if (d_set) (void)hipFree(d_set);
     if (!rc && e != hipSuccess) { set_error(std::string("tstar_cell_reduce: ") + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
     return rc;
+}
+
+// device results of the selection -> the caller's host arrays; the staging buffer is freed here
+static int image_query_finish(const char* fn, int rc, void* d_buf, const ImageQueryOut& o, int n, float* h_embeds, int32_t* h_best, float* h_boxes,
+                              int32_t* h_n_selected, int32_t* h_status, hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemcpyAsync(h_embeds, o.embeds, (size_t)n * 512 * sizeof(float), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_boxes, o.boxes, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_best, o.best, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_n_selected, o.n_selected, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_status, o.status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);             // also before the staging buffer is freed after a failed launch
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(d_buf);
+    if (!rc && e != hipSuccess) { set_error(std::string(fn) + ": " + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
+    return rc;
+}
+
+int tstar_image_query_select(const float* d_cls, const float* d_boxes_cxcywh, int n, int np, float* h_embeds, int32_t* h_best, float* h_boxes_cxcywh,
+                             int32_t* h_n_selected, int32_t* h_status, void* stream) {
+    TSTAR_REQUIRE(d_cls && d_boxes_cxcywh && h_embeds && h_best && h_boxes_cxcywh && h_n_selected && h_status, "tstar_image_query_select: null argument");
+    TSTAR_REQUIRE(n >= 1 && n <= 65535, "tstar_image_query_select: n must be in 1..65535");
+    TSTAR_REQUIRE(np >= 1 && np <= IMAGE_QUERY_MAX_NP, "tstar_image_query_select: np must be in 1..3600");
+    TSTAR_REQUIRE(((uintptr_t)d_cls & 15) == 0, "tstar_image_query_select: d_cls must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    void* d_buf = nullptr;
+    TSTAR_HIP_CHECK(hipMalloc(&d_buf, image_query_out_bytes(n)));
+    const ImageQueryOut o = image_query_out_at(d_buf, n);
+    const int rc = image_query_select(d_cls, d_boxes_cxcywh, n, np, o, s);
+    return image_query_finish("tstar_image_query_select", rc, d_buf, o, n, h_embeds, h_best, h_boxes_cxcywh, h_n_selected, h_status, s);
+}
+
+int tstar_owl_embed_image_queries(tstar_owl* h, const uint8_t* d_images, int n, int H, int W, float* h_embeds, int32_t* h_best, float* h_boxes_cxcywh,
+                                  int32_t* h_n_selected, int32_t* h_status, void* stream) {
+    TSTAR_REQUIRE(h && d_images && h_embeds && h_best && h_boxes_cxcywh && h_n_selected && h_status, "tstar_owl_embed_image_queries: null argument");
+    TSTAR_REQUIRE(n >= 1 && n <= 65535 && H >= 1 && W >= 1, "tstar_owl_embed_image_queries: empty batch or image (n in 1..65535)");
+    if (!h->has_vision) { set_error("tstar_owl_embed_image_queries: handle was created without vision weights (text-only)"); return TSTAR_ERR_STATE; }
+    if (h->geom.family == TSTAR_OWL_FAMILY_OWLV2) {          // refusals before anything is launched
+        const Owlv2Plan vp = plan_owlv2_preprocess(H, W, h->geom.in_h, h->geom.in_w);
+        if (vp.error) { set_error(vp.error); return TSTAR_ERR_ARG; }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    auto& L = h->lane[0];                                     // the handle's own workspace, as the text tower
+    const int NP = h->geom.np;
+    void* d_buf = nullptr;
+    TSTAR_HIP_CHECK(hipMalloc(&d_buf, image_query_out_bytes(n)));
+    const ImageQueryOut o = image_query_out_at(d_buf, n);
+    int rc = TSTAR_OK;
+    for (int b0 = 0; b0 < n && !rc; b0 += L.cap) {
+        const int Bc = (n - b0) < L.cap ? (n - b0) : L.cap;
+        const int MP = Bc * NP;
+        OwlHeadTensors t;
+        rc = owl_forward_heads(h, L, d_images + (size_t)b0 * H * W * 3, Bc, H, W, &t, s);
+        if (rc) break;
+        // the box head's tail is detect_rows, as in tstar_owl_score (the boxes are its d_boxes_cxcywh bits); what it writes besides
+        // goes to L.x, which is free after merge_cls_ln: scores | labels | xyxy | cxcywh, each at a multiple of four floats
+        const size_t R = round_up((size_t)MP, 4);
+        DetectRowsArgs a = detect_args(h);
+        a.feats = t.feats; a.cls = t.cls; a.boxh = t.bh2;
+        a.scores = L.x; a.labels = reinterpret_cast<int*>(L.x + R); a.xyxy = L.x + 2 * R; a.cxcywh = L.x + 6 * R;
+        a.logits = nullptr; a.image_set = nullptr;
+        a.rows = MP; a.np = NP; a.Q = h->Q[0];
+        box_scale(h->geom, H, W, &a.box_sx, &a.box_sy);
+        rc = detect_rows(a, s);
+        if (!rc) rc = image_query_select(t.cls, a.cxcywh, Bc, NP, image_query_out_offset(o, b0), s);
+    }
+    return image_query_finish("tstar_owl_embed_image_queries", rc, d_buf, o, n, h_embeds, h_best, h_boxes_cxcywh, h_n_selected, h_status, s);
 }
 
 int tstar_owlv2_last_preprocess_form(tstar_owl* h, int lane) {

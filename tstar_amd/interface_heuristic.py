@@ -81,7 +81,13 @@ class OWLInterface(HeuristicInterface):
         ``state_dict`` (``owlvit.*`` / ``owlv2.*``); any other geometry (L/14, OWLv2 at image 768, ...) raises ValueError before
         anything is allocated on the device.  An OWLv2 heuristic pre-processes as HF's ``Owlv2ImageProcessorPil`` does (pad to a
         square, Gaussian anti-aliasing, linear resize; bit for bit), scales boxes by max(H, W) as its post-processing does, and
-        ``self.scorer.score(..., objectness=True)`` returns HF's ``objectness_logits``; image-guided queries are not supported.
+        ``self.scorer.score(..., objectness=True)`` returns HF's ``objectness_logits``.
+
+        Image-guided (one-shot) queries, both families: ``set_query_images({name: image})`` registers example images; from then
+        on any object NAME found in the registry is represented by its example's embedding (HF's ``embed_image_query``:
+        ``image_guided_detection`` up to the query vector) instead of its text, in every way queries are installed.  HF's
+        ``post_process_image_guided_detection`` (NMS, per-image score rescaling) is not part of it: an image-backed query is
+        scored, thresholded and weighted exactly like a text query.
         ``family`` ("owlvit" / "owlv2") chooses the family of SYNTHETIC weights; not given, it is ``TSTAR_OWL_FAMILY``, else
         "owlv2" when ``model_name_or_path`` contains ``owlv2``, else "owlvit"; given together with real weights it must agree
         with them.  ``patch_size`` (32 or 16) chooses
@@ -187,6 +193,59 @@ class OWLInterface(HeuristicInterface):
         self.detections_inbatch: List[Detections] = []
         self._class_weight: Optional[np.ndarray] = None
         self._ids = None
+        self._query_images: Dict[str, np.ndarray] = {}       # name -> raw class embedding f32 [512] of its example image
+        self.query_image_info: Dict[str, Dict] = {}
+
+    # ---- image-guided queries ------------------------------------------------------------
+    def set_query_images(self, images: Dict[str, object]):
+        """Register example images: ``{name: HxWx3 uint8 RGB array, or the path of an image file}``.  They are embedded at once
+        (images of one size in one batched ``OwlScorer.embed_image_queries`` call) and the embeddings cached; from the next
+        ``reparameterize_object_list`` / ``install_queries`` / ``install_queries_many`` on, a target or cue object whose name
+        (after ``.strip()``) is registered is represented by its example's embedding instead of its text -- ``texts``, labels,
+        class weights, the trailing blank query and the 32-query limit are as before, so a searcher needs no change.
+        ``query_image_info[name]`` = ``{"best_index", "box_cxcywh", "n_selected", "giou_fallback"}``.  An example for which HF
+        would produce no query (no box within 80 % of the best overlap: every generalized IoU negative) raises ValueError naming
+        the object, and nothing is registered.  Queries already installed are not touched."""
+        import torch
+        from PIL import Image
+        arrays = {}
+        for name, img in images.items():
+            key = str(name).strip()
+            if not key:
+                raise ValueError("set_query_images: an object name must not be blank")
+            if isinstance(img, (str, os.PathLike)):
+                with Image.open(img) as im:
+                    img = np.asarray(im.convert("RGB"), dtype=np.uint8)
+            img = np.ascontiguousarray(img)
+            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+                raise ValueError(f"set_query_images: {key!r} must be an HxWx3 uint8 RGB image or a path")
+            arrays[key] = img
+        by_shape: Dict[tuple, List[str]] = {}
+        for key, img in arrays.items():
+            by_shape.setdefault(img.shape, []).append(key)
+        embeds, info = {}, {}
+        for keys in by_shape.values():
+            r = self.scorer.embed_image_queries(torch.from_numpy(np.stack([arrays[k] for k in keys])).cuda())
+            for i, key in enumerate(keys):
+                if int(r.status[i]) == 2:
+                    raise ValueError(f"set_query_images: no query can be formed from the example image of {key!r}: none of its "
+                                     "predicted boxes overlaps the whole image (empty selection in HF's embed_image_query)")
+                embeds[key] = r.embeds[i].copy()
+                info[key] = dict(best_index=int(r.best[i]), box_cxcywh=r.boxes_cxcywh[i].copy(), n_selected=int(r.n_selected[i]),
+                                 giou_fallback=bool(r.status[i] == 1))
+        self._query_images.update(embeds)
+        self.query_image_info.update(info)
+
+    def clear_query_images(self):
+        """Forget every example image: names are text queries again from the next install on."""
+        self._query_images = {}
+        self.query_image_info = {}
+
+    def _image_overrides(self, texts):
+        """{query row: embedding} of the rows of ``texts`` whose name has an example image (never the trailing blank query)."""
+        if not self._query_images:
+            return None
+        return {i: self._query_images[t[0]] for i, t in enumerate(texts[:-1]) if t[0] in self._query_images} or None
 
     # ---- reference surface -------------------------------------------------------------
     def reparameterize_object_list(self, target_objects: List[str], cue_objects: List[str]):
@@ -199,7 +258,7 @@ class OWLInterface(HeuristicInterface):
         w = [1.0] * len(target_objects) + [0.5] * len(cue_objects) + [0.5]
         # recorded now, run through the text tower when slot 0 is first used (OwlScorer.set_queries): a searcher's constructor
         # calls this like the reference's, but a lock-step group never scores against slot 0
-        self.scorer.set_queries(ids, am, w, lazy=True)
+        self.scorer.set_queries(ids, am, w, lazy=True, overrides=self._image_overrides(self.texts))
         self._class_weight = np.asarray(w, dtype=np.float64)
 
     def inference_detector(self, images, **kwargs) -> List[Detections]:
@@ -245,13 +304,14 @@ class OWLInterface(HeuristicInterface):
         """Install a question's queries in slot 1..63 WITHOUT touching ``self.texts`` (slot 0 is what
         ``reparameterize_object_list`` manages).  Several (video, question) items can then be scored in
         one batch, each image against its own slot.  Returns the texts list of the slot."""
-        texts, (slot, ids, am, weights) = self._query_entry(slot, target_objects, cue_objects, object2weight)
-        self.scorer.set_queries(ids, am, weights, slot=slot)
+        texts, (slot, ids, am, weights, overrides) = self._query_entry(slot, target_objects, cue_objects, object2weight)
+        self.scorer.set_queries(ids, am, weights, slot=slot, overrides=overrides)
         return texts
 
     def _query_entry(self, slot, target_objects, cue_objects, object2weight):
-        """(texts of the slot, (slot, token ids, attention mask, class weights)) of one question: blank query appended, targets
-        weigh 1.0 and cues 0.5 unless ``object2weight`` says otherwise (interface_searcher.py:88-91, 135-137)."""
+        """(texts of the slot, (slot, token ids, attention mask, class weights, image rows)) of one question: blank query appended,
+        targets weigh 1.0 and cues 0.5 unless ``object2weight`` says otherwise (interface_searcher.py:88-91, 135-137); image rows:
+        ``_image_overrides``."""
         if not 1 <= int(slot) <= 63:
             raise ValueError("install_queries: slot must be in 1..63")
         texts = [[obj.strip()] for obj in list(target_objects) + list(cue_objects)] + [[' ']]
@@ -261,7 +321,7 @@ class OWLInterface(HeuristicInterface):
             o2w.setdefault(o, 1.0)
         for o in cue_objects:
             o2w.setdefault(o, 0.5)
-        return texts, (int(slot), ids, am, [float(o2w.get(t[0], 0.5)) for t in texts])
+        return texts, (int(slot), ids, am, [float(o2w.get(t[0], 0.5)) for t in texts], self._image_overrides(texts))
 
     def install_queries_many(self, items) -> List[List[List[str]]]:
         """``install_queries`` for several slots at once -- ``items``: [(slot, target_objects, cue_objects, object2weight)] -- with
@@ -392,6 +452,11 @@ class YoloWorldInterface(HeuristicInterface):
         self._pending0 = (ids, am, list(w))
         self._text_feats = None
         self._class_weight = np.asarray(w, dtype=np.float64)
+
+    def set_query_images(self, images):
+        """Image-guided queries are OWL-ViT / OWLv2's (``OWLInterface.set_query_images``): YOLO-World has no counterpart."""
+        raise NotImplementedError("YoloWorldInterface has no image-guided queries: YOLO-World matches text features only; use the "
+                                  "OWL-ViT / OWLv2 heuristic (heuristic_type='owl-vit') for example images")
 
     def _flush0(self):
         """Install the recorded queries of slot 0 (see ``reparameterize_object_list``)."""

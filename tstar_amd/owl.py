@@ -72,6 +72,19 @@ class ScoreResult:
     objectness: "object" = None   # f32 [B,np]: HF's objectness_logits (OWLv2 only, ``score(..., objectness=True)``)
 
 
+IMAGE_QUERY_IOU, IMAGE_QUERY_GIOU, IMAGE_QUERY_EMPTY = 0, 1, 2     # ImageQueryResult.status (tstar_owl_embed_image_queries)
+
+
+@dataclass
+class ImageQueryResult:
+    """Host arrays of one tstar_owl_embed_image_queries call, one entry per example image (HF's ``embed_image_query``)."""
+    embeds: np.ndarray        # f32 [n,512] class embedding of the chosen patch, NOT normalised (zeros where status is 2)
+    best: np.ndarray          # i32 [n] the chosen patch (-1 where status is 2)
+    boxes_cxcywh: np.ndarray  # f32 [n,4] its pred_box, relative
+    n_selected: np.ndarray    # i32 [n] patches with IoU (GIoU) >= 0.8 x the maximum
+    status: np.ndarray        # i32 [n] 0 IoU, 1 the GIoU fallback was used, 2 empty selection (HF produces no query)
+
+
 class OwlScorer:
     """One OWL-ViT scorer (B/32, or B/16 with ``patch_size=16``), or an OWLv2 B/16 scorer (``family="owlv2"``), resident on the
     current HIP device."""
@@ -119,7 +132,7 @@ class OwlScorer:
         self.num_patches = int(self._lib.tstar_owl_num_patches(h))   # detections per image: 576 (B/32) or 2304 (B/16)
         self.max_batch = int(max_batch)
         self.Qs = {}                # query-set slot -> number of queries
-        self._pending = {}          # slot -> (ids, mask, weights) recorded by set_queries(lazy=True), installed on first use
+        self._pending = {}          # slot -> (ids, mask, weights, image-backed rows) recorded by set_queries(lazy=True), installed on first use
         self.device = torch.device("cuda", torch.cuda.current_device())
 
     @classmethod
@@ -153,8 +166,11 @@ class OwlScorer:
         return self.Qs.get(0, 0)
 
     def set_queries(self, input_ids: np.ndarray, attention_mask: np.ndarray, class_weight: Sequence[float], slot: int = 0,
-                    lazy: bool = False):
-        """Run the text tower on the queries and install them in ``slot``.  ``lazy=True`` only records them (after the checks
+                    lazy: bool = False, overrides=None):
+        """Run the text tower on the queries and install them in ``slot``.  ``overrides``: {row: raw embedding f32 [512]} -- rows
+        that an image-guided query stands for (``embed_image_queries``): after the text install the slot is read back, those rows
+        replaced and the set installed again with query mask 1 for them; the text rows keep their raw bits, so their normalised
+        bits too.  ``lazy=True`` only records them (after the checks
         the library would make): the text tower runs when the slot is first USED -- scored against, read back, re-weighted.
         A searcher's constructor installs its question in slot 0 like the reference's does (interface_searcher.py:87), but a
         lock-step group scores every item against its own slot 1..63 and never touches slot 0; the solo path uses it at once."""
@@ -164,32 +180,61 @@ class OwlScorer:
         Q = ids.shape[0]
         if ids.shape != (Q, W.T_LEN) or am.shape != ids.shape or w.shape != (Q,):
             raise ValueError("set_queries: ids/mask must be [Q,16] and class_weight [Q]")
+        overrides = self._check_overrides(overrides, Q)
         self._pending.pop(int(slot), None)
         if lazy:
             if not 1 <= Q <= 32:
                 raise _lib.TStarHipError(f"tstar_owl_set_queries: Q must be in 1..32 (got {Q})")
             if ids.min() < 0 or ids.max() >= 49408:
                 raise _lib.TStarHipError("tstar_owl_set_queries: token id out of range")
-            self._pending[int(slot)] = (ids.copy(), am.copy(), w.copy())
+            self._pending[int(slot)] = (ids.copy(), am.copy(), w.copy(), overrides)
             self.Qs[int(slot)] = Q
             return
         rc = self._lib.tstar_owl_set_queries(self._h, int(slot), ids.ctypes.data, am.ctypes.data, w.ctypes.data, Q,
                                              _lib.stream_ptr())
         _lib.check(rc, "tstar_owl_set_queries")
         self.Qs[int(slot)] = Q
+        self._apply_overrides(int(slot), ids, w, overrides)
+
+    @staticmethod
+    def _check_overrides(overrides, Q):
+        if not overrides:
+            return None
+        out = {}
+        for row, e in overrides.items():
+            e = np.ascontiguousarray(e, dtype=np.float32)
+            if not 0 <= int(row) < Q or e.shape != (W.PROJ,):
+                raise ValueError("set_queries: overrides must map a query row to a float32 [512] embedding")
+            out[int(row)] = e.copy()
+        return out
+
+    def _apply_overrides(self, slot, ids, w, overrides):
+        """Image-backed rows of a slot the text tower has just filled: raw rows read back, the image rows replaced, installed
+        again (tstar_owl_set_query_embeds re-derives the normalised rows; the query mask of a text row is ``ids[:, 0] > 0`` as
+        tstar_owl_set_queries computes it, of an image row 1)."""
+        if not overrides:
+            return
+        e = self.get_query_embeds(slot)
+        mask = (ids[:, 0] > 0).astype(np.uint8)
+        for row, emb in overrides.items():
+            e[row] = emb
+            mask[row] = 1
+        self.set_query_embeds(e, mask, w, slot=slot)
 
     def _flush(self, slots):
         """Install the recorded (lazy) queries of the slots about to be used."""
         for sl in {int(v) for v in slots}:
             p = self._pending.pop(sl, None)
             if p is not None:
-                self.set_queries(p[0], p[1], p[2], slot=sl)
+                self.set_queries(p[0], p[1], p[2], slot=sl, overrides=p[3])
 
     def set_queries_many(self, entries):
         """``entries``: [(slot, input_ids [Q,16], attention_mask [Q,16], class_weight [Q])] -- the queries of several slots through
-        ONE text-tower forward (tstar_owl_set_queries_many); bit-identical to one ``set_queries`` call per slot."""
+        ONE text-tower forward (tstar_owl_set_queries_many); bit-identical to one ``set_queries`` call per slot.  An entry may
+        carry a fifth element, the ``overrides`` of ``set_queries``."""
         if not entries:
             return
+        overrides = [self._check_overrides(e[4] if len(e) > 4 else None, np.shape(e[1])[0]) for e in entries]
         slots = np.ascontiguousarray([int(e[0]) for e in entries], dtype=np.int32)
         ids = [np.ascontiguousarray(e[1], dtype=np.int32) for e in entries]
         am = [np.ascontiguousarray(e[2], dtype=np.int32) for e in entries]
@@ -205,6 +250,8 @@ class OwlScorer:
         for sl, q in zip(slots, Qs):
             self._pending.pop(int(sl), None)
             self.Qs[int(sl)] = int(q)
+        for sl, i_, w_, ov in zip(slots, ids, w, overrides):
+            self._apply_overrides(int(sl), i_, w_, ov)
 
     def set_query_embeds(self, embeds: np.ndarray, query_mask: Sequence[int], class_weight: Sequence[float], slot: int = 0):
         e = np.ascontiguousarray(embeds, dtype=np.float32)
@@ -225,7 +272,7 @@ class OwlScorer:
             raise ValueError("set_class_weights: one weight per installed query")
         if int(slot) in self._pending:                       # not installed yet: the weights ride along
             p = self._pending[int(slot)]
-            self._pending[int(slot)] = (p[0], p[1], w.copy())
+            self._pending[int(slot)] = (p[0], p[1], w.copy(), p[3])
             return
         rc = self._lib.tstar_owl_set_class_weights(self._h, int(slot), w.ctypes.data, len(w), _lib.stream_ptr())
         _lib.check(rc, "tstar_owl_set_class_weights")
@@ -237,6 +284,28 @@ class OwlScorer:
         rc = self._lib.tstar_owl_get_query_embeds(self._h, int(slot), out.ctypes.data, q, _lib.stream_ptr())
         _lib.check(rc, "tstar_owl_get_query_embeds")
         return out
+
+    # ---- image-guided queries
+    def embed_image_queries(self, images) -> ImageQueryResult:
+        """images: torch u8 cuda tensor [n,H,W,3] of example images -> ``ImageQueryResult`` (host arrays): HF's
+        ``embed_image_query`` per image -- the class embedding of the patch whose box covers the image best and is least like the
+        mean embedding.  Runs in lane 0; installed queries are untouched.  Install ``embeds[i]`` with ``set_query_embeds`` (mask
+        1) or through ``set_queries(..., overrides=)``; an image with ``status == 2`` has no query (HF skips it too)."""
+        torch = self._torch
+        if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
+            raise ValueError("embed_image_queries: images must be a cuda uint8 tensor [n,H,W,3]")
+        images = images.contiguous()
+        n, H, Wd, _ = images.shape
+        if n < 1:
+            raise ValueError("embed_image_queries: no image")
+        r = ImageQueryResult(embeds=np.zeros((n, W.PROJ), np.float32), best=np.zeros(n, np.int32), boxes_cxcywh=np.zeros((n, 4), np.float32),
+                             n_selected=np.zeros(n, np.int32), status=np.zeros(n, np.int32))
+        if self.family == "owlv2":
+            self._prepare_v2(H, Wd)
+        rc = self._lib.tstar_owl_embed_image_queries(self._h, images.data_ptr(), n, H, Wd, r.embeds.ctypes.data, r.best.ctypes.data,
+                                                     r.boxes_cxcywh.ctypes.data, r.n_selected.ctypes.data, r.status.ctypes.data, _lib.stream_ptr())
+        _lib.check(rc, "tstar_owl_embed_image_queries")
+        return r
 
     # ---- scoring
     def _prepare_v2(self, H: int, Wd: int):
