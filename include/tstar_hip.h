@@ -66,7 +66,9 @@ typedef struct tstar_owl tstar_owl;
  *     round-to-nearest bf16 terms a_hi + a_lo (16 significand bits, |a - a_hi - a_lo| <= 2^-17 |a|):
  *     C += a_lo*w + a_hi*w, exact products, f32 accumulation -- 2 MFMA products per algorithmic product.
  *     Detector scores stay within 1e-3 of a float32 run on the same rounded weights (tests state the measured
- *     bound, ~1e-5).  The vision tower's attention runs on the bf16 pipe as well in modes 1 and 3 (f32-split
+ *     bound, ~1e-5).  The text tower is the exception: its GEMMs (once per query set, M <= 512 rows) run with the exact
+ *     three-term split of mode 3 on the same bf16 plane, so the query embeddings, which enter every score, are the
+ *     float32-class embeddings of the rounded checkpoint.  The vision tower's attention runs on the bf16 pipe as well in modes 1 and 3 (f32-split
  *     operands: two bf16 terms each, 3 products, f32 accumulation).
  *   (2, TSTAR_WEIGHTS_F32_SPLIT of ABI 2 -- both operands as two bf16 terms, 16 significand bits -- is retired and
  *     refused; TSTAR_WEIGHTS_F32X3 below carries all 24 bits.)
@@ -242,6 +244,17 @@ int tstar_owl_debug_heads(tstar_owl* h, const float* d_feats, const float* d_cls
  * merge_cls_ln on d_x [B*ntok,768] (ntok = np + 1) with the handle's post-LayerNorm / detection-LayerNorm weights:
  * d_feats [B*np,768] = LN_det(LN_post(x[b,1+p]) * LN_post(x[b,0])).  B in 1..max_batch. */
 int tstar_owl_debug_merge(tstar_owl* h, float* d_x, int B, int write_cls, float* d_feats, void* stream);
+/* The vision tower's entry as the forward runs it, in lane 0's workspace (an added entry; tstar_abi_version() stays 3): the patch
+ * embedding GEMM on d_patches [B*np, patch_k] (the handle's weight plane of its weights mode, its -- possibly resampled -- position
+ * table, token rows 1..np of every image), then write_cls_rows (token row 0).  stage 0 stops there; stage 1 also runs the
+ * pre-LayerNorm IN PLACE, as the forward does.  The token rows are copied to d_x [B*ntok, 768].  B in 1..the images of one forward
+ * chunk (min(max_batch, chunk limit)); any other stage is refused. */
+int tstar_owl_debug_embed(tstar_owl* h, const float* d_patches, int B, int stage, float* d_x, void* stream);
+/* The text tower as tstar_owl_set_queries runs it, in the handle's workspace, WITHOUT installing a query set (an added entry;
+ * tstar_abi_version() stays 3).  h_ids, h_am: HOST [Q,16] as for tstar_owl_set_queries.  stage 0: h_out (HOST) [Q*16, 512] = the token +
+ * position embedding rows; stage 1: h_out [Q, 512] = the rows of the final LayerNorm at every sequence's first maximum id (what the
+ * text projection reads).  Refuses what tstar_owl_set_queries refuses, and any other stage.  Synchronises the stream. */
+int tstar_owl_debug_text(tstar_owl* h, const int32_t* h_ids, const int32_t* h_am, int Q, int stage, float* h_out, void* stream);
 /* cell_reduce without a handle: d_scores [B,np], d_labels [B,np] (0..31; rows with score <= thr are not read), d_boxes_xyxy [B,np,4]
  * -> d_cell_conf f64 [B,rows*cols], d_cell_mask u32 [B,rows*cols], d_n_kept [B] exactly as tstar_owl_score writes them.
  * h_weights: HOST float64 [n_sets,32] class weights; h_image_set: HOST [B] weight row of every image, or NULL (row 0).  W, H: the
@@ -527,6 +540,14 @@ int tstar_gemm_f32x3_pre(const float* d_A, const void* d_Wp, float* d_C, const f
  * 128x128 / 64x128 / 64x64 tiles, 3 = hybrid (rows [0, m_split) in 128x128 tiles, the rest 64x128), 4 = wide (128x256 + 64x128 tail),
  * 5 = wide with the weights streamed global -> VGPR.  TSTAR_ERR_ARG where tstar_gemm_* would refuse the same arguments. */
 int tstar_gemm_plan(int weights_mode, int M, int N, int ldc, int patch_np, int tile_cfg, int has_packed_w2, int* plan4);
+/* The patch-embedding form of the GEMM, which no other tstar_gemm_* entry can ask for (an added entry; tstar_abi_version() stays 3):
+ * d_X [B*(np+1), N] token row b*(np+1) + 1 + p = d_A [B*np, K] row (b*np + p) x d_W[N, K]^T + d_pos [np+1, N] row (1 + p); the
+ * class-token rows b*(np+1) are not written.  weights_mode: a TSTAR_WEIGHTS_* value; the bf16 / fragment-packed / three-plane
+ * weights are made from d_W as tstar_gemm_bf16w / tstar_gemm_bf16w2 / tstar_gemm_f32x3 make them.  tile_cfg as above.  Refuses
+ * (TSTAR_ERR_ARG, nothing launched) what tstar_gemm_plan(weights_mode, B*np, N, N, np, tile_cfg, two-term mode && N % 256 == 0)
+ * refuses, and K % 32 != 0.  Synchronises the stream. */
+int tstar_gemm_patch_embed(const float* d_A, const float* d_W, float* d_X, const float* d_pos, int B, int np, int N, int K,
+                           int weights_mode, int tile_cfg, void* stream);
 /* The launch plan tstar_frames_resize (op 0: n frames -> out_w x out_h = ow x oh) or tstar_frames_to_grid (op 1: n = grid_rows * grid_cols,
  * ow x oh = the 200 x 95 cell) makes (an added entry; tstar_abi_version() stays 3).  Pure: needs no GPU and launches nothing.
  * out_aligned4 / video_aligned4: the output / frame-store pointer is a multiple of 4; generic, nv12_lds, grid_px: the values of

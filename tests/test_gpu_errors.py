@@ -208,6 +208,81 @@ def test_owl_tail_diagnostic_entries_validate_their_arguments(env):
     assert torch.isfinite(o).all() and torch.isfinite(sco).all() and int(lab.max()) < sc.Q and torch.isfinite(f).all() and x[0].any() and not x[1].any()
 
 
+def test_owl_front_diagnostic_entries_validate_their_arguments(env):
+    """tstar_gemm_patch_embed / tstar_owl_debug_embed / tstar_owl_debug_text: one case per refusal, each message names its entry;
+    nothing is launched on a refusal and the entries work afterwards."""
+    from tstar_amd import weights as W
+    from tstar_amd.owl import OwlScorer
+    L, lib, h = env
+    sc = h.scorer
+    st = torch.cuda.current_stream().cuda_stream
+    B, npatch, N, K = 2, 3, 256, 64
+    A = torch.ones((B * npatch, K), device="cuda")
+    Wt = torch.ones((N, K), device="cuda")
+    pos = torch.ones((npatch + 1, N), device="cuda")
+    X = torch.full((B * (npatch + 1), N), 7.0, device="cuda")
+
+    def patch(a=A.data_ptr(), w=Wt.data_ptr(), x=X.data_ptr(), p=pos.data_ptr(), b=B, n=npatch, N=N, K=K, mode=0, cfg=-1):
+        return lib.tstar_gemm_patch_embed(a, w, x, p, b, n, N, K, mode, cfg, st)
+
+    for bad, msg in ((dict(a=None), b"null argument"), (dict(w=None), b"null argument"), (dict(x=None), b"null argument"), (dict(p=None), b"null argument"),
+                     (dict(b=0), b"B and np must be at least 1"), (dict(n=0), b"B and np must be at least 1"), (dict(b=1 << 30, n=3), b"do not fit an int"),
+                     (dict(mode=2), b"unknown weights_mode"), (dict(mode=5), b"unknown weights_mode"), (dict(K=48), b"multiple of 32"), (dict(K=0), b"multiple of 32"),
+                     (dict(N=192), b"N must be a multiple of 128"), (dict(N=0), b"multiple of 32"), (dict(cfg=7), b"tile_cfg must be -1..6"),
+                     (dict(cfg=-2), b"tile_cfg must be -1..6"), (dict(cfg=6), b"tile_cfg 6"), (dict(mode=4, cfg=6), b"tile_cfg 6"),
+                     (dict(mode=1, cfg=6), b"tile_cfg 6")):        # two-term mode, but no full 128-row panel in 6 rows
+        assert patch(**bad) == 1 and b"tstar_gemm_patch_embed" in lib.tstar_last_error() and msg in lib.tstar_last_error(), (bad, lib.tstar_last_error())
+    torch.cuda.synchronize()
+    assert (X == 7.0).all()                                  # nothing ran
+    for mode in (0, 1, 3, 4):
+        assert patch(mode=mode) == 0
+        torch.cuda.synchronize()
+        assert (X.view(B, npatch + 1, N)[:, 0] == 7.0).all() and (X.view(B, npatch + 1, N)[:, 1:] == K + 1.0).all()
+        X.fill_(7.0)
+
+    pk, ntok = 3 * 32 * 32, sc.num_patches + 1
+    P = torch.zeros((2 * sc.num_patches, pk), device="cuda")
+    x = torch.full((2 * ntok, 768), 7.0, device="cuda")
+    text_only = OwlScorer(None, W.pack_blob(W.synthetic_state_dict(0, "text"), W.text_spec()), max_batch=1)
+    vision_only = OwlScorer.synthetic(0, max_batch=1, with_text=False, input_size=(64, 96))
+    for args, code, msg in (((None, P.data_ptr(), 2, 0, x.data_ptr()), 1, b"null argument"), ((sc._h, None, 2, 0, x.data_ptr()), 1, b"null argument"),
+                            ((sc._h, P.data_ptr(), 2, 0, None), 1, b"null argument"), ((sc._h, P.data_ptr(), 0, 0, x.data_ptr()), 1, b"B must be in 1.."),
+                            ((sc._h, P.data_ptr(), 3, 0, x.data_ptr()), 1, b"B must be in 1.."), ((sc._h, P.data_ptr(), 2, 2, x.data_ptr()), 1, b"stage must be 0"),
+                            ((sc._h, P.data_ptr(), 2, -1, x.data_ptr()), 1, b"stage must be 0"),
+                            ((text_only._h, P.data_ptr(), 1, 0, x.data_ptr()), 3, b"without vision weights")):
+        assert lib.tstar_owl_debug_embed(*args, st) == code and b"tstar_owl_debug_embed" in lib.tstar_last_error() and msg in lib.tstar_last_error(), (args, lib.tstar_last_error())
+    torch.cuda.synchronize()
+    assert (x == 7.0).all()                                  # nothing ran
+    for stage in (0, 1):
+        assert lib.tstar_owl_debug_embed(sc._h, P.data_ptr(), 2, stage, x.data_ptr(), st) == 0
+        torch.cuda.synchronize()
+        assert torch.isfinite(x).all() and torch.equal(x[:ntok], x[ntok:])
+
+    ids = np.zeros((2, 16), np.int32); ids[:, 0] = 49406; ids[:, 1] = 49407
+    am = np.ones_like(ids)
+    bad_ids = ids.copy(); bad_ids[1, 5] = 49408
+    neg_ids = ids.copy(); neg_ids[0, 0] = -1
+    out = np.full((2 * 16, 512), np.float32(7.0))
+    hx = text_only._h
+    for args, code, msg in (((None, ids.ctypes.data, am.ctypes.data, 2, 0, out.ctypes.data), 1, b"null argument"),
+                            ((hx, None, am.ctypes.data, 2, 0, out.ctypes.data), 1, b"null argument"), ((hx, ids.ctypes.data, None, 2, 0, out.ctypes.data), 1, b"null argument"),
+                            ((hx, ids.ctypes.data, am.ctypes.data, 2, 0, None), 1, b"null argument"), ((hx, ids.ctypes.data, am.ctypes.data, 0, 0, out.ctypes.data), 1, b"Q must be in 1..32"),
+                            ((hx, ids.ctypes.data, am.ctypes.data, 33, 0, out.ctypes.data), 1, b"Q must be in 1..32"),
+                            ((hx, ids.ctypes.data, am.ctypes.data, 2, 2, out.ctypes.data), 1, b"stage must be 0"),
+                            ((hx, bad_ids.ctypes.data, am.ctypes.data, 2, 1, out.ctypes.data), 1, b"token id out of range"),
+                            ((hx, neg_ids.ctypes.data, am.ctypes.data, 2, 0, out.ctypes.data), 1, b"token id out of range"),
+                            ((vision_only._h, ids.ctypes.data, am.ctypes.data, 2, 0, out.ctypes.data), 3, b"without text weights")):
+        assert lib.tstar_owl_debug_text(*args, st) == code and b"tstar_owl_debug_text" in lib.tstar_last_error() and msg in lib.tstar_last_error(), (args, lib.tstar_last_error())
+    torch.cuda.synchronize()
+    assert (out == np.float32(7.0)).all()                    # nothing was copied out
+    assert lib.tstar_owl_debug_text(hx, ids.ctypes.data, am.ctypes.data, 2, 0, out.ctypes.data, st) == 0
+    assert np.isfinite(out).all() and np.array_equal(out[:16], out[16:])
+    assert lib.tstar_owl_debug_text(hx, ids.ctypes.data, am.ctypes.data, 2, 1, out.ctypes.data, st) == 0
+    assert np.array_equal(out[0], out[1]) and text_only.Qs == {}
+    text_only.close()
+    vision_only.close()
+
+
 def test_yolo_postprocess_argument_validation(env):
     """tstar_yolo_postprocess checks what tstar_yolo_detect checks, plus its own level arrays."""
     L, lib, _ = env

@@ -172,6 +172,30 @@ def test_every_ingest_kernel_form_is_gpu_tested():
                      (1, 0, 0, 1), (1, 0, 1, 1), (1, 1, 0, 1), (1, 1, 2, 1)}
 
 
+def test_every_patch_embed_form_is_gpu_tested():
+    """The (mode, B, np, N, tile_cfg) tests/test_gpu_owl_front.py hands to tstar_gemm_patch_embed reach every kernel launch_mode can
+    launch for a patch problem -- kinds 0..3 in all four weight modes, the wide tile in the two-term and f32x3 modes, the wide tile with
+    streamed weights in the two-term mode -- and every hybrid and wide form at least once with a full big panel AND a ragged tail."""
+    import owl_front_util as Fr
+    import test_gpu_owl_front as G
+    from tstar_amd import _lib
+    lib = _lib.load()
+    reached, ragged, refused = set(), set(), 0
+    for mode, B, np_, N, K, cfg in G.library_shapes():
+        M = B * np_
+        plan = Fr.gemm_plan(lib, mode, M, N, np_, cfg)
+        if plan is None:
+            refused += 1
+            continue
+        kind, m_split = plan
+        reached.add((mode, kind))
+        if kind >= Fr.HYBRID and 0 < m_split < M and (M - m_split) % 64 != 0:
+            ragged.add((mode, kind))
+    assert reached == Fr.REACHABLE == {(m, k) for m, ks in dict(f32=range(4), bf16_exact=range(4), f32x3=range(5), bf16=range(6)).items() for k in ks}
+    assert ragged == {(m, k) for m, k in Fr.REACHABLE if k >= Fr.HYBRID}
+    assert refused == 1                                      # tile_cfg 6 at N = 128 (S3): the entry must refuse it too
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():

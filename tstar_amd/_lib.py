@@ -50,6 +50,8 @@ SIGNATURES = {
     "tstar_owl_debug_preprocess": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "tstar_owl_debug_heads": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tstar_owl_debug_merge": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "tstar_owl_debug_embed": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "tstar_owl_debug_text": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "tstar_cell_reduce": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp]),
     "tstar_owl_embed_image_queries": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tstar_image_query_select": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -104,6 +106,7 @@ SIGNATURES = {
     "tstar_pack_f32x3": (_i, [_vp, _vp, _i, _i, _vp]),
     "tstar_gemm_f32x3_pre": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "tstar_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "tstar_gemm_patch_embed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "tstar_ingest_plan": (_i, [_i] * 12 + [C.POINTER(_i)]),
     "tstar_layernorm_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "tstar_draw_boxes": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),

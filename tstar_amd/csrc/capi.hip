@@ -214,6 +214,16 @@ static GemmArgs mk_gemm(const tstar_owl* h, const float* A, const float* W, floa
     return g;
 }
 
+// The text tower's GEMMs.  The query embeddings are computed once per query set and enter every score, so the two-term mode runs
+// them with the exact three-term activation split on the same bf16 weight plane (what TSTAR_WEIGHTS_BF16_EXACT runs everywhere):
+// float32-class embeddings of the rounded checkpoint.  The other modes are unchanged.
+static GemmArgs mk_text_gemm(const tstar_owl* h, const float* A, const float* W, float* C, const float* bias, const float* res,
+                             int M, int N, int K, int lda, int ldc, int act) {
+    GemmArgs g = mk_gemm(h, A, W, C, bias, res, M, N, K, lda, ldc, act);
+    if (g.a_terms == 2) { g.a_terms = 0; g.Wq = nullptr; }
+    return g;
+}
+
 // TSTAR_X3_ATTN_F32=1: the f32x3 mode with the exact-f32 MFMA attention of rounds 1-4 (same-session A/Bs)
 static bool x3_attention_f32() {
     static const bool v = getenv("TSTAR_X3_ATTN_F32") != nullptr;
@@ -224,19 +234,21 @@ static bool x3_attention_f32() {
 static int run_encoder(tstar_owl* h, tstar_owl::Lane& L, const LayerW* layers, int nlayers, int B, int T, int D, int FF, int heads,
                        int mode, const uint8_t* key_mask, hipStream_t s) {
     const int M = B * T;
+    // mode 1 is the text tower, whose mk_text_gemm keeps every activation bit; mode 0 the vision tower
+    const auto mk = mode == 1 ? mk_text_gemm : mk_gemm;
     for (int l = 0; l < nlayers; ++l) {
         const LayerW& w = layers[l];
         RC(layernorm_f32(L.x, L.xn, w.ln1_w, w.ln1_b, M, D, s));
-        RC(gemm_f32(mk_gemm(h, L.xn, w.qkv_w, L.qkv, w.qkv_b, nullptr, M, 3 * D, D, D, 3 * D, ACT_NONE), s));
+        RC(gemm_f32(mk(h, L.xn, w.qkv_w, L.qkv, w.qkv_b, nullptr, M, 3 * D, D, D, 3 * D, ACT_NONE), s));
         // full attention in the bf16-WEIGHT modes runs on the bf16 matrix pipe too (operands as two bf16 terms); in the f32x3
         // mode with all operand bits (three exact terms, six products: its claim is an error no larger than the f32 path's)
         if (mode == 0 && (h->weights_mode == TSTAR_WEIGHTS_BF16 || h->weights_mode == TSTAR_WEIGHTS_BF16_EXACT)) RC(attention_split(L.qkv, L.att, B, T, heads, s));
         else if (mode == 0 && h->weights_mode == TSTAR_WEIGHTS_F32X3 && !x3_attention_f32()) RC(attention_x3(L.qkv, L.att, B, T, heads, s));
         else RC(attention_f32(L.qkv, L.att, B, T, heads, mode, key_mask, s));
-        RC(gemm_f32(mk_gemm(h, L.att, w.out_w, L.x, w.out_b, L.x, M, D, D, D, D, ACT_NONE), s));
+        RC(gemm_f32(mk(h, L.att, w.out_w, L.x, w.out_b, L.x, M, D, D, D, D, ACT_NONE), s));
         RC(layernorm_f32(L.x, L.xn, w.ln2_w, w.ln2_b, M, D, s));
-        RC(gemm_f32(mk_gemm(h, L.xn, w.fc1_w, L.hid, w.fc1_b, nullptr, M, FF, D, D, FF, ACT_QGELU), s));
-        RC(gemm_f32(mk_gemm(h, L.hid, w.fc2_w, L.x, w.fc2_b, L.x, M, D, FF, FF, D, ACT_NONE), s));
+        RC(gemm_f32(mk(h, L.xn, w.fc1_w, L.hid, w.fc1_b, nullptr, M, FF, D, D, FF, ACT_QGELU), s));
+        RC(gemm_f32(mk(h, L.hid, w.fc2_w, L.x, w.fc2_b, L.x, M, D, FF, FF, D, ACT_NONE), s));
     }
     return TSTAR_OK;
 }
@@ -584,6 +596,43 @@ static int finish_queries(tstar_owl* h, int set, const uint8_t* h_mask, const do
     return TSTAR_OK;
 }
 
+// Host staging of one text forward; lives until the stream has been synchronised (the copies below are asynchronous)
+struct TextStage {
+    std::vector<int> eos;
+    std::vector<uint8_t> km, qm;
+};
+
+// The text tower on one query set in lane 0 (the handle's own workspace): token + position embedding -> L.x [Q*16, 512]; with
+// pooled != 0 also the 12 layers, the final LayerNorm and the row of every sequence's first maximum id -> L.att [Q, 512].
+static int text_forward(tstar_owl* h, const char* fn, const int32_t* h_ids, const int32_t* h_am, int Q, int pooled, TextStage& st, hipStream_t s) {
+    auto& L = h->lane[0];
+    st.eos.resize(Q); st.km.resize(Q * T_LEN); st.qm.resize(Q);
+    for (int q = 0; q < Q; ++q) {
+        int best = 0;
+        for (int t = 0; t < T_LEN; ++t) {
+            const int id = h_ids[q * T_LEN + t];
+            TSTAR_REQUIRE(id >= 0 && id < T_VOCAB, std::string(fn) + ": token id out of range");
+            if (id > h_ids[q * T_LEN + best]) best = t;        // argmax, first occurrence
+            st.km[q * T_LEN + t] = h_am[q * T_LEN + t] != 0;
+        }
+        st.eos[q] = best;
+        st.qm[q] = h_ids[q * T_LEN] > 0;                       // modeling_owlvit.py:1447
+    }
+    TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_ids, h_ids, Q * T_LEN * sizeof(int), hipMemcpyHostToDevice, s));
+    TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_eos, st.eos.data(), Q * sizeof(int), hipMemcpyHostToDevice, s));
+    TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_kmask, st.km.data(), Q * T_LEN, hipMemcpyHostToDevice, s));
+    const int M = Q * T_LEN;
+    hipLaunchKernelGGL(embed_tokens_kernel, dim3(M), dim3(128), 0, s, h->d_ids, h->tw.tok_emb, h->tw.tpos_emb, L.x,
+                       T_LEN, T_D);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    if (!pooled) return TSTAR_OK;
+    RC(run_encoder(h, L, h->tw.layers, T_LAYERS, Q, T_LEN, T_D, T_FF, T_HEADS, 1, h->d_kmask, s));
+    RC(layernorm_f32(L.x, L.xn, h->tw.final_ln_w, h->tw.final_ln_b, M, T_D, s));
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(Q), dim3(128), 0, s, L.xn, h->d_eos, L.att, T_LEN, T_D);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    return TSTAR_OK;
+}
+
 int tstar_owl_set_queries(tstar_owl* h, int query_set, const int32_t* h_ids, const int32_t* h_am, const double* h_w, int Q,
                           void* stream) {
     TSTAR_REQUIRE(h && h_ids && h_am && h_w, "tstar_owl_set_queries: null argument");
@@ -592,35 +641,28 @@ int tstar_owl_set_queries(tstar_owl* h, int query_set, const int32_t* h_ids, con
     if (!h->has_text) { set_error("tstar_owl_set_queries: handle was created without text weights"); return TSTAR_ERR_STATE; }
     hipStream_t s = (hipStream_t)stream;
     auto& L = h->lane[0];                                      // the text tower runs in the handle's own workspace
-    std::vector<int> eos(Q);
-    std::vector<uint8_t> km(Q * T_LEN), qm(Q);
-    for (int q = 0; q < Q; ++q) {
-        int best = 0;
-        for (int t = 0; t < T_LEN; ++t) {
-            const int id = h_ids[q * T_LEN + t];
-            TSTAR_REQUIRE(id >= 0 && id < T_VOCAB, "tstar_owl_set_queries: token id out of range");
-            if (id > h_ids[q * T_LEN + best]) best = t;        // argmax, first occurrence
-            km[q * T_LEN + t] = h_am[q * T_LEN + t] != 0;
-        }
-        eos[q] = best;
-        qm[q] = h_ids[q * T_LEN] > 0;                          // modeling_owlvit.py:1447
-    }
-    TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_ids, h_ids, Q * T_LEN * sizeof(int), hipMemcpyHostToDevice, s));
-    TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_eos, eos.data(), Q * sizeof(int), hipMemcpyHostToDevice, s));
-    TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_kmask, km.data(), Q * T_LEN, hipMemcpyHostToDevice, s));
-    const int M = Q * T_LEN;
-    hipLaunchKernelGGL(embed_tokens_kernel, dim3(M), dim3(128), 0, s, h->d_ids, h->tw.tok_emb, h->tw.tpos_emb, L.x,
-                       T_LEN, T_D);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    RC(run_encoder(h, L, h->tw.layers, T_LAYERS, Q, T_LEN, T_D, T_FF, T_HEADS, 1, h->d_kmask, s));
-    RC(layernorm_f32(L.x, L.xn, h->tw.final_ln_w, h->tw.final_ln_b, M, T_D, s));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(Q), dim3(128), 0, s, L.xn, h->d_eos, L.att, T_LEN, T_D);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    RC(gemm_f32(mk_gemm(h, L.att, h->tw.text_proj, L.hid, nullptr, nullptr, Q, PROJ, T_D, T_D, PROJ, ACT_NONE), s));
+    TextStage st;
+    RC(text_forward(h, "tstar_owl_set_queries", h_ids, h_am, Q, 1, st, s));
+    RC(gemm_f32(mk_text_gemm(h, L.att, h->tw.text_proj, L.hid, nullptr, nullptr, Q, PROJ, T_D, T_D, PROJ, ACT_NONE), s));
     hipLaunchKernelGGL(l2norm_rows_kernel, dim3(Q), dim3(64), 0, s, L.hid,
                        h->q_raw + (size_t)query_set * TSTAR_OWL_MAX_QUERIES * PROJ, 0.0f);
     TSTAR_HIP_CHECK(hipGetLastError());
-    return finish_queries(h, query_set, qm.data(), h_w, Q, s);
+    return finish_queries(h, query_set, st.qm.data(), h_w, Q, s);
+}
+
+int tstar_owl_debug_text(tstar_owl* h, const int32_t* h_ids, const int32_t* h_am, int Q, int stage, float* h_out, void* stream) {
+    TSTAR_REQUIRE(h && h_ids && h_am && h_out, "tstar_owl_debug_text: null argument");
+    TSTAR_REQUIRE(Q >= 1 && Q <= TSTAR_OWL_MAX_QUERIES, "tstar_owl_debug_text: Q must be in 1..32");
+    TSTAR_REQUIRE(stage == 0 || stage == 1, "tstar_owl_debug_text: stage must be 0 (embedding rows) or 1 (pooled rows)");
+    if (!h->has_text) { set_error("tstar_owl_debug_text: handle was created without text weights"); return TSTAR_ERR_STATE; }
+    hipStream_t s = (hipStream_t)stream;
+    auto& L = h->lane[0];
+    TextStage st;
+    RC(text_forward(h, "tstar_owl_debug_text", h_ids, h_am, Q, stage, st, s));
+    const size_t n = (size_t)Q * (stage == 0 ? T_LEN : 1) * T_D;
+    TSTAR_HIP_CHECK(hipMemcpyAsync(h_out, stage == 0 ? L.x : L.att, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    TSTAR_HIP_CHECK(hipStreamSynchronize(s));
+    return TSTAR_OK;
 }
 
 int tstar_owl_set_queries_many(tstar_owl* h, int n_sets, const int32_t* h_sets, const int32_t* h_Q, const int32_t* h_ids, const int32_t* h_am,
@@ -678,7 +720,7 @@ int tstar_owl_set_queries_many(tstar_owl* h, int n_sets, const int32_t* h_sets, 
         RC(layernorm_f32(L.x, L.xn, h->tw.final_ln_w, h->tw.final_ln_b, M, T_D, s));
         hipLaunchKernelGGL(gather_rows_kernel, dim3(nseq), dim3(128), 0, s, L.xn, h->d_eos, L.att, T_LEN, T_D);
         TSTAR_HIP_CHECK(hipGetLastError());
-        RC(gemm_f32(mk_gemm(h, L.att, h->tw.text_proj, L.hid, nullptr, nullptr, nseq, PROJ, T_D, T_D, PROJ, ACT_NONE), s));
+        RC(gemm_f32(mk_text_gemm(h, L.att, h->tw.text_proj, L.hid, nullptr, nullptr, nseq, PROJ, T_D, T_D, PROJ, ACT_NONE), s));
         int off = 0;
         for (int i = i0; i < i1; ++i) {
             const int set = h_sets[i], Q = h_Q[i];
@@ -858,6 +900,24 @@ int tstar_owl_debug_merge(tstar_owl* h, float* d_x, int B, int write_cls, float*
     hipStream_t s = (hipStream_t)stream;
     if (write_cls) RC(write_cls_rows(d_x, h->vw.class_emb, h->vw.pos_emb, B, h->geom.ntok, V_D, s));
     return merge_cls_ln(d_x, d_feats, h->vw.post_ln_w, h->vw.post_ln_b, h->vw.det_ln_w, h->vw.det_ln_b, B, h->geom.ntok, V_D, s);
+}
+
+int tstar_owl_debug_embed(tstar_owl* h, const float* d_patches, int B, int stage, float* d_x, void* stream) {
+    TSTAR_REQUIRE(h && d_patches && d_x, "tstar_owl_debug_embed: null argument");
+    TSTAR_REQUIRE(stage == 0 || stage == 1, "tstar_owl_debug_embed: stage must be 0 (patch GEMM + class rows) or 1 (+ pre-LayerNorm)");
+    if (!h->has_vision) { set_error("tstar_owl_debug_embed: handle was created without vision weights (text-only)"); return TSTAR_ERR_STATE; }
+    auto& L = h->lane[0];
+    TSTAR_REQUIRE(B >= 1 && B <= L.cap, "tstar_owl_debug_embed: B must be in 1..the images of one forward chunk (min(max_batch, chunk limit))");
+    hipStream_t s = (hipStream_t)stream;
+    const OwlGeom& G = h->geom;
+    const int M = B * G.ntok;
+    GemmArgs pg = mk_gemm(h, d_patches, h->vw.patch_w, L.x, nullptr, nullptr, B * G.np, V_D, G.patch_k, G.patch_k, V_D, ACT_NONE);
+    pg.pos = h->vw.pos_emb; pg.patch_np = G.np;
+    RC(gemm_f32(pg, s));
+    RC(write_cls_rows(L.x, h->vw.class_emb, h->vw.pos_emb, B, G.ntok, V_D, s));
+    if (stage == 1) RC(layernorm_f32(L.x, L.x, h->vw.pre_ln_w, h->vw.pre_ln_b, M, V_D, s));
+    TSTAR_HIP_CHECK(hipMemcpyAsync(d_x, L.x, (size_t)M * V_D * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return TSTAR_OK;
 }
 
 int tstar_cell_reduce(const float* d_scores, const int32_t* d_labels, const float* d_boxes_xyxy, const double* h_weights, int n_sets,
@@ -1137,14 +1197,63 @@ int tstar_gemm_f32x3_pre(const float* d_A, const void* d_Wp, float* d_C, const f
     return gemm_f32(g, (hipStream_t)stream);
 }
 
+static int gemm_wmode_of(int weights_mode) {
+    return weights_mode == TSTAR_WEIGHTS_F32 ? GEMM_W_F32 : weights_mode == TSTAR_WEIGHTS_BF16 ? GEMM_W_BF16_2T :
+           weights_mode == TSTAR_WEIGHTS_BF16_EXACT ? GEMM_W_BF16_EXACT : weights_mode == TSTAR_WEIGHTS_F32X3 ? GEMM_W_F32X3 : -1;
+}
+
 int tstar_gemm_plan(int weights_mode, int M, int N, int ldc, int patch_np, int tile_cfg, int has_packed_w2, int* plan4) {
     TSTAR_REQUIRE(plan4, "tstar_gemm_plan: null argument");
-    const int wmode = weights_mode == TSTAR_WEIGHTS_F32 ? GEMM_W_F32 : weights_mode == TSTAR_WEIGHTS_BF16 ? GEMM_W_BF16_2T :
-                      weights_mode == TSTAR_WEIGHTS_BF16_EXACT ? GEMM_W_BF16_EXACT : weights_mode == TSTAR_WEIGHTS_F32X3 ? GEMM_W_F32X3 : -1;
-    const GemmPlan p = plan_gemm(wmode, M, N, ldc, patch_np, tile_cfg, has_packed_w2 != 0);
+    const GemmPlan p = plan_gemm(gemm_wmode_of(weights_mode), M, N, ldc, patch_np, tile_cfg, has_packed_w2 != 0);
     if (p.error) { set_error(p.error); return TSTAR_ERR_ARG; }
     plan4[0] = p.kind; plan4[1] = p.m_split; plan4[2] = p.blocks; plan4[3] = p.lds_bytes;
     return TSTAR_OK;
+}
+
+// The patch-embedding launch of owl_forward_heads (pos != nullptr, patch_np = np: the PATCH epilogue) on caller-supplied operands, with
+// the weight planes of `weights_mode` made as the tstar_gemm_* diagnostics make them.  Every refusal comes before the first allocation.
+int tstar_gemm_patch_embed(const float* d_A, const float* d_W, float* d_X, const float* d_pos, int B, int np, int N, int K,
+                           int weights_mode, int tile_cfg, void* stream) {
+    TSTAR_REQUIRE(d_A && d_W && d_X && d_pos, "tstar_gemm_patch_embed: null argument");
+    TSTAR_REQUIRE(B >= 1 && np >= 1, "tstar_gemm_patch_embed: B and np must be at least 1");
+    TSTAR_REQUIRE((long long)B * (np + 1ll) < (1ll << 31), "tstar_gemm_patch_embed: B * (np + 1) token rows do not fit an int");
+    const int wmode = gemm_wmode_of(weights_mode);
+    TSTAR_REQUIRE(wmode >= 0, "tstar_gemm_patch_embed: unknown weights_mode (a TSTAR_WEIGHTS_* value)");
+    TSTAR_REQUIRE(N > 0 && K > 0 && K % 32 == 0, "tstar_gemm_patch_embed: K must be a positive multiple of 32 (gemm_f32)");
+    const int M = B * np;
+    const bool two_term = weights_mode == TSTAR_WEIGHTS_BF16;
+    const bool has_wq = two_term && N % 256 == 0;             // the fragment-packed plane, where gemm_converted makes one
+    const GemmPlan p = plan_gemm(wmode, M, N, N, np, tile_cfg, has_wq);
+    if (p.error) { set_error(std::string("tstar_gemm_patch_embed: ") + p.error); return TSTAR_ERR_ARG; }
+    hipStream_t s = (hipStream_t)stream;
+    __bf16* wb = nullptr;
+    void *wq = nullptr, *wp = nullptr;
+    int rc = TSTAR_OK;
+    if (two_term || weights_mode == TSTAR_WEIGHTS_BF16_EXACT) {
+        TSTAR_HIP_CHECK(hipMalloc(&wb, (size_t)N * K * sizeof(__bf16)));
+        rc = convert_f32_to_bf16(d_W, wb, nullptr, (size_t)N * K, s);
+        if (!rc && has_wq) {
+            TSTAR_HIP_CHECK(hipMalloc(&wq, (size_t)N * K * sizeof(__bf16)));
+            rc = pack_weights_w2(wb, wq, N, K, s);
+        }
+    } else if (weights_mode == TSTAR_WEIGHTS_F32X3) {
+        TSTAR_HIP_CHECK(hipMalloc(&wp, (size_t)N * K * 6));
+        rc = pack_weights_x3(d_W, wp, N, K, s);
+    }
+    if (!rc) {
+        GemmArgs g = mk_gemm(nullptr, d_A, d_W, d_X, nullptr, nullptr, M, N, K, K, N, ACT_NONE);
+        g.Wb = wb; g.Wq = wq; g.Wp = wp;
+        g.a_terms = two_term ? 2 : wb ? 3 : 0;
+        g.pos = d_pos; g.patch_np = np;
+        g.tile_cfg = tile_cfg;
+        rc = gemm_f32(g, s);
+    }
+    hipError_t e = hipStreamSynchronize(s);
+    if (wb) (void)hipFree(wb);
+    if (wq) (void)hipFree(wq);
+    if (wp) (void)hipFree(wp);
+    if (!rc && e != hipSuccess) { set_error(std::string("tstar_gemm_patch_embed: ") + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
+    return rc;
 }
 
 int tstar_ingest_plan(int op, int nv12, int H, int W, int n, int ow, int oh, int out_aligned4, int video_aligned4, int generic, int nv12_lds,
