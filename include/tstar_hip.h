@@ -201,6 +201,18 @@ int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, in
                              double* d_cell_conf, uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits,
                              float* d_boxes_cxcywh, float* d_objectness, void* stream);
 
+/* tstar_owl_score_lane_obj WITHOUT the box outputs, for images scored as a 1 x 1 grid (an added entry; tstar_abi_version() stays 3).
+ * With one cell the boxes cannot reach cell_conf / cell_mask / n_kept: the cell of a detection is its clamped box centre's, which is
+ * cell 0, and everything else comes from the class head.  That is the searcher's verification call: the reference's
+ * verify_and_remove_target (TStar/interface_searcher.py:382-420) reads the detections' confidence and class names only.  The entry
+ * skips the box head's two 768 x 768 GELU layers, the box tail of the row kernel and both box stores; the launches of the class head
+ * are the same, so d_scores, d_labels, d_cell_conf, d_cell_mask, d_n_kept, d_logits and d_objectness hold the bits of the full entry
+ * in every weights mode.  Arguments as tstar_owl_score_lane_obj minus d_boxes_xyxy and d_boxes_cxcywh; TSTAR_ERR_ARG (nothing
+ * launched) when grid_rows * grid_cols != 1: a larger grid needs the box centres. */
+int tstar_owl_score_cells(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
+                          const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, double* d_cell_conf,
+                          uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_objectness, void* stream);
+
 /* OWLv2 pre-processing policy (added entries; pure: no GPU, nothing launched).  plan10 = { form, tile_h, tile_w, win_h, win_w, LDS bytes
  * per workgroup, grid.x, grid.y, radius_y, radius_x } for a u8 image H x W resized to out_h x out_w (multiples of 16): form 0 = direct
  * (no axis shrinks: four taps per output pixel straight from the source), 1 = filtered (a workgroup owns tile_h x tile_w output pixels and
@@ -567,6 +579,14 @@ int tstar_attention_split(const float* d_qkv, float* d_out, int B, int T, int he
  * products per MFMA step, f32 accumulation (what TSTAR_WEIGHTS_F32X3 uses for the vision tower; replaces the fp32
  * softmax(Q K^T / 8) V of HF modeling_owlvit.py:377-402 behind TStar/interface_heuristic.py:237-239) */
 int tstar_attention_x3(const float* d_qkv, float* d_out, int B, int T, int heads, void* stream);
+/* The same with the block order given (diagnostics / A-B runs; added entries): order 1 = the query tiles of one (image, head), which
+ * stage the same K / V rows, run back to back on ONE XCD (what tstar_attention_x3 does unless TSTAR_AX3_XCD_OFF is set in the
+ * environment), 0 = linear block ids, query tile fastest.  Every block computes the same tile either way: the output bits are equal.
+ * tstar_xcd_group_block (pure, no GPU): the logical block (group * gsize + member) that hardware block bid of the order-1 grid of
+ * tstar_xcd_groups_grid(ngroups, gsize) blocks computes, -1 for a padding block that exits at once, -2 for a bad argument. */
+int tstar_attention_x3_order(const float* d_qkv, float* d_out, int B, int T, int heads, int order, void* stream);
+int tstar_xcd_group_block(int bid, int ngroups, int gsize);
+int tstar_xcd_groups_grid(int ngroups, int gsize);
 
 /* Per-kernel timing with HIP events recorded on the launch stream, for bench.py's roofline leg.
  * category 0 = gemm_f32_kernel, 1 = attention_f32_kernel, 2 = conv_valu_kernel (YOLO-World backend).  enable(n > 0) resets the counters and times ONE of every

@@ -33,6 +33,7 @@ SIGNATURES = {
     "tstar_owl_create_family": (_i, [C.POINTER(_vp), _i, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _i, _i]),
     "tstar_owl_vision_blob_floats_family": (_sz, [_i, _i, _i, _i]),
     "tstar_owl_score_lane_obj": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tstar_owl_score_cells": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tstar_owlv2_set_axis_weights": (_i, [_vp, _i, _i, _vp, _i]),
     "tstar_owlv2_preprocess_plan": (_i, [_i, _i, _i, _i, C.POINTER(_i)]),
     "tstar_owlv2_axis_window": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
@@ -113,6 +114,9 @@ SIGNATURES = {
     "tstar_draw_boxes_np": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "tstar_attention_split": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "tstar_attention_x3": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "tstar_attention_x3_order": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "tstar_xcd_group_block": (_i, [_i, _i, _i]),
+    "tstar_xcd_groups_grid": (_i, [_i, _i]),
     "tstar_attention_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "tstar_prof_enable": (_i, [_i]),
     "tstar_prof_read": (_i, [_i, _vp, _vp, _vp]),

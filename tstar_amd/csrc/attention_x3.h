@@ -23,6 +23,11 @@
 //    iterations (soft_piece 0): its rows past T - 1 are staged as ZEROS (the buffer resource ends at the image's last row, so
 //    nothing behind the last image of the workspace is read), their scores are set to -inf and their probabilities are
 //    exp2(-inf) = 0 exactly.  Same pipeline, one barrier per tile.
+//  * block order: the ceil(T / 128) query tiles of one (image, head) stage the same K / V rows.  With linear block ids (query tile
+//    fastest) the dispatcher's round-robin puts them on as many different XCDs, so every L2 fetches those rows for itself;
+//    xcd_remap_groups (common.h) gives them consecutive slots of ONE XCD instead (grid padded to a multiple of 8 groups, the
+//    padding blocks exit at once).  Only the block -> tile assignment changes: same bits (tests/test_gpu_attention_x3_order.py).
+//    TSTAR_AX3_XCD_OFF restores the linear order; figures: profiles/unread_work_measure.md.
 //  * measured (B = 256, T = 577, 12 heads; tools/lab/attn_lab.hip, profiles/r05_attention_x3_lab.log, r05_attention_x3_counters.md):
 //    154 TFLOP/s algorithmic (0.92 PFLOP/s executed) against 120-125 for attention_f32_kernel, 147 vs 103 inside the bench; error
 //    against float64 below the f32 kernel's (tests/test_gpu_kernels.py::test_attention_x3).  Matrix pipe busy 0.51: the kernel is
@@ -31,6 +36,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <utility>
+#include "common.h"
 
 namespace tstar {
 namespace ax3 {
@@ -95,13 +101,16 @@ __device__ __forceinline__ f32x16 mfma(const bf16x8 a, const u32x4 b, const f32x
 // query block); key tiles are then the global tiles that overlap the image's rows, masked at both ends.
 template <bool PLANES>
 __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const float* __restrict__ qkv, const char* __restrict__ planes,
-                                                              float* __restrict__ out, int T, int heads, int qtiles) {
+                                                              float* __restrict__ out, int T, int heads, int qtiles, int xcd_groups) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const kbuf = smem;
     char* const vbuf = smem + NKB * KBUF;
 
     const int D = heads * HD, D3 = 3 * D;
-    int bid = blockIdx.x;
+    // xcd_groups = B * heads: the grid is xcd_groups_grid() blocks and the query tiles of one (image, head), which stage the same K / V
+    // rows, run back to back on one XCD (common.h); 0: the linear order, query tile fastest over B * heads * qtiles blocks
+    int bid = xcd_groups ? xcd_remap_groups(blockIdx.x, xcd_groups, qtiles) : (int)blockIdx.x;
+    if (bid < 0) return;
     const int qt = bid % qtiles; bid /= qtiles;
     const int head = bid % heads;
     const int b = bid / heads;
@@ -547,8 +556,11 @@ __global__ __launch_bounds__(256) void kv_planes_kernel(const float* __restrict_
 // (the library's form).  The plane-tile + LDS-DMA form is compiled for the lab only (TSTAR_ATTN_X3_LAB): measured at the bench shape
 // it is 7 % faster (159.7 vs 148.8 TFLOP/s, profiles/r05_attention_x3_planes_dma_lab.log) -- about 1 % of a step, less than what
 // writing the tiles from the qkv GEMM's epilogue would cost -- so the library does not use it.
-inline int attention_x3_launch(const float* qkv, float* out, int B, int T, int heads, hipStream_t s, const char* planes = nullptr) {
+inline int attention_x3_launch(const float* qkv, float* out, int B, int T, int heads, hipStream_t s, const char* planes = nullptr,
+                               bool xcd_order = false) {
     const int qtiles = (T + 127) / 128;
+    const int xcd_groups = xcd_order ? B * heads : 0;
+    const int nblocks = xcd_order ? xcd_groups_grid(B * heads, qtiles) : B * heads * qtiles;
 #ifdef TSTAR_ATTN_X3_LAB
     // the lab harness is one device, one host thread: a process-wide flag is enough there.  The LIBRARY raises the dynamic-LDS
     // limit through ensure_dyn_lds (keyed on kernel AND device, mutex-protected: the attribute applies to the current device only)
@@ -560,7 +572,7 @@ inline int attention_x3_launch(const float* qkv, float* out, int B, int T, int h
             if (e != hipSuccess) return (int)e;
             attr[1] = true;
         }
-        hipLaunchKernelGGL(ax3::attention_x3_kernel<true>, dim3(B * heads * qtiles), dim3(256), ax3::LDS_BYTES, s, qkv, planes, out, T, heads, qtiles);
+        hipLaunchKernelGGL(ax3::attention_x3_kernel<true>, dim3(nblocks), dim3(256), ax3::LDS_BYTES, s, qkv, planes, out, T, heads, qtiles, xcd_groups);
         return (int)hipGetLastError();
     }
     if (!attr[0]) {
@@ -570,7 +582,7 @@ inline int attention_x3_launch(const float* qkv, float* out, int B, int T, int h
     }
 #endif
     if (planes) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(ax3::attention_x3_kernel<false>, dim3(B * heads * qtiles), dim3(256), ax3::LDS_BYTES, s, qkv, planes, out, T, heads, qtiles);
+    hipLaunchKernelGGL(ax3::attention_x3_kernel<false>, dim3(nblocks), dim3(256), ax3::LDS_BYTES, s, qkv, planes, out, T, heads, qtiles, xcd_groups);
     return (int)hipGetLastError();
 }
 

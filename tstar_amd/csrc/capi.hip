@@ -371,15 +371,17 @@ static DetectRowsArgs detect_args(const tstar_owl* h) {
 }
 
 // One forward chunk up to the head tensors, shared by scoring and the image-query embedding: pre-processing of either family,
-// patch embedding, the encoder in the handle's weight mode, merge_cls_ln, the class head's dense0 and the box head's two GELU
-// layers.  The tensors live in the lane's workspaces (L.x is free again on return).
+// patch embedding, the encoder in the handle's weight mode, merge_cls_ln, the class head's dense0 and -- with want_boxes -- the box
+// head's two GELU layers (without: bh1 / bh2 are only the free buffers the objectness head may use).  The tensors live in the
+// lane's workspaces (L.x is free again on return).
 struct OwlHeadTensors {
     float* feats;    // [Bc * np, 768]  L.xn
     float* cls;      // [Bc * np, 512]  L.att
     float* bh1;      // [Bc * np, 768]  L.qkv: the box head's first layer (free once bh2 is written)
     float* bh2;      // [Bc * np, 768]  L.hid
 };
-static int owl_forward_heads(tstar_owl* h, tstar_owl::Lane& L, const uint8_t* d_images, int Bc, int H, int W, OwlHeadTensors* t, hipStream_t s) {
+static int owl_forward_heads(tstar_owl* h, tstar_owl::Lane& L, const uint8_t* d_images, int Bc, int H, int W, bool want_boxes, OwlHeadTensors* t,
+                             hipStream_t s) {
     const OwlGeom& G = h->geom;
     const int NP = G.np, NTOK = G.ntok, PK = G.patch_k;
     const int M = Bc * NTOK, MP = Bc * NP;
@@ -393,6 +395,7 @@ static int owl_forward_heads(tstar_owl* h, tstar_owl::Lane& L, const uint8_t* d_
     t->feats = L.xn; t->cls = L.att; t->bh1 = L.qkv; t->bh2 = L.hid;
     RC(merge_cls_ln(L.x, t->feats, h->vw.post_ln_w, h->vw.post_ln_b, h->vw.det_ln_w, h->vw.det_ln_b, Bc, NTOK, V_D, s));
     RC(gemm_f32(mk_gemm(h, t->feats, h->vw.cls_w, t->cls, h->vw.cls_b, nullptr, MP, PROJ, V_D, V_D, PROJ, ACT_NONE), s));
+    if (!want_boxes) return TSTAR_OK;
     RC(gemm_f32(mk_gemm(h, t->feats, h->vw.box0_w, t->bh1, h->vw.box0_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
     RC(gemm_f32(mk_gemm(h, t->bh1, h->vw.box1_w, t->bh2, h->vw.box1_b, nullptr, MP, V_D, V_D, V_D, V_D, ACT_GELU), s));
     return TSTAR_OK;
@@ -776,25 +779,11 @@ int tstar_owl_get_query_embeds(tstar_owl* h, int query_set, float* h_out, int Q,
     return TSTAR_OK;
 }
 
-int tstar_owl_score(tstar_owl* h, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
-                    const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
-                    uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_boxes_cxcywh, void* stream) {
-    return tstar_owl_score_lane(h, 0, d_images, B, H, W, grid_rows, grid_cols, h_image_query_set, d_scores, d_labels, d_boxes_xyxy, d_cell_conf,
-                                d_cell_mask, d_n_kept, d_logits, d_boxes_cxcywh, stream);
-}
-
-int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
-                         const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
-                         uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_boxes_cxcywh, void* stream) {
-    return tstar_owl_score_lane_obj(h, lane, d_images, B, H, W, grid_rows, grid_cols, h_image_query_set, d_scores, d_labels, d_boxes_xyxy, d_cell_conf,
-                                    d_cell_mask, d_n_kept, d_logits, d_boxes_cxcywh, nullptr, stream);
-}
-
-int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
-                             const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
-                             uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_boxes_cxcywh, float* d_objectness, void* stream) {
-    TSTAR_REQUIRE(h && d_images && d_scores && d_labels && d_boxes_xyxy && d_cell_conf && d_cell_mask,
-                  "tstar_owl_score: null argument");
+// the body of the score entries; d_boxes_xyxy == nullptr (tstar_owl_score_cells, 1 x 1 grid): no box head, no box outputs
+static int owl_score(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
+                     const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
+                     uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_boxes_cxcywh, float* d_objectness, void* stream) {
+    const bool want_boxes = d_boxes_xyxy != nullptr;
     TSTAR_REQUIRE(lane >= 0 && lane < TSTAR_OWL_LANES, "tstar_owl_score_lane: lane must be 0 or 1");
     TSTAR_REQUIRE(B >= 1 && H >= 1 && W >= 1, "tstar_owl_score: empty batch or image");
     TSTAR_REQUIRE(grid_rows >= 1 && grid_cols >= 1, "tstar_owl_score: grid must be at least 1x1");
@@ -833,13 +822,13 @@ int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, in
         const int Bc = (B - b0) < L.cap ? (B - b0) : L.cap;
         const int MP = Bc * NP;
         OwlHeadTensors t;
-        RC(owl_forward_heads(h, L, d_images + (size_t)b0 * H * W * 3, Bc, H, W, &t, s));
+        RC(owl_forward_heads(h, L, d_images + (size_t)b0 * H * W * 3, Bc, H, W, want_boxes, &t, s));
         float *feats = t.feats, *cls = t.cls, *bh1 = t.bh1, *bh2 = t.bh2;
         DetectRowsArgs a = detect_args(h);
-        a.feats = feats; a.cls = cls; a.boxh = bh2;
+        a.feats = feats; a.cls = cls; a.boxh = want_boxes ? bh2 : nullptr;
         a.scores = d_scores + (size_t)b0 * NP;
         a.labels = d_labels + (size_t)b0 * NP;
-        a.xyxy = d_boxes_xyxy + (size_t)b0 * NP * 4;
+        a.xyxy = want_boxes ? d_boxes_xyxy + (size_t)b0 * NP * 4 : nullptr;
         a.logits = d_logits ? d_logits + (size_t)b0 * NP * q_uniform : nullptr;
         a.image_set = h_image_query_set ? L.d_image_set + b0 : nullptr;
         a.cxcywh = d_boxes_cxcywh ? d_boxes_cxcywh + (size_t)b0 * NP * 4 : nullptr;
@@ -856,6 +845,39 @@ int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, in
                        d_n_kept ? d_n_kept + b0 : nullptr, s));
     }
     return TSTAR_OK;
+}
+
+int tstar_owl_score(tstar_owl* h, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
+                    const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
+                    uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_boxes_cxcywh, void* stream) {
+    return tstar_owl_score_lane(h, 0, d_images, B, H, W, grid_rows, grid_cols, h_image_query_set, d_scores, d_labels, d_boxes_xyxy, d_cell_conf,
+                                d_cell_mask, d_n_kept, d_logits, d_boxes_cxcywh, stream);
+}
+
+int tstar_owl_score_lane(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
+                         const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
+                         uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_boxes_cxcywh, void* stream) {
+    return tstar_owl_score_lane_obj(h, lane, d_images, B, H, W, grid_rows, grid_cols, h_image_query_set, d_scores, d_labels, d_boxes_xyxy, d_cell_conf,
+                                    d_cell_mask, d_n_kept, d_logits, d_boxes_cxcywh, nullptr, stream);
+}
+
+int tstar_owl_score_lane_obj(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
+                             const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, float* d_boxes_xyxy, double* d_cell_conf,
+                             uint32_t* d_cell_mask, int32_t* d_n_kept, float* d_logits, float* d_boxes_cxcywh, float* d_objectness, void* stream) {
+    TSTAR_REQUIRE(h && d_images && d_scores && d_labels && d_boxes_xyxy && d_cell_conf && d_cell_mask,
+                  "tstar_owl_score: null argument");
+    return owl_score(h, lane, d_images, B, H, W, grid_rows, grid_cols, h_image_query_set, d_scores, d_labels, d_boxes_xyxy, d_cell_conf, d_cell_mask,
+                     d_n_kept, d_logits, d_boxes_cxcywh, d_objectness, stream);
+}
+
+int tstar_owl_score_cells(tstar_owl* h, int lane, const uint8_t* d_images, int B, int H, int W, int grid_rows, int grid_cols,
+                          const int32_t* h_image_query_set, float* d_scores, int32_t* d_labels, double* d_cell_conf, uint32_t* d_cell_mask,
+                          int32_t* d_n_kept, float* d_logits, float* d_objectness, void* stream) {
+    TSTAR_REQUIRE(h && d_images && d_scores && d_labels && d_cell_conf && d_cell_mask, "tstar_owl_score_cells: null argument");
+    TSTAR_REQUIRE(grid_rows >= 1 && grid_cols >= 1, "tstar_owl_score: grid must be at least 1x1");
+    TSTAR_REQUIRE(grid_rows * grid_cols == 1, "tstar_owl_score_cells: only a 1x1 grid can be scored without boxes (the cell of a detection is its box centre's)");
+    return owl_score(h, lane, d_images, B, H, W, grid_rows, grid_cols, h_image_query_set, d_scores, d_labels, nullptr, d_cell_conf, d_cell_mask,
+                     d_n_kept, d_logits, nullptr, d_objectness, stream);
 }
 
 int tstar_owl_debug_preprocess(tstar_owl* h, const uint8_t* d_images, int B, int H, int W, uint8_t* d_out_u8,
@@ -1000,7 +1022,7 @@ int tstar_owl_embed_image_queries(tstar_owl* h, const uint8_t* d_images, int n, 
         const int Bc = (n - b0) < L.cap ? (n - b0) : L.cap;
         const int MP = Bc * NP;
         OwlHeadTensors t;
-        rc = owl_forward_heads(h, L, d_images + (size_t)b0 * H * W * 3, Bc, H, W, &t, s);
+        rc = owl_forward_heads(h, L, d_images + (size_t)b0 * H * W * 3, Bc, H, W, true, &t, s);
         if (rc) break;
         // the box head's tail is detect_rows, as in tstar_owl_score (the boxes are its d_boxes_cxcywh bits); what it writes besides
         // goes to L.x, which is free after merge_cls_ln: scores | labels | xyxy | cxcywh, each at a multiple of four floats
@@ -1291,6 +1313,18 @@ int tstar_attention_x3(const float* d_qkv, float* d_out, int B, int T, int heads
     TSTAR_REQUIRE(d_qkv && d_out, "tstar_attention_x3: null argument");
     return attention_x3(d_qkv, d_out, B, T, heads, (hipStream_t)stream);
 }
+
+int tstar_attention_x3_order(const float* d_qkv, float* d_out, int B, int T, int heads, int order, void* stream) {
+    TSTAR_REQUIRE(d_qkv && d_out, "tstar_attention_x3_order: null argument");
+    TSTAR_REQUIRE(order == 0 || order == 1, "tstar_attention_x3_order: order must be 0 (linear) or 1 (XCD groups)");
+    return attention_x3(d_qkv, d_out, B, T, heads, (hipStream_t)stream, order);
+}
+
+int tstar_xcd_group_block(int bid, int ngroups, int gsize) {
+    if (bid < 0 || ngroups < 1 || gsize < 1 || bid >= xcd_groups_grid(ngroups, gsize)) return -2;
+    return xcd_remap_groups(bid, ngroups, gsize);
+}
+int tstar_xcd_groups_grid(int ngroups, int gsize) { return ngroups < 1 || gsize < 1 ? -1 : xcd_groups_grid(ngroups, gsize); }
 
 int tstar_attention_split(const float* d_qkv, float* d_out, int B, int T, int heads, void* stream) {
     TSTAR_REQUIRE(d_qkv && d_out, "tstar_attention_split: null argument");

@@ -41,12 +41,24 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // Bijective XCD-aware remap of a 1-D block id: the dispatcher places block b on
 // XCD b % 8 (observed, speed only); give each XCD a contiguous chunk of the
 // tile space so neighbouring tiles share that XCD's private L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+__host__ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     const int nx = 8;
     int xcd = bid % nx, idx = bid / nx;
     int q = nwg / nx, r = nwg % nx;
     int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + idx;
+}
+
+// The same remap for blocks that come in GROUPS of gsize which share operands (the query tiles of one (image, head)): the whole
+// group must sit on ONE XCD, which no permutation of ngroups * gsize ids can give unless every XCD's share is a multiple of gsize.
+// So the grid is padded to xcd_groups_grid() blocks: XCD x runs its blocks bid = 8 idx + x in order, gsize consecutive idx are one
+// group, group slot (idx / gsize) * 8 + x goes through xcd_remap over the groups, and the slots past ngroups (fewer than 8 groups'
+// worth of blocks) return -1: they exit at once.  The live blocks map one-to-one onto 0 .. ngroups * gsize - 1.
+static inline int xcd_groups_grid(int ngroups, int gsize) { return (ngroups + 7) / 8 * 8 * gsize; }
+__host__ __device__ __forceinline__ int xcd_remap_groups(int bid, int ngroups, int gsize) {
+    const int xcd = bid % 8, idx = bid / 8;
+    const int slot = (idx / gsize) * 8 + xcd;
+    return slot < ngroups ? xcd_remap(slot, ngroups) * gsize + idx % gsize : -1;
 }
 
 // 12 bytes of 4 consecutive RGB pixels -> three aligned dword stores (d dword-aligned: rows are multiples of 4 pixels;

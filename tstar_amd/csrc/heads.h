@@ -7,7 +7,7 @@ namespace tstar {
 struct DetectRowsArgs {
     const float* feats;    // [rows, 768]  image feats after detection LayerNorm
     const float* cls;      // [rows, 512]  class_head.dense0 output
-    const float* boxh;     // [rows, 768]  box_head after dense1 + GELU
+    const float* boxh;     // [rows, 768]  box_head after dense1 + GELU, or null: no box tail, xyxy / cxcywh are not written
     const float* qn;       // [sets][32][512]  query embeds / (||q|| + 1e-6)
     const uint8_t* qmask;  // [sets][32]       0 = padded query
     const int* image_set;  // [B] query set of every image, or null (all images use set 0)
@@ -19,7 +19,7 @@ struct DetectRowsArgs {
     const float* box_bias; // [np, 4]
     float* scores;         // [rows]
     int* labels;           // [rows]
-    float* xyxy;           // [rows, 4] pixels of the passed image
+    float* xyxy;           // [rows, 4] pixels of the passed image (may be null when boxh is)
     float* logits;         // [rows, Q] or null
     float* cxcywh;         // [rows, 4] or null
     int rows, np, Q;       // Q: common query count (row stride of `logits`), 0 if the sets differ
@@ -30,6 +30,7 @@ int detect_rows(const DetectRowsArgs& a, hipStream_t s);
 // out[r] = dot(h[r, :768], w) + b[0]: the last layer of OWLv2's objectness head (one wave per row)
 int row_dot768(const float* h, const float* w, const float* b, float* out, int rows, hipStream_t s);
 
+// xyxy may be null for a 1 x 1 grid: every kept detection then falls in cell 0, where the clamped centre puts it anyway
 int cell_reduce(const float* scores, const int* labels, const float* xyxy, const double* qweight, const int* image_set, int B, int np,
                 int img_w, int img_h, int grows, int gcols, float thr, double* cell_conf, uint32_t* cell_mask,
                 int* n_kept, hipStream_t s);

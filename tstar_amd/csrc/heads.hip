@@ -86,42 +86,49 @@ __global__ __launch_bounds__(256) void detect_rows_kernel(DetectRowsArgs a) {
         if (lg > best) { best = lg; label = q; }        // ties -> lowest index (torch CPU max)
     }
 
-    // ---- box head tail: 4 dots over the second GELU layer's output
-    f32x4 hb[3];
+    // ---- box head tail: 4 dots over the second GELU layer's output (skipped with its stores when the caller has no box head
+    // output: a.boxh == nullptr, the score-only forward of a 1 x 1 grid)
+    float bx[4] = {0.f, 0.f, 0.f, 0.f};
+    const bool boxes = a.boxh != nullptr;
+    if (boxes) {
+        f32x4 hb[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) hb[i] = *reinterpret_cast<const f32x4*>(a.boxh + (size_t)row * 768 + (i * 64 + lane) * 4);
-    float bx[4];
+        for (int i = 0; i < 3; ++i) hb[i] = *reinterpret_cast<const f32x4*>(a.boxh + (size_t)row * 768 + (i * 64 + lane) * 4);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float d = 0.f;
+        for (int k = 0; k < 4; ++k) {
+            float d = 0.f;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(a.box2_w + (size_t)k * 768 + (i * 64 + lane) * 4);
+            for (int i = 0; i < 3; ++i) {
+                const f32x4 w = *reinterpret_cast<const f32x4*>(a.box2_w + (size_t)k * 768 + (i * 64 + lane) * 4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) d += hb[i][e] * w[e];
+                for (int e = 0; e < 4; ++e) d += hb[i][e] * w[e];
+            }
+            d = wsum(d) + a.box2_b[k] + a.box_bias[p * 4 + k];
+            bx[k] = 1.0f / (1.0f + expf(-d));
         }
-        d = wsum(d) + a.box2_b[k] + a.box_bias[p * 4 + k];
-        bx[k] = 1.0f / (1.0f + expf(-d));
     }
 
     if (lane == 0) {
         const float score = 1.0f / (1.0f + expf(-best));
-        const float fw = a.box_sx, fh = a.box_sy;
-        const float x0 = (bx[0] - 0.5f * bx[2]) * fw, y0 = (bx[1] - 0.5f * bx[3]) * fh;
-        const float x1 = (bx[0] + 0.5f * bx[2]) * fw, y1 = (bx[1] + 0.5f * bx[3]) * fh;
         a.scores[row] = score;
         a.labels[row] = label;
-        f32x4 o; o[0] = x0; o[1] = y0; o[2] = x1; o[3] = y1;
-        *reinterpret_cast<f32x4*>(a.xyxy + (size_t)row * 4) = o;
-        if (a.cxcywh) {
-            f32x4 bb; bb[0] = bx[0]; bb[1] = bx[1]; bb[2] = bx[2]; bb[3] = bx[3];
-            *reinterpret_cast<f32x4*>(a.cxcywh + (size_t)row * 4) = bb;
+        if (boxes) {
+            const float fw = a.box_sx, fh = a.box_sy;
+            const float x0 = (bx[0] - 0.5f * bx[2]) * fw, y0 = (bx[1] - 0.5f * bx[3]) * fh;
+            const float x1 = (bx[0] + 0.5f * bx[2]) * fw, y1 = (bx[1] + 0.5f * bx[3]) * fh;
+            f32x4 o; o[0] = x0; o[1] = y0; o[2] = x1; o[3] = y1;
+            *reinterpret_cast<f32x4*>(a.xyxy + (size_t)row * 4) = o;
+            if (a.cxcywh) {
+                f32x4 bb; bb[0] = bx[0]; bb[1] = bx[1]; bb[2] = bx[2]; bb[3] = bx[3];
+                *reinterpret_cast<f32x4*>(a.cxcywh + (size_t)row * 4) = bb;
+            }
         }
     }
 }
 
 int detect_rows(const DetectRowsArgs& a, hipStream_t s) {
     TSTAR_REQUIRE(a.rows > 0 && a.setQ, "detect_rows: empty problem");
+    TSTAR_REQUIRE(a.boxh ? a.xyxy != nullptr : !a.cxcywh, "detect_rows: box outputs go with the box head's hidden rows");
     hipLaunchKernelGGL(detect_rows_kernel, dim3(cdiv(a.rows, 4)), dim3(256), 0, s, a);
     TSTAR_HIP_CHECK(hipGetLastError());
     return TSTAR_OK;
@@ -179,14 +186,17 @@ __global__ __launch_bounds__(256) void cell_reduce_kernel(const float* __restric
         if (s > thr) {
             const int lab = labels[r];
             const double conf = (double)s * qweight[lab];
-            const f32x4 bb = *reinterpret_cast<const f32x4*>(xyxy + r * 4);
-            const float cx = (bb[0] + bb[2]) * 0.5f;          // f32 add, exact halving
-            const float cy = (bb[1] + bb[3]) * 0.5f;
-            int gx = (int)np_floor_divide((double)cx, cw), gy = (int)np_floor_divide((double)cy, ch);   // cx // grid_width (:141-142)
-            gx = gx < gcols - 1 ? gx : gcols - 1;
-            gy = gy < grows - 1 ? gy : grows - 1;
-            gx = gx < 0 ? 0 : gx; gy = gy < 0 ? 0 : gy;
-            const int cell = gy * gcols + gx;
+            int cell = 0;                                     // xyxy == nullptr: one cell (the launcher checks), where the clamps below end too
+            if (xyxy) {
+                const f32x4 bb = *reinterpret_cast<const f32x4*>(xyxy + r * 4);
+                const float cx = (bb[0] + bb[2]) * 0.5f;          // f32 add, exact halving
+                const float cy = (bb[1] + bb[3]) * 0.5f;
+                int gx = (int)np_floor_divide((double)cx, cw), gy = (int)np_floor_divide((double)cy, ch);   // cx // grid_width (:141-142)
+                gx = gx < gcols - 1 ? gx : gcols - 1;
+                gy = gy < grows - 1 ? gy : grows - 1;
+                gx = gx < 0 ? 0 : gx; gy = gy < 0 ? 0 : gy;
+                cell = gy * gcols + gx;
+            }
             atomicMax(&cbits[cell], (unsigned long long)__double_as_longlong(conf));
             atomicOr(&cmask[cell], 1u << lab);
             atomicAdd(&kept, 1);
@@ -204,6 +214,7 @@ int cell_reduce(const float* scores, const int* labels, const float* xyxy, const
                 int B, int np, int img_w, int img_h, int grows, int gcols, float thr, double* cell_conf, uint32_t* cell_mask,
                 int* n_kept, hipStream_t s) {
     TSTAR_REQUIRE(grows > 0 && gcols > 0 && grows * gcols <= 4096, "cell_reduce: grid must have 1..4096 cells");
+    TSTAR_REQUIRE(xyxy || grows * gcols == 1, "cell_reduce: a grid of more than one cell needs the boxes");
     const size_t lds = (size_t)grows * gcols * (sizeof(unsigned long long) + sizeof(uint32_t));
     hipLaunchKernelGGL(cell_reduce_kernel, dim3(B), dim3(256), lds, s, scores, labels, xyxy, qweight, image_set, np, img_w, img_h,
                        grows, gcols, thr, cell_conf, cell_mask, n_kept);

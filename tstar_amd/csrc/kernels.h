@@ -98,6 +98,8 @@ int attention_f32(const float* qkv, float* out, int B, int T, int heads, int mod
 int attention_split(const float* qkv, float* out, int B, int T, int heads, hipStream_t s);
 
 // the same (mode 0 only) with EXACT operands: every f32 operand as three bf16 terms, six products per MFMA step (the f32x3 mode)
-int attention_x3(const float* qkv, float* out, int B, int T, int heads, hipStream_t s);
+// order: block id -> (image, head, query tile).  1 = the query tiles of an (image, head) back to back on one XCD (xcd_remap_groups),
+// 0 = linear, -1 = the library's choice (1 unless TSTAR_AX3_XCD_OFF is set).  Every block computes the same tile either way: same bits.
+int attention_x3(const float* qkv, float* out, int B, int T, int heads, hipStream_t s, int order = -1);
 
 }  // namespace tstar

@@ -52,6 +52,10 @@ class Detections:
         return int(self.xyxy.shape[0])
 
 
+# what ``annotated_batch`` / ``_detections_from`` raise (ValueError) on a ``score_batch(..., boxes=False)`` result
+NO_BOXES_ERROR = "this result was scored with boxes=False and holds no boxes; score the images with boxes=True to draw or list detections"
+
+
 def _env_int(name: str, default):
     v = os.environ.get(name)
     if v is None or v.strip() == "":
@@ -294,10 +298,13 @@ class OWLInterface(HeuristicInterface):
 
     aux_lane = True      # score_batch(..., lane=1) runs in a second workspace: safe to enqueue on another stream beside lane 0
 
-    def score_batch(self, d_images, grid_rows: int, grid_cols: int, image_sets=None, lane: int = 0):
+    def score_batch(self, d_images, grid_rows: int, grid_cols: int, image_sets=None, lane: int = 0, boxes: bool = True):
         """Batched scoring of device images u8 [B,H,W,3] -> tstar_amd.owl.ScoreResult (device tensors).
-        ``image_sets``: query-set slot per image (see ``install_queries``); default slot 0.  ``lane``: see ``OwlScorer.score``."""
-        return self.scorer.score(d_images, grid_rows, grid_cols, image_sets=image_sets, lane=lane)
+        ``image_sets``: query-set slot per image (see ``install_queries``); default slot 0.  ``lane``: see ``OwlScorer.score``.
+        ``boxes=False`` (1 x 1 grid only): the box head is skipped and the result's ``boxes`` is None -- for callers that read only
+        ``cell_conf`` / ``cell_mask`` (the searcher's verification frames without a visual history); same bits in every other field.
+        ``annotated_batch`` / ``_detections_from`` raise ``NO_BOXES_ERROR`` on such a result."""
+        return self.scorer.score(d_images, grid_rows, grid_cols, image_sets=image_sets, lane=lane, boxes=boxes)
 
     def install_queries(self, slot: int, target_objects: List[str], cue_objects: List[str],
                         object2weight: Optional[Dict[str, float]] = None) -> List[List[str]]:
@@ -339,6 +346,8 @@ class OWLInterface(HeuristicInterface):
         count = int(d_images.shape[0]) if count is None else int(count)
         if not d_images.is_contiguous() or d_images.shape[0] != count:
             raise ValueError("annotated_batch: d_images must be a contiguous [count,H,W,3] uint8 device tensor")
+        if r.boxes is None:
+            raise ValueError("annotated_batch: " + NO_BOXES_ERROR)
         boxes = r.boxes[start:start + count].contiguous()
         scores = r.scores[start:start + count].contiguous()
         lib = _lib.load()
@@ -354,6 +363,8 @@ class OWLInterface(HeuristicInterface):
         return imgs, dets
 
     def _detections_from(self, r, b: int) -> Detections:
+        if r.boxes is None:
+            raise ValueError("_detections_from: " + NO_BOXES_ERROR)
         s = r.scores[b].cpu().numpy()
         keep = s > np.float32(0.005)
         return Detections(xyxy=r.boxes[b].cpu().numpy()[keep], confidence=s[keep],

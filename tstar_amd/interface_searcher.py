@@ -33,6 +33,36 @@ from .video import FrameStore, open_video
 
 CELL_W, CELL_H = 200, 95            # create_image_grid's hard-coded cell size (:186)
 VERIFY_W, VERIFY_H = 200 * 3, 95 * 3  # verify_and_remove_target's resize (:403)
+_ACCEPTS = {}
+
+
+def accepts_keyword(fn, name: str) -> bool:
+    """Does ``fn`` take the keyword ``name``?  A wrapper installed over ``heuristic.score_batch`` (a recorder, a logger) or another
+    backend with an older signature keeps working: the caller then leaves the keyword out."""
+    import inspect
+    key = (getattr(fn, "__func__", fn), name)
+    if key not in _ACCEPTS:
+        try:
+            ps = inspect.signature(fn).parameters
+            _ACCEPTS[key] = name in ps or any(p.kind == inspect.Parameter.VAR_KEYWORD for p in ps.values())
+        except (TypeError, ValueError):
+            _ACCEPTS[key] = False
+    return _ACCEPTS[key]
+
+
+def verify_score_kwargs(heuristic, keep_boxes: bool) -> dict:
+    """Keywords of a verification forward (1 x 1 grid).  The replay reads ``cell_conf[:, 0]`` and ``cell_mask[:, 0]`` only, as the
+    reference's verify_and_remove_target reads the confidence and the names (:382-420); boxes are read for the visual history
+    alone, so without one the detector is asked not to compute them (``OWLInterface.score_batch(boxes=False)``: same bits).
+    Only the detector's OWN ``score_batch`` is asked: a wrapper installed over it (a recorder, a logger) may read the boxes of
+    every result it sees and keeps getting them, and a backend without the keyword is called as before."""
+    fn = heuristic.score_batch
+    own = getattr(fn, "__self__", None) is heuristic and "score_batch" not in vars(heuristic)
+    if keep_boxes or not own or not accepts_keyword(fn, "boxes"):
+        return {}
+    return {"boxes": False}
+
+
 SAMPLER_WARNING = "Warning: Not enough non-zero entries, adjusting probability distribution."      # (:350)
 
 
@@ -547,7 +577,7 @@ class TStarSearcher:
         if not cands:
             return None
         vframes = self._device_verify_frames([secs[i] for i in cands])
-        res = self.heuristic.score_batch(vframes, 1, 1)
+        res = self.heuristic.score_batch(vframes, 1, 1, **verify_score_kwargs(self.heuristic, self.keep_visual_history))
         self.device_images_scored += len(cands)
         return cands, vframes, res
 
@@ -600,7 +630,7 @@ class TStarSearcher:
             if target in detected_objects:
                 d_frame = self._device_verify_frames([int(frame_sec)])
                 if self._fast:
-                    res = self.heuristic.score_batch(d_frame, 1, 1)
+                    res = self.heuristic.score_batch(d_frame, 1, 1, **verify_score_kwargs(self.heuristic, self.keep_visual_history))
                     single_conf = float(res.cell_conf[0, 0].item())
                     single_names = self._names_from_mask(int(res.cell_mask[0, 0].item()) & 0xFFFFFFFF)
                     det = self.heuristic._detections_from(res, 0) if self.keep_visual_history else None

@@ -26,7 +26,7 @@ from typing import List, Sequence, Tuple
 import numpy as np
 
 from . import spline_pool
-from .interface_searcher import CELL_H, CELL_W, SAMPLER_WARNING, VERIFY_H, VERIFY_W, TStarSearcher
+from .interface_searcher import CELL_H, CELL_W, SAMPLER_WARNING, VERIFY_H, VERIFY_W, TStarSearcher, verify_score_kwargs
 
 MAX_GROUP = 63          # TSTAR_OWL_MAX_SETS - 1 query-set slots (include/tstar_hip.h); slot 0 stays the heuristic's own
 
@@ -298,7 +298,8 @@ class _Group:
                 vframes = torch.cat([s._device_verify_frames([secs_l[i][j] for j in cand_l[i]])
                                      for i, s in enumerate(act) if cand_l[i]])
             sets = None if self.solo else [s._slot for i, s in enumerate(act) for _ in cand_l[i]]
-            vres = h.score_batch(vframes, 1, 1, image_sets=sets)
+            # (also the batch verify_ahead() queues) boxes only where an item of the batch keeps a visual history
+            vres = h.score_batch(vframes, 1, 1, image_sets=sets, **verify_score_kwargs(h, any(s.keep_visual_history for s in act)))
             ev = torch.cuda.Event()
             ev.record(self.main)
         return masks, (vres, vframes, ev, cand_l, offs, [list(s.remaining_targets) for s in act])

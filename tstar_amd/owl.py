@@ -63,7 +63,7 @@ class ScoreResult:
     """Device tensors produced by one tstar_owl_score call (np = 576 at B/32, 2304 at B/16; gh * gw at another input size)."""
     scores: "object"       # f32 [B,np]
     labels: "object"       # i32 [B,np]
-    boxes: "object"        # f32 [B,np,4] xyxy pixels
+    boxes: "object"        # f32 [B,np,4] xyxy pixels; None when scored with ``boxes=False`` (1 x 1 grid, no box head)
     cell_conf: "object"    # f64 [B,rows*cols]
     cell_mask: "object"    # i32 view of u32 [B,rows*cols]
     n_kept: "object"       # i32 [B]
@@ -323,16 +323,20 @@ class OwlScorer:
             done.add((S, out))
 
     def score(self, images, grid_rows: int, grid_cols: int, want_logits: bool = False,
-              image_sets: Optional[Sequence[int]] = None, lane: int = 0, objectness: bool = False) -> ScoreResult:
+              image_sets: Optional[Sequence[int]] = None, lane: int = 0, objectness: bool = False, boxes: bool = True) -> ScoreResult:
         """images: torch u8 cuda tensor [B,H,W,3] (contiguous); ``image_sets``: query-set slot per image
         (default: slot 0 for all).  ``lane``: activation workspace of the forward (tstar_owl_score_lane) -- 0 = the handle's own,
         1 = the small second one: a call on lane 1 enqueued on ANOTHER stream may run beside a call on lane 0 (same results).
-        ``objectness=True`` (OWLv2 only): also ``r.objectness`` f32 [B,np], HF's ``objectness_logits``; no other output changes."""
+        ``objectness=True`` (OWLv2 only): also ``r.objectness`` f32 [B,np], HF's ``objectness_logits``; no other output changes.
+        ``boxes=False`` (1 x 1 grid only: tstar_owl_score_cells): the box head is not run, ``r.boxes`` / ``r.boxes_cxcywh`` are None; with
+        one cell the boxes reach no other output, so every other field holds the same bits."""
         torch = self._torch
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
             raise ValueError("score: images must be a cuda uint8 tensor [B,H,W,3]")
         if grid_rows < 1 or grid_cols < 1:
             raise ValueError("score: the grid must be at least 1x1")
+        if not boxes and grid_rows * grid_cols != 1:
+            raise ValueError("score: boxes=False needs a 1x1 grid (the cell of a detection is its box centre's)")
         images = images.contiguous()
         B, H, Wd, _ = images.shape
         dev = images.device
@@ -341,7 +345,7 @@ class OwlScorer:
         r = ScoreResult(
             scores=torch.empty((B, npatch), dtype=torch.float32, device=dev),
             labels=torch.empty((B, npatch), dtype=torch.int32, device=dev),
-            boxes=torch.empty((B, npatch, 4), dtype=torch.float32, device=dev),
+            boxes=torch.empty((B, npatch, 4), dtype=torch.float32, device=dev) if boxes else None,
             cell_conf=torch.empty((B, ncell), dtype=torch.float64, device=dev),
             cell_mask=torch.empty((B, ncell), dtype=torch.int32, device=dev),
             n_kept=torch.empty((B,), dtype=torch.int32, device=dev),
@@ -358,13 +362,21 @@ class OwlScorer:
             if len(qs) != 1:
                 raise ValueError("score: raw logits need the same query count for every image")
             r.logits = torch.empty((B, npatch, qs.pop()), dtype=torch.float32, device=dev)
-            r.boxes_cxcywh = torch.empty((B, npatch, 4), dtype=torch.float32, device=dev)
+            if boxes:
+                r.boxes_cxcywh = torch.empty((B, npatch, 4), dtype=torch.float32, device=dev)
         if objectness:
             if self.family != "owlv2":
                 raise ValueError("score: objectness needs an OWLv2 scorer (OWL-ViT has no objectness head)")
             r.objectness = torch.empty((B, npatch), dtype=torch.float32, device=dev)
         if self.family == "owlv2":
             self._prepare_v2(H, Wd)
+        if not boxes:
+            rc = self._lib.tstar_owl_score_cells(
+                self._h, int(lane), images.data_ptr(), B, H, Wd, grid_rows, grid_cols,
+                None if sets is None else sets.ctypes.data, r.scores.data_ptr(), r.labels.data_ptr(), r.cell_conf.data_ptr(),
+                r.cell_mask.data_ptr(), r.n_kept.data_ptr(), _lib.ptr(r.logits), _lib.ptr(r.objectness), _lib.stream_ptr())
+            _lib.check(rc, "tstar_owl_score_cells")
+            return r
         rc = self._lib.tstar_owl_score_lane_obj(
             self._h, int(lane), images.data_ptr(), B, H, Wd, grid_rows, grid_cols,
             None if sets is None else sets.ctypes.data, r.scores.data_ptr(), r.labels.data_ptr(), r.boxes.data_ptr(), r.cell_conf.data_ptr(),
