@@ -45,6 +45,9 @@ def main():
                     help="video files / JPEG frame folders to search instead of synthetic videos (one item each; overrides --items)")
     ap.add_argument("--video-fps", type=float, default=None,
                     help="frame rate of JPEG frame folders (default 1) and .mjpeg streams (default 25) among --videos")
+    ap.add_argument("--jpeg-entropy", choices=("host", "device"), default=None,
+                    help="where Motion-JPEG / JPEG-folder videos are entropy-decoded (default: TSTAR_JPEG_ENTROPY, else host); "
+                         "'device' keeps the Huffman decode off the rank's CPUs")
     ap.add_argument("--query-image", action="append", default=[], metavar="NAME=PATH",
                     help="example image of an object (repeatable): every target / cue object called NAME is searched for by the "
                          "image-guided query embedded from PATH instead of by its text")
@@ -68,6 +71,8 @@ def main():
         _shard.PREFER_RCCL = os.environ.get("TSTAR_BENCH_BACKEND", "nccl") == "nccl"
         dist.init_process_group("gloo")
 
+    if args.jpeg_entropy is not None:
+        os.environ["TSTAR_JPEG_ENTROPY"] = args.jpeg_entropy       # the searcher opens paths itself: the variable reaches it too
     paths = args.videos if args.videos else [f"synthetic://n={args.nframes},seed={100 + i}" for i in range(args.items)]
     items = [{"video_path": p, "targets": QUESTIONS[i % 4][0], "cues": QUESTIONS[i % 4][1]} for i, p in enumerate(paths)]
 
@@ -76,7 +81,7 @@ def main():
         p = items[i]["video_path"]
         if args.video_fps is not None and (os.path.isdir(p) or p.lower().endswith((".mjpeg", ".mjpg"))):
             from tstar_amd.video import open_video
-            return open_video(p, fps=args.video_fps)
+            return open_video(p, fps=args.video_fps, jpeg_entropy=args.jpeg_entropy)
         return p
 
     owl_kw = {}

@@ -418,6 +418,38 @@ int tstar_jpeg_reconstruct_host(const int16_t* coef, const uint16_t* quant, int 
  * upsampling + YCbCr -> RGB into d_rgb u8 [n,H,W,3] (typically store[s0 : s0 + n]).  d_coef / d_quant 16-byte aligned. */
 int tstar_jpeg_reconstruct(const int16_t* d_coef, const uint16_t* d_quant, int n, int W, int H, int ncomp, int hs, int vs,
                            uint8_t* d_planes, uint8_t* d_rgb, void* stream);
+/* Entropy stage on the device.  The unit of parallel work is a SEGMENT: a run of MCUs that starts at a byte boundary with
+ * zero DC predictors (one restart interval; a frame without DRI is one segment).  The planner below cuts frames into
+ * segments on the host, the kernel decodes one segment per lane into the coefficient layout above, and
+ * tstar_jpeg_reconstruct runs on the result unchanged.  Flat little-endian records, no pointers:
+ *   segment     6 x u32  {frame, byte begin, byte end (offset of the terminating marker), first MCU, MCU count, last (0 / 1)}
+ *   frame       4 x i32  {table set (-1: routed to the host decoder), first segment, segment count, 0}
+ *   table set   9016 bytes (six Huffman tables, quantisation rows, zigzag order, energy limits; csrc/jpeg_entropy_core.h)
+ * Segment status: 0 OK, 1 malformed, 2 uncovered (the codes above); a frame's status is that of its first segment, in
+ * stream order, that is not OK.
+ *
+ * Planner (host only, no HIP state): frame i is datas[i][0 .. lens[i]) and sits at byte_offsets[i] of the byte buffer the
+ * segments will index (offset + length must stay below 2^32).  route i32 [n]: 0 device, 1 host -- a frame whose header,
+ * tables or geometry tstar_jpeg_entropy_batch would not accept as they are, or whose framing (RSTn in order mod 8, their
+ * count, EOI behind the last segment) is not exactly what the sequential decoder expects; that decoder's result is then
+ * authoritative.  frames [n], quant u16 [n][192] (zero rows for host-routed frames), table sets deduplicated by content and
+ * segments go to caller buffers of cap_sets / cap_segments records.  out5 = {table sets, segments, bytes of a table set,
+ * bytes of a segment, bytes of a frame record}.  Returns 4 when a capacity is too small: out5 holds the counts needed, route /
+ * frames / quant are already filled, table sets and segments were not written. */
+int tstar_jpeg_plan_segments(const uint8_t* const* datas, const size_t* lens, const uint64_t* byte_offsets, int n, int W, int H,
+                             int ncomp, int hs, int vs, int32_t* route, void* frames, uint16_t* quant, void* table_sets,
+                             int cap_sets, void* segments, int cap_segments, size_t* out5);
+/* Launcher on caller tensors: clears d_coef int16 [n_frames][blocks][64], then one lane per segment writes coefficients
+ * and d_seg_status i32 [n_segments].  Every read is bounded by the segment's byte range inside d_bytes[0 .. total_bytes),
+ * every store by the segment's frame's region of d_coef; a record that points outside the batch is status 1 and touches
+ * nothing.  Refuses bad arguments before any launch. */
+int tstar_jpeg_entropy_device(const uint8_t* d_bytes, size_t total_bytes, const void* d_segments, const void* d_table_sets,
+                              int n_sets, const void* d_frames, int n_frames, int n_segments, int W, int H, int ncomp, int hs,
+                              int vs, int16_t* d_coef, int32_t* d_seg_status, void* stream);
+/* The same arguments in host memory, the same decode core, segment by segment on the CPU. */
+int tstar_jpeg_entropy_segments_host(const uint8_t* bytes, size_t total_bytes, const void* segments, const void* table_sets,
+                                     int n_sets, const void* frames, int n_frames, int n_segments, int W, int H, int ncomp,
+                                     int hs, int vs, int16_t* coef, int32_t* seg_status);
 /* Native-resolution RGB u8 [n,H,W,3] of NV12 frames (the keyframes pop_frames hands back, :379-380). */
 int tstar_nv12_to_rgb(const uint8_t* d_video, int N, int H, int W, const int32_t* d_frame_idx, int n,
                       uint8_t* d_out, void* stream);

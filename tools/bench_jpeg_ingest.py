@@ -13,6 +13,8 @@ two halves of the device path on their own: the entropy stage (host clock) and t
 events), with the kernels' bytes/s against the achievable-HBM figure of the microarchitecture guide.
 
   python tools/bench_jpeg_ingest.py --out profiles/jpeg_ingest_measure          # writes .md and .json
+  python tools/bench_jpeg_ingest.py --entropy device                            # the same, with the entropy stage on the GPU
+  python tools/bench_jpeg_ingest.py --entropy compare                           # host against device entropy -> profiles/jpeg_device_entropy_measure
   rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_jpeg_ingest.py --kernels-only     # kernel times, a run of its own
 
 No GPU -> error (a CPU timing says nothing about this).
@@ -60,14 +62,16 @@ def write_avi(path, frames, W, H, rate):
         f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
-def make_avi(path, n, H, W, threads=16):
+def make_avi(path, n, H, W, threads=16, restart_blocks=0):
+    """restart_blocks > 0: a restart marker every that many MCUs."""
     from PIL import Image
     from tstar_amd.video import synthetic_video
     frames = synthetic_video(n, H, W, seed=21).frames.cpu().numpy()
 
     def enc(i):
         b = io.BytesIO()
-        Image.fromarray(frames[i]).save(b, "JPEG", quality=85, subsampling=2)
+        kw = {"restart_marker_blocks": restart_blocks} if restart_blocks else {}
+        Image.fromarray(frames[i]).save(b, "JPEG", quality=85, subsampling=2, **kw)
         return b.getvalue()
 
     with ThreadPoolExecutor(threads) as ex:
@@ -182,9 +186,122 @@ def halves(path, reps=20):
         src.close()
 
 
+def device_entropy_figures(path, reps=10):
+    """What the device entropy path moves and how long its kernel takes: upload bytes per frame over every chunk of the
+    file (compressed bytes + records, as load_jpeg sends them), and the launch (coefficient clear + kernel) of the first chunk
+    by HIP events."""
+    import torch
+    from tstar_amd import _lib, jpeg
+    src = jpeg.avi_mjpeg(path)
+    try:
+        n_all = src.n_frames
+        rc, geom, _ = jpeg.probe(src.read(0))
+        assert rc == 0
+        blocks, _ = jpeg._sizes(geom)
+        chunk = jpeg.device_entropy_chunk(blocks, n_all)
+        up = segs = host_routed = 0
+        t_plan = c_plan = 0.0
+        first = None
+        for s0 in range(0, n_all, chunk):
+            datas = [src.read(i) for i in range(s0, min(n_all, s0 + chunk))]
+            t0, c0 = time.perf_counter(), time.process_time()
+            batch = jpeg.DeviceBatch(datas, geom)
+            t_plan += time.perf_counter() - t0
+            c_plan += time.process_time() - c0
+            up += batch.nbytes
+            segs += len(batch.plan.segments)
+            host_routed += int(batch.plan.route.sum())
+            if first is None:
+                first = batch
+        n = len(first.datas)
+        host = np.zeros(first.nbytes, dtype=np.uint8)
+        first.fill(host)
+        d_buf = torch.from_numpy(host).cuda()
+        d_coef = torch.empty((n, blocks * 64), dtype=torch.int16, device="cuda")
+        d_status = torch.empty(len(first.plan.segments), dtype=torch.int32, device="cuda")
+        first.launch(d_buf, d_coef, d_status, geom, _lib.stream_ptr())
+        torch.cuda.synchronize()
+        assert not d_status.cpu().numpy().any()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            first.launch(d_buf, d_coef, d_status, geom, _lib.stream_ptr())
+        e1.record()
+        torch.cuda.synchronize()
+        per_chunk = e0.elapsed_time(e1) * 1e-3 / reps
+        return dict(chunk=n, frames=n_all, segments_per_frame=segs / n_all, host_routed=host_routed, table_sets_first_chunk=len(first.plan.table_sets),
+                    h2d_bytes_per_frame=up / n_all, h2d_bytes_per_frame_host_mode=blocks * 128 + 384, plan_wall_s=t_plan, plan_cpu_s=c_plan,
+                    entropy_kernel_s_per_chunk=per_chunk, entropy_kernel_s_all_frames=per_chunk / n * n_all, launches_timed=reps)
+    finally:
+        src.close()
+
+
+def compare_entropy(args):
+    """Host against device entropy through open_video, alternating in one process; the host mode is the baseline."""
+    import torch
+    from tstar_amd.video import open_video
+    props = torch.cuda.get_device_properties(0)
+    res = {"board": f"{torch.cuda.get_device_name(0)} ({getattr(props, 'gcnArchName', '?')})", "cpus_allowed": len(os.sched_getaffinity(0)), "cases": {}}
+    cases = [(name, n, H, W, 0) for name, n, H, W in CASES] + [("360x640, restart per MCU row", 3600, 360, 640, 640 // 16)]
+    with tempfile.TemporaryDirectory() as tmp:
+        for k, (name, n, H, W, restart) in enumerate(cases):
+            n = max(8, int(n * args.scale))
+            path = os.path.join(tmp, f"case{k}.avi")
+            jpeg_bytes = make_avi(path, n, H, W, restart_blocks=restart)
+            print(f"[{name}] {n} frames, {jpeg_bytes / n / 1024:.1f} KiB/frame", flush=True)
+            case = {"frames": n, "jpeg_bytes_per_frame": jpeg_bytes / n, "host": [], "device": []}
+            a, b = open_video(path, jpeg_entropy="host"), open_video(path, jpeg_entropy="device")        # warm-up of both
+            case["same_bytes"] = bool(torch.equal(a.frames, b.frames))
+            case["entropy_stats"] = b.entropy_stats
+            del a, b
+            for _ in range(args.repeats):
+                for mode in ("host", "device"):
+                    st, w, c = timed(lambda: open_video(path, jpeg_entropy=mode))
+                    case[mode].append({"wall_s": w, "cpu_s": c, "frames_per_s": n / w})
+                    del st
+            for mode in ("host", "device"):
+                case[mode + "_median"] = {m: float(np.median([r[m] for r in case[mode]])) for m in ("wall_s", "cpu_s", "frames_per_s")}
+            case["figures"] = device_entropy_figures(path)
+            res["cases"][name] = case
+            print(json.dumps({name: {k2: case[k2] for k2 in ("host_median", "device_median", "same_bytes", "figures")}}), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out + ".json", "w") as f:
+        json.dump(res, f, indent=1)
+    with open(args.out + ".md", "w") as f:
+        f.write(f"# JPEG ingest: entropy stage on the host against on the device ({res['board']}, {res['cpus_allowed']} CPUs allowed)\n\n"
+                "`tools/bench_jpeg_ingest.py --entropy compare`; Motion-JPEG AVI -> resident store through `open_video`, 4:2:0, quality 85, "
+                f"synthetic video, every frame wanted. Medians of {args.repeats} runs of each mode, alternating in one process after one warm-up of "
+                "each; the host mode is the behaviour before the device stage existed and is the baseline. CPU-seconds = `time.process_time` "
+                "(all threads).\n\n| case | entropy on | wall s | frames/s | host CPU-s | H2D bytes/frame | segments/frame |\n|---|---|---|---|---|---|---|\n")
+        for name, c in res["cases"].items():
+            g = c["figures"]
+            for mode in ("host", "device"):
+                m = c[mode + "_median"]
+                h2d = g["h2d_bytes_per_frame_host_mode"] if mode == "host" else g["h2d_bytes_per_frame"]
+                f.write(f"| {name} x {c['frames']} | {mode} | {m['wall_s']:.3f} | {m['frames_per_s']:.0f} | {m['cpu_s']:.2f} | {h2d:.0f} | "
+                        f"{g['segments_per_frame']:.0f} |\n")
+        f.write("\nAll runs:\n\n")
+        for name, c in res["cases"].items():
+            for mode in ("host", "device"):
+                f.write(f"- {name}, {mode}: wall " + ", ".join(f"{r['wall_s']:.3f}" for r in c[mode]) + " s; CPU "
+                        + ", ".join(f"{r['cpu_s']:.2f}" for r in c[mode]) + f" s; stores byte-equal: {c['same_bytes']}; {c['entropy_stats']}\n")
+        f.write("\n## The entropy kernel alone\n\n| case | frames per chunk | segments (lanes) per chunk | clear + kernel, one chunk s (HIP events) | "
+                "all frames s | planning on the host, all frames: wall s (CPU-s) |\n|---|---|---|---|---|---|\n")
+        for name, c in res["cases"].items():
+            g = c["figures"]
+            f.write(f"| {name} | {g['chunk']} | {g['segments_per_frame'] * g['chunk']:.0f} | {g['entropy_kernel_s_per_chunk']:.4f} | "
+                    f"{g['entropy_kernel_s_all_frames']:.3f} | {g['plan_wall_s']:.3f} ({g['plan_cpu_s']:.2f}) |\n")
+        f.write("\nOne lane decodes one segment, so a file without restart markers gives one lane per frame; the kernel time is that of "
+                f"the slowest lane. The launch is timed over {next(iter(res['cases'].values()))['figures']['launches_timed']} repeats on a resident chunk.\n")
+    print("wrote", args.out + ".md")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_ingest_measure"))
+    ap.add_argument("--out", default=None, help="path stem of the .md / .json written (default: profiles/jpeg_ingest_measure, or "
+                                                "profiles/jpeg_device_entropy_measure with --entropy compare)")
+    ap.add_argument("--entropy", choices=("host", "device", "compare"), default="host",
+                    help="where the device path entropy-decodes; 'compare' measures both modes against each other instead of against Pillow")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the frame counts (rehearsal)")
     ap.add_argument("--kernels-only", action="store_true", help="only run the kernels of one chunk per case (for a rocprofv3 run)")
@@ -192,7 +309,12 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_jpeg_ingest needs an MI355X: a CPU timing says nothing about this path")
-    from tstar_amd.video import open_video
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "jpeg_device_entropy_measure" if args.entropy == "compare" else "jpeg_ingest_measure")
+    if args.entropy == "compare":
+        return compare_entropy(args)
+    from tstar_amd import video
+    open_video = lambda p: video.open_video(p, jpeg_entropy=args.entropy)      # noqa: E731
     props = torch.cuda.get_device_properties(0)
     res = {"board": f"{torch.cuda.get_device_name(0)} ({getattr(props, 'gcnArchName', '?')})", "cpus_allowed": len(os.sched_getaffinity(0)), "cases": {}}
     with tempfile.TemporaryDirectory() as tmp:

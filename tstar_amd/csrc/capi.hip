@@ -5,6 +5,7 @@
 #include "heads.h"
 #include "image_query.h"
 #include "ingest.h"
+#include "jpeg_entropy_core.h"
 #include "jpeg_host.h"
 #include "kernels.h"
 #include "owl_weights.h"
@@ -1111,6 +1112,22 @@ int tstar_nv12_to_rgb(const uint8_t* d_video, int N, int H, int W, const int32_t
 int tstar_i420_to_nv12(const uint8_t* d_i420, int n, int H, int W, uint8_t* d_nv12, void* stream) {
     TSTAR_REQUIRE(d_i420 && d_nv12 && d_i420 != d_nv12, "tstar_i420_to_nv12: null or aliased argument");
     return i420_to_nv12_u8(d_i420, n, H, W, d_nv12, (hipStream_t)stream);
+}
+
+int tstar_jpeg_entropy_device(const uint8_t* d_bytes, size_t total_bytes, const void* d_segments, const void* d_table_sets,
+                              int n_sets, const void* d_frames, int n_frames, int n_segments, int W, int H, int ncomp, int hs,
+                              int vs, int16_t* d_coef, int32_t* d_seg_status, void* stream) {
+    TSTAR_REQUIRE(d_bytes && d_segments && d_table_sets && d_frames && d_coef && d_seg_status, "tstar_jpeg_entropy_device: null argument");
+    TSTAR_REQUIRE(n_sets > 0 && n_frames > 0 && n_segments > 0, "tstar_jpeg_entropy_device: empty batch");
+    const JpegGeom g{W, H, ncomp, hs, vs};
+    TSTAR_REQUIRE(g.valid(), "tstar_jpeg_entropy_device: unsupported geometry");
+    jpegcore::SegmentBatch b;
+    b.bytes = d_bytes; b.total_bytes = total_bytes;
+    b.segments = (const JpegSegment*)d_segments; b.tables = (const JpegTableSet*)d_table_sets; b.frames = (const JpegFrameDesc*)d_frames;
+    b.n_sets = (uint32_t)n_sets; b.n_frames = (uint32_t)n_frames; b.n_segments = (uint32_t)n_segments;
+    b.g = jpeg_seg_geom(g);
+    b.coef = d_coef; b.seg_status = d_seg_status;
+    return jpeg_entropy_segments(b, (hipStream_t)stream);
 }
 
 int tstar_jpeg_reconstruct(const int16_t* d_coef, const uint16_t* d_quant, int n, int W, int H, int ncomp, int hs, int vs,

@@ -60,5 +60,8 @@ int resample_v_normalize_patchify(const uint8_t* in, float* out, uint8_t* out_u8
 struct JpegGeom;
 int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const JpegGeom& g, uint8_t* planes, uint8_t* rgb,
                         hipStream_t s);
+namespace jpegcore { struct SegmentBatch; }
+// jpeg_entropy.hip: clear b.coef, then one lane per segment of the batch (every pointer of b is device memory)
+int jpeg_entropy_segments(const jpegcore::SegmentBatch& b, hipStream_t s);
 
 }  // namespace tstar

@@ -2,6 +2,7 @@
 // reconstruction.  HIP-free.  This file parses untrusted bytes: every read goes through a bounds-checked cursor, every
 // table index and run length is checked before use, and a broken stream is an error, never a partial picture.
 #include "jpeg_host.h"
+#include "jpeg_entropy_core.h"
 #include "jpeg_math.h"
 
 #include <math.h>
@@ -487,6 +488,138 @@ size_t jpeg_frame_end(const uint8_t* d, size_t len, size_t pos) {
     }
 }
 
+namespace {
+
+void flatten(const Huff& t, JpegHuffFlat* f) {
+    memcpy(f->fast, t.fast, sizeof(f->fast));
+    f->maxcode[0] = -1;
+    f->delta[0] = 0;
+    for (int l = 1; l <= 16; ++l) {
+        f->maxcode[l] = t.maxcode[l];
+        f->delta[l] = t.valptr[l] - t.mincode[l];
+    }
+    f->maxcode[17] = t.maxcode[17];
+    f->nvals = t.nvals;
+    memcpy(f->vals, t.vals, (size_t)t.nvals);
+}
+
+// One frame: false = route it to jpeg_entropy.  On true, *ts is the frame's table set, quant its rows and segs its
+// segments with frame-local byte offsets.
+bool plan_frame(const uint8_t* d, size_t len, const JpegGeom& g, Header& h, JpegTableSet* ts, uint16_t* quant,
+                std::vector<JpegSegment>& segs) {
+    const Err e{nullptr, 0};
+    if (!d || parse_header(d, len, h, e) != JPEG_OK) return false;
+    JpegGeom got;
+    if (classify(h, &got, e) != JPEG_OK) return false;
+    if (got.W != g.W || got.H != g.H || got.ncomp != g.ncomp || got.hs != g.hs || got.vs != g.vs) return false;
+    std_tables(h);
+    for (int c = 0; c < g.ncomp; ++c) {
+        const Component& k = h.comp[c];
+        if (!h.have_quant[k.tq] || !h.dc[k.td].present || !h.ac[k.ta].present) return false;
+    }
+    memset((void*)ts, 0, sizeof(*ts));                              // padding and unused tables too: sets are compared by content
+    memset(quant, 0, 192 * sizeof(uint16_t));
+    for (int c = 0; c < g.ncomp; ++c) {
+        const Component& k = h.comp[c];
+        memcpy(quant + 64 * c, h.quant[k.tq], 64 * sizeof(uint16_t));
+        ts->limit[c] = energy_limit(quant + 64 * c);
+        flatten(h.dc[k.td], &ts->h[2 * c]);
+        flatten(h.ac[k.ta], &ts->h[2 * c + 1]);
+    }
+    memcpy(ts->quant, quant, sizeof(ts->quant));
+    memcpy(ts->zigzag, kZigzag, 64);
+
+    // the entropy data, once: a segment ends at the first FF that is not followed by 00 (where the bit reader stops)
+    const size_t n_mcu = (size_t)g.mcux() * g.mcuy(), ri = (size_t)h.restart_interval;
+    const size_t n_seg = ri ? (n_mcu + ri - 1) / ri : 1;
+    size_t p = h.scan_data;
+    for (size_t i = 0; i < n_seg; ++i) {
+        const size_t begin = p;
+        for (;;) {
+            const void* f = p < len ? memchr(d + p, 0xFF, len - p) : nullptr;
+            if (!f) return false;                                   // the data ends without a marker
+            p = (size_t)((const uint8_t*)f - d);
+            if (p + 1 >= len) return false;
+            if (d[p + 1] != 0x00) break;
+            p += 2;
+        }
+        const size_t end = p;
+        while (p + 1 < len && d[p] == 0xFF && d[p + 1] == 0xFF) ++p;       // fill bytes in front of the marker
+        if (p + 1 >= len) return false;
+        const bool last = i + 1 == n_seg;
+        if (d[p + 1] != (last ? 0xD9 : 0xD0 + (int)(i & 7))) return false;  // RSTn in order, EOI behind the last segment
+        p += 2;
+        JpegSegment s;
+        s.frame = 0;
+        s.begin = (uint32_t)begin;
+        s.end = (uint32_t)end;
+        s.first_mcu = (uint32_t)(ri ? i * ri : 0);
+        s.n_mcu = (uint32_t)(ri && (i + 1) * ri < n_mcu ? ri : n_mcu - s.first_mcu);
+        s.last = last ? 1u : 0u;
+        segs.push_back(s);
+    }
+    return true;
+}
+
+}  // namespace
+
+bool jpeg_plan_segments(const uint8_t* const* datas, const size_t* lens, const uint64_t* byte_offsets, int n, const JpegGeom& g,
+                        int32_t* route, JpegFrameDesc* frames, uint16_t* quant, std::vector<JpegTableSet>* sets,
+                        std::vector<JpegSegment>* segments) {
+    std::vector<Header> hv(1);                                     // ~10 KB of tables: off the stack
+    std::vector<JpegTableSet> one(1);
+    std::vector<JpegSegment> segs;
+    for (int i = 0; i < n; ++i) {
+        if (byte_offsets[i] + (uint64_t)lens[i] >= 0xffffffffull) return false;
+        hv[0] = Header();
+        segs.clear();
+        uint16_t* q = quant + 192 * (size_t)i;
+        JpegFrameDesc& fd = frames[i];
+        fd.table_set = -1; fd.first_segment = 0; fd.n_segments = 0; fd.reserved = 0;
+        if (!plan_frame(datas[i], lens[i], g, hv[0], &one[0], q, segs)) {
+            memset(q, 0, 192 * sizeof(uint16_t));
+            route[i] = 1;
+            continue;
+        }
+        route[i] = 0;
+        size_t k = 0;
+        while (k < sets->size() && memcmp((const void*)&(*sets)[k], (const void*)&one[0], sizeof(JpegTableSet)) != 0) ++k;
+        if (k == sets->size()) sets->push_back(one[0]);
+        fd.table_set = (int32_t)k;
+        fd.first_segment = (int32_t)segments->size();
+        fd.n_segments = (int32_t)segs.size();
+        for (JpegSegment s : segs) {
+            s.frame = (uint32_t)i;
+            s.begin += (uint32_t)byte_offsets[i];
+            s.end += (uint32_t)byte_offsets[i];
+            segments->push_back(s);
+        }
+    }
+    return true;
+}
+
+bool jpeg_entropy_segments_host(const uint8_t* bytes, size_t total_bytes, const JpegSegment* segments, const JpegTableSet* tables,
+                                int n_sets, const JpegFrameDesc* frames, int n_frames, int n_segments, const JpegGeom& g,
+                                int16_t* coef, int32_t* seg_status) {
+    if (!bytes || !segments || !tables || !frames || !coef || !seg_status || n_sets <= 0 || n_frames <= 0 || n_segments <= 0 ||
+        total_bytes == 0 || total_bytes >= 0xffffffffull || !g.valid())
+        return false;
+    jpegcore::SegmentBatch b;
+    b.bytes = bytes; b.total_bytes = total_bytes; b.segments = segments; b.tables = tables; b.frames = frames;
+    b.n_sets = (uint32_t)n_sets; b.n_frames = (uint32_t)n_frames; b.n_segments = (uint32_t)n_segments;
+    b.g = jpeg_seg_geom(g);
+    b.coef = coef; b.seg_status = seg_status;
+    memset(coef, 0, (size_t)n_frames * b.g.per_frame * sizeof(int16_t));
+    for (int i = 0; i < n_segments; ++i) {
+        const JpegSegment s = segments[i];
+        const int ts = jpegcore::segment_table_set(b, s);
+        seg_status[i] = ts < 0 ? (int)JPEG_MALFORMED
+                               : jpegcore::decode_segment(bytes, s.begin, s.end, tables + ts, b.g, s.first_mcu, s.n_mcu, s.last != 0,
+                                                          coef + (size_t)s.frame * b.g.per_frame);
+    }
+    return true;
+}
+
 void jpeg_reconstruct_host(const JpegGeom& g, const int16_t* coef, const uint16_t* quant, uint8_t* scratch, uint8_t* rgb) {
     using namespace jpegmath;
     const uint8_t* plane[3] = {nullptr, nullptr, nullptr};
@@ -619,6 +752,48 @@ int tstar_jpeg_entropy_batch(const uint8_t* const* datas, const size_t* lens, in
             set_error("tstar_jpeg_entropy_batch: frame " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]);
             return 3;
         }
+    return 0;
+}
+
+int tstar_jpeg_plan_segments(const uint8_t* const* datas, const size_t* lens, const uint64_t* byte_offsets, int n, int W, int H,
+                             int ncomp, int hs, int vs, int32_t* route, void* frames, uint16_t* quant, void* table_sets,
+                             int cap_sets, void* segments, int cap_segments, size_t* out5) {
+    JpegGeom g;
+    if (!datas || !lens || !byte_offsets || !route || !frames || !quant || !out5 || n <= 0 || cap_sets < 0 || cap_segments < 0 ||
+        (cap_sets > 0 && !table_sets) || (cap_segments > 0 && !segments) || !geom_from_args(W, H, ncomp, hs, vs, &g)) {
+        set_error("tstar_jpeg_plan_segments: null argument, n <= 0 or unsupported geometry");
+        return 1;
+    }
+    struct { std::vector<JpegTableSet> sets; std::vector<JpegSegment> segments; } plan;
+    if (!jpeg_plan_segments(datas, lens, byte_offsets, n, g, route, (JpegFrameDesc*)frames, quant, &plan.sets, &plan.segments)) {
+        set_error("tstar_jpeg_plan_segments: a frame ends beyond the 32-bit byte offsets of a segment");
+        return 1;
+    }
+    out5[0] = plan.sets.size();
+    out5[1] = plan.segments.size();
+    out5[2] = sizeof(JpegTableSet);
+    out5[3] = sizeof(JpegSegment);
+    out5[4] = sizeof(JpegFrameDesc);
+    if (plan.sets.size() > (size_t)cap_sets || plan.segments.size() > (size_t)cap_segments) {
+        set_error("tstar_jpeg_plan_segments: " + std::to_string(plan.sets.size()) + " table sets and " +
+                  std::to_string(plan.segments.size()) + " segments do not fit the given buffers");
+        return 4;
+    }
+    if (!plan.sets.empty()) memcpy(table_sets, (const void*)plan.sets.data(), plan.sets.size() * sizeof(JpegTableSet));
+    if (!plan.segments.empty()) memcpy(segments, plan.segments.data(), plan.segments.size() * sizeof(JpegSegment));
+    return 0;
+}
+
+int tstar_jpeg_entropy_segments_host(const uint8_t* bytes, size_t total_bytes, const void* segments, const void* table_sets,
+                                     int n_sets, const void* frames, int n_frames, int n_segments, int W, int H, int ncomp,
+                                     int hs, int vs, int16_t* coef, int32_t* seg_status) {
+    JpegGeom g;
+    if (!geom_from_args(W, H, ncomp, hs, vs, &g) ||
+        !jpeg_entropy_segments_host(bytes, total_bytes, (const JpegSegment*)segments, (const JpegTableSet*)table_sets, n_sets,
+                                    (const JpegFrameDesc*)frames, n_frames, n_segments, g, coef, seg_status)) {
+        set_error("tstar_jpeg_entropy_segments_host: null argument, empty batch or unsupported geometry");
+        return 1;
+    }
     return 0;
 }
 

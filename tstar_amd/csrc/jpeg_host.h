@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace tstar {
 
 // status of one frame (also the return value of the single-frame calls)
@@ -58,6 +60,25 @@ int jpeg_entropy(const uint8_t* data, size_t len, const JpegGeom& g, int16_t* co
 // Byte offset one past the EOI of the JPEG that starts at data[pos] (found by walking marker segments and the stuffed
 // entropy data), or 0 when the stream is broken / ends first.
 size_t jpeg_frame_end(const uint8_t* data, size_t len, size_t pos);
+
+// Segments for the entropy stage on the device (records and decode core: jpeg_entropy_core.h).  Walks the header and, once,
+// the entropy data of n frames of geometry g; frame i sits at byte_offsets[i] of the byte buffer the segments index.
+// route[i] = 0: frames[i], quant row i, its table set and its segments are filled; 1: the frame goes to jpeg_entropy, whose
+// result is authoritative (header, tables or geometry it would not accept as they are, or framing that is not exactly what
+// it expects).  Table sets (deduplicated by content) and segments are appended to *sets / *segments.  Returns false when an
+// offset does not fit the segments' 32 bits.
+struct JpegTableSet;
+struct JpegSegment;
+struct JpegFrameDesc;
+bool jpeg_plan_segments(const uint8_t* const* datas, const size_t* lens, const uint64_t* byte_offsets, int n, const JpegGeom& g,
+                        int32_t* route, JpegFrameDesc* frames, uint16_t* quant, std::vector<JpegTableSet>* sets,
+                        std::vector<JpegSegment>* segments);
+
+// The device kernel's decode core on the CPU, segment by segment: clears coef [n_frames][g.blocks() * 64], then writes it
+// and seg_status [n_segments].  False on a null argument or unsupported geometry.
+bool jpeg_entropy_segments_host(const uint8_t* bytes, size_t total_bytes, const JpegSegment* segments, const JpegTableSet* tables,
+                                int n_sets, const JpegFrameDesc* frames, int n_frames, int n_segments, const JpegGeom& g,
+                                int16_t* coef, int32_t* seg_status);
 
 // Scalar reference of the device stage: coefficients + tables -> RGB u8 [H][W][3].  scratch: g.plane_bytes() bytes.
 void jpeg_reconstruct_host(const JpegGeom& g, const int16_t* coef, const uint16_t* quant, uint8_t* scratch, uint8_t* rgb);

@@ -7,6 +7,10 @@ pinned memory; dequantisation, inverse DCT, chroma upsampling and YCbCr -> RGB r
 straight into the store, the copy and kernels of one chunk overlapping the entropy decode of the next.  The result is
 byte-equal to Pillow / libjpeg-turbo.  Frames the kernels do not cover (progressive, arithmetic, CMYK, unusual sampling)
 are decoded by Pillow and copied in; ``FrameStore.decode_stats`` says how many frames went which way.
+
+``entropy="device"`` moves the entropy stage to the GPU as well (tstar_jpeg_plan_segments cuts the frames into restart
+segments on the host, tstar_jpeg_entropy_device decodes one segment per lane): the compressed bytes go up instead of the
+coefficients, and a frame the device does not vouch for is run through the host decoder again, whose verdict stands.
 """
 from __future__ import annotations
 
@@ -296,6 +300,163 @@ def entropy_batch(datas: Sequence[bytes], geom, coef: np.ndarray, quant: np.ndar
     return status, (lib.tstar_last_error().decode() if rc else "")
 
 
+# records of the device entropy stage (include/tstar_hip.h; csrc/jpeg_entropy_core.h)
+SEGMENT_DTYPE = np.dtype([("frame", "<u4"), ("begin", "<u4"), ("end", "<u4"), ("first_mcu", "<u4"), ("n_mcu", "<u4"), ("last", "<u4")])
+FRAME_DTYPE = np.dtype([("table_set", "<i4"), ("first_segment", "<i4"), ("n_segments", "<i4"), ("reserved", "<i4")])
+TABLE_SET_BYTES = 9016
+ROUTE_DEVICE, ROUTE_HOST = 0, 1
+ENTROPY_MODES = ("host", "device")
+
+
+def entropy_mode(entropy: Optional[str] = None) -> str:
+    """The keyword when given, else TSTAR_JPEG_ENTROPY, else "host"."""
+    mode = entropy if entropy is not None else (os.environ.get("TSTAR_JPEG_ENTROPY") or "host")
+    if mode not in ENTROPY_MODES:
+        raise ValueError(f"JPEG entropy mode {mode!r}: expected one of {ENTROPY_MODES}")
+    return mode
+
+
+def device_entropy_chunk(blocks: int, n_frames: int, chunk: Optional[int] = None, coef_budget: int = 512 << 20,
+                         max_frames: int = 1024) -> int:
+    """Frames per chunk of the device entropy path.  A frame without restart markers is one lane, so a launch wants as many
+    frames as fit: bounded by ``coef_budget`` bytes of device coefficients (blocks * 128 per frame), by ``max_frames`` and
+    by the frames there are; never below 1.  ``chunk`` overrides the budget, not the frame count."""
+    if blocks <= 0 or n_frames <= 0:
+        raise ValueError("device_entropy_chunk: blocks and n_frames must be positive")
+    c = int(chunk) if chunk else min(max_frames, coef_budget // (blocks * 128))
+    return max(1, min(c, n_frames))
+
+
+class SegmentPlan:
+    """What tstar_jpeg_plan_segments says about a batch: route int32 [n], frames FRAME_DTYPE [n], quant uint16 [n,192],
+    table_sets uint8 [n_sets, TABLE_SET_BYTES], segments SEGMENT_DTYPE [n_segments], offsets uint64 [n], total_bytes."""
+
+    def __init__(self, route, frames, quant, table_sets, segments, offsets, total_bytes):
+        self.route, self.frames, self.quant, self.table_sets = route, frames, quant, table_sets
+        self.segments, self.offsets, self.total_bytes = segments, offsets, int(total_bytes)
+
+    def frame_status(self, seg_status: np.ndarray) -> np.ndarray:
+        """int32 [n]: the status of a frame's first segment, in stream order, that is not OK; -1 for a host-routed frame."""
+        out = np.where(self.route == ROUTE_DEVICE, OK, -1).astype(np.int32)
+        bad = np.nonzero(seg_status)[0]
+        for i in bad[::-1]:                                # the earliest segment of a frame is written last
+            out[self.segments["frame"][i]] = seg_status[i]
+        return out
+
+
+def pack_offsets(datas: Sequence[bytes]):
+    """(offsets uint64 [n], total bytes) of the frames laid end to end."""
+    lens = np.fromiter((len(d) for d in datas), dtype=np.uint64, count=len(datas))
+    offsets = np.zeros(len(datas), dtype=np.uint64)
+    np.cumsum(lens[:-1], out=offsets[1:])
+    return offsets, int(lens.sum())
+
+
+def plan_segments(datas: Sequence[bytes], geom, offsets: Optional[np.ndarray] = None, cap_sets: int = 4,
+                  cap_segments: Optional[int] = None) -> SegmentPlan:
+    """Cut ``datas`` (frames of geometry ``geom``) into segments for the device entropy stage.  ``offsets``: where each frame
+    sits in the byte buffer the segments index (default: end to end)."""
+    from . import _lib
+    lib = _lib.load()
+    n = len(datas)
+    if offsets is None:
+        offsets, total = pack_offsets(datas)
+    else:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        total = int(max(int(o) + len(d) for o, d in zip(offsets, datas)))
+    ptrs = (C.c_char_p * n)(*datas)
+    lens = (C.c_size_t * n)(*[len(d) for d in datas])
+    route = np.empty(n, dtype=np.int32)
+    frames = np.empty(n, dtype=FRAME_DTYPE)
+    quant = np.empty((n, 192), dtype=np.uint16)
+    out5 = (C.c_size_t * 5)()
+    if cap_segments is None:
+        # frames of one geometry and restart interval have one segment count: the first frame's, times n, fits in one call
+        # (planning one frame twice is cheap; planning a chunk of restart-coded frames twice is not)
+        per = 1 if n == 1 else len(plan_segments(datas[:1], geom, offsets[:1], cap_sets=1, cap_segments=64).segments)
+        cap_segments = max(64, (per + 1) * n)
+    while True:
+        sets = np.empty((cap_sets, TABLE_SET_BYTES), dtype=np.uint8)
+        segs = np.empty(cap_segments, dtype=SEGMENT_DTYPE)
+        rc = lib.tstar_jpeg_plan_segments(ptrs, lens, offsets.ctypes.data, n, *geom, route.ctypes.data, frames.ctypes.data,
+                                          quant.ctypes.data, sets.ctypes.data, cap_sets, segs.ctypes.data, cap_segments, out5)
+        if rc != 4:
+            break
+        cap_sets, cap_segments = max(cap_sets, int(out5[0])), max(cap_segments, int(out5[1]))
+    _lib.check(rc, "tstar_jpeg_plan_segments")
+    assert (int(out5[2]), int(out5[3]), int(out5[4])) == (TABLE_SET_BYTES, SEGMENT_DTYPE.itemsize, FRAME_DTYPE.itemsize)
+    return SegmentPlan(route, frames, quant, sets[:int(out5[0])], segs[:int(out5[1])], offsets, total)
+
+
+def entropy_segments_host(buf: np.ndarray, plan: SegmentPlan, geom, coef: Optional[np.ndarray] = None):
+    """The device kernel's decode core on the CPU over ``buf`` (uint8, the frames at plan.offsets) -> (coef int16
+    [n, blocks * 64], seg_status int32 [n_segments])."""
+    from . import _lib
+    n, nseg = len(plan.route), len(plan.segments)
+    blocks, _ = _sizes(geom)
+    if coef is None:
+        coef = np.empty((n, blocks * 64), dtype=np.int16)
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size >= n * blocks * 64
+    assert buf.dtype == np.uint8 and buf.flags.c_contiguous and buf.size >= plan.total_bytes
+    status = np.full(nseg, -1, dtype=np.int32)
+    if nseg:
+        _lib.check(_lib.load().tstar_jpeg_entropy_segments_host(
+            buf.ctypes.data, plan.total_bytes, plan.segments.ctypes.data, plan.table_sets.ctypes.data, len(plan.table_sets),
+            plan.frames.ctypes.data, n, nseg, *geom, coef.ctypes.data, status.ctypes.data), "tstar_jpeg_entropy_segments_host")
+    return coef, status
+
+
+def device_entropy_take(lens: Sequence[int], byte_budget: int = 1 << 30) -> int:
+    """How many of a chunk's frames (compressed sizes ``lens``, in order) go up together: whole files are uploaded, metadata
+    included, and a segment addresses the upload with 32 bits, so a chunk stops before ``byte_budget`` bytes; never below 1."""
+    total = 0
+    for k, n in enumerate(lens):
+        total += int(n)
+        if k and total > byte_budget:
+            return k
+    return max(1, len(lens))
+
+
+def _round16(x: int) -> int:
+    return (x + 15) & ~15
+
+
+class DeviceBatch:
+    """One chunk's upload for the device entropy stage: the compressed bytes, then (16-byte aligned) the quant rows, the frame
+    records, the segments and the table sets, in ONE buffer so that one copy carries everything."""
+
+    def __init__(self, datas: Sequence[bytes], geom):
+        self.offsets, self.total = pack_offsets(datas)
+        self.plan = plan_segments(datas, geom, self.offsets)
+        p = self.plan
+        self.parts = {}
+        at = _round16(self.total)
+        for name, arr in (("quant", p.quant), ("frames", p.frames), ("segments", p.segments), ("table_sets", p.table_sets)):
+            self.parts[name] = (at, arr.nbytes)
+            at = _round16(at + arr.nbytes)
+        self.nbytes = at
+        self.datas = datas
+
+    def fill(self, host: np.ndarray) -> None:
+        """Write the upload into ``host`` (uint8, at least nbytes)."""
+        for o, d in zip(self.offsets, self.datas):
+            host[int(o):int(o) + len(d)] = np.frombuffer(d, dtype=np.uint8)
+        p = self.plan
+        for name, arr in (("quant", p.quant), ("frames", p.frames), ("segments", p.segments), ("table_sets", p.table_sets)):
+            at, nb = self.parts[name]
+            host[at:at + nb] = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+
+    def launch(self, d_buf, d_coef, d_seg_status, geom, stream: int) -> None:
+        """Entropy-decode on the device: d_buf holds what fill() wrote; d_coef int16 [>= n, blocks * 64]."""
+        from . import _lib
+        p = self.plan
+        base = d_buf.data_ptr()
+        _lib.check(_lib.load().tstar_jpeg_entropy_device(
+            base, self.total, base + self.parts["segments"][0], base + self.parts["table_sets"][0], len(p.table_sets),
+            base + self.parts["frames"][0], len(p.route), len(p.segments), *geom, d_coef.data_ptr(), d_seg_status.data_ptr(), stream),
+            "tstar_jpeg_entropy_device")
+
+
 def _pillow_rgb(data: bytes, label: str) -> np.ndarray:
     import io
     from PIL import Image
@@ -333,8 +494,12 @@ def wanted_frames(n_frames: int, fps: float):
     return [int(sec * fps) for sec in range(int(n_frames / fps))]
 
 
-def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None, threads: int = 0):
-    """Decode the wanted frames of ``src`` into a FrameStore (RGB u8 [N,H,W,3] on ``device``)."""
+def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None, threads: int = 0, entropy: Optional[str] = None):
+    """Decode the wanted frames of ``src`` into a FrameStore (RGB u8 [N,H,W,3] on ``device``).  ``entropy``: "host" (the
+    default; TSTAR_JPEG_ENTROPY when absent) or "device", where the Huffman decode runs on the GPU too and the store's
+    ``entropy_stats`` says how many frames each side entropy-decoded.  The device mode works on larger chunks (a frame without
+    restart markers is one lane): next to the store it holds up to 512 MiB of coefficients plus half as much of planes on the
+    device while loading, against two times 64 frames' worth in host mode (``device_entropy_chunk``; ``chunk`` lowers both)."""
     import torch
     from . import _lib
     from .video import FrameStore
@@ -343,6 +508,9 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
     if not want:
         raise ValueError(f"Cannot open video file: {src.name} (shorter than one second)")
     on_gpu = not str(device).startswith("cpu")
+    if entropy == "device" and not on_gpu:
+        raise ValueError("load_jpeg: entropy='device' needs a GPU store (device='cpu' was asked for)")
+    dev_entropy = entropy_mode(entropy) == "device" and on_gpu       # TSTAR_JPEG_ENTROPY=device leaves a CPU store on the host path
 
     # the first wanted frame fixes the picture size; the first frame the kernels cover fixes the device geometry
     first = src.read(want[0])
@@ -356,6 +524,7 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
     n_sec = len(want)
     store = torch.empty((n_sec, H, W, 3), dtype=torch.uint8, device=device)
     stats = {"device": 0, "host": 0, "pillow": 0}
+    estats = {"device": 0, "host": 0}
     geom = None
     bufs = None
     side = torch.cuda.Stream(device=device) if on_gpu else None
@@ -366,7 +535,14 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
         c = chunk if chunk else max(1, min(64, (48 << 20) // (blocks * 128)))
         c = min(c, n_sec)
         b = {"chunk": c, "blocks": blocks}
-        if on_gpu:
+        if dev_entropy:
+            c = b["chunk"] = device_entropy_chunk(blocks, n_sec, chunk)
+            b["pinned"] = [None, None]                  # uploads (grown on demand); statuses come back into "status"
+            b["status"] = [None, None]
+            b["d_buf"] = None
+            b["d_coef"] = torch.empty((c, blocks * 64), dtype=torch.int16, device=device)
+            b["planes"] = torch.empty((c, plane_bytes), dtype=torch.uint8, device=device)
+        elif on_gpu:
             b["coef"] = [torch.empty((c, blocks * 64), dtype=torch.int16).pin_memory() for _ in range(2)]
             b["quant"] = [torch.empty((c, 192), dtype=torch.int16).pin_memory() for _ in range(2)]
             b["d_coef"] = [torch.empty((c, blocks * 64), dtype=torch.int16, device=device) for _ in range(2)]
@@ -376,6 +552,81 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
             b["coef"] = [torch.empty((c, blocks * 64), dtype=torch.int16)]
             b["quant"] = [torch.empty((c, 192), dtype=torch.int16)]
         return b
+
+    def fallback_rgb(data, label, status, message=None):
+        """A frame the host entropy stage did not return OK for: ValueError when it is broken or of another size, else what
+        Pillow decodes (uncovered, or covered sampling other than the batch's: exact, on the host)."""
+        if status == MALFORMED:
+            if message is None:
+                one_c = np.empty((1, bufs["blocks"] * 64), dtype=np.int16)
+                _, message = entropy_batch([data], geom, one_c, np.empty((1, 192), dtype=np.uint16), 1)
+            raise ValueError(f"Cannot open video file: {label} ({message.split(': ', 2)[-1]})")
+        if status == GEOMETRY:
+            _, inf, _ = probe(data)
+            if (inf[0], inf[1]) != (W, H):
+                raise ValueError(f"Cannot open video file: {label} is {inf[0]}x{inf[1]}, the first frame is {W}x{H}")
+        arr = _pillow_rgb(data, label)
+        if arr.shape != (H, W, 3):
+            raise ValueError(f"Cannot open video file: {label} is {arr.shape[1]}x{arr.shape[0]}, the first frame is {W}x{H}")
+        return arr
+
+    pending = []                                        # device entropy: chunks launched whose statuses are not read yet
+
+    def submit_device(s0, idx, datas, b):
+        """Upload, entropy-decode and reconstruct one chunk on the side stream; the statuses are read in finish_device."""
+        n = len(idx)
+        batch = DeviceBatch(datas, geom)
+        nseg = len(batch.plan.segments)
+        if done[b] is not None:
+            done[b].synchronize()                         # this pinned buffer's previous copy has left
+        if bufs["pinned"][b] is None or bufs["pinned"][b].numel() < batch.nbytes:
+            bufs["pinned"][b] = torch.empty(batch.nbytes + batch.nbytes // 4, dtype=torch.uint8).pin_memory()
+        if bufs["status"][b] is None or bufs["status"][b].numel() < nseg:
+            bufs["status"][b] = torch.empty(nseg + nseg // 4 + 64, dtype=torch.int32).pin_memory()
+        batch.fill(bufs["pinned"][b].numpy())
+        with torch.cuda.stream(side):
+            if bufs["d_buf"] is None or bufs["d_buf"].numel() < batch.nbytes:
+                # in order on the side stream, so one device buffer serves every chunk (allocated under that stream: a
+                # replaced one is not handed out again before the work queued on it is done)
+                bufs["d_buf"] = torch.empty(batch.nbytes + batch.nbytes // 4, dtype=torch.uint8, device=device)
+            d_buf = bufs["d_buf"]
+            d_buf[:batch.nbytes].copy_(bufs["pinned"][b][:batch.nbytes], non_blocking=True)
+            if nseg:
+                d_status = torch.empty(nseg, dtype=torch.int32, device=device)
+                batch.launch(d_buf, bufs["d_coef"], d_status, geom, side.cuda_stream)
+                bufs["status"][b][:nseg].copy_(d_status, non_blocking=True)
+                # host-routed and refused frames reconstruct from cleared coefficients; finish_device overwrites their slots
+                _lib.check(lib.tstar_jpeg_reconstruct(bufs["d_coef"].data_ptr(), d_buf.data_ptr() + batch.parts["quant"][0], n, *geom,
+                                                      bufs["planes"].data_ptr(), store[s0:s0 + n].data_ptr(), side.cuda_stream),
+                           "tstar_jpeg_reconstruct")
+            done[b] = torch.cuda.Event(blocking=True)            # the wait in finish_device sleeps: the CPU is what this mode saves
+            done[b].record(side)
+        pending.append((s0, idx, datas, b, batch))
+
+    def finish_device():
+        """Read one launched chunk's statuses; every frame the device did not return OK for goes through the host decoder,
+        whose verdict stands: its coefficients are reconstructed on the device, or the frame is Pillow's / an error."""
+        s0, idx, datas, b, batch = pending.pop(0)
+        done[b].synchronize()
+        nseg = len(batch.plan.segments)
+        fstat = batch.plan.frame_status(bufs["status"][b][:nseg].numpy())
+        redo = [int(j) for j in np.nonzero(fstat)[0]]
+        for j in redo:
+            coef1 = torch.empty((1, bufs["blocks"] * 64), dtype=torch.int16)
+            quant1 = torch.empty((1, 192), dtype=torch.int16)
+            st1, msg = entropy_batch([datas[j]], geom, coef1.numpy(), quant1.numpy().view(np.uint16), 1)
+            estats["host"] += 1
+            with torch.cuda.stream(side):
+                if st1[0] == OK:
+                    dc, dq = coef1.to(device), quant1.to(device)
+                    _lib.check(lib.tstar_jpeg_reconstruct(dc.data_ptr(), dq.data_ptr(), 1, *geom, bufs["planes"].data_ptr(),
+                                                          store[s0 + j:s0 + j + 1].data_ptr(), side.cuda_stream), "tstar_jpeg_reconstruct")
+                    stats["device"] += 1
+                else:
+                    store[s0 + j].copy_(torch.from_numpy(fallback_rgb(datas[j], src.label(idx[j]), int(st1[0]), msg)))
+                    stats["pillow"] += 1
+        stats["device"] += len(idx) - len(redo)
+        estats["device"] += len(idx) - len(redo)
 
     s0, ci = 0, 0
     step = chunk if chunk else None
@@ -404,27 +655,23 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
             idx = want[s0:s0 + step]
             n = len(idx)
             b = ci & 1 if on_gpu else 0
+            if dev_entropy:
+                datas = [first if (s0 + j == 0) else src.read(fi) for j, fi in enumerate(idx)]
+                n = device_entropy_take([len(d) for d in datas])
+                idx, datas = idx[:n], datas[:n]
+                submit_device(s0, idx, datas, b)          # the host plans the next chunk while this one runs
+                if len(pending) > 1:
+                    finish_device()
+                s0 += n
+                ci += 1
+                continue
             if on_gpu and done[b] is not None:
                 done[b].synchronize()                     # the pinned buffers' previous copy has left
             datas = [first if (s0 + j == 0) else src.read(fi) for j, fi in enumerate(idx)]
             coef, quant = bufs["coef"][b], bufs["quant"][b]
             status, _ = entropy_batch(datas, geom, coef.numpy(), quant.numpy().view(np.uint16), threads)
-            fallback = []
-            for j in np.nonzero(status)[0]:
-                j = int(j)
-                label = src.label(idx[j])
-                if status[j] == MALFORMED:
-                    one_c = np.empty((1, bufs["blocks"] * 64), dtype=np.int16)
-                    _, m = entropy_batch([datas[j]], geom, one_c, np.empty((1, 192), dtype=np.uint16), 1)
-                    raise ValueError(f"Cannot open video file: {label} ({m.split(': ', 2)[-1]})")
-                if status[j] == GEOMETRY:
-                    _, inf, _ = probe(datas[j])
-                    if (inf[0], inf[1]) != (W, H):
-                        raise ValueError(f"Cannot open video file: {label} is {inf[0]}x{inf[1]}, the first frame is {W}x{H}")
-                arr = _pillow_rgb(datas[j], label)          # uncovered, or covered sampling other than the batch's: exact, on the host
-                if arr.shape != (H, W, 3):
-                    raise ValueError(f"Cannot open video file: {label} is {arr.shape[1]}x{arr.shape[0]}, the first frame is {W}x{H}")
-                fallback.append((j, arr))
+            fallback = [(int(j), fallback_rgb(datas[int(j)], src.label(idx[int(j)]), int(status[int(j)]))) for j in np.nonzero(status)[0]]
+            estats["host"] += n
             if on_gpu:
                 with torch.cuda.stream(side):
                     bufs["d_coef"][b][:n].copy_(coef[:n], non_blocking=True)
@@ -446,6 +693,8 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
             stats["pillow"] += len(fallback)
             s0 += n
             ci += 1
+        while pending:
+            finish_device()
     finally:
         # also on the way out with an error: the side stream may still be writing the previous chunk into the store, the
         # planes and the staged coefficients, and the allocator must not hand those blocks out before it is done
@@ -453,4 +702,5 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
             side.synchronize()
     st = FrameStore(store, src.fps, src.n_frames, name=src.name)
     st.decode_stats = stats
+    st.entropy_stats = estats
     return st

@@ -83,6 +83,7 @@ class FrameStore:
                                     else round(frames.shape[0] * self.raw_fps))
         self.name = name
         self.decode_stats = None      # JPEG sources: {"device": n, "host": n, "pillow": n} frames decoded by each path
+        self.entropy_stats = None     # JPEG sources: {"device": n, "host": n} frames run through each side's entropy decoder
 
     @property
     def num_seconds(self) -> int:
@@ -339,11 +340,12 @@ def load_pillow_sequence(path: str, device: str = "cuda", chunk: int = 64) -> Fr
 _SYN = re.compile(r"^synthetic://")
 
 
-def open_video(video, device: str = "cuda", fps: Optional[float] = None) -> FrameStore:
+def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_entropy: Optional[str] = None) -> FrameStore:
     """``video``: a FrameStore, a ``synthetic://n=..,h=..,w=..,seed=..,fps=..`` URL, a folder of .jpg / .jpeg frames or a
     list of JPEG paths / bytes (``fps`` frames per second, default 1), a .mjpeg / .mjpg stream (``fps`` default 25), a
     Motion-JPEG .avi, or another file path (.y4m, the Pillow sequences; else decoded at native rate through decord, else
-    cv2; both absent -> ValueError like the reference's ``Cannot open video file`` at interface_searcher.py:61-62)."""
+    cv2; both absent -> ValueError like the reference's ``Cannot open video file`` at interface_searcher.py:61-62).
+    ``jpeg_entropy``: where JPEG sources are entropy-decoded, "host" (default; TSTAR_JPEG_ENTROPY when absent) or "device"."""
     if isinstance(video, FrameStore):
         return video
     other_codec = None
@@ -355,7 +357,7 @@ def open_video(video, device: str = "cuda", fps: Optional[float] = None) -> Fram
             src, other_codec = None, e
         if src is not None:
             try:
-                return jpeg.load_jpeg(src, device)
+                return jpeg.load_jpeg(src, device, entropy=jpeg_entropy)
             finally:
                 src.close()
     if fps is not None:
