@@ -450,6 +450,42 @@ int tstar_jpeg_entropy_device(const uint8_t* d_bytes, size_t total_bytes, const 
 int tstar_jpeg_entropy_segments_host(const uint8_t* bytes, size_t total_bytes, const void* segments, const void* table_sets,
                                      int n_sets, const void* frames, int n_frames, int n_segments, int W, int H, int ncomp,
                                      int hs, int vs, int16_t* coef, int32_t* seg_status);
+/* The split path: the same result for frames WITHOUT restart markers at many lanes per scan (self-synchronising parallel
+ * Huffman decoding: Weissenberger & Schmidt, ICPP 2018).  A segment of at least min_split_bytes bytes (0: none, which is
+ * tstar_jpeg_entropy_device's work exactly) is cut into sub-sequences of sub_bytes bytes, one lane each.  A decoder state is
+ * the bit position, the block within the MCU, the zigzag index and the AC energy of the open block.
+ *   rounds   round 0 starts every sub-sequence from a blank state at its own byte boundary (behind the 00 when that byte is the
+ *            00 of an FF 00 pair), round r from the exit state its predecessor recorded in round r - 1; the first sub-sequence
+ *            of a segment always starts at the segment start.  Nothing is stored but exit states, block counts and DC sums.  A
+ *            segment has converged in the first round that changes none of its exits; after round max_rounds a segment that
+ *            has not is abandoned.
+ *   scan     per segment, exclusive, over (blocks completed, DC sums): first block and predictors of every sub-sequence.
+ *   write    converged segments: one lane per sub-sequence stores coefficients under every check of the one-lane decoder.
+ *            Every other segment (shorter than min_split_bytes, abandoned): one lane per segment, as before.
+ *   redo     a cut segment whose write pass reports anything but OK is decoded again by one lane, and that status stands; were
+ *            it OK the segment reports 2 (uncovered), which never happens.  Coefficients of a frame whose status is not 0 are
+ *            unspecified and must not be read: the caller runs such a frame through the host decoder.
+ * d_seg_info i32 [n_segments]: 0 one lane, r > 0 cut and converged in round r, -1 cut and abandoned.  d_seg_status and d_coef
+ * are tstar_jpeg_entropy_device's, value for value.  TSTAR_JPEG_SUB_BYTES_MIN is the smallest legal sub_bytes (a symbol with
+ * its magnitude bits is at most 27 bits; a state that lies behind a whole sub-sequence passes through it unchanged);
+ * sub_bytes is a multiple of 4, max_rounds in 1 .. TSTAR_JPEG_SPLIT_MAX_ROUNDS.  The workspace is caller memory, 8-byte
+ * aligned, of the size the query returns (0: bad arguments; no HIP work; it depends on the byte count, not on the records).
+ * The launcher queues max_rounds + 5 launches (none of the rounds when min_split_bytes is 0) on the stream and never synchronises: order between the phases comes from the
+ * kernel boundaries, no lane waits on another workgroup, every loop is bounded by the bits of its sub-sequence plus one
+ * symbol, reads stay inside the segment's byte range and stores inside the frame's coefficient region and the workspace.
+ * Refuses bad arguments before any launch.  The host mirror takes the same arguments in host memory, runs the same core in
+ * the same round order and gives the same coefficients, statuses and seg_info. */
+#define TSTAR_JPEG_SUB_BYTES_MIN 8
+#define TSTAR_JPEG_SPLIT_MAX_ROUNDS 65536
+size_t tstar_jpeg_split_workspace_bytes(size_t total_bytes, int n_segments, int sub_bytes);
+int tstar_jpeg_entropy_split_device(const uint8_t* d_bytes, size_t total_bytes, const void* d_segments, const void* d_table_sets,
+                                    int n_sets, const void* d_frames, int n_frames, int n_segments, int W, int H, int ncomp, int hs,
+                                    int vs, int sub_bytes, int min_split_bytes, int max_rounds, void* d_workspace,
+                                    size_t workspace_bytes, int16_t* d_coef, int32_t* d_seg_status, int32_t* d_seg_info, void* stream);
+int tstar_jpeg_entropy_split_host(const uint8_t* bytes, size_t total_bytes, const void* segments, const void* table_sets, int n_sets,
+                                  const void* frames, int n_frames, int n_segments, int W, int H, int ncomp, int hs, int vs,
+                                  int sub_bytes, int min_split_bytes, int max_rounds, void* workspace, size_t workspace_bytes,
+                                  int16_t* coef, int32_t* seg_status, int32_t* seg_info);
 /* Native-resolution RGB u8 [n,H,W,3] of NV12 frames (the keyframes pop_frames hands back, :379-380). */
 int tstar_nv12_to_rgb(const uint8_t* d_video, int N, int H, int W, const int32_t* d_frame_idx, int n,
                       uint8_t* d_out, void* stream);

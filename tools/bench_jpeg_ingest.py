@@ -14,7 +14,8 @@ events), with the kernels' bytes/s against the achievable-HBM figure of the micr
 
   python tools/bench_jpeg_ingest.py --out profiles/jpeg_ingest_measure          # writes .md and .json
   python tools/bench_jpeg_ingest.py --entropy device                            # the same, with the entropy stage on the GPU
-  python tools/bench_jpeg_ingest.py --entropy compare                           # host against device entropy -> profiles/jpeg_device_entropy_measure
+  python tools/bench_jpeg_ingest.py --entropy compare                           # host against device entropy, the split path on and
+                                                                                # off (TSTAR_JPEG_SPLIT_BYTES=0) -> profiles/jpeg_split_entropy_measure
   rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_jpeg_ingest.py --kernels-only     # kernel times, a run of its own
 
 No GPU -> error (a CPU timing says nothing about this).
@@ -36,6 +37,7 @@ sys.path.insert(0, ROOT)
 
 HBM_ACHIEVABLE = 6.3e12          # B/s, MI355X_MICROARCH.md (achievable, not the 8 TB/s peak)
 CASES = [("360x640", 3600, 360, 640), ("1080x1920", 600, 1080, 1920)]
+MODES = ("host", "device", "device, split off")          # --entropy compare
 
 
 def write_avi(path, frames, W, H, rate):
@@ -229,7 +231,37 @@ def device_entropy_figures(path, reps=10):
         e1.record()
         torch.cuda.synchronize()
         per_chunk = e0.elapsed_time(e1) * 1e-3 / reps
-        return dict(chunk=n, frames=n_all, segments_per_frame=segs / n_all, host_routed=host_routed, table_sets_first_chunk=len(first.plan.table_sets),
+        # the split launcher on the same resident chunk: the defaults, then a sweep of each argument around them
+        nseg = len(first.plan.segments)
+        d_info = torch.empty(nseg, dtype=torch.int32, device="cuda")
+
+        def split_launch(sub, min_split, rounds, reps):
+            ws = torch.empty(jpeg.split_workspace_bytes(first.total, nseg, sub) // 8, dtype=torch.int64, device="cuda")
+            run = lambda: first.launch_split(d_buf, d_coef, d_status, d_info, ws, geom, _lib.stream_ptr(), sub, min_split, rounds)  # noqa: E731
+            run()
+            torch.cuda.synchronize()
+            assert not d_status.cpu().numpy().any()
+            info = d_info.cpu().numpy()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                run()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) * 1e-3 / reps, info
+
+        sub0, min0, rounds0 = jpeg.SPLIT_SUB_BYTES, jpeg.SPLIT_MIN_BYTES, jpeg.SPLIT_MAX_ROUNDS
+        split_s, info = split_launch(sub0, min0, rounds0, reps)
+        hist = {str(int(k)): int(v) for k, v in zip(*np.unique(info, return_counts=True))}
+        sweep = []
+        for sub, min_split, rounds in ([(sb, min0, rounds0) for sb in (32, 64, 128, 256, 512)] + [(sub0, ms, rounds0) for ms in (256, 4096, 16384)]
+                                       + [(sub0, min0, r) for r in (8, 16, 96)]):
+            t, inf = split_launch(sub, min_split, rounds, 3)
+            sweep.append(dict(sub_bytes=sub, min_split_bytes=min_split, max_rounds=rounds, s_per_chunk=t, split=int((inf != 0).sum()),
+                              abandoned=int((inf < 0).sum()), rounds_max=int(inf.max(initial=0))))
+        return dict(split_kernel_s_per_chunk=split_s, split_kernel_s_all_frames=split_s / n * n_all, split_rounds_histogram=hist,
+                    split_sweep=sweep, split_defaults=dict(sub_bytes=sub0, min_split_bytes=min0, max_rounds=rounds0),
+                    chunk=n, frames=n_all, segments_per_frame=segs / n_all, host_routed=host_routed, table_sets_first_chunk=len(first.plan.table_sets),
                     h2d_bytes_per_frame=up / n_all, h2d_bytes_per_frame_host_mode=blocks * 128 + 384, plan_wall_s=t_plan, plan_cpu_s=c_plan,
                     entropy_kernel_s_per_chunk=per_chunk, entropy_kernel_s_all_frames=per_chunk / n * n_all, launches_timed=reps)
     finally:
@@ -237,7 +269,9 @@ def device_entropy_figures(path, reps=10):
 
 
 def compare_entropy(args):
-    """Host against device entropy through open_video, alternating in one process; the host mode is the baseline."""
+    """Host against device entropy through open_video, the device mode with the split path on (the default) and off
+    (TSTAR_JPEG_SPLIT_BYTES=0: one lane per segment, the device mode before the split path), alternating in one process; the host
+    mode is the baseline."""
     import torch
     from tstar_amd.video import open_video
     props = torch.cuda.get_device_properties(0)
@@ -249,21 +283,32 @@ def compare_entropy(args):
             path = os.path.join(tmp, f"case{k}.avi")
             jpeg_bytes = make_avi(path, n, H, W, restart_blocks=restart)
             print(f"[{name}] {n} frames, {jpeg_bytes / n / 1024:.1f} KiB/frame", flush=True)
-            case = {"frames": n, "jpeg_bytes_per_frame": jpeg_bytes / n, "host": [], "device": []}
-            a, b = open_video(path, jpeg_entropy="host"), open_video(path, jpeg_entropy="device")        # warm-up of both
-            case["same_bytes"] = bool(torch.equal(a.frames, b.frames))
+            case = {"frames": n, "jpeg_bytes_per_frame": jpeg_bytes / n, "host": [], "device": [], "device, split off": []}
+
+            def open_mode(mode):
+                os.environ.pop("TSTAR_JPEG_SPLIT_BYTES", None)
+                if mode == "device, split off":
+                    os.environ["TSTAR_JPEG_SPLIT_BYTES"] = "0"
+                try:
+                    return open_video(path, jpeg_entropy="host" if mode == "host" else "device")
+                finally:
+                    os.environ.pop("TSTAR_JPEG_SPLIT_BYTES", None)
+
+            a, b, b0 = (open_mode(m) for m in MODES)                                                   # warm-up of all
+            case["same_bytes"] = bool(torch.equal(a.frames, b.frames) and torch.equal(a.frames, b0.frames))
             case["entropy_stats"] = b.entropy_stats
-            del a, b
+            case["entropy_split_stats"] = b.entropy_split_stats
+            del a, b, b0
             for _ in range(args.repeats):
-                for mode in ("host", "device"):
-                    st, w, c = timed(lambda: open_video(path, jpeg_entropy=mode))
+                for mode in MODES:
+                    st, w, c = timed(lambda: open_mode(mode))
                     case[mode].append({"wall_s": w, "cpu_s": c, "frames_per_s": n / w})
                     del st
-            for mode in ("host", "device"):
+            for mode in MODES:
                 case[mode + "_median"] = {m: float(np.median([r[m] for r in case[mode]])) for m in ("wall_s", "cpu_s", "frames_per_s")}
             case["figures"] = device_entropy_figures(path)
             res["cases"][name] = case
-            print(json.dumps({name: {k2: case[k2] for k2 in ("host_median", "device_median", "same_bytes", "figures")}}), flush=True)
+            print(json.dumps({name: {k2: case[k2] for k2 in ("host_median", "device_median", "device, split off_median", "same_bytes", "entropy_split_stats", "figures")}}), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out + ".json", "w") as f:
         json.dump(res, f, indent=1)
@@ -271,20 +316,22 @@ def compare_entropy(args):
         f.write(f"# JPEG ingest: entropy stage on the host against on the device ({res['board']}, {res['cpus_allowed']} CPUs allowed)\n\n"
                 "`tools/bench_jpeg_ingest.py --entropy compare`; Motion-JPEG AVI -> resident store through `open_video`, 4:2:0, quality 85, "
                 f"synthetic video, every frame wanted. Medians of {args.repeats} runs of each mode, alternating in one process after one warm-up of "
-                "each; the host mode is the behaviour before the device stage existed and is the baseline. CPU-seconds = `time.process_time` "
+                "each; the host mode is the behaviour before the device stage existed and is the baseline; `device, split off` is the device "
+                "mode with `TSTAR_JPEG_SPLIT_BYTES=0` (one lane per segment). CPU-seconds = `time.process_time` "
                 "(all threads).\n\n| case | entropy on | wall s | frames/s | host CPU-s | H2D bytes/frame | segments/frame |\n|---|---|---|---|---|---|---|\n")
         for name, c in res["cases"].items():
             g = c["figures"]
-            for mode in ("host", "device"):
+            for mode in MODES:
                 m = c[mode + "_median"]
                 h2d = g["h2d_bytes_per_frame_host_mode"] if mode == "host" else g["h2d_bytes_per_frame"]
                 f.write(f"| {name} x {c['frames']} | {mode} | {m['wall_s']:.3f} | {m['frames_per_s']:.0f} | {m['cpu_s']:.2f} | {h2d:.0f} | "
                         f"{g['segments_per_frame']:.0f} |\n")
         f.write("\nAll runs:\n\n")
         for name, c in res["cases"].items():
-            for mode in ("host", "device"):
+            for mode in MODES:
                 f.write(f"- {name}, {mode}: wall " + ", ".join(f"{r['wall_s']:.3f}" for r in c[mode]) + " s; CPU "
-                        + ", ".join(f"{r['cpu_s']:.2f}" for r in c[mode]) + f" s; stores byte-equal: {c['same_bytes']}; {c['entropy_stats']}\n")
+                        + ", ".join(f"{r['cpu_s']:.2f}" for r in c[mode]) + f" s; stores byte-equal: {c['same_bytes']}; {c['entropy_stats']}; "
+                        f"split on: {c['entropy_split_stats']}\n")
         f.write("\n## The entropy kernel alone\n\n| case | frames per chunk | segments (lanes) per chunk | clear + kernel, one chunk s (HIP events) | "
                 "all frames s | planning on the host, all frames: wall s (CPU-s) |\n|---|---|---|---|---|---|\n")
         for name, c in res["cases"].items():
@@ -293,13 +340,28 @@ def compare_entropy(args):
                     f"{g['entropy_kernel_s_all_frames']:.3f} | {g['plan_wall_s']:.3f} ({g['plan_cpu_s']:.2f}) |\n")
         f.write("\nOne lane decodes one segment, so a file without restart markers gives one lane per frame; the kernel time is that of "
                 f"the slowest lane. The launch is timed over {next(iter(res['cases'].values()))['figures']['launches_timed']} repeats on a resident chunk.\n")
+        d = next(iter(res["cases"].values()))["figures"]["split_defaults"]
+        f.write(f"\n## The split launcher alone (sub_bytes {d['sub_bytes']}, min_split_bytes {d['min_split_bytes']}, max_rounds {d['max_rounds']})\n\n"
+                "The same resident chunk through `tstar_jpeg_entropy_split_device` (clear + every launch of the call, HIP events). seg_info "
+                "histogram of that chunk: `0` one lane, `r` converged in round r, `-1` abandoned.\n\n"
+                "| case | one chunk s | all frames s | one lane per segment, all frames s | seg_info: segments |\n|---|---|---|---|---|\n")
+        for name, c in res["cases"].items():
+            g = c["figures"]
+            hist = ", ".join(f"{k}: {v}" for k, v in sorted(g["split_rounds_histogram"].items(), key=lambda kv: int(kv[0])))
+            f.write(f"| {name} | {g['split_kernel_s_per_chunk']:.5f} | {g['split_kernel_s_all_frames']:.4f} | {g['entropy_kernel_s_all_frames']:.4f} | {hist} |\n")
+        f.write("\nSweep, one argument at a time around the defaults (3 launches each; s per chunk):\n\n| case | sub_bytes | min_split_bytes | "
+                "max_rounds | one chunk s | split | abandoned | rounds_max |\n|---|---|---|---|---|---|---|---|\n")
+        for name, c in res["cases"].items():
+            for r in c["figures"]["split_sweep"]:
+                f.write(f"| {name} | {r['sub_bytes']} | {r['min_split_bytes']} | {r['max_rounds']} | {r['s_per_chunk']:.5f} | {r['split']} | "
+                        f"{r['abandoned']} | {r['rounds_max']} |\n")
     print("wrote", args.out + ".md")
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="path stem of the .md / .json written (default: profiles/jpeg_ingest_measure, or "
-                                                "profiles/jpeg_device_entropy_measure with --entropy compare)")
+                                                "profiles/jpeg_split_entropy_measure with --entropy compare)")
     ap.add_argument("--entropy", choices=("host", "device", "compare"), default="host",
                     help="where the device path entropy-decodes; 'compare' measures both modes against each other instead of against Pillow")
     ap.add_argument("--repeats", type=int, default=3)
@@ -310,7 +372,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_jpeg_ingest needs an MI355X: a CPU timing says nothing about this path")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "jpeg_device_entropy_measure" if args.entropy == "compare" else "jpeg_ingest_measure")
+        args.out = os.path.join(ROOT, "profiles", "jpeg_split_entropy_measure" if args.entropy == "compare" else "jpeg_ingest_measure")
     if args.entropy == "compare":
         return compare_entropy(args)
     from tstar_amd import video

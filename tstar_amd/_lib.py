@@ -80,6 +80,9 @@ SIGNATURES = {
     "tstar_jpeg_plan_segments": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "tstar_jpeg_entropy_device": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tstar_jpeg_entropy_segments_host": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "tstar_jpeg_split_workspace_bytes": (_sz, [_sz, _i, _i]),
+    "tstar_jpeg_entropy_split_device": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "tstar_jpeg_entropy_split_host": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "tstar_searcher_create": (_i, [C.POINTER(_vp), _i, C.c_double, C.c_double]),
     "tstar_searcher_destroy": (_i, [_vp]),
     "tstar_searcher_apply_grid": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

@@ -1,7 +1,8 @@
 // Baseline JPEG entropy decode of one SEGMENT: a run of MCUs that starts at a byte boundary with zero DC predictors (one
 // restart interval, or a whole scan without DRI).  One core for both sides: g++ compiles this file as plain C++
-// (jpeg_host.cpp: jpeg_entropy_segments_host, the sanitizer checker), hipcc as __host__ __device__ (jpeg_entropy.hip: one
-// lane per segment).  Everything the decoder looks at lives in flat, pointer-free records (JpegTableSet, JpegSegment,
+// (jpeg_host.cpp: jpeg_entropy_segments_host, jpeg_entropy_split_host, the sanitizer checkers), hipcc as __host__ __device__
+// (jpeg_entropy.hip: one lane per segment; jpeg_entropy_split.hip: a long segment cut into sub-sequences, one lane each -- the
+// second half of this file).  Everything the decoder looks at lives in flat, pointer-free records (JpegTableSet, JpegSegment,
 // JpegFrameDesc) that may sit in host memory, global memory or LDS.
 //
 // This code parses untrusted bytes, on the device next to other people's work:
@@ -265,6 +266,353 @@ TSTAR_JPEG_HD inline int segment_table_set(const SegmentBatch& b, const JpegSegm
     const int32_t ts = b.frames[s.frame].table_set;
     if (ts < 0 || (uint32_t)ts >= b.n_sets) return -1;
     return ts;
+}
+
+// ------------------------------------------------------------------------------------------------ sub-sequences
+// A long segment is cut into SUB-SEQUENCES of sub_bytes bytes, one lane each (self-synchronising Huffman decoding:
+// Weissenberger & Schmidt, "Massively Parallel Huffman Decoding on GPUs", ICPP 2018).  A decoder STATE is where the next
+// symbol starts (byte offset in the batch's byte buffer and bit within that byte; the byte is never the 00 of an FF 00
+// pair), the block within the MCU j, the zigzag index k and the AC energy of the open block.  Sub-sequence i of a segment
+// decodes from an entry state to the first symbol that starts at or behind its byte limit and records that exit state;
+// started from a guess, it falls into step with the true symbol sequence after some symbols, so rounds in which every
+// sub-sequence starts from its predecessor's last exit reach the sequential decoder's states.
+//
+// walk_sub<false> (count form) writes no coefficient: it reports the exit state, the blocks completed and the sum of the DC
+// differences of each component (mod 2^32).  A bad code is no error there, only "no exit state".  It cannot check the DC
+// range or the energy of a block (both need the predictors) and does not try.
+// walk_sub<true> (write form) is the same walk from a TRUE entry state with the predictors and the block index in front of
+// it: it stores coefficients and applies every check of decode_segment, in decode_segment's order.  The DC of a block
+// opened in an earlier sub-sequence is the entry predictor of its component, so the energy check needs no second pass.
+// The sub-sequence in which the segment's last block completes checks the padding in front of the marker the way
+// decode_segment does; sub-sequences behind it have nothing to do.
+constexpr uint32_t kSubBytesMin = 8;           // TSTAR_JPEG_SUB_BYTES_MIN (include/tstar_hip.h)
+constexpr uint32_t kSubValid = 1u << 14;       // SubState::pk = bit | j << 3 | k << 7 | kSubValid
+
+struct SubState {
+    uint32_t pos, pk;
+    int64_t energy;
+};
+
+TSTAR_JPEG_HD inline bool sub_state_equal(const SubState& a, const SubState& b) { return a.pos == b.pos && a.pk == b.pk && a.energy == b.energy; }
+
+struct SubCount {
+    uint32_t blocks, dc0, dc1, dc2;
+};
+
+// BitReader that also knows where its unread bits sit in the raw bytes: ff has one bit per byte pushed, newest lowest, set
+// when that byte was an FF followed by its stuffed 00.
+struct SubReader {
+    BitReader br;
+    uint32_t ff;
+
+    // as BitReader::fill, byte for byte
+    TSTAR_JPEG_HD void fill() {
+        while (br.nbits <= 56) {
+            unsigned b = 0, stuffed = 0;
+            if (!br.at_marker) {
+                if (br.p >= br.end) {
+                    br.at_marker = true;
+                } else {
+                    const unsigned x = br.d[br.p];
+                    if (x != 0xFF) {
+                        b = x;
+                        ++br.p;
+                    } else if (br.p + 1 < br.end && br.d[br.p + 1] == 0x00) {
+                        b = 0xFF;
+                        stuffed = 1;
+                        br.p += 2;
+                    } else {
+                        br.at_marker = true;
+                    }
+                }
+            }
+            if (br.at_marker) br.fake += 8;
+            br.acc = (br.acc << 8) | b;
+            ff = (ff << 1) | stuffed;
+            br.nbits += 8;
+        }
+    }
+    // the next unread bit (no padding bit has been consumed: nbits >= fake): byte offset and bit within it
+    TSTAR_JPEG_HD void where(uint32_t* byte, uint32_t* bit) const {
+        const uint32_t real = (uint32_t)(br.nbits - br.fake), nb = (real + 7) >> 3, nf = (uint32_t)br.fake >> 3;
+        const uint32_t stuffed = (uint32_t)__builtin_popcount((ff >> nf) & ((1u << nb) - 1));       // nb <= 8, nf <= 8
+        *byte = br.p - nb - stuffed;
+        *bit = (8 - (real & 7)) & 7;
+    }
+};
+
+// Where sub-sequence i > 0 of a segment starts when nothing is known: its own first byte, or the byte behind it when that
+// first byte is the 00 of an FF 00 pair (in entropy data an FF is always followed by 00).  at < end.
+TSTAR_JPEG_HD inline SubState sub_blank_state(const uint8_t* bytes, uint32_t begin, uint32_t at) {
+    SubState s;
+    s.pos = (at > begin && bytes[at - 1] == 0xFF && bytes[at] == 0x00) ? at + 1 : at;
+    s.pk = kSubValid;
+    s.energy = 0;
+    return s;
+}
+
+// What a write-form walk knows beyond the entry state.
+struct SubWrite {
+    uint32_t first_mcu, seg_blocks;            // the segment's first MCU and its blocks (n_mcu * blocks of an MCU)
+    uint32_t first_block;                      // blocks of the segment completed in front of this sub-sequence
+    int pred0, pred1, pred2;
+    bool last_sub, last_seg;                   // the segment's last sub-sequence; the frame's last segment
+    int16_t* coef;                             // the FRAME's region
+};
+
+// One sub-sequence: symbols from `in` (a valid state with begin <= pos <= end) up to the first one that starts at or
+// behind byte `lim` (<= end).  Reads stay inside [begin, end); the loop is bounded by the bits of [in.pos, lim) plus one
+// symbol (write form of the segment's last sub-sequence: lim = end).
+//   count form: *out = the exit state (pk == 0: none), *cnt the blocks completed and DC sums; returns JPEG_OK.
+//   write form: returns the status; *out and *cnt are not written.
+template <bool kWrite, class Tables>
+TSTAR_JPEG_HD inline int walk_sub(const uint8_t* bytes, uint32_t end, uint32_t lim, Tables T, const JpegSegGeom& g, const SubState& in,
+                                  const SubWrite* w, SubState* out, SubCount* cnt) {
+    const uint32_t luma = g.hs * g.vs, bpm = g.ncomp == 3 ? luma + 2 : 1;
+    uint32_t j = (in.pk >> 3) & 15;
+    int k = (int)((in.pk >> 7) & 127);
+    int64_t energy = in.energy;                                                 // AC terms of the open block
+    if (kWrite) {
+        if (w->first_block >= w->seg_blocks) return JPEG_OK;                    // behind the segment's last block: nothing to do
+        if (j != w->first_block % bpm) return JPEG_MALFORMED;                   // never with a true state
+    }
+    if (j >= bpm || k > 63) {                                                   // never with a state this code recorded
+        if (!kWrite) { out->pos = 0; out->pk = 0; out->energy = 0; cnt->blocks = cnt->dc0 = cnt->dc1 = cnt->dc2 = 0; }
+        return JPEG_MALFORMED;
+    }
+    SubReader sr;
+    sr.br.d = bytes; sr.br.p = in.pos; sr.br.end = end; sr.br.acc = 0; sr.br.nbits = 0; sr.br.fake = 0; sr.br.at_marker = false;
+    sr.ff = 0;
+    BitReader& br = sr.br;
+    sr.fill();
+    bool bad = !br.skip((int)(in.pk & 7));                                      // the bits of the first byte in front of the state
+    uint32_t left = 0, mx = 0, my = 0;
+    int pred0 = 0, pred1 = 0, pred2 = 0;
+    if (kWrite) {
+        left = w->seg_blocks - w->first_block;
+        const uint32_t m = w->first_mcu + w->first_block / bpm;
+        mx = m % g.mcux; my = m / g.mcux;
+        pred0 = w->pred0; pred1 = w->pred1; pred2 = w->pred2;
+        // the sequential decoder never carries a predictor outside the DC range: an earlier sub-sequence has refused the segment
+        if (pred0 < -2048 || pred0 > 2047 || pred1 < -2048 || pred1 > 2047 || pred2 < -2048 || pred2 > 2047) return JPEG_MALFORMED;
+    }
+    uint32_t blocks = 0, dc0 = 0, dc1 = 0, dc2 = 0;
+    const bool to_end = kWrite && w->last_sub;                                  // runs into the end of the data, as decode_segment does
+    uint64_t budget = (in.pos <= lim ? 8ull * (lim - in.pos) : 0) + 1;     // a state already behind lim is its own exit
+    int status = JPEG_OK;
+    bool have_exit = false;
+    uint32_t xb = 0, xbit = 0;
+    while (!bad && budget != 0) {
+        --budget;
+        sr.fill();
+        if (!to_end) {
+            sr.where(&xb, &xbit);
+            if (xb >= lim) { have_exit = true; break; }
+        }
+        const uint32_t c = j < luma ? 0u : j - luma + 1;
+        uint64_t blk = 0;
+        if (kWrite) {
+            const uint32_t u = c == 0 ? j % g.hs : 0u, v = c == 0 ? j / g.hs : 0u;
+            const uint32_t nh = c == 0 ? g.hs : 1u, nv = c == 0 ? g.vs : 1u;
+            const uint32_t bw = c == 0 ? g.bw0 : g.bw1;
+            const uint32_t base = c == 0 ? 0u : (c == 1 ? g.off1 : g.off2);
+            blk = ((uint64_t)base + (uint64_t)(my * nv + v) * bw + (mx * nh + u)) * 64;
+            if (blk + 64 > g.per_frame) { status = JPEG_MALFORMED; break; }    // the store bound
+        }
+        const bool dc = k == 0;
+        const int sym = huff_decode(br, &T->h[2 * c + (dc ? 0 : 1)]);
+        if (sym < 0) { status = JPEG_MALFORMED; break; }
+        const int r = dc ? 0 : sym >> 4, s = dc ? sym : sym & 15;
+        if (s > (dc ? 11 : 10)) { status = JPEG_MALFORMED; break; }
+        bool done = false;
+        if (!dc && s == 0) {
+            if (r == 15) {
+                k += 16;
+                if (k > 64) { status = JPEG_MALFORMED; break; }
+                done = k == 64;
+            } else if (r != 0) {
+                status = JPEG_MALFORMED;
+                break;
+            } else {
+                done = true;
+            }
+        } else {
+            k += r;
+            if (k > 63) { status = JPEG_MALFORMED; break; }
+            int val = 0;
+            if (s) {
+                const int bits = (int)br.peek(s);
+                if (!br.skip(s)) { status = JPEG_MALFORMED; break; }
+                val = bits < (1 << (s - 1)) ? bits - (1 << s) + 1 : bits;
+            }
+            int nat = 0;
+            if (dc) {
+                dc0 += c == 0 ? (uint32_t)val : 0u;
+                dc1 += c == 1 ? (uint32_t)val : 0u;
+                dc2 += c == 2 ? (uint32_t)val : 0u;
+                if (kWrite) {
+                    val += c == 0 ? pred0 : (c == 1 ? pred1 : pred2);
+                    if (val < -2048 || val > 2047) { status = JPEG_MALFORMED; break; }
+                    pred0 = c == 0 ? val : pred0;
+                    pred1 = c == 1 ? val : pred1;
+                    pred2 = c == 2 ? val : pred2;
+                }
+                energy = 0;
+            } else {
+                nat = T->zigzag[k] & 63;
+                const int q = (int)T->quant[64 * c + (uint32_t)nat];
+                energy += (int64_t)(val * q) * (val * q);
+            }
+            if (kWrite) w->coef[blk + (uint32_t)nat] = (int16_t)val;
+            ++k;
+            done = k == 64;
+        }
+        if (done) {
+            if (kWrite) {
+                const int d = c == 0 ? pred0 : (c == 1 ? pred1 : pred2);       // this block's DC, wherever the block was opened
+                const int q = (int)T->quant[64 * c];
+                if (energy + (int64_t)(d * q) * (d * q) > T->limit[c]) { status = JPEG_UNCOVERED; break; }
+            }
+            k = 0;
+            energy = 0;
+            ++blocks;
+            if (++j == bpm) {
+                j = 0;
+                if (kWrite && ++mx == g.mcux) { mx = 0; ++my; }
+            }
+            if (kWrite && --left == 0) break;
+        }
+    }
+    if (!kWrite) {
+        cnt->blocks = blocks; cnt->dc0 = dc0; cnt->dc1 = dc1; cnt->dc2 = dc2;
+        out->pos = 0; out->pk = 0; out->energy = 0;
+        if (have_exit) {
+            out->pos = xb;
+            out->pk = xbit | j << 3 | (uint32_t)k << 7 | kSubValid;
+            out->energy = energy;
+        }
+        return JPEG_OK;
+    }
+    if (bad) return JPEG_MALFORMED;
+    if (status != JPEG_OK) return status;
+    if (left != 0) return w->last_sub ? JPEG_MALFORMED : (have_exit ? JPEG_OK : JPEG_MALFORMED);
+    br.fill();
+    if (!br.at_marker || br.nbits - br.fake >= 8) return w->last_seg ? JPEG_UNCOVERED : JPEG_MALFORMED;
+    return JPEG_OK;
+}
+
+// The caller-sized workspace of a split call, structure of arrays over `cap` sub-sequences and n segments:
+//   per sub-sequence  exit state, two copies (round r reads copy (r - 1) & 1 and writes copy r & 1): pos, pk, energy;
+//                     changed in that round, two copies; blocks, dc0..2 (count form); first block, pred0..2 (scan)
+//   per segment       sub-sequences (0: not split), first sub-sequence, the last round that changed an exit;
+//   one word          sub-sequences in all.
+struct SplitWs {
+    int64_t* energy[2];
+    uint32_t *pos[2], *pk[2], *chg[2];
+    uint32_t *blocks, *dc0, *dc1, *dc2, *first_block, *pred0, *pred1, *pred2;
+    uint32_t *n_sub, *sub_first, *last_changed, *total;
+    uint32_t cap;
+};
+
+// cap: no list of disjoint segments inside total_bytes has more sub-sequences
+TSTAR_JPEG_HD inline uint64_t split_cap(uint64_t total_bytes, uint64_t n_segments, uint32_t sub_bytes) {
+    return total_bytes / sub_bytes + n_segments;
+}
+TSTAR_JPEG_HD inline uint64_t split_ws_bytes(uint64_t cap, uint64_t n_segments) { return (cap * (16 + 14 * 4) + n_segments * 12 + 16 + 7) & ~7ull; }
+
+inline SplitWs split_ws_carve(void* base, uint64_t cap, uint64_t n_segments) {
+    SplitWs w;
+    int64_t* e = (int64_t*)base;                                                // base is 8-byte aligned
+    w.energy[0] = e; w.energy[1] = e + cap;
+    uint32_t* u = (uint32_t*)(e + 2 * cap);
+    uint32_t** lanes[14] = {&w.pos[0], &w.pos[1], &w.pk[0], &w.pk[1], &w.chg[0], &w.chg[1], &w.blocks, &w.dc0, &w.dc1, &w.dc2,
+                            &w.first_block, &w.pred0, &w.pred1, &w.pred2};
+    for (int i = 0; i < 14; ++i) { *lanes[i] = u; u += cap; }
+    w.n_sub = u; u += n_segments;
+    w.sub_first = u; u += n_segments;
+    w.last_changed = u; u += n_segments;
+    w.total = u;
+    w.cap = (uint32_t)cap;
+    return w;
+}
+
+// Is segment s cut into sub-sequences, and into how many?  0: one lane.
+TSTAR_JPEG_HD inline uint32_t split_n_sub(const SegmentBatch& b, const JpegSegment& s, uint32_t sub_bytes, uint32_t min_split_bytes) {
+    if (min_split_bytes == 0 || segment_table_set(b, s) < 0) return 0;
+    const uint32_t len = s.end - s.begin;
+    if (len < min_split_bytes) return 0;
+    return (len - 1) / sub_bytes + 1;
+}
+
+// Sub-sequence `lane` (i of segment `si`) in round `round`: round 0 starts from nothing, a later round from the exit its
+// predecessor recorded in the round before, and only when that exit changed then.  Returns whether its own exit changed.
+template <class Tables>
+TSTAR_JPEG_HD inline bool split_round_lane(const SegmentBatch& b, const SplitWs& w, uint32_t sub_bytes, uint32_t round, uint32_t si,
+                                           uint32_t lane, Tables T) {
+    const JpegSegment s = b.segments[si];
+    const uint32_t i = lane - w.sub_first[si], n = w.n_sub[si];
+    const uint32_t in = (round + 1) & 1, o = round & 1;
+    if (round != 0 && (i == 0 || w.chg[in][lane - 1] == 0)) {                  // same entry as last round: same exit
+        w.pos[o][lane] = w.pos[in][lane]; w.pk[o][lane] = w.pk[in][lane]; w.energy[o][lane] = w.energy[in][lane];
+        w.chg[o][lane] = 0;
+        return false;
+    }
+    const uint32_t at = s.begin + i * sub_bytes;
+    SubState e;
+    if (i == 0) {
+        e.pos = s.begin; e.pk = kSubValid; e.energy = 0;
+    } else if (round == 0) {
+        e = sub_blank_state(b.bytes, s.begin, at);
+    } else {
+        e.pos = w.pos[in][lane - 1]; e.pk = w.pk[in][lane - 1]; e.energy = w.energy[in][lane - 1];
+        if (!(e.pk & kSubValid) || e.pos < s.begin || e.pos > s.end) e = sub_blank_state(b.bytes, s.begin, at);
+    }
+    const uint32_t lim = i + 1 == n ? s.end : at + sub_bytes;
+    SubState x;
+    SubCount c;
+    walk_sub<false>(b.bytes, s.end, lim, T, b.g, e, (const SubWrite*)nullptr, &x, &c);
+    bool changed = true;
+    if (round != 0) {
+        SubState old;
+        old.pos = w.pos[in][lane]; old.pk = w.pk[in][lane]; old.energy = w.energy[in][lane];
+        changed = !sub_state_equal(old, x);
+    }
+    w.pos[o][lane] = x.pos; w.pk[o][lane] = x.pk; w.energy[o][lane] = x.energy;
+    w.chg[o][lane] = changed ? 1u : 0u;
+    w.blocks[lane] = c.blocks; w.dc0[lane] = c.dc0; w.dc1[lane] = c.dc1; w.dc2[lane] = c.dc2;
+    if (changed && round != 0) w.last_changed[si] = round;                     // every writer of a round stores the same value
+    return changed;
+}
+
+// seg_info of a split segment after rounds 0 .. max_rounds: the first round that changed none of its exits, or -1
+TSTAR_JPEG_HD inline int32_t split_seg_info(const SplitWs& w, uint32_t si, uint32_t max_rounds) {
+    if (w.n_sub[si] == 0) return 0;
+    const uint32_t r = w.last_changed[si] + 1;
+    return r <= max_rounds ? (int32_t)r : -1;
+}
+
+// Sub-sequence `lane` of converged segment si in the write pass -> its status
+template <class Tables>
+TSTAR_JPEG_HD inline int split_write_lane(const SegmentBatch& b, const SplitWs& w, uint32_t sub_bytes, uint32_t max_rounds, uint32_t si,
+                                          uint32_t lane, Tables T) {
+    const JpegSegment s = b.segments[si];
+    const uint32_t i = lane - w.sub_first[si], n = w.n_sub[si], f = max_rounds & 1;
+    const uint32_t luma = b.g.hs * b.g.vs, bpm = b.g.ncomp == 3 ? luma + 2 : 1;
+    SubState e;
+    if (i == 0) {
+        e.pos = s.begin; e.pk = kSubValid; e.energy = 0;
+    } else {
+        e.pos = w.pos[f][lane - 1]; e.pk = w.pk[f][lane - 1]; e.energy = w.energy[f][lane - 1];
+    }
+    SubWrite sw;
+    sw.first_mcu = s.first_mcu; sw.seg_blocks = s.n_mcu * bpm; sw.first_block = w.first_block[lane];
+    sw.pred0 = (int)w.pred0[lane]; sw.pred1 = (int)w.pred1[lane]; sw.pred2 = (int)w.pred2[lane];
+    sw.last_sub = i + 1 == n; sw.last_seg = s.last != 0;
+    sw.coef = b.coef + (size_t)s.frame * b.g.per_frame;
+    if (sw.first_block >= sw.seg_blocks) return JPEG_OK;
+    if (!(e.pk & kSubValid) || e.pos < s.begin || e.pos > s.end) return JPEG_MALFORMED;   // the predecessor met a bad code
+    const uint32_t lim = sw.last_sub ? s.end : s.begin + (i + 1) * sub_bytes;
+    return walk_sub<true>(b.bytes, s.end, lim, T, b.g, e, &sw, (SubState*)nullptr, (SubCount*)nullptr);
 }
 
 }  // namespace jpegcore

@@ -620,6 +620,120 @@ bool jpeg_entropy_segments_host(const uint8_t* bytes, size_t total_bytes, const 
     return true;
 }
 
+size_t jpeg_split_workspace_bytes(size_t total_bytes, int n_segments, int sub_bytes) {
+    if (total_bytes == 0 || total_bytes >= 0xffffffffull || n_segments <= 0 || sub_bytes < (int)jpegcore::kSubBytesMin || sub_bytes % 4 != 0)
+        return 0;
+    const uint64_t cap = jpegcore::split_cap(total_bytes, (uint64_t)n_segments, (uint32_t)sub_bytes);
+    if (cap >= 0x7fffffffull - 1024) return 0;
+    return (size_t)jpegcore::split_ws_bytes(cap, (uint64_t)n_segments);
+}
+
+bool jpeg_split_args_ok(size_t total_bytes, int n_segments, int sub_bytes, int min_split_bytes, int max_rounds, const void* workspace,
+                        size_t workspace_bytes) {
+    const size_t need = jpeg_split_workspace_bytes(total_bytes, n_segments, sub_bytes);
+    return need != 0 && min_split_bytes >= 0 && max_rounds >= 1 && max_rounds <= kJpegSplitMaxRounds && workspace &&
+           (uintptr_t)workspace % 8 == 0 && workspace_bytes >= need;
+}
+
+bool jpeg_entropy_split_host(const uint8_t* bytes, size_t total_bytes, const JpegSegment* segments, const JpegTableSet* tables,
+                             int n_sets, const JpegFrameDesc* frames, int n_frames, int n_segments, const JpegGeom& g, int sub_bytes,
+                             int min_split_bytes, int max_rounds, void* workspace, size_t workspace_bytes, int16_t* coef,
+                             int32_t* seg_status, int32_t* seg_info) {
+    if (!bytes || !segments || !tables || !frames || !coef || !seg_status || !seg_info || n_sets <= 0 || n_frames <= 0 || n_segments <= 0 ||
+        total_bytes == 0 || total_bytes >= 0xffffffffull || !g.valid() ||
+        !jpeg_split_args_ok(total_bytes, n_segments, sub_bytes, min_split_bytes, max_rounds, workspace, workspace_bytes))
+        return false;
+    using namespace jpegcore;
+    SegmentBatch b;
+    b.bytes = bytes; b.total_bytes = total_bytes; b.segments = segments; b.tables = tables; b.frames = frames;
+    b.n_sets = (uint32_t)n_sets; b.n_frames = (uint32_t)n_frames; b.n_segments = (uint32_t)n_segments;
+    b.g = jpeg_seg_geom(g);
+    b.coef = coef; b.seg_status = seg_status;
+    const uint32_t sub = (uint32_t)sub_bytes, rounds = (uint32_t)max_rounds, nseg = (uint32_t)n_segments;
+    const uint64_t cap = split_cap(total_bytes, nseg, sub);
+    const SplitWs w = split_ws_carve(workspace, cap, nseg);
+    memset(coef, 0, (size_t)n_frames * b.g.per_frame * sizeof(int16_t));
+    // the layout: which segments are cut, and where their sub-sequences sit in the workspace
+    uint64_t at = 0;
+    *w.total = 0;
+    for (uint32_t si = 0; si < nseg; ++si) {
+        const uint32_t n = split_n_sub(b, segments[si], sub, (uint32_t)min_split_bytes);
+        const bool fits = n != 0 && at + n <= cap;
+        w.n_sub[si] = fits ? n : 0;
+        w.sub_first[si] = (uint32_t)(at < 0xffffffffull ? at : 0xffffffffull);
+        w.last_changed[si] = 0;
+        at += n;
+        if (fits) *w.total = (uint32_t)at;
+    }
+    // (a) the rounds, in the kernels' order: every sub-sequence of round r reads what round r - 1 recorded
+    // Only sub-sequences a round can touch are visited: the successor of one whose exit changed in the round before (it walks
+    // again), and one whose own exit changed in one of the two rounds before (its other copy and flag are brought up to
+    // date).  For every other one the round is a copy of equal words, so the result is the kernels' word for word.
+    {
+        const uint32_t total = *w.total;
+        std::vector<uint32_t> seg_of(total), stamp(total, 0xffffffffu), prev, prev2, cur, todo;
+        for (uint32_t si = 0; si < nseg; ++si)
+            for (uint32_t i = 0; i < w.n_sub[si]; ++i) seg_of[w.sub_first[si] + i] = si;
+        for (uint32_t lane = 0; lane < total; ++lane) prev.push_back(lane);     // round 0 changes every exit
+        for (uint32_t r = 0; r <= rounds && !(prev.empty() && prev2.empty()); ++r) {
+            todo.clear();
+            auto want = [&](uint32_t lane) {
+                if (stamp[lane] != r) { stamp[lane] = r; todo.push_back(lane); }
+            };
+            if (r == 0) {
+                todo = prev;
+            } else {
+                for (uint32_t lane : prev) {
+                    want(lane);
+                    const uint32_t si = seg_of[lane];
+                    if (lane + 1 < w.sub_first[si] + w.n_sub[si]) want(lane + 1);
+                }
+                for (uint32_t lane : prev2) want(lane);
+            }
+            cur.clear();
+            for (uint32_t lane : todo) {
+                const uint32_t si = seg_of[lane];
+                if (split_round_lane(b, w, sub, r, si, lane, tables + segment_table_set(b, segments[si]))) cur.push_back(lane);
+            }
+            if (r != 0) prev2.swap(prev);
+            prev.swap(cur);
+        }
+    }
+    // (b) first block and predictors of every sub-sequence of a converged segment
+    for (uint32_t si = 0; si < nseg; ++si) {
+        seg_info[si] = split_seg_info(w, si, rounds);
+        if (seg_info[si] <= 0) continue;
+        seg_status[si] = JPEG_OK;
+        uint64_t blocks = 0;
+        uint32_t d0 = 0, d1 = 0, d2 = 0;
+        for (uint32_t lane = w.sub_first[si]; lane < w.sub_first[si] + w.n_sub[si]; ++lane) {
+            w.first_block[lane] = (uint32_t)(blocks < 0xffffffffull ? blocks : 0xffffffffull);
+            w.pred0[lane] = d0; w.pred1[lane] = d1; w.pred2[lane] = d2;
+            blocks += w.blocks[lane]; d0 += w.dc0[lane]; d1 += w.dc1[lane]; d2 += w.dc2[lane];
+        }
+    }
+    // (c) the write pass of the converged segments
+    for (uint32_t si = 0; si < nseg; ++si) {
+        if (seg_info[si] <= 0) continue;
+        for (uint32_t i = 0; i < w.n_sub[si]; ++i)
+            if (split_write_lane(b, w, sub, rounds, si, w.sub_first[si] + i, tables + segment_table_set(b, segments[si])) != JPEG_OK)
+                seg_status[si] = JPEG_MALFORMED;
+    }
+    // (c) every other segment and (d) the refused ones again, by one lane: that status stands
+    for (uint32_t si = 0; si < nseg; ++si) {
+        const bool redo = seg_info[si] > 0;
+        if (redo && seg_status[si] == JPEG_OK) continue;
+        const JpegSegment s = segments[si];
+        const int ts = segment_table_set(b, s);
+        int st = ts < 0 ? (int)JPEG_MALFORMED
+                        : decode_segment(bytes, s.begin, s.end, tables + ts, b.g, s.first_mcu, s.n_mcu, s.last != 0,
+                                         coef + (size_t)s.frame * b.g.per_frame);
+        if (redo && st == JPEG_OK) st = JPEG_UNCOVERED;                         // the write pass refused what one lane accepts: never
+        seg_status[si] = st;
+    }
+    return true;
+}
+
 void jpeg_reconstruct_host(const JpegGeom& g, const int16_t* coef, const uint16_t* quant, uint8_t* scratch, uint8_t* rgb) {
     using namespace jpegmath;
     const uint8_t* plane[3] = {nullptr, nullptr, nullptr};
@@ -792,6 +906,27 @@ int tstar_jpeg_entropy_segments_host(const uint8_t* bytes, size_t total_bytes, c
         !jpeg_entropy_segments_host(bytes, total_bytes, (const JpegSegment*)segments, (const JpegTableSet*)table_sets, n_sets,
                                     (const JpegFrameDesc*)frames, n_frames, n_segments, g, coef, seg_status)) {
         set_error("tstar_jpeg_entropy_segments_host: null argument, empty batch or unsupported geometry");
+        return 1;
+    }
+    return 0;
+}
+
+size_t tstar_jpeg_split_workspace_bytes(size_t total_bytes, int n_segments, int sub_bytes) {
+    return jpeg_split_workspace_bytes(total_bytes, n_segments, sub_bytes);
+}
+
+int tstar_jpeg_entropy_split_host(const uint8_t* bytes, size_t total_bytes, const void* segments, const void* table_sets, int n_sets,
+                                  const void* frames, int n_frames, int n_segments, int W, int H, int ncomp, int hs, int vs,
+                                  int sub_bytes, int min_split_bytes, int max_rounds, void* workspace, size_t workspace_bytes,
+                                  int16_t* coef, int32_t* seg_status, int32_t* seg_info) {
+    JpegGeom g;
+    if (!geom_from_args(W, H, ncomp, hs, vs, &g) ||
+        !jpeg_entropy_split_host(bytes, total_bytes, (const JpegSegment*)segments, (const JpegTableSet*)table_sets, n_sets,
+                                 (const JpegFrameDesc*)frames, n_frames, n_segments, g, sub_bytes, min_split_bytes, max_rounds, workspace,
+                                 workspace_bytes, coef, seg_status, seg_info)) {
+        set_error("tstar_jpeg_entropy_split_host: null argument, empty batch, unsupported geometry, sub_bytes below " +
+                  std::to_string(jpegcore::kSubBytesMin) + " or no multiple of 4, max_rounds outside 1.." +
+                  std::to_string(kJpegSplitMaxRounds) + ", or a workspace that is misaligned or too small");
         return 1;
     }
     return 0;

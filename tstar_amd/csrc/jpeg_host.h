@@ -80,6 +80,23 @@ bool jpeg_entropy_segments_host(const uint8_t* bytes, size_t total_bytes, const 
                                 int n_sets, const JpegFrameDesc* frames, int n_frames, int n_segments, const JpegGeom& g,
                                 int16_t* coef, int32_t* seg_status);
 
+// The split path (jpeg_entropy_core.h "sub-sequences"): segments of at least min_split_bytes bytes (0: none) are cut into
+// sub-sequences of sub_bytes bytes that are decoded side by side; rounds 0 .. max_rounds bring their entry states to the
+// sequential decoder's, a scan hands out block indices and DC predictors, a write pass stores the coefficients.  Every
+// other segment, and every cut one the write pass does not return OK for, is decoded by decode_segment, whose status
+// stands (coefficients of a frame that is not OK are never read: the host decoder replaces the frame).  seg_info [n_segments]:
+// 0 one lane, r > 0 cut and converged in round r, -1 cut and abandoned after max_rounds.  The workspace is caller memory of
+// jpeg_split_workspace_bytes bytes (0: bad arguments), 8-byte aligned.  This is the CPU mirror of the device launcher:
+// the same core in the same round order.
+constexpr int kJpegSplitMaxRounds = 65536;        // TSTAR_JPEG_SPLIT_MAX_ROUNDS (include/tstar_hip.h)
+size_t jpeg_split_workspace_bytes(size_t total_bytes, int n_segments, int sub_bytes);
+bool jpeg_split_args_ok(size_t total_bytes, int n_segments, int sub_bytes, int min_split_bytes, int max_rounds, const void* workspace,
+                        size_t workspace_bytes);
+bool jpeg_entropy_split_host(const uint8_t* bytes, size_t total_bytes, const JpegSegment* segments, const JpegTableSet* tables,
+                             int n_sets, const JpegFrameDesc* frames, int n_frames, int n_segments, const JpegGeom& g, int sub_bytes,
+                             int min_split_bytes, int max_rounds, void* workspace, size_t workspace_bytes, int16_t* coef,
+                             int32_t* seg_status, int32_t* seg_info);
+
 // Scalar reference of the device stage: coefficients + tables -> RGB u8 [H][W][3].  scratch: g.plane_bytes() bytes.
 void jpeg_reconstruct_host(const JpegGeom& g, const int16_t* coef, const uint16_t* quant, uint8_t* scratch, uint8_t* rgb);
 

@@ -11,6 +11,9 @@ are decoded by Pillow and copied in; ``FrameStore.decode_stats`` says how many f
 ``entropy="device"`` moves the entropy stage to the GPU as well (tstar_jpeg_plan_segments cuts the frames into restart
 segments on the host, tstar_jpeg_entropy_device decodes one segment per lane): the compressed bytes go up instead of the
 coefficients, and a frame the device does not vouch for is run through the host decoder again, whose verdict stands.
+A frame without restart markers is one segment; the device mode cuts segments of at least TSTAR_JPEG_SPLIT_BYTES bytes into
+sub-sequences of SPLIT_SUB_BYTES bytes, one lane each (tstar_jpeg_entropy_split_device: self-synchronising parallel Huffman
+decoding), and ``FrameStore.entropy_split_stats`` says how many segments went that way.
 """
 from __future__ import annotations
 
@@ -316,6 +319,39 @@ def entropy_mode(entropy: Optional[str] = None) -> str:
     return mode
 
 
+# The split path of the device mode (include/tstar_hip.h, tstar_jpeg_entropy_split_device).  Defaults from the sweep in
+# profiles/jpeg_split_entropy_measure.md; rounds behind the one in which a segment converges only copy states, so a generous
+# max_rounds is cheap, while ONE abandoned 1080p frame costs a launch as much as the unsplit path did.
+SPLIT_SUB_BYTES = 128          # bytes of a sub-sequence (one lane)
+SPLIT_MAX_ROUNDS = 48          # a segment that has not converged by then is decoded by one lane
+SPLIT_MIN_BYTES = 4096         # default of TSTAR_JPEG_SPLIT_BYTES: shorter segments stay one lane (a restart interval of an MCU row)
+SUB_BYTES_MIN = 8              # TSTAR_JPEG_SUB_BYTES_MIN
+
+
+def split_min_bytes() -> int:
+    """min_split_bytes of the device mode: TSTAR_JPEG_SPLIT_BYTES when set (0: never split, the device mode as it was before the
+    split path, for A/B runs), else SPLIT_MIN_BYTES."""
+    v = os.environ.get("TSTAR_JPEG_SPLIT_BYTES")
+    if v is None or v == "":
+        return SPLIT_MIN_BYTES
+    try:
+        n = int(v)
+    except ValueError:
+        n = -1
+    if n < 0 or n >= 1 << 31:
+        raise ValueError(f"TSTAR_JPEG_SPLIT_BYTES={v!r}: expected a byte count >= 0 (0: never split)")
+    return n
+
+
+def split_workspace_bytes(total_bytes: int, n_segments: int, sub_bytes: int = SPLIT_SUB_BYTES) -> int:
+    """Bytes of workspace a split call over ``n_segments`` segments inside ``total_bytes`` bytes needs (no HIP work)."""
+    from . import _lib
+    n = int(_lib.load().tstar_jpeg_split_workspace_bytes(total_bytes, n_segments, sub_bytes))
+    if n == 0:
+        raise ValueError(f"split_workspace_bytes: bad arguments (total_bytes={total_bytes}, n_segments={n_segments}, sub_bytes={sub_bytes})")
+    return n
+
+
 def device_entropy_chunk(blocks: int, n_frames: int, chunk: Optional[int] = None, coef_budget: int = 512 << 20,
                          max_frames: int = 1024) -> int:
     """Frames per chunk of the device entropy path.  A frame without restart markers is one lane, so a launch wants as many
@@ -406,6 +442,28 @@ def entropy_segments_host(buf: np.ndarray, plan: SegmentPlan, geom, coef: Option
     return coef, status
 
 
+def entropy_split_host(buf: np.ndarray, plan: SegmentPlan, geom, sub_bytes: int = SPLIT_SUB_BYTES, min_split_bytes: int = SPLIT_MIN_BYTES,
+                       max_rounds: int = SPLIT_MAX_ROUNDS, coef: Optional[np.ndarray] = None):
+    """The split launcher's CPU mirror (same core, same round order) over ``buf`` -> (coef int16 [n, blocks * 64], seg_status
+    int32 [n_segments], seg_info int32 [n_segments]: 0 one lane, r > 0 converged in round r, -1 abandoned)."""
+    from . import _lib
+    n, nseg = len(plan.route), len(plan.segments)
+    blocks, _ = _sizes(geom)
+    if coef is None:
+        coef = np.empty((n, blocks * 64), dtype=np.int16)
+    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size >= n * blocks * 64
+    assert buf.dtype == np.uint8 and buf.flags.c_contiguous and buf.size >= plan.total_bytes
+    status = np.full(nseg, -1, dtype=np.int32)
+    info = np.full(nseg, -9, dtype=np.int32)
+    if nseg:
+        ws = np.empty(split_workspace_bytes(plan.total_bytes, nseg, sub_bytes) // 8 + 1, dtype=np.uint64)
+        _lib.check(_lib.load().tstar_jpeg_entropy_split_host(
+            buf.ctypes.data, plan.total_bytes, plan.segments.ctypes.data, plan.table_sets.ctypes.data, len(plan.table_sets),
+            plan.frames.ctypes.data, n, nseg, *geom, sub_bytes, min_split_bytes, max_rounds, ws.ctypes.data, ws.nbytes,
+            coef.ctypes.data, status.ctypes.data, info.ctypes.data), "tstar_jpeg_entropy_split_host")
+    return coef, status, info
+
+
 def device_entropy_take(lens: Sequence[int], byte_budget: int = 1 << 30) -> int:
     """How many of a chunk's frames (compressed sizes ``lens``, in order) go up together: whole files are uploaded, metadata
     included, and a segment addresses the upload with 32 bits, so a chunk stops before ``byte_budget`` bytes; never below 1."""
@@ -457,6 +515,20 @@ class DeviceBatch:
             "tstar_jpeg_entropy_device")
 
 
+    def launch_split(self, d_buf, d_coef, d_seg_status, d_seg_info, d_workspace, geom, stream: int, sub_bytes: int = SPLIT_SUB_BYTES,
+                     min_split_bytes: int = SPLIT_MIN_BYTES, max_rounds: int = SPLIT_MAX_ROUNDS) -> None:
+        """launch() through the split path: d_seg_info int32 [>= n_segments]; d_workspace uint8, 8-byte aligned, at least
+        split_workspace_bytes(self.total, n_segments, sub_bytes)."""
+        from . import _lib
+        p = self.plan
+        base = d_buf.data_ptr()
+        _lib.check(_lib.load().tstar_jpeg_entropy_split_device(
+            base, self.total, base + self.parts["segments"][0], base + self.parts["table_sets"][0], len(p.table_sets),
+            base + self.parts["frames"][0], len(p.route), len(p.segments), *geom, sub_bytes, min_split_bytes, max_rounds,
+            d_workspace.data_ptr(), d_workspace.numel() * d_workspace.element_size(), d_coef.data_ptr(), d_seg_status.data_ptr(),
+            d_seg_info.data_ptr(), stream), "tstar_jpeg_entropy_split_device")
+
+
 def _pillow_rgb(data: bytes, label: str) -> np.ndarray:
     import io
     from PIL import Image
@@ -498,8 +570,12 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
     """Decode the wanted frames of ``src`` into a FrameStore (RGB u8 [N,H,W,3] on ``device``).  ``entropy``: "host" (the
     default; TSTAR_JPEG_ENTROPY when absent) or "device", where the Huffman decode runs on the GPU too and the store's
     ``entropy_stats`` says how many frames each side entropy-decoded.  The device mode works on larger chunks (a frame without
-    restart markers is one lane): next to the store it holds up to 512 MiB of coefficients plus half as much of planes on the
-    device while loading, against two times 64 frames' worth in host mode (``device_entropy_chunk``; ``chunk`` lowers both)."""
+    restart markers is one segment): next to the store it holds up to 512 MiB of coefficients plus half as much of planes on the
+    device while loading, against two times 64 frames' worth in host mode (``device_entropy_chunk``; ``chunk`` lowers both), and
+    72 bytes of workspace per SPLIT_SUB_BYTES compressed bytes of a chunk.  Segments of at least TSTAR_JPEG_SPLIT_BYTES bytes
+    (``split_min_bytes``; 0: none) are decoded by many lanes; ``entropy_split_stats`` counts the segments that were
+    (``split``), those of them given up after SPLIT_MAX_ROUNDS rounds and decoded by one lane (``abandoned``) and the most
+    rounds a segment took (``rounds_max``)."""
     import torch
     from . import _lib
     from .video import FrameStore
@@ -525,6 +601,8 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
     store = torch.empty((n_sec, H, W, 3), dtype=torch.uint8, device=device)
     stats = {"device": 0, "host": 0, "pillow": 0}
     estats = {"device": 0, "host": 0}
+    sstats = {"split": 0, "abandoned": 0, "rounds_max": 0}
+    min_split = split_min_bytes() if dev_entropy else 0
     geom = None
     bufs = None
     side = torch.cuda.Stream(device=device) if on_gpu else None
@@ -540,6 +618,7 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
             b["pinned"] = [None, None]                  # uploads (grown on demand); statuses come back into "status"
             b["status"] = [None, None]
             b["d_buf"] = None
+            b["d_ws"] = None
             b["d_coef"] = torch.empty((c, blocks * 64), dtype=torch.int16, device=device)
             b["planes"] = torch.empty((c, plane_bytes), dtype=torch.uint8, device=device)
         elif on_gpu:
@@ -581,8 +660,8 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
             done[b].synchronize()                         # this pinned buffer's previous copy has left
         if bufs["pinned"][b] is None or bufs["pinned"][b].numel() < batch.nbytes:
             bufs["pinned"][b] = torch.empty(batch.nbytes + batch.nbytes // 4, dtype=torch.uint8).pin_memory()
-        if bufs["status"][b] is None or bufs["status"][b].numel() < nseg:
-            bufs["status"][b] = torch.empty(nseg + nseg // 4 + 64, dtype=torch.int32).pin_memory()
+        if bufs["status"][b] is None or bufs["status"][b].numel() < 2 * nseg:       # statuses, then seg_info
+            bufs["status"][b] = torch.empty(2 * (nseg + nseg // 4 + 64), dtype=torch.int32).pin_memory()
         batch.fill(bufs["pinned"][b].numpy())
         with torch.cuda.stream(side):
             if bufs["d_buf"] is None or bufs["d_buf"].numel() < batch.nbytes:
@@ -592,9 +671,16 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
             d_buf = bufs["d_buf"]
             d_buf[:batch.nbytes].copy_(bufs["pinned"][b][:batch.nbytes], non_blocking=True)
             if nseg:
-                d_status = torch.empty(nseg, dtype=torch.int32, device=device)
-                batch.launch(d_buf, bufs["d_coef"], d_status, geom, side.cuda_stream)
-                bufs["status"][b][:nseg].copy_(d_status, non_blocking=True)
+                d_status = torch.empty(2 * nseg, dtype=torch.int32, device=device)
+                ws_bytes = split_workspace_bytes(batch.total, nseg)
+                if bufs["d_ws"] is None or bufs["d_ws"].numel() * 8 < ws_bytes:             # like d_buf: one, in order on the side stream
+                    bufs["d_ws"] = torch.empty((ws_bytes + ws_bytes // 4) // 8 + 1, dtype=torch.int64, device=device)
+                # the segment lengths are known here: a chunk without a long segment does not queue the rounds at all
+                seg = batch.plan.segments
+                longest = int((seg["end"].astype(np.int64) - seg["begin"]).max())
+                batch.launch_split(d_buf, bufs["d_coef"], d_status[:nseg], d_status[nseg:], bufs["d_ws"], geom, side.cuda_stream,
+                                   min_split_bytes=min_split if longest >= min_split else 0)
+                bufs["status"][b][:2 * nseg].copy_(d_status, non_blocking=True)
                 # host-routed and refused frames reconstruct from cleared coefficients; finish_device overwrites their slots
                 _lib.check(lib.tstar_jpeg_reconstruct(bufs["d_coef"].data_ptr(), d_buf.data_ptr() + batch.parts["quant"][0], n, *geom,
                                                       bufs["planes"].data_ptr(), store[s0:s0 + n].data_ptr(), side.cuda_stream),
@@ -610,6 +696,10 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
         done[b].synchronize()
         nseg = len(batch.plan.segments)
         fstat = batch.plan.frame_status(bufs["status"][b][:nseg].numpy())
+        info = bufs["status"][b][nseg:2 * nseg].numpy()
+        sstats["split"] += int((info != 0).sum())
+        sstats["abandoned"] += int((info < 0).sum())
+        sstats["rounds_max"] = max(sstats["rounds_max"], int(info.max(initial=0)))
         redo = [int(j) for j in np.nonzero(fstat)[0]]
         for j in redo:
             coef1 = torch.empty((1, bufs["blocks"] * 64), dtype=torch.int16)
@@ -703,4 +793,5 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
     st = FrameStore(store, src.fps, src.n_frames, name=src.name)
     st.decode_stats = stats
     st.entropy_stats = estats
+    st.entropy_split_stats = sstats
     return st

@@ -84,6 +84,7 @@ class FrameStore:
         self.name = name
         self.decode_stats = None      # JPEG sources: {"device": n, "host": n, "pillow": n} frames decoded by each path
         self.entropy_stats = None     # JPEG sources: {"device": n, "host": n} frames run through each side's entropy decoder
+        self.entropy_split_stats = None   # JPEG sources: {"split": n, "abandoned": n, "rounds_max": r} segments cut into sub-sequences
 
     @property
     def num_seconds(self) -> int:
