@@ -184,6 +184,43 @@ def test_never_split_and_one_round():
     assert info[0] == -1 and not seg_status.any() and np.array_equal(coef, want_c)
 
 
+def test_not_cut_kept_and_redone_segments_in_one_launch():
+    """The one-lane kernel's two modes side by side: 17x33 frames with min_split_bytes between their lengths, so that in ONE call
+    the short ones are not cut (seg_info 0: decoded by one lane), an intact long one converges and is kept (the one-lane kernel
+    skips it), and a long one with a corrupted byte converges, is refused by the write pass and decoded again by one lane,
+    whose status stands.  The corrupted byte is one after which the sequential decoder says UNCOVERED: the write pass leaves
+    MALFORMED for whatever it refuses, so only the redo can have written that status.  Everything equals the host mirror word
+    for word."""
+    from tstar_amd import jpeg
+    H, W = 17, 33
+    short = [JU.encode(JU.synthetic_picture(H, W), "420", 30), JU.encode(JU.noise_picture(H, W, seed=4), "420", 75, "restart")]
+    long = [JU.encode(JU.noise_picture(H, W, seed=s), "420", 95) for s in (5, 6)]
+    geom = jpeg.probe(long[0])[1]
+    s0 = JU.segments(long[1])[1]
+    broken = None
+    for p in range(s0 + (len(long[1]) - 2 - s0) // 2, len(long[1]) - 2):       # the first flip the sequential decoder calls UNCOVERED
+        if long[1][p - 1] == 0xFF or long[1][p] == 0xFF or long[1][p] ^ 0x10 == 0xFF:
+            continue                                                            # no new marker, no broken FF 00 pair: the plan stays
+        m = bytearray(long[1])
+        m[p] ^= 0x10
+        if SH.host_decode([bytes(m)], geom)[2][0] == jpeg.UNCOVERED:
+            broken = bytes(m)
+            break
+    assert broken is not None
+    datas = [short[0], long[0], short[1], broken]
+    want_c, _, want_s = SH.host_decode(datas, geom)
+    assert want_s[:3].tolist() == [jpeg.OK] * 3 and want_s[3] == jpeg.UNCOVERED != jpeg.MALFORMED
+    lens = SH.seg_lens(jpeg.plan_segments(datas, geom))
+    min_split = int(lens[[1, -1]].min())
+    assert lens[0] < min_split and lens[2:-1].max() < min_split
+    plan, coef, seg_status, info, _ = check_against_mirror(datas, geom, 8, min_split)
+    assert (plan.route == jpeg.ROUTE_DEVICE).all() and plan.frames["n_segments"].tolist()[::2] == [1, len(lens) - 3]
+    SH.check_info(plan, info, min_split)
+    assert info[0] == 0 and info[1] > 0 and info[-1] > 0 and not info[2:-1].any()
+    assert not seg_status[:-1].any() and seg_status[-1] == jpeg.UNCOVERED      # not cut, kept, not cut ... and the redo's status
+    assert np.array_equal(coef[:3], want_c[:3])
+
+
 def test_launcher_refuses_bad_arguments():
     import torch
     from tstar_amd import _lib, jpeg

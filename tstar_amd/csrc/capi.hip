@@ -1117,16 +1117,10 @@ int tstar_i420_to_nv12(const uint8_t* d_i420, int n, int H, int W, uint8_t* d_nv
 int tstar_jpeg_entropy_device(const uint8_t* d_bytes, size_t total_bytes, const void* d_segments, const void* d_table_sets,
                               int n_sets, const void* d_frames, int n_frames, int n_segments, int W, int H, int ncomp, int hs,
                               int vs, int16_t* d_coef, int32_t* d_seg_status, void* stream) {
-    TSTAR_REQUIRE(d_bytes && d_segments && d_table_sets && d_frames && d_coef && d_seg_status, "tstar_jpeg_entropy_device: null argument");
-    TSTAR_REQUIRE(n_sets > 0 && n_frames > 0 && n_segments > 0, "tstar_jpeg_entropy_device: empty batch");
-    const JpegGeom g{W, H, ncomp, hs, vs};
-    TSTAR_REQUIRE(g.valid(), "tstar_jpeg_entropy_device: unsupported geometry");
     jpegcore::SegmentBatch b;
-    b.bytes = d_bytes; b.total_bytes = total_bytes;
-    b.segments = (const JpegSegment*)d_segments; b.tables = (const JpegTableSet*)d_table_sets; b.frames = (const JpegFrameDesc*)d_frames;
-    b.n_sets = (uint32_t)n_sets; b.n_frames = (uint32_t)n_frames; b.n_segments = (uint32_t)n_segments;
-    b.g = jpeg_seg_geom(g);
-    b.coef = d_coef; b.seg_status = d_seg_status;
+    const char* bad = jpegcore::segment_batch(d_bytes, total_bytes, d_segments, d_table_sets, n_sets, d_frames, n_frames, n_segments,
+                                              JpegGeom{W, H, ncomp, hs, vs}, d_coef, d_seg_status, &b);
+    TSTAR_REQUIRE(!bad, std::string("tstar_jpeg_entropy_device: ") + bad);
     return jpeg_entropy_segments(b, (hipStream_t)stream);
 }
 
@@ -1134,17 +1128,11 @@ int tstar_jpeg_entropy_split_device(const uint8_t* d_bytes, size_t total_bytes, 
                                     int n_sets, const void* d_frames, int n_frames, int n_segments, int W, int H, int ncomp, int hs,
                                     int vs, int sub_bytes, int min_split_bytes, int max_rounds, void* d_workspace,
                                     size_t workspace_bytes, int16_t* d_coef, int32_t* d_seg_status, int32_t* d_seg_info, void* stream) {
-    TSTAR_REQUIRE(d_bytes && d_segments && d_table_sets && d_frames && d_coef && d_seg_status && d_seg_info && d_workspace,
-                  "tstar_jpeg_entropy_split_device: null argument");
-    TSTAR_REQUIRE(n_sets > 0 && n_frames > 0 && n_segments > 0, "tstar_jpeg_entropy_split_device: empty batch");
-    const JpegGeom g{W, H, ncomp, hs, vs};
-    TSTAR_REQUIRE(g.valid(), "tstar_jpeg_entropy_split_device: unsupported geometry");
+    TSTAR_REQUIRE(d_seg_info && d_workspace, "tstar_jpeg_entropy_split_device: null argument");
     jpegcore::SegmentBatch b;
-    b.bytes = d_bytes; b.total_bytes = total_bytes;
-    b.segments = (const JpegSegment*)d_segments; b.tables = (const JpegTableSet*)d_table_sets; b.frames = (const JpegFrameDesc*)d_frames;
-    b.n_sets = (uint32_t)n_sets; b.n_frames = (uint32_t)n_frames; b.n_segments = (uint32_t)n_segments;
-    b.g = jpeg_seg_geom(g);
-    b.coef = d_coef; b.seg_status = d_seg_status;
+    const char* bad = jpegcore::segment_batch(d_bytes, total_bytes, d_segments, d_table_sets, n_sets, d_frames, n_frames, n_segments,
+                                              JpegGeom{W, H, ncomp, hs, vs}, d_coef, d_seg_status, &b);
+    TSTAR_REQUIRE(!bad, std::string("tstar_jpeg_entropy_split_device: ") + bad);
     return jpeg_entropy_split(b, sub_bytes, min_split_bytes, max_rounds, d_workspace, workspace_bytes, d_seg_info, (hipStream_t)stream);
 }
 

@@ -63,7 +63,7 @@ int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const
 namespace jpegcore { struct SegmentBatch; }
 // jpeg_entropy.hip: clear b.coef, then one lane per segment of the batch (every pointer of b is device memory)
 int jpeg_entropy_segments(const jpegcore::SegmentBatch& b, hipStream_t s);
-// jpeg_entropy_split.hip: the same result, with segments of at least min_split_bytes bytes cut into sub-sequences of sub_bytes
+// the same result, with segments of at least min_split_bytes bytes cut into sub-sequences of sub_bytes
 // bytes, one lane each (workspace: jpeg_split_workspace_bytes bytes of device memory; seg_info i32 [n_segments])
 int jpeg_entropy_split(const jpegcore::SegmentBatch& b, int sub_bytes, int min_split_bytes, int max_rounds, void* workspace,
                        size_t workspace_bytes, int32_t* seg_info, hipStream_t s);

@@ -1,14 +1,19 @@
-// Baseline JPEG entropy decode of one SEGMENT: a run of MCUs that starts at a byte boundary with zero DC predictors (one
-// restart interval, or a whole scan without DRI).  One core for both sides: g++ compiles this file as plain C++
-// (jpeg_host.cpp: jpeg_entropy_segments_host, jpeg_entropy_split_host, the sanitizer checkers), hipcc as __host__ __device__
-// (jpeg_entropy.hip: one lane per segment; jpeg_entropy_split.hip: a long segment cut into sub-sequences, one lane each -- the
-// second half of this file).  Everything the decoder looks at lives in flat, pointer-free records (JpegTableSet, JpegSegment,
-// JpegFrameDesc) that may sit in host memory, global memory or LDS.
+// Baseline JPEG entropy decode.  A SEGMENT is a run of MCUs that starts at a byte boundary with zero DC predictors (one
+// restart interval, or a whole scan without DRI); a long segment may be cut into SUB-SEQUENCES of sub_bytes bytes, one lane
+// each.  There is one symbol loop, walk_sub, in two forms:
+//   walk_sub<false> (count form)  from a guessed or recorded state to the sub-sequence's limit: writes no coefficient, reports
+//                                 the exit state, the blocks completed and the DC sums;
+//   walk_sub<true>  (write form)  from a TRUE state with block index and predictors: stores coefficients under every check;
+// and decode_segment, a wrapper: the write form from the segment's start state to its end, one lane per segment.
+// One core for both sides: g++ compiles this file as plain C++ (jpeg_host.cpp: jpeg_entropy_segments_host,
+// jpeg_entropy_split_host, the sanitizer checkers), hipcc as __host__ __device__ (jpeg_entropy.hip).  Everything the decoder
+// looks at lives in flat, pointer-free records (JpegTableSet, JpegSegment, JpegFrameDesc) that may sit in host memory, global
+// memory or LDS.
 //
 // This code parses untrusted bytes, on the device next to other people's work:
 //   - every byte read is inside the segment's [begin, end), which segment_table_set first checks against the byte buffer;
 //   - every coefficient store is inside the segment's frame's own region of the coefficient buffer;
-//   - the symbol loop is bounded by the bits of the segment (a symbol consumes at least one real bit or is an error).
+//   - the symbol loop is bounded by the bits it may read (a symbol consumes at least one real bit or is an error).
 // The checks of a block are those of decode_block in jpeg_host.cpp, which stays the yardstick: DC category <= 11 and DC
 // range, AC category <= 10, run past 63, ZRL past 64, the energy bound, every table index before use.
 #pragma once
@@ -87,18 +92,23 @@ inline JpegSegGeom jpeg_seg_geom(const JpegGeom& g) {
 namespace jpegcore {
 
 // MSB-first bit reader over [p, end): removes FF00 stuffing, stops at a marker (an FF followed by anything but 00) or at
-// end.  Bits past that point read as zero so that table look-ahead is safe; CONSUMING one of them is the error.
+// end.  Bits past that point read as zero so that table look-ahead is safe; CONSUMING one of them is the error.  It also
+// knows where its unread bits sit in the raw bytes: ff has one bit per byte pushed, newest lowest, set when that byte was
+// an FF followed by its stuffed 00.
 struct BitReader {
     const uint8_t* d;
     uint32_t p, end;
     uint64_t acc;
     int nbits, fake;             // the lowest `fake` bits of acc are padding
+    uint32_t ff;
     bool at_marker;
 
+    TSTAR_JPEG_HD BitReader(const uint8_t* bytes, uint32_t at, uint32_t stop)
+        : d(bytes), p(at), end(stop), acc(0), nbits(0), fake(0), ff(0), at_marker(false) {}
     // at most 8 rounds; afterwards nbits > 56: enough for one code (<= 16 bits) and its magnitude field (<= 11)
     TSTAR_JPEG_HD void fill() {
         while (nbits <= 56) {
-            unsigned b = 0;
+            unsigned b = 0, stuffed = 0;
             if (!at_marker) {
                 if (p >= end) {
                     at_marker = true;
@@ -109,6 +119,7 @@ struct BitReader {
                         ++p;
                     } else if (p + 1 < end && d[p + 1] == 0x00) {
                         b = 0xFF;
+                        stuffed = 1;
                         p += 2;
                     } else {
                         at_marker = true;                           // p stays on the FF
@@ -117,6 +128,7 @@ struct BitReader {
             }
             if (at_marker) fake += 8;
             acc = (acc << 8) | b;
+            ff = (ff << 1) | stuffed;
             nbits += 8;
         }
     }
@@ -124,6 +136,13 @@ struct BitReader {
     TSTAR_JPEG_HD bool skip(int n) {
         nbits -= n;
         return nbits >= fake;
+    }
+    // the next unread bit (no padding bit has been consumed: nbits >= fake): byte offset and bit within it
+    TSTAR_JPEG_HD void where(uint32_t* byte, uint32_t* bit) const {
+        const uint32_t real = (uint32_t)(nbits - fake), nb = (real + 7) >> 3, nf = (uint32_t)fake >> 3;
+        const uint32_t stuffed = (uint32_t)__builtin_popcount((ff >> nf) & ((1u << nb) - 1));       // nb <= 8, nf <= 8
+        *byte = p - nb - stuffed;
+        *bit = (8 - (real & 7)) & 7;
     }
 };
 
@@ -149,40 +168,156 @@ TSTAR_JPEG_HD inline int huff_decode(BitReader& br, const Table* t) {
     return t->vals[idx];
 }
 
-// MCUs [first_mcu, first_mcu + n_mcu) of one frame out of bytes[begin, end) into coef (the FRAME's region, g.per_frame
-// elements, already zero) -> JPEG_OK / JPEG_MALFORMED / JPEG_UNCOVERED.  The caller has checked begin <= end <= size of bytes
-// and first_mcu + n_mcu <= g.n_mcu.
+// Everything a launch (or the host loop) hands to every segment.
+struct SegmentBatch {
+    const uint8_t* bytes;
+    uint64_t total_bytes;
+    const JpegSegment* segments;
+    const JpegTableSet* tables;
+    const JpegFrameDesc* frames;
+    uint32_t n_sets, n_frames, n_segments;
+    JpegSegGeom g;
+    int16_t* coef;               // [n_frames][g.per_frame]
+    int32_t* seg_status;         // [n_segments]
+};
+
+// The one place that checks an entry point's arguments and fills the batch (host code, like jpeg_seg_geom) -> nullptr, or
+// what is wrong, for the entry point to report under its own name.  total_bytes is the callee's to check.
+inline const char* segment_batch(const uint8_t* bytes, size_t total_bytes, const void* segments, const void* tables, int n_sets,
+                                 const void* frames, int n_frames, int n_segments, const JpegGeom& g, int16_t* coef,
+                                 int32_t* seg_status, SegmentBatch* b) {
+    if (!bytes || !segments || !tables || !frames || !coef || !seg_status) return "null argument";
+    if (n_sets <= 0 || n_frames <= 0 || n_segments <= 0) return "empty batch";
+    if (!g.valid()) return "unsupported geometry";
+    b->bytes = bytes; b->total_bytes = total_bytes;
+    b->segments = (const JpegSegment*)segments; b->tables = (const JpegTableSet*)tables; b->frames = (const JpegFrameDesc*)frames;
+    b->n_sets = (uint32_t)n_sets; b->n_frames = (uint32_t)n_frames; b->n_segments = (uint32_t)n_segments;
+    b->g = jpeg_seg_geom(g);
+    b->coef = coef; b->seg_status = seg_status;
+    return nullptr;
+}
+
+// The segment list is checked like the stream: a record that points outside the batch is MALFORMED and touches nothing.
+// Returns the table set of a usable segment, -1 otherwise.
+TSTAR_JPEG_HD inline int segment_table_set(const SegmentBatch& b, const JpegSegment& s) {
+    if (s.frame >= b.n_frames) return -1;
+    if (s.begin > s.end || s.end > b.total_bytes) return -1;
+    if (s.n_mcu == 0 || s.first_mcu >= b.g.n_mcu || s.n_mcu > b.g.n_mcu - s.first_mcu) return -1;
+    const int32_t ts = b.frames[s.frame].table_set;
+    if (ts < 0 || (uint32_t)ts >= b.n_sets) return -1;
+    return ts;
+}
+
+// ------------------------------------------------------------------------------------------------ sub-sequences
+// A long segment is cut into SUB-SEQUENCES of sub_bytes bytes, one lane each (self-synchronising Huffman decoding:
+// Weissenberger & Schmidt, "Massively Parallel Huffman Decoding on GPUs", ICPP 2018).  A decoder STATE is where the next
+// symbol starts (byte offset in the batch's byte buffer and bit within that byte; the byte is never the 00 of an FF 00
+// pair), the block within the MCU j, the zigzag index k and the AC energy of the open block.  Sub-sequence i of a segment
+// decodes from an entry state to the first symbol that starts at or behind its byte limit and records that exit state;
+// started from a guess, it falls into step with the true symbol sequence after some symbols, so rounds in which every
+// sub-sequence starts from its predecessor's last exit reach the sequential decoder's states.
 //
+// walk_sub<false> (count form) writes no coefficient: it reports the exit state, the blocks completed and the sum of the DC
+// differences of each component (mod 2^32).  A bad code is no error there, only "no exit state".  It cannot check the DC
+// range or the energy of a block (both need the predictors) and does not try.
+// walk_sub<true> (write form) is the same walk from a TRUE entry state with the predictors and the block index in front of
+// it: it stores coefficients and applies every check of a block.  The energy of a block is the AC terms as they come plus
+// the DC term when the block completes; the DC of a block opened in an earlier sub-sequence is the entry predictor of its
+// component, so the energy check needs no second pass.  The sub-sequence in which the segment's last block completes
+// checks the padding in front of the marker; sub-sequences behind it have nothing to do.
+constexpr uint32_t kSubBytesMin = 8;           // TSTAR_JPEG_SUB_BYTES_MIN (include/tstar_hip.h)
+constexpr uint32_t kSubValid = 1u << 14;       // SubState::pk = bit | j << 3 | k << 7 | kSubValid
+
+struct SubState {
+    uint32_t pos, pk;
+    int64_t energy;
+};
+
+TSTAR_JPEG_HD inline bool sub_state_equal(const SubState& a, const SubState& b) { return a.pos == b.pos && a.pk == b.pk && a.energy == b.energy; }
+
+struct SubCount {
+    uint32_t blocks, dc0, dc1, dc2;
+};
+
+// Where sub-sequence i > 0 of a segment starts when nothing is known: its own first byte, or the byte behind it when that
+// first byte is the 00 of an FF 00 pair (in entropy data an FF is always followed by 00).  at < end.
+TSTAR_JPEG_HD inline SubState sub_blank_state(const uint8_t* bytes, uint32_t begin, uint32_t at) {
+    SubState s;
+    s.pos = (at > begin && bytes[at - 1] == 0xFF && bytes[at] == 0x00) ? at + 1 : at;
+    s.pk = kSubValid;
+    s.energy = 0;
+    return s;
+}
+
+// What a write-form walk knows beyond the entry state.
+struct SubWrite {
+    uint32_t first_mcu, seg_blocks;            // the segment's first MCU and its blocks (n_mcu * blocks of an MCU)
+    uint32_t first_block;                      // blocks of the segment completed in front of this sub-sequence
+    int pred0, pred1, pred2;
+    bool last_sub, last_seg;                   // the segment's last sub-sequence; the frame's last segment
+    int16_t* coef;                             // the FRAME's region
+};
+
+// One sub-sequence: symbols from `in` (a valid state with begin <= pos <= end) up to the first one that starts at or
+// behind byte `lim` (<= end).  Reads stay inside [begin, end); the loop is bounded by the bits of [in.pos, lim) plus one
+// symbol (write form of the segment's last sub-sequence: lim = end).
 // One loop; an iteration decodes one Huffman symbol and its magnitude bits and refills the reader.  Which table (DC when
 // k == 0, else AC, of the block's component), which predictor and which destination are picked by data, so lanes that sit
 // at different places of different streams run the same instructions.  Tables may be in LDS or global memory (Tables is the
 // pointer type the caller hands in).
-template <class Tables>
-TSTAR_JPEG_HD inline int decode_segment(const uint8_t* bytes, uint32_t begin, uint32_t end, Tables T, const JpegSegGeom& g,
-                                        uint32_t first_mcu, uint32_t n_mcu, bool last, int16_t* coef) {
-    BitReader br;
-    br.d = bytes; br.p = begin; br.end = end; br.acc = 0; br.nbits = 0; br.fake = 0; br.at_marker = false;
-    const uint32_t luma = g.hs * g.vs, bpm = g.ncomp == 3 ? luma + 2 : 1;      // blocks of an MCU; luma first
-    uint32_t left = n_mcu;                                                      // MCUs not finished yet
-    uint32_t mx = first_mcu % g.mcux, my = first_mcu / g.mcux;
-    uint32_t j = 0;                                                             // block within the MCU
+//   count form: *out = the exit state (pk == 0: none), *cnt the blocks completed and DC sums; returns JPEG_OK.
+//   write form: returns the status; *out and *cnt are not written.
+template <bool kWrite, class Tables>
+TSTAR_JPEG_HD inline int walk_sub(const uint8_t* bytes, uint32_t end, uint32_t lim, Tables T, const JpegSegGeom& g, const SubState& in,
+                                  const SubWrite* w, SubState* out, SubCount* cnt) {
+    const uint32_t luma = g.hs * g.vs, bpm = g.ncomp == 3 ? luma + 2 : 1;
+    uint32_t j = (in.pk >> 3) & 15;
+    int k = (int)((in.pk >> 7) & 127);
+    int64_t energy = in.energy;                                                 // AC terms of the open block
+    if (kWrite) {
+        if (w->first_block >= w->seg_blocks) return JPEG_OK;                    // behind the segment's last block: nothing to do
+        if (j != w->first_block % bpm) return JPEG_MALFORMED;                   // never with a true state
+    }
+    if (j >= bpm || k > 63) {                                                   // never with a state this code recorded
+        if (!kWrite) { out->pos = 0; out->pk = 0; out->energy = 0; cnt->blocks = cnt->dc0 = cnt->dc1 = cnt->dc2 = 0; }
+        return JPEG_MALFORMED;
+    }
+    BitReader br(bytes, in.pos, end);
+    br.fill();
+    bool bad = !br.skip((int)(in.pk & 7));                                      // the bits of the first byte in front of the state
+    uint32_t left = 0, mx = 0, my = 0;
     int pred0 = 0, pred1 = 0, pred2 = 0;                                        // three scalars: an indexed array would live in scratch
-    int k = 0;
-    int64_t energy = 0;
-    // a symbol consumes at least one real bit, so this many iterations read any segment to its end
-    uint64_t budget = 8ull * (end - begin) + 1;
+    if (kWrite) {
+        left = w->seg_blocks - w->first_block;
+        const uint32_t m = w->first_mcu + w->first_block / bpm;
+        mx = m % g.mcux; my = m / g.mcux;
+        pred0 = w->pred0; pred1 = w->pred1; pred2 = w->pred2;
+        // the sequential decoder never carries a predictor outside the DC range: an earlier sub-sequence has refused the segment
+        if (pred0 < -2048 || pred0 > 2047 || pred1 < -2048 || pred1 > 2047 || pred2 < -2048 || pred2 > 2047) return JPEG_MALFORMED;
+    }
+    uint32_t blocks = 0, dc0 = 0, dc1 = 0, dc2 = 0;
+    const bool to_end = kWrite && w->last_sub;                                  // runs into the end of the data
+    uint64_t budget = (in.pos <= lim ? 8ull * (lim - in.pos) : 0) + 1;     // a state already behind lim is its own exit
     int status = JPEG_OK;
-    while (left != 0 && budget != 0) {
+    bool have_exit = false;
+    uint32_t xb = 0, xbit = 0;
+    while (!bad && budget != 0) {
         --budget;
-        // where this block lives: component c, block (bx, by) of the component's raster
-        const uint32_t c = j < luma ? 0u : j - luma + 1;
-        const uint32_t u = c == 0 ? j % g.hs : 0u, v = c == 0 ? j / g.hs : 0u;
-        const uint32_t nh = c == 0 ? g.hs : 1u, nv = c == 0 ? g.vs : 1u;
-        const uint32_t bw = c == 0 ? g.bw0 : g.bw1;
-        const uint32_t base = c == 0 ? 0u : (c == 1 ? g.off1 : g.off2);
-        const uint64_t blk = ((uint64_t)base + (uint64_t)(my * nv + v) * bw + (mx * nh + u)) * 64;
-        if (blk + 64 > g.per_frame) { status = JPEG_MALFORMED; break; }        // never with a checked segment: the store bound
         br.fill();
+        if (!to_end) {
+            br.where(&xb, &xbit);
+            if (xb >= lim) { have_exit = true; break; }
+        }
+        const uint32_t c = j < luma ? 0u : j - luma + 1;
+        uint64_t blk = 0;
+        if (kWrite) {                                                           // where this block lives: block (bx, by) of component c's raster
+            const uint32_t u = c == 0 ? j % g.hs : 0u, v = c == 0 ? j / g.hs : 0u;
+            const uint32_t nh = c == 0 ? g.hs : 1u, nv = c == 0 ? g.vs : 1u;
+            const uint32_t bw = c == 0 ? g.bw0 : g.bw1;
+            const uint32_t base = c == 0 ? 0u : (c == 1 ? g.off1 : g.off2);
+            blk = ((uint64_t)base + (uint64_t)(my * nv + v) * bw + (mx * nh + u)) * 64;
+            if (blk + 64 > g.per_frame) { status = JPEG_MALFORMED; break; }    // never with a checked segment: the store bound
+        }
         const bool dc = k == 0;
         const int sym = huff_decode(br, &T->h[2 * c + (dc ? 0 : 1)]);
         if (sym < 0) { status = JPEG_MALFORMED; break; }                        // bad code or data ends inside a code
@@ -211,255 +346,19 @@ TSTAR_JPEG_HD inline int decode_segment(const uint8_t* bytes, uint32_t begin, ui
             }
             int nat = 0;
             if (dc) {
-                val += c == 0 ? pred0 : (c == 1 ? pred1 : pred2);
-                if (val < -2048 || val > 2047) { status = JPEG_MALFORMED; break; }     // DC out of the 8-bit range
-                pred0 = c == 0 ? val : pred0;
-                pred1 = c == 1 ? val : pred1;
-                pred2 = c == 2 ? val : pred2;
-                energy = 0;
-            } else {
-                nat = T->zigzag[k] & 63;                                       // the table is data too: the store stays in the block
-            }
-            coef[blk + (uint32_t)nat] = (int16_t)val;
-            const int q = (int)T->quant[64 * c + (uint32_t)nat];
-            energy += (int64_t)(val * q) * (val * q);
-            ++k;
-            done = k == 64;
-        }
-        if (done) {
-            if (energy > T->limit[c]) { status = JPEG_UNCOVERED; break; }      // more energy than 8-bit samples can carry
-            k = 0;
-            if (++j == bpm) {
-                j = 0;
-                --left;
-                if (++mx == g.mcux) { mx = 0; ++my; }
-            }
-        }
-    }
-    if (status != JPEG_OK) return status;
-    if (left != 0) return JPEG_MALFORMED;                                       // budget spent: not reachable, kept as the loop's bound
-    // every block of the segment is decoded: less than a byte of padding may be left in front of the marker
-    br.fill();
-    if (!br.at_marker || br.nbits - br.fake >= 8) return last ? JPEG_UNCOVERED : JPEG_MALFORMED;
-    return JPEG_OK;
-}
-
-// Everything a launch (or the host loop) hands to every segment.
-struct SegmentBatch {
-    const uint8_t* bytes;
-    uint64_t total_bytes;
-    const JpegSegment* segments;
-    const JpegTableSet* tables;
-    const JpegFrameDesc* frames;
-    uint32_t n_sets, n_frames, n_segments;
-    JpegSegGeom g;
-    int16_t* coef;               // [n_frames][g.per_frame]
-    int32_t* seg_status;         // [n_segments]
-};
-
-// The segment list is checked like the stream: a record that points outside the batch is MALFORMED and touches nothing.
-// Returns the table set of a usable segment, -1 otherwise.
-TSTAR_JPEG_HD inline int segment_table_set(const SegmentBatch& b, const JpegSegment& s) {
-    if (s.frame >= b.n_frames) return -1;
-    if (s.begin > s.end || s.end > b.total_bytes) return -1;
-    if (s.n_mcu == 0 || s.first_mcu >= b.g.n_mcu || s.n_mcu > b.g.n_mcu - s.first_mcu) return -1;
-    const int32_t ts = b.frames[s.frame].table_set;
-    if (ts < 0 || (uint32_t)ts >= b.n_sets) return -1;
-    return ts;
-}
-
-// ------------------------------------------------------------------------------------------------ sub-sequences
-// A long segment is cut into SUB-SEQUENCES of sub_bytes bytes, one lane each (self-synchronising Huffman decoding:
-// Weissenberger & Schmidt, "Massively Parallel Huffman Decoding on GPUs", ICPP 2018).  A decoder STATE is where the next
-// symbol starts (byte offset in the batch's byte buffer and bit within that byte; the byte is never the 00 of an FF 00
-// pair), the block within the MCU j, the zigzag index k and the AC energy of the open block.  Sub-sequence i of a segment
-// decodes from an entry state to the first symbol that starts at or behind its byte limit and records that exit state;
-// started from a guess, it falls into step with the true symbol sequence after some symbols, so rounds in which every
-// sub-sequence starts from its predecessor's last exit reach the sequential decoder's states.
-//
-// walk_sub<false> (count form) writes no coefficient: it reports the exit state, the blocks completed and the sum of the DC
-// differences of each component (mod 2^32).  A bad code is no error there, only "no exit state".  It cannot check the DC
-// range or the energy of a block (both need the predictors) and does not try.
-// walk_sub<true> (write form) is the same walk from a TRUE entry state with the predictors and the block index in front of
-// it: it stores coefficients and applies every check of decode_segment, in decode_segment's order.  The DC of a block
-// opened in an earlier sub-sequence is the entry predictor of its component, so the energy check needs no second pass.
-// The sub-sequence in which the segment's last block completes checks the padding in front of the marker the way
-// decode_segment does; sub-sequences behind it have nothing to do.
-constexpr uint32_t kSubBytesMin = 8;           // TSTAR_JPEG_SUB_BYTES_MIN (include/tstar_hip.h)
-constexpr uint32_t kSubValid = 1u << 14;       // SubState::pk = bit | j << 3 | k << 7 | kSubValid
-
-struct SubState {
-    uint32_t pos, pk;
-    int64_t energy;
-};
-
-TSTAR_JPEG_HD inline bool sub_state_equal(const SubState& a, const SubState& b) { return a.pos == b.pos && a.pk == b.pk && a.energy == b.energy; }
-
-struct SubCount {
-    uint32_t blocks, dc0, dc1, dc2;
-};
-
-// BitReader that also knows where its unread bits sit in the raw bytes: ff has one bit per byte pushed, newest lowest, set
-// when that byte was an FF followed by its stuffed 00.
-struct SubReader {
-    BitReader br;
-    uint32_t ff;
-
-    // as BitReader::fill, byte for byte
-    TSTAR_JPEG_HD void fill() {
-        while (br.nbits <= 56) {
-            unsigned b = 0, stuffed = 0;
-            if (!br.at_marker) {
-                if (br.p >= br.end) {
-                    br.at_marker = true;
-                } else {
-                    const unsigned x = br.d[br.p];
-                    if (x != 0xFF) {
-                        b = x;
-                        ++br.p;
-                    } else if (br.p + 1 < br.end && br.d[br.p + 1] == 0x00) {
-                        b = 0xFF;
-                        stuffed = 1;
-                        br.p += 2;
-                    } else {
-                        br.at_marker = true;
-                    }
-                }
-            }
-            if (br.at_marker) br.fake += 8;
-            br.acc = (br.acc << 8) | b;
-            ff = (ff << 1) | stuffed;
-            br.nbits += 8;
-        }
-    }
-    // the next unread bit (no padding bit has been consumed: nbits >= fake): byte offset and bit within it
-    TSTAR_JPEG_HD void where(uint32_t* byte, uint32_t* bit) const {
-        const uint32_t real = (uint32_t)(br.nbits - br.fake), nb = (real + 7) >> 3, nf = (uint32_t)br.fake >> 3;
-        const uint32_t stuffed = (uint32_t)__builtin_popcount((ff >> nf) & ((1u << nb) - 1));       // nb <= 8, nf <= 8
-        *byte = br.p - nb - stuffed;
-        *bit = (8 - (real & 7)) & 7;
-    }
-};
-
-// Where sub-sequence i > 0 of a segment starts when nothing is known: its own first byte, or the byte behind it when that
-// first byte is the 00 of an FF 00 pair (in entropy data an FF is always followed by 00).  at < end.
-TSTAR_JPEG_HD inline SubState sub_blank_state(const uint8_t* bytes, uint32_t begin, uint32_t at) {
-    SubState s;
-    s.pos = (at > begin && bytes[at - 1] == 0xFF && bytes[at] == 0x00) ? at + 1 : at;
-    s.pk = kSubValid;
-    s.energy = 0;
-    return s;
-}
-
-// What a write-form walk knows beyond the entry state.
-struct SubWrite {
-    uint32_t first_mcu, seg_blocks;            // the segment's first MCU and its blocks (n_mcu * blocks of an MCU)
-    uint32_t first_block;                      // blocks of the segment completed in front of this sub-sequence
-    int pred0, pred1, pred2;
-    bool last_sub, last_seg;                   // the segment's last sub-sequence; the frame's last segment
-    int16_t* coef;                             // the FRAME's region
-};
-
-// One sub-sequence: symbols from `in` (a valid state with begin <= pos <= end) up to the first one that starts at or
-// behind byte `lim` (<= end).  Reads stay inside [begin, end); the loop is bounded by the bits of [in.pos, lim) plus one
-// symbol (write form of the segment's last sub-sequence: lim = end).
-//   count form: *out = the exit state (pk == 0: none), *cnt the blocks completed and DC sums; returns JPEG_OK.
-//   write form: returns the status; *out and *cnt are not written.
-template <bool kWrite, class Tables>
-TSTAR_JPEG_HD inline int walk_sub(const uint8_t* bytes, uint32_t end, uint32_t lim, Tables T, const JpegSegGeom& g, const SubState& in,
-                                  const SubWrite* w, SubState* out, SubCount* cnt) {
-    const uint32_t luma = g.hs * g.vs, bpm = g.ncomp == 3 ? luma + 2 : 1;
-    uint32_t j = (in.pk >> 3) & 15;
-    int k = (int)((in.pk >> 7) & 127);
-    int64_t energy = in.energy;                                                 // AC terms of the open block
-    if (kWrite) {
-        if (w->first_block >= w->seg_blocks) return JPEG_OK;                    // behind the segment's last block: nothing to do
-        if (j != w->first_block % bpm) return JPEG_MALFORMED;                   // never with a true state
-    }
-    if (j >= bpm || k > 63) {                                                   // never with a state this code recorded
-        if (!kWrite) { out->pos = 0; out->pk = 0; out->energy = 0; cnt->blocks = cnt->dc0 = cnt->dc1 = cnt->dc2 = 0; }
-        return JPEG_MALFORMED;
-    }
-    SubReader sr;
-    sr.br.d = bytes; sr.br.p = in.pos; sr.br.end = end; sr.br.acc = 0; sr.br.nbits = 0; sr.br.fake = 0; sr.br.at_marker = false;
-    sr.ff = 0;
-    BitReader& br = sr.br;
-    sr.fill();
-    bool bad = !br.skip((int)(in.pk & 7));                                      // the bits of the first byte in front of the state
-    uint32_t left = 0, mx = 0, my = 0;
-    int pred0 = 0, pred1 = 0, pred2 = 0;
-    if (kWrite) {
-        left = w->seg_blocks - w->first_block;
-        const uint32_t m = w->first_mcu + w->first_block / bpm;
-        mx = m % g.mcux; my = m / g.mcux;
-        pred0 = w->pred0; pred1 = w->pred1; pred2 = w->pred2;
-        // the sequential decoder never carries a predictor outside the DC range: an earlier sub-sequence has refused the segment
-        if (pred0 < -2048 || pred0 > 2047 || pred1 < -2048 || pred1 > 2047 || pred2 < -2048 || pred2 > 2047) return JPEG_MALFORMED;
-    }
-    uint32_t blocks = 0, dc0 = 0, dc1 = 0, dc2 = 0;
-    const bool to_end = kWrite && w->last_sub;                                  // runs into the end of the data, as decode_segment does
-    uint64_t budget = (in.pos <= lim ? 8ull * (lim - in.pos) : 0) + 1;     // a state already behind lim is its own exit
-    int status = JPEG_OK;
-    bool have_exit = false;
-    uint32_t xb = 0, xbit = 0;
-    while (!bad && budget != 0) {
-        --budget;
-        sr.fill();
-        if (!to_end) {
-            sr.where(&xb, &xbit);
-            if (xb >= lim) { have_exit = true; break; }
-        }
-        const uint32_t c = j < luma ? 0u : j - luma + 1;
-        uint64_t blk = 0;
-        if (kWrite) {
-            const uint32_t u = c == 0 ? j % g.hs : 0u, v = c == 0 ? j / g.hs : 0u;
-            const uint32_t nh = c == 0 ? g.hs : 1u, nv = c == 0 ? g.vs : 1u;
-            const uint32_t bw = c == 0 ? g.bw0 : g.bw1;
-            const uint32_t base = c == 0 ? 0u : (c == 1 ? g.off1 : g.off2);
-            blk = ((uint64_t)base + (uint64_t)(my * nv + v) * bw + (mx * nh + u)) * 64;
-            if (blk + 64 > g.per_frame) { status = JPEG_MALFORMED; break; }    // the store bound
-        }
-        const bool dc = k == 0;
-        const int sym = huff_decode(br, &T->h[2 * c + (dc ? 0 : 1)]);
-        if (sym < 0) { status = JPEG_MALFORMED; break; }
-        const int r = dc ? 0 : sym >> 4, s = dc ? sym : sym & 15;
-        if (s > (dc ? 11 : 10)) { status = JPEG_MALFORMED; break; }
-        bool done = false;
-        if (!dc && s == 0) {
-            if (r == 15) {
-                k += 16;
-                if (k > 64) { status = JPEG_MALFORMED; break; }
-                done = k == 64;
-            } else if (r != 0) {
-                status = JPEG_MALFORMED;
-                break;
-            } else {
-                done = true;
-            }
-        } else {
-            k += r;
-            if (k > 63) { status = JPEG_MALFORMED; break; }
-            int val = 0;
-            if (s) {
-                const int bits = (int)br.peek(s);
-                if (!br.skip(s)) { status = JPEG_MALFORMED; break; }
-                val = bits < (1 << (s - 1)) ? bits - (1 << s) + 1 : bits;
-            }
-            int nat = 0;
-            if (dc) {
                 dc0 += c == 0 ? (uint32_t)val : 0u;
                 dc1 += c == 1 ? (uint32_t)val : 0u;
                 dc2 += c == 2 ? (uint32_t)val : 0u;
                 if (kWrite) {
                     val += c == 0 ? pred0 : (c == 1 ? pred1 : pred2);
-                    if (val < -2048 || val > 2047) { status = JPEG_MALFORMED; break; }
+                    if (val < -2048 || val > 2047) { status = JPEG_MALFORMED; break; }     // DC out of the 8-bit range
                     pred0 = c == 0 ? val : pred0;
                     pred1 = c == 1 ? val : pred1;
                     pred2 = c == 2 ? val : pred2;
                 }
                 energy = 0;
             } else {
-                nat = T->zigzag[k] & 63;
+                nat = T->zigzag[k] & 63;                                       // the table is data too: the store stays in the block
                 const int q = (int)T->quant[64 * c + (uint32_t)nat];
                 energy += (int64_t)(val * q) * (val * q);
             }
@@ -471,7 +370,7 @@ TSTAR_JPEG_HD inline int walk_sub(const uint8_t* bytes, uint32_t end, uint32_t l
             if (kWrite) {
                 const int d = c == 0 ? pred0 : (c == 1 ? pred1 : pred2);       // this block's DC, wherever the block was opened
                 const int q = (int)T->quant[64 * c];
-                if (energy + (int64_t)(d * q) * (d * q) > T->limit[c]) { status = JPEG_UNCOVERED; break; }
+                if (energy + (int64_t)(d * q) * (d * q) > T->limit[c]) { status = JPEG_UNCOVERED; break; }   // more than 8-bit samples can carry
             }
             k = 0;
             energy = 0;
@@ -496,9 +395,32 @@ TSTAR_JPEG_HD inline int walk_sub(const uint8_t* bytes, uint32_t end, uint32_t l
     if (bad) return JPEG_MALFORMED;
     if (status != JPEG_OK) return status;
     if (left != 0) return w->last_sub ? JPEG_MALFORMED : (have_exit ? JPEG_OK : JPEG_MALFORMED);
+    // every block of the segment is decoded: less than a byte of padding may be left in front of the marker
     br.fill();
     if (!br.at_marker || br.nbits - br.fake >= 8) return w->last_seg ? JPEG_UNCOVERED : JPEG_MALFORMED;
     return JPEG_OK;
+}
+
+// The start of a segment is a true state: its first byte, block 0, no open block.
+TSTAR_JPEG_HD inline SubState sub_start_state(uint32_t begin) {
+    SubState s;
+    s.pos = begin; s.pk = kSubValid; s.energy = 0;
+    return s;
+}
+
+// One lane per segment: MCUs [first_mcu, first_mcu + n_mcu) of one frame out of bytes[begin, end) into coef (the FRAME's
+// region, g.per_frame elements, already zero) -> JPEG_OK / JPEG_MALFORMED / JPEG_UNCOVERED.  The caller has checked
+// begin <= end <= size of bytes and 0 < n_mcu, first_mcu + n_mcu <= g.n_mcu (segment_table_set).  The write form from the
+// segment's start state, as the segment's only and last sub-sequence.
+template <class Tables>
+TSTAR_JPEG_HD inline int decode_segment(const uint8_t* bytes, uint32_t begin, uint32_t end, Tables T, const JpegSegGeom& g,
+                                        uint32_t first_mcu, uint32_t n_mcu, bool last, int16_t* coef) {
+    SubWrite w;
+    w.first_mcu = first_mcu; w.seg_blocks = n_mcu * (g.ncomp == 3 ? g.hs * g.vs + 2 : 1); w.first_block = 0;
+    w.pred0 = w.pred1 = w.pred2 = 0;
+    w.last_sub = true; w.last_seg = last;
+    w.coef = coef;
+    return walk_sub<true>(bytes, end, end, T, g, sub_start_state(begin), &w, (SubState*)nullptr, (SubCount*)nullptr);
 }
 
 // The caller-sized workspace of a split call, structure of arrays over `cap` sub-sequences and n segments:
@@ -536,12 +458,31 @@ inline SplitWs split_ws_carve(void* base, uint64_t cap, uint64_t n_segments) {
     return w;
 }
 
+TSTAR_JPEG_HD inline SubState split_ws_load(const SplitWs& w, uint32_t copy, uint32_t lane) {
+    SubState s;
+    s.pos = w.pos[copy][lane]; s.pk = w.pk[copy][lane]; s.energy = w.energy[copy][lane];
+    return s;
+}
+TSTAR_JPEG_HD inline void split_ws_store(const SplitWs& w, uint32_t copy, uint32_t lane, const SubState& s) {
+    w.pos[copy][lane] = s.pos; w.pk[copy][lane] = s.pk; w.energy[copy][lane] = s.energy;
+}
+
 // Is segment s cut into sub-sequences, and into how many?  0: one lane.
 TSTAR_JPEG_HD inline uint32_t split_n_sub(const SegmentBatch& b, const JpegSegment& s, uint32_t sub_bytes, uint32_t min_split_bytes) {
     if (min_split_bytes == 0 || segment_table_set(b, s) < 0) return 0;
     const uint32_t len = s.end - s.begin;
     if (len < min_split_bytes) return 0;
     return (len - 1) / sub_bytes + 1;
+}
+
+// Same entry as last round, same exit: after round 0 the segment's first sub-sequence (at lane `first`), and one whose
+// predecessor's exit did not change in the round before, copy their exit and are done.  Returns whether `lane` was one.
+TSTAR_JPEG_HD inline bool split_round_copies(const SplitWs& w, uint32_t round, uint32_t first, uint32_t lane) {
+    const uint32_t in = (round + 1) & 1, o = round & 1;
+    if (round == 0 || (lane != first && w.chg[in][lane - 1] != 0)) return false;
+    split_ws_store(w, o, lane, split_ws_load(w, in, lane));
+    w.chg[o][lane] = 0;
+    return true;
 }
 
 // Sub-sequence `lane` (i of segment `si`) in round `round`: round 0 starts from nothing, a later round from the exit its
@@ -552,32 +493,23 @@ TSTAR_JPEG_HD inline bool split_round_lane(const SegmentBatch& b, const SplitWs&
     const JpegSegment s = b.segments[si];
     const uint32_t i = lane - w.sub_first[si], n = w.n_sub[si];
     const uint32_t in = (round + 1) & 1, o = round & 1;
-    if (round != 0 && (i == 0 || w.chg[in][lane - 1] == 0)) {                  // same entry as last round: same exit
-        w.pos[o][lane] = w.pos[in][lane]; w.pk[o][lane] = w.pk[in][lane]; w.energy[o][lane] = w.energy[in][lane];
-        w.chg[o][lane] = 0;
-        return false;
-    }
+    if (split_round_copies(w, round, w.sub_first[si], lane)) return false;
     const uint32_t at = s.begin + i * sub_bytes;
     SubState e;
     if (i == 0) {
-        e.pos = s.begin; e.pk = kSubValid; e.energy = 0;
+        e = sub_start_state(s.begin);
     } else if (round == 0) {
         e = sub_blank_state(b.bytes, s.begin, at);
     } else {
-        e.pos = w.pos[in][lane - 1]; e.pk = w.pk[in][lane - 1]; e.energy = w.energy[in][lane - 1];
+        e = split_ws_load(w, in, lane - 1);
         if (!(e.pk & kSubValid) || e.pos < s.begin || e.pos > s.end) e = sub_blank_state(b.bytes, s.begin, at);
     }
     const uint32_t lim = i + 1 == n ? s.end : at + sub_bytes;
     SubState x;
     SubCount c;
     walk_sub<false>(b.bytes, s.end, lim, T, b.g, e, (const SubWrite*)nullptr, &x, &c);
-    bool changed = true;
-    if (round != 0) {
-        SubState old;
-        old.pos = w.pos[in][lane]; old.pk = w.pk[in][lane]; old.energy = w.energy[in][lane];
-        changed = !sub_state_equal(old, x);
-    }
-    w.pos[o][lane] = x.pos; w.pk[o][lane] = x.pk; w.energy[o][lane] = x.energy;
+    const bool changed = round == 0 || !sub_state_equal(split_ws_load(w, in, lane), x);
+    split_ws_store(w, o, lane, x);
     w.chg[o][lane] = changed ? 1u : 0u;
     w.blocks[lane] = c.blocks; w.dc0[lane] = c.dc0; w.dc1[lane] = c.dc1; w.dc2[lane] = c.dc2;
     if (changed && round != 0) w.last_changed[si] = round;                     // every writer of a round stores the same value
@@ -598,12 +530,7 @@ TSTAR_JPEG_HD inline int split_write_lane(const SegmentBatch& b, const SplitWs& 
     const JpegSegment s = b.segments[si];
     const uint32_t i = lane - w.sub_first[si], n = w.n_sub[si], f = max_rounds & 1;
     const uint32_t luma = b.g.hs * b.g.vs, bpm = b.g.ncomp == 3 ? luma + 2 : 1;
-    SubState e;
-    if (i == 0) {
-        e.pos = s.begin; e.pk = kSubValid; e.energy = 0;
-    } else {
-        e.pos = w.pos[f][lane - 1]; e.pk = w.pk[f][lane - 1]; e.energy = w.energy[f][lane - 1];
-    }
+    const SubState e = i == 0 ? sub_start_state(s.begin) : split_ws_load(w, f, lane - 1);
     SubWrite sw;
     sw.first_mcu = s.first_mcu; sw.seg_blocks = s.n_mcu * bpm; sw.first_block = w.first_block[lane];
     sw.pred0 = (int)w.pred0[lane]; sw.pred1 = (int)w.pred1[lane]; sw.pred2 = (int)w.pred2[lane];

@@ -601,14 +601,10 @@ bool jpeg_plan_segments(const uint8_t* const* datas, const size_t* lens, const u
 bool jpeg_entropy_segments_host(const uint8_t* bytes, size_t total_bytes, const JpegSegment* segments, const JpegTableSet* tables,
                                 int n_sets, const JpegFrameDesc* frames, int n_frames, int n_segments, const JpegGeom& g,
                                 int16_t* coef, int32_t* seg_status) {
-    if (!bytes || !segments || !tables || !frames || !coef || !seg_status || n_sets <= 0 || n_frames <= 0 || n_segments <= 0 ||
-        total_bytes == 0 || total_bytes >= 0xffffffffull || !g.valid())
-        return false;
     jpegcore::SegmentBatch b;
-    b.bytes = bytes; b.total_bytes = total_bytes; b.segments = segments; b.tables = tables; b.frames = frames;
-    b.n_sets = (uint32_t)n_sets; b.n_frames = (uint32_t)n_frames; b.n_segments = (uint32_t)n_segments;
-    b.g = jpeg_seg_geom(g);
-    b.coef = coef; b.seg_status = seg_status;
+    if (jpegcore::segment_batch(bytes, total_bytes, segments, tables, n_sets, frames, n_frames, n_segments, g, coef, seg_status, &b) ||
+        total_bytes == 0 || total_bytes >= 0xffffffffull)
+        return false;
     memset(coef, 0, (size_t)n_frames * b.g.per_frame * sizeof(int16_t));
     for (int i = 0; i < n_segments; ++i) {
         const JpegSegment s = segments[i];
@@ -639,16 +635,11 @@ bool jpeg_entropy_split_host(const uint8_t* bytes, size_t total_bytes, const Jpe
                              int n_sets, const JpegFrameDesc* frames, int n_frames, int n_segments, const JpegGeom& g, int sub_bytes,
                              int min_split_bytes, int max_rounds, void* workspace, size_t workspace_bytes, int16_t* coef,
                              int32_t* seg_status, int32_t* seg_info) {
-    if (!bytes || !segments || !tables || !frames || !coef || !seg_status || !seg_info || n_sets <= 0 || n_frames <= 0 || n_segments <= 0 ||
-        total_bytes == 0 || total_bytes >= 0xffffffffull || !g.valid() ||
-        !jpeg_split_args_ok(total_bytes, n_segments, sub_bytes, min_split_bytes, max_rounds, workspace, workspace_bytes))
-        return false;
     using namespace jpegcore;
     SegmentBatch b;
-    b.bytes = bytes; b.total_bytes = total_bytes; b.segments = segments; b.tables = tables; b.frames = frames;
-    b.n_sets = (uint32_t)n_sets; b.n_frames = (uint32_t)n_frames; b.n_segments = (uint32_t)n_segments;
-    b.g = jpeg_seg_geom(g);
-    b.coef = coef; b.seg_status = seg_status;
+    if (segment_batch(bytes, total_bytes, segments, tables, n_sets, frames, n_frames, n_segments, g, coef, seg_status, &b) || !seg_info ||
+        !jpeg_split_args_ok(total_bytes, n_segments, sub_bytes, min_split_bytes, max_rounds, workspace, workspace_bytes))
+        return false;
     const uint32_t sub = (uint32_t)sub_bytes, rounds = (uint32_t)max_rounds, nseg = (uint32_t)n_segments;
     const uint64_t cap = split_cap(total_bytes, nseg, sub);
     const SplitWs w = split_ws_carve(workspace, cap, nseg);

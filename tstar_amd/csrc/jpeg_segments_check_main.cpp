@@ -11,20 +11,13 @@
 // stream: a frame jpeg_entropy accepts takes the device route; a device-routed frame's status (its first segment that is
 // not OK) equals jpeg_entropy's; when that is OK, coefficients and quantisation rows are identical.  Prints one line per
 // file; exit status 1 on any difference or when the intact file does not decode on the device route.
-#include "jpeg_entropy_core.h"
-#include "jpeg_host.h"
-
-#include <stdio.h>
-#include <string.h>
-
-#include <string>
-#include <vector>
+#include "jpeg_check_common.h"
 
 namespace tstar {
 void set_error(const std::string&) {}
 }  // namespace tstar
 
-using namespace tstar;
+using namespace jpegcheck;
 
 struct Tally {
     int streams = 0, device_routed = 0, device_ok = 0, differ = 0;
@@ -32,29 +25,21 @@ struct Tally {
 
 // one stream, exact-size copies -> false when the two decoders disagree
 static bool run(const uint8_t* d, size_t n, const JpegGeom& g, Tally& t, int* device_status) {
-    std::vector<uint8_t> copy(d, d + n);
-    const size_t per = g.blocks() * 64;
-    std::vector<int16_t> want(per), got(per);
-    std::vector<uint16_t> want_q(192), got_q(192);
-    char msg[160];
-    const int host = jpeg_entropy(copy.data(), n, g, want.data(), want_q.data(), msg, sizeof(msg));
-
-    const uint8_t* datas[1] = {copy.data()};
-    const size_t lens[1] = {n};
-    const uint64_t offsets[1] = {0};
-    int32_t route = -1;
-    JpegFrameDesc frame;
-    struct { std::vector<JpegTableSet> sets; std::vector<JpegSegment> segments; } plan;
+    OneFrame f;
     ++t.streams;
     *device_status = -1;
-    if (!jpeg_plan_segments(datas, lens, offsets, 1, g, &route, &frame, got_q.data(), &plan.sets, &plan.segments)) return false;
-    if (route != 0) return host != JPEG_OK;                         // what the sequential decoder accepts is planned
+    if (!plan_one_frame(d, n, g, &f)) return false;
+    const size_t per = g.blocks() * 64;
+    std::vector<int16_t> want(per), got(per);
+    std::vector<uint16_t> want_q(192);
+    char msg[160];
+    const int host = jpeg_entropy(f.bytes.data(), n, g, want.data(), want_q.data(), msg, sizeof(msg));
+    if (f.route != 0) return host != JPEG_OK;                       // what the sequential decoder accepts is planned
     ++t.device_routed;
-    std::vector<JpegSegment> segs(plan.segments);                   // exact-size blocks of the records too
-    std::vector<JpegTableSet> sets(plan.sets);
-    std::vector<int32_t> status(segs.size(), -1);
-    if (segs.empty() || frame.n_segments != (int32_t)segs.size() || frame.table_set != 0 || sets.size() != 1) return false;
-    if (!jpeg_entropy_segments_host(copy.data(), n, segs.data(), sets.data(), 1, &frame, 1, (int)segs.size(), g, got.data(), status.data()))
+    std::vector<int32_t> status(f.segs.size(), -1);
+    if (f.segs.empty() || f.frame.n_segments != (int32_t)f.segs.size() || f.frame.table_set != 0 || f.sets.size() != 1) return false;
+    if (!jpeg_entropy_segments_host(f.bytes.data(), n, f.segs.data(), f.sets.data(), 1, &f.frame, 1, (int)f.segs.size(), g, got.data(),
+                                    status.data()))
         return false;
     int dev = JPEG_OK;
     for (size_t i = 0; i < status.size() && dev == JPEG_OK; ++i) dev = status[i];
@@ -62,7 +47,7 @@ static bool run(const uint8_t* d, size_t n, const JpegGeom& g, Tally& t, int* de
     if (dev != host) return false;
     if (dev == JPEG_OK) {
         ++t.device_ok;
-        if (memcmp(want.data(), got.data(), per * sizeof(int16_t)) != 0 || memcmp(want_q.data(), got_q.data(), 192 * sizeof(uint16_t)) != 0)
+        if (memcmp(want.data(), got.data(), per * sizeof(int16_t)) != 0 || memcmp(want_q.data(), f.quant.data(), 192 * sizeof(uint16_t)) != 0)
             return false;
     }
     return true;
@@ -71,13 +56,8 @@ static bool run(const uint8_t* d, size_t n, const JpegGeom& g, Tally& t, int* de
 int main(int argc, char** argv) {
     int bad = 0;
     for (int a = 1; a < argc; ++a) {
-        FILE* f = fopen(argv[a], "rb");
-        if (!f) { fprintf(stderr, "cannot read %s\n", argv[a]); return 2; }
         std::vector<uint8_t> d;
-        uint8_t buf[65536];
-        size_t got;
-        while ((got = fread(buf, 1, sizeof(buf), f)) > 0) d.insert(d.end(), buf, buf + got);
-        fclose(f);
+        if (!read_file(argv[a], &d)) return 2;
         char msg[160];
         JpegGeom g;
         if (jpeg_probe(d.data(), d.size(), &g, msg, sizeof(msg)) != JPEG_OK) { fprintf(stderr, "%s: %s\n", argv[a], msg); return 2; }
@@ -91,14 +71,7 @@ int main(int argc, char** argv) {
         };
         check(d.data(), d.size(), "intact", 0);
         const int intact = st;
-        size_t sos = 0;                                             // start of the entropy data: after the first SOS segment
-        for (size_t p = 2; p + 4 <= d.size();) {
-            if (d[p] != 0xFF) break;
-            const int m = d[p + 1];
-            const size_t L = ((size_t)d[p + 2] << 8) | d[p + 3];
-            if (m == 0xDA) { sos = p + 2 + L; break; }
-            p += 2 + L;
-        }
+        const size_t sos = entropy_start(d);
         for (size_t n = 0; n < d.size(); n += 97) check(d.data(), n, "truncation", n);
         if (sos && sos + 2 < d.size()) {
             const size_t span = d.size() - 2 - sos, step = span / 64 + 1;

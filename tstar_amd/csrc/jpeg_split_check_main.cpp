@@ -13,21 +13,15 @@
 // 8-byte sub-sequences, whose thousands of rounds are the intact file's to walk); for the first N files (--exhaustive,
 // default 2; meant for small files) EVERY truncation and every single byte of the entropy data corrupted in three ways.
 // Prints one line per file; exit status 1 on any difference.
-#include "jpeg_entropy_core.h"
-#include "jpeg_host.h"
+#include "jpeg_check_common.h"
 
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
-
-#include <string>
-#include <vector>
 
 namespace tstar {
 void set_error(const std::string&) {}
 }  // namespace tstar
 
-using namespace tstar;
+using namespace jpegcheck;
 
 struct Tally {
     int streams = 0, routed = 0, ok = 0, differ = 0, split = 0, abandoned = 0, rounds_max = 0;
@@ -37,26 +31,19 @@ static const int kSubs[3] = {8, 64, 128};
 
 // one stream -> false when the split path and the sequential decoder disagree
 static bool run(const uint8_t* d, size_t n, const JpegGeom& g, Tally& t, bool must_converge, bool smallest = true) {
-    std::vector<uint8_t> copy(d, d + n);
+    OneFrame f;
+    ++t.streams;
+    if (!plan_one_frame(d, n, g, &f)) return false;
     const size_t per = g.blocks() * 64;
     std::vector<int16_t> want(per), got(per);
-    std::vector<uint16_t> want_q(192), got_q(192);
+    std::vector<uint16_t> want_q(192);
     char msg[160];
-    const int host = jpeg_entropy(copy.data(), n, g, want.data(), want_q.data(), msg, sizeof(msg));
-    const uint8_t* datas[1] = {copy.data()};
-    const size_t lens[1] = {n};
-    const uint64_t offsets[1] = {0};
-    int32_t route = -1;
-    JpegFrameDesc frame;
-    struct { std::vector<JpegTableSet> sets; std::vector<JpegSegment> segments; } plan;
-    ++t.streams;
-    if (!jpeg_plan_segments(datas, lens, offsets, 1, g, &route, &frame, got_q.data(), &plan.sets, &plan.segments)) return false;
-    if (route != 0) return host != JPEG_OK;
+    const int host = jpeg_entropy(f.bytes.data(), n, g, want.data(), want_q.data(), msg, sizeof(msg));
+    if (f.route != 0) return host != JPEG_OK;
     ++t.routed;
-    std::vector<JpegSegment> segs(plan.segments);
-    std::vector<JpegTableSet> sets(plan.sets);
+    const std::vector<JpegSegment>& segs = f.segs;
     const int nseg = (int)segs.size();
-    if (nseg == 0 || sets.size() != 1) return false;
+    if (nseg == 0 || f.sets.size() != 1) return false;
     bool good = true;
     for (int v = smallest ? 0 : 1; v < 4; ++v) {                    // three sub-sequence sizes, then one round only
         const int sub = kSubs[v % 3], rounds = v == 3 ? 1 : kJpegSplitMaxRounds;
@@ -64,7 +51,7 @@ static bool run(const uint8_t* d, size_t n, const JpegGeom& g, Tally& t, bool mu
         if (wsb == 0) return false;
         std::vector<uint64_t> ws((wsb + 7) / 8);
         std::vector<int32_t> status((size_t)nseg, -1), info((size_t)nseg, -7);
-        if (!jpeg_entropy_split_host(copy.data(), n, segs.data(), sets.data(), 1, &frame, 1, nseg, g, sub, 1, rounds, ws.data(), wsb,
+        if (!jpeg_entropy_split_host(f.bytes.data(), n, segs.data(), f.sets.data(), 1, &f.frame, 1, nseg, g, sub, 1, rounds, ws.data(), wsb,
                                      got.data(), status.data(), info.data()))
             return false;
         int dev = JPEG_OK;
@@ -78,7 +65,7 @@ static bool run(const uint8_t* d, size_t n, const JpegGeom& g, Tally& t, bool mu
         }
         if (dev != host) good = false;
         if (dev == JPEG_OK && (memcmp(want.data(), got.data(), per * sizeof(int16_t)) != 0 ||
-                               memcmp(want_q.data(), got_q.data(), 192 * sizeof(uint16_t)) != 0))
+                               memcmp(want_q.data(), f.quant.data(), 192 * sizeof(uint16_t)) != 0))
             good = false;
         if (dev == JPEG_OK && v == 1) ++t.ok;
     }
@@ -89,13 +76,8 @@ int main(int argc, char** argv) {
     int bad = 0, exhaustive = 2, a = 1;
     if (argc > 2 && strcmp(argv[1], "--exhaustive") == 0) { exhaustive = atoi(argv[2]); a = 3; }
     for (int fi = 0; a < argc; ++a, ++fi) {
-        FILE* f = fopen(argv[a], "rb");
-        if (!f) { fprintf(stderr, "cannot read %s\n", argv[a]); return 2; }
         std::vector<uint8_t> d;
-        uint8_t buf[65536];
-        size_t got;
-        while ((got = fread(buf, 1, sizeof(buf), f)) > 0) d.insert(d.end(), buf, buf + got);
-        fclose(f);
+        if (!read_file(argv[a], &d)) return 2;
         char msg[160];
         JpegGeom g;
         if (jpeg_probe(d.data(), d.size(), &g, msg, sizeof(msg)) != JPEG_OK) { fprintf(stderr, "%s: %s\n", argv[a], msg); return 2; }
@@ -108,14 +90,7 @@ int main(int argc, char** argv) {
         };
         check(d.data(), d.size(), "intact", 0, true);
         const bool intact = t.ok == 1 && t.differ == 0;
-        size_t sos = 0;
-        for (size_t p = 2; p + 4 <= d.size();) {
-            if (d[p] != 0xFF) break;
-            const int m = d[p + 1];
-            const size_t L = ((size_t)d[p + 2] << 8) | d[p + 3];
-            if (m == 0xDA) { sos = p + 2 + L; break; }
-            p += 2 + L;
-        }
+        const size_t sos = entropy_start(d);
         const bool all = fi < exhaustive;
         const bool big = d.size() > 8192;
         for (size_t n = all ? sos : 0; n < d.size(); n += all ? 1 : (big ? d.size() / 24 : 97)) check(d.data(), n, "truncation", n, false);

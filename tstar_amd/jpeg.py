@@ -424,10 +424,8 @@ def plan_segments(datas: Sequence[bytes], geom, offsets: Optional[np.ndarray] = 
     return SegmentPlan(route, frames, quant, sets[:int(out5[0])], segs[:int(out5[1])], offsets, total)
 
 
-def entropy_segments_host(buf: np.ndarray, plan: SegmentPlan, geom, coef: Optional[np.ndarray] = None):
-    """The device kernel's decode core on the CPU over ``buf`` (uint8, the frames at plan.offsets) -> (coef int16
-    [n, blocks * 64], seg_status int32 [n_segments])."""
-    from . import _lib
+def _host_batch(buf: np.ndarray, plan: SegmentPlan, geom, coef: Optional[np.ndarray]):
+    """What the two host entry points share -> (coef, seg_status, the leading arguments of the call up to the geometry)."""
     n, nseg = len(plan.route), len(plan.segments)
     blocks, _ = _sizes(geom)
     if coef is None:
@@ -435,10 +433,19 @@ def entropy_segments_host(buf: np.ndarray, plan: SegmentPlan, geom, coef: Option
     assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size >= n * blocks * 64
     assert buf.dtype == np.uint8 and buf.flags.c_contiguous and buf.size >= plan.total_bytes
     status = np.full(nseg, -1, dtype=np.int32)
-    if nseg:
-        _lib.check(_lib.load().tstar_jpeg_entropy_segments_host(
-            buf.ctypes.data, plan.total_bytes, plan.segments.ctypes.data, plan.table_sets.ctypes.data, len(plan.table_sets),
-            plan.frames.ctypes.data, n, nseg, *geom, coef.ctypes.data, status.ctypes.data), "tstar_jpeg_entropy_segments_host")
+    head = (buf.ctypes.data, plan.total_bytes, plan.segments.ctypes.data, plan.table_sets.ctypes.data, len(plan.table_sets),
+            plan.frames.ctypes.data, n, nseg, *geom)
+    return coef, status, head
+
+
+def entropy_segments_host(buf: np.ndarray, plan: SegmentPlan, geom, coef: Optional[np.ndarray] = None):
+    """The device kernel's decode core on the CPU over ``buf`` (uint8, the frames at plan.offsets) -> (coef int16
+    [n, blocks * 64], seg_status int32 [n_segments])."""
+    from . import _lib
+    coef, status, head = _host_batch(buf, plan, geom, coef)
+    if len(status):
+        _lib.check(_lib.load().tstar_jpeg_entropy_segments_host(*head, coef.ctypes.data, status.ctypes.data),
+                   "tstar_jpeg_entropy_segments_host")
     return coef, status
 
 
@@ -447,20 +454,14 @@ def entropy_split_host(buf: np.ndarray, plan: SegmentPlan, geom, sub_bytes: int 
     """The split launcher's CPU mirror (same core, same round order) over ``buf`` -> (coef int16 [n, blocks * 64], seg_status
     int32 [n_segments], seg_info int32 [n_segments]: 0 one lane, r > 0 converged in round r, -1 abandoned)."""
     from . import _lib
-    n, nseg = len(plan.route), len(plan.segments)
-    blocks, _ = _sizes(geom)
-    if coef is None:
-        coef = np.empty((n, blocks * 64), dtype=np.int16)
-    assert coef.dtype == np.int16 and coef.flags.c_contiguous and coef.size >= n * blocks * 64
-    assert buf.dtype == np.uint8 and buf.flags.c_contiguous and buf.size >= plan.total_bytes
-    status = np.full(nseg, -1, dtype=np.int32)
+    coef, status, head = _host_batch(buf, plan, geom, coef)
+    nseg = len(status)
     info = np.full(nseg, -9, dtype=np.int32)
     if nseg:
         ws = np.empty(split_workspace_bytes(plan.total_bytes, nseg, sub_bytes) // 8 + 1, dtype=np.uint64)
         _lib.check(_lib.load().tstar_jpeg_entropy_split_host(
-            buf.ctypes.data, plan.total_bytes, plan.segments.ctypes.data, plan.table_sets.ctypes.data, len(plan.table_sets),
-            plan.frames.ctypes.data, n, nseg, *geom, sub_bytes, min_split_bytes, max_rounds, ws.ctypes.data, ws.nbytes,
-            coef.ctypes.data, status.ctypes.data, info.ctypes.data), "tstar_jpeg_entropy_split_host")
+            *head, sub_bytes, min_split_bytes, max_rounds, ws.ctypes.data, ws.nbytes, coef.ctypes.data, status.ctypes.data,
+            info.ctypes.data), "tstar_jpeg_entropy_split_host")
     return coef, status, info
 
 
@@ -504,29 +505,28 @@ class DeviceBatch:
             at, nb = self.parts[name]
             host[at:at + nb] = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
 
+    def _head(self, d_buf, geom):
+        """The leading arguments of both device entry points, up to the geometry."""
+        p = self.plan
+        base = d_buf.data_ptr()
+        return (base, self.total, base + self.parts["segments"][0], base + self.parts["table_sets"][0], len(p.table_sets),
+                base + self.parts["frames"][0], len(p.route), len(p.segments), *geom)
+
     def launch(self, d_buf, d_coef, d_seg_status, geom, stream: int) -> None:
         """Entropy-decode on the device: d_buf holds what fill() wrote; d_coef int16 [>= n, blocks * 64]."""
         from . import _lib
-        p = self.plan
-        base = d_buf.data_ptr()
-        _lib.check(_lib.load().tstar_jpeg_entropy_device(
-            base, self.total, base + self.parts["segments"][0], base + self.parts["table_sets"][0], len(p.table_sets),
-            base + self.parts["frames"][0], len(p.route), len(p.segments), *geom, d_coef.data_ptr(), d_seg_status.data_ptr(), stream),
-            "tstar_jpeg_entropy_device")
-
+        _lib.check(_lib.load().tstar_jpeg_entropy_device(*self._head(d_buf, geom), d_coef.data_ptr(), d_seg_status.data_ptr(), stream),
+                   "tstar_jpeg_entropy_device")
 
     def launch_split(self, d_buf, d_coef, d_seg_status, d_seg_info, d_workspace, geom, stream: int, sub_bytes: int = SPLIT_SUB_BYTES,
                      min_split_bytes: int = SPLIT_MIN_BYTES, max_rounds: int = SPLIT_MAX_ROUNDS) -> None:
         """launch() through the split path: d_seg_info int32 [>= n_segments]; d_workspace uint8, 8-byte aligned, at least
         split_workspace_bytes(self.total, n_segments, sub_bytes)."""
         from . import _lib
-        p = self.plan
-        base = d_buf.data_ptr()
         _lib.check(_lib.load().tstar_jpeg_entropy_split_device(
-            base, self.total, base + self.parts["segments"][0], base + self.parts["table_sets"][0], len(p.table_sets),
-            base + self.parts["frames"][0], len(p.route), len(p.segments), *geom, sub_bytes, min_split_bytes, max_rounds,
-            d_workspace.data_ptr(), d_workspace.numel() * d_workspace.element_size(), d_coef.data_ptr(), d_seg_status.data_ptr(),
-            d_seg_info.data_ptr(), stream), "tstar_jpeg_entropy_split_device")
+            *self._head(d_buf, geom), sub_bytes, min_split_bytes, max_rounds, d_workspace.data_ptr(),
+            d_workspace.numel() * d_workspace.element_size(), d_coef.data_ptr(), d_seg_status.data_ptr(), d_seg_info.data_ptr(), stream),
+            "tstar_jpeg_entropy_split_device")
 
 
 def _pillow_rgb(data: bytes, label: str) -> np.ndarray:
