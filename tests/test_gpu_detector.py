@@ -41,7 +41,7 @@ def setup():
     ids, am = _token_ids(["couch", "tv", "chair", ""])
     weights = [1.0, 0.5, 0.5, 0.5]
     scorer.set_queries(ids, am, weights)
-    return dict(scorer=scorer, wv=wv, wt=wt, ids=ids, am=am, names=names, weights=weights)
+    return dict(scorer=scorer, wv=wv, wt=wt, ids=ids, am=am, names=names, weights=weights, vb=vb, tb=tb)
 
 
 @pytest.fixture(scope="module")
@@ -388,3 +388,97 @@ def test_install_queries_many_equals_one_by_one():
     for (slot, t, c, o2w), f in zip(yitems, feats):
         y.install_queries(slot, t, c, o2w)
         assert np.array_equal(y.text_tower.get_query_embeds(0), f), slot          # install_queries encodes through text slot 0
+
+
+_RESULT_KEYS = ("scores", "labels", "boxes", "cell_conf", "cell_mask", "n_kept")
+
+
+def _same_image(batch, b, one, keys):
+    return all(torch.equal(getattr(batch, k)[b], getattr(one, k)[0]) for k in keys)
+
+
+@pytest.mark.parametrize("family", ["owlvit", "owlv2"])
+def test_owl_staging_grows_and_is_reused(family):
+    """The handle's grow-on-demand staging (image -> query-set array, the u8 image of the horizontal resampling pass; OWLv2: the
+    per-image clip bounds) over a call sequence that grows it, reuses it and grows it again, on the smallest geometry (input 64 x 96:
+    6 patches at B/32, 24 at OWLv2's B/16) with two resident query sets of different sizes: every batch equals its single-image calls bit for bit, and
+    the first call repeated at the end returns what it returned at the start."""
+    from tstar_amd.owl import OwlScorer
+    keys, kw = (_RESULT_KEYS, {}) if family == "owlvit" else (("scores", "objectness"), {"objectness": True})
+    sc = OwlScorer.synthetic(0, max_batch=4, input_size=(64, 96), family=family)
+    assert sc.num_patches == (6 if family == "owlvit" else 24)
+    sets = {0: ["couch", "tv", "chair", ""], 5: ["dog", "leash", ""]}
+    for slot, names in sets.items():
+        ids, am = _token_ids(names)
+        sc.set_queries(ids, am, [1.0] + [0.5] * (len(names) - 1), slot=slot)
+    img, big = torch.from_numpy(_images(3, 40, 56, 31)).cuda(), torch.from_numpy(_images(4, 88, 120, 32)).cuda()
+    # B = 1; B = 3 grows image_set (and tmp_u8 / minmax); B = 2 fits; OWL-ViT: B = 4 of the larger source grows tmp_u8 again
+    calls = [(img[:1], [5]), (img, [0, 5, 0]), (img[1:], [5, 0])] + ([(big, [5, 0, 0, 5])] if family == "owlvit" else [])
+    batches = [sc.score(x, 2, 2, image_sets=s, **kw) for x, s in calls]
+    for (x, s), r in zip(calls, batches):
+        for b in range(len(s)):
+            one = sc.score(x[b:b + 1], 2, 2, image_sets=s[b:b + 1], **kw)
+            assert _same_image(r, b, one, keys), (len(s), b)
+    again = sc.score(img[:1], 2, 2, image_sets=[5], **kw)
+    assert _same_image(batches[0], 0, again, keys)
+    assert int(batches[1].labels[1].max()) < 3 and int(batches[1].labels[0].max()) < 4      # a label stays inside its own set
+    sc.close()
+
+
+def test_set_queries_many_group_boundaries(setup):
+    """tstar_owl_set_queries_many where lane 0 holds 40 sequences per forward (max_batch = 1 at 768 x 768, B/32: 640 rows -- the
+    text-only handle of the YOLO-World backend has the same lane; this one has a vision tower too, so that query masks and class
+    weights show in a score): set sizes (32, 8, 1) -- the first group exactly full -- then (32, 9) -- a set that does not fit opens
+    the next group.  Embeddings, Qs and, through the logits (a masked query's are -inf-like constants) and the cell confidences,
+    masks and weights of every slot equal one set_queries per slot bit for bit; tstar_owl_debug_text returns the same rows before
+    and after the batched call grew the staging; a token id out of range in the LAST set refuses the whole call before any slot is
+    installed."""
+    from tstar_amd import _lib, weights as W
+    from tstar_amd.owl import OwlScorer
+    sc = OwlScorer(setup["vb"], setup["tb"], max_batch=1)
+    rs = np.random.RandomState(7)
+    img = torch.from_numpy(_images(1, 95, 200, 41)).cuda()
+
+    def entry(slot, Q):
+        # [BOS or 0 (query mask 0: every fourth row, the first of a set among them), random ids, EOS, sometimes twice (first maximum), padding]
+        ids, am = np.zeros((Q, 16), np.int32), np.zeros((Q, 16), np.int32)
+        for q in range(Q):
+            toks = [49406 if q % 4 else 0] + list(rs.randint(1, 49000, rs.randint(0, 12))) + [49407] * int(rs.randint(1, 3))
+            ids[q, :len(toks)] = toks
+            am[q, :len(toks)] = 1
+        return (slot, ids, am, rs.uniform(0.1, 1.0, Q))
+
+    def debug_text(ids, am, stage):
+        out = np.empty((ids.shape[0] * (16 if stage == 0 else 1), 512), np.float32)
+        rc = sc._lib.tstar_owl_debug_text(sc._h, ids.ctypes.data, am.ctypes.data, ids.shape[0], stage, out.ctypes.data, _lib.stream_ptr())
+        _lib.check(rc, "tstar_owl_debug_text")
+        return out
+
+    def installed(slot):
+        r = sc.score(img, 1, 1, image_sets=[slot], want_logits=True, boxes=False)
+        return sc.Qs[slot], sc.get_query_embeds(slot), r.logits.cpu().numpy(), r.cell_conf.cpu().numpy(), r.cell_mask.cpu().numpy()
+
+    first = entry(1, 32)
+    before = [debug_text(first[1], first[2], stage) for stage in (0, 1)]
+    for sizes in ((32, 8, 1), (32, 9)):
+        entries = [first] + [entry(2 + k, Q) for k, Q in enumerate(sizes[1:])]
+        sc.set_queries_many(entries)
+        many = [installed(e[0]) for e in entries]
+        for (slot, ids, am, w), m in zip(entries, many):
+            sc.set_queries(ids, am, w, slot=slot)
+            one = installed(slot)
+            assert m[0] == one[0] == ids.shape[0]
+            assert all(np.array_equal(a, b) for a, b in zip(m[1:], one[1:])), (sizes, slot)
+    for stage in (0, 1):
+        assert np.array_equal(debug_text(first[1], first[2], stage), before[stage]), stage
+    # refused before anything is launched or installed: every slot keeps its size and its rows
+    held = {slot: sc.get_query_embeds(slot) for slot in (1, 2)}
+    qs = dict(sc.Qs)
+    bad = [entry(1, 3), entry(2, 4), entry(9, 2)]
+    bad[2][1][1, 3] = W.VOCAB
+    with pytest.raises(_lib.TStarHipError, match="tstar_owl_set_queries_many: token id out of range"):
+        sc.set_queries_many(bad)
+    assert sc.Qs == qs and 9 not in sc.Qs
+    for slot, e in held.items():
+        assert np.array_equal(sc.get_query_embeds(slot), e), slot
+    sc.close()

@@ -221,6 +221,36 @@ def test_wrapper_semantics_and_query_sets(yolo):
         det.detect(img, 4, 4, image_sets=[0, 9])
 
 
+
+def test_yolo_staging_grows_and_is_reused():
+    """The handle's grow-on-demand staging over a call sequence that grows all of it: slot 0 with Q = 2, a B = 1 detection; then
+    slot 1 with Q = 5 (four times the candidate entries per image) and a B = 2 detection of a larger source image with
+    image_sets = [1, 0] (the image -> query-set array, the resized u8 images).  Each image of the batch equals its single-image
+    call bit for bit, and the first call repeated returns what it returned at the start."""
+    from tstar_amd import yolo_world as Y
+    from tstar_amd.yolo import YoloDetector
+    det = YoloDetector(Y.synthetic_state_dict(0, "s"), "s", max_batch=2)
+    rs = np.random.RandomState(3)
+    txt = rs.standard_normal((7, 512)).astype(np.float32)
+    txt /= np.linalg.norm(txt, axis=1, keepdims=True)
+    keys = ("scores", "labels", "boxes", "n_kept", "cell_conf", "cell_mask")
+    same = lambda a, i, b, ks: all(torch.equal(getattr(a, k)[i], getattr(b, k)[0]) for k in ks)
+    det.set_text_feats(txt[:2], [1.0, 0.5])
+    small = torch.from_numpy(GU.detector_test_image(70, 95, 200)).cuda().unsqueeze(0)
+    first = det.detect(small, 2, 2, score_threshold=0.001, want_dense=True)
+    det.set_text_feats(txt[2:], [1.0, 0.5, 0.5, 0.25, 0.25], slot=1)
+    big = torch.from_numpy(np.stack([GU.detector_test_image(71 + b, 300, 400) for b in range(2)])).cuda()
+    both = det.detect(big, 2, 2, score_threshold=0.001, image_sets=[1, 0])
+    assert int(both.n_kept.min()) > 0 and int(first.n_kept[0]) > 0
+    for b, slot in enumerate([1, 0]):
+        one = det.detect(big[b:b + 1], 2, 2, score_threshold=0.001, image_sets=[slot], want_dense=True)
+        assert same(both, b, one, keys), b
+        assert one.dense_scores.shape[2] == (5, 2)[b] and int(one.labels[0].max()) < (5, 2)[b]
+    again = det.detect(small, 2, 2, score_threshold=0.001, want_dense=True)
+    assert same(first, 0, again, keys + ("dense_scores", "dense_boxes"))
+    det.close()
+
+
 def test_interface_surface_and_search_replay():
     """initialize_heuristic("yolo-World") -> YoloWorldInterface with the reference's surface; a T* search on the 3600-frame
     video through the fast path, replayed through the oracle searcher (same sampled seconds, histories, keyframes); the

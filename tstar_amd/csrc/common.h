@@ -27,6 +27,11 @@ void set_error(const std::string& msg);
         }                                                                            \
     } while (0)
 
+#define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+
+// a query-set slot of either detector handle (fn: the entry's name, a literal or a std::string)
+#define TSTAR_CHECK_SET(set, fn) TSTAR_REQUIRE((set) >= 0 && (set) < TSTAR_OWL_MAX_SETS, std::string(fn) + ": query_set must be in 0..63")
+
 // hipFuncAttributeMaxDynamicSharedMemorySize for kernels that need more than 64 KB of dynamic LDS: set once per
 // (kernel, device) under a mutex -- launches may come from several host threads and a process may use more than
 // one device (the attribute is applied to the kernel's code object of the CURRENT device).  Returns TSTAR_OK / TSTAR_ERR_HIP.

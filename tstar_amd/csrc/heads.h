@@ -1,6 +1,7 @@
 // Launchers of heads.hip / preprocess.hip / jpeg.hip (internal); the searcher ingest is ingest.h.
 #pragma once
-#include "common.h"
+#include "../../include/tstar_hip.h"
+#include "device_buf.h"
 
 namespace tstar {
 
@@ -37,6 +38,29 @@ int cell_reduce(const float* scores, const int* labels, const float* xyxy, const
 
 // paint the kept detections' boxes (score > thr) on u8 images [B,H,W,3] in place; xyxy [B,np,4], scores [B,np]
 int draw_boxes(uint8_t* images, int B, int H, int W, const float* xyxy, const float* scores, int np, float thr, hipStream_t s);
+
+// The per-image query sets of a call on either detector handle (Q[slot]: the queries installed there).  Every image's slot
+// (h_image_set[b]; slot 0 without an array) is in range and has queries installed -- `missing` says what is not there and which
+// entry installs it.  *q_uniform = the common Q when every image uses one set size, else 0; *q_max (optional) the largest.  A
+// passed array is copied into `staged` on stream s (grown when a larger batch arrives).
+static inline int check_query_sets(const std::string& fn, const char* missing, const int* Q, const int32_t* h_image_set, int B,
+                                   DeviceBuf<int>& staged, hipStream_t s, int* q_uniform, int* q_max = nullptr) {
+    int qu = -1, qm = 0;
+    for (int b = 0; b < B; ++b) {
+        const int set = h_image_set ? h_image_set[b] : 0;
+        TSTAR_CHECK_SET(set, fn);
+        if (Q[set] == 0) { set_error(fn + ": " + missing); return TSTAR_ERR_STATE; }
+        qu = (b == 0 || qu == Q[set]) ? Q[set] : 0;
+        qm = qm > Q[set] ? qm : Q[set];
+    }
+    if (h_image_set) {
+        RC(staged.reserve((size_t)B, s));
+        TSTAR_HIP_CHECK(hipMemcpyAsync(staged.p, h_image_set, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    *q_uniform = qu;
+    if (q_max) *q_max = qm;
+    return TSTAR_OK;
+}
 
 // ---- preprocess.hip: the detector's bicubic pass ----
 // Pillow-compatible fixed-point resampling tables for one axis (host side).

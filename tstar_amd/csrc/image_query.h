@@ -22,4 +22,9 @@ static inline ImageQueryOut image_query_out_offset(const ImageQueryOut& o, int b
 // cls [n * np, 512], boxes_cxcywh [n * np, 4]: one workgroup per image; np <= IMAGE_QUERY_MAX_NP
 int image_query_select(const float* cls, const float* boxes_cxcywh, int n, int np, const ImageQueryOut& out, hipStream_t s);
 
+// The end of an image-query entry `fn`: with rc == 0 the device results go to the caller's host arrays; the stream is synchronised
+// and the staging buffer d_buf (what image_query_out_at carved `o` from) freed either way.  Returns rc, or the copies' error.
+int image_query_finish(const char* fn, int rc, void* d_buf, const ImageQueryOut& o, int n, float* h_embeds, int32_t* h_best, float* h_boxes,
+                       int32_t* h_n_selected, int32_t* h_status, hipStream_t s);
+
 }  // namespace tstar

@@ -185,4 +185,21 @@ ImageQueryOut image_query_out_at(void* d_buf, int n) {
     return o;
 }
 
+int image_query_finish(const char* fn, int rc, void* d_buf, const ImageQueryOut& o, int n, float* h_embeds, int32_t* h_best, float* h_boxes,
+                       int32_t* h_n_selected, int32_t* h_status, hipStream_t s) {
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        e = hipMemcpyAsync(h_embeds, o.embeds, (size_t)n * 512 * sizeof(float), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_boxes, o.boxes, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_best, o.best, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_n_selected, o.n_selected, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_status, o.status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t e2 = hipStreamSynchronize(s);             // also before the staging buffer is freed after a failed launch
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(d_buf);
+    if (!rc && e != hipSuccess) { set_error(std::string(fn) + ": " + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
+    return rc;
+}
+
 }  // namespace tstar

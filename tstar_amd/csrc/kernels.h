@@ -40,6 +40,15 @@ enum GemmTileCfg {
     TILE_HYBRID_N = 16,   // 16 + n: hybrid with n big row tiles (diagnostic, tile-policy sweeps)
 };
 
+// a launch on the f32 matrix alone: no converted weight plane, no patch epilogue, the launcher's tile choice
+static inline GemmArgs gemm_args(const float* A, const float* W, float* C, const float* bias, const float* res, int M, int N, int K, int lda, int ldc,
+                                 int act) {
+    GemmArgs g{};
+    g.A = A; g.W = W; g.C = C; g.bias = bias; g.res = res;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldc = ldc; g.act = act; g.tile_cfg = TILE_AUTO;
+    return g;
+}
+
 // How a launch reads its weights; the values are the WMODE template argument of the kernels.
 enum GemmWeightMode {
     GEMM_W_F32 = 0,       // native f32 MFMA

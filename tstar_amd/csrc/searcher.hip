@@ -408,8 +408,6 @@ struct tstar_searcher {
     size_t lds = 0;
 };
 
-#define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 extern "C" {
 
 int tstar_searcher_destroy(tstar_searcher* s) {

@@ -1320,11 +1320,12 @@ struct tstar_yolo {
     int Q[YOLO_SETS] = {0};
     float *d_text = nullptr, *d_textn = nullptr;              // [sets][32][512] raw / normalised
     double* d_qweight = nullptr;
-    int *d_setQ = nullptr, *d_image_set = nullptr, *d_iota = nullptr, *d_cand_count = nullptr;
-    int image_set_cap = 0;
-    uint8_t* d_tmp_u8 = nullptr; size_t tmp_u8_bytes = 0;
+    int *d_setQ = nullptr, *d_iota = nullptr, *d_cand_count = nullptr;
+    DeviceBuf<int> image_set;                                 // the image -> query set array of a call
+    DeviceBuf<uint8_t> tmp_u8;                                // the chunk's images at the letterbox's inner size
     float* d_boxes = nullptr;                                 // [max_batch, n_anchor, 4]
-    unsigned long long* d_cand = nullptr; int cand_cap = 0;   // [max_batch, cand_cap]
+    DeviceBuf<unsigned long long> cand;                       // [max_batch, cand_cap()]
+    int cand_cap() const { return (int)(cand.cap / max_batch); }
 };
 
 // element offset of the zero quad behind a source buffer of max_batch images; 0 = beyond the 32-bit byte offsets of the scalar-weight forms
@@ -1333,17 +1334,15 @@ static unsigned conv_zoff(int max_batch, int H, int W, int ld) {
     return zo < (1ull << 30) ? (unsigned)zo : 0;
 }
 
-#define RC(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 static size_t pow2_at_least(size_t v) { size_t p = 1; while (p < v) p <<= 1; return p; }
 
 extern "C" {
 
 int tstar_yolo_destroy(tstar_yolo* h) {
     if (!h) return TSTAR_OK;
-    void* ptrs[] = {h->d_blob, h->d_blob_t, h->d_text, h->d_textn, h->d_qweight, h->d_setQ, h->d_image_set, h->d_iota, h->d_cand_count,
-                    h->d_tmp_u8, h->d_boxes, h->d_cand};
+    void* ptrs[] = {h->d_blob, h->d_blob_t, h->d_text, h->d_textn, h->d_qweight, h->d_setQ, h->d_iota, h->d_cand_count, h->d_boxes};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    h->image_set.release(); h->tmp_u8.release(); h->cand.release();
     for (float* p : h->bufs) if (p) (void)hipFree(p);
     for (auto& g : h->guides) if (g.d_guide) (void)hipFree(g.d_guide);
     delete h;
@@ -1490,11 +1489,9 @@ int tstar_yolo_create(tstar_yolo** out, const float* h_blob, size_t n_blob, cons
     return TSTAR_OK;
 }
 
-#define YCHECK_SET(set, fn) TSTAR_REQUIRE((set) >= 0 && (set) < YOLO_SETS, fn ": query_set must be in 0..63")
-
 int tstar_yolo_set_text_feats(tstar_yolo* h, int query_set, const float* h_text, const double* h_class_weight, int Q, void* stream) {
     TSTAR_REQUIRE(h && h_text && h_class_weight, "tstar_yolo_set_text_feats: null argument");
-    YCHECK_SET(query_set, "tstar_yolo_set_text_feats");
+    TSTAR_CHECK_SET(query_set, "tstar_yolo_set_text_feats");
     TSTAR_REQUIRE(Q >= 1 && Q <= YOLO_MAX_Q, "tstar_yolo_set_text_feats: Q must be in 1..32");
     hipStream_t s = (hipStream_t)stream;
     const size_t qo = (size_t)query_set * YOLO_MAX_Q;
@@ -1513,7 +1510,7 @@ int tstar_yolo_set_text_feats(tstar_yolo* h, int query_set, const float* h_text,
 
 int tstar_yolo_set_class_weights(tstar_yolo* h, int query_set, const double* h_class_weight, int Q, void* stream) {
     TSTAR_REQUIRE(h && h_class_weight, "tstar_yolo_set_class_weights: null argument");
-    YCHECK_SET(query_set, "tstar_yolo_set_class_weights");
+    TSTAR_CHECK_SET(query_set, "tstar_yolo_set_class_weights");
     TSTAR_REQUIRE(Q == h->Q[query_set] && Q >= 1, "tstar_yolo_set_class_weights: Q does not match the installed text features");
     hipStream_t s = (hipStream_t)stream;
     TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_qweight + (size_t)query_set * YOLO_MAX_Q, h_class_weight, Q * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1567,32 +1564,10 @@ static int run_program(tstar_yolo* h, int B, const int* d_image_set, hipStream_t
 // mmyolo test pipeline geometry: YOLOv5KeepRatioResize(640) then LetterResize(640, allow_scale_up=False, pad 114)
 struct YoloGeom { double ratio, sfw, sfh; int rw, rh, top, left; };
 
-// The per-image query sets of a batch: checked against the installed text features and uploaded to d_image_set.
-static int yolo_query_sets(tstar_yolo* h, const std::string& f, int B, const int32_t* h_image_query_set, hipStream_t s, int* q_uniform_out, int* q_max_out) {
-    int q_uniform = -1, q_max = 0;
-    for (int b = 0; b < B; ++b) {
-        const int set = h_image_query_set ? h_image_query_set[b] : 0;
-        TSTAR_REQUIRE(set >= 0 && set < YOLO_SETS, f + ": query_set must be in 0..63");
-        if (h->Q[set] == 0) { set_error(f + ": no text features installed in the requested query set (call tstar_yolo_set_text_feats first)"); return TSTAR_ERR_STATE; }
-        q_uniform = (b == 0 || q_uniform == h->Q[set]) ? h->Q[set] : 0;
-        q_max = q_max > h->Q[set] ? q_max : h->Q[set];
-    }
-    if (h_image_query_set) {
-        if (B > h->image_set_cap) {
-            TSTAR_HIP_CHECK(hipStreamSynchronize(s));
-            if (h->d_image_set) TSTAR_HIP_CHECK(hipFree(h->d_image_set));
-            h->d_image_set = nullptr; h->image_set_cap = 0;
-            TSTAR_HIP_CHECK(hipMalloc(&h->d_image_set, (size_t)B * sizeof(int)));
-            h->image_set_cap = B;
-        }
-        TSTAR_HIP_CHECK(hipMemcpyAsync(h->d_image_set, h_image_query_set, (size_t)B * sizeof(int), hipMemcpyHostToDevice, s));
-    }
-    *q_uniform_out = q_uniform; *q_max_out = q_max;
-    return TSTAR_OK;
-}
+static const char* const NO_TEXT_FEATS = "no text features installed in the requested query set (call tstar_yolo_set_text_feats first)";
 
 // What tstar_yolo_detect and tstar_yolo_postprocess share before the first launch: argument checks, the per-image query
-// sets (uploaded to d_image_set), the candidate lists' capacity and the letterbox geometry of an H x W image.
+// sets (uploaded to image_set), the candidate lists' capacity and the letterbox geometry of an H x W image.
 static int yolo_prepare(tstar_yolo* h, const char* fn, int B, int H, int W, int grid_rows, int grid_cols, const int32_t* h_image_query_set,
                         int max_dets, const double* d_cell_conf, const uint32_t* d_cell_mask, const float* d_dense_scores, hipStream_t s,
                         int* q_uniform_out, YoloGeom* g) {
@@ -1602,17 +1577,10 @@ static int yolo_prepare(tstar_yolo* h, const char* fn, int B, int H, int W, int 
     TSTAR_REQUIRE(!d_cell_conf == !d_cell_mask, f + ": cell_conf and cell_mask go together");
     TSTAR_REQUIRE(!d_cell_conf || (grid_rows >= 1 && grid_cols >= 1 && grid_rows * grid_cols <= 4096), f + ": grid must have 1..4096 cells");
     int q_uniform = -1, q_max = 0;
-    RC(yolo_query_sets(h, f, B, h_image_query_set, s, &q_uniform, &q_max));
+    RC(check_query_sets(f, NO_TEXT_FEATS, h->Q, h_image_query_set, B, h->image_set, s, &q_uniform, &q_max));
     TSTAR_REQUIRE(!d_dense_scores || q_uniform > 0, f + ": dense scores need the same query count for every image");
     // candidate lists: every (anchor, class) pair can qualify
-    const int need_cap = (int)pow2_at_least((size_t)h->n_anchor * q_max);
-    if (need_cap > h->cand_cap) {
-        TSTAR_HIP_CHECK(hipStreamSynchronize(s));
-        if (h->d_cand) TSTAR_HIP_CHECK(hipFree(h->d_cand));
-        h->d_cand = nullptr; h->cand_cap = 0;
-        TSTAR_HIP_CHECK(hipMalloc(&h->d_cand, (size_t)h->max_batch * need_cap * sizeof(unsigned long long)));
-        h->cand_cap = need_cap;
-    }
+    RC(h->cand.reserve((size_t)h->max_batch * pow2_at_least((size_t)h->n_anchor * q_max), s));
     g->ratio = fmin(640.0 / (H > W ? H : W), 640.0 / (H < W ? H : W));
     g->rw = g->ratio != 1.0 ? (int)(W * g->ratio) : W; g->rh = g->ratio != 1.0 ? (int)(H * g->ratio) : H;
     TSTAR_REQUIRE(g->rw >= 1 && g->rh >= 1 && g->rw <= YOLO_IMG && g->rh <= YOLO_IMG, f + ": image shape outside the letterbox geometry");
@@ -1641,7 +1609,7 @@ static int yolo_tail(tstar_yolo* h, const float* const* E, const float* const* R
         a.anchor0 = anchor0; a.n_anchor = h->n_anchor; a.logit_scale = l.logit_scale; a.bias = l.bias;
         a.textn = h->d_textn; a.setQ = h->d_setQ; a.image_set = d_sets;
         a.pad_left = (float)g.left; a.pad_top = (float)g.top; a.sf_w = (float)g.sfw; a.sf_h = (float)g.sfh; a.cand_thr = cand_thr;
-        a.boxes = h->d_boxes; a.cand = h->d_cand; a.cand_cap = h->cand_cap; a.cand_count = h->d_cand_count;
+        a.boxes = h->d_boxes; a.cand = h->cand.p; a.cand_cap = h->cand_cap(); a.cand_count = h->d_cand_count;
         a.dense_scores = d_dense_scores ? d_dense_scores + (size_t)b0 * h->n_anchor * q_uniform : nullptr; a.dense_q = q_uniform;
         const int rows = Bc * a.HW;
         hipLaunchKernelGGL(head_decode_kernel, dim3(cdiv(rows, HD_APB)), dim3(256), 0, s, a, rows);
@@ -1649,7 +1617,7 @@ static int yolo_tail(tstar_yolo* h, const float* const* E, const float* const* R
         anchor0 += a.HW;
     }
     RC(ensure_dyn_lds(reinterpret_cast<const void*>(sort_nms_kernel), NMS_LDS_KEYS * 8));
-    hipLaunchKernelGGL(sort_nms_kernel, dim3(Bc), dim3(1024), (size_t)NMS_LDS_KEYS * 8, s, h->d_cand, h->cand_cap, h->d_cand_count, h->d_boxes, h->n_anchor,
+    hipLaunchKernelGGL(sort_nms_kernel, dim3(Bc), dim3(1024), (size_t)NMS_LDS_KEYS * 8, s, h->cand.p, h->cand_cap(), h->d_cand_count, h->d_boxes, h->n_anchor,
                        (float)W, (float)H, score_threshold, max_dets, d_det_scores + (size_t)b0 * max_dets, d_det_labels + (size_t)b0 * max_dets,
                        d_det_boxes + (size_t)b0 * max_dets * 4, d_n_det + b0);
     TSTAR_HIP_CHECK(hipGetLastError());
@@ -1688,22 +1656,15 @@ int tstar_yolo_detect(tstar_yolo* h, const uint8_t* d_images, int B, int H, int 
         const uint8_t* imgs = d_images + (size_t)b0 * H * W * 3;
         const uint8_t* packed_src = imgs;
         if (rw != W || rh != H) {
-            const size_t need = (size_t)Bc * rh * rw * 3;
-            if (need > h->tmp_u8_bytes) {
-                TSTAR_HIP_CHECK(hipStreamSynchronize(s));
-                if (h->d_tmp_u8) TSTAR_HIP_CHECK(hipFree(h->d_tmp_u8));
-                h->d_tmp_u8 = nullptr; h->tmp_u8_bytes = 0;
-                TSTAR_HIP_CHECK(hipMalloc(&h->d_tmp_u8, need));
-                h->tmp_u8_bytes = need;
-            }
+            RC(h->tmp_u8.reserve((size_t)Bc * rh * rw * 3, s));
             if (g.ratio < 1.0) {
                 const size_t total = (size_t)Bc * rh * rw;
-                hipLaunchKernelGGL(area_resize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, imgs, H, W, h->d_tmp_u8, rh, rw, total);
+                hipLaunchKernelGGL(area_resize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, imgs, H, W, h->tmp_u8.p, rh, rw, total);
                 TSTAR_HIP_CHECK(hipGetLastError());
             } else {
-                RC(bilinear_gather_u8(imgs, H, W, h->d_iota, Bc, rw, rh, h->d_tmp_u8, 0, s));
+                RC(bilinear_gather_u8(imgs, H, W, h->d_iota, Bc, rw, rh, h->tmp_u8.p, 0, s));
             }
-            packed_src = h->d_tmp_u8;
+            packed_src = h->tmp_u8.p;
         }
         {
             const size_t total = (size_t)Bc * YOLO_IMG * YOLO_IMG;
@@ -1711,7 +1672,7 @@ int tstar_yolo_detect(tstar_yolo* h, const uint8_t* d_images, int B, int H, int 
                                h->bufs[h->input_buf], total);
             TSTAR_HIP_CHECK(hipGetLastError());
         }
-        const int* d_sets = h_image_query_set ? h->d_image_set + b0 : nullptr;
+        const int* d_sets = h_image_query_set ? h->image_set.p + b0 : nullptr;
         RC(run_program(h, Bc, d_sets, s));
         const float* E[8]; const float* R[8];
         for (size_t li = 0; li < h->levels.size(); ++li) { E[li] = h->bufs[h->levels[li].e_buf]; R[li] = h->bufs[h->levels[li].r_buf]; }
@@ -1733,14 +1694,14 @@ int tstar_yolo_postprocess(tstar_yolo* h, const float* const* d_level_embed, con
     YoloGeom g{};
     RC(yolo_prepare(h, "tstar_yolo_postprocess", B, H, W, grid_rows, grid_cols, h_image_query_set, max_dets, d_cell_conf, d_cell_mask, d_dense_scores,
                     s, &q_uniform, &g));
-    for (int b0 = 0; b0 < B; b0 += h->max_batch) {                   // chunked like detect: d_boxes / d_cand hold max_batch images
+    for (int b0 = 0; b0 < B; b0 += h->max_batch) {                   // chunked like detect: d_boxes / cand hold max_batch images
         const int Bc = (B - b0) < h->max_batch ? (B - b0) : h->max_batch;
         const float* E[8]; const float* R[8];
         for (int l = 0; l < n_levels; ++l) {
             const size_t row0 = (size_t)b0 * h->levels[l].size * h->levels[l].size;
             E[l] = d_level_embed[l] + row0 * YOLO_TEXT; R[l] = d_level_dfl[l] + row0 * 4 * YOLO_REG_MAX;
         }
-        RC(yolo_tail(h, E, R, b0, Bc, H, W, g, h_image_query_set ? h->d_image_set + b0 : nullptr, q_uniform, grid_rows, grid_cols, score_threshold,
+        RC(yolo_tail(h, E, R, b0, Bc, H, W, g, h_image_query_set ? h->image_set.p + b0 : nullptr, q_uniform, grid_rows, grid_cols, score_threshold,
                      max_dets, d_det_scores, d_det_labels, d_det_boxes, d_n_det, d_cell_conf, d_cell_mask, d_dense_scores, d_dense_boxes, s));
     }
     return TSTAR_OK;
@@ -1764,10 +1725,10 @@ int tstar_yolo_run_ops(tstar_yolo* h, int B, const int32_t* h_image_query_set, i
     TSTAR_REQUIRE(B >= 1 && B <= h->max_batch, "tstar_yolo_run_ops: B must be in 1..max_batch");
     hipStream_t s = (hipStream_t)stream;
     if (!h->guides.empty()) {                                            // only the attention ops read the query sets
-        int q_uniform = 0, q_max = 0;
-        RC(yolo_query_sets(h, "tstar_yolo_run_ops", B, h_image_query_set, s, &q_uniform, &q_max));
+        int q_uniform = 0;
+        RC(check_query_sets("tstar_yolo_run_ops", NO_TEXT_FEATS, h->Q, h_image_query_set, B, h->image_set, s, &q_uniform));
     }
-    RC(run_program(h, B, h_image_query_set && !h->guides.empty() ? h->d_image_set : nullptr, s, h_forms));
+    RC(run_program(h, B, h_image_query_set && !h->guides.empty() ? h->image_set.p : nullptr, s, h_forms));
     TSTAR_HIP_CHECK(hipStreamSynchronize(s));
     return TSTAR_OK;
 }
