@@ -30,7 +30,11 @@ ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]
 # likewise preprocess_v2.hip: its float64 filter / zoom sums (device) and tables (host) are scipy's bits only without contraction
 # image_query.hip: the IoU / GIoU arithmetic selects torch's rows only as plain float32 operations
-PER_FILE = {"searcher.hip": ["-ffp-contract=off"], "preprocess_v2.hip": ["-ffp-contract=off"], "image_query.hip": ["-ffp-contract=off"]}
+PER_FILE = {"searcher.hip": ["-ffp-contract=off"], "preprocess_v2.hip": ["-ffp-contract=off"], "image_query.hip": ["-ffp-contract=off"],
+            # attention_x3.hip: the SLP vectoriser pairs the scalar f32 subtractions / multiplies of the key loop into v_pk_add_f32 /
+            # v_pk_mul_f32, which issue slower beside MFMAs than their two scalar halves; same bits either way (tools/attention_x3_isa.py,
+            # profiles/attention_x3_issue_stream.md).  tools/lab/attn_lab is built with the same flag.
+            "attention_x3.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

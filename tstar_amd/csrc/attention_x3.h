@@ -32,6 +32,13 @@
 //    154 TFLOP/s algorithmic (0.92 PFLOP/s executed) against 120-125 for attention_f32_kernel, 147 vs 103 inside the bench; error
 //    against float64 below the f32 kernel's (tests/test_gpu_kernels.py::test_attention_x3).  Matrix pipe busy 0.51: the kernel is
 //    bound by VALU issue, 7.5 VALU instructions per MFMA (the exact splits of P and of the staged K / V cost 5.5 per element).
+//  * compiled form (tools/attention_x3_isa.py, tests/test_attention_x3_compiled_form.py, profiles/attention_x3_issue_stream.md): the
+//    file is built with -fno-slp-vectorize (build.py; the lab alike).  Under plain -O3 the SLP vectoriser paired the scalar f32
+//    subtractions of split2_rn3 and the alpha rescale into v_pk_add_f32 / v_pk_mul_f32 (70 in the two-tile loop), which issue
+//    slower beside MFMAs than their scalar halves; it also decided which products of the prologue and of the straggler key were
+//    contracted into fused multiply-adds, so those are now written out (split2_rn3_scaled, rounded()).  The epilogue forms the
+//    lane's position again and the straggler's q values are kept behind the loops: 256 registers, no spill, no scratch (before:
+//    59 spilled registers, 240 bytes of scratch per lane).  Same bits (tests/test_gpu_attention_x3_same_bits.py).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -70,6 +77,24 @@ __device__ __forceinline__ void split2_rn3(float x0, float x1, unsigned (&o)[3])
         }
     }
 }
+// The same for the products (a0 sc, a1 sc) (the pre-scaled Q): the FIRST term is the rounded product's, the first remainder is taken
+// from the EXACT product (one fused multiply-add).  The kernel has computed Q this way since round 5 (the compiler had contracted
+// the scaling into the first subtraction); it is written out so that the bits do not hang on a compiler's choice of contraction.
+__device__ __forceinline__ void split2_rn3_scaled(float a0, float a1, float sc, unsigned (&o)[3]) {
+    f32x2 x; x[0] = a0 * sc; x[1] = a1 * sc;
+    unsigned hb = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
+    o[0] = hb;
+    x[0] = __builtin_fmaf(a0, sc, -__uint_as_float(hb << 16));
+    x[1] = __builtin_fmaf(a1, sc, -__uint_as_float(hb & 0xFFFF0000u));
+    hb = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
+    o[1] = hb;
+    x[0] = x[0] - __uint_as_float(hb << 16);
+    x[1] = x[1] - __uint_as_float(hb & 0xFFFF0000u);
+    o[2] = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
+}
+// x, unchanged, as a value the compiler knows nothing about (emits no instruction): a product passed through it is ROUNDED before it
+// is added, whatever the contraction mode
+__device__ __forceinline__ float rounded(float x) { asm volatile("" : "+v"(x)); return x; }
 // value of lane ^ 32 combined with this lane's, without the LDS pipe (gfx950 v_permlane32_swap)
 __device__ __forceinline__ float xhalf_max(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -130,10 +155,11 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const float* __res
         const float sc = 0.125f * 1.44269504088896340736f;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(src + 16 * s) * sc;
-            const f32x4 c = *reinterpret_cast<const f32x4*>(src + 16 * s + 4) * sc;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(src + 16 * s);
+            const f32x4 c = *reinterpret_cast<const f32x4*>(src + 16 * s + 4);
             unsigned o0[3], o1[3], o2[3], o3[3];
-            split2_rn3(a[0], a[1], o0); split2_rn3(a[2], a[3], o1); split2_rn3(c[0], c[1], o2); split2_rn3(c[2], c[3], o3);
+            split2_rn3_scaled(a[0], a[1], sc, o0); split2_rn3_scaled(a[2], a[3], sc, o1);
+            split2_rn3_scaled(c[0], c[1], sc, o2); split2_rn3_scaled(c[2], c[3], sc, o3);
 #pragma unroll
             for (int k = 0; k < 3; ++k) { qp[k][s][0] = o0[k]; qp[k][s][1] = o1[k]; qp[k][s][2] = o2[k]; qp[k][s][3] = o3[k]; }
         }
@@ -306,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const float* __res
             for (int r = 4 * c; r < 4 * c + 4; ++r) { sc_[r] = __builtin_amdgcn_exp2f(sc_[r] - m_new); ps += sc_[r]; }
         } else if constexpr (p == 6) {
             ps = xhalf_sum(ps);
-            l_run = l_run * alpha + ps;
+            l_run = __builtin_fmaf(l_run, alpha, ps);                        // fused, as it has always been compiled
         } else {
             constexpr int j = p - 7;                                         // pair j: r = 2 j, 2 j + 1 -> K = 16 step j >> 2, dword j & 3
             unsigned o[3];
@@ -451,8 +477,21 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const float* __res
         }
     }
 
+    // ---- epilogue.  The lane's position is formed AGAIN here (v_mbcnt: the compiler cannot tie it to threadIdx), so that neither q
+    // nor the output address occupies registers across the key loops, which run at the 256-register limit
+    const int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int h_e = lane_e >> 5;
+    const int q_e = qt * 128 + wave * 32 + (lane_e & 31);
+
     if (tail_key && wave_active) {
-        // straggler key T - 1 in f32 VALU arithmetic; q is rebuilt exactly from its three terms
+        // straggler key T - 1 in f32 VALU arithmetic; q is rebuilt exactly from its three terms.  The empty statements emit nothing:
+        // they keep the compiler from forming the 64 rebuilt values ahead of the key loops (it did, and spilled them around the loops)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(qp[k][s]));
+        }
+        const int h = h_e;
         const size_t ro = (rowbase + (T - 1)) * D3 + head * HD;
         float sx = 0.f;
 #pragma unroll
@@ -464,14 +503,18 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const float* __res
                 // element e of a plane dword pair: even -> low half, odd -> high half
                 auto term = [&](int k) { const unsigned dw = qp[k][s][e >> 1]; return __uint_as_float((e & 1) ? (dw & 0xFFFF0000u) : (dw << 16)); };
                 const float qv = (term(0) + term(1)) + term(2);
-                sx += (e < 4 ? k0[e] : k1[e - 4]) * qv;
+                const float kv = e < 4 ? k0[e] : k1[e - 4];
+                // one fused multiply-add per element, but the last four products are rounded before they are added: the form this
+                // sum has had since round 5 (then the compiler's choice), written out so that the bits are the source's
+                if (s == 3 && e >= 4) sx = sx + rounded(kv * qv);
+                else sx = __builtin_fmaf(kv, qv, sx);
             }
         }
         sx = xhalf_sum(sx);
         const float mn = fmaxf(m_run, sx);
         const float al = __builtin_amdgcn_exp2f(m_run - mn);
         const float p = __builtin_amdgcn_exp2f(sx - mn);
-        l_run = l_run * al + p;
+        l_run = __builtin_fmaf(l_run, al, p);
         m_run = mn;
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
@@ -479,15 +522,22 @@ __global__ __launch_bounds__(256, 2) void attention_x3_kernel(const float* __res
             const f32x4 v1 = *reinterpret_cast<const f32x4*>(qkv + ro + 2 * D + 32 + 8 * g4 + 4 * h);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                o0[g4 * 4 + e] = o0[g4 * 4 + e] * al + p * v0[e];
-                o1[g4 * 4 + e] = o1[g4 * 4 + e] * al + p * v1[e];
+                // o al is rounded, then p v joins it in one fused multiply-add; in the last two elements of either half both
+                // products are rounded (same history as the sum above)
+                if (g4 == 3 && e >= 2) {
+                    o0[g4 * 4 + e] = rounded(p * v0[e]) + rounded(o0[g4 * 4 + e] * al);
+                    o1[g4 * 4 + e] = rounded(p * v1[e]) + rounded(o1[g4 * 4 + e] * al);
+                } else {
+                    o0[g4 * 4 + e] = __builtin_fmaf(p, v0[e], o0[g4 * 4 + e] * al);
+                    o1[g4 * 4 + e] = __builtin_fmaf(p, v1[e], o1[g4 * 4 + e] * al);
+                }
             }
         }
     }
 
-    if (q < T) {
+    if (q_e < T) {
         const float inv = 1.0f / l_run;
-        float* op = out + (rowbase + q) * D + head * HD + 4 * h;
+        float* op = out + (rowbase + q_e) * D + head * HD + 4 * h_e;
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             f32x4 a, c;
