@@ -12,6 +12,7 @@ a Motion-JPEG .avi, a .mjpeg stream, a folder of .jpg frames (--video-fps for th
   python examples/run_dataset.py --items 8 --out /tmp/results.json
   python examples/run_dataset.py --videos clips/a.avi clips/b_frames/ --video-fps 1
   python examples/run_dataset.py --query-image mug=shots/my_mug.png --query-image dog=shots/rex.jpg
+  python examples/run_dataset.py --query-image mug=shots/desk.png@120,40,260,210
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 examples/run_dataset.py --items 32
 """
 import argparse
@@ -48,9 +49,10 @@ def main():
     ap.add_argument("--jpeg-entropy", choices=("host", "device"), default=None,
                     help="where Motion-JPEG / JPEG-folder videos are entropy-decoded (default: TSTAR_JPEG_ENTROPY, else host); "
                          "'device' keeps the Huffman decode off the rank's CPUs")
-    ap.add_argument("--query-image", action="append", default=[], metavar="NAME=PATH",
+    ap.add_argument("--query-image", action="append", default=[], metavar="NAME=PATH[@x0,y0,x1,y1]",
                     help="example image of an object (repeatable): every target / cue object called NAME is searched for by the "
-                         "image-guided query embedded from PATH instead of by its text")
+                         "image-guided query embedded from PATH instead of by its text; @x0,y0,x1,y1 (pixels of that image) "
+                         "means only that region of it")
     args = ap.parse_args()
 
     import torch
@@ -95,9 +97,17 @@ def main():
     query_images = {}
     for spec in args.query_image:
         name, sep, path = spec.partition("=")
+        box = None
+        head, at, tail = path.rpartition("@")
+        if at and tail.count(",") == 3:
+            try:
+                box = tuple(float(v) for v in tail.split(","))
+                path = head
+            except ValueError:
+                ap.error(f"--query-image: the box of {spec!r} must be four numbers x0,y0,x1,y1")
         if not sep or not name.strip() or not path:
-            ap.error(f"--query-image must look like NAME=PATH, not {spec!r}")
-        query_images[name.strip()] = path
+            ap.error(f"--query-image must look like NAME=PATH or NAME=PATH@x0,y0,x1,y1, not {spec!r}")
+        query_images[name.strip()] = path if box is None else (path, box)
     if query_images:
         heuristic.set_query_images(query_images)
     mine = shard_items(len(items), world, rank)

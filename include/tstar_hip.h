@@ -299,6 +299,36 @@ int tstar_owl_embed_image_queries(tstar_owl* h, const uint8_t* d_images, int n, 
 int tstar_image_query_select(const float* d_cls, const float* d_boxes_cxcywh, int n, int np, float* h_embeds, int32_t* h_best,
                              float* h_boxes_cxcywh, int32_t* h_n_selected, int32_t* h_status, void* stream);
 
+/* Query boxes (added entries; tstar_abi_version() stays 3): the same selection against a per-example query box instead of the unit
+ * box -- "this region of the example" -- with HF's box_iou / generalized_box_iou in their general form: area_q = (x1-x0)(y1-y0),
+ * inter from max of the top-left and min of the bottom-right corners clamped at 0, union = (area_q + area_p) - inter, iou = inter /
+ * union; the GIoU fallback uses the enclosing box of the two.  Boxes are (x0, y0, x1, y1), relative, float32.
+ * tstar_image_query_select_box: tstar_image_query_select plus d_boxes_q f32 [n,4] on the DEVICE (NULL: unit boxes).
+ * tstar_owl_embed_image_queries_box: tstar_owl_embed_image_queries plus h_query_boxes f32 [n,4] on the HOST (NULL: unit boxes).
+ * With NULL or unit boxes both return the bits of the entries above, which are calls of these with NULL. */
+int tstar_owl_embed_image_queries_box(tstar_owl* h, const uint8_t* d_images, int n, int H, int W, const float* h_query_boxes,
+                                      float* h_embeds, int32_t* h_best, float* h_boxes_cxcywh, int32_t* h_n_selected, int32_t* h_status,
+                                      void* stream);
+int tstar_image_query_select_box(const float* d_cls, const float* d_boxes_cxcywh, const float* d_boxes_q, int n, int np, float* h_embeds,
+                                 int32_t* h_best, float* h_boxes_cxcywh, int32_t* h_n_selected, int32_t* h_status, void* stream);
+
+/* HF's post_process_image_guided_detection (added entries; tstar_abi_version() stays 3), bit for bit in float32.  Per image:
+ * d_scores f32 [B,np] (the sigmoid of the max logit over the queries: what tstar_owl_score returns as d_scores), d_boxes_cxcywh
+ * f32 [B,np,4] (relative) -> d_alphas f32 [B,np], d_boxes_xyxy f32 [B,np,4] (corners cx -+ 0.5 w, cy -+ 0.5 h, scaled by (sx, sy, sx,
+ * sy)), d_keep u8 [B,np] (alpha > 0; HF returns these rows, in patch order), d_n_kept i32 [B].  When nms_threshold < 1: greedy NMS in
+ * descending score order (equal scores: lowest index first; torch's argsort leaves ties open), a candidate with score 0 is skipped, a
+ * live candidate i zeroes every j != i with inter / ((area_i + area_j) - inter) > nms_threshold (a NaN IoU suppresses nothing).  An
+ * image with no non-zero score left has all-zero alphas and keeps nothing (HF drops it from its result list; here its entry is
+ * empty).  Otherwise scores < threshold become 0, m = max + 1e-6f, alpha = clip((s - m * 0.1f) / (m * 0.9f), 0, 1).
+ * h_scale_xy: HOST f32 [B,2] (sx, sy) per image, or NULL (no scaling, HF's target_sizes=None; the call is then asynchronous,
+ * otherwise it synchronises the stream).  One workgroup per image, no atomics; np in 1..3600, TSTAR_ERR_ARG beyond with nothing
+ * launched.  tstar_image_guided_postprocess_host: the same statements on HOST arrays (no device is touched), scale_xy NULL or [B,2]. */
+int tstar_image_guided_postprocess(const float* d_scores, const float* d_boxes_cxcywh, int B, int np, float threshold, float nms_threshold,
+                                   const float* h_scale_xy, float* d_alphas, float* d_boxes_xyxy, uint8_t* d_keep, int32_t* d_n_kept,
+                                   void* stream);
+int tstar_image_guided_postprocess_host(const float* scores, const float* boxes_cxcywh, int B, int np, float threshold, float nms_threshold,
+                                        const float* scale_xy, float* alphas, float* boxes_xyxy, uint8_t* keep, int32_t* n_kept);
+
 /* ------------------------------------------------------------------ second detector backend: YOLO-World (D13)
  * Replaces YoloWorldInterface (interface_heuristic.py:39-190; wired at TStarFramework.py:178-184) -- the mmdet test
  * pipeline (keep-ratio resize to 640, letterbox pad 114, /255, channel swap), model.test_step (YOLOv8 CSPDarknet,

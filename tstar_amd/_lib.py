@@ -56,6 +56,10 @@ SIGNATURES = {
     "tstar_cell_reduce": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp]),
     "tstar_owl_embed_image_queries": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tstar_image_query_select": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tstar_owl_embed_image_queries_box": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tstar_image_query_select_box": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tstar_image_guided_postprocess": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tstar_image_guided_postprocess_host": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "tstar_yolo_create": (_i, [C.POINTER(_vp), _vp, _sz, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i]),
     "tstar_yolo_destroy": (_i, [_vp]),
     "tstar_yolo_num_anchors": (_i, [_vp]),

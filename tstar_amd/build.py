@@ -30,7 +30,9 @@ ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]
 # likewise preprocess_v2.hip: its float64 filter / zoom sums (device) and tables (host) are scipy's bits only without contraction
 # image_query.hip: the IoU / GIoU arithmetic selects torch's rows only as plain float32 operations
+# image_guided_post.hip / image_guided_post_host.cpp: the NMS compares IoUs with a threshold; torch's side of it needs plain float32 operations
 PER_FILE = {"searcher.hip": ["-ffp-contract=off"], "preprocess_v2.hip": ["-ffp-contract=off"], "image_query.hip": ["-ffp-contract=off"],
+            "image_guided_post.hip": ["-ffp-contract=off"], "image_guided_post_host.cpp": ["-ffp-contract=off"],
             # attention_x3.hip: the SLP vectoriser pairs the scalar f32 subtractions / multiplies of the key loop into v_pk_add_f32 /
             # v_pk_mul_f32, which issue slower beside MFMAs than their two scalar halves; same bits either way (tools/attention_x3_isa.py,
             # profiles/attention_x3_issue_stream.md).  tools/lab/attn_lab is built with the same flag.
@@ -45,7 +47,7 @@ def _hipcc() -> str:
 
 
 # HIP-free host sources that are part of libtstar_hip.so (hipcc compiles them as plain C++)
-HOST_SOURCES = ("jpeg_host.cpp",)
+HOST_SOURCES = ("jpeg_host.cpp", "image_guided_post_host.cpp")
 HOST_FLAGS = ["-x", "c++", "-O3", "-std=c++20", "-fPIC", "-Wall", "-pthread"]
 
 
@@ -72,7 +74,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         stale = force or not os.path.exists(op) or os.path.getmtime(op) < max(os.path.getmtime(sp), hdr)
         if stale:
             if src in HOST_SOURCES:
-                jobs.append([hipcc] + HOST_FLAGS + ["-c", sp, "-o", op])
+                jobs.append([hipcc] + HOST_FLAGS + PER_FILE.get(src, []) + ["-c", sp, "-o", op])
             else:
                 jobs.append([hipcc] + FLAGS + PER_FILE.get(src, []) + ["-c", sp, "-o", op])
 

@@ -3,6 +3,7 @@
 #include "../../include/tstar_hip.h"
 #include "common.h"
 #include "heads.h"
+#include "image_guided_post.h"
 #include "image_query.h"
 #include "ingest.h"
 #include "jpeg_entropy_core.h"
@@ -82,18 +83,50 @@ int tstar_cell_reduce(const float* d_scores, const int32_t* d_labels, const floa
     return rc;
 }
 
-int tstar_image_query_select(const float* d_cls, const float* d_boxes_cxcywh, int n, int np, float* h_embeds, int32_t* h_best, float* h_boxes_cxcywh,
-                             int32_t* h_n_selected, int32_t* h_status, void* stream) {
-    TSTAR_REQUIRE(d_cls && d_boxes_cxcywh && h_embeds && h_best && h_boxes_cxcywh && h_n_selected && h_status, "tstar_image_query_select: null argument");
-    TSTAR_REQUIRE(n >= 1 && n <= 65535, "tstar_image_query_select: n must be in 1..65535");
-    TSTAR_REQUIRE(np >= 1 && np <= IMAGE_QUERY_MAX_NP, "tstar_image_query_select: np must be in 1..3600");
-    TSTAR_REQUIRE(((uintptr_t)d_cls & 15) == 0, "tstar_image_query_select: d_cls must be 16-byte aligned");
+// the selection launcher on caller tensors; fn: the entry's name in messages
+static int image_query_select_entry(const std::string& fn, const float* d_cls, const float* d_boxes_cxcywh, const float* d_boxes_q, int n, int np,
+                                    float* h_embeds, int32_t* h_best, float* h_boxes_cxcywh, int32_t* h_n_selected, int32_t* h_status, void* stream) {
+    TSTAR_REQUIRE(d_cls && d_boxes_cxcywh && h_embeds && h_best && h_boxes_cxcywh && h_n_selected && h_status, fn + ": null argument");
+    TSTAR_REQUIRE(n >= 1 && n <= 65535, fn + ": n must be in 1..65535");
+    TSTAR_REQUIRE(np >= 1 && np <= IMAGE_QUERY_MAX_NP, fn + ": np must be in 1..3600");
+    TSTAR_REQUIRE(((uintptr_t)d_cls & 15) == 0, fn + ": d_cls must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     void* d_buf = nullptr;
     TSTAR_HIP_CHECK(hipMalloc(&d_buf, image_query_out_bytes(n)));
     const ImageQueryOut o = image_query_out_at(d_buf, n);
-    const int rc = image_query_select(d_cls, d_boxes_cxcywh, n, np, o, s);
-    return image_query_finish("tstar_image_query_select", rc, d_buf, o, n, h_embeds, h_best, h_boxes_cxcywh, h_n_selected, h_status, s);
+    const int rc = image_query_select(d_cls, d_boxes_cxcywh, d_boxes_q, n, np, o, s);
+    return image_query_finish(fn.c_str(), rc, d_buf, o, n, h_embeds, h_best, h_boxes_cxcywh, h_n_selected, h_status, s);
+}
+
+int tstar_image_query_select_box(const float* d_cls, const float* d_boxes_cxcywh, const float* d_boxes_q, int n, int np, float* h_embeds,
+                                 int32_t* h_best, float* h_boxes_cxcywh, int32_t* h_n_selected, int32_t* h_status, void* stream) {
+    return image_query_select_entry("tstar_image_query_select_box", d_cls, d_boxes_cxcywh, d_boxes_q, n, np, h_embeds, h_best, h_boxes_cxcywh,
+                                    h_n_selected, h_status, stream);
+}
+
+int tstar_image_query_select(const float* d_cls, const float* d_boxes_cxcywh, int n, int np, float* h_embeds, int32_t* h_best, float* h_boxes_cxcywh,
+                             int32_t* h_n_selected, int32_t* h_status, void* stream) {
+    return image_query_select_entry("tstar_image_query_select", d_cls, d_boxes_cxcywh, nullptr, n, np, h_embeds, h_best, h_boxes_cxcywh, h_n_selected,
+                                    h_status, stream);
+}
+
+int tstar_image_guided_postprocess(const float* d_scores, const float* d_boxes_cxcywh, int B, int np, float threshold, float nms_threshold,
+                                   const float* h_scale_xy, float* d_alphas, float* d_boxes_xyxy, uint8_t* d_keep, int32_t* d_n_kept, void* stream) {
+    TSTAR_REQUIRE(d_scores && d_boxes_cxcywh && d_alphas && d_boxes_xyxy && d_keep && d_n_kept, "tstar_image_guided_postprocess: null argument");
+    TSTAR_REQUIRE(B >= 1 && B <= 65535, "tstar_image_guided_postprocess: B must be in 1..65535");
+    TSTAR_REQUIRE(np >= 1 && np <= 3600, "tstar_image_guided_postprocess: np must be in 1..3600");
+    hipStream_t s = (hipStream_t)stream;
+    if (!h_scale_xy) return image_guided_post(d_scores, d_boxes_cxcywh, nullptr, B, np, threshold, nms_threshold, d_alphas, d_boxes_xyxy, d_keep, d_n_kept, s);
+    float* d_scale = nullptr;
+    TSTAR_HIP_CHECK(hipMalloc(&d_scale, (size_t)B * 2 * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(d_scale, h_scale_xy, (size_t)B * 2 * sizeof(float), hipMemcpyHostToDevice, s);
+    int rc = TSTAR_OK;
+    if (e == hipSuccess) rc = image_guided_post(d_scores, d_boxes_cxcywh, d_scale, B, np, threshold, nms_threshold, d_alphas, d_boxes_xyxy, d_keep, d_n_kept, s);
+    const hipError_t e2 = hipStreamSynchronize(s);              // the staging copy is freed below
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(d_scale);
+    if (!rc && e != hipSuccess) { set_error(std::string("tstar_image_guided_postprocess: ") + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
+    return rc;
 }
 
 int tstar_frames_to_grid(const uint8_t* d_video, int N, int H, int W, const int32_t* d_frame_idx, int grid_rows,

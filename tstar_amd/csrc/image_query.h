@@ -19,8 +19,9 @@ static inline ImageQueryOut image_query_out_offset(const ImageQueryOut& o, int b
     return ImageQueryOut{o.embeds + (size_t)b0 * 512, o.best + b0, o.boxes + (size_t)b0 * 4, o.n_selected + b0, o.status + b0};
 }
 
-// cls [n * np, 512], boxes_cxcywh [n * np, 4]: one workgroup per image; np <= IMAGE_QUERY_MAX_NP
-int image_query_select(const float* cls, const float* boxes_cxcywh, int n, int np, const ImageQueryOut& out, hipStream_t s);
+// cls [n * np, 512], boxes_cxcywh [n * np, 4]: one workgroup per image; np <= IMAGE_QUERY_MAX_NP.  boxes_q [n, 4] (device):
+// the query box of every example, relative xyxy; null = the unit box [0, 0, 1, 1] for all
+int image_query_select(const float* cls, const float* boxes_cxcywh, const float* boxes_q, int n, int np, const ImageQueryOut& out, hipStream_t s);
 
 // The end of an image-query entry `fn`: with rc == 0 the device results go to the caller's host arrays; the stream is synchronised
 // and the staging buffer d_buf (what image_query_out_at carved `o` from) freed either way.  Returns rc, or the copies' error.

@@ -1,9 +1,15 @@
 // Image-guided (one-shot) queries: the query-box selection of HF's embed_image_query (modeling_owlvit.py; modeling_owlv2.py is
 // the same statements).  For one example image with class embeddings cls [np, 512] (class head dense0, NOT normalised) and
 // boxes [np, 4] (cxcywh):
-//   corners x0 = cx - 0.5 w, x1 = cx + 0.5 w (y likewise); IoU with the unit box [0, 0, 1, 1] in float32:
-//     area = (x1 - x0)(y1 - y0), inter from the clamped extents, union = (1 + area) - inter, iou = inter / union;
-//   when EVERY iou is 0: generalized IoU, iou - (enclosing - union) / enclosing;
+//   corners x0 = cx - 0.5 w, x1 = cx + 0.5 w (y likewise); IoU with the example's query box q = (qx0, qy0, qx1, qy1) (relative
+//   xyxy; HF's own is the unit box [0, 0, 1, 1], which is what a null boxes_q stands for) in float32, HF's box_iou /
+//   generalized_box_iou in their general form:
+//     area_q = (qx1 - qx0)(qy1 - qy0), area = (x1 - x0)(y1 - y0), inter = the product of the extents
+//     min(bottom-right corners) - max(top-left corners), each clamped at 0, union = (area_q + area) - inter, iou = inter / union;
+//   when EVERY iou is 0: generalized IoU, iou - (enclosing - union) / enclosing, enclosing = the product of the extents
+//     max(bottom-right corners) - min(top-left corners), each clamped at 0.
+//   With the unit box area_q is exactly 1 and every min / max has the constant 0 or 1 on one side: the bits of the statements
+//   this kernel had before it took a box;
 //   thr = max * 0.8 (a float32 product); selected = rows with value >= thr (possibly none: a negative maximum);
 //   mean = cls.mean(0) over ALL rows; mean_sim[i] = mean . cls[i] for the selected rows;
 //   best = the selected row with the smallest mean_sim, lowest index on a tie; the query is cls[best].
@@ -43,7 +49,8 @@ __device__ __forceinline__ float wmax64(float v) {
     return v;
 }
 
-__global__ __launch_bounds__(256) void image_query_select_kernel(const float* __restrict__ cls_all, const float* __restrict__ boxes_all, int np,
+__global__ __launch_bounds__(256) void image_query_select_kernel(const float* __restrict__ cls_all, const float* __restrict__ boxes_all,
+                                                                 const float* __restrict__ boxes_q, int np,
                                                                  float* __restrict__ embeds, int* __restrict__ best_out, float* __restrict__ box_out,
                                                                  int* __restrict__ nsel_out, int* __restrict__ status_out) {
     __shared__ float s_iou[IMAGE_QUERY_MAX_NP];
@@ -59,18 +66,21 @@ __global__ __launch_bounds__(256) void image_query_select_kernel(const float* __
     const float* cls = cls_all + (size_t)b * np * 512;
     const float* boxes = boxes_all + (size_t)b * np * 4;
 
-    // ---- 1. IoU / GIoU of every row against the unit box
+    // ---- 1. IoU / GIoU of every row against the query box
+    float qx0 = 0.0f, qy0 = 0.0f, qx1 = 1.0f, qy1 = 1.0f;
+    if (boxes_q) { qx0 = boxes_q[(size_t)b * 4 + 0]; qy0 = boxes_q[(size_t)b * 4 + 1]; qx1 = boxes_q[(size_t)b * 4 + 2]; qy1 = boxes_q[(size_t)b * 4 + 3]; }
+    const float area_q = (qx1 - qx0) * (qy1 - qy0);
     float mi = -FLT_MAX, mg = -FLT_MAX;
     int any = 0;
     for (int p = tid; p < np; p += 256) {
         const float cx = boxes[(size_t)p * 4 + 0], cy = boxes[(size_t)p * 4 + 1], w = boxes[(size_t)p * 4 + 2], h = boxes[(size_t)p * 4 + 3];
         const float x0 = cx - 0.5f * w, y0 = cy - 0.5f * h, x1 = cx + 0.5f * w, y1 = cy + 0.5f * h;
         const float area = (x1 - x0) * (y1 - y0);
-        const float iw = fmaxf(fminf(1.0f, x1) - fmaxf(0.0f, x0), 0.0f), ih = fmaxf(fminf(1.0f, y1) - fmaxf(0.0f, y0), 0.0f);
+        const float iw = fmaxf(fminf(qx1, x1) - fmaxf(qx0, x0), 0.0f), ih = fmaxf(fminf(qy1, y1) - fmaxf(qy0, y0), 0.0f);
         const float inter = iw * ih;
-        const float uni = (1.0f + area) - inter;
+        const float uni = (area_q + area) - inter;
         const float iou = inter / uni;
-        const float ew = fmaxf(fmaxf(1.0f, x1) - fminf(0.0f, x0), 0.0f), eh = fmaxf(fmaxf(1.0f, y1) - fminf(0.0f, y0), 0.0f);
+        const float ew = fmaxf(fmaxf(qx1, x1) - fminf(qx0, x0), 0.0f), eh = fmaxf(fmaxf(qy1, y1) - fminf(qy0, y0), 0.0f);
         const float enc = ew * eh;
         const float giou = iou - (enc - uni) / enc;
         s_iou[p] = iou;
@@ -164,11 +174,11 @@ __global__ __launch_bounds__(256) void image_query_select_kernel(const float* __
     if (tid < 4) box_out[(size_t)b * 4 + tid] = bi >= 0 ? boxes[(size_t)bi * 4 + tid] : 0.f;
 }
 
-int image_query_select(const float* cls, const float* boxes_cxcywh, int n, int np, const ImageQueryOut& out, hipStream_t s) {
+int image_query_select(const float* cls, const float* boxes_cxcywh, const float* boxes_q, int n, int np, const ImageQueryOut& out, hipStream_t s) {
     TSTAR_REQUIRE(cls && boxes_cxcywh && out.embeds && out.best && out.boxes && out.n_selected && out.status, "image_query_select: null argument");
     TSTAR_REQUIRE(n >= 1 && np >= 1 && np <= IMAGE_QUERY_MAX_NP, "image_query_select: n must be positive and np in 1..3600");
     TSTAR_REQUIRE(((uintptr_t)cls & 15) == 0 && ((uintptr_t)out.embeds & 7) == 0, "image_query_select: cls must be 16-byte aligned, embeds 8-byte aligned");
-    hipLaunchKernelGGL(image_query_select_kernel, dim3(n), dim3(256), 0, s, cls, boxes_cxcywh, np, out.embeds, out.best, out.boxes, out.n_selected,
+    hipLaunchKernelGGL(image_query_select_kernel, dim3(n), dim3(256), 0, s, cls, boxes_cxcywh, boxes_q, np, out.embeds, out.best, out.boxes, out.n_selected,
                        out.status);
     TSTAR_HIP_CHECK(hipGetLastError());
     return TSTAR_OK;

@@ -848,11 +848,12 @@ int tstar_owl_debug_embed(tstar_owl* h, const float* d_patches, int B, int stage
     return TSTAR_OK;
 }
 
-int tstar_owl_embed_image_queries(tstar_owl* h, const uint8_t* d_images, int n, int H, int W, float* h_embeds, int32_t* h_best, float* h_boxes_cxcywh,
-                                  int32_t* h_n_selected, int32_t* h_status, void* stream) {
-    TSTAR_REQUIRE(h && d_images && h_embeds && h_best && h_boxes_cxcywh && h_n_selected && h_status, "tstar_owl_embed_image_queries: null argument");
-    TSTAR_REQUIRE(n >= 1 && n <= 65535 && H >= 1 && W >= 1, "tstar_owl_embed_image_queries: empty batch or image (n in 1..65535)");
-    if (!h->has_vision) { set_error("tstar_owl_embed_image_queries: handle was created without vision weights (text-only)"); return TSTAR_ERR_STATE; }
+// fn: the entry's name in messages
+static int embed_image_queries_entry(const std::string& fn, tstar_owl* h, const uint8_t* d_images, int n, int H, int W, const float* h_query_boxes,
+                                     float* h_embeds, int32_t* h_best, float* h_boxes_cxcywh, int32_t* h_n_selected, int32_t* h_status, void* stream) {
+    TSTAR_REQUIRE(h && d_images && h_embeds && h_best && h_boxes_cxcywh && h_n_selected && h_status, fn + ": null argument");
+    TSTAR_REQUIRE(n >= 1 && n <= 65535 && H >= 1 && W >= 1, fn + ": empty batch or image (n in 1..65535)");
+    if (!h->has_vision) { set_error(fn + ": handle was created without vision weights (text-only)"); return TSTAR_ERR_STATE; }
     if (h->geom.family == TSTAR_OWL_FAMILY_OWLV2) {          // refusals before anything is launched
         const Owlv2Plan vp = plan_owlv2_preprocess(H, W, h->geom.in_h, h->geom.in_w);
         if (vp.error) { set_error(vp.error); return TSTAR_ERR_ARG; }
@@ -861,9 +862,15 @@ int tstar_owl_embed_image_queries(tstar_owl* h, const uint8_t* d_images, int n, 
     auto& L = h->lane[0];                                     // the handle's own workspace, as the text tower
     const int NP = h->geom.np;
     void* d_buf = nullptr;
-    TSTAR_HIP_CHECK(hipMalloc(&d_buf, image_query_out_bytes(n)));
+    // the staging allocation: the outputs, then (with query boxes) the boxes [n, 4]
+    TSTAR_HIP_CHECK(hipMalloc(&d_buf, image_query_out_bytes(n) + (h_query_boxes ? (size_t)n * 4 * sizeof(float) : 0)));
     const ImageQueryOut o = image_query_out_at(d_buf, n);
+    float* d_qboxes = h_query_boxes ? reinterpret_cast<float*>(static_cast<char*>(d_buf) + image_query_out_bytes(n)) : nullptr;
     int rc = TSTAR_OK;
+    if (d_qboxes) {
+        const hipError_t e = hipMemcpyAsync(d_qboxes, h_query_boxes, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice, s);
+        if (e != hipSuccess) { set_error(fn + ": " + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
+    }
     for (int b0 = 0; b0 < n && !rc; b0 += L.cap) {
         const int Bc = (n - b0) < L.cap ? (n - b0) : L.cap;
         const int MP = Bc * NP;
@@ -880,9 +887,21 @@ int tstar_owl_embed_image_queries(tstar_owl* h, const uint8_t* d_images, int n, 
         a.rows = MP; a.np = NP; a.Q = h->Q[0];
         box_scale(h->geom, H, W, &a.box_sx, &a.box_sy);
         rc = detect_rows(a, s);
-        if (!rc) rc = image_query_select(t.cls, a.cxcywh, Bc, NP, image_query_out_offset(o, b0), s);
+        if (!rc) rc = image_query_select(t.cls, a.cxcywh, d_qboxes ? d_qboxes + (size_t)b0 * 4 : nullptr, Bc, NP, image_query_out_offset(o, b0), s);
     }
-    return image_query_finish("tstar_owl_embed_image_queries", rc, d_buf, o, n, h_embeds, h_best, h_boxes_cxcywh, h_n_selected, h_status, s);
+    return image_query_finish(fn.c_str(), rc, d_buf, o, n, h_embeds, h_best, h_boxes_cxcywh, h_n_selected, h_status, s);
+}
+
+int tstar_owl_embed_image_queries(tstar_owl* h, const uint8_t* d_images, int n, int H, int W, float* h_embeds, int32_t* h_best, float* h_boxes_cxcywh,
+                                  int32_t* h_n_selected, int32_t* h_status, void* stream) {
+    return embed_image_queries_entry("tstar_owl_embed_image_queries", h, d_images, n, H, W, nullptr, h_embeds, h_best, h_boxes_cxcywh, h_n_selected,
+                                     h_status, stream);
+}
+
+int tstar_owl_embed_image_queries_box(tstar_owl* h, const uint8_t* d_images, int n, int H, int W, const float* h_query_boxes, float* h_embeds,
+                                      int32_t* h_best, float* h_boxes_cxcywh, int32_t* h_n_selected, int32_t* h_status, void* stream) {
+    return embed_image_queries_entry("tstar_owl_embed_image_queries_box", h, d_images, n, H, W, h_query_boxes, h_embeds, h_best, h_boxes_cxcywh,
+                                     h_n_selected, h_status, stream);
 }
 
 int tstar_owlv2_last_preprocess_form(tstar_owl* h, int lane) {

@@ -89,9 +89,11 @@ class OWLInterface(HeuristicInterface):
 
         Image-guided (one-shot) queries, both families: ``set_query_images({name: image})`` registers example images; from then
         on any object NAME found in the registry is represented by its example's embedding (HF's ``embed_image_query``:
-        ``image_guided_detection`` up to the query vector) instead of its text, in every way queries are installed.  HF's
-        ``post_process_image_guided_detection`` (NMS, per-image score rescaling) is not part of it: an image-backed query is
-        scored, thresholded and weighted exactly like a text query.
+        ``image_guided_detection`` up to the query vector) instead of its text, in every way queries are installed; an
+        image-backed query is scored, thresholded and weighted exactly like a text query.  An example may be a REGION of an
+        image: ``{name: (image, (x0, y0, x1, y1))}``, the box in pixels of the example.  ``detect_image_guided`` is HF's whole
+        one-shot pipeline, ``image_guided_detection`` + ``post_process_image_guided_detection`` (NMS, per-image score
+        rescaling), outside the search loop.
         ``family`` ("owlvit" / "owlv2") chooses the family of SYNTHETIC weights; not given, it is ``TSTAR_OWL_FAMILY``, else
         "owlv2" when ``model_name_or_path`` contains ``owlv2``, else "owlvit"; given together with real weights it must agree
         with them.  ``patch_size`` (32 or 16) chooses
@@ -201,44 +203,187 @@ class OWLInterface(HeuristicInterface):
         self.query_image_info: Dict[str, Dict] = {}
 
     # ---- image-guided queries ------------------------------------------------------------
+    @staticmethod
+    def _load_example(img, what: str) -> np.ndarray:
+        from PIL import Image
+        if isinstance(img, (str, os.PathLike)):
+            with Image.open(img) as im:
+                img = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        img = np.ascontiguousarray(img)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"{what} must be an HxWx3 uint8 RGB image or a path")
+        return img
+
+    @staticmethod
+    def _relative_box(box, H: int, Wd: int, what: str) -> np.ndarray:
+        """A query box in pixels of its H x W example -> float32 [4] relative (x0, y0, x1, y1), each ``float32(x) / float32(W)``;
+        ValueError when the box is empty, inverted or reaches outside the image."""
+        try:
+            b = np.asarray(box, dtype=np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            b = np.zeros(0, np.float32)
+        if b.shape != (4,) or not np.isfinite(b).all():
+            raise ValueError(f"{what}: the query box must be four finite numbers (x0, y0, x1, y1) in pixels")
+        x0, y0, x1, y1 = (float(v) for v in b)
+        if not (0 <= x0 < x1 <= Wd and 0 <= y0 < y1 <= H):
+            raise ValueError(f"{what}: the query box ({x0:g}, {y0:g}, {x1:g}, {y1:g}) is empty, inverted or outside the "
+                             f"{Wd} x {H} example image")
+        return b / np.array([Wd, H, Wd, H], dtype=np.float32)
+
+    def _embed_examples(self, arrays: Dict[object, np.ndarray], boxes: Dict[object, Optional[np.ndarray]]):
+        """{key: example image} (+ {key: relative box or None}) -> {key: (ImageQueryResult, row)}: the examples of one size in one
+        batched ``OwlScorer.embed_image_queries`` call."""
+        import torch
+        by_shape: Dict[tuple, list] = {}
+        for key, img in arrays.items():
+            by_shape.setdefault(img.shape, []).append(key)
+        out = {}
+        unit = np.array([0, 0, 1, 1], dtype=np.float32)
+        for keys in by_shape.values():
+            qb = None
+            if any(boxes.get(k) is not None for k in keys):
+                qb = np.stack([unit if boxes.get(k) is None else boxes[k] for k in keys])
+            d_imgs = torch.from_numpy(np.stack([arrays[k] for k in keys])).cuda()
+            r = self.scorer.embed_image_queries(d_imgs) if qb is None else self.scorer.embed_image_queries(d_imgs, query_boxes=qb)
+            for i, key in enumerate(keys):
+                out[key] = (r, i)
+        return out
+
     def set_query_images(self, images: Dict[str, object]):
-        """Register example images: ``{name: HxWx3 uint8 RGB array, or the path of an image file}``.  They are embedded at once
+        """Register example images: ``{name: HxWx3 uint8 RGB array, or the path of an image file}``, or ``{name: (image_or_path,
+        (x0, y0, x1, y1))}`` when only a region of the example is meant -- the box in pixels of the example; the whole example
+        still goes through the vision tower, so the region keeps its surroundings, and the box takes the place of HF's whole-image
+        query box in the selection (``OwlScorer.embed_image_queries(..., query_boxes=)``).  They are embedded at once
         (images of one size in one batched ``OwlScorer.embed_image_queries`` call) and the embeddings cached; from the next
         ``reparameterize_object_list`` / ``install_queries`` / ``install_queries_many`` on, a target or cue object whose name
         (after ``.strip()``) is registered is represented by its example's embedding instead of its text -- ``texts``, labels,
         class weights, the trailing blank query and the 32-query limit are as before, so a searcher needs no change.
-        ``query_image_info[name]`` = ``{"best_index", "box_cxcywh", "n_selected", "giou_fallback"}``.  An example for which HF
+        ``query_image_info[name]`` = ``{"best_index", "box_cxcywh", "n_selected", "giou_fallback", "query_box"}`` (``query_box``:
+        the relative float32 box, None for a whole image).  An example for which HF
         would produce no query (no box within 80 % of the best overlap: every generalized IoU negative) raises ValueError naming
-        the object, and nothing is registered.  Queries already installed are not touched."""
-        import torch
-        from PIL import Image
-        arrays = {}
+        the object, as does a box that is empty, inverted or outside its image; nothing is registered then.  Queries already
+        installed are not touched."""
+        arrays, boxes = {}, {}
         for name, img in images.items():
             key = str(name).strip()
             if not key:
                 raise ValueError("set_query_images: an object name must not be blank")
-            if isinstance(img, (str, os.PathLike)):
-                with Image.open(img) as im:
-                    img = np.asarray(im.convert("RGB"), dtype=np.uint8)
-            img = np.ascontiguousarray(img)
-            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
-                raise ValueError(f"set_query_images: {key!r} must be an HxWx3 uint8 RGB image or a path")
-            arrays[key] = img
-        by_shape: Dict[tuple, List[str]] = {}
-        for key, img in arrays.items():
-            by_shape.setdefault(img.shape, []).append(key)
+            box = None
+            if isinstance(img, tuple):
+                if len(img) != 2:
+                    raise ValueError(f"set_query_images: {key!r} must be an image, a path, or (image_or_path, (x0, y0, x1, y1))")
+                img, box = img
+            arrays[key] = self._load_example(img, f"set_query_images: {key!r}")
+            boxes[key] = None if box is None else self._relative_box(box, arrays[key].shape[0], arrays[key].shape[1],
+                                                                      f"set_query_images: {key!r}")
         embeds, info = {}, {}
-        for keys in by_shape.values():
-            r = self.scorer.embed_image_queries(torch.from_numpy(np.stack([arrays[k] for k in keys])).cuda())
-            for i, key in enumerate(keys):
-                if int(r.status[i]) == 2:
-                    raise ValueError(f"set_query_images: no query can be formed from the example image of {key!r}: none of its "
-                                     "predicted boxes overlaps the whole image (empty selection in HF's embed_image_query)")
-                embeds[key] = r.embeds[i].copy()
-                info[key] = dict(best_index=int(r.best[i]), box_cxcywh=r.boxes_cxcywh[i].copy(), n_selected=int(r.n_selected[i]),
-                                 giou_fallback=bool(r.status[i] == 1))
+        for key, (r, i) in self._embed_examples(arrays, boxes).items():
+            if int(r.status[i]) == 2:
+                raise ValueError(f"set_query_images: no query can be formed from the example image of {key!r}: none of its "
+                                 "predicted boxes overlaps the " + ("whole image" if boxes[key] is None else "query box") +
+                                 " (empty selection in HF's embed_image_query)")
+            embeds[key] = r.embeds[i].copy()
+            info[key] = dict(best_index=int(r.best[i]), box_cxcywh=r.boxes_cxcywh[i].copy(), n_selected=int(r.n_selected[i]),
+                             giou_fallback=bool(r.status[i] == 1), query_box=None if boxes[key] is None else boxes[key].copy())
         self._query_images.update(embeds)
         self.query_image_info.update(info)
+
+    def detect_image_guided(self, images, query_images, query_boxes=None, threshold: float = 0.0, nms_threshold: float = 0.3,
+                            target_sizes=None):
+        """HF's one-shot detection end to end: ``image_guided_detection`` + ``post_process_image_guided_detection``.
+        ``images``: list of HxWx3 uint8 arrays.  ``query_images``: ONE example (array or path) for all images, or a list with one
+        per image (HF's pairing: image b with query b).  ``query_boxes``: None, one box or one per example (None entries allowed):
+        the region of the example that is meant, (x0, y0, x1, y1) in pixels of the example.  ``target_sizes``: (height, width)
+        per image the boxes are scaled to, default each image's own; an OWLv2 heuristic scales by max(height, width) on both
+        axes, as its HF processor does.
+        Returns one dict per image: ``{"scores": alphas float32 [k], "labels": None, "boxes": xyxy float32 [k,4], "patches": int64
+        [k], "detections": Detections}`` -- the kept patches in patch order.  An image for which nothing is left (HF drops it
+        from its list) has an empty entry.  An example from which no query can be formed raises ValueError naming its index.
+        The query sets of ``reparameterize_object_list`` / ``install_queries`` are not touched: the queries go to slots the
+        scorer's registry does not hold, a group at a time when there are more distinct examples than free slots, and the
+        registry is what it was when the call returns.  RuntimeError when no slot is free: slots stay held until they are
+        released -- after a lock-step group that filled all of them, ``scorer.release_slot(slot)`` for the slots no searcher uses
+        any more frees them."""
+        import torch
+        images = [np.ascontiguousarray(im) for im in images]
+        n = len(images)
+        if n < 1:
+            raise ValueError("detect_image_guided: no image")
+        for b, im in enumerate(images):
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError(f"detect_image_guided: image {b} must be an HxWx3 uint8 RGB array")
+        shared = not isinstance(query_images, (list, tuple))
+        queries = [query_images] * n if shared else list(query_images)
+        if len(queries) != n:
+            raise ValueError("detect_image_guided: query_images must be one example, or one per image")
+        if query_boxes is None:
+            qboxes = [None] * n
+        elif len(query_boxes) == 4 and all(q is not None and np.ndim(q) == 0 for q in query_boxes):
+            qboxes = [query_boxes] * n                           # one box (four numbers) for every example
+        else:
+            qboxes = list(query_boxes)
+            if len(qboxes) != n:
+                raise ValueError("detect_image_guided: query_boxes must be one box, or one per example")
+        if target_sizes is None:
+            target_sizes = [im.shape[:2] for im in images]
+        target_sizes = np.asarray(target_sizes)
+        if target_sizes.shape != (n, 2):
+            raise ValueError("detect_image_guided: target_sizes needs one (height, width) per image")
+        # 1. the distinct (example, box) pairs, embedded once each
+        distinct, arrays, boxes, of_image = {}, {}, {}, []
+        for b, (q, qb) in enumerate(zip(queries, qboxes)):
+            ident = (q if isinstance(q, (str, os.PathLike)) else id(q), None if qb is None else tuple(float(v) for v in np.ravel(qb)))
+            if ident not in distinct:
+                k = distinct[ident] = len(distinct)
+                arrays[k] = self._load_example(q, f"detect_image_guided: query image {b}")
+                boxes[k] = None if qb is None else self._relative_box(qb, arrays[k].shape[0], arrays[k].shape[1],
+                                                                      f"detect_image_guided: query image {b}")
+            of_image.append(distinct[ident])
+        embeds = {}
+        for k, (r, i) in self._embed_examples(arrays, boxes).items():
+            if int(r.status[i]) == 2:
+                b = of_image.index(k)
+                raise ValueError(f"detect_image_guided: no query can be formed from query image {b}: none of its predicted boxes "
+                                 "overlaps the " + ("whole image" if boxes[k] is None else "query box") +
+                                 " (empty selection in HF's embed_image_query)")
+            embeds[k] = r.embeds[i]
+        # 2. - 4. a group of distinct queries at a time, in slots the registry does not hold
+        sc = self.scorer
+        from .owl import MAX_SETS
+        free = [sl for sl in range(MAX_SETS - 1, -1, -1) if sl not in sc.Qs and sl not in sc._pending]
+        if not free:
+            raise RuntimeError(f"detect_image_guided: all {MAX_SETS} query-set slots hold installed query sets; none is free for a "
+                               "one-shot query (scorer.release_slot(slot) frees one that is no longer used)")
+        results = [None] * n
+        ks = sorted(embeds)
+        try:
+            for g0 in range(0, len(ks), len(free)):
+                slot_of = {k: free[j] for j, k in enumerate(ks[g0:g0 + len(free)])}
+                for k, sl in slot_of.items():
+                    sc.set_query_embeds(embeds[k][None, :], [1], [1.0], slot=sl)
+                by_shape: Dict[tuple, List[int]] = {}
+                for b in range(n):
+                    if of_image[b] in slot_of:
+                        by_shape.setdefault(images[b].shape, []).append(b)
+                for idx in by_shape.values():
+                    for c0 in range(0, len(idx), sc.max_batch):
+                        chunk = idx[c0:c0 + sc.max_batch]
+                        d_img = torch.from_numpy(np.stack([images[b] for b in chunk])).cuda()
+                        r = sc.score(d_img, 1, 1, want_logits=True, image_sets=[slot_of[of_image[b]] for b in chunk])
+                        post = sc.image_guided_postprocess(r.scores, r.boxes_cxcywh, threshold, nms_threshold, target_sizes[chunk])
+                        alphas, xyxy, keep = post.alphas.cpu().numpy(), post.boxes.cpu().numpy(), post.keep.cpu().numpy()
+                        for j, b in enumerate(chunk):
+                            m = keep[j]
+                            dets = Detections(xyxy=xyxy[j][m], confidence=alphas[j][m], class_id=np.zeros(int(m.sum()), dtype=np.int64))
+                            results[b] = {"scores": dets.confidence, "labels": None, "boxes": dets.xyxy, "patches": np.nonzero(m)[0],
+                                          "detections": dets}
+        finally:
+            # the registry as it was: these slots held nothing.  The handle keeps Q = 1 and the one-shot row in them; with the registry
+            # entry gone (Qs.get(slot, 0) == 0) they are reachable neither through score(want_logits) nor get_query_embeds, and the
+            # next install of the slot overwrites them
+            for sl in free:
+                sc.release_slot(sl)
+        return results
 
     def clear_query_images(self):
         """Forget every example image: names are text queries again from the next install on."""

@@ -72,6 +72,7 @@ class ScoreResult:
     objectness: "object" = None   # f32 [B,np]: HF's objectness_logits (OWLv2 only, ``score(..., objectness=True)``)
 
 
+MAX_SETS = 64                                              # TSTAR_OWL_MAX_SETS of include/tstar_hip.h: query-set slots of a handle
 IMAGE_QUERY_IOU, IMAGE_QUERY_GIOU, IMAGE_QUERY_EMPTY = 0, 1, 2     # ImageQueryResult.status (tstar_owl_embed_image_queries)
 
 
@@ -83,6 +84,15 @@ class ImageQueryResult:
     boxes_cxcywh: np.ndarray  # f32 [n,4] its pred_box, relative
     n_selected: np.ndarray    # i32 [n] patches with IoU (GIoU) >= 0.8 x the maximum
     status: np.ndarray        # i32 [n] 0 IoU, 1 the GIoU fallback was used, 2 empty selection (HF produces no query)
+
+
+@dataclass
+class ImageGuidedPostResult:
+    """Device tensors of one tstar_image_guided_postprocess call (HF's ``post_process_image_guided_detection``)."""
+    alphas: "object"       # f32 [B,np] HF's rescaled scores; 0 where the patch is not kept
+    boxes: "object"        # f32 [B,np,4] xyxy, scaled to the target sizes (every patch, kept or not)
+    keep: "object"         # bool [B,np] alpha > 0: the rows HF returns, in patch order
+    n_kept: "object"       # i32 [B]
 
 
 class OwlScorer:
@@ -277,6 +287,13 @@ class OwlScorer:
         rc = self._lib.tstar_owl_set_class_weights(self._h, int(slot), w.ctypes.data, len(w), _lib.stream_ptr())
         _lib.check(rc, "tstar_owl_set_class_weights")
 
+    def release_slot(self, slot: int):
+        """Forget the query set of ``slot``: the registry (``Qs``, lazily recorded queries) no longer holds it, so the slot counts as
+        free (``OWLInterface.detect_image_guided`` uses free slots).  The handle keeps the rows until the slot is installed again;
+        with the registry entry gone they are not reachable through ``score(..., want_logits=True)`` or ``get_query_embeds``."""
+        self.Qs.pop(int(slot), None)
+        self._pending.pop(int(slot), None)
+
     def get_query_embeds(self, slot: int = 0) -> np.ndarray:
         self._flush([slot])
         q = self.Qs.get(int(slot), 0)
@@ -286,10 +303,11 @@ class OwlScorer:
         return out
 
     # ---- image-guided queries
-    def embed_image_queries(self, images) -> ImageQueryResult:
+    def embed_image_queries(self, images, query_boxes=None) -> ImageQueryResult:
         """images: torch u8 cuda tensor [n,H,W,3] of example images -> ``ImageQueryResult`` (host arrays): HF's
         ``embed_image_query`` per image -- the class embedding of the patch whose box covers the image best and is least like the
-        mean embedding.  Runs in lane 0; installed queries are untouched.  Install ``embeds[i]`` with ``set_query_embeds`` (mask
+        mean embedding.  ``query_boxes``: float32 [n,4] relative (x0, y0, x1, y1) per example -- the region of the example that is
+        meant, in place of HF's whole image [0, 0, 1, 1] (None, or unit boxes: HF's bits).  Runs in lane 0; installed queries are untouched.  Install ``embeds[i]`` with ``set_query_embeds`` (mask
         1) or through ``set_queries(..., overrides=)``; an image with ``status == 2`` has no query (HF skips it too)."""
         torch = self._torch
         if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3 or not images.is_cuda:
@@ -300,11 +318,53 @@ class OwlScorer:
             raise ValueError("embed_image_queries: no image")
         r = ImageQueryResult(embeds=np.zeros((n, W.PROJ), np.float32), best=np.zeros(n, np.int32), boxes_cxcywh=np.zeros((n, 4), np.float32),
                              n_selected=np.zeros(n, np.int32), status=np.zeros(n, np.int32))
+        qb = None
+        if query_boxes is not None:
+            qb = np.ascontiguousarray(query_boxes, dtype=np.float32)
+            if qb.shape != (n, 4) or not np.isfinite(qb).all():
+                raise ValueError("embed_image_queries: query_boxes must be a finite float32 [n,4] array of relative (x0, y0, x1, y1)")
         if self.family == "owlv2":
             self._prepare_v2(H, Wd)
-        rc = self._lib.tstar_owl_embed_image_queries(self._h, images.data_ptr(), n, H, Wd, r.embeds.ctypes.data, r.best.ctypes.data,
-                                                     r.boxes_cxcywh.ctypes.data, r.n_selected.ctypes.data, r.status.ctypes.data, _lib.stream_ptr())
+        rc = self._lib.tstar_owl_embed_image_queries_box(self._h, images.data_ptr(), n, H, Wd, None if qb is None else qb.ctypes.data,
+                                                         r.embeds.ctypes.data, r.best.ctypes.data, r.boxes_cxcywh.ctypes.data,
+                                                         r.n_selected.ctypes.data, r.status.ctypes.data, _lib.stream_ptr())
         _lib.check(rc, "tstar_owl_embed_image_queries")
+        return r
+
+    def box_scale(self, H: int, Wd: int):
+        """(sx, sy) relative boxes are scaled by for an image of H x W pixels: (W, H) on OWL-ViT; max(H, W) on both axes on OWLv2,
+        whose processor pads the image to a square."""
+        return (float(max(H, Wd)),) * 2 if self.family == "owlv2" else (float(Wd), float(H))
+
+    def image_guided_postprocess(self, scores, boxes_cxcywh, threshold: float = 0.0, nms_threshold: float = 0.3,
+                                 target_sizes=None) -> ImageGuidedPostResult:
+        """HF's ``post_process_image_guided_detection`` on device tensors: ``scores`` f32 [B,np] and ``boxes_cxcywh`` f32 [B,np,4]
+        as ``score(..., want_logits=True)`` returns them (one query per image).  Greedy NMS (``nms_threshold`` >= 1: none; equal
+        scores go lowest patch first, where torch leaves the order open), scores below ``threshold`` dropped, alphas rescaled per
+        image.  ``target_sizes``: (height, width) per image -- boxes are scaled as the family's HF processor does (``box_scale``);
+        None: relative boxes.  An image where nothing is left keeps nothing (HF drops it from its list; here its row of ``keep``
+        is all False)."""
+        torch = self._torch
+        if (scores.dtype != torch.float32 or boxes_cxcywh.dtype != torch.float32 or not scores.is_cuda or not boxes_cxcywh.is_cuda
+                or scores.dim() != 2 or boxes_cxcywh.shape != (*scores.shape, 4)):
+            raise ValueError("image_guided_postprocess: scores must be cuda float32 [B,np] and boxes_cxcywh cuda float32 [B,np,4]")
+        scores, boxes_cxcywh = scores.contiguous(), boxes_cxcywh.contiguous()
+        B, npatch = scores.shape
+        scale = None
+        if target_sizes is not None:
+            ts = np.asarray(target_sizes)
+            if ts.shape != (B, 2):
+                raise ValueError("image_guided_postprocess: target_sizes needs one (height, width) per image")
+            scale = np.ascontiguousarray([self.box_scale(int(h_), int(w_)) for h_, w_ in ts], dtype=np.float32)
+        dev = scores.device
+        r = ImageGuidedPostResult(alphas=torch.empty((B, npatch), dtype=torch.float32, device=dev),
+                                  boxes=torch.empty((B, npatch, 4), dtype=torch.float32, device=dev),
+                                  keep=torch.empty((B, npatch), dtype=torch.bool, device=dev),
+                                  n_kept=torch.empty((B,), dtype=torch.int32, device=dev))
+        rc = self._lib.tstar_image_guided_postprocess(scores.data_ptr(), boxes_cxcywh.data_ptr(), B, npatch, float(threshold), float(nms_threshold),
+                                                      None if scale is None else scale.ctypes.data, r.alphas.data_ptr(), r.boxes.data_ptr(),
+                                                      r.keep.data_ptr(), r.n_kept.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "tstar_image_guided_postprocess")
         return r
 
     # ---- scoring
