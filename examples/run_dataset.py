@@ -59,6 +59,12 @@ def main():
     ap.add_argument("--feature-cache", type=int, default=None, metavar="N",
                     help="keep the detector's frame records of up to N verification frames on the device (default: TSTAR_FEATURE_CACHE, "
                          "else off): later questions about a video skip the vision tower for frames an earlier one verified; same results")
+    ap.add_argument("--keyframe-jpegs", default=None, metavar="DIR",
+                    help="write the K keyframes of each item as DIR/<item>/<second>.jpg, encoded on the device from the resident store "
+                         "(Pillow's default JPEG bytes; the reference's keyframe writer, TStarFramework.py:136-146)")
+    ap.add_argument("--save-mjpeg", default=None, metavar="DIR",
+                    help="write each opened video once as DIR/<name>.avi (Motion-JPEG, quality 90, 1 frame per second), skipped when the "
+                         "file is there: a later run passes those files as --videos and opens them through the device decode path")
     args = ap.parse_args()
 
     import torch
@@ -96,6 +102,12 @@ def main():
                 stores[p] = open_video(p, fps=args.video_fps, jpeg_entropy=args.jpeg_entropy)
             else:
                 stores[p] = open_video(p)
+            if args.save_mjpeg:
+                import re
+                os.makedirs(args.save_mjpeg, exist_ok=True)
+                out = os.path.join(args.save_mjpeg, re.sub(r"[^A-Za-z0-9._-]+", "_", os.path.splitext(os.path.basename(p.rstrip("/")))[0] or "video") + ".avi")
+                if not os.path.exists(out):
+                    stores[p].save_mjpeg(out, quality=90)
         return stores[p]
 
     owl_kw = {}
@@ -141,6 +153,12 @@ def main():
         for group, ss, res in zip(groups, sss, search_lockstep_groups(sss)):
             for i, s, (frames, ts) in zip(group, ss, res):
                 rows.append([int(t) for t in ts])
+                if args.keyframe_jpegs:
+                    d = os.path.join(args.keyframe_jpegs, f"{i:05d}")
+                    os.makedirs(d, exist_ok=True)
+                    for t, data in zip(rows[-1], video_of(i).jpeg_frames(rows[-1])):
+                        with open(os.path.join(d, f"{t}.jpg"), "wb") as f:
+                            f.write(data)
                 dists[i] = s.P_history[-1] if s.P_history else []
                 uses[items[i]["video_path"]] -= 1
                 if uses[items[i]["video_path"]] == 0:      # the last question about this video: its frames (and frame records) can go

@@ -482,6 +482,40 @@ int tstar_jpeg_reconstruct_host(const int16_t* coef, const uint16_t* quant, int 
  * upsampling + YCbCr -> RGB into d_rgb u8 [n,H,W,3] (typically store[s0 : s0 + n]).  d_coef / d_quant 16-byte aligned. */
 int tstar_jpeg_reconstruct(const int16_t* d_coef, const uint16_t* d_quant, int n, int W, int H, int ncomp, int hs, int vs,
                            uint8_t* d_planes, uint8_t* d_rgb, void* stream);
+/* ---- Baseline JPEG ENCODE: RGB u8 frames -> the bytes Pillow's Image.fromarray(frame).save(buf, "JPEG", quality=q, subsampling=s)
+ * writes, for quality 1..100 and luma sampling (hs, vs) = (2,2) 4:2:0, (2,1) 4:2:2, (1,1) 4:4:4.  Two stages share the decoder's
+ * coefficient layout (above, 3 components): frames -> int16 coefficients, coefficients -> the stuffed bytes of the scan (from
+ * behind SOS to EOI).  The header (SOI .. SOS, 623 bytes) is the same for every frame of a call.  Per-frame status: 0 written,
+ * 1 the slot is too short (nothing of the frame is written; its length is then a lower bound), 2 a coefficient no 8-bit baseline
+ * JPEG can code.  The _host entries touch no HIP state.  counters (optional, u64 [5], added to): ZRL symbols, blocks without
+ * EOB, stuffed bytes, right-edge dummy blocks, bottom-edge dummy blocks. */
+/* Pure plan for n frames whose scans go into slots of slot_bytes: out8 = {blocks per frame, coefficient bytes per frame, bytes
+ * that hold any scan (2 * ceil(blocks * 1660 / 8) + 2: the longest codes everywhere, every byte stuffed, EOI), header bytes,
+ * workspace bytes, workgroups of the block stage, workgroups per frame of the entropy stage, of the stuffing passes}. */
+int tstar_jpeg_encode_plan(int W, int H, int hs, int vs, int n, size_t slot_bytes, size_t* out8);
+/* SOI, APP0, DQT x 2, SOF0, DHT x 4, SOS -> out (cap bytes), *len = 623.  TSTAR_ERR_ARG / 4 (cap short, nothing written). */
+int tstar_jpeg_encode_header(int W, int H, int quality, int hs, int vs, uint8_t* out, size_t cap, size_t* len);
+/* Block stage on the host: frames u8 [N,H,W,3], idx i32 [n] -> coef int16 [n][blocks][64]; quant (optional) u16 [3][64]. */
+int tstar_jpeg_encode_blocks_host(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
+                                  int16_t* coef, uint16_t* quant, int threads, uint64_t* counters);
+/* Scan stage on the host: coef -> out u8 [n][slot_bytes], lengths u32 [n], status i32 [n]. */
+int tstar_jpeg_encode_scan_host(const int16_t* coef, int n, int W, int H, int hs, int vs, uint8_t* out, size_t slot_bytes,
+                                uint32_t* lengths, int32_t* status, int threads, uint64_t* counters);
+/* Whole files on the host (header + scan) into slots of slot_bytes; never writes past a slot, a short slot is left as it was. */
+int tstar_jpeg_encode_host(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
+                           uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status, int threads, uint64_t* counters);
+/* Block stage on the device: d_frames u8 [N,H,W,3] (a resident store), d_idx i32 [n] device memory (read in place, no staging
+ * copy; an index outside 0..N-1 is clamped) -> d_coef (16-byte aligned); h_quant (optional, HOST) u16 [3][64]. */
+int tstar_jpeg_encode_blocks(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
+                             int16_t* d_coef, uint16_t* h_quant, void* stream);
+/* Scan stage on the device: d_coef -> d_out u8 [n][slot_bytes], d_lengths u32 [n], d_status i32 [n]; d_workspace: 16-byte
+ * aligned device memory of the plan's workspace bytes.  Nothing is written past a slot; no host synchronisation. */
+int tstar_jpeg_encode_scan(const int16_t* d_coef, int n, int W, int H, int hs, int vs, uint8_t* d_out, size_t slot_bytes,
+                           uint32_t* d_lengths, int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+/* Both stages: frames by index -> scans, lengths, status (d_coef: n * coefficient bytes of scratch). */
+int tstar_jpeg_encode(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
+                      int16_t* d_coef, uint8_t* d_out, size_t slot_bytes, uint32_t* d_lengths, int32_t* d_status, void* d_workspace,
+                      size_t workspace_bytes, void* stream);
 /* Entropy stage on the device.  The unit of parallel work is a SEGMENT: a run of MCUs that starts at a byte boundary with
  * zero DC predictors (one restart interval; a frame without DRI is one segment).  The planner below cuts frames into
  * segments on the host, the kernel decodes one segment per lane into the coefficient layout above, and

@@ -85,6 +85,14 @@ SIGNATURES = {
     "tstar_jpeg_entropy_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "tstar_jpeg_reconstruct_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i]),
     "tstar_jpeg_reconstruct": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "tstar_jpeg_encode_plan": (_i, [_i, _i, _i, _i, _i, _sz, _vp]),
+    "tstar_jpeg_encode_header": (_i, [_i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "tstar_jpeg_encode_blocks_host": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "tstar_jpeg_encode_scan_host": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _i, _vp]),
+    "tstar_jpeg_encode_host": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _i, _vp]),
+    "tstar_jpeg_encode_blocks": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "tstar_jpeg_encode_scan": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "tstar_jpeg_encode": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "tstar_jpeg_plan_segments": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "tstar_jpeg_entropy_device": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tstar_jpeg_entropy_segments_host": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -1,0 +1,484 @@
+// Baseline JPEG encoder, device half: RGB u8 frames of a resident store, gathered by an index list -> per frame the stuffed
+// entropy-coded bytes of one interleaved scan (the header is the same for every frame and is joined on the host).  The
+// integers are those of jpeg_enc_math.h, shared with the host twin (jpeg_enc_host.cpp): byte-equal to libjpeg-turbo as
+// Pillow drives it.  Layouts, the workspace and the capacity rule: jpeg_enc_host.h.
+//
+//   block stage    jpeg_enc_blocks_kernel    colour conversion, chroma downsampling, level shift, forward DCT, quantisation
+//                                            -> int16 coefficients in the decoder's layout
+//                  jpeg_enc_dummy_dc_kernel  DC of the dummy luma blocks of the last MCU column / row (a lookup of a real block)
+//   entropy stage  jpeg_enc_bits_kernel<0>   bit length of every block's codes (one lane per block, scan order)
+//                  jpeg_enc_offsets_kernel   exclusive sum per frame -> bit offsets, the scan's size, whether it can fit
+//                  jpeg_enc_bits_kernel<1>   the same walk again, writing the bits into the zeroed unstuffed stream: whole words
+//                                            stored, the two boundary words of a block merged by atomicOr (commutative: the
+//                                            result does not depend on the order of arrival)
+//   stuffing       jpeg_enc_ff_kernel<0>     0xFF bytes per chunk of 64 unstuffed bytes
+//                  jpeg_enc_lengths_kernel   exclusive sum per frame -> where each chunk lands, the frame's length and status
+//                  jpeg_enc_ff_kernel<1>     scatter with FF 00, one-bits in the last byte, EOI; only into slots that fit
+#include "../../include/tstar_hip.h"
+#include "common.h"
+#include "jpeg_enc_host.h"
+#include "jpeg_enc_math.h"
+
+namespace tstar {
+
+namespace {
+
+__constant__ jpegenc::EncTables kDevTables = jpegenc::make_tables();
+__constant__ uint8_t kDevZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+constexpr int kBlocksPerWg = 32;       // 256 threads: 8 lanes per 8x8 block
+constexpr int kRowPitch = 9;           // LDS dwords per block row, 72 per block: the bank argument of jpeg.hip's IDCT kernel
+constexpr int kBlockPitch = 72;
+
+struct EncQuant { uint16_t q[3][64]; };                       // by value in the kernel arguments (384 bytes)
+
+struct BlockArgs {
+    const uint8_t* frames;      // [N][H][W][3]
+    const int32_t* idx;         // [n]
+    int16_t* coef;              // [n][blocks][64]
+    int N, H, W, hs, vs;
+    int bw[3], bh[3];           // padded blocks of each component
+    int off[3];                 // first block of each component in a frame's layout
+    int real_bw, real_bh;       // luma blocks that hold picture
+    int blocks;                 // per frame
+    int dwords;                 // 1: frames and rows are dword-aligned (4 | W and an aligned store)
+    size_t total_blocks;
+};
+
+// npx (8 or 16) consecutive pixels of a row starting at x0 -> R | G << 8 | B << 16 each.  Inside the picture and dword-aligned
+// (x0 is a multiple of 8, so 3 * x0 of 24): 3 * npx / 4 dword loads.  Otherwise byte loads with the column clamped.
+template <int NPX>
+__device__ __forceinline__ void load_span(const uint8_t* __restrict__ row, int x0, int W, int dwords, uint32_t (&px)[NPX]) {
+    if (dwords && x0 + NPX <= W) {
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(row + 3 * (size_t)x0);
+        uint32_t w[NPX * 3 / 4];
+#pragma unroll
+        for (int k = 0; k < NPX * 3 / 4; ++k) w[k] = p[k];
+#pragma unroll
+        for (int k = 0; k < NPX / 4; ++k) {
+            px[4 * k] = w[3 * k] & 0xffffffu;
+            px[4 * k + 1] = (w[3 * k] >> 24) | ((w[3 * k + 1] & 0xffffu) << 8);
+            px[4 * k + 2] = (w[3 * k + 1] >> 16) | ((w[3 * k + 2] & 0xffu) << 16);
+            px[4 * k + 3] = w[3 * k + 2] >> 8;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NPX; ++k) {
+            const int x = x0 + k < W ? x0 + k : W - 1;
+            const uint8_t* p = row + 3 * (size_t)x;
+            px[k] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+        }
+    }
+}
+
+__device__ __forceinline__ int comp_of(int c, uint32_t px) {
+    return jpegenc::rgb_to_comp(c, (int)(px & 255), (int)((px >> 8) & 255), (int)(px >> 16));
+}
+
+// One workgroup = 32 consecutive blocks of the chunk (frame after frame, a frame's blocks in layout order).
+//   rows    lane (block, r) gathers the 8 samples of row r of its block (luma: 8 pixels of one picture row; subsampled chroma:
+//           16 pixels of one or two rows, box-filtered), subtracts 128, runs the row pass in registers and parks it in LDS;
+//   cols    lane (block, c) runs the column pass on column c, quantises and writes back in place;
+//   store   lane (block, r) packs row r to eight int16 and stores them as one 16-byte vector (a wave writes 1 KiB contiguous).
+// Dummy luma blocks are written as zeros here; jpeg_enc_dummy_dc_kernel fills their DC.
+__global__ __launch_bounds__(256) void jpeg_enc_blocks_kernel(BlockArgs a, EncQuant eq) {
+    __shared__ int32_t ws[kBlocksPerWg * kBlockPitch];
+    const int t = threadIdx.x, bl = t >> 3, r = t & 7;
+    const size_t gb = (size_t)blockIdx.x * kBlocksPerWg + bl;
+    const bool live = gb < a.total_blocks;
+    int c = 0, by = 0, bx = 0;
+    size_t f = 0;
+    bool real = false;
+    if (live) {
+        f = gb / (size_t)a.blocks;
+        const int g = (int)(gb % (size_t)a.blocks);
+        c = g >= a.off[2] ? 2 : (g >= a.off[1] ? 1 : 0);
+        const int gi = g - a.off[c];
+        by = gi / a.bw[c];
+        bx = gi % a.bw[c];
+        real = c != 0 || (by < a.real_bh && bx < a.real_bw);
+    }
+    int32_t* mine = ws + bl * kBlockPitch;
+    if (live && real) {
+        int fi = a.idx[f];
+        fi = fi < 0 ? 0 : (fi >= a.N ? a.N - 1 : fi);          // the entry checks what the host can see; a bad index never leaves the store
+        const uint8_t* frame = a.frames + (size_t)fi * a.H * a.W * 3;
+        int32_t d[8];
+        if (c == 0 || a.hs == 1) {
+            const int y = by * 8 + r < a.H ? by * 8 + r : a.H - 1;
+            uint32_t px[8];
+            load_span<8>(frame + (size_t)y * a.W * 3, bx * 8, a.W, a.dwords, px);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) d[k] = comp_of(c, px[k]) - 128;
+        } else {
+            const int oy = jpegenc::comp_row(c, by * 8 + r, a.H, a.vs);
+            int32_t sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (int j = 0; j < a.vs; ++j) {
+                const int y = oy * a.vs + j < a.H ? oy * a.vs + j : a.H - 1;
+                uint32_t px[16];
+                load_span<16>(frame + (size_t)y * a.W * 3, bx * 16, a.W, a.dwords, px);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) sum[k] += comp_of(c, px[2 * k]) + comp_of(c, px[2 * k + 1]);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int ox = bx * 8 + k;
+                d[k] = (a.vs == 2 ? (sum[k] + jpegenc::h2v2_bias(ox)) >> 2 : (sum[k] + jpegenc::h2v1_bias(ox)) >> 1) - 128;
+            }
+        }
+        int32_t o[8];
+        jpegenc::fdct8<true>(d, o);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) mine[r * kRowPitch + k] = o[k];
+    }
+    __syncthreads();
+    if (live && real) {
+        const int col = r;
+        int32_t d[8], o[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) d[k] = mine[k * kRowPitch + col];
+        jpegenc::fdct8<false>(d, o);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) mine[k * kRowPitch + col] = jpegenc::quantise(o[k], (int)eq.q[c][k * 8 + col]);
+    }
+    __syncthreads();
+    if (live) {
+        uint4 v = {0, 0, 0, 0};
+        if (real) {
+            const int32_t* row = mine + r * kRowPitch;
+            v.x = ((uint32_t)row[0] & 0xffffu) | ((uint32_t)row[1] << 16);
+            v.y = ((uint32_t)row[2] & 0xffffu) | ((uint32_t)row[3] << 16);
+            v.z = ((uint32_t)row[4] & 0xffffu) | ((uint32_t)row[5] << 16);
+            v.w = ((uint32_t)row[6] & 0xffffu) | ((uint32_t)row[7] << 16);
+        }
+        *reinterpret_cast<uint4*>(a.coef + gb * 64 + r * 8) = v;
+    }
+}
+
+// one lane per luma block of the chunk: a dummy block copies the DC of the real block jpegenc::dummy_source names
+__global__ __launch_bounds__(256) void jpeg_enc_dummy_dc_kernel(int16_t* __restrict__ coef, int blocks, int bw0, int bh0, int real_bw,
+                                                                int real_bh, int hs, size_t total) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int per = bw0 * bh0;
+    const size_t f = i / (size_t)per;
+    const int g = (int)(i % (size_t)per), by = g / bw0, bx = g % bw0;
+    int kind;
+    const int src = jpegenc::dummy_source(by, bx, real_bw, real_bh, hs, bw0, &kind);
+    if (src < 0) return;
+    int16_t* fc = coef + f * (size_t)blocks * 64;
+    fc[(size_t)g * 64] = fc[(size_t)src * 64];
+}
+
+// ------------------------------------------------------------------------------------------------ entropy stage
+enum { META_BITS = 0, META_BYTES = 1, META_FF = 2, META_FLAGS = 3 };
+enum { FLAG_BAD_COEF = 1, FLAG_SKIP = 2 };          // SKIP: the unstuffed bytes alone exceed the slot; nothing of the frame is written
+
+struct EntropyArgs {
+    const int16_t* coef;
+    uint32_t* meta;             // [n][4]
+    uint32_t* bits;             // [n][blocks]
+    uint32_t* raw;              // [n][raw_words]
+    jpegenc::ScanGeom sg;
+    int blocks;
+    uint32_t raw_words;
+};
+
+struct CountPut {
+    uint32_t n = 0;
+    __device__ __forceinline__ void operator()(unsigned, int len) { n += (uint32_t)len; }
+};
+
+// Writes the bits of one block at bit offset `pos` of a big-endian word stream.  A word is stored whole when every bit of it
+// is this block's; the first and the last word of the block, which neighbours share, are merged by atomicOr into the zeroed
+// buffer.  Nothing is written at or beyond word `limit`.
+struct WritePut {
+    uint32_t* words;
+    uint32_t w, limit;
+    uint64_t acc = 0;
+    int nb;
+    bool first = true;
+    __device__ __forceinline__ WritePut(uint32_t* words_, uint32_t pos, uint32_t limit_) : words(words_), w(pos >> 5), limit(limit_), nb((int)(pos & 31)) {}
+    __device__ __forceinline__ void emit(uint32_t v) {
+        if (w < limit) {
+            if (first) atomicOr(words + w, v);
+            else words[w] = v;
+        }
+        first = false;
+        ++w;
+    }
+    __device__ __forceinline__ void operator()(unsigned code, int len) {
+        acc = (acc << len) | code;
+        nb += len;
+        if (nb >= 32) {
+            nb -= 32;
+            emit((uint32_t)(acc >> nb));
+            acc &= (1ull << nb) - 1ull;
+        }
+    }
+    __device__ __forceinline__ void finish() {
+        if (nb && w < limit) atomicOr(words + w, (uint32_t)(acc << (32 - nb)));
+    }
+};
+
+// grid (ceil(blocks / 256), n): lane k of frame f walks the k-th block of the scan.  The DC predictor is the quantised DC of the
+// previous block of the component, a lookup in the coefficients.
+template <int WRITE>
+__global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(EntropyArgs a) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+    if (k >= a.blocks) return;
+    uint32_t* meta = a.meta + (size_t)f * 4;
+    if (WRITE && meta[META_FLAGS]) return;
+    int c, b, pb;
+    jpegenc::scan_block(a.sg, k, &c, &b, &pb);
+    const int16_t* fc = a.coef + (size_t)f * a.blocks * 64;
+    const int pred = pb < 0 ? 0 : fc[(size_t)pb * 64];
+    const jpegenc::HuffCodes& dc = kDevTables.codes[c ? 2 : 0];
+    const jpegenc::HuffCodes& ac = kDevTables.codes[c ? 3 : 1];
+    if (WRITE) {
+        WritePut put(a.raw + (size_t)f * a.raw_words, a.bits[(size_t)f * a.blocks + k], a.raw_words);
+        jpegenc::encode_block(fc + (size_t)b * 64, pred, dc, ac, kDevZigzag, put);
+        put.finish();
+    } else {
+        CountPut put;
+        const jpegenc::BlockEvents ev = jpegenc::encode_block(fc + (size_t)b * 64, pred, dc, ac, kDevZigzag, put);
+        a.bits[(size_t)f * a.blocks + k] = put.n;
+        if (ev.bad) atomicOr(meta + META_FLAGS, (uint32_t)FLAG_BAD_COEF);
+    }
+}
+
+// In-place exclusive sum of data[0 .. count) by one workgroup of 256 lanes, tiles of 1024 with a running carry; every lane
+// returns the total.  Wave sums by shuffles, the four waves' sums through LDS.
+__device__ uint32_t workgroup_exclusive_scan(uint32_t* data, uint32_t count) {
+    __shared__ uint32_t wave_sum[4];
+    __shared__ uint32_t carry_s;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) carry_s = 0;
+    __syncthreads();
+    for (uint32_t base = 0; base < count; base += 1024) {
+        const uint32_t i0 = base + (uint32_t)t * 4;
+        uint32_t v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = i0 + j < count ? data[i0 + j] : 0u;
+        const uint32_t mine = v[0] + v[1] + v[2] + v[3];
+        uint32_t inc = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += up;
+        }
+        if (lane == 63) wave_sum[wave] = inc;
+        __syncthreads();
+        uint32_t before = carry_s;
+        for (int w = 0; w < wave; ++w) before += wave_sum[w];
+        uint32_t run = before + inc - mine;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (i0 + j < count) data[i0 + j] = run;
+            run += v[j];
+        }
+        __syncthreads();
+        if (t == 255) carry_s = before + inc;
+        __syncthreads();
+    }
+    return carry_s;
+}
+
+// grid (n): block lengths -> bit offsets; the scan's bits and unstuffed bytes; frames whose unstuffed bytes and EOI alone
+// exceed the slot are marked and never written
+__global__ __launch_bounds__(256) void jpeg_enc_offsets_kernel(uint32_t* bits, uint32_t* meta, int blocks, uint32_t slot_bytes) {
+    const int f = blockIdx.x;
+    const uint32_t total = workgroup_exclusive_scan(bits + (size_t)f * blocks, (uint32_t)blocks);
+    if (threadIdx.x == 0) {
+        uint32_t* m = meta + (size_t)f * 4;
+        const uint32_t nbytes = (total >> 3) + ((total & 7u) ? 1u : 0u);          // total < 2^32 by the plan's bound
+        m[META_BITS] = total;
+        m[META_BYTES] = nbytes;
+        if ((uint64_t)nbytes + 2 > slot_bytes) atomicOr(m + META_FLAGS, (uint32_t)FLAG_SKIP);
+    }
+}
+
+struct StuffArgs {
+    const uint32_t* raw;
+    uint32_t* meta;
+    uint32_t* ff;               // [n][ff_chunks]
+    uint8_t* out;               // [n][slot_bytes]
+    uint32_t* lengths;
+    int32_t* status;
+    uint32_t raw_words, ff_chunks, slot_bytes;
+};
+
+// byte i of the unstuffed stream (i < nbytes); the last byte's unused low bits are ones
+__device__ __forceinline__ uint32_t raw_byte(const uint32_t* raw, uint32_t i, uint32_t nbytes, uint32_t total_bits) {
+    uint32_t b = (raw[i >> 2] >> (24 - 8 * (i & 3))) & 255u;
+    if (i + 1 == nbytes && (total_bits & 7u)) b |= (1u << (8 - (total_bits & 7u))) - 1u;
+    return b;
+}
+
+// grid (ceil(ff_chunks / 256), n): one lane per chunk of 64 unstuffed bytes.  SCATTER = 0 counts its 0xFF bytes; SCATTER = 1
+// writes the chunk at its place in the slot (its raw offset plus the 0xFF bytes before it) and, from the lane of the last
+// chunk, EOI.  A frame whose status is not 0 is left alone, so every write lands inside [0, length) <= slot_bytes.
+template <int SCATTER>
+__global__ __launch_bounds__(256) void jpeg_enc_ff_kernel(StuffArgs a) {
+    const uint32_t chunk = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+    const uint32_t* m = a.meta + (size_t)f * 4;
+    if (m[META_FLAGS]) return;
+    const uint32_t nbytes = m[META_BYTES], total_bits = m[META_BITS];
+    const uint32_t begin = chunk * (uint32_t)kJpegEncStuffChunk;
+    if (chunk >= a.ff_chunks || begin >= nbytes) return;
+    const uint32_t end = begin + kJpegEncStuffChunk < nbytes ? begin + kJpegEncStuffChunk : nbytes;
+    const uint32_t* raw = a.raw + (size_t)f * a.raw_words;
+    if (!SCATTER) {
+        uint32_t n = 0;
+        for (uint32_t i = begin; i < end; ++i) n += raw_byte(raw, i, nbytes, total_bits) == 255u;
+        a.ff[(size_t)f * a.ff_chunks + chunk] = n;
+    } else {
+        if (a.status[f] != JPEG_ENC_OK) return;
+        uint8_t* out = a.out + (size_t)f * a.slot_bytes;
+        const uint32_t len = a.lengths[f];
+        uint32_t o = begin + a.ff[(size_t)f * a.ff_chunks + chunk];
+        for (uint32_t i = begin; i < end; ++i) {
+            const uint32_t b = raw_byte(raw, i, nbytes, total_bits);
+            if (o < len) out[o] = (uint8_t)b;
+            ++o;
+            if (b == 255u) {
+                if (o < len) out[o] = 0;
+                ++o;
+            }
+        }
+        if (end == nbytes && o + 2 == len) {
+            out[o] = 0xFF;
+            out[o + 1] = 0xD9;
+        }
+    }
+}
+
+// grid (n): chunk counts -> the count before each chunk; the frame's length (with EOI) and status
+__global__ __launch_bounds__(256) void jpeg_enc_lengths_kernel(StuffArgs a) {
+    const int f = blockIdx.x;
+    uint32_t* m = a.meta + (size_t)f * 4;
+    const uint32_t flags = m[META_FLAGS], nbytes = m[META_BYTES];
+    uint32_t total = 0;
+    if (!flags) {
+        const uint32_t chunks = (nbytes + kJpegEncStuffChunk - 1) / kJpegEncStuffChunk;
+        total = workgroup_exclusive_scan(a.ff + (size_t)f * a.ff_chunks, chunks < a.ff_chunks ? chunks : a.ff_chunks);
+    }
+    if (threadIdx.x == 0) {
+        m[META_FF] = total;
+        const uint64_t len = (uint64_t)nbytes + total + 2;
+        if (flags & FLAG_BAD_COEF) {
+            a.lengths[f] = 0;
+            a.status[f] = JPEG_ENC_BAD_COEF;
+        } else if (flags || len > a.slot_bytes) {
+            // a skipped frame's 0xFF bytes were never counted: its length is a lower bound, which is all a short status promises
+            a.lengths[f] = (uint32_t)(len > 0xffffffffull ? 0xffffffffull : len);
+            a.status[f] = JPEG_ENC_SHORT;
+        } else {
+            a.lengths[f] = (uint32_t)len;
+            a.status[f] = JPEG_ENC_OK;
+        }
+    }
+}
+
+}  // namespace
+
+int jpeg_encode_blocks_u8(const uint8_t* frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, const JpegGeom& g,
+                          int16_t* coef, hipStream_t s) {
+    const JpegEncPlan p = plan_jpeg_encode(g, n, 2);
+    TSTAR_REQUIRE(!p.error, std::string("jpeg_encode_blocks_u8: ") + (p.error ? p.error : ""));
+    TSTAR_REQUIRE(N >= 1 && quality >= 1 && quality <= 100, "jpeg_encode_blocks_u8: empty store or quality outside 1..100");
+    TSTAR_REQUIRE((uintptr_t)coef % 16 == 0, "jpeg_encode_blocks_u8: the coefficient buffer needs 16-byte alignment");
+    BlockArgs a;
+    a.frames = frames; a.idx = d_idx; a.coef = coef;
+    a.N = N; a.H = H; a.W = W; a.hs = g.hs; a.vs = g.vs;
+    for (int c = 0; c < 3; ++c) { a.bw[c] = g.bw(c); a.bh[c] = g.bh(c); a.off[c] = (int)g.block_offset(c); }
+    a.real_bw = (W + 7) / 8; a.real_bh = (H + 7) / 8;
+    a.blocks = (int)p.blocks;
+    a.dwords = (W % 4 == 0 && (uintptr_t)frames % 4 == 0) ? 1 : 0;
+    a.total_blocks = (size_t)n * p.blocks;
+    EncQuant eq;
+    jpeg_enc_quant(quality, &eq.q[0][0]);
+    hipLaunchKernelGGL(jpeg_enc_blocks_kernel, dim3(p.block_wgs), dim3(256), 0, s, a, eq);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    if (g.hs * g.vs > 1 && (g.bw(0) > a.real_bw || g.bh(0) > a.real_bh)) {
+        const size_t total = (size_t)n * g.bw(0) * g.bh(0);
+        hipLaunchKernelGGL(jpeg_enc_dummy_dc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, coef, a.blocks, g.bw(0), g.bh(0),
+                           a.real_bw, a.real_bh, g.hs, total);
+        TSTAR_HIP_CHECK(hipGetLastError());
+    }
+    return TSTAR_OK;
+}
+
+int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status,
+                        void* workspace, size_t workspace_bytes, hipStream_t s) {
+    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes);
+    TSTAR_REQUIRE(!p.error, std::string("jpeg_encode_scan_u8: ") + (p.error ? p.error : ""));
+    TSTAR_REQUIRE((uintptr_t)workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
+                  "jpeg_encode_scan_u8: the workspace is misaligned or smaller than the plan's workspace_bytes");
+    uint8_t* ws = (uint8_t*)workspace;
+    EntropyArgs e;
+    e.coef = coef;
+    e.meta = (uint32_t*)(ws + p.off_meta);
+    e.bits = (uint32_t*)(ws + p.off_bits);
+    e.raw = (uint32_t*)(ws + p.off_raw);
+    e.sg = jpegenc::ScanGeom{g.hs, g.vs, g.mcux(), g.mcuy(), g.bw(0), (int)g.block_offset(1), (int)g.block_offset(2)};
+    e.blocks = (int)p.blocks;
+    e.raw_words = (uint32_t)p.raw_words;
+    // meta (flags) and the unstuffed stream start from zero: the stream is assembled by OR
+    TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), s));
+    TSTAR_HIP_CHECK(hipMemsetAsync(e.raw, 0, (size_t)n * p.raw_words * sizeof(uint32_t), s));
+    const dim3 egrid(p.entropy_wgs_x, (unsigned)n), sgrid(p.stuff_wgs_x, (unsigned)n);
+    hipLaunchKernelGGL(jpeg_enc_bits_kernel<0>, egrid, dim3(256), 0, s, e);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_offsets_kernel, dim3((unsigned)n), dim3(256), 0, s, e.bits, e.meta, e.blocks, (uint32_t)slot_bytes);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_bits_kernel<1>, egrid, dim3(256), 0, s, e);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    StuffArgs a;
+    a.raw = e.raw; a.meta = e.meta;
+    a.ff = (uint32_t*)(ws + p.off_ff);
+    a.out = out; a.lengths = lengths; a.status = status;
+    a.raw_words = (uint32_t)p.raw_words; a.ff_chunks = (uint32_t)p.ff_chunks; a.slot_bytes = (uint32_t)slot_bytes;
+    hipLaunchKernelGGL(jpeg_enc_ff_kernel<0>, sgrid, dim3(256), 0, s, a);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_lengths_kernel, dim3((unsigned)n), dim3(256), 0, s, a);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_ff_kernel<1>, sgrid, dim3(256), 0, s, a);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    return TSTAR_OK;
+}
+
+}  // namespace tstar
+
+using namespace tstar;
+
+extern "C" {
+
+int tstar_jpeg_encode_blocks(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
+                             int16_t* d_coef, uint16_t* h_quant, void* stream) {
+    TSTAR_REQUIRE(d_frames && d_idx && d_coef, "tstar_jpeg_encode_blocks: null argument");
+    const JpegGeom g{W, H, 3, hs, vs};
+    RC(jpeg_encode_blocks_u8(d_frames, N, H, W, d_idx, n, quality, g, d_coef, (hipStream_t)stream));
+    if (h_quant) jpeg_enc_quant(quality, h_quant);
+    return TSTAR_OK;
+}
+
+int tstar_jpeg_encode_scan(const int16_t* d_coef, int n, int W, int H, int hs, int vs, uint8_t* d_out, size_t slot_bytes,
+                           uint32_t* d_lengths, int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
+    TSTAR_REQUIRE(d_coef && d_out && d_lengths && d_status && d_workspace, "tstar_jpeg_encode_scan: null argument");
+    return jpeg_encode_scan_u8(d_coef, n, JpegGeom{W, H, 3, hs, vs}, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes,
+                               (hipStream_t)stream);
+}
+
+int tstar_jpeg_encode(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
+                      int16_t* d_coef, uint8_t* d_out, size_t slot_bytes, uint32_t* d_lengths, int32_t* d_status, void* d_workspace,
+                      size_t workspace_bytes, void* stream) {
+    TSTAR_REQUIRE(d_frames && d_idx && d_coef && d_out && d_lengths && d_status && d_workspace, "tstar_jpeg_encode: null argument");
+    const JpegGeom g{W, H, 3, hs, vs};
+    RC(jpeg_encode_blocks_u8(d_frames, N, H, W, d_idx, n, quality, g, d_coef, (hipStream_t)stream));
+    return jpeg_encode_scan_u8(d_coef, n, g, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

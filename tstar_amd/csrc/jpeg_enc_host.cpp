@@ -1,0 +1,319 @@
+// Baseline JPEG encoder, host half: see jpeg_enc_host.h.  HIP-free; every integer comes from jpeg_enc_math.h, which the
+// kernels of jpeg_enc.hip share.
+#include "jpeg_enc_host.h"
+
+#include <string.h>
+
+#include <atomic>
+#include <initializer_list>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "jpeg_enc_math.h"
+
+namespace tstar {
+
+void set_error(const std::string& msg);          // capi.hip (or the stand-alone checker): thread-local last error
+
+namespace {
+constexpr jpegenc::EncTables kTables = jpegenc::make_tables();
+}
+
+bool jpeg_enc_geom_ok(const JpegGeom& g) {
+    return g.W > 0 && g.H > 0 && g.W <= 16384 && g.H <= 16384 && g.ncomp == 3 &&
+           ((g.hs == 1 && g.vs == 1) || (g.hs == 2 && (g.vs == 1 || g.vs == 2)));
+}
+
+size_t jpeg_enc_max_scan_bytes(const JpegGeom& g) { return 2 * ((g.blocks() * (size_t)jpegenc::kMaxBlockBits + 7) / 8) + 2; }
+
+JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes) {
+    JpegEncPlan p = {};
+    if (!jpeg_enc_geom_ok(g)) { p.error = "unsupported geometry (3 components, sampling 2x2 / 2x1 / 1x1, sides 1..16384)"; return p; }
+    if (n < 1 || n > 65535) { p.error = "n must be in 1..65535"; return p; }
+    p.blocks = g.blocks();
+    if (p.blocks * (size_t)jpegenc::kMaxBlockBits >= (1ull << 32)) { p.error = "frame too large: a scan's bit offsets would not fit 32 bits"; return p; }
+    if (slot_bytes < 2 || slot_bytes >= (1ull << 31)) { p.error = "slot_bytes must be in 2..2^31-1"; return p; }
+    p.coef_bytes = p.blocks * 128;
+    p.max_scan_bytes = jpeg_enc_max_scan_bytes(g);
+    p.header_bytes = kJpegEncHeaderBytes;
+    const size_t max_raw = (p.blocks * (size_t)jpegenc::kMaxBlockBits + 7) / 8;
+    const size_t raw_cap = slot_bytes < max_raw ? slot_bytes : max_raw;      // unstuffed bytes never exceed the stuffed ones
+    p.raw_words = raw_cap / 4 + 1;
+    p.ff_chunks = (p.raw_words * 4 + kJpegEncStuffChunk - 1) / kJpegEncStuffChunk;
+    auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+    p.off_meta = 0;
+    p.off_bits = up((size_t)n * 4 * sizeof(uint32_t));
+    p.off_raw = p.off_bits + up((size_t)n * p.blocks * sizeof(uint32_t));
+    p.off_ff = p.off_raw + up((size_t)n * p.raw_words * sizeof(uint32_t));
+    p.workspace_bytes = p.off_ff + up((size_t)n * p.ff_chunks * sizeof(uint32_t));
+    const size_t total_blocks = (size_t)n * p.blocks;
+    if (total_blocks / 32 + 1 >= 0x7fffffffull) { p.error = "chunk too large for one launch"; return p; }
+    p.block_wgs = (unsigned)((total_blocks + 31) / 32);
+    p.entropy_wgs_x = (unsigned)((p.blocks + 255) / 256);
+    p.stuff_wgs_x = (unsigned)((p.ff_chunks + 255) / 256);
+    return p;
+}
+
+void jpeg_enc_quant(int quality, uint16_t* quant) {
+    const int scale = jpegenc::quality_scale(quality);
+    for (int c = 0; c < 3; ++c)
+        for (int k = 0; k < 64; ++k) quant[c * 64 + k] = (uint16_t)jpegenc::quant_entry(jpegenc::kStd.q[c ? 1 : 0][k], scale);
+}
+
+void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out) {
+    uint8_t* p = out;
+    auto put = [&](std::initializer_list<int> v) { for (int b : v) *p++ = (uint8_t)b; };
+    uint16_t quant[192];
+    jpeg_enc_quant(quality, quant);
+    put({0xFF, 0xD8});
+    put({0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
+    for (int t = 0; t < 2; ++t) {
+        put({0xFF, 0xDB, 0, 67, t});
+        for (int k = 0; k < 64; ++k) *p++ = (uint8_t)quant[t * 64 + jpegenc::kStd.zigzag[k]];
+    }
+    put({0xFF, 0xC0, 0, 17, 8, g.H >> 8, g.H & 255, g.W >> 8, g.W & 255, 3, 1, (g.hs << 4) | g.vs, 0, 2, 0x11, 1, 3, 0x11, 1});
+    const int ids[4] = {0x00, 0x10, 0x01, 0x11};                // DC 0, AC 0, DC 1, AC 1
+    for (int t = 0; t < 4; ++t) {
+        const jpegenc::HuffSpec& s = kTables.spec[t];
+        const int len = 2 + 1 + 16 + s.nvals;
+        put({0xFF, 0xC4, len >> 8, len & 255, ids[t]});
+        for (int i = 0; i < 16; ++i) *p++ = s.bits[i];
+        for (int i = 0; i < s.nvals; ++i) *p++ = s.vals[i];
+    }
+    put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
+}
+
+void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2) {
+    const int real_bw = (g.W + 7) / 8, real_bh = (g.H + 7) / 8;
+    for (int c = 0; c < 3; ++c) {
+        const int bw = g.bw(c), bh = g.bh(c);
+        int16_t* cc = coef + g.block_offset(c) * 64;
+        const uint16_t* q = quant + 64 * c;
+        for (int by = 0; by < bh; ++by)
+            for (int bx = 0; bx < bw; ++bx) {
+                int16_t* o = cc + ((size_t)by * bw + bx) * 64;
+                if (c == 0 && (by >= real_bh || bx >= real_bw)) {       // DC in the second loop below
+                    memset(o, 0, 128);
+                    continue;
+                }
+                int32_t ws[64];
+                for (int r = 0; r < 8; ++r) {
+                    int32_t d[8];
+                    for (int i = 0; i < 8; ++i) d[i] = jpegenc::sample_at(rgb, g.W, g.H, g.hs, g.vs, c, by * 8 + r, bx * 8 + i) - 128;
+                    jpegenc::fdct8<true>(d, ws + r * 8);
+                }
+                for (int i = 0; i < 8; ++i) {
+                    int32_t d[8], t[8];
+                    for (int r = 0; r < 8; ++r) d[r] = ws[r * 8 + i];
+                    jpegenc::fdct8<false>(d, t);
+                    for (int r = 0; r < 8; ++r) o[r * 8 + i] = (int16_t)jpegenc::quantise(t[r], q[r * 8 + i]);
+                }
+            }
+    }
+    const int bw0 = g.bw(0), bh0 = g.bh(0);
+    for (int by = 0; by < bh0; ++by)
+        for (int bx = 0; bx < bw0; ++bx) {
+            int kind = 0;
+            const int src = jpegenc::dummy_source(by, bx, real_bw, real_bh, g.hs, bw0, &kind);
+            if (src < 0) continue;
+            coef[((size_t)by * bw0 + bx) * 64] = coef[(size_t)src * 64];
+            if (dummy2) ++dummy2[kind];
+        }
+}
+
+namespace {
+
+jpegenc::ScanGeom scan_geom(const JpegGeom& g) {
+    return jpegenc::ScanGeom{g.hs, g.vs, g.mcux(), g.mcuy(), g.bw(0), (int)g.block_offset(1), (int)g.block_offset(2)};
+}
+
+struct ByteSink {                        // MSB-first bit writer with FF -> FF 00
+    std::vector<uint8_t> bytes;
+    uint64_t acc = 0, stuffed = 0;
+    int nb = 0;
+    void byte(uint8_t b) {
+        bytes.push_back(b);
+        if (b == 0xFF) { bytes.push_back(0); ++stuffed; }
+    }
+    void operator()(unsigned code, int len) {
+        acc = (acc << len) | code;
+        nb += len;
+        while (nb >= 8) {
+            byte((uint8_t)(acc >> (nb - 8)));
+            nb -= 8;
+        }
+    }
+    void finish() {
+        if (nb) byte((uint8_t)((acc << (8 - nb)) | ((1u << (8 - nb)) - 1u)));
+        nb = 0;
+        bytes.push_back(0xFF);
+        bytes.push_back(0xD9);
+    }
+};
+
+}  // namespace
+
+// the whole scan of one frame into sink.bytes; JPEG_ENC_OK or JPEG_ENC_BAD_COEF
+static int scan_frame(const int16_t* coef, const JpegGeom& g, ByteSink& sink, uint64_t* counters) {
+    const jpegenc::ScanGeom sg = scan_geom(g);
+    sink.bytes.reserve(g.blocks() * 16);
+    uint64_t zrl = 0, no_eob = 0;
+    int bad = 0;
+    const int nb = sg.blocks();
+    for (int k = 0; k < nb; ++k) {
+        int c, b, pb;
+        jpegenc::scan_block(sg, k, &c, &b, &pb);
+        const int pred = pb < 0 ? 0 : coef[(size_t)pb * 64];
+        const jpegenc::BlockEvents ev = jpegenc::encode_block(coef + (size_t)b * 64, pred, kTables.codes[c ? 2 : 0], kTables.codes[c ? 3 : 1],
+                                                              jpegenc::kStd.zigzag, sink);
+        zrl += (uint64_t)ev.zrl;
+        no_eob += (uint64_t)ev.no_eob;
+        bad |= ev.bad;
+    }
+    sink.finish();
+    if (counters) {
+        counters[JPEG_ENC_N_ZRL] += zrl;
+        counters[JPEG_ENC_N_NO_EOB] += no_eob;
+        counters[JPEG_ENC_N_STUFFED] += sink.stuffed;
+    }
+    return bad ? JPEG_ENC_BAD_COEF : JPEG_ENC_OK;
+}
+
+int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, uint8_t* out, size_t cap, size_t* len, uint64_t* counters) {
+    ByteSink sink;
+    *len = 0;
+    if (scan_frame(coef, g, sink, counters) != JPEG_ENC_OK) return JPEG_ENC_BAD_COEF;
+    *len = sink.bytes.size();
+    if (sink.bytes.size() > cap) return JPEG_ENC_SHORT;
+    memcpy(out, sink.bytes.data(), sink.bytes.size());
+    return JPEG_ENC_OK;
+}
+
+namespace {
+
+// run fn(i, counters of the worker) for i in [0, n) on up to `threads` workers; the workers' counters are summed into `counters`
+template <class F>
+void parallel_frames(int n, int threads, uint64_t* counters, F fn) {
+    const int allow = jpeg_thread_allowance(threads);
+    const int t = allow < n ? allow : n;
+    std::vector<uint64_t> local((size_t)(t < 1 ? 1 : t) * JPEG_ENC_N_COUNTERS, 0);
+    if (t <= 1) {
+        for (int i = 0; i < n; ++i) fn(i, local.data());
+    } else {
+        std::atomic<int> next{0};
+        std::vector<std::thread> pool;
+        pool.reserve((size_t)t);
+        for (int w = 0; w < t; ++w)
+            pool.emplace_back([&, w] {
+                for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i, local.data() + (size_t)w * JPEG_ENC_N_COUNTERS);
+            });
+        for (auto& th : pool) th.join();
+    }
+    if (counters)
+        for (size_t k = 0; k < local.size(); ++k) counters[k % JPEG_ENC_N_COUNTERS] += local[k];
+}
+
+bool frames_args_ok(const char* fn, const void* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs, JpegGeom* g) {
+    *g = JpegGeom{W, H, 3, hs, vs};
+    if (!frames || !idx || N < 1 || n < 1 || quality < 1 || quality > 100 || !jpeg_enc_geom_ok(*g)) {
+        set_error(std::string(fn) + ": null argument, empty batch, quality outside 1..100 or unsupported geometry");
+        return false;
+    }
+    for (int i = 0; i < n; ++i)
+        if (idx[i] < 0 || idx[i] >= N) {
+            set_error(std::string(fn) + ": frame index " + std::to_string(idx[i]) + " outside the " + std::to_string(N) + " frames");
+            return false;
+        }
+    return true;
+}
+
+}  // namespace
+}  // namespace tstar
+
+// ---------------------------------------------------------------------------------------------- C ABI (include/tstar_hip.h)
+using namespace tstar;
+
+extern "C" {
+
+int tstar_jpeg_encode_plan(int W, int H, int hs, int vs, int n, size_t slot_bytes, size_t* out8) {
+    if (!out8) { set_error("tstar_jpeg_encode_plan: null argument"); return 1; }
+    const JpegEncPlan p = plan_jpeg_encode(JpegGeom{W, H, 3, hs, vs}, n, slot_bytes);
+    if (p.error) { set_error(std::string("tstar_jpeg_encode_plan: ") + p.error); return 1; }
+    out8[0] = p.blocks; out8[1] = p.coef_bytes; out8[2] = p.max_scan_bytes; out8[3] = p.header_bytes; out8[4] = p.workspace_bytes;
+    out8[5] = p.block_wgs; out8[6] = p.entropy_wgs_x; out8[7] = p.stuff_wgs_x;
+    return 0;
+}
+
+int tstar_jpeg_encode_header(int W, int H, int quality, int hs, int vs, uint8_t* out, size_t cap, size_t* len) {
+    const JpegGeom g{W, H, 3, hs, vs};
+    if (!out || !len || quality < 1 || quality > 100 || !jpeg_enc_geom_ok(g)) {
+        set_error("tstar_jpeg_encode_header: null argument, quality outside 1..100 or unsupported geometry");
+        return 1;
+    }
+    *len = kJpegEncHeaderBytes;
+    if (cap < (size_t)kJpegEncHeaderBytes) { set_error("tstar_jpeg_encode_header: the buffer is shorter than the header"); return 4; }
+    jpeg_enc_header(g, quality, out);
+    return 0;
+}
+
+int tstar_jpeg_encode_blocks_host(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
+                                  int16_t* coef, uint16_t* quant, int threads, uint64_t* counters) {
+    JpegGeom g;
+    if (!frames_args_ok("tstar_jpeg_encode_blocks_host", frames, N, H, W, idx, n, quality, hs, vs, &g)) return 1;
+    if (!coef) { set_error("tstar_jpeg_encode_blocks_host: null argument"); return 1; }
+    uint16_t q[192];
+    jpeg_enc_quant(quality, q);
+    if (quant) memcpy(quant, q, sizeof(q));
+    const size_t per = g.blocks() * 64, frame = (size_t)W * H * 3;
+    parallel_frames(n, threads, counters, [&](int i, uint64_t* cnt) {
+        jpeg_enc_blocks(frames + frame * (size_t)idx[i], g, q, coef + per * (size_t)i, cnt + JPEG_ENC_N_DUMMY_RIGHT);
+    });
+    return 0;
+}
+
+int tstar_jpeg_encode_scan_host(const int16_t* coef, int n, int W, int H, int hs, int vs, uint8_t* out, size_t slot_bytes,
+                                uint32_t* lengths, int32_t* status, int threads, uint64_t* counters) {
+    const JpegGeom g{W, H, 3, hs, vs};
+    if (!coef || !lengths || !status || (!out && slot_bytes) || n < 1 || !jpeg_enc_geom_ok(g)) {
+        set_error("tstar_jpeg_encode_scan_host: null argument, empty batch or unsupported geometry");
+        return 1;
+    }
+    const size_t per = g.blocks() * 64;
+    parallel_frames(n, threads, counters, [&](int i, uint64_t* cnt) {
+        size_t len = 0;
+        status[i] = jpeg_enc_scan(coef + per * (size_t)i, g, out + slot_bytes * (size_t)i, slot_bytes, &len, cnt);
+        lengths[i] = (uint32_t)len;
+    });
+    return 0;
+}
+
+int tstar_jpeg_encode_host(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
+                           uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status, int threads, uint64_t* counters) {
+    JpegGeom g;
+    if (!frames_args_ok("tstar_jpeg_encode_host", frames, N, H, W, idx, n, quality, hs, vs, &g)) return 1;
+    if (!lengths || !status || (!out && slot_bytes)) { set_error("tstar_jpeg_encode_host: null argument"); return 1; }
+    uint16_t q[192];
+    jpeg_enc_quant(quality, q);
+    uint8_t header[kJpegEncHeaderBytes];
+    jpeg_enc_header(g, quality, header);
+    const size_t per = g.blocks() * 64, frame = (size_t)W * H * 3;
+    parallel_frames(n, threads, counters, [&](int i, uint64_t* cnt) {
+        std::vector<int16_t> coef(per);
+        jpeg_enc_blocks(frames + frame * (size_t)idx[i], g, q, coef.data(), cnt + JPEG_ENC_N_DUMMY_RIGHT);
+        uint8_t* slot = out + slot_bytes * (size_t)i;
+        // the scan goes behind the header only when the whole file fits: a short slot is left as it was
+        ByteSink sink;
+        const int rc = scan_frame(coef.data(), g, sink, cnt);
+        const size_t len = sink.bytes.size();
+        lengths[i] = (uint32_t)(kJpegEncHeaderBytes + len);
+        status[i] = rc;
+        if (rc != JPEG_ENC_OK) return;
+        if (kJpegEncHeaderBytes + len > slot_bytes) { status[i] = JPEG_ENC_SHORT; return; }
+        memcpy(slot, header, kJpegEncHeaderBytes);
+        memcpy(slot + kJpegEncHeaderBytes, sink.bytes.data(), len);
+    });
+    return 0;
+}
+
+}  // extern "C"

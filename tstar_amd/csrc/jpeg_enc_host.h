@@ -1,0 +1,67 @@
+// Baseline JPEG encoder, host half (HIP-free: also compiled alone by the CPU sanitizer build).  The twin of jpeg_enc.hip:
+// the same two stages on the same integers (jpeg_enc_math.h), byte-equal to Pillow's
+// Image.fromarray(frame).save(buf, "JPEG", quality=q, subsampling=s).
+//
+//   stage 1  RGB u8 frames -> int16 coefficients in the DECODER's layout (jpeg_host.h: [g.blocks()][64], natural order,
+//            component after component, block raster, padded to whole MCUs; g.ncomp = 3)
+//   stage 2  coefficients -> the stuffed entropy-coded bytes of the one interleaved scan, ending in EOI
+//   header   SOI, APP0, DQT x 2, SOF0, DHT x 4, SOS: the same for every frame of a call
+//
+// Capacity rule of a scan buffer: jpeg_enc_max_scan_bytes(g) always fits.  It is 2 * ceil(blocks * kMaxBlockBits / 8) + 2:
+// the longest codes of the four tables on every coefficient, every byte of it stuffed, plus EOI.  A caller that gives
+// less gets JPEG_ENC_SHORT for the frames that do not fit, and nothing is written for them.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "jpeg_host.h"
+
+namespace tstar {
+
+enum {
+    JPEG_ENC_OK = 0,
+    JPEG_ENC_SHORT = 1,          // the buffer's capacity is short of this frame: nothing of the frame was written
+    JPEG_ENC_BAD_COEF = 2,       // a coefficient outside what 8-bit baseline JPEG can code (scan stage fed foreign data)
+};
+
+// counters of the scan stage (optional out-array of the host entries)
+enum { JPEG_ENC_N_ZRL = 0, JPEG_ENC_N_NO_EOB = 1, JPEG_ENC_N_STUFFED = 2, JPEG_ENC_N_DUMMY_RIGHT = 3, JPEG_ENC_N_DUMMY_BOTTOM = 4, JPEG_ENC_N_COUNTERS = 5 };
+
+constexpr int kJpegEncHeaderBytes = 623;      // 2 + 18 + 2 * 69 + 19 + 2 * 33 + 2 * 183 + 14
+
+// what the encoder covers: 3 components, luma sampling 2x2 / 2x1 / 1x1, 1 <= W, H <= 16384 (JpegGeom::valid() is the DECODER's
+// coverage and is narrower: it leaves pictures with subsampled chroma at most 2 samples wide to Pillow)
+bool jpeg_enc_geom_ok(const JpegGeom& g);
+size_t jpeg_enc_max_scan_bytes(const JpegGeom& g);
+
+// Launch plan of the device encoder (jpeg_enc.hip), pure: no HIP call, no global state; integers in, integers out.  The
+// workspace of a chunk of n frames whose scans go into slots of slot_bytes bytes holds, 16-byte aligned one after another:
+//   meta  u32 [n][4]          bits of the scan, unstuffed bytes, 0xFF bytes among them, flags
+//   bits  u32 [n][blocks]     bit length of every block in scan order, then (scanned in place) its bit offset
+//   raw   u32 [n][raw_words]  the unstuffed stream, big-endian words; min(slot_bytes, the bound) bytes: unstuffed bytes never
+//                             exceed stuffed ones, so a frame that does not fit here does not fit its slot either
+//   ff    u32 [n][ff_chunks]  0xFF bytes per chunk of kJpegEncStuffChunk raw bytes, then (scanned in place) the count before it
+constexpr int kJpegEncStuffChunk = 64;
+struct JpegEncPlan {
+    const char* error;          // non-null: the launchers refuse these arguments
+    size_t blocks, coef_bytes, max_scan_bytes, header_bytes, workspace_bytes;
+    size_t raw_words, ff_chunks;                       // per frame
+    size_t off_meta, off_bits, off_raw, off_ff;        // byte offsets inside the workspace
+    unsigned block_wgs;         // block stage: workgroups of 32 blocks over all frames
+    unsigned entropy_wgs_x;     // entropy stage: workgroups of 256 blocks per frame (grid y = n)
+    unsigned stuff_wgs_x;       // stuffing passes: workgroups of 256 chunks per frame (grid y = n)
+};
+JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes);
+
+// quant u16 [3][64], natural order, rows Y / Cb / Cr (the decoder's table layout); quality 1..100
+void jpeg_enc_quant(int quality, uint16_t* quant);
+// the header of every frame of geometry g at this quality: exactly kJpegEncHeaderBytes bytes
+void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out);
+
+// stage 1, one frame: rgb u8 [H][W][3] -> coef int16 [g.blocks()][64]; dummy2 (optional) += {right-edge, bottom-edge} dummy blocks
+void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2);
+// stage 2, one frame: -> *len = the bytes the scan takes (with EOI), written to out only when they fit cap.  counters
+// (optional, JPEG_ENC_N_*) are added to, for frames that fit and frames that do not alike.
+int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, uint8_t* out, size_t cap, size_t* len, uint64_t* counters);
+
+}  // namespace tstar

@@ -1,0 +1,409 @@
+"""Baseline JPEG encode of resident frames: the bytes ``PIL.Image.fromarray(frame).save(buf, "JPEG", quality=q,
+subsampling=s)`` writes, for quality 1..100 and subsampling 4:2:0 / 4:2:2 / 4:4:4 (csrc/jpeg_enc.hip on the device,
+csrc/jpeg_enc_host.cpp on the host).
+
+The reference's exits are JPEG: ``encode_image_to_base64`` (TStar/utilites.py:15-37) for the grounding frames and the QA
+keyframes, ``.jpg`` files for the keyframes (TStarFramework.py:136-146).  Here the frames never leave HBM as pixels: the
+kernels turn them into scans, one read of the lengths per chunk brings the bytes over, the header (the same for every frame
+of a call) is joined on the host.  ``save_mjpeg`` writes a store as Motion-JPEG, which ``open_video`` reads back through
+the device decode path.
+"""
+from __future__ import annotations
+
+import base64
+import ctypes as C
+import os
+import struct
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+SUBSAMPLINGS = {"4:2:0": (2, 2), "4:2:2": (2, 1), "4:4:4": (1, 1)}
+_PIL_SUBSAMPLING = {0: "4:4:4", 1: "4:2:2", 2: "4:2:0"}
+STATUS_OK, STATUS_SHORT, STATUS_BAD_COEF = 0, 1, 2
+COUNTERS = ("zrl", "no_eob", "stuffed", "dummy_right", "dummy_bottom")
+AVI_LIMIT = 1 << 30            # a RIFF AVI of this size or more needs OpenDML index segments, which nobody here writes or reads
+
+
+def sampling(subsampling) -> tuple:
+    """"4:2:0" / "4:2:2" / "4:4:4" (or Pillow's 2 / 1 / 0) -> the luma sampling factors (hs, vs)."""
+    s = _PIL_SUBSAMPLING.get(subsampling, subsampling)
+    if s not in SUBSAMPLINGS:
+        raise ValueError(f"JPEG subsampling {subsampling!r}: expected one of {tuple(SUBSAMPLINGS)}")
+    return SUBSAMPLINGS[s]
+
+
+def _quality(quality) -> int:
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise ValueError(f"JPEG quality {quality!r}: expected 1..100")
+    return q
+
+
+class Plan:
+    """tstar_jpeg_encode_plan: sizes and launch shape for n frames of W x H whose scans go into slots of slot_bytes."""
+    FIELDS = ("blocks", "coef_bytes", "max_scan_bytes", "header_bytes", "workspace_bytes", "block_wgs", "entropy_wgs_x", "stuff_wgs_x")
+
+    def __init__(self, W: int, H: int, hs: int, vs: int, n: int = 1, slot_bytes: int = 2):
+        from . import _lib
+        out = (C.c_size_t * 8)()
+        _lib.check(_lib.load().tstar_jpeg_encode_plan(W, H, hs, vs, n, slot_bytes, out), "tstar_jpeg_encode_plan")
+        for k, v in zip(self.FIELDS, out):
+            setattr(self, k, int(v))
+
+
+def header(W: int, H: int, quality: int = 75, subsampling="4:2:0") -> bytes:
+    """SOI .. SOS as Pillow writes them from an array."""
+    from . import _lib
+    hs, vs = sampling(subsampling)
+    buf = np.empty(1024, dtype=np.uint8)
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().tstar_jpeg_encode_header(W, H, _quality(quality), hs, vs, buf.ctypes.data, buf.size, C.byref(n)),
+               "tstar_jpeg_encode_header")
+    return buf[:n.value].tobytes()
+
+
+def _host_array(frames) -> np.ndarray:
+    a = np.ascontiguousarray(frames)
+    if a.ndim == 3:
+        a = a[None]
+    if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3 or 0 in a.shape:
+        raise ValueError("encode_frames: expected uint8 frames [n,H,W,3] (or one [H,W,3])")
+    return a
+
+
+def blocks_host(frames, quality: int = 75, subsampling="4:2:0", idx: Optional[Sequence[int]] = None, threads: int = 0, counters=None):
+    """Block stage of the host twin -> (coef int16 [n, blocks * 64], quant uint16 [3, 64])."""
+    from . import _lib
+    a = _host_array(frames)
+    hs, vs = sampling(subsampling)
+    N, H, W, _ = a.shape
+    ii = np.ascontiguousarray(np.arange(N) if idx is None else idx, dtype=np.int32)
+    p = Plan(W, H, hs, vs, len(ii))
+    coef = np.empty((len(ii), p.blocks * 64), dtype=np.int16)
+    quant = np.empty((3, 64), dtype=np.uint16)
+    _lib.check(_lib.load().tstar_jpeg_encode_blocks_host(a.ctypes.data, N, H, W, ii.ctypes.data, len(ii), _quality(quality), hs, vs,
+                                                         coef.ctypes.data, quant.ctypes.data, threads, _counter_ptr(counters)),
+               "tstar_jpeg_encode_blocks_host")
+    return coef, quant
+
+
+def scan_host(coef: np.ndarray, W: int, H: int, subsampling="4:2:0", slot_bytes: Optional[int] = None, threads: int = 0, counters=None):
+    """Scan stage of the host twin: coef int16 [n, blocks * 64] -> (list of scans (None where the status is not 0), lengths, status)."""
+    from . import _lib
+    hs, vs = sampling(subsampling)
+    coef = np.ascontiguousarray(coef, dtype=np.int16)
+    n = coef.shape[0]
+    p = Plan(W, H, hs, vs, n)
+    assert coef.size == n * p.blocks * 64, "coefficients do not match the geometry"
+    slot = p.max_scan_bytes if slot_bytes is None else int(slot_bytes)
+    out = np.empty((n, slot), dtype=np.uint8)
+    lengths = np.zeros(n, dtype=np.uint32)
+    status = np.full(n, -1, dtype=np.int32)
+    _lib.check(_lib.load().tstar_jpeg_encode_scan_host(coef.ctypes.data, n, W, H, hs, vs, out.ctypes.data, slot, lengths.ctypes.data,
+                                                       status.ctypes.data, threads, _counter_ptr(counters)), "tstar_jpeg_encode_scan_host")
+    return [out[i, :lengths[i]].tobytes() if status[i] == 0 else None for i in range(n)], lengths, status
+
+
+def _counter_ptr(counters):
+    if counters is None:
+        return None
+    assert isinstance(counters, np.ndarray) and counters.dtype == np.uint64 and counters.size == len(COUNTERS)
+    return counters.ctypes.data
+
+
+def encode_host(frames, quality: int = 75, subsampling="4:2:0", idx: Optional[Sequence[int]] = None, slot_bytes: Optional[int] = None,
+                threads: int = 0, counters=None, out: Optional[np.ndarray] = None):
+    """Whole files from the host twin -> (out uint8 [n, slot_bytes], lengths, status).  ``slot_bytes`` defaults to what holds any
+    file of the geometry; ``out`` may be a caller's buffer of at least n * slot_bytes bytes (the capacity tests pass one)."""
+    from . import _lib
+    a = _host_array(frames)
+    hs, vs = sampling(subsampling)
+    N, H, W, _ = a.shape
+    ii = np.ascontiguousarray(np.arange(N) if idx is None else idx, dtype=np.int32)
+    n = len(ii)
+    p = Plan(W, H, hs, vs, n)
+    slot = p.header_bytes + p.max_scan_bytes if slot_bytes is None else int(slot_bytes)
+    if out is None:
+        out = np.empty((n, slot), dtype=np.uint8)
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= n * slot
+    lengths = np.zeros(n, dtype=np.uint32)
+    status = np.full(n, -1, dtype=np.int32)
+    _lib.check(_lib.load().tstar_jpeg_encode_host(a.ctypes.data, N, H, W, ii.ctypes.data, n, _quality(quality), hs, vs, out.ctypes.data,
+                                                  slot, lengths.ctypes.data, status.ctypes.data, threads, _counter_ptr(counters)),
+               "tstar_jpeg_encode_host")
+    return out, lengths, status
+
+
+def _typical_slot(W: int, H: int, p: Plan) -> int:
+    """Slot of the first device pass: 3/4 byte per pixel (a quality-75 photograph takes a third of that), at least 4 KiB, never
+    more than what holds any scan.  Frames that do not fit are encoded again into slots of the bound."""
+    return min(p.max_scan_bytes, max(4096, (W * H * 3 // 4 + 15) // 16 * 16))
+
+
+class DeviceEncoder:
+    """Buffers and launches of the device path for frames of one geometry, reused chunk after chunk."""
+
+    def __init__(self, W: int, H: int, quality: int, subsampling, chunk: int, slot_bytes: Optional[int] = None, device=None):
+        import torch
+        self.W, self.H, self.quality = W, H, _quality(quality)
+        self.hs, self.vs = sampling(subsampling)
+        self.chunk = int(chunk)
+        one = Plan(W, H, self.hs, self.vs, 1)
+        self.slot = int(slot_bytes) if slot_bytes else _typical_slot(W, H, one)
+        self.plan = Plan(W, H, self.hs, self.vs, self.chunk, self.slot)
+        self.max_scan_bytes = one.max_scan_bytes
+        self.device = device
+        u8 = dict(dtype=torch.uint8, device=device)
+        self.coef = torch.empty(self.chunk * self.plan.coef_bytes, **u8)
+        self.work = torch.empty(self.plan.workspace_bytes, **u8)
+        self.out = torch.empty((self.chunk, self.slot), **u8)
+        self.meta = torch.empty((2, self.chunk), dtype=torch.int32, device=device)      # lengths (u32 bits), status
+        self.block_ms = self.entropy_ms = 0.0
+        self.timed = False
+
+    def launch(self, frames, idx) -> None:
+        """Both stages for frames[idx] (idx: int32 device tensor, at most ``chunk`` long); nothing is read back."""
+        import torch
+        from . import _lib
+        lib = _lib.load()
+        n = int(idx.numel())
+        N = int(frames.shape[0])
+        s = _lib.stream_ptr()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if self.timed else None
+        if ev:
+            ev[0].record()
+        _lib.check(lib.tstar_jpeg_encode_blocks(frames.data_ptr(), N, self.H, self.W, idx.data_ptr(), n, self.quality, self.hs, self.vs,
+                                                self.coef.data_ptr(), None, s), "tstar_jpeg_encode_blocks")
+        if ev:
+            ev[1].record()
+        _lib.check(lib.tstar_jpeg_encode_scan(self.coef.data_ptr(), n, self.W, self.H, self.hs, self.vs, self.out.data_ptr(), self.slot,
+                                              self.meta[0].data_ptr(), self.meta[1].data_ptr(), self.work.data_ptr(), self.work.numel(), s),
+                   "tstar_jpeg_encode_scan")
+        if ev:
+            ev[2].record()
+            ev[2].synchronize()
+            self.block_ms += ev[0].elapsed_time(ev[1])
+            self.entropy_ms += ev[1].elapsed_time(ev[2])
+
+    def collect(self, n: int):
+        """ONE device -> host read of lengths and status, then the used bytes of the slots in one copy -> (list of scans (None where
+        the slot was short), status)."""
+        import torch
+        meta = self.meta[:, :n].cpu().numpy()
+        lengths, status = meta[0].view(np.uint32).astype(np.int64), meta[1]
+        if (status == STATUS_BAD_COEF).any():
+            raise ValueError("JPEG encode: a coefficient outside 8-bit baseline JPEG")
+        take = np.where(status == STATUS_OK, lengths, 0)
+        cols = torch.arange(self.slot, device=self.out.device)[None, :]
+        used = self.out[:n][cols < torch.as_tensor(take, device=self.out.device)[:, None]].cpu().numpy()
+        ends = np.cumsum(take)
+        return [used[e - t:e].tobytes() if st == STATUS_OK else None for e, t, st in zip(ends, take, status)], status
+
+
+def encode_chunk_size(blocks: int, n_frames: int, chunk: Optional[int] = None) -> int:
+    """Frames per chunk: the coefficient buffer's budget and frame limit of the decoder's device entropy path."""
+    from . import jpeg
+    return jpeg.device_entropy_chunk(blocks, n_frames, chunk)
+
+
+def _encode_device(frames, idx, quality, subsampling, chunk=None, slot_bytes=None, stats=None) -> List[bytes]:
+    """frames: cuda uint8 [N,H,W,3]; idx: int32 cuda tensor of frame numbers -> the JPEG files."""
+    import torch
+    N, H, W, _ = (int(v) for v in frames.shape)
+    hs, vs = sampling(subsampling)
+    n = int(idx.numel())
+    if n == 0:
+        return []
+    head = header(W, H, quality, subsampling)
+    one = Plan(W, H, hs, vs, 1)
+    with torch.cuda.device(frames.device):
+        enc = DeviceEncoder(W, H, quality, subsampling, encode_chunk_size(one.blocks, n, chunk), slot_bytes, frames.device)
+        enc.timed = stats is not None
+        out: List[Optional[bytes]] = []
+        short: List[int] = []
+        for s0 in range(0, n, enc.chunk):
+            part = idx[s0:s0 + enc.chunk]
+            enc.launch(frames, part)
+            scans, status = enc.collect(int(part.numel()))
+            short += [s0 + int(i) for i in np.nonzero(status == STATUS_SHORT)[0]]
+            out += scans
+        if stats is not None:
+            stats["block_ms"] = stats.get("block_ms", 0.0) + enc.block_ms
+            stats["entropy_ms"] = stats.get("entropy_ms", 0.0) + enc.entropy_ms
+            stats["retried"] = stats.get("retried", 0) + len(short)
+        if short:
+            if enc.slot >= enc.max_scan_bytes:
+                raise RuntimeError("JPEG encode: a scan did not fit the bound of its geometry")
+            del enc
+            # frames the typical slot was short of: once more into slots that hold any scan, a few at a time
+            step = max(1, min(len(short), (256 << 20) // one.max_scan_bytes))
+            big = DeviceEncoder(W, H, quality, subsampling, step, one.max_scan_bytes, frames.device)
+            for s0 in range(0, len(short), step):
+                ids = short[s0:s0 + step]
+                big.launch(frames, idx[torch.as_tensor(ids, device=idx.device, dtype=torch.long)])
+                scans, status = big.collect(len(ids))
+                if (status != STATUS_OK).any():
+                    raise RuntimeError("JPEG encode: a scan did not fit the bound of its geometry")
+                for i, sc in zip(ids, scans):
+                    out[i] = sc
+    return [head + sc for sc in out]
+
+
+def encode_frames(frames, quality: int = 75, subsampling="4:2:0", device: bool = True, chunk: Optional[int] = None,
+                  slot_bytes: Optional[int] = None, stats: Optional[dict] = None, threads: int = 0) -> List[bytes]:
+    """One JPEG file per frame, byte for byte Pillow's ``Image.fromarray(frame).save(buf, "JPEG", quality=, subsampling=)``.
+
+    ``frames``: a cuda uint8 tensor [n,H,W,3], or ``(store, secs)`` -- a FrameStore (RGB or NV12) and the logical seconds wanted,
+    read straight from the store through the index list.  ``device=False``: the host twin on a numpy array [n,H,W,3] (the
+    fallback a caller without a device can choose; there is no silent one).  ``chunk`` / ``slot_bytes`` override the device
+    path's frames per chunk and per-frame scan capacity (frames a slot is short of are encoded again at the bound)."""
+    quality = _quality(quality)
+    sampling(subsampling)
+    if isinstance(frames, tuple) and len(frames) == 2 and hasattr(frames[0], "fmt"):
+        store, secs = frames
+        if not device:
+            return encode_frames(store.host_frames(secs), quality, subsampling, device=False, threads=threads)
+        return _encode_store(store, secs, quality, subsampling, chunk, slot_bytes, stats)
+    if not device:
+        a = _host_array(frames)
+        out, lengths, status = encode_host(a, quality, subsampling, threads=threads)
+        if (status != STATUS_OK).any():
+            raise RuntimeError(f"JPEG encode (host): status {status.tolist()}")
+        return [out[i, :lengths[i]].tobytes() for i in range(len(a))]
+    import torch
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4
+            and frames.shape[3] == 3):
+        raise ValueError("encode_frames: expected a cuda uint8 tensor [n,H,W,3] or (store, secs); pass device=False for numpy frames")
+    if 0 in frames.shape[1:]:
+        raise ValueError("encode_frames: empty frames")
+    frames = frames.contiguous()
+    idx = torch.arange(frames.shape[0], dtype=torch.int32, device=frames.device)
+    return _encode_device(frames, idx, quality, subsampling, chunk, slot_bytes, stats)
+
+
+def _encode_store(store, secs, quality, subsampling, chunk, slot_bytes, stats) -> List[bytes]:
+    import torch
+    from . import _lib
+    N, H, W, _ = store.shape
+    secs = [int(s) for s in secs]
+    for s in secs:
+        if not 0 <= s < N:
+            raise IndexError(f"second {s} outside the store's 0..{N - 1}")
+    dev = store.frames.device
+    idx = torch.as_tensor(secs, dtype=torch.int32, device=dev)
+    if store.fmt == "rgb":
+        return _encode_device(store.frames, idx, quality, subsampling, chunk, slot_bytes, stats)
+    # NV12: converted chunk by chunk with the kernel host_frames uses, so the bytes are Pillow's encode of host_frames(secs)
+    out: List[bytes] = []
+    step = max(1, min(len(secs), 256, (256 << 20) // (H * W * 3)))
+    with torch.cuda.device(dev):
+        rgb = torch.empty((step, H, W, 3), dtype=torch.uint8, device=dev)
+        for s0 in range(0, len(secs), step):
+            part = idx[s0:s0 + step]
+            m = int(part.numel())
+            _lib.check(_lib.load().tstar_nv12_to_rgb(store.frames.data_ptr(), N, H, W, part.data_ptr(), m, rgb.data_ptr(),
+                                                      _lib.stream_ptr()), "tstar_nv12_to_rgb")
+            out += _encode_device(rgb, torch.arange(m, dtype=torch.int32, device=dev), quality, subsampling, chunk, slot_bytes, stats)
+    return out
+
+
+def frames_to_base64(store, secs=None, quality: int = 75, subsampling="4:2:0") -> List[str]:
+    """The reference's ``encode_image_to_base64`` (TStar/utilites.py:15-37: Pillow's default JPEG, base64, utf-8) for frames that
+    never left HBM as pixels.  ``store``: a FrameStore with ``secs``, or frames as ``encode_frames`` takes them (a numpy array
+    goes through the host twin)."""
+    if secs is not None:
+        files = encode_frames((store, secs), quality, subsampling)
+    elif isinstance(store, np.ndarray):
+        files = encode_frames(store, quality, subsampling, device=False)
+    else:
+        files = encode_frames(store, quality, subsampling)
+    return [base64.b64encode(f).decode("utf-8") for f in files]
+
+
+# ------------------------------------------------------------------------------------------------ containers
+def avi_bytes(frame_lengths: Sequence[int]) -> int:
+    """Size of the RIFF AVI ``write_avi`` makes of frames of these lengths (no file is written)."""
+    movi = 4 + sum(8 + n + (n & 1) for n in frame_lengths)
+    return 12 + (8 + _HDRL_BYTES) + (8 + movi) + (8 + 16 * len(frame_lengths))
+
+
+_HDRL_BYTES = 4 + (8 + 56) + (8 + 4 + (8 + 56) + (8 + 40))
+
+
+def check_avi_size(frame_lengths: Sequence[int], path: str = "") -> int:
+    total = avi_bytes(frame_lengths)
+    if total >= AVI_LIMIT:
+        raise ValueError(f"save_mjpeg: {path or 'the file'} would take {total} bytes; a RIFF AVI of 1 GiB or more needs OpenDML "
+                         "segments, which are not written (nor read) here: save it as .mjpeg instead")
+    return total
+
+
+def _fps_fraction(fps: float):
+    from fractions import Fraction
+    fr = Fraction(float(fps)).limit_denominator(1_000_000)
+    if fr <= 0 or fr.numerator >= 1 << 31:
+        raise ValueError(f"save_mjpeg: frame rate {fps!r} cannot be written")
+    return fr.numerator, fr.denominator            # dwRate, dwScale
+
+
+def write_avi(path: str, files: Sequence[bytes], W: int, H: int, fps: float = 1.0) -> None:
+    """A RIFF AVI with one ``MJPG`` video stream: ``hdrl`` (``avih``, ``strl`` = ``strh`` + ``strf``), ``movi`` with one ``00dc``
+    chunk per frame, ``idx1`` -- what ``jpeg.avi_mjpeg`` parses."""
+    lens = [len(f) for f in files]
+    total = check_avi_size(lens, path)
+    n = len(files)
+    rate, scale = _fps_fraction(fps)
+    biggest = max(lens) if lens else 0
+    avih = struct.pack("<14I", int(round(1e6 * scale / rate)), 0, 0, 0x10, n, 0, 1, biggest, W, H, 0, 0, 0, 0)       # AVIF_HASINDEX
+    strh = struct.pack("<4s4sIHHIIIIIIII4H", b"vids", b"MJPG", 0, 0, 0, 0, scale, rate, 0, n, biggest, 0xFFFFFFFF, 0, 0, 0, W, H)
+    strf = struct.pack("<IiiHH4sIiiII", 40, W, H, 1, 24, b"MJPG", W * H * 3, 0, 0, 0, 0)
+    strl = b"LIST" + struct.pack("<I", 4 + 8 + len(strh) + 8 + len(strf)) + b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh \
+        + b"strf" + struct.pack("<I", len(strf)) + strf
+    hdrl = b"hdrl" + b"avih" + struct.pack("<I", len(avih)) + avih + strl
+    assert len(hdrl) == _HDRL_BYTES, len(hdrl)
+    movi_size = 4 + sum(8 + m + (m & 1) for m in lens)
+    with open(path, "wb") as f:
+        f.write(b"RIFF" + struct.pack("<I", total - 8) + b"AVI ")
+        f.write(b"LIST" + struct.pack("<I", len(hdrl)) + hdrl)
+        f.write(b"LIST" + struct.pack("<I", movi_size) + b"movi")
+        index, off = [], 4                                         # idx1 offsets count from the 'movi' fourcc
+        for data in files:
+            f.write(b"00dc" + struct.pack("<I", len(data)) + data + (b"\x00" if len(data) & 1 else b""))
+            index.append(struct.pack("<4sIII", b"00dc", 0x10, off, len(data)))                          # AVIIF_KEYFRAME
+            off += 8 + len(data) + (len(data) & 1)
+        f.write(b"idx1" + struct.pack("<I", 16 * n) + b"".join(index))
+
+
+def write_mjpeg_file(path: str, files: Sequence[bytes], W: int, H: int, fps: float = 1.0) -> None:
+    """``.avi`` -> ``write_avi``; ``.mjpeg`` / ``.mjpg`` -> the frames one after another (``jpeg.mjpeg_stream`` reads them; such a
+    stream carries no frame rate)."""
+    low = os.fspath(path).lower()
+    if not files:
+        raise ValueError("save_mjpeg: no frames")
+    if low.endswith(".avi"):
+        write_avi(path, files, W, H, fps)
+    elif low.endswith((".mjpeg", ".mjpg")):
+        with open(path, "wb") as f:
+            for data in files:
+                f.write(data)
+    else:
+        raise ValueError(f"save_mjpeg: {path}: expected .avi, .mjpeg or .mjpg")
+
+
+def save_mjpeg(store, path: str, quality: int = 90, subsampling="4:2:0", fps: Optional[float] = None, device: bool = True,
+               piece: int = 1024) -> int:
+    """Write a FrameStore (or, with ``device=False``, a numpy array [n,H,W,3]) as Motion-JPEG at its LOGICAL rate (1 frame per
+    second unless ``fps`` is given), so that ``open_video(path)`` gives back a store of the same seconds.  Returns the frames
+    written."""
+    if hasattr(store, "fmt"):
+        N, H, W, _ = store.shape
+        files: List[bytes] = []
+        for s0 in range(0, N, piece):
+            files += encode_frames((store, range(s0, min(N, s0 + piece))), quality, subsampling, device=device)
+    else:
+        a = _host_array(store)
+        N, H, W, _ = a.shape
+        files = encode_frames(a, quality, subsampling, device=False) if not device else encode_frames(store, quality, subsampling)
+    write_mjpeg_file(path, files, W, H, 1.0 if fps is None else float(fps))
+    return len(files)

@@ -112,6 +112,19 @@ class FrameStore:
         ii = torch.as_tensor([int(i) for i in secs], dtype=torch.long, device=self.frames.device)
         return self.frames.index_select(0, ii).cpu().numpy()
 
+    def jpeg_frames(self, secs, quality: int = 75, subsampling: str = "4:2:0"):
+        """The given logical seconds as JPEG files (list of bytes), encoded on the device straight from the store: byte for
+        byte Pillow's ``Image.fromarray(frame).save(buf, "JPEG", quality=, subsampling=)`` of ``host_frames(secs)``."""
+        from . import jpeg_encode
+        return jpeg_encode.encode_frames((self, secs), quality, subsampling)
+
+    def save_mjpeg(self, path: str, quality: int = 90, subsampling: str = "4:2:0", fps: Optional[float] = None) -> int:
+        """Write the store as Motion-JPEG (.avi: RIFF with one MJPG stream; .mjpeg / .mjpg: concatenated frames) at its logical
+        rate, 1 frame per second unless ``fps`` is given, so that ``open_video(path)`` returns a store of the same seconds.  A
+        file that would need OpenDML (1 GiB and above) is refused with a ValueError that names .mjpeg as the way out."""
+        from . import jpeg_encode
+        return jpeg_encode.save_mjpeg(self, path, quality, subsampling, fps)
+
 
 def synthetic_video(n_frames: int = 3600, H: int = 360, W: int = 640, seed: int = 0, raw_fps: float = 1.0,
                     device: str = "cuda", chunk: int = 256) -> FrameStore:
