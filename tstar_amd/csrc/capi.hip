@@ -200,28 +200,15 @@ int tstar_gemm_f32_cfg(const float* d_A, const float* d_W, float* d_C, const flo
     return gemm_f32(g, (hipStream_t)stream);
 }
 
-static int gemm_converted(const char* fn, int a_terms, const float* d_A, const float* d_W, float* d_C, const float* d_bias,
-                          const float* d_residual, int M, int N, int K, int act, int tile_cfg, void* stream) {
+// The converting diagnostics: the planes of `wmode` built for this one launch (a Wq plane wherever the shape allows), the launch,
+// and a wait for it; the planes are freed by scope, after the wait.  g: the launch on the f32 matrix; fn: the entry's name.
+static int gemm_on_built_planes(const char* fn, GemmArgs g, int wmode, int tile_cfg, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    __bf16* wb = nullptr;
-    TSTAR_HIP_CHECK(hipMalloc(&wb, (size_t)N * K * sizeof(__bf16)));
-    int rc = convert_f32_to_bf16(d_W, wb, nullptr, (size_t)N * K, s);
-    void* wq = nullptr;
-    if (!rc && a_terms == 2 && N % 256 == 0 && K % 32 == 0) {       // the fragment-packed plane of the two-term mode's VGPR-weight tile (tile_cfg 6, or N = 768)
-        TSTAR_HIP_CHECK(hipMalloc(&wq, (size_t)N * K * sizeof(__bf16)));
-        rc = pack_weights_w2(wb, wq, N, K, s);
-    }
-    if (!rc) {
-        GemmArgs g = gemm_args(d_A, d_W, d_C, d_bias, d_residual, M, N, K, K, N, act);
-        g.Wb = wb;
-        g.Wq = wq;
-        g.a_terms = a_terms;
-        g.tile_cfg = tile_cfg;
-        rc = gemm_f32(g, s);
-    }
-    hipError_t e = hipStreamSynchronize(s);
-    (void)hipFree(wb);
-    if (wq) (void)hipFree(wq);
+    g.tile_cfg = tile_cfg;
+    WeightPlanes planes;
+    int rc = build_weight_planes(g.W, g.N, g.K, wmode, true, s, &planes);
+    if (!rc) rc = gemm_f32(with_planes(g, planes), s);
+    const hipError_t e = hipStreamSynchronize(s);
     if (!rc && e != hipSuccess) { set_error(std::string(fn) + ": " + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
     return rc;
 }
@@ -229,7 +216,7 @@ static int gemm_converted(const char* fn, int a_terms, const float* d_A, const f
 int tstar_gemm_bf16w(const float* d_A, const float* d_W, float* d_C, const float* d_bias, const float* d_residual, int M,
                      int N, int K, int act, int tile_cfg, void* stream) {
     TSTAR_REQUIRE(d_A && d_W && d_C, "tstar_gemm_bf16w: null argument");
-    return gemm_converted("tstar_gemm_bf16w", 0, d_A, d_W, d_C, d_bias, d_residual, M, N, K, act, tile_cfg, stream);
+    return gemm_on_built_planes("tstar_gemm_bf16w", gemm_args(d_A, d_W, d_C, d_bias, d_residual, M, N, K, K, N, act), GEMM_W_BF16_EXACT, tile_cfg, stream);
 }
 
 int tstar_gemm_bf16w_pre(const float* d_A, const void* d_Wb, float* d_C, const float* d_bias, const float* d_residual, int M, int N,
@@ -237,8 +224,8 @@ int tstar_gemm_bf16w_pre(const float* d_A, const void* d_Wb, float* d_C, const f
     TSTAR_REQUIRE(d_A && d_Wb && d_C, "tstar_gemm_bf16w_pre: null argument");
     TSTAR_REQUIRE(a_terms == 2 || a_terms == 3, "tstar_gemm_bf16w_pre: a_terms must be 2 or 3");
     GemmArgs g = gemm_args(d_A, reinterpret_cast<const float*>(d_Wb), d_C, d_bias, d_residual, M, N, K, K, N, act);
-    g.Wb = static_cast<const __bf16*>(d_Wb);
-    g.a_terms = a_terms;
+    g.Wb = static_cast<const __bf16*>(d_Wb);                 // the caller's plane
+    g.wmode = a_terms == 2 ? GEMM_W_BF16_2T : GEMM_W_BF16_EXACT;
     g.tile_cfg = tile_cfg;
     return gemm_f32(g, (hipStream_t)stream);
 }
@@ -246,27 +233,14 @@ int tstar_gemm_bf16w_pre(const float* d_A, const void* d_Wb, float* d_C, const f
 int tstar_gemm_bf16w2(const float* d_A, const float* d_W, float* d_C, const float* d_bias, const float* d_residual, int M,
                       int N, int K, int act, int tile_cfg, void* stream) {
     TSTAR_REQUIRE(d_A && d_W && d_C, "tstar_gemm_bf16w2: null argument");
-    return gemm_converted("tstar_gemm_bf16w2", 2, d_A, d_W, d_C, d_bias, d_residual, M, N, K, act, tile_cfg, stream);
+    return gemm_on_built_planes("tstar_gemm_bf16w2", gemm_args(d_A, d_W, d_C, d_bias, d_residual, M, N, K, K, N, act), GEMM_W_BF16_2T, tile_cfg, stream);
 }
 
 int tstar_gemm_f32x3(const float* d_A, const float* d_W, float* d_C, const float* d_bias, const float* d_residual, int M,
                      int N, int K, int act, int tile_cfg, void* stream) {
     TSTAR_REQUIRE(d_A && d_W && d_C, "tstar_gemm_f32x3: null argument");
     TSTAR_REQUIRE(M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 32 == 0, "tstar_gemm_f32x3: N must be a multiple of 128, K of 32 (include/tstar_hip.h)");
-    hipStream_t s = (hipStream_t)stream;
-    void* wp = nullptr;
-    TSTAR_HIP_CHECK(hipMalloc(&wp, (size_t)N * K * 6));
-    int rc = pack_weights_x3(d_W, wp, N, K, s);
-    if (!rc) {
-        GemmArgs g = gemm_args(d_A, d_W, d_C, d_bias, d_residual, M, N, K, K, N, act);
-        g.Wp = wp;
-        g.tile_cfg = tile_cfg;
-        rc = gemm_f32(g, s);
-    }
-    hipError_t e = hipStreamSynchronize(s);
-    (void)hipFree(wp);
-    if (!rc && e != hipSuccess) { set_error(std::string("tstar_gemm_f32x3: ") + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
-    return rc;
+    return gemm_on_built_planes("tstar_gemm_f32x3", gemm_args(d_A, d_W, d_C, d_bias, d_residual, M, N, K, K, N, act), GEMM_W_F32X3, tile_cfg, stream);
 }
 
 int tstar_pack_f32x3(const float* d_W, void* d_Wp, int N, int K, void* stream) {
@@ -280,14 +254,10 @@ int tstar_gemm_f32x3_pre(const float* d_A, const void* d_Wp, float* d_C, const f
     TSTAR_REQUIRE(d_A && d_Wp && d_C, "tstar_gemm_f32x3_pre: null argument");
     TSTAR_REQUIRE(M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 32 == 0, "tstar_gemm_f32x3_pre: N must be a multiple of 128, K of 32 (include/tstar_hip.h)");
     GemmArgs g = gemm_args(d_A, reinterpret_cast<const float*>(d_Wp), d_C, d_bias, d_residual, M, N, K, K, N, act);
-    g.Wp = d_Wp;
+    g.Wp = d_Wp;                                             // the caller's planes (tstar_pack_f32x3)
+    g.wmode = GEMM_W_F32X3;
     g.tile_cfg = tile_cfg;
     return gemm_f32(g, (hipStream_t)stream);
-}
-
-static int gemm_wmode_of(int weights_mode) {
-    return weights_mode == TSTAR_WEIGHTS_F32 ? GEMM_W_F32 : weights_mode == TSTAR_WEIGHTS_BF16 ? GEMM_W_BF16_2T :
-           weights_mode == TSTAR_WEIGHTS_BF16_EXACT ? GEMM_W_BF16_EXACT : weights_mode == TSTAR_WEIGHTS_F32X3 ? GEMM_W_F32X3 : -1;
 }
 
 int tstar_gemm_plan(int weights_mode, int M, int N, int ldc, int patch_np, int tile_cfg, int has_packed_w2, int* plan4) {
@@ -309,39 +279,12 @@ int tstar_gemm_patch_embed(const float* d_A, const float* d_W, float* d_X, const
     TSTAR_REQUIRE(wmode >= 0, "tstar_gemm_patch_embed: unknown weights_mode (a TSTAR_WEIGHTS_* value)");
     TSTAR_REQUIRE(N > 0 && K > 0 && K % 32 == 0, "tstar_gemm_patch_embed: K must be a positive multiple of 32 (gemm_f32)");
     const int M = B * np;
-    const bool two_term = weights_mode == TSTAR_WEIGHTS_BF16;
-    const bool has_wq = two_term && N % 256 == 0;             // the fragment-packed plane, where gemm_converted makes one
+    const bool has_wq = wmode == GEMM_W_BF16_2T && w2_plane_shape_ok(N, K);     // what gemm_on_built_planes will hand the launch
     const GemmPlan p = plan_gemm(wmode, M, N, N, np, tile_cfg, has_wq);
     if (p.error) { set_error(std::string("tstar_gemm_patch_embed: ") + p.error); return TSTAR_ERR_ARG; }
-    hipStream_t s = (hipStream_t)stream;
-    __bf16* wb = nullptr;
-    void *wq = nullptr, *wp = nullptr;
-    int rc = TSTAR_OK;
-    if (two_term || weights_mode == TSTAR_WEIGHTS_BF16_EXACT) {
-        TSTAR_HIP_CHECK(hipMalloc(&wb, (size_t)N * K * sizeof(__bf16)));
-        rc = convert_f32_to_bf16(d_W, wb, nullptr, (size_t)N * K, s);
-        if (!rc && has_wq) {
-            TSTAR_HIP_CHECK(hipMalloc(&wq, (size_t)N * K * sizeof(__bf16)));
-            rc = pack_weights_w2(wb, wq, N, K, s);
-        }
-    } else if (weights_mode == TSTAR_WEIGHTS_F32X3) {
-        TSTAR_HIP_CHECK(hipMalloc(&wp, (size_t)N * K * 6));
-        rc = pack_weights_x3(d_W, wp, N, K, s);
-    }
-    if (!rc) {
-        GemmArgs g = gemm_args(d_A, d_W, d_X, nullptr, nullptr, M, N, K, K, N, ACT_NONE);
-        g.Wb = wb; g.Wq = wq; g.Wp = wp;
-        g.a_terms = two_term ? 2 : wb ? 3 : 0;
-        g.pos = d_pos; g.patch_np = np;
-        g.tile_cfg = tile_cfg;
-        rc = gemm_f32(g, s);
-    }
-    hipError_t e = hipStreamSynchronize(s);
-    if (wb) (void)hipFree(wb);
-    if (wq) (void)hipFree(wq);
-    if (wp) (void)hipFree(wp);
-    if (!rc && e != hipSuccess) { set_error(std::string("tstar_gemm_patch_embed: ") + hipGetErrorString(e)); rc = TSTAR_ERR_HIP; }
-    return rc;
+    GemmArgs g = gemm_args(d_A, d_W, d_X, nullptr, nullptr, M, N, K, K, N, ACT_NONE);
+    g.pos = d_pos; g.patch_np = np;
+    return gemm_on_built_planes("tstar_gemm_patch_embed", g, wmode, tile_cfg, stream);
 }
 
 int tstar_ingest_plan(int op, int nv12, int H, int W, int n, int ow, int oh, int out_aligned4, int video_aligned4, int generic, int nv12_lds,

@@ -260,8 +260,8 @@ __device__ __forceinline__ void split4_bf16x2(const f32x4 v, u32x2 (&out)[2]) {
 template <class CF, int WMODE, int ACT, bool HAS_BIAS, bool HAS_RES, bool PATCH>
 __device__ __forceinline__ void gemm_tile_bf16w(const GemmArgs& g, const int m0, const int n0, float* smem_f) {
     constexpr int TM = CF::TM, TN = CF::TN, BM = CF::BM, BN = CF::BN;
-    constexpr int NAT = WMODE == 1 ? 3 : 2, NWT = 1;                      // operand terms
-    constexpr int NPROD = WMODE == 3 ? 2 : 3;                             // MFMA products per algorithmic product
+    constexpr int NAT = WMODE == GEMM_W_BF16_EXACT ? 3 : 2, NWT = 1;                      // operand terms
+    constexpr int NPROD = WMODE == GEMM_W_BF16_2T ? 2 : 3;                             // MFMA products per algorithmic product
     constexpr int DEPTH = TN >= 4 ? 1 : 2;                                // register prefetch depth in K tiles
     constexpr int A_T = BM * 64, W_T = BN * 64, BUF = NAT * A_T + NWT * W_T;       // bytes
     char* smem = reinterpret_cast<char*>(smem_f);
@@ -311,7 +311,7 @@ __device__ __forceinline__ void gemm_tile_bf16w(const GemmArgs& g, const int m0,
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             u32x2 sp[NAT];
-            if constexpr (WMODE == 1) split4_bf16x3(ra[st][i], sp);
+            if constexpr (WMODE == GEMM_W_BF16_EXACT) split4_bf16x3(ra[st][i], sp);
             else split4_bf16x2(ra[st][i], sp);
             const int off = bfw_off(r0 + 32 * i, c4 >> 1) + (c4 & 1) * 8;
 #pragma unroll
@@ -887,6 +887,27 @@ int pack_weights_w2(const __bf16* Wb, void* Wq, int N, int K, hipStream_t s) {
     return TSTAR_OK;
 }
 
+int build_weight_planes(const float* d_W, int N, int K, int wmode, bool want_w2_packed, hipStream_t s, WeightPlanes* out) {
+    *out = WeightPlanes();
+    TSTAR_REQUIRE(wmode == GEMM_W_F32 || wmode == GEMM_W_BF16_EXACT || wmode == GEMM_W_BF16_2T || wmode == GEMM_W_F32X3, "build_weight_planes: unknown weight mode");
+    WeightPlanes p;                                          // every early return below frees what it holds
+    p.wmode = wmode; p.N = N; p.K = K;
+    const size_t n = (size_t)N * K;
+    if (wmode == GEMM_W_F32X3) {
+        TSTAR_HIP_CHECK(hipMalloc(&p.Wp, n * 6));
+        RC(pack_weights_x3(d_W, p.Wp, N, K, s));
+    } else if (wmode != GEMM_W_F32) {
+        TSTAR_HIP_CHECK(hipMalloc(&p.Wb, n * sizeof(__bf16)));
+        RC(convert_f32_to_bf16(d_W, p.Wb, nullptr, n, s));
+        if (wmode == GEMM_W_BF16_2T && want_w2_packed && w2_plane_shape_ok(N, K)) {
+            TSTAR_HIP_CHECK(hipMalloc(&p.Wq, n * sizeof(__bf16)));
+            RC(pack_weights_w2(p.Wb, p.Wq, N, K, s));
+        }
+    }
+    *out = std::move(p);
+    return TSTAR_OK;
+}
+
 // One output tile of shape CF at (m0, n0).  `smem` is the block's dynamic LDS.
 template <class CF, int ACT, bool HAS_BIAS, bool HAS_RES, bool PATCH>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int m0, const int n0, float* smem) {
@@ -986,8 +1007,8 @@ __global__ __launch_bounds__(256, CF::MINW) void gemm_f32_kernel(GemmArgs g) {
     const int tile = xcd_remap(blockIdx.x, mt * nt);
     int mi, ni;
     tile_mn(tile, mt, nt, g.group_m, mi, ni);
-    if constexpr (WMODE == 4) gemm_tile_x3<CF, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * CF::BM, ni * CF::BN, smem);
-    else if constexpr (WMODE != 0) gemm_tile_bf16w<CF, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * CF::BM, ni * CF::BN, smem);
+    if constexpr (WMODE == GEMM_W_F32X3) gemm_tile_x3<CF, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * CF::BM, ni * CF::BN, smem);
+    else if constexpr (WMODE != GEMM_W_F32) gemm_tile_bf16w<CF, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * CF::BM, ni * CF::BN, smem);
     else gemm_tile<CF, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * CF::BM, ni * CF::BN, smem);
 }
 
@@ -1003,16 +1024,16 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_hybrid_kernel(GemmArgs g) {
         const int tile = xcd_remap(blockIdx.x, n_big);
         int mi, ni;
         tile_mn(tile, g.m_split / 128, nt, g.group_m, mi, ni);
-        if constexpr (WMODE == 4) gemm_tile_x3<Cfg128, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 128, smem);
-        else if constexpr (WMODE != 0) gemm_tile_bf16w<Cfg128, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 128, smem);
+        if constexpr (WMODE == GEMM_W_F32X3) gemm_tile_x3<Cfg128, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 128, smem);
+        else if constexpr (WMODE != GEMM_W_F32) gemm_tile_bf16w<Cfg128, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 128, smem);
         else gemm_tile<Cfg128, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 128, smem);
     } else {
         const int n_small = gridDim.x - n_big;
         const int tile = xcd_remap(blockIdx.x - n_big, n_small);
         int mi, ni;
         tile_mn(tile, n_small / nt, nt, g.group_m, mi, ni);
-        if constexpr (WMODE == 4) gemm_tile_x3<Cfg64N, ACT, HAS_BIAS, HAS_RES, PATCH>(g, g.m_split + mi * 64, ni * 128, smem);
-        else if constexpr (WMODE != 0) gemm_tile_bf16w<Cfg64N, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(g, g.m_split + mi * 64, ni * 128, smem);
+        if constexpr (WMODE == GEMM_W_F32X3) gemm_tile_x3<Cfg64N, ACT, HAS_BIAS, HAS_RES, PATCH>(g, g.m_split + mi * 64, ni * 128, smem);
+        else if constexpr (WMODE != GEMM_W_F32) gemm_tile_bf16w<Cfg64N, WMODE, ACT, HAS_BIAS, HAS_RES, PATCH>(g, g.m_split + mi * 64, ni * 128, smem);
         else gemm_tile<Cfg64N, ACT, HAS_BIAS, HAS_RES, PATCH>(g, g.m_split + mi * 64, ni * 128, smem);
     }
 }
@@ -1029,17 +1050,17 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w2_wide_kernel(GemmArgs g) {
         const int tile = xcd_remap(blockIdx.x, n_big);
         int mi, ni;
         tile_mn(tile, g.m_split / 128, ntw, g.group_m, mi, ni);
-        if constexpr (WMODE == 4) gemm_tile_x3<Cfg128W, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 256, smem);
+        if constexpr (WMODE == GEMM_W_F32X3) gemm_tile_x3<Cfg128W, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 256, smem);
         else if constexpr (VW) gemm_tile_w2v<Cfg128W, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 256, smem);
-        else gemm_tile_bf16w<Cfg128W, 3, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 256, smem);
+        else gemm_tile_bf16w<Cfg128W, GEMM_W_BF16_2T, ACT, HAS_BIAS, HAS_RES, PATCH>(g, mi * 128, ni * 256, smem);
     } else {
         const int nt = g.N / 128;
         const int n_small = gridDim.x - n_big;
         const int tile = xcd_remap(blockIdx.x - n_big, n_small);
         int mi, ni;
         tile_mn(tile, n_small / nt, nt, g.group_m, mi, ni);
-        if constexpr (WMODE == 4) gemm_tile_x3<Cfg64N, ACT, HAS_BIAS, HAS_RES, PATCH>(g, g.m_split + mi * 64, ni * 128, smem);
-        else gemm_tile_bf16w<Cfg64N, 3, ACT, HAS_BIAS, HAS_RES, PATCH>(g, g.m_split + mi * 64, ni * 128, smem);
+        if constexpr (WMODE == GEMM_W_F32X3) gemm_tile_x3<Cfg64N, ACT, HAS_BIAS, HAS_RES, PATCH>(g, g.m_split + mi * 64, ni * 128, smem);
+        else gemm_tile_bf16w<Cfg64N, GEMM_W_BF16_2T, ACT, HAS_BIAS, HAS_RES, PATCH>(g, g.m_split + mi * 64, ni * 128, smem);
     }
 }
 
@@ -1050,7 +1071,7 @@ static constexpr int lds_bytes(int wmode, int bm, int bn) {
 
 // algorithmic HBM bytes of one launch: A and W read once, C written once, residual read once, bias / position rows
 static double gemm_algorithmic_bytes(const GemmArgs& g) {
-    const double wbytes = g.Wp ? 6.0 : g.Wb ? 2.0 : 4.0;                // f32x3: three bf16 planes; bf16 weights: one term
+    const double wbytes = g.wmode == GEMM_W_F32X3 ? 6.0 : g.wmode == GEMM_W_F32 ? 4.0 : 2.0;   // f32x3: three bf16 planes; bf16 weights: one term
     return 4.0 * g.M * g.K + wbytes * g.N * g.K + 4.0 * g.M * g.N * (g.res ? 2.0 : 1.0) + (g.bias ? 4.0 * g.N : 0.0) +
            (g.pos ? 4.0 * (g.patch_np + 1) * g.N : 0.0);
 }
@@ -1181,10 +1202,21 @@ static int launch_mode(const GemmArgs& g0, hipStream_t stream) {
 
 template <int ACT, bool HAS_BIAS, bool HAS_RES, bool PATCH>
 static int launch_one(const GemmArgs& g, hipStream_t stream) {
-    if (g.Wp) return launch_mode<GEMM_W_F32X3, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
-    if (g.Wb && g.a_terms == 2) return launch_mode<GEMM_W_BF16_2T, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
-    if (g.Wb) return launch_mode<GEMM_W_BF16_EXACT, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
-    return launch_mode<GEMM_W_F32, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
+    // the mode is what the caller states; a mode without its plane is refused, never run as another arithmetic
+    // (the modes stand in the order f32x3, two-term, exact, f32: the kernels are emitted in the order they are named here)
+    switch (g.wmode) {
+        case GEMM_W_F32X3:
+            TSTAR_REQUIRE(g.Wp != nullptr, "gemm_f32: the f32x3 mode needs the packed three-plane copy (Wp)");
+            return launch_mode<GEMM_W_F32X3, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
+        case GEMM_W_BF16_2T:
+        case GEMM_W_BF16_EXACT:
+            TSTAR_REQUIRE(g.Wb != nullptr, "gemm_f32: the bf16-weight modes need the bf16 plane (Wb)");
+            return g.wmode == GEMM_W_BF16_2T ? launch_mode<GEMM_W_BF16_2T, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream)
+                                             : launch_mode<GEMM_W_BF16_EXACT, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
+        case GEMM_W_F32: return launch_mode<GEMM_W_F32, ACT, HAS_BIAS, HAS_RES, PATCH>(g, stream);
+    }
+    set_error("gemm_f32: unknown weight mode");
+    return TSTAR_ERR_ARG;
 }
 
 // rows of a super-panel (tile_mn): TSTAR_GEMM_GM overrides the default for A/B runs (1 = the panel-major order of rounds 1-3)

@@ -92,26 +92,10 @@ struct tstar_owl {
     std::map<std::pair<int, int>, Owlv2AxisTable> tabs_v2;   // OWLv2: (square side, out_size) -> zoom taps + Gaussian weights of one axis
     std::map<std::pair<int, int>, std::vector<double>> gw_v2;  // OWLv2: Gaussian weights installed by the caller (tstar_owlv2_set_axis_weights)
     // weights_mode 1 / 3 (BASELINE config 5, bf16 weights; two-term / exact three-term activations): bfloat16 copy of every
-    // GEMM weight matrix; weights_mode 4 (f32x3): every f32 matrix as three exact bf16 planes in MFMA-fragment order
+    // GEMM weight matrix (two-term mode, the N = 768 matrices: once more in MFMA-fragment order); weights_mode 4 (f32x3): every f32
+    // matrix as three exact bf16 planes in MFMA-fragment order.  Empty in the f32 mode; freed with the handle.
     int weights_mode = TSTAR_WEIGHTS_F32;
-    std::unordered_map<const float*, __bf16*> wb;
-    std::unordered_map<const float*, void*> wp;
-    std::unordered_map<const float*, void*> wq;          // two-term mode, the N = 768 matrices: the bf16 plane once more in MFMA-fragment order
-    const void* w2_of(const float* w) const {
-        if (weights_mode != TSTAR_WEIGHTS_BF16) return nullptr;
-        auto it = wq.find(w);
-        return it == wq.end() ? nullptr : it->second;
-    }
-    const __bf16* bf16_of(const float* w) const {
-        if (weights_mode != TSTAR_WEIGHTS_BF16 && weights_mode != TSTAR_WEIGHTS_BF16_EXACT) return nullptr;
-        auto it = wb.find(w);
-        return it == wb.end() ? nullptr : it->second;
-    }
-    const void* packed_of(const float* w) const {
-        if (weights_mode != TSTAR_WEIGHTS_F32X3) return nullptr;
-        auto it = wp.find(w);
-        return it == wp.end() ? nullptr : it->second;
-    }
+    std::unordered_map<const float*, WeightPlanes> planes;           // f32 matrix -> its planes in gemm_wmode_of(weights_mode)
 };
 
 static size_t padded(size_t n) { return (n + 63) / 64 * 64; }
@@ -181,9 +165,8 @@ static int get_table(tstar_owl* h, int in_size, int out_size, ResampleTable** ou
 static GemmArgs mk_gemm(const tstar_owl* h, const float* A, const float* W, float* C, const float* bias, const float* res,
                         int M, int N, int K, int lda, int ldc, int act) {
     GemmArgs g = gemm_args(A, W, C, bias, res, M, N, K, lda, ldc, act);
-    g.Wb = h->bf16_of(W); g.Wp = h->packed_of(W); g.Wq = h->w2_of(W);
-    g.a_terms = h->weights_mode == TSTAR_WEIGHTS_BF16 ? 2 : 0;           // bf16 weights: two-term activations unless the exact mode is asked for
-    return g;
+    const auto it = h->planes.find(W);
+    return it == h->planes.end() ? g : with_planes(g, it->second);
 }
 
 // The text tower's GEMMs.  The query embeddings are computed once per query set and enter every score, so the two-term mode runs
@@ -192,7 +175,7 @@ static GemmArgs mk_gemm(const tstar_owl* h, const float* A, const float* W, floa
 static GemmArgs mk_text_gemm(const tstar_owl* h, const float* A, const float* W, float* C, const float* bias, const float* res,
                              int M, int N, int K, int lda, int ldc, int act) {
     GemmArgs g = mk_gemm(h, A, W, C, bias, res, M, N, K, lda, ldc, act);
-    if (g.a_terms == 2) { g.a_terms = 0; g.Wq = nullptr; }
+    if (g.wmode == GEMM_W_BF16_2T) { g.wmode = GEMM_W_BF16_EXACT; g.Wq = nullptr; }
     return g;
 }
 
@@ -366,7 +349,7 @@ int tstar_owl_num_patches(tstar_owl* h) {
     return h->geom.np;
 }
 
-static int make_bf16_copies(tstar_owl* h, int mode) {
+static int build_all_weight_planes(tstar_owl* h, int mode) {
     struct Mat { const float* w; int n, k; };
     std::vector<Mat> mats;
     mats.push_back({h->vw.patch_w, V_D, h->geom.patch_k});
@@ -383,29 +366,9 @@ static int make_bf16_copies(tstar_owl* h, int mode) {
         for (int i = 0; i < T_LAYERS; ++i) layer(h->tw.layers[i], T_D, T_FF);
         mats.push_back({h->tw.text_proj, PROJ, T_D});
     }
-    for (auto& m : mats) {
-        const size_t n = (size_t)m.n * m.k;
-        int rc;
-        if (mode == TSTAR_WEIGHTS_F32X3) {
-            void* p = nullptr;
-            TSTAR_HIP_CHECK(hipMalloc(&p, n * 6));
-            h->wp[m.w] = p;
-            rc = pack_weights_x3(m.w, p, m.n, m.k, 0);
-        } else {
-            __bf16* p = nullptr;
-            TSTAR_HIP_CHECK(hipMalloc(&p, n * sizeof(__bf16)));
-            h->wb[m.w] = p;
-            rc = convert_f32_to_bf16(m.w, p, nullptr, n, 0);
-            static const bool w2v_off = getenv("TSTAR_W2V_OFF") != nullptr;           // same-session A/Bs: every layer on the LDS tile
-            if (!rc && mode == TSTAR_WEIGHTS_BF16 && m.n == 768 && m.k % 32 == 0 && !w2v_off) {       // per-shape dispatch (gemm_f32.hip plan_gemm)
-                void* q = nullptr;
-                TSTAR_HIP_CHECK(hipMalloc(&q, n * sizeof(__bf16)));
-                h->wq[m.w] = q;
-                rc = pack_weights_w2(p, q, m.n, m.k, 0);
-            }
-        }
-        if (rc) return rc;
-    }
+    static const bool w2v_off = getenv("TSTAR_W2V_OFF") != nullptr;   // same-session A/Bs: every layer on the LDS tile
+    // the handle's policy: a fragment-packed two-term plane for the N = 768 matrices only (per-shape dispatch, gemm_f32.hip plan_gemm)
+    for (auto& m : mats) RC(build_weight_planes(m.w, m.n, m.k, gemm_wmode_of(mode), m.n == 768 && !w2v_off, 0, &h->planes[m.w]));
     TSTAR_HIP_CHECK(hipDeviceSynchronize());
     h->weights_mode = mode;
     return TSTAR_OK;
@@ -497,7 +460,7 @@ int tstar_owl_create_family(tstar_owl** out, int family, int input_h, int input_
     rc = h->reserve_text_staging(TSTAR_OWL_MAX_QUERIES, nullptr);
     if (rc) { tstar_owl_destroy(h); return rc; }
     if (weights_mode != TSTAR_WEIGHTS_F32) {
-        rc = make_bf16_copies(h, weights_mode);
+        rc = build_all_weight_planes(h, weights_mode);
         if (rc) { tstar_owl_destroy(h); return rc; }
     }
     *out = h;
@@ -513,10 +476,7 @@ int tstar_owl_destroy(tstar_owl* h) {
     for (auto& L : h->lane) free_lane(L);
     for (auto& kv : h->tabs) free_table(&kv.second);
     for (auto& kv : h->tabs_v2) free_owlv2_axis_table(&kv.second);
-    for (auto& kv : h->wb) if (kv.second) (void)hipFree(kv.second);
-    for (auto& kv : h->wp) if (kv.second) (void)hipFree(kv.second);
-    for (auto& kv : h->wq) if (kv.second) (void)hipFree(kv.second);
-    delete h;
+    delete h;                                                // the weight planes go with the map that owns them
     return TSTAR_OK;
 }
 
