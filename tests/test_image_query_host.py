@@ -62,7 +62,10 @@ def test_restatement_is_hfs_selection_bit_for_bit(family):
         assert r["selected"][best]
         if r["gap"] >= 1e-3 * r["scale"]:
             compared += 1
-            assert best == r["best"], (best, r["best"])                          # identical rows: torch's argmin takes the first too
+            # identical rows tie exactly in float64 (the restatement takes the first); HF's float32 einsum gives them sums that differ in
+            # the last bits by where the row falls in the BLAS kernel's blocking (it changes with the thread count), so its argmin may
+            # name a later copy: another index must be a bit-identical row, and the embedding below is the same either way
+            assert best == r["best"] or np.array_equal(cls[best].view(np.uint32), cls[r["best"]].view(np.uint32)), (best, r["best"])
             assert np.array_equal(emb.view(np.uint32), cls[r["best"]].view(np.uint32))
     assert compared > 150
 
