@@ -50,6 +50,9 @@ def main():
     ap.add_argument("--jpeg-entropy", choices=("host", "device"), default=None,
                     help="where Motion-JPEG / JPEG-folder videos are entropy-decoded (default: TSTAR_JPEG_ENTROPY, else host); "
                          "'device' keeps the Huffman decode off the rank's CPUs")
+    ap.add_argument("--jpeg-resident", nargs="?", type=int, const=0, default=None, metavar="N",
+                    help="keep Motion-JPEG / JPEG-folder videos compressed in HBM and decode frames on demand into a pool of N slots "
+                         "(default 512; sets TSTAR_JPEG_RESIDENT / TSTAR_JPEG_POOL): same results from a fraction of the memory")
     ap.add_argument("--query-image", action="append", default=[], metavar="NAME=PATH[@x0,y0,x1,y1]",
                     help="example image of an object (repeatable): every target / cue object called NAME is searched for by the "
                          "image-guided query embedded from PATH instead of by its text; @x0,y0,x1,y1 (pixels of that image) "
@@ -87,6 +90,10 @@ def main():
 
     if args.jpeg_entropy is not None:
         os.environ["TSTAR_JPEG_ENTROPY"] = args.jpeg_entropy       # the searcher opens paths itself: the variable reaches it too
+    if args.jpeg_resident is not None:
+        os.environ["TSTAR_JPEG_RESIDENT"] = "1"
+        if args.jpeg_resident > 0:
+            os.environ["TSTAR_JPEG_POOL"] = str(args.jpeg_resident)
     per_video = max(1, args.questions_per_video)
     paths = args.videos if args.videos else [f"synthetic://n={args.nframes},seed={100 + i // per_video}" for i in range(args.items * per_video)]
     items = [{"video_path": p, "targets": QUESTIONS[i % 4][0], "cues": QUESTIONS[i % 4][1]} for i, p in enumerate(paths)]

@@ -584,6 +584,33 @@ int tstar_jpeg_entropy_split_host(const uint8_t* bytes, size_t total_bytes, cons
                                   const void* frames, int n_frames, int n_segments, int W, int H, int ncomp, int hs, int vs,
                                   int sub_bytes, int min_split_bytes, int max_rounds, void* workspace, size_t workspace_bytes,
                                   int16_t* coef, int32_t* seg_status, int32_t* seg_info);
+/* Compressed-resident store (added entries; tstar_abi_version() stays 3).  A file's wanted frames stay on the device as they are
+ * on disk, in an ARENA, next to what the planner said about each: d_off u64 [n_entries] (the arena may exceed 4 GiB; a frame
+ * may start at any byte), d_len u32 [n_entries], d_quant u16 [n_entries][192] (16-byte aligned), frame records whose
+ * first_segment indexes d_segments, and segments whose begin / end count from the frame's first byte.  A FETCH of m arena
+ * frames (repeats allowed) builds the buffer the entropy launchers take, without the host touching a compressed byte:
+ *   bytes     the frames end to end, each at a 16-byte-aligned start, padded with zeros; total_bytes < 2^32
+ *   quant     u16 [m][192] | frame records [m] | segments [n_segments], rebased to the batch (offsets from the size query)
+ * Descriptor, 6 x u32 per frame, written by the host from the counts it kept when the file was opened: {arena frame, byte offset
+ * in the batch, bytes, first segment in the batch, segments, 0}.  The launcher checks the HOST copy before any launch (ids,
+ * exact tiling of the bytes and of the segment list, capacities, the 2^32 bound) and refuses what fails; the kernel reads the
+ * DEVICE copy and checks each frame against the arena's own records again: one that disagrees is copied as zeros with a frame
+ * record without a table set and segments that name no frame (status 1, nothing touched).  No load leaves a frame's arena
+ * range, no store the batch buffer; one launch, no synchronisation.  The host mirror takes everything in host memory and
+ * gives the same buffer word for word. */
+/* Pure: bytes of the batch buffer for m frames (total_bytes: the sum of their lengths, each rounded up to 16) and n_segments
+ * segments; out3 (optional) = byte offsets of {quant rows, frame records, segments}.  0: not a batch. */
+size_t tstar_jpeg_gather_bytes(size_t total_bytes, int m, int n_segments, size_t* out3);
+int tstar_jpeg_gather(const uint8_t* d_arena, size_t arena_bytes, const uint64_t* d_off, const uint32_t* d_len, const uint16_t* d_quant,
+                      const void* d_frames, const void* d_segments, int n_entries, int n_arena_segments, const void* h_desc,
+                      const void* d_desc, int m, size_t total_bytes, int n_segments, uint8_t* d_batch, size_t batch_bytes, void* stream);
+int tstar_jpeg_gather_host(const uint8_t* arena, size_t arena_bytes, const uint64_t* off, const uint32_t* len, const uint16_t* quant,
+                           const void* frames, const void* segments, int n_entries, int n_arena_segments, const void* desc, int m,
+                           size_t total_bytes, int n_segments, uint8_t* batch, size_t batch_bytes);
+/* tstar_jpeg_reconstruct with frame j written to d_pool[d_slots[j]] (d_pool u8 [pool_frames,H,W,3]; d_slots i32 [m], device
+ * memory, read in place).  A slot outside 0 .. pool_frames - 1 is skipped: nothing of that frame is written. */
+int tstar_jpeg_reconstruct_slots(const int16_t* d_coef, const uint16_t* d_quant, int m, int W, int H, int ncomp, int hs, int vs,
+                                 uint8_t* d_planes, uint8_t* d_pool, int pool_frames, const int32_t* d_slots, void* stream);
 /* Native-resolution RGB u8 [n,H,W,3] of NV12 frames (the keyframes pop_frames hands back, :379-380). */
 int tstar_nv12_to_rgb(const uint8_t* d_video, int N, int H, int W, const int32_t* d_frame_idx, int n,
                       uint8_t* d_out, void* stream);

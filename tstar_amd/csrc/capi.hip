@@ -8,6 +8,7 @@
 #include "ingest.h"
 #include "jpeg_entropy_core.h"
 #include "jpeg_host.h"
+#include "jpeg_resident_core.h"
 #include "kernels.h"
 #include "owl_weights.h"
 #include <mutex>
@@ -184,6 +185,24 @@ int tstar_jpeg_reconstruct(const int16_t* d_coef, const uint16_t* d_quant, int n
     TSTAR_REQUIRE(d_coef && d_quant && d_planes && d_rgb, "tstar_jpeg_reconstruct: null argument");
     const JpegGeom g{W, H, ncomp, hs, vs};
     return jpeg_reconstruct_u8(d_coef, d_quant, n, g, d_planes, d_rgb, (hipStream_t)stream);
+}
+
+int tstar_jpeg_reconstruct_slots(const int16_t* d_coef, const uint16_t* d_quant, int m, int W, int H, int ncomp, int hs, int vs,
+                                 uint8_t* d_planes, uint8_t* d_pool, int pool_frames, const int32_t* d_slots, void* stream) {
+    TSTAR_REQUIRE(d_coef && d_quant && d_planes && d_pool && d_slots, "tstar_jpeg_reconstruct_slots: null argument");
+    const JpegGeom g{W, H, ncomp, hs, vs};
+    return jpeg_reconstruct_slots_u8(d_coef, d_quant, m, g, d_planes, d_pool, pool_frames, d_slots, (hipStream_t)stream);
+}
+
+int tstar_jpeg_gather(const uint8_t* d_arena, size_t arena_bytes, const uint64_t* d_off, const uint32_t* d_len, const uint16_t* d_quant,
+                      const void* d_frames, const void* d_segments, int n_entries, int n_arena_segments, const void* h_desc,
+                      const void* d_desc, int m, size_t total_bytes, int n_segments, uint8_t* d_batch, size_t batch_bytes, void* stream) {
+    jpegres::Arena a;
+    jpegres::Batch b;
+    const char* bad = jpegres::gather_args(d_arena, arena_bytes, d_off, d_len, d_quant, d_frames, d_segments, n_entries, n_arena_segments,
+                                           h_desc, m, total_bytes, n_segments, d_batch, batch_bytes, &a, &b);
+    TSTAR_REQUIRE(!bad, std::string("tstar_jpeg_gather: ") + bad);
+    return jpeg_gather(a, b, (const jpegres::GatherDesc*)h_desc, (const jpegres::GatherDesc*)d_desc, (hipStream_t)stream);
 }
 
 int tstar_gemm_f32(const float* d_A, const float* d_W, float* d_C, const float* d_bias, const float* d_residual, int M,

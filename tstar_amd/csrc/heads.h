@@ -84,6 +84,15 @@ int resample_v_normalize_patchify(const uint8_t* in, float* out, uint8_t* out_u8
 struct JpegGeom;
 int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const JpegGeom& g, uint8_t* planes, uint8_t* rgb,
                         hipStream_t s);
+// the same pixels with frame j written to pool[slots[j]] (pool u8 [pool_frames,H,W,3]; slots i32 [m], device memory; a slot
+// outside the pool is skipped)
+int jpeg_reconstruct_slots_u8(const int16_t* coef, const uint16_t* quant, int m, const JpegGeom& g, uint8_t* planes, uint8_t* pool,
+                              int pool_frames, const int32_t* slots, hipStream_t s);
+namespace jpegres { struct Arena; struct Batch; struct GatherDesc; }
+// jpeg_resident.hip: arena frames -> the batch buffer of the entropy launchers (h_desc: what gather_args checked; d_desc: the
+// same words in device memory, like every pointer of a and b)
+int jpeg_gather(const jpegres::Arena& a, const jpegres::Batch& b, const jpegres::GatherDesc* h_desc, const jpegres::GatherDesc* d_desc,
+                hipStream_t s);
 namespace jpegcore { struct SegmentBatch; }
 // jpeg_entropy.hip: clear b.coef, then one lane per segment of the batch (every pointer of b is device memory)
 int jpeg_entropy_segments(const jpegcore::SegmentBatch& b, hipStream_t s);

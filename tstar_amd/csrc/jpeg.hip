@@ -89,39 +89,21 @@ struct ColorArgs {
     int pitch0, pitch1, W, H, ncomp, hs, vs, cw, ch;
 };
 
-// Four consecutive pixels of the chunk (flat index over [n, H, W]) per lane -> 12 bytes = three dword stores.  A chroma
-// sample is read by the (up to four) pixels it feeds from L1 / L2; HBM sees every plane byte once.
-// DWORDS = false: the byte-store form for a destination that is not 4-byte aligned (odd W * H * s0).
-template <bool DWORDS>
-__global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restrict__ planes, ColorArgs a, uint8_t* __restrict__ rgb,
-                                                         size_t total_px) {
-    const size_t q = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (q >= total_px) return;
-    const size_t per = (size_t)a.W * a.H;
-    size_t f = q / per;
-    const size_t rem = q % per;
-    int y = (int)(rem / a.W), x = (int)(rem % a.W);
-    const int npx = total_px - q < 4 ? (int)(total_px - q) : 4;
-    uint32_t px[4] = {0, 0, 0, 0};                                 // R | G << 8 | B << 16 of each pixel, kept in registers
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (j < npx) {
-            const uint8_t* fp = planes + f * a.plane_frame_stride;
-            const int yy = fp[(size_t)y * a.pitch0 + x];
-            uint8_t t[3] = {(uint8_t)yy, (uint8_t)yy, (uint8_t)yy};
-            if (a.ncomp == 3) {
-                const int cb = jpegmath::upsample_at(fp + a.off1, a.pitch1, a.cw, a.ch, a.hs, a.vs, x, y);
-                const int cr = jpegmath::upsample_at(fp + a.off2, a.pitch1, a.cw, a.ch, a.hs, a.vs, x, y);
-                jpegmath::ycc_to_rgb(yy, cb, cr, t);
-            }
-            px[j] = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16);
-            if (++x == a.W) {
-                x = 0;
-                if (++y == a.H) { y = 0; ++f; }
-            }
-        }
+// R | G << 8 | B << 16 of pixel (x, y) of the frame whose planes start at fp.
+__device__ inline uint32_t color_pixel(const uint8_t* __restrict__ fp, const ColorArgs& a, int x, int y) {
+    const int yy = fp[(size_t)y * a.pitch0 + x];
+    uint8_t t[3] = {(uint8_t)yy, (uint8_t)yy, (uint8_t)yy};
+    if (a.ncomp == 3) {
+        const int cb = jpegmath::upsample_at(fp + a.off1, a.pitch1, a.cw, a.ch, a.hs, a.vs, x, y);
+        const int cr = jpegmath::upsample_at(fp + a.off2, a.pitch1, a.cw, a.ch, a.hs, a.vs, x, y);
+        jpegmath::ycc_to_rgb(yy, cb, cr, t);
     }
-    uint8_t* dst = rgb + q * 3;
+    return (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16);
+}
+
+// npx <= 4 pixels -> 3 * npx bytes at dst: three dword stores for a full, 4-byte-aligned quad, else bytes.
+template <bool DWORDS>
+__device__ inline void store_pixels(uint8_t* __restrict__ dst, const uint32_t (&px)[4], int npx) {
     if (DWORDS && npx == 4) {
         uint32_t* d4 = reinterpret_cast<uint32_t*>(dst);
         d4[0] = px[0] | (px[1] << 24);
@@ -138,16 +120,68 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restri
     }
 }
 
+// Four consecutive pixels of the chunk (flat index over [n, H, W]) per lane -> 12 bytes = three dword stores.  A chroma
+// sample is read by the (up to four) pixels it feeds from L1 / L2; HBM sees every plane byte once.
+// DWORDS = false: the byte-store form for a destination that is not 4-byte aligned (odd W * H * s0).
+template <bool DWORDS>
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restrict__ planes, ColorArgs a, uint8_t* __restrict__ rgb,
+                                                         size_t total_px) {
+    const size_t q = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (q >= total_px) return;
+    const size_t per = (size_t)a.W * a.H;
+    size_t f = q / per;
+    const size_t rem = q % per;
+    int y = (int)(rem / a.W), x = (int)(rem % a.W);
+    const int npx = total_px - q < 4 ? (int)(total_px - q) : 4;
+    uint32_t px[4] = {0, 0, 0, 0};                                 // kept in registers
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j < npx) {
+            px[j] = color_pixel(planes + f * a.plane_frame_stride, a, x, y);
+            if (++x == a.W) {
+                x = 0;
+                if (++y == a.H) { y = 0; ++f; }
+            }
+        }
+    }
+    store_pixels<DWORDS>(rgb + q * 3, px, npx);
+}
+
+// The same pixels for frames that go to NAMED slots of a pool: frame blockIdx.y -> pool[slots[blockIdx.y]], four consecutive
+// pixels of the frame per lane (a quad never crosses into another frame: slots need not be neighbours).  A slot outside
+// 0 .. pool_frames - 1 is skipped.  DWORDS: the pool and a frame's bytes are multiples of 4.
+template <bool DWORDS>
+__global__ __launch_bounds__(256) void jpeg_color_slots_kernel(const uint8_t* __restrict__ planes, ColorArgs a, uint8_t* __restrict__ pool,
+                                                               int pool_frames, const int32_t* __restrict__ slots) {
+    const int f = blockIdx.y, slot = slots[f];
+    if (slot < 0 || slot >= pool_frames) return;
+    const size_t per = (size_t)a.W * a.H;
+    const size_t q = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (q >= per) return;
+    int y = (int)(q / a.W), x = (int)(q % a.W);
+    const int npx = per - q < 4 ? (int)(per - q) : 4;
+    uint32_t px[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j < npx) {
+            px[j] = color_pixel(planes + (size_t)f * a.plane_frame_stride, a, x, y);
+            if (++x == a.W) { x = 0; ++y; }
+        }
+    }
+    store_pixels<DWORDS>(pool + ((size_t)slot * per + q) * 3, px, npx);
+}
+
 }  // namespace
 
-int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const JpegGeom& g, uint8_t* planes, uint8_t* rgb,
-                        hipStream_t s) {
-    TSTAR_REQUIRE(n > 0 && g.valid(), "jpeg_reconstruct_u8: n <= 0 or unsupported geometry");
+// dequantise + IDCT of n frames into their planes, and the colour stage's arguments
+static int jpeg_idct_planes(const int16_t* coef, const uint16_t* quant, int n, const JpegGeom& g, uint8_t* planes, ColorArgs* a,
+                            hipStream_t s, const char* fn) {
+    TSTAR_REQUIRE(n > 0 && g.valid(), std::string(fn) + ": n <= 0 or unsupported geometry");
     TSTAR_REQUIRE((uintptr_t)coef % 16 == 0 && (uintptr_t)quant % 16 == 0 && (uintptr_t)planes % 8 == 0,
-                  "jpeg_reconstruct_u8: coefficient / table buffers need 16-byte, the plane workspace 8-byte alignment");
+                  std::string(fn) + ": coefficient / table buffers need 16-byte, the plane workspace 8-byte alignment");
     const size_t blocks = g.blocks();
     TSTAR_REQUIRE(blocks * (size_t)n / kBlocksPerWg + 1 < 0x7fffffffull && (size_t)n * g.W * g.H / 1024 + 1 < 0x7fffffffull,
-                  "jpeg_reconstruct_u8: chunk too large for one launch");
+                  std::string(fn) + ": chunk too large for one launch");
     for (int c = 0; c < g.ncomp; ++c) {
         const int nblk = g.bw(c) * g.bh(c);
         const size_t total = (size_t)nblk * n;
@@ -156,18 +190,39 @@ int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const
                            g.plane_bytes(), nblk, g.bw(c), total);
         TSTAR_HIP_CHECK(hipGetLastError());
     }
+    a->plane_frame_stride = g.plane_bytes();
+    a->off1 = g.ncomp == 3 ? g.block_offset(1) * 64 : 0;
+    a->off2 = g.ncomp == 3 ? g.block_offset(2) * 64 : 0;
+    a->pitch0 = g.bw(0) * 8;
+    a->pitch1 = g.ncomp == 3 ? g.bw(1) * 8 : 0;
+    a->W = g.W; a->H = g.H; a->ncomp = g.ncomp; a->hs = g.hs; a->vs = g.vs;
+    a->cw = g.cw(1); a->ch = g.ch(1);
+    return TSTAR_OK;
+}
+
+int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const JpegGeom& g, uint8_t* planes, uint8_t* rgb,
+                        hipStream_t s) {
     ColorArgs a;
-    a.plane_frame_stride = g.plane_bytes();
-    a.off1 = g.ncomp == 3 ? g.block_offset(1) * 64 : 0;
-    a.off2 = g.ncomp == 3 ? g.block_offset(2) * 64 : 0;
-    a.pitch0 = g.bw(0) * 8;
-    a.pitch1 = g.ncomp == 3 ? g.bw(1) * 8 : 0;
-    a.W = g.W; a.H = g.H; a.ncomp = g.ncomp; a.hs = g.hs; a.vs = g.vs;
-    a.cw = g.cw(1); a.ch = g.ch(1);
+    if (const int rc = jpeg_idct_planes(coef, quant, n, g, planes, &a, s, "jpeg_reconstruct_u8")) return rc;
     const size_t total_px = (size_t)n * g.W * g.H;
     const dim3 grid((unsigned)((total_px + 1023) / 1024));
     if ((uintptr_t)rgb % 4 == 0) hipLaunchKernelGGL(jpeg_color_kernel<true>, grid, dim3(256), 0, s, planes, a, rgb, total_px);
     else hipLaunchKernelGGL(jpeg_color_kernel<false>, grid, dim3(256), 0, s, planes, a, rgb, total_px);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    return TSTAR_OK;
+}
+
+int jpeg_reconstruct_slots_u8(const int16_t* coef, const uint16_t* quant, int m, const JpegGeom& g, uint8_t* planes, uint8_t* pool,
+                              int pool_frames, const int32_t* slots, hipStream_t s) {
+    TSTAR_REQUIRE(pool_frames > 0 && m <= 65535, "jpeg_reconstruct_slots_u8: pool_frames <= 0 or more than 65535 frames");
+    TSTAR_REQUIRE((uintptr_t)slots % 4 == 0, "jpeg_reconstruct_slots_u8: misaligned slot list");
+    ColorArgs a;
+    if (const int rc = jpeg_idct_planes(coef, quant, m, g, planes, &a, s, "jpeg_reconstruct_slots_u8")) return rc;
+    const size_t per = (size_t)g.W * g.H;
+    const dim3 grid((unsigned)((per + 1023) / 1024), (unsigned)m);
+    if ((uintptr_t)pool % 4 == 0 && per * 3 % 4 == 0)
+        hipLaunchKernelGGL(jpeg_color_slots_kernel<true>, grid, dim3(256), 0, s, planes, a, pool, pool_frames, slots);
+    else hipLaunchKernelGGL(jpeg_color_slots_kernel<false>, grid, dim3(256), 0, s, planes, a, pool, pool_frames, slots);
     TSTAR_HIP_CHECK(hipGetLastError());
     return TSTAR_OK;
 }

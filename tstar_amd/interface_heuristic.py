@@ -478,10 +478,10 @@ class OWLInterface(HeuristicInterface):
     def _gather_resized(frames, size):
         """[(store, second)] -> cuda u8 [n, height, width, 3]: the frames gathered from their stores and resized to ``size`` =
         (width, height) by the searcher's own kernel (tstar_frames_resize, as ``TStarSearcher._device_verify_frames``); one launch
-        per run of frames of one store, one index upload."""
+        per run of frames of one store (at most ``store.lease_frames`` of them: a run is one lease), one index upload."""
         import torch
         ow, oh = int(size[0]), int(size[1])
-        dev = frames[0][0].frames.device
+        dev = frames[0][0].device
         out = torch.empty((len(frames), oh, ow, 3), dtype=torch.uint8, device=dev)
         d_idx = torch.as_tensor([int(sec) for _, sec in frames], dtype=torch.int32, device=dev)
         lib = _lib.load()
@@ -489,11 +489,13 @@ class OWLInterface(HeuristicInterface):
         while i0 < len(frames):
             store = frames[i0][0]
             i1 = i0
-            while i1 < len(frames) and frames[i1][0] is store:
+            while i1 < len(frames) and frames[i1][0] is store and i1 - i0 < (store.lease_frames or len(frames)):
                 i1 += 1
-            N, H, Wd, _ = store.shape
-            _lib.check(lib.tstar_frames_resize(store.frames.data_ptr(), N, H, Wd, d_idx[i0:i1].data_ptr(), i1 - i0, ow, oh,
+            _, H, Wd, _ = store.shape
+            lease = store.lease([int(sec) for _, sec in frames[i0:i1]], d_idx[i0:i1])
+            _lib.check(lib.tstar_frames_resize(lease.frames.data_ptr(), lease.N, H, Wd, lease.idx.data_ptr(), i1 - i0, ow, oh,
                                                out[i0:i1].data_ptr(), int(store.fmt == "nv12"), _lib.stream_ptr()), "tstar_frames_resize")
+            lease.done()
             i0 = i1
         return out
 

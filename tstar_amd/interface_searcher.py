@@ -338,10 +338,6 @@ class TStarSearcher:
     def _names_from_mask(self, mask: int) -> List[str]:
         return [self._texts[q][0] for q in range(len(self._texts)) if (mask >> q) & 1]
 
-    def _d_idx(self, secs):
-        import torch
-        return torch.as_tensor([int(s) for s in secs], dtype=torch.int32, device=self.store.frames.device)
-
     # ---- detection -------------------------------------------------------------------------------
     def imageGridScoreFunction(self, images: List[np.ndarray], output_dir: Optional[str], image_grids: Tuple[int, int]):
         """Generic (host-image) path with the reference's signature and return types (:94-155): one detector call per image through
@@ -401,7 +397,7 @@ class TStarSearcher:
         if st.ndim != 4 or st.shape[3] != 3:
             raise ValueError("create_image_grid expects HxWx3 uint8 frames of one size")
         n, H, Wd, _ = st.shape
-        dev = self.store.frames.device
+        dev = self.store.device
         d = torch.from_numpy(st).to(dev)
         out = torch.empty((n, CELL_H, CELL_W, 3), dtype=torch.uint8, device=dev)
         idx = torch.arange(n, dtype=torch.int32, device=dev)
@@ -413,44 +409,40 @@ class TStarSearcher:
     def _device_grid(self, secs):
         import torch
         rows, cols = self.image_grid_shape
-        if len(secs) != rows * cols:
-            raise ValueError("Frame count does not match grid dimensions")      # :183-184
-        N, H, Wd, _ = self.store.shape
-        grid = torch.empty((rows * CELL_H, cols * CELL_W, 3), dtype=torch.uint8, device=self.store.frames.device)
-        idx = self._d_idx(secs)
-        _lib.check(self._state.lib.tstar_frames_to_grid(self.store.frames.data_ptr(), N, H, Wd, idx.data_ptr(), rows,
-                                                        cols, grid.data_ptr(), int(self.store.fmt == "nv12"),
-                                                        _lib.stream_ptr()), "tstar_frames_to_grid")
+        grid = torch.empty((rows * CELL_H, cols * CELL_W, 3), dtype=torch.uint8, device=self.store.device)
+        self._device_grid_into(None, grid, secs)
         return grid
 
-    def _device_grid_into(self, d_idx, grid):
-        """``_device_grid`` with the sampled seconds already on the device (int32 [rows * cols]) into a caller-provided uint8
-        [rows * 95, cols * 200, 3] tensor (a slice of a group's stacked grid batch: no per-item index upload, no torch.stack copy)."""
+    def _device_grid_into(self, d_idx, grid, secs):
+        """``_device_grid`` into a caller-provided uint8 [rows * 95, cols * 200, 3] tensor (a slice of a group's stacked grid batch:
+        no torch.stack copy).  ``secs``: the sampled seconds on the host; ``d_idx``: the same already on the device (int32
+        [rows * cols]; None: uploaded here), which a decoded store reads in place (no per-item index upload)."""
         rows, cols = self.image_grid_shape
-        if int(d_idx.numel()) != rows * cols:
+        if len(secs) != rows * cols:
             raise ValueError("Frame count does not match grid dimensions")      # :183-184
-        N, H, Wd, _ = self.store.shape
-        _lib.check(self._state.lib.tstar_frames_to_grid(self.store.frames.data_ptr(), N, H, Wd, d_idx.data_ptr(), rows, cols,
+        _, H, Wd, _ = self.store.shape
+        lease = self.store.lease(secs, d_idx)
+        _lib.check(self._state.lib.tstar_frames_to_grid(lease.frames.data_ptr(), lease.N, H, Wd, lease.idx.data_ptr(), rows, cols,
                                                         grid.data_ptr(), int(self.store.fmt == "nv12"), _lib.stream_ptr()),
                    "tstar_frames_to_grid")
+        lease.done()
 
-    def _device_resized_into(self, d_idx, out):
-        """``_device_resized`` with the seconds already on the device (int32 [n]) into a caller-provided uint8 [n, h, w, 3] tensor."""
-        N, H, Wd, _ = self.store.shape
+    def _device_resized_into(self, d_idx, out, secs):
+        """``_device_resized`` into a caller-provided uint8 [n, h, w, 3] tensor; ``secs`` / ``d_idx`` as for ``_device_grid_into``."""
+        _, H, Wd, _ = self.store.shape
         n, oh, ow, _ = out.shape
-        _lib.check(self._state.lib.tstar_frames_resize(self.store.frames.data_ptr(), N, H, Wd, d_idx.data_ptr(), int(n), int(ow), int(oh),
+        if len(secs) != int(n):
+            raise ValueError("Frame count does not match the output tensor")
+        lease = self.store.lease(secs, d_idx)
+        _lib.check(self._state.lib.tstar_frames_resize(lease.frames.data_ptr(), lease.N, H, Wd, lease.idx.data_ptr(), int(n), int(ow), int(oh),
                                                        out.data_ptr(), int(self.store.fmt == "nv12"), _lib.stream_ptr()),
                    "tstar_frames_resize")
+        lease.done()
 
     def _device_resized(self, secs, out_w: int, out_h: int):
         import torch
-        N, H, Wd, _ = self.store.shape
-        out = torch.empty((len(secs), out_h, out_w, 3), dtype=torch.uint8, device=self.store.frames.device)
-        idx = self._d_idx(secs)
-        _lib.check(self._state.lib.tstar_frames_resize(self.store.frames.data_ptr(), N, H, Wd, idx.data_ptr(), len(secs),
-                                                       out_w, out_h, out.data_ptr(), int(self.store.fmt == "nv12"),
-                                                       _lib.stream_ptr()),
-                   "tstar_frames_resize")
+        out = torch.empty((len(secs), out_h, out_w, 3), dtype=torch.uint8, device=self.store.device)
+        self._device_resized_into(None, out, secs)
         return out
 
     def _device_verify_frames(self, secs):
@@ -538,7 +530,7 @@ class TStarSearcher:
         secs = [int(s) for s in sampled_frame_indices]
         frame_confidences = [confidence_map[i // grid_cols, i % grid_cols] for i in range(len(secs))]
         frame_detected_objects = [detected_objects_map[i] for i in range(len(secs))]
-        d_conf = torch.tensor(frame_confidences, dtype=torch.float64, device=self.store.frames.device)
+        d_conf = torch.tensor(frame_confidences, dtype=torch.float64, device=self.store.device)
         self._update_from_device(secs, d_conf)
         return frame_confidences, frame_detected_objects
 

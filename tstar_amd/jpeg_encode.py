@@ -290,12 +290,21 @@ def _encode_store(store, secs, quality, subsampling, chunk, slot_bytes, stats) -
     for s in secs:
         if not 0 <= s < N:
             raise IndexError(f"second {s} outside the store's 0..{N - 1}")
-    dev = store.frames.device
-    idx = torch.as_tensor(secs, dtype=torch.int32, device=dev)
+    dev = store.device
     if store.fmt == "rgb":
-        return _encode_device(store.frames, idx, quality, subsampling, chunk, slot_bytes, stats)
+        # a compressed-resident store hands out at most its pool per lease: encode pool-sized runs
+        step = max(1, min(len(secs), store.lease_frames or len(secs)))
+        out: List[bytes] = []
+        for s0 in range(0, len(secs), step):
+            lease = store.lease(secs[s0:s0 + step])
+            try:
+                out += _encode_device(lease.frames, lease.idx, quality, subsampling, chunk, slot_bytes, stats)
+            finally:
+                lease.done()
+        return out
+    idx = torch.as_tensor(secs, dtype=torch.int32, device=dev)
     # NV12: converted chunk by chunk with the kernel host_frames uses, so the bytes are Pillow's encode of host_frames(secs)
-    out: List[bytes] = []
+    out = []
     step = max(1, min(len(secs), 256, (256 << 20) // (H * W * 3)))
     with torch.cuda.device(dev):
         rgb = torch.empty((step, H, W, 3), dtype=torch.uint8, device=dev)

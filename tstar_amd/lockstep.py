@@ -203,7 +203,7 @@ class _Group:
         if not _ONE_UPLOAD:
             grids = [s._device_grid(secs) for s, secs in zip(items, secs_l)]
             return torch.stack(grids), grids
-        dev = items[0].store.frames.device
+        dev = items[0].store.device
         n = self.n
         for secs in secs_l:
             if len(secs) != n:
@@ -211,7 +211,7 @@ class _Group:
         d_idx = torch.as_tensor([int(v) for secs in secs_l for v in secs], dtype=torch.int32, device=dev)
         batch = torch.empty((len(items), self.rows * CELL_H, self.cols * CELL_W, 3), dtype=torch.uint8, device=dev)
         for i, s in enumerate(items):
-            s._device_grid_into(d_idx[i * n:(i + 1) * n], batch[i])
+            s._device_grid_into(d_idx[i * n:(i + 1) * n], batch[i], secs_l[i])
         return batch, [batch[i] for i in range(len(items))]
 
     def speculate(self):
@@ -299,12 +299,13 @@ class _Group:
                 # ONE index upload and ONE output tensor for the whole group (each item's resize writes its slice): the host's share of the
                 # step between a grid forward's masks and the first kernel of the verification batch is detector idle time
                 if _ONE_UPLOAD:
-                    dev = act[0].store.frames.device
+                    dev = act[0].store.device
                     d_idx = torch.as_tensor([secs_l[i][j] for i in range(len(act)) for j in cand_l[i]], dtype=torch.int32, device=dev)
                     vframes = torch.empty((int(offs[-1]), VERIFY_H, VERIFY_W, 3), dtype=torch.uint8, device=dev)
                     for i, s in enumerate(act):
                         if cand_l[i]:
-                            s._device_resized_into(d_idx[int(offs[i]):int(offs[i + 1])], vframes[int(offs[i]):int(offs[i + 1])])
+                            s._device_resized_into(d_idx[int(offs[i]):int(offs[i + 1])], vframes[int(offs[i]):int(offs[i + 1])],
+                                                   [secs_l[i][j] for j in cand_l[i]])
                 else:
                     vframes = torch.cat([s._device_verify_frames([secs_l[i][j] for j in cand_l[i]])
                                          for i, s in enumerate(act) if cand_l[i]])

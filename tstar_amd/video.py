@@ -65,6 +65,22 @@ def synthetic_frames_numpy(idx, n_frames: int, H: int = 360, W: int = 640, seed:
     return out
 
 
+class Lease:
+    """Frames of a store that a kernel may read: ``frames`` (the tensor to pass), ``N`` (its frame count), ``idx`` (int32 tensor on
+    the store's device: where the asked seconds sit in ``frames``, in the order asked).  ``done()`` is called once the kernels that
+    read them are queued on the current stream; the positions may be given to other frames afterwards."""
+
+    __slots__ = ("frames", "N", "idx", "_release")
+
+    def __init__(self, frames, N: int, idx, release=None):
+        self.frames, self.N, self.idx, self._release = frames, int(N), idx, release
+
+    def done(self) -> None:
+        release, self._release = self._release, None
+        if release is not None:
+            release()
+
+
 class FrameStore:
     """A decoded video in HBM at the searcher's logical rate (1 frame per second):
     ``frames`` uint8 cuda tensor [N,H,W,3] with frames[s] = raw frame int(s * raw_fps)
@@ -91,6 +107,21 @@ class FrameStore:
         return int(self.frames.shape[0])
 
     @property
+    def device(self):
+        return self.frames.device
+
+    lease_frames = None      # the most distinct seconds one lease may name (None: any number)
+
+    def lease(self, secs, d_idx=None) -> Lease:
+        """The frames of the logical seconds ``secs`` for a kernel to read (see ``Lease``).  ``d_idx``: the same seconds as an int32
+        tensor already on the device, when the caller has one.  A decoded store leases its whole tensor, the positions are the
+        seconds themselves and ``done()`` does nothing."""
+        if d_idx is None:
+            import torch
+            d_idx = torch.as_tensor([int(s) for s in secs], dtype=torch.int32, device=self.frames.device)
+        return Lease(self.frames, self.frames.shape[0], d_idx)
+
+    @property
     def shape(self):
         """(N, H, W, 3) of the RGB view, whatever the storage format."""
         if self.fmt == "nv12":
@@ -101,16 +132,26 @@ class FrameStore:
     def host_frames(self, secs) -> np.ndarray:
         """Native-resolution RGB frames of the given logical seconds -> uint8 numpy [n,H,W,3]."""
         import torch
+        secs = [int(i) for i in secs]
         if self.fmt == "nv12":
             from . import _lib
             N, H, W, _ = self.shape
-            idx = torch.as_tensor([int(i) for i in secs], dtype=torch.int32, device=self.frames.device)
-            out = torch.empty((len(idx), H, W, 3), dtype=torch.uint8, device=self.frames.device)
-            _lib.check(_lib.load().tstar_nv12_to_rgb(self.frames.data_ptr(), N, H, W, idx.data_ptr(), len(idx),
+            lease = self.lease(secs)
+            out = torch.empty((len(secs), H, W, 3), dtype=torch.uint8, device=self.device)
+            _lib.check(_lib.load().tstar_nv12_to_rgb(lease.frames.data_ptr(), lease.N, H, W, lease.idx.data_ptr(), len(secs),
                                                       out.data_ptr(), _lib.stream_ptr()), "tstar_nv12_to_rgb")
+            lease.done()
             return out.cpu().numpy()
-        ii = torch.as_tensor([int(i) for i in secs], dtype=torch.long, device=self.frames.device)
-        return self.frames.index_select(0, ii).cpu().numpy()
+        step = self.lease_frames or max(1, len(secs))
+        parts = []
+        for s0 in range(0, len(secs), step):
+            lease = self.lease(secs[s0:s0 + step])
+            parts.append(lease.frames.index_select(0, lease.idx.long()))
+            lease.done()
+        if len(parts) == 1:
+            return parts[0].cpu().numpy()
+        _, H, W, _ = self.shape
+        return torch.cat(parts).cpu().numpy() if parts else np.empty((0, H, W, 3), dtype=np.uint8)
 
     def jpeg_frames(self, secs, quality: int = 75, subsampling: str = "4:2:0"):
         """The given logical seconds as JPEG files (list of bytes), encoded on the device straight from the store: byte for
@@ -124,6 +165,205 @@ class FrameStore:
         file that would need OpenDML (1 GiB and above) is refused with a ValueError that names .mjpeg as the way out."""
         from . import jpeg_encode
         return jpeg_encode.save_mjpeg(self, path, quality, subsampling, fps)
+
+
+class JpegFrameStore(FrameStore):
+    """A Motion-JPEG video kept COMPRESSED in HBM (``open_video(..., resident="jpeg")``; built by ``jpeg_resident.load_resident``):
+    the wanted frames' file bytes and the decode plan stay on the device, and ``lease(secs)`` decodes the frames that are not in
+    the pool of ``pool_frames`` RGB slots on the current stream, without a host synchronisation.  Frames the device decoder does not
+    cover sit decoded in permanent slots behind the pool.  There is no ``frames`` tensor: every reader goes through ``lease`` or
+    ``host_frames``."""
+
+    def __init__(self, arena, d_arena, sec_entry, geom, hw, exceptions, pool_frames: int, raw_fps: float,
+                 raw_total_frames: Optional[int] = None, name: str = "<jpeg frames>", min_split_bytes: Optional[int] = None,
+                 max_rounds: Optional[int] = None):
+        """``max_rounds``: rounds of the split path a fetch queues (default jpeg.SPLIT_MAX_ROUNDS).  Sub-sequences are cut from a
+        segment's own first byte, so a segment converges in the round it converged in at open, wherever a fetch puts it: an open
+        passes the most rounds any segment took, and a fetch queues that many launches instead of 48 (same coefficients)."""
+        import torch
+        from . import jpeg, jpeg_resident as JR
+        self.fmt = "rgb"
+        self.raw_fps = float(raw_fps)
+        self.raw_total_frames = int(raw_total_frames if raw_total_frames is not None else round(len(sec_entry) * self.raw_fps))
+        self.name = name
+        self.decode_stats = self.entropy_stats = self.entropy_split_stats = None
+        self.arena, self.d_arena = arena, d_arena
+        self._sec_entry = np.asarray(sec_entry, dtype=np.int64)
+        self._geom = tuple(int(v) for v in geom) if geom is not None else None
+        H, W = hw
+        self._shape = (len(self._sec_entry), int(H), int(W), 3)
+        dev = d_arena.device
+        exc = sorted(exceptions)
+        normal = arena.n_entries - len(exc)
+        self.pool_frames = max(1, min(int(pool_frames), max(1, normal)))
+        self._pool = JR.SlotPool(self.pool_frames, exc)
+        self._slots = torch.empty((self.pool_frames + len(exc), H, W, 3), dtype=torch.uint8, device=dev)
+        for k, e in enumerate(exc):
+            self._slots[self.pool_frames + k].copy_(torch.as_tensor(exceptions[e]))
+        self._min_split = jpeg.split_min_bytes() if min_split_bytes is None else int(min_split_bytes)
+        self._max_rounds = jpeg.SPLIT_MAX_ROUNDS if max_rounds is None else max(1, min(int(max_rounds), jpeg.SPLIT_MAX_ROUNDS))
+        self._err = torch.zeros((), dtype=torch.int32, device=dev)
+        self._last_fetch = None                     # (stream key, event) of the last fetch: the next one reuses its workspace
+        self._len = arena.len.astype(np.int64)
+        self._nseg = arena.frames["n_segments"].astype(np.int64)
+        seg_len = arena.segments["end"].astype(np.int64) - arena.segments["begin"]
+        self._seg_longest = np.zeros(arena.n_entries, dtype=np.int64)
+        np.maximum.at(self._seg_longest, arena.segments["frame"].astype(np.int64), seg_len)
+        if self._geom is None or normal == 0:
+            return
+        # device copies of the arena's records (torch has no unsigned 32 / 64-bit tensors: same bits, signed types)
+        up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt).reshape(-1)).to(dev)       # noqa: E731
+        self._d_off, self._d_len = up(arena.off, np.int64), up(arena.len, np.int32)
+        self._d_quant, self._d_frames = up(arena.quant, np.int16), up(arena.frames, np.int32)
+        self._d_segments = up(arena.segments, np.int32) if len(arena.segments) else torch.zeros(6, dtype=torch.int32, device=dev)
+        self._d_sets = up(arena.table_sets, np.uint8)
+        # a fetch's workspace, sized once for the largest piece a fetch can be (never reallocated: fetches on several streams share
+        # it, ordered by events)
+        blocks, plane_bytes = jpeg._sizes(self._geom)
+        c = self._piece = max(1, min(self.pool_frames, JR.FETCH_COEF_BUDGET // (blocks * 128)))
+        keep = np.ones(arena.n_entries, dtype=bool)
+        keep[exc] = False
+        top = lambda a: int(np.sort(a[keep])[::-1][:c].sum())                                            # noqa: E731
+        self._cap_bytes, self._cap_segments = top((self._len + 15) & ~15), top(self._nseg)
+        self._d_batch = torch.empty(JR.gather_layout(self._cap_bytes, c, self._cap_segments)[0], dtype=torch.uint8, device=dev)
+        self._d_coef = torch.empty((c, blocks * 64), dtype=torch.int16, device=dev)
+        self._d_planes = torch.empty((c, plane_bytes), dtype=torch.uint8, device=dev)
+        self._d_status = torch.empty(2 * self._cap_segments, dtype=torch.int32, device=dev)
+        self._ws_bytes = jpeg.split_workspace_bytes(self._cap_bytes, self._cap_segments)
+        self._d_ws = torch.empty(self._ws_bytes // 8 + 1, dtype=torch.int64, device=dev)
+
+    @property
+    def frames(self):
+        raise AttributeError(f"{type(self).__name__} keeps {self.name} compressed and has no 'frames' tensor: read frames through "
+                             "lease(secs) (device) or host_frames(secs)")
+
+    @property
+    def num_seconds(self) -> int:
+        return self._shape[0]
+
+    @property
+    def shape(self):
+        return self._shape
+
+    @property
+    def device(self):
+        return self.d_arena.device
+
+    @property
+    def lease_frames(self):
+        return self.pool_frames
+
+    def _entries(self, secs):
+        secs = [int(s) for s in secs]
+        n = self._shape[0]
+        for s in secs:
+            if not 0 <= s < n:
+                raise IndexError(f"second {s} outside the store's 0..{n - 1}")
+        return self._sec_entry[secs] if secs else np.zeros(0, dtype=np.int64)
+
+    def lease(self, secs, d_idx=None) -> Lease:
+        """Slots of the pool that hold the frames ``secs`` until ``done()``: missing frames are decoded on the current stream first.
+        ``d_idx`` (the seconds on the device) is of no use here: ``idx`` names slots.  ValueError when the request needs more free
+        slots than the pool has."""
+        import torch
+        entries = self._entries(secs)
+        stream = torch.cuda.current_stream(self.device)
+        key = stream.cuda_stream
+        slots, fill, waits = self._pool.acquire(entries, key)
+        try:
+            for ev in waits:
+                stream.wait_event(ev)
+            # ONE pinned staging tensor and one copy: the positions of the asked frames, then per piece the descriptor and the slots
+            words = len(slots) + 7 * len(fill)
+            h = torch.empty(max(1, words), dtype=torch.int32, pin_memory=True)
+            hn = h.numpy()
+            hn[:len(slots)] = slots
+            d = torch.empty(max(1, words), dtype=torch.int32, device=self.device)
+            pieces, at = [], len(slots)
+            for c0 in range(0, len(fill), getattr(self, "_piece", 1)):
+                part = fill[c0:c0 + self._piece]
+                pieces.append(self._describe(part, hn, at))
+                at += 7 * len(part)
+            d.copy_(h, non_blocking=True)
+            if fill:
+                if self._last_fetch is not None and self._last_fetch[0] != key:
+                    stream.wait_event(self._last_fetch[1])
+                for piece in pieces:
+                    self._fetch(piece, h, d, stream)
+                ev = torch.cuda.Event()
+                ev.record(stream)
+                self._last_fetch = (key, ev)
+                self._pool.filled([s for _, s in fill], key, ev)
+        except Exception:
+            self._pool.forget(fill)
+            self._pool.release(slots)
+            raise
+
+        def release():
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.device))
+            self._pool.release(slots, torch.cuda.current_stream(self.device).cuda_stream, ev)
+
+        return Lease(self._slots, self._slots.shape[0], d[:len(slots)], release)
+
+    def _describe(self, part, hn, at):
+        """One piece of a fetch, [(entry, slot)]: its descriptor and slots into the staging words at ``at`` -> what _fetch needs."""
+        from . import jpeg_resident as JR
+        ids = [e for e, _ in part]
+        desc, total, nseg = JR.gather_descriptor(ids, self._len, self._nseg)
+        m = len(part)
+        if total > self._cap_bytes or nseg > self._cap_segments:
+            raise ValueError("JpegFrameStore: a fetch larger than the workspace sized at open")
+        hn[at:at + 6 * m] = desc.view(np.int32)
+        hn[at + 6 * m:at + 7 * m] = [s for _, s in part]
+        longest = int(self._seg_longest[ids].max())
+        return at, m, total, nseg, longest
+
+    def _fetch(self, piece, h, d, stream) -> None:
+        """Gather, entropy-decode and reconstruct one piece into its slots on ``stream``: three launchers, no synchronisation."""
+        from . import _lib, jpeg, jpeg_resident as JR
+        lib = _lib.load()
+        at, m, total, nseg, longest = piece
+        nbytes, q_at, f_at, s_at = JR.gather_layout(total, m, nseg)
+        ws = jpeg.split_workspace_bytes(total, nseg)
+        if nbytes > self._d_batch.numel() or ws > self._ws_bytes:
+            raise ValueError("JpegFrameStore: a fetch larger than the workspace sized at open")
+        a, base, sp = self.arena, self._d_batch.data_ptr(), stream.cuda_stream
+        _lib.check(lib.tstar_jpeg_gather(self.d_arena.data_ptr(), self.d_arena.numel(), self._d_off.data_ptr(), self._d_len.data_ptr(),
+                                         self._d_quant.data_ptr(), self._d_frames.data_ptr(), self._d_segments.data_ptr(), a.n_entries,
+                                         len(a.segments), h.data_ptr() + 4 * at, d.data_ptr() + 4 * at, m, total, nseg, base,
+                                         self._d_batch.numel(), sp), "tstar_jpeg_gather")
+        st = self._d_status
+        _lib.check(lib.tstar_jpeg_entropy_split_device(
+            base, total, base + s_at, self._d_sets.data_ptr(), len(a.table_sets), base + f_at, m, nseg, *self._geom, jpeg.SPLIT_SUB_BYTES,
+            self._min_split if longest >= self._min_split else 0, self._max_rounds, self._d_ws.data_ptr(), self._ws_bytes,
+            self._d_coef.data_ptr(), st.data_ptr(), st.data_ptr() + 4 * self._cap_segments, sp), "tstar_jpeg_entropy_split_device")
+        _lib.check(lib.tstar_jpeg_reconstruct_slots(self._d_coef.data_ptr(), base + q_at, m, *self._geom, self._d_planes.data_ptr(),
+                                                    self._slots.data_ptr(), self.pool_frames, d.data_ptr() + 4 * (at + 6 * m), sp),
+                   "tstar_jpeg_reconstruct_slots")
+        self._err.bitwise_or_(st[:nseg].max())
+
+    def fetch_errors(self) -> int:
+        """OR of the largest segment status of every fetch so far (0: every fetched frame decoded as it did at open).  Reads a device
+        word: this call synchronises, the fetch path never does."""
+        return int(self._err.item())
+
+    def flush(self) -> int:
+        """Forget every decoded frame no live lease holds (the next lease decodes again) -> how many."""
+        return self._pool.flush()
+
+    def source_frames(self, secs):
+        """The original file bytes of the given seconds (list of bytes), copied from the arena."""
+        out = []
+        for e in self._entries(secs):
+            o, n = int(self.arena.off[e]), int(self.arena.len[e])
+            out.append(self.d_arena[o:o + n].cpu().numpy().tobytes())
+        return out
+
+    def pool_stats(self) -> dict:
+        p = self._pool
+        return {"hits": p.hits, "misses": p.misses, "evictions": p.evictions, "exceptions": len(p.permanent),
+                "arena_bytes": int(self.d_arena.numel()), "pool_bytes": int(self._slots.numel())}
 
 
 def synthetic_video(n_frames: int = 3600, H: int = 360, W: int = 640, seed: int = 0, raw_fps: float = 1.0,
@@ -354,14 +594,20 @@ def load_pillow_sequence(path: str, device: str = "cuda", chunk: int = 64) -> Fr
 _SYN = re.compile(r"^synthetic://")
 
 
-def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_entropy: Optional[str] = None) -> FrameStore:
+def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_entropy: Optional[str] = None,
+               resident: Optional[str] = None, pool_frames: Optional[int] = None) -> FrameStore:
     """``video``: a FrameStore, a ``synthetic://n=..,h=..,w=..,seed=..,fps=..`` URL, a folder of .jpg / .jpeg frames or a
     list of JPEG paths / bytes (``fps`` frames per second, default 1), a .mjpeg / .mjpg stream (``fps`` default 25), a
     Motion-JPEG .avi, or another file path (.y4m, the Pillow sequences; else decoded at native rate through decord, else
     cv2; both absent -> ValueError like the reference's ``Cannot open video file`` at interface_searcher.py:61-62).
-    ``jpeg_entropy``: where JPEG sources are entropy-decoded, "host" (default; TSTAR_JPEG_ENTROPY when absent) or "device"."""
+    ``jpeg_entropy``: where JPEG sources are entropy-decoded, "host" (default; TSTAR_JPEG_ENTROPY when absent) or "device".
+    ``resident="jpeg"`` (TSTAR_JPEG_RESIDENT=1 when absent): a JPEG source stays compressed in HBM and its frames are decoded on
+    demand into a pool of ``pool_frames`` slots (default 512; TSTAR_JPEG_POOL) -> a ``JpegFrameStore``.  The keyword on a source
+    that is not JPEG is a ValueError; the variable alone leaves such a source as it is."""
     if isinstance(video, FrameStore):
         return video
+    from . import jpeg_resident
+    mode = jpeg_resident.resident_mode(resident)
     other_codec = None
     if not (isinstance(video, str) and _SYN.match(video)):
         from . import jpeg
@@ -371,9 +617,13 @@ def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_en
             src, other_codec = None, e
         if src is not None:
             try:
+                if mode == "jpeg" and (resident is not None or not str(device).startswith("cpu")):
+                    return jpeg_resident.load_resident(src, device, pool_frames)
                 return jpeg.load_jpeg(src, device, entropy=jpeg_entropy)
             finally:
                 src.close()
+    if resident is not None:
+        raise ValueError(f"open_video: resident={resident!r} needs a Motion-JPEG .avi, a .mjpeg stream or JPEG frames; {video!r} is none of them")
     if fps is not None:
         raise ValueError("open_video: fps= applies to JPEG frame folders / lists and .mjpeg streams only")
     if isinstance(video, str) and _SYN.match(video):
