@@ -352,6 +352,28 @@ def split_workspace_bytes(total_bytes: int, n_segments: int, sub_bytes: int = SP
     return n
 
 
+def split_threshold(min_split_bytes: int, longest: int) -> int:
+    """The min_split_bytes a split call over segments of at most ``longest`` bytes is made with: the segment lengths are known on
+    the host, and a call without a segment to split says 0 (never split), so that it does not queue the rounds at all."""
+    return min_split_bytes if longest >= min_split_bytes else 0
+
+
+def split_launch(head, longest: int, min_split_bytes: int, max_rounds: int, ws_ptr: int, ws_bytes: int, coef_ptr: int, status_ptr: int,
+                 info_ptr: int, stream: int, sub_bytes: int = SPLIT_SUB_BYTES) -> None:
+    """tstar_jpeg_entropy_split_device over the batch ``head`` describes (the leading arguments up to the geometry:
+    DeviceBatch._head, or the same of a gathered batch), the one place that calls it; ``longest``: see split_threshold."""
+    from . import _lib
+    _lib.check(_lib.load().tstar_jpeg_entropy_split_device(*head, sub_bytes, split_threshold(min_split_bytes, longest), max_rounds, ws_ptr,
+                                                           ws_bytes, coef_ptr, status_ptr, info_ptr, stream), "tstar_jpeg_entropy_split_device")
+
+
+def count_split(sstats: dict, seg_info: np.ndarray) -> None:
+    """Add a split call's seg_info (0 one lane, r > 0 converged in round r, -1 abandoned) to ``entropy_split_stats``."""
+    sstats["split"] += int((seg_info != 0).sum())
+    sstats["abandoned"] += int((seg_info < 0).sum())
+    sstats["rounds_max"] = max(sstats["rounds_max"], int(seg_info.max(initial=0)))
+
+
 def device_entropy_chunk(blocks: int, n_frames: int, chunk: Optional[int] = None, coef_budget: int = 512 << 20,
                          max_frames: int = 1024) -> int:
     """Frames per chunk of the device entropy path.  A frame without restart markers is one lane, so a launch wants as many
@@ -495,6 +517,8 @@ class DeviceBatch:
             at = _round16(at + arr.nbytes)
         self.nbytes = at
         self.datas = datas
+        seg = p.segments
+        self.longest = int((seg["end"].astype(np.int64) - seg["begin"]).max(initial=0))      # bytes of the longest segment
 
     def fill(self, host: np.ndarray) -> None:
         """Write the upload into ``host`` (uint8, at least nbytes)."""
@@ -522,11 +546,9 @@ class DeviceBatch:
                      min_split_bytes: int = SPLIT_MIN_BYTES, max_rounds: int = SPLIT_MAX_ROUNDS) -> None:
         """launch() through the split path: d_seg_info int32 [>= n_segments]; d_workspace uint8, 8-byte aligned, at least
         split_workspace_bytes(self.total, n_segments, sub_bytes)."""
-        from . import _lib
-        _lib.check(_lib.load().tstar_jpeg_entropy_split_device(
-            *self._head(d_buf, geom), sub_bytes, min_split_bytes, max_rounds, d_workspace.data_ptr(),
-            d_workspace.numel() * d_workspace.element_size(), d_coef.data_ptr(), d_seg_status.data_ptr(), d_seg_info.data_ptr(), stream),
-            "tstar_jpeg_entropy_split_device")
+        split_launch(self._head(d_buf, geom), self.longest, min_split_bytes, max_rounds, d_workspace.data_ptr(),
+                     d_workspace.numel() * d_workspace.element_size(), d_coef.data_ptr(), d_seg_status.data_ptr(), d_seg_info.data_ptr(),
+                     stream, sub_bytes)
 
 
 def _pillow_rgb(data: bytes, label: str) -> np.ndarray:
@@ -566,6 +588,252 @@ def wanted_frames(n_frames: int, fps: float):
     return [int(sec * fps) for sec in range(int(n_frames / fps))]
 
 
+# ------------------------------------------------------------------------------------------------ open
+class JpegOpen:
+    """What an open of a JPEG source knows before its first chunk, and what every mode does with ONE frame: ``raw`` is the raw frame
+    behind every frame k the open decodes, the first of them fixes the picture size (W, H), the first one the kernels cover fixes the
+    geometry.  The three counter dicts of the store live here; ``seconds`` [len(raw)] says how many logical seconds frame k serves
+    (default one each), and every count is in seconds."""
+
+    def __init__(self, src: JpegFrames, raw: Sequence[int], device, seconds: Optional[np.ndarray] = None):
+        self.src, self.raw, self.device = src, raw, device
+        self.first = src.read(raw[0])
+        self.W = self.H = self.geom = None
+        self.blocks = self.plane_bytes = 0
+        self.seconds = np.ones(len(raw), dtype=np.int64) if seconds is None else seconds
+        self.reconstructs = "host" if str(device).startswith("cpu") else "device"       # who turns coefficients into pixels
+        self.stats = {"device": 0, "host": 0, "pillow": 0}
+        self.estats = {"device": 0, "host": 0}
+        self.sstats = {"split": 0, "abandoned": 0, "rounds_max": 0}
+
+    def attach(self, store):
+        store.decode_stats, store.entropy_stats, store.entropy_split_stats = self.stats, self.estats, self.sstats
+        return store
+
+    def count(self, frames, decode: Optional[str] = None, entropy: Optional[str] = None) -> None:
+        n = int(self.seconds[frames].sum())
+        if decode is not None:
+            self.stats[decode] += n
+        if entropy is not None:
+            self.estats[entropy] += n
+
+    def read(self, k: int) -> bytes:
+        return self.first if k == 0 else self.src.read(self.raw[k])
+
+    def error(self, k: int, why: str) -> ValueError:
+        return ValueError(f"Cannot open video file: {self.src.label(self.raw[k])} ({why})")
+
+    def check_size(self, k: int, w: int, h: int) -> None:
+        """The first frame's size is the picture size; ValueError for a later frame of another."""
+        if self.W is None:
+            self.W, self.H = int(w), int(h)
+        elif (w, h) != (self.W, self.H):
+            raise ValueError(f"Cannot open video file: {self.src.label(self.raw[k])} is {w}x{h}, the first frame is {self.W}x{self.H}")
+
+    def pillow(self, k: int, data: bytes) -> np.ndarray:
+        """Frame k as Pillow decodes it (exact, on the host), size-checked and counted."""
+        arr = _pillow_rgb(data, self.src.label(self.raw[k]))
+        self.check_size(k, arr.shape[1], arr.shape[0])
+        self.count([k], "pillow")
+        return arr
+
+    def prelude(self, k: int, data: bytes) -> Optional[np.ndarray]:
+        """One step while no covered frame has been seen: frame k is probed alone -> None when the kernels cover it (its geometry is
+        the open's from here on), else Pillow's pixels; ValueError when it is broken or of another size."""
+        rc, info, msg = probe(data)
+        if rc == MALFORMED:
+            raise self.error(k, msg)
+        if rc != OK:
+            return self.pillow(k, data)
+        self.check_size(k, info[0], info[1])
+        self.geom = info
+        self.blocks, self.plane_bytes = _sizes(info)
+        return None
+
+    def host_verdict(self, k: int, data: bytes):
+        """Frame k, which a batch did not return OK for, alone through the host entropy decoder, whose verdict stands -> (coef int16
+        [1, blocks * 64], quant int16 [1, 192]) (torch, host) to reconstruct when it is OK after all, else Pillow's pixels (uncovered,
+        or covered sampling other than the batch's); ValueError when it is broken or of another size."""
+        import torch
+        coef1, quant1 = torch.empty((1, self.blocks * 64), dtype=torch.int16), torch.empty((1, 192), dtype=torch.int16)
+        status, message = entropy_batch([data], self.geom, coef1.numpy(), quant1.numpy().view(np.uint16), 1)
+        self.count([k], entropy="host")
+        if status[0] == OK:
+            self.count([k], self.reconstructs)
+            return coef1, quant1
+        if status[0] == MALFORMED:
+            raise self.error(k, message.split(': ', 2)[-1])
+        if status[0] == GEOMETRY:
+            _, info, _ = probe(data)
+            self.check_size(k, info[0], info[1])
+        return self.pillow(k, data)
+
+    def reconstruct_one(self, coef1, quant1, out, planes=None) -> None:
+        """One frame from host_verdict's coefficients into ``out`` (u8 [1,H,W,3] on the device), on the current stream."""
+        import torch
+        from . import _lib
+        if planes is None:
+            planes = torch.empty(self.plane_bytes, dtype=torch.uint8, device=self.device)
+        dc, dq = coef1.to(self.device), quant1.to(self.device)
+        _lib.check(_lib.load().tstar_jpeg_reconstruct(dc.data_ptr(), dq.data_ptr(), 1, *self.geom, planes.data_ptr(), out.data_ptr(),
+                                                      _lib.stream_ptr()), "tstar_jpeg_reconstruct")
+
+
+class EntropyRunner:
+    """The device-entropy stage of an open, chunk by chunk.  Owns its buffers -- two pinned uploads and two pinned status blocks (grown
+    on demand, used in turn), and ONE d_buf, d_ws and d_coef [chunk, blocks * 64]: every chunk of an open goes to the same stream, in
+    order -- the chunk size (device_entropy_chunk) and the take rule (device_entropy_take).  ``submit`` queues a chunk without waiting;
+    ``collect`` waits for it and says which frames the device did not return OK for."""
+
+    def __init__(self, ctx: JpegOpen, chunk: Optional[int], min_split_bytes: int):
+        import torch
+        self.ctx, self.min_split = ctx, min_split_bytes
+        self.chunk = device_entropy_chunk(ctx.blocks, len(ctx.raw), chunk)
+        self.d_coef = torch.empty((self.chunk, ctx.blocks * 64), dtype=torch.int16, device=ctx.device)
+        self.pinned, self.status, self.done = [None, None], [None, None], [None, None]
+        self.d_buf = self.d_ws = None
+        self.submitted = 0
+
+    def read(self, k0: int):
+        """The files of the chunk that starts at frame k0."""
+        datas = [self.ctx.read(k) for k in range(k0, min(len(self.ctx.raw), k0 + self.chunk))]
+        return datas[:device_entropy_take([len(d) for d in datas])]
+
+    def submit(self, k0: int, datas, stream):
+        """Plan, fill, upload, entropy-decode into d_coef and copy the statuses back, all on ``stream`` -> the ticket for collect();
+        d_buf holds the chunk as DeviceBatch.fill wrote it until the next submit."""
+        import torch
+        batch = DeviceBatch(datas, self.ctx.geom)
+        nseg, b, device = len(batch.plan.segments), self.submitted & 1, self.ctx.device
+        self.submitted += 1
+        if self.done[b] is not None:
+            self.done[b].synchronize()                    # this pinned buffer's previous copy has left
+        if self.pinned[b] is None or self.pinned[b].numel() < batch.nbytes:
+            self.pinned[b] = torch.empty(batch.nbytes + batch.nbytes // 4, dtype=torch.uint8).pin_memory()
+        if self.status[b] is None or self.status[b].numel() < 2 * nseg:          # statuses, then seg_info
+            self.status[b] = torch.empty(2 * (nseg + nseg // 4 + 64), dtype=torch.int32).pin_memory()
+        batch.fill(self.pinned[b].numpy())
+        with torch.cuda.stream(stream):
+            if self.d_buf is None or self.d_buf.numel() < batch.nbytes:
+                # allocated under the stream: a replaced buffer is not handed out again before the work queued on it is done
+                self.d_buf = None
+                self.d_buf = torch.empty(batch.nbytes + batch.nbytes // 4, dtype=torch.uint8, device=device)
+            self.d_buf[:batch.nbytes].copy_(self.pinned[b][:batch.nbytes], non_blocking=True)
+            if nseg:
+                d_status = torch.empty(2 * nseg, dtype=torch.int32, device=device)
+                ws_bytes = split_workspace_bytes(batch.total, nseg)
+                if self.d_ws is None or self.d_ws.numel() * 8 < ws_bytes:
+                    self.d_ws = None
+                    self.d_ws = torch.empty((ws_bytes + ws_bytes // 4) // 8 + 1, dtype=torch.int64, device=device)
+                batch.launch_split(self.d_buf, self.d_coef, d_status[:nseg], d_status[nseg:], self.d_ws, self.ctx.geom, stream.cuda_stream,
+                                   min_split_bytes=self.min_split)
+                self.status[b][:2 * nseg].copy_(d_status, non_blocking=True)
+            self.done[b] = torch.cuda.Event(blocking=True)       # the wait in collect sleeps: the CPU is what this stage saves
+            self.done[b].record(stream)
+        return k0, batch, b
+
+    def collect(self, ticket):
+        """Wait for a chunk's statuses -> the frames (positions in the chunk) the device did not return OK for, host-routed ones
+        included; the others are counted as the device's, and the split counters are updated."""
+        k0, batch, b = ticket
+        self.done[b].synchronize()
+        nseg = len(batch.plan.segments)
+        status = self.status[b][:2 * nseg].numpy()
+        fstat = batch.plan.frame_status(status[:nseg])
+        count_split(self.ctx.sstats, status[nseg:])
+        self.ctx.count(k0 + np.flatnonzero(fstat == OK), "device", "device")
+        return [int(j) for j in np.nonzero(fstat)[0]]
+
+
+def _device_entropy_chunks(ctx: JpegOpen, store, s0: int, chunk: Optional[int], min_split_bytes: int, side) -> None:
+    """load_jpeg from frame s0 on with the entropy stage on the device: every chunk is submitted, reconstructed into the store and
+    collected one chunk later (the host plans the next chunk while this one runs); a frame the device did not return OK for gets the
+    host decoder's verdict."""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    run = EntropyRunner(ctx, chunk, min_split_bytes)
+    planes = torch.empty((run.chunk, ctx.plane_bytes), dtype=torch.uint8, device=ctx.device)
+
+    def finish(ticket):
+        k0, batch, _ = ticket
+        for j in run.collect(ticket):
+            verdict = ctx.host_verdict(k0 + j, batch.datas[j])
+            with torch.cuda.stream(side):                 # behind the chunk's kernels, which wrote cleared coefficients' pixels here
+                if isinstance(verdict, tuple):
+                    ctx.reconstruct_one(*verdict, store[k0 + j:k0 + j + 1], planes)
+                else:
+                    store[k0 + j].copy_(torch.from_numpy(verdict))
+
+    before = None
+    while s0 < len(ctx.raw):
+        datas = run.read(s0)
+        ticket = run.submit(s0, datas, side)
+        batch = ticket[1]
+        if len(batch.plan.segments):
+            _lib.check(lib.tstar_jpeg_reconstruct(run.d_coef.data_ptr(), run.d_buf.data_ptr() + batch.parts["quant"][0], len(datas), *ctx.geom,
+                                                  planes.data_ptr(), store[s0:s0 + len(datas)].data_ptr(), side.cuda_stream),
+                       "tstar_jpeg_reconstruct")
+        if before is not None:
+            finish(before)
+        before = ticket
+        s0 += len(datas)
+    if before is not None:
+        finish(before)
+
+
+def _host_entropy_chunks(ctx: JpegOpen, store, s0: int, chunk: Optional[int], threads: int, side) -> None:
+    """load_jpeg from frame s0 on with the entropy stage on the host thread pool: coefficients into (on a GPU: two sets of pinned)
+    buffers, reconstruction by the HIP kernels on the side stream while the next chunk is entropy-decoded, or by their host mirror."""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    n_sec, geom, on_gpu = len(ctx.raw), ctx.geom, side is not None
+    c = min(chunk if chunk else max(1, min(64, (48 << 20) // (ctx.blocks * 128))), n_sec)
+    coefs = [torch.empty((c, ctx.blocks * 64), dtype=torch.int16, pin_memory=on_gpu) for _ in range(1 + on_gpu)]
+    quants = [torch.empty((c, 192), dtype=torch.int16, pin_memory=on_gpu) for _ in range(1 + on_gpu)]
+    if on_gpu:
+        d_coef = [torch.empty((c, ctx.blocks * 64), dtype=torch.int16, device=ctx.device) for _ in range(2)]
+        d_quant = [torch.empty((c, 192), dtype=torch.int16, device=ctx.device) for _ in range(2)]
+        planes = torch.empty((c, ctx.plane_bytes), dtype=torch.uint8, device=ctx.device)    # one: the side stream runs chunks in order
+        done = [None, None]
+    ci = 0
+    while s0 < n_sec:
+        b = ci & 1 if on_gpu else 0
+        if on_gpu and done[b] is not None:
+            done[b].synchronize()                         # the pinned buffers' previous copy has left
+        datas = [ctx.read(k) for k in range(s0, min(n_sec, s0 + c))]
+        n = len(datas)
+        coef, quant = coefs[b], quants[b]
+        status, _ = entropy_batch(datas, geom, coef.numpy(), quant.numpy().view(np.uint16), threads)
+        ctx.count(s0 + np.flatnonzero(status == OK), ctx.reconstructs, "host")
+        fallback = []
+        for j in (int(j) for j in np.nonzero(status)[0]):
+            verdict = ctx.host_verdict(s0 + j, datas[j])
+            if isinstance(verdict, tuple):
+                coef[j], quant[j] = verdict[0][0], verdict[1][0]
+            else:
+                fallback.append((j, verdict))
+        if on_gpu:
+            with torch.cuda.stream(side):
+                d_coef[b][:n].copy_(coef[:n], non_blocking=True)
+                d_quant[b][:n].copy_(quant[:n], non_blocking=True)
+                _lib.check(lib.tstar_jpeg_reconstruct(d_coef[b].data_ptr(), d_quant[b].data_ptr(), n, *geom, planes.data_ptr(),
+                                                      store[s0:s0 + n].data_ptr(), side.cuda_stream), "tstar_jpeg_reconstruct")
+                done[b] = torch.cuda.Event()
+                done[b].record(side)
+                for j, arr in fallback:                   # after the kernels, which wrote whatever the stale coefficients gave into these slots
+                    store[s0 + j].copy_(torch.from_numpy(arr))
+        else:
+            out = store[s0:s0 + n].numpy()
+            _lib.check(lib.tstar_jpeg_reconstruct_host(coef.data_ptr(), quant.data_ptr(), n, *geom, out.ctypes.data, threads),
+                       "tstar_jpeg_reconstruct_host")
+            for j, arr in fallback:
+                out[j] = arr
+        s0 += n
+        ci += 1
+
+
 def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None, threads: int = 0, entropy: Optional[str] = None):
     """Decode the wanted frames of ``src`` into a FrameStore (RGB u8 [N,H,W,3] on ``device``).  ``entropy``: "host" (the
     default; TSTAR_JPEG_ENTROPY when absent) or "device", where the Huffman decode runs on the GPU too and the store's
@@ -575,11 +843,10 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
     72 bytes of workspace per SPLIT_SUB_BYTES compressed bytes of a chunk.  Segments of at least TSTAR_JPEG_SPLIT_BYTES bytes
     (``split_min_bytes``; 0: none) are decoded by many lanes; ``entropy_split_stats`` counts the segments that were
     (``split``), those of them given up after SPLIT_MAX_ROUNDS rounds and decoded by one lane (``abandoned``) and the most
-    rounds a segment took (``rounds_max``)."""
+    rounds a segment took (``rounds_max``).  A JpegOpen carries the open: its prelude sends frames to Pillow until one is covered, then
+    the chunks go through _device_entropy_chunks (an EntropyRunner, as ``jpeg_resident.load_resident`` drives one) or _host_entropy_chunks."""
     import torch
-    from . import _lib
     from .video import FrameStore
-    lib = _lib.load()
     want = wanted_frames(src.n_frames, src.fps)
     if not want:
         raise ValueError(f"Cannot open video file: {src.name} (shorter than one second)")
@@ -587,211 +854,25 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
     if entropy == "device" and not on_gpu:
         raise ValueError("load_jpeg: entropy='device' needs a GPU store (device='cpu' was asked for)")
     dev_entropy = entropy_mode(entropy) == "device" and on_gpu       # TSTAR_JPEG_ENTROPY=device leaves a CPU store on the host path
-
-    # the first wanted frame fixes the picture size; the first frame the kernels cover fixes the device geometry
-    first = src.read(want[0])
-    rc, info, msg = probe(first)
-    if rc == MALFORMED:
-        raise ValueError(f"Cannot open video file: {src.label(want[0])} ({msg})")
-    if rc == OK:
-        W, H = info[0], info[1]
-    else:
-        H, W = _pillow_rgb(first, src.label(want[0])).shape[:2]
-    n_sec = len(want)
-    store = torch.empty((n_sec, H, W, 3), dtype=torch.uint8, device=device)
-    stats = {"device": 0, "host": 0, "pillow": 0}
-    estats = {"device": 0, "host": 0}
-    sstats = {"split": 0, "abandoned": 0, "rounds_max": 0}
     min_split = split_min_bytes() if dev_entropy else 0
-    geom = None
-    bufs = None
+    ctx = JpegOpen(src, want, device)
     side = torch.cuda.Stream(device=device) if on_gpu else None
-    done = [None, None]
-
-    def alloc(g):
-        blocks, plane_bytes = _sizes(g)
-        c = chunk if chunk else max(1, min(64, (48 << 20) // (blocks * 128)))
-        c = min(c, n_sec)
-        b = {"chunk": c, "blocks": blocks}
-        if dev_entropy:
-            c = b["chunk"] = device_entropy_chunk(blocks, n_sec, chunk)
-            b["pinned"] = [None, None]                  # uploads (grown on demand); statuses come back into "status"
-            b["status"] = [None, None]
-            b["d_buf"] = None
-            b["d_ws"] = None
-            b["d_coef"] = torch.empty((c, blocks * 64), dtype=torch.int16, device=device)
-            b["planes"] = torch.empty((c, plane_bytes), dtype=torch.uint8, device=device)
-        elif on_gpu:
-            b["coef"] = [torch.empty((c, blocks * 64), dtype=torch.int16).pin_memory() for _ in range(2)]
-            b["quant"] = [torch.empty((c, 192), dtype=torch.int16).pin_memory() for _ in range(2)]
-            b["d_coef"] = [torch.empty((c, blocks * 64), dtype=torch.int16, device=device) for _ in range(2)]
-            b["d_quant"] = [torch.empty((c, 192), dtype=torch.int16, device=device) for _ in range(2)]
-            b["planes"] = torch.empty((c, plane_bytes), dtype=torch.uint8, device=device)   # one: the side stream runs chunks in order
-        else:
-            b["coef"] = [torch.empty((c, blocks * 64), dtype=torch.int16)]
-            b["quant"] = [torch.empty((c, 192), dtype=torch.int16)]
-        return b
-
-    def fallback_rgb(data, label, status, message=None):
-        """A frame the host entropy stage did not return OK for: ValueError when it is broken or of another size, else what
-        Pillow decodes (uncovered, or covered sampling other than the batch's: exact, on the host)."""
-        if status == MALFORMED:
-            if message is None:
-                one_c = np.empty((1, bufs["blocks"] * 64), dtype=np.int16)
-                _, message = entropy_batch([data], geom, one_c, np.empty((1, 192), dtype=np.uint16), 1)
-            raise ValueError(f"Cannot open video file: {label} ({message.split(': ', 2)[-1]})")
-        if status == GEOMETRY:
-            _, inf, _ = probe(data)
-            if (inf[0], inf[1]) != (W, H):
-                raise ValueError(f"Cannot open video file: {label} is {inf[0]}x{inf[1]}, the first frame is {W}x{H}")
-        arr = _pillow_rgb(data, label)
-        if arr.shape != (H, W, 3):
-            raise ValueError(f"Cannot open video file: {label} is {arr.shape[1]}x{arr.shape[0]}, the first frame is {W}x{H}")
-        return arr
-
-    pending = []                                        # device entropy: chunks launched whose statuses are not read yet
-
-    def submit_device(s0, idx, datas, b):
-        """Upload, entropy-decode and reconstruct one chunk on the side stream; the statuses are read in finish_device."""
-        n = len(idx)
-        batch = DeviceBatch(datas, geom)
-        nseg = len(batch.plan.segments)
-        if done[b] is not None:
-            done[b].synchronize()                         # this pinned buffer's previous copy has left
-        if bufs["pinned"][b] is None or bufs["pinned"][b].numel() < batch.nbytes:
-            bufs["pinned"][b] = torch.empty(batch.nbytes + batch.nbytes // 4, dtype=torch.uint8).pin_memory()
-        if bufs["status"][b] is None or bufs["status"][b].numel() < 2 * nseg:       # statuses, then seg_info
-            bufs["status"][b] = torch.empty(2 * (nseg + nseg // 4 + 64), dtype=torch.int32).pin_memory()
-        batch.fill(bufs["pinned"][b].numpy())
-        with torch.cuda.stream(side):
-            if bufs["d_buf"] is None or bufs["d_buf"].numel() < batch.nbytes:
-                # in order on the side stream, so one device buffer serves every chunk (allocated under that stream: a
-                # replaced one is not handed out again before the work queued on it is done)
-                bufs["d_buf"] = torch.empty(batch.nbytes + batch.nbytes // 4, dtype=torch.uint8, device=device)
-            d_buf = bufs["d_buf"]
-            d_buf[:batch.nbytes].copy_(bufs["pinned"][b][:batch.nbytes], non_blocking=True)
-            if nseg:
-                d_status = torch.empty(2 * nseg, dtype=torch.int32, device=device)
-                ws_bytes = split_workspace_bytes(batch.total, nseg)
-                if bufs["d_ws"] is None or bufs["d_ws"].numel() * 8 < ws_bytes:             # like d_buf: one, in order on the side stream
-                    bufs["d_ws"] = torch.empty((ws_bytes + ws_bytes // 4) // 8 + 1, dtype=torch.int64, device=device)
-                # the segment lengths are known here: a chunk without a long segment does not queue the rounds at all
-                seg = batch.plan.segments
-                longest = int((seg["end"].astype(np.int64) - seg["begin"]).max())
-                batch.launch_split(d_buf, bufs["d_coef"], d_status[:nseg], d_status[nseg:], bufs["d_ws"], geom, side.cuda_stream,
-                                   min_split_bytes=min_split if longest >= min_split else 0)
-                bufs["status"][b][:2 * nseg].copy_(d_status, non_blocking=True)
-                # host-routed and refused frames reconstruct from cleared coefficients; finish_device overwrites their slots
-                _lib.check(lib.tstar_jpeg_reconstruct(bufs["d_coef"].data_ptr(), d_buf.data_ptr() + batch.parts["quant"][0], n, *geom,
-                                                      bufs["planes"].data_ptr(), store[s0:s0 + n].data_ptr(), side.cuda_stream),
-                           "tstar_jpeg_reconstruct")
-            done[b] = torch.cuda.Event(blocking=True)            # the wait in finish_device sleeps: the CPU is what this mode saves
-            done[b].record(side)
-        pending.append((s0, idx, datas, b, batch))
-
-    def finish_device():
-        """Read one launched chunk's statuses; every frame the device did not return OK for goes through the host decoder,
-        whose verdict stands: its coefficients are reconstructed on the device, or the frame is Pillow's / an error."""
-        s0, idx, datas, b, batch = pending.pop(0)
-        done[b].synchronize()
-        nseg = len(batch.plan.segments)
-        fstat = batch.plan.frame_status(bufs["status"][b][:nseg].numpy())
-        info = bufs["status"][b][nseg:2 * nseg].numpy()
-        sstats["split"] += int((info != 0).sum())
-        sstats["abandoned"] += int((info < 0).sum())
-        sstats["rounds_max"] = max(sstats["rounds_max"], int(info.max(initial=0)))
-        redo = [int(j) for j in np.nonzero(fstat)[0]]
-        for j in redo:
-            coef1 = torch.empty((1, bufs["blocks"] * 64), dtype=torch.int16)
-            quant1 = torch.empty((1, 192), dtype=torch.int16)
-            st1, msg = entropy_batch([datas[j]], geom, coef1.numpy(), quant1.numpy().view(np.uint16), 1)
-            estats["host"] += 1
-            with torch.cuda.stream(side):
-                if st1[0] == OK:
-                    dc, dq = coef1.to(device), quant1.to(device)
-                    _lib.check(lib.tstar_jpeg_reconstruct(dc.data_ptr(), dq.data_ptr(), 1, *geom, bufs["planes"].data_ptr(),
-                                                          store[s0 + j:s0 + j + 1].data_ptr(), side.cuda_stream), "tstar_jpeg_reconstruct")
-                    stats["device"] += 1
-                else:
-                    store[s0 + j].copy_(torch.from_numpy(fallback_rgb(datas[j], src.label(idx[j]), int(st1[0]), msg)))
-                    stats["pillow"] += 1
-        stats["device"] += len(idx) - len(redo)
-        estats["device"] += len(idx) - len(redo)
-
-    s0, ci = 0, 0
-    step = chunk if chunk else None
+    store, s0 = None, 0
     try:
-        while s0 < n_sec:
-            if geom is None:
-                # no covered frame seen yet: look one frame ahead at a time (each goes to Pillow until one is covered)
-                data = first if s0 == 0 else src.read(want[s0])
-                rc, info, msg = probe(data)
-                if rc == OK:
-                    if (info[0], info[1]) != (W, H):
-                        raise ValueError(f"Cannot open video file: {src.label(want[s0])} is {info[0]}x{info[1]}, the first frame is {W}x{H}")
-                    geom = info
-                    bufs = alloc(geom)
-                    step = bufs["chunk"]
-                    continue
-                if rc == MALFORMED:
-                    raise ValueError(f"Cannot open video file: {src.label(want[s0])} ({msg})")
-                arr = _pillow_rgb(data, src.label(want[s0]))
-                if arr.shape != (H, W, 3):
-                    raise ValueError(f"Cannot open video file: {src.label(want[s0])} is {arr.shape[1]}x{arr.shape[0]}, the first frame is {W}x{H}")
+        while s0 < len(want) and ctx.geom is None:
+            arr = ctx.prelude(s0, ctx.read(s0))
+            if store is None:                             # the first frame has fixed the picture size
+                store = torch.empty((len(want), ctx.H, ctx.W, 3), dtype=torch.uint8, device=device)
+            if arr is not None:
                 store[s0].copy_(torch.from_numpy(arr))
-                stats["pillow"] += 1
                 s0 += 1
-                continue
-            idx = want[s0:s0 + step]
-            n = len(idx)
-            b = ci & 1 if on_gpu else 0
-            if dev_entropy:
-                datas = [first if (s0 + j == 0) else src.read(fi) for j, fi in enumerate(idx)]
-                n = device_entropy_take([len(d) for d in datas])
-                idx, datas = idx[:n], datas[:n]
-                submit_device(s0, idx, datas, b)          # the host plans the next chunk while this one runs
-                if len(pending) > 1:
-                    finish_device()
-                s0 += n
-                ci += 1
-                continue
-            if on_gpu and done[b] is not None:
-                done[b].synchronize()                     # the pinned buffers' previous copy has left
-            datas = [first if (s0 + j == 0) else src.read(fi) for j, fi in enumerate(idx)]
-            coef, quant = bufs["coef"][b], bufs["quant"][b]
-            status, _ = entropy_batch(datas, geom, coef.numpy(), quant.numpy().view(np.uint16), threads)
-            fallback = [(int(j), fallback_rgb(datas[int(j)], src.label(idx[int(j)]), int(status[int(j)]))) for j in np.nonzero(status)[0]]
-            estats["host"] += n
-            if on_gpu:
-                with torch.cuda.stream(side):
-                    bufs["d_coef"][b][:n].copy_(coef[:n], non_blocking=True)
-                    bufs["d_quant"][b][:n].copy_(quant[:n], non_blocking=True)
-                    _lib.check(lib.tstar_jpeg_reconstruct(bufs["d_coef"][b].data_ptr(), bufs["d_quant"][b].data_ptr(), n, *geom,
-                                                          bufs["planes"].data_ptr(), store[s0:s0 + n].data_ptr(), side.cuda_stream),
-                               "tstar_jpeg_reconstruct")
-                    done[b] = torch.cuda.Event()
-                    done[b].record(side)
-                    for j, arr in fallback:               # after the kernels, which wrote whatever the stale coefficients gave into these slots
-                        store[s0 + j].copy_(torch.from_numpy(arr))
-            else:
-                out = store[s0:s0 + n].numpy()
-                _lib.check(lib.tstar_jpeg_reconstruct_host(coef.data_ptr(), quant.data_ptr(), n, *geom, out.ctypes.data, threads),
-                           "tstar_jpeg_reconstruct_host")
-                for j, arr in fallback:
-                    out[j] = arr
-            stats["device" if on_gpu else "host"] += n - len(fallback)
-            stats["pillow"] += len(fallback)
-            s0 += n
-            ci += 1
-        while pending:
-            finish_device()
+        if s0 < len(want) and dev_entropy:
+            _device_entropy_chunks(ctx, store, s0, chunk, min_split, side)
+        elif s0 < len(want):
+            _host_entropy_chunks(ctx, store, s0, chunk, threads, side)
     finally:
         # also on the way out with an error: the side stream may still be writing the previous chunk into the store, the
         # planes and the staged coefficients, and the allocator must not hand those blocks out before it is done
         if side is not None:
             side.synchronize()
-    st = FrameStore(store, src.fps, src.n_frames, name=src.name)
-    st.decode_stats = stats
-    st.entropy_stats = estats
-    st.entropy_split_stats = sstats
-    return st
+    return ctx.attach(FrameStore(store, src.fps, src.n_frames, name=src.name))

@@ -1,8 +1,9 @@
 """Compressed-resident Motion-JPEG store: the file's wanted frames stay in HBM as they are on disk and are decoded on demand.
 
-``load_resident`` opens a JPEG source the way ``jpeg.load_jpeg(entropy="device")`` does -- every wanted frame is planned, uploaded,
-entropy-decoded on the device and status-checked once, so a broken file fails at open with the same messages -- but keeps the
-compressed bytes (the ARENA) and the planner's records instead of the pixels.  A ``video.JpegFrameStore`` then serves ``lease(secs)``:
+``load_resident`` opens a JPEG source with the pieces ``jpeg.load_jpeg(entropy="device")`` opens it with (``jpeg.JpegOpen``,
+``jpeg.EntropyRunner``) -- every wanted frame is planned, uploaded, entropy-decoded on the device and status-checked once, so a broken
+file fails at open with the same messages -- but keeps the compressed bytes (the ARENA) and the planner's records instead of the
+pixels.  A ``video.JpegFrameStore`` then serves ``lease(secs)``:
 frames that are not in its small pool of RGB slots are gathered from the arena into one batch buffer (tstar_jpeg_gather), entropy-
 decoded (tstar_jpeg_entropy_split_device) and reconstructed into their slots (tstar_jpeg_reconstruct_slots) on the current stream,
 just before the ingest kernel reads them.  Frames the device decoder does not vouch for (progressive, arithmetic, CMYK, another
@@ -246,12 +247,12 @@ def _entry_keys(src, want):
 
 
 def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optional[int] = None, chunk: Optional[int] = None):
-    """Open ``src`` as a ``video.JpegFrameStore`` (see the module text).  Works in chunks like ``load_jpeg``'s device mode: one upload
-    per chunk carries the bytes and the records, the entropy kernels check every frame, the bytes move on into the arena."""
+    """Open ``src`` as a ``video.JpegFrameStore`` (see the module text).  The open is ``load_jpeg``'s device mode with another
+    destination: the same ``jpeg.JpegOpen`` (prelude, host verdict, counters, messages) and the same ``jpeg.EntropyRunner`` (one upload
+    per chunk carries the bytes and the records, the entropy kernels check every frame); here the bytes move on into the arena, and a
+    frame the device did not return OK for becomes an exception: RGB in a permanent slot."""
     import torch
-    from . import _lib
     from .video import JpegFrameStore
-    lib = _lib.load()
     if str(device).startswith("cpu"):
         raise ValueError("resident='jpeg' needs a GPU store (device='cpu' was asked for)")
     P = pool_size(pool_frames)
@@ -260,140 +261,58 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
         raise ValueError(f"Cannot open video file: {src.name} (shorter than one second)")
     sec_entry, raw = _entry_keys(src, want)
     E = len(raw)
-    first = src.read(raw[0])
-    rc, info, msg = jpeg.probe(first)
-    if rc == jpeg.MALFORMED:
-        raise ValueError(f"Cannot open video file: {src.label(raw[0])} ({msg})")
-    if rc == jpeg.OK:
-        W, H = info[0], info[1]
-    else:
-        H, W = jpeg._pillow_rgb(first, src.label(raw[0])).shape[:2]
-    stats = {"device": 0, "host": 0, "pillow": 0}
-    estats = {"device": 0, "host": 0}
-    sstats = {"split": 0, "abandoned": 0, "rounds_max": 0}
+    # the counters are per logical second, as load_jpeg's: an entry counts once for every second that shares it
+    ctx = jpeg.JpegOpen(src, raw, device, seconds=np.bincount(sec_entry, minlength=E))
     min_split = jpeg.split_min_bytes()
     sizes = [src.ranges[fi][1] for fi in raw] if getattr(src, "ranges", None) is not None else None
     builder = ArenaBuilder()
     d_parts = []                                        # the arena's bytes, chunk by chunk, when the sizes are not known up front
     d_arena = torch.empty(sum(sizes), dtype=torch.uint8, device=device) if sizes is not None else None
     exceptions = {}                                     # entry -> RGB uint8 [H,W,3] (numpy), or a cuda tensor
-    kind = ["device"] * E                               # who decoded an entry: "device", "host" (entropy), "host-pillow", "pillow"
-    geom, blocks, bufs = None, 0, {}
 
-    def check_size(arr, label):
-        if arr.shape != (H, W, 3):
-            raise ValueError(f"Cannot open video file: {label} is {arr.shape[1]}x{arr.shape[0]}, the first frame is {W}x{H}")
-        return arr
-
-    def redo(e, data):
-        """A frame the device did not return OK for: the host decoder's verdict stands (load_jpeg's finish_device)."""
-        label = src.label(raw[e])
-        coef1 = torch.empty((1, blocks * 64), dtype=torch.int16)
-        quant1 = torch.empty((1, 192), dtype=torch.int16)
-        st1, m1 = jpeg.entropy_batch([data], geom, coef1.numpy(), quant1.numpy().view(np.uint16), 1)
-        estats["host"] += 1
-        if st1[0] == jpeg.OK:
-            rgb = torch.empty((1, H, W, 3), dtype=torch.uint8, device=device)
-            planes = torch.empty(jpeg._sizes(geom)[1], dtype=torch.uint8, device=device)
-            dc, dq = coef1.to(device), quant1.to(device)
-            _lib.check(lib.tstar_jpeg_reconstruct(dc.data_ptr(), dq.data_ptr(), 1, *geom, planes.data_ptr(), rgb.data_ptr(),
-                                                  _lib.stream_ptr()), "tstar_jpeg_reconstruct")
-            torch.cuda.current_stream().synchronize()
-            exceptions[e], kind[e] = rgb[0], "host"
-            stats["device"] += 1
-            return
-        if st1[0] == jpeg.MALFORMED:
-            raise ValueError(f"Cannot open video file: {label} ({m1.split(': ', 2)[-1]})")
-        if st1[0] == jpeg.GEOMETRY:
-            _, inf, _ = jpeg.probe(data)
-            if (inf[0], inf[1]) != (W, H):
-                raise ValueError(f"Cannot open video file: {label} is {inf[0]}x{inf[1]}, the first frame is {W}x{H}")
-        exceptions[e], kind[e] = check_size(jpeg._pillow_rgb(data, label), label), "host-pillow"
-        stats["pillow"] += 1
-
-    def place(datas):
-        """A chunk's bytes that did not come through a DeviceBatch upload, into the arena."""
-        host = torch.from_numpy(np.frombuffer(b"".join(datas), dtype=np.uint8).copy())
+    def place(d_bytes):
+        """A chunk's bytes (a tensor, host or device) into the arena, behind what is there."""
         if d_arena is not None:
-            d_arena[builder.total:builder.total + host.numel()].copy_(host)
+            d_arena[builder.total:builder.total + d_bytes.numel()].copy_(d_bytes)
         else:
-            d_parts.append(host.to(device))
+            d_parts.append(d_bytes.to(device, copy=True))
 
     e0 = 0
+    while e0 < E and ctx.geom is None:
+        data = ctx.read(e0)
+        arr = ctx.prelude(e0, data)
+        if arr is None:
+            break
+        exceptions[e0] = arr
+        place(torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()))
+        builder.add(jpeg.SegmentPlan(np.ones(1, np.int32), np.array([(-1, 0, 0, 0)], dtype=jpeg.FRAME_DTYPE), np.zeros((1, 192), np.uint16),
+                                     np.zeros((0, jpeg.TABLE_SET_BYTES), np.uint8), np.zeros(0, jpeg.SEGMENT_DTYPE),
+                                     np.zeros(1, np.uint64), len(data)), [len(data)])
+        e0 += 1
+    run = jpeg.EntropyRunner(ctx, chunk, min_split) if e0 < E else None
+    stream = torch.cuda.current_stream()
     while e0 < E:
-        if geom is None:
-            # no covered frame seen yet: one frame at a time, each Pillow's until one is covered (as load_jpeg)
-            data = first if e0 == 0 else src.read(raw[e0])
-            rc, info, msg = jpeg.probe(data)
-            if rc == jpeg.OK:
-                if (info[0], info[1]) != (W, H):
-                    raise ValueError(f"Cannot open video file: {src.label(raw[e0])} is {info[0]}x{info[1]}, the first frame is {W}x{H}")
-                geom = info
-                blocks = jpeg._sizes(geom)[0]
-                bufs["chunk"] = jpeg.device_entropy_chunk(blocks, E, chunk)
-                bufs["d_coef"] = torch.empty((bufs["chunk"], blocks * 64), dtype=torch.int16, device=device)
-                continue
-            if rc == jpeg.MALFORMED:
-                raise ValueError(f"Cannot open video file: {src.label(raw[e0])} ({msg})")
-            exceptions[e0], kind[e0] = check_size(jpeg._pillow_rgb(data, src.label(raw[e0])), src.label(raw[e0])), "pillow"
-            stats["pillow"] += 1
-            place([data])
-            builder.add(jpeg.SegmentPlan(np.ones(1, np.int32), np.array([(-1, 0, 0, 0)], dtype=jpeg.FRAME_DTYPE), np.zeros((1, 192), np.uint16),
-                                         np.zeros((0, jpeg.TABLE_SET_BYTES), np.uint8), np.zeros(0, jpeg.SEGMENT_DTYPE),
-                                         np.zeros(1, np.uint64), len(data)), [len(data)])
-            e0 += 1
-            continue
-        ids = list(range(e0, min(E, e0 + bufs["chunk"])))
-        datas = [first if e == 0 else src.read(raw[e]) for e in ids]
-        n = jpeg.device_entropy_take([len(d) for d in datas])
-        ids, datas = ids[:n], datas[:n]
-        batch = jpeg.DeviceBatch(datas, geom)
-        nseg = len(batch.plan.segments)
-        pinned = torch.empty(batch.nbytes, dtype=torch.uint8).pin_memory()
-        batch.fill(pinned.numpy())
-        d_buf = torch.empty(batch.nbytes, dtype=torch.uint8, device=device)
-        d_buf.copy_(pinned, non_blocking=True)
-        fstat = np.full(n, -1, dtype=np.int32)
-        if nseg:
-            d_status = torch.empty(2 * nseg, dtype=torch.int32, device=device)
-            d_ws = torch.empty(jpeg.split_workspace_bytes(batch.total, nseg) // 8 + 1, dtype=torch.int64, device=device)
-            seg = batch.plan.segments
-            longest = int((seg["end"].astype(np.int64) - seg["begin"]).max())
-            batch.launch_split(d_buf, bufs["d_coef"], d_status[:nseg], d_status[nseg:], d_ws, geom, _lib.stream_ptr(),
-                               min_split_bytes=min_split if longest >= min_split else 0)
-            st = d_status.cpu().numpy()                  # waits for the chunk: the statuses decide what the arena may serve
-            fstat = batch.plan.frame_status(st[:nseg])
-            info = st[nseg:]
-            sstats["split"] += int((info != 0).sum())
-            sstats["abandoned"] += int((info < 0).sum())
-            sstats["rounds_max"] = max(sstats["rounds_max"], int(info.max(initial=0)))
-        if d_arena is not None:
-            d_arena[builder.total:builder.total + batch.total].copy_(d_buf[:batch.total])
-        else:
-            d_parts.append(d_buf[:batch.total].clone())
+        datas = run.read(e0)
+        ticket = run.submit(e0, datas, stream)
+        batch = ticket[1]
+        place(run.d_buf[:batch.total])
         builder.add(batch.plan, [len(d) for d in datas])
-        bad = [int(j) for j in np.nonzero(fstat)[0]]
-        for j in bad:
-            redo(ids[j], datas[j])
-        stats["device"] += n - len(bad)
-        estats["device"] += n - len(bad)
-        e0 += n
-    torch.cuda.current_stream().synchronize()
-    bufs.clear()
+        for j in run.collect(ticket):                    # waits for the chunk: the statuses decide what the arena may serve
+            verdict = ctx.host_verdict(e0 + j, datas[j])
+            if isinstance(verdict, tuple):
+                rgb = torch.empty((1, ctx.H, ctx.W, 3), dtype=torch.uint8, device=device)
+                ctx.reconstruct_one(*verdict, rgb)
+                stream.synchronize()
+                verdict = rgb[0]
+            exceptions[e0 + j] = verdict
+        e0 += len(datas)
+    stream.synchronize()
+    run = None                                          # its buffers go back before the store allocates the pool
     if d_arena is None:
         d_arena = torch.cat(d_parts) if len(d_parts) > 1 else d_parts[0]
         del d_parts
     arena = builder.finish()
     assert arena.n_entries == E and builder.total == d_arena.numel()
-    # the counters are per logical second, as load_jpeg's: seconds that share an arena entry count once each
-    per_sec = np.bincount(sec_entry, minlength=E)
-    for e in range(E):
-        if per_sec[e] > 1:
-            k = kind[e]
-            stats["pillow" if k.endswith("pillow") else "device"] += int(per_sec[e]) - 1
-            if k != "pillow":
-                estats["device" if k == "device" else "host"] += int(per_sec[e]) - 1
-    st = JpegFrameStore(arena, d_arena, sec_entry, geom, (H, W), exceptions, P, src.fps, src.n_frames, name=src.name, min_split_bytes=min_split,
-                        max_rounds=sstats["rounds_max"])
-    st.decode_stats, st.entropy_stats, st.entropy_split_stats = stats, estats, sstats
-    return st
+    st = JpegFrameStore(arena, d_arena, sec_entry, ctx.geom, (ctx.H, ctx.W), exceptions, P, src.fps, src.n_frames, name=src.name,
+                        min_split_bytes=min_split, max_rounds=ctx.sstats["rounds_max"])
+    return ctx.attach(st)

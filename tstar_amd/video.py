@@ -334,10 +334,9 @@ class JpegFrameStore(FrameStore):
                                          len(a.segments), h.data_ptr() + 4 * at, d.data_ptr() + 4 * at, m, total, nseg, base,
                                          self._d_batch.numel(), sp), "tstar_jpeg_gather")
         st = self._d_status
-        _lib.check(lib.tstar_jpeg_entropy_split_device(
-            base, total, base + s_at, self._d_sets.data_ptr(), len(a.table_sets), base + f_at, m, nseg, *self._geom, jpeg.SPLIT_SUB_BYTES,
-            self._min_split if longest >= self._min_split else 0, self._max_rounds, self._d_ws.data_ptr(), self._ws_bytes,
-            self._d_coef.data_ptr(), st.data_ptr(), st.data_ptr() + 4 * self._cap_segments, sp), "tstar_jpeg_entropy_split_device")
+        jpeg.split_launch((base, total, base + s_at, self._d_sets.data_ptr(), len(a.table_sets), base + f_at, m, nseg, *self._geom), longest,
+                          self._min_split, self._max_rounds, self._d_ws.data_ptr(), self._ws_bytes, self._d_coef.data_ptr(), st.data_ptr(),
+                          st.data_ptr() + 4 * self._cap_segments, sp)
         _lib.check(lib.tstar_jpeg_reconstruct_slots(self._d_coef.data_ptr(), base + q_at, m, *self._geom, self._d_planes.data_ptr(),
                                                     self._slots.data_ptr(), self.pool_frames, d.data_ptr() + 4 * (at + 6 * m), sp),
                    "tstar_jpeg_reconstruct_slots")
