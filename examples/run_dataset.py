@@ -53,6 +53,9 @@ def main():
     ap.add_argument("--jpeg-resident", nargs="?", type=int, const=0, default=None, metavar="N",
                     help="keep Motion-JPEG / JPEG-folder videos compressed in HBM and decode frames on demand into a pool of N slots "
                          "(default 512; sets TSTAR_JPEG_RESIDENT / TSTAR_JPEG_POOL): same results from a fraction of the memory")
+    ap.add_argument("--jpeg-scale", type=int, choices=(1, 2, 4, 8), default=None, metavar="N",
+                    help="decode Motion-JPEG / JPEG-folder videos at 1/N size (2, 4 or 8; sets TSTAR_JPEG_SCALE), byte for byte Pillow's "
+                         "draft: the store shrinks by N * N, and the search sees the smaller frames (boxes are in their pixels)")
     ap.add_argument("--query-image", action="append", default=[], metavar="NAME=PATH[@x0,y0,x1,y1]",
                     help="example image of an object (repeatable): every target / cue object called NAME is searched for by the "
                          "image-guided query embedded from PATH instead of by its text; @x0,y0,x1,y1 (pixels of that image) "
@@ -94,6 +97,8 @@ def main():
         os.environ["TSTAR_JPEG_RESIDENT"] = "1"
         if args.jpeg_resident > 0:
             os.environ["TSTAR_JPEG_POOL"] = str(args.jpeg_resident)
+    if args.jpeg_scale is not None:
+        os.environ["TSTAR_JPEG_SCALE"] = str(args.jpeg_scale)
     per_video = max(1, args.questions_per_video)
     paths = args.videos if args.videos else [f"synthetic://n={args.nframes},seed={100 + i // per_video}" for i in range(args.items * per_video)]
     items = [{"video_path": p, "targets": QUESTIONS[i % 4][0], "cues": QUESTIONS[i % 4][1]} for i, p in enumerate(paths)]

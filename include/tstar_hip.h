@@ -611,6 +611,27 @@ int tstar_jpeg_gather_host(const uint8_t* arena, size_t arena_bytes, const uint6
  * memory, read in place).  A slot outside 0 .. pool_frames - 1 is skipped: nothing of that frame is written. */
 int tstar_jpeg_reconstruct_slots(const int16_t* d_coef, const uint16_t* d_quant, int m, int W, int H, int ncomp, int hs, int vs,
                                  uint8_t* d_planes, uint8_t* d_pool, int pool_frames, const int32_t* d_slots, void* stream);
+/* Decode at 1/2, 1/4 or 1/8 size (added entries; tstar_abi_version() stays 3): the scaled decode of libjpeg-turbo, byte for byte what
+ * Pillow's Image.draft gives.  scale 1, 2, 4 or 8; scale 1 is the entry without _scaled, argument for argument.  The entropy
+ * stages, the coefficients and the tables are those of the full-size decode; only the inverse DCT and the chroma stage change.
+ * With k = 8 / scale, every luma block goes through a k x k inverse DCT on its low-frequency corner (jidctred.c).  4:2:0 chroma
+ * takes a 2k x 2k one, which makes its planes as large as the picture: nothing is upsampled.  4:2:2 chroma takes k x k and is
+ * upsampled horizontally, by the triangle filter for k >= 2 and by replication for k = 1.  The picture is ow x oh =
+ * ceil(W / scale) x ceil(H / scale).  NOT COVERED at a scale: 4:2:2 at scale 2 or 4 whose scaled chroma row, ceil(W * k / 16)
+ * samples, is at most 2 samples long (the libjpeg quirk that excludes W <= 4 at full size); such frames go to a general decoder.
+ * out4 = {ow, oh, bytes of the per-frame plane workspace at this scale, covered (1 / 0)}; TSTAR_ERR_ARG for a geometry the
+ * full-size entries refuse or another scale. */
+int tstar_jpeg_sizes_scaled(int W, int H, int ncomp, int hs, int vs, int scale, size_t* out4);
+/* tstar_jpeg_reconstruct_host / tstar_jpeg_reconstruct / tstar_jpeg_reconstruct_slots with rgb u8 [n,oh,ow,3] (d_pool u8
+ * [pool_frames,oh,ow,3]) and d_planes of n times the scaled plane-workspace bytes; alignment and argument rules as theirs.
+ * TSTAR_ERR_ARG, before anything is written or launched, for another scale or a geometry that is not covered at this scale. */
+int tstar_jpeg_reconstruct_scaled_host(const int16_t* coef, const uint16_t* quant, int n, int W, int H, int ncomp, int hs, int vs,
+                                       int scale, uint8_t* rgb, int threads);
+int tstar_jpeg_reconstruct_scaled(const int16_t* d_coef, const uint16_t* d_quant, int n, int W, int H, int ncomp, int hs, int vs,
+                                  int scale, uint8_t* d_planes, uint8_t* d_rgb, void* stream);
+int tstar_jpeg_reconstruct_slots_scaled(const int16_t* d_coef, const uint16_t* d_quant, int m, int W, int H, int ncomp, int hs, int vs,
+                                        int scale, uint8_t* d_planes, uint8_t* d_pool, int pool_frames, const int32_t* d_slots,
+                                        void* stream);
 /* Native-resolution RGB u8 [n,H,W,3] of NV12 frames (the keyframes pop_frames hands back, :379-380). */
 int tstar_nv12_to_rgb(const uint8_t* d_video, int N, int H, int W, const int32_t* d_frame_idx, int n,
                       uint8_t* d_out, void* stream);

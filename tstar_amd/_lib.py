@@ -103,6 +103,10 @@ SIGNATURES = {
     "tstar_jpeg_gather": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _sz, _i, _vp, _sz, _vp]),
     "tstar_jpeg_gather_host": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _sz, _i, _vp, _sz]),
     "tstar_jpeg_reconstruct_slots": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "tstar_jpeg_sizes_scaled": (_i, [_i, _i, _i, _i, _i, _i, _vp]),
+    "tstar_jpeg_reconstruct_scaled_host": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i]),
+    "tstar_jpeg_reconstruct_scaled": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "tstar_jpeg_reconstruct_slots_scaled": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "tstar_searcher_create": (_i, [C.POINTER(_vp), _i, C.c_double, C.c_double]),
     "tstar_searcher_destroy": (_i, [_vp]),
     "tstar_searcher_apply_grid": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),

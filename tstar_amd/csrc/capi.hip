@@ -194,6 +194,23 @@ int tstar_jpeg_reconstruct_slots(const int16_t* d_coef, const uint16_t* d_quant,
     return jpeg_reconstruct_slots_u8(d_coef, d_quant, m, g, d_planes, d_pool, pool_frames, d_slots, (hipStream_t)stream);
 }
 
+int tstar_jpeg_reconstruct_scaled(const int16_t* d_coef, const uint16_t* d_quant, int n, int W, int H, int ncomp, int hs, int vs,
+                                  int scale, uint8_t* d_planes, uint8_t* d_rgb, void* stream) {
+    if (scale == 1) return tstar_jpeg_reconstruct(d_coef, d_quant, n, W, H, ncomp, hs, vs, d_planes, d_rgb, stream);
+    TSTAR_REQUIRE(d_coef && d_quant && d_planes && d_rgb, "tstar_jpeg_reconstruct_scaled: null argument");
+    const JpegScaledGeom sg{JpegGeom{W, H, ncomp, hs, vs}, scale};
+    return jpeg_reconstruct_scaled_u8(d_coef, d_quant, n, sg, d_planes, d_rgb, (hipStream_t)stream);
+}
+
+int tstar_jpeg_reconstruct_slots_scaled(const int16_t* d_coef, const uint16_t* d_quant, int m, int W, int H, int ncomp, int hs, int vs,
+                                        int scale, uint8_t* d_planes, uint8_t* d_pool, int pool_frames, const int32_t* d_slots,
+                                        void* stream) {
+    if (scale == 1) return tstar_jpeg_reconstruct_slots(d_coef, d_quant, m, W, H, ncomp, hs, vs, d_planes, d_pool, pool_frames, d_slots, stream);
+    TSTAR_REQUIRE(d_coef && d_quant && d_planes && d_pool && d_slots, "tstar_jpeg_reconstruct_slots_scaled: null argument");
+    const JpegScaledGeom sg{JpegGeom{W, H, ncomp, hs, vs}, scale};
+    return jpeg_reconstruct_slots_scaled_u8(d_coef, d_quant, m, sg, d_planes, d_pool, pool_frames, d_slots, (hipStream_t)stream);
+}
+
 int tstar_jpeg_gather(const uint8_t* d_arena, size_t arena_bytes, const uint64_t* d_off, const uint32_t* d_len, const uint16_t* d_quant,
                       const void* d_frames, const void* d_segments, int n_entries, int n_arena_segments, const void* h_desc,
                       const void* d_desc, int m, size_t total_bytes, int n_segments, uint8_t* d_batch, size_t batch_bytes, void* stream) {

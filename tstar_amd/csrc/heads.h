@@ -88,6 +88,13 @@ int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const
 // outside the pool is skipped)
 int jpeg_reconstruct_slots_u8(const int16_t* coef, const uint16_t* quant, int m, const JpegGeom& g, uint8_t* planes, uint8_t* pool,
                               int pool_frames, const int32_t* slots, hipStream_t s);
+// both at 1/sg.scale size (scale 2, 4, 8; jpeg_host.h JpegScaledGeom): rgb u8 [n,oh,ow,3], pool u8 [pool_frames,oh,ow,3], planes
+// a workspace of n * sg.plane_bytes() bytes
+struct JpegScaledGeom;
+int jpeg_reconstruct_scaled_u8(const int16_t* coef, const uint16_t* quant, int n, const JpegScaledGeom& sg, uint8_t* planes, uint8_t* rgb,
+                               hipStream_t s);
+int jpeg_reconstruct_slots_scaled_u8(const int16_t* coef, const uint16_t* quant, int m, const JpegScaledGeom& sg, uint8_t* planes,
+                                     uint8_t* pool, int pool_frames, const int32_t* slots, hipStream_t s);
 namespace jpegres { struct Arena; struct Batch; struct GatherDesc; }
 // jpeg_resident.hip: arena frames -> the batch buffer of the entropy launchers (h_desc: what gather_args checked; d_desc: the
 // same words in device memory, like every pointer of a and b)

@@ -84,9 +84,108 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
     }
 }
 
+// The reduced forms for a decode at 1/2, 1/4, 1/8 size (jpeg_host.h JpegScaledGeom): K x K pixels per block from its low-frequency
+// corner, K = 4 or 2 (jpeg_math.h idct4 / idct2).  The same workgroup, loads and LDS layout as above.  The blocks are counted over
+// rows padded to bwp = bw rounded up to a multiple of 4 / K blocks (the lanes of the padding idle), so that the row pieces of 4 / K
+// neighbouring lanes always start a dword of the plane (rows of `pitch` bytes, a multiple of 4).
+//   load   as above, every row (a block is one 128-byte line whichever rows are read);
+//   pass 1 lane (block, c) transforms column c, for the columns the row pass reads, and writes K values back;
+//   pass 2 lane (block, r), r < K, transforms row r.  K = 4: the four pixels are one dword store.  K = 2: the lane of the even block
+//          takes the odd neighbour's two pixels from lane + 8 and stores the dword; a last block without a neighbour stores 2 bytes.
+// LDS accesses are dwords: banks are words mod 32 within each half of a wave.  A half is lanes (b, i) of 4 consecutive blocks,
+// i = 0 .. 7: for a fixed k (pass 1) 8b + i + 9k, for a fixed c (load / pass 2) 8b + 9i + c are distinct mod 32 over them.
+template <int K>
+__global__ __launch_bounds__(256) void jpeg_idct_reduced_kernel(const int16_t* __restrict__ coef, size_t coef_frame_stride,
+                                                                const uint16_t* __restrict__ quant, uint8_t* __restrict__ planes,
+                                                                size_t plane_frame_stride, int bw, int bh, int pitch, size_t total_blocks) {
+    static_assert(K == 4 || K == 2, "block sizes 8 and 1 have kernels of their own");
+    __shared__ uint32_t ws[kBlocksPerWg * kBlockPitch];
+    const int t = threadIdx.x, bl = t >> 3, i = t & 7;
+    const int bwp = (bw + 4 / K - 1) & ~(4 / K - 1);
+    const size_t vb = (size_t)blockIdx.x * kBlocksPerWg + bl, per = (size_t)bh * bwp;
+    const size_t f = vb / per;
+    const int by = (int)(vb % per / bwp), bx = (int)(vb % per % bwp);
+    const bool live = vb < total_blocks && bx < bw;
+    uint32_t* blk = ws + bl * kBlockPitch;
+    if (live) {
+        const uint4 cv = *reinterpret_cast<const uint4*>(coef + f * coef_frame_stride + ((size_t)by * bw + bx) * 64 + i * 8);
+        const uint4 qv = *reinterpret_cast<const uint4*>(quant + f * 192 + i * 8);
+        const uint32_t cw[4] = {cv.x, cv.y, cv.z, cv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
+        uint32_t* dst = blk + i * kRowPitch;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c0 = (int16_t)(cw[k] & 0xffff), c1 = (int16_t)(cw[k] >> 16);
+            dst[2 * k] = (uint32_t)(c0 * (int)(qw[k] & 0xffff));
+            dst[2 * k + 1] = (uint32_t)(c1 * (int)(qw[k] >> 16));
+        }
+    }
+    __syncthreads();
+    if (live && jpegmath::idct_reads(K, i)) {
+        uint32_t* col = blk + i;
+        uint32_t x[8];
+        int32_t o[K];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = col[k * kRowPitch];
+        if (K == 4) jpegmath::idct4(x, o, 12);
+        else jpegmath::idct2(x, o, 13);
+#pragma unroll
+        for (int k = 0; k < K; ++k) col[k * kRowPitch] = (uint32_t)o[k];
+    }
+    __syncthreads();
+    uint32_t px = 0;
+    const bool row = live && i < K;
+    if (row) {
+        const uint32_t* src = blk + i * kRowPitch;
+        uint32_t x[8];
+        int32_t o[K];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = src[k];
+        if (K == 4) jpegmath::idct4(x, o, 19);
+        else jpegmath::idct2(x, o, 20);
+#pragma unroll
+        for (int k = 0; k < K; ++k) px |= (uint32_t)jpegmath::range_limit(o[k]) << (8 * k);
+    }
+    uint8_t* dst = planes + f * plane_frame_stride + ((size_t)by * K + i) * pitch + (size_t)bx * K;
+    if (K == 4) {
+        if (row) *reinterpret_cast<uint32_t*>(dst) = px;
+    } else {
+        const uint32_t right = (uint32_t)__shfl_xor((int)px, 8);       // block bl ^ 1, the same row: every lane of the wave takes part
+        if (row && !(bx & 1)) {
+            if (bx + 1 < bw) *reinterpret_cast<uint32_t*>(dst) = px | (right << 16);
+            else *reinterpret_cast<uint16_t*>(dst) = (uint16_t)px;
+        }
+    }
+}
+
+// K = 1: the dequantised DC term alone, no LDS.  One lane per four neighbouring blocks of a plane row (rows of `pitch` bytes, a
+// multiple of 4) -> one dword store; the last lane of a row stores the 1 .. 3 bytes that are left.  The four 2-byte loads sit 128
+// bytes apart: a block costs the memory system its line whatever is read of it.
+__global__ __launch_bounds__(256) void jpeg_idct_dc_kernel(const int16_t* __restrict__ coef, size_t coef_frame_stride,
+                                                           const uint16_t* __restrict__ quant, uint8_t* __restrict__ planes,
+                                                           size_t plane_frame_stride, int bw, int bh, int pitch, size_t total_quads) {
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= total_quads) return;
+    const int bwq = (bw + 3) >> 2;
+    const size_t per = (size_t)bh * bwq, f = q / per;
+    const int by = (int)(q % per / bwq), bx = (int)(q % per % bwq) * 4;
+    const int nb = bw - bx < 4 ? bw - bx : 4;
+    const int16_t* src = coef + f * coef_frame_stride + ((size_t)by * bw + bx) * 64;
+    const int q0 = quant[f * 192];
+    uint32_t px = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < nb) px |= (uint32_t)jpegmath::range_limit(jpegmath::idct1((uint32_t)(src[j * 64] * q0))) << (8 * j);
+    uint8_t* dst = planes + f * plane_frame_stride + (size_t)by * pitch + bx;
+    if (nb == 4) *reinterpret_cast<uint32_t*>(dst) = px;
+    else
+        for (int j = 0; j < nb; ++j) dst[j] = (uint8_t)(px >> (8 * j));
+}
+
+// W, H: the size of the picture the stage writes; cw, ch: the true size of a chroma plane.  replicate: chroma of half width is read
+// as p[x >> 1] (the scaled decode's 4:2:2 at block size 1) instead of through the triangle filter.
 struct ColorArgs {
     size_t plane_frame_stride, off1, off2;       // byte offsets of the Cb / Cr planes inside a frame's planes
-    int pitch0, pitch1, W, H, ncomp, hs, vs, cw, ch;
+    int pitch0, pitch1, W, H, ncomp, hs, vs, cw, ch, replicate;
 };
 
 // R | G << 8 | B << 16 of pixel (x, y) of the frame whose planes start at fp.
@@ -94,8 +193,9 @@ __device__ inline uint32_t color_pixel(const uint8_t* __restrict__ fp, const Col
     const int yy = fp[(size_t)y * a.pitch0 + x];
     uint8_t t[3] = {(uint8_t)yy, (uint8_t)yy, (uint8_t)yy};
     if (a.ncomp == 3) {
-        const int cb = jpegmath::upsample_at(fp + a.off1, a.pitch1, a.cw, a.ch, a.hs, a.vs, x, y);
-        const int cr = jpegmath::upsample_at(fp + a.off2, a.pitch1, a.cw, a.ch, a.hs, a.vs, x, y);
+        const int hs = a.replicate ? 1 : a.hs, cx = a.replicate ? x >> 1 : x;
+        const int cb = jpegmath::upsample_at(fp + a.off1, a.pitch1, a.cw, a.ch, hs, a.vs, cx, y);
+        const int cr = jpegmath::upsample_at(fp + a.off2, a.pitch1, a.cw, a.ch, hs, a.vs, cx, y);
         jpegmath::ycc_to_rgb(yy, cb, cr, t);
     }
     return (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16);
@@ -197,6 +297,76 @@ static int jpeg_idct_planes(const int16_t* coef, const uint16_t* quant, int n, c
     a->pitch1 = g.ncomp == 3 ? g.bw(1) * 8 : 0;
     a->W = g.W; a->H = g.H; a->ncomp = g.ncomp; a->hs = g.hs; a->vs = g.vs;
     a->cw = g.cw(1); a->ch = g.ch(1);
+    a->replicate = 0;
+    return TSTAR_OK;
+}
+
+// the same at 1 / sg.scale size: every component through the kernel of its block size
+static int jpeg_idct_scaled_planes(const int16_t* coef, const uint16_t* quant, int n, const JpegScaledGeom& sg, uint8_t* planes, ColorArgs* a,
+                                   hipStream_t s, const char* fn) {
+    const JpegGeom& g = sg.g;
+    TSTAR_REQUIRE(n > 0 && sg.scale > 1 && sg.covered(),
+                  std::string(fn) + ": n <= 0, a scale other than 2, 4, 8 or a geometry that is not covered at this scale");
+    TSTAR_REQUIRE((uintptr_t)coef % 16 == 0 && (uintptr_t)quant % 16 == 0 && (uintptr_t)planes % 8 == 0,
+                  std::string(fn) + ": coefficient / table buffers need 16-byte, the plane workspace 8-byte alignment");
+    const size_t blocks = g.blocks(), stride = sg.plane_bytes();
+    TSTAR_REQUIRE((blocks + 3 * (size_t)g.bh(0)) * (size_t)n / kBlocksPerWg + 1 < 0x7fffffffull &&
+                      (size_t)n * sg.ow() * sg.oh() / 1024 + 1 < 0x7fffffffull,
+                  std::string(fn) + ": chunk too large for one launch");
+    for (int c = 0; c < g.ncomp; ++c) {
+        const int bw = g.bw(c), bh = g.bh(c), kc = sg.kc(c), pitch = sg.pitch(c);
+        const int16_t* cc = coef + g.block_offset(c) * 64;
+        const uint16_t* qc = quant + 64 * c;
+        uint8_t* pc = planes + sg.plane_offset(c);
+        if (kc == 8) {                                   // 4:2:0 chroma at scale 2: the full transform (pitch = bw * 8)
+            const size_t total = (size_t)bw * bh * n;
+            hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((total + kBlocksPerWg - 1) / kBlocksPerWg)), dim3(256), 0, s, cc,
+                               blocks * 64, qc, pc, stride, bw * bh, bw, total);
+        } else if (kc == 1) {
+            const size_t total = (size_t)((bw + 3) / 4) * bh * n;
+            hipLaunchKernelGGL(jpeg_idct_dc_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cc, blocks * 64, qc, pc, stride,
+                               bw, bh, pitch, total);
+        } else {
+            const size_t total = (size_t)(kc == 4 ? bw : (bw + 1) & ~1) * bh * n;
+            const dim3 grid((unsigned)((total + kBlocksPerWg - 1) / kBlocksPerWg));
+            if (kc == 4)
+                hipLaunchKernelGGL(jpeg_idct_reduced_kernel<4>, grid, dim3(256), 0, s, cc, blocks * 64, qc, pc, stride, bw, bh, pitch, total);
+            else
+                hipLaunchKernelGGL(jpeg_idct_reduced_kernel<2>, grid, dim3(256), 0, s, cc, blocks * 64, qc, pc, stride, bw, bh, pitch, total);
+        }
+        TSTAR_HIP_CHECK(hipGetLastError());
+    }
+    const int mode = sg.chroma_mode();
+    a->plane_frame_stride = stride;
+    a->off1 = g.ncomp == 3 ? sg.plane_offset(1) : 0;
+    a->off2 = g.ncomp == 3 ? sg.plane_offset(2) : 0;
+    a->pitch0 = sg.pitch(0);
+    a->pitch1 = g.ncomp == 3 ? sg.pitch(1) : 0;
+    a->W = sg.ow(); a->H = sg.oh(); a->ncomp = g.ncomp;
+    a->hs = mode == JPEG_CHROMA_FULL ? 1 : 2; a->vs = 1;
+    a->cw = sg.cw(1); a->ch = sg.ch(1);
+    a->replicate = mode == JPEG_CHROMA_REPLICATE_H2V1;
+    return TSTAR_OK;
+}
+
+// the colour stage over n consecutive frames / over m frames into named slots of a pool
+static int jpeg_color_frames(const uint8_t* planes, const ColorArgs& a, int n, uint8_t* rgb, hipStream_t s) {
+    const size_t total_px = (size_t)n * a.W * a.H;
+    const dim3 grid((unsigned)((total_px + 1023) / 1024));
+    if ((uintptr_t)rgb % 4 == 0) hipLaunchKernelGGL(jpeg_color_kernel<true>, grid, dim3(256), 0, s, planes, a, rgb, total_px);
+    else hipLaunchKernelGGL(jpeg_color_kernel<false>, grid, dim3(256), 0, s, planes, a, rgb, total_px);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    return TSTAR_OK;
+}
+
+static int jpeg_color_slots(const uint8_t* planes, const ColorArgs& a, int m, uint8_t* pool, int pool_frames, const int32_t* slots,
+                            hipStream_t s) {
+    const size_t per = (size_t)a.W * a.H;
+    const dim3 grid((unsigned)((per + 1023) / 1024), (unsigned)m);
+    if ((uintptr_t)pool % 4 == 0 && per * 3 % 4 == 0)
+        hipLaunchKernelGGL(jpeg_color_slots_kernel<true>, grid, dim3(256), 0, s, planes, a, pool, pool_frames, slots);
+    else hipLaunchKernelGGL(jpeg_color_slots_kernel<false>, grid, dim3(256), 0, s, planes, a, pool, pool_frames, slots);
+    TSTAR_HIP_CHECK(hipGetLastError());
     return TSTAR_OK;
 }
 
@@ -204,12 +374,14 @@ int jpeg_reconstruct_u8(const int16_t* coef, const uint16_t* quant, int n, const
                         hipStream_t s) {
     ColorArgs a;
     if (const int rc = jpeg_idct_planes(coef, quant, n, g, planes, &a, s, "jpeg_reconstruct_u8")) return rc;
-    const size_t total_px = (size_t)n * g.W * g.H;
-    const dim3 grid((unsigned)((total_px + 1023) / 1024));
-    if ((uintptr_t)rgb % 4 == 0) hipLaunchKernelGGL(jpeg_color_kernel<true>, grid, dim3(256), 0, s, planes, a, rgb, total_px);
-    else hipLaunchKernelGGL(jpeg_color_kernel<false>, grid, dim3(256), 0, s, planes, a, rgb, total_px);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    return TSTAR_OK;
+    return jpeg_color_frames(planes, a, n, rgb, s);
+}
+
+int jpeg_reconstruct_scaled_u8(const int16_t* coef, const uint16_t* quant, int n, const JpegScaledGeom& sg, uint8_t* planes, uint8_t* rgb,
+                               hipStream_t s) {
+    ColorArgs a;
+    if (const int rc = jpeg_idct_scaled_planes(coef, quant, n, sg, planes, &a, s, "jpeg_reconstruct_scaled_u8")) return rc;
+    return jpeg_color_frames(planes, a, n, rgb, s);
 }
 
 int jpeg_reconstruct_slots_u8(const int16_t* coef, const uint16_t* quant, int m, const JpegGeom& g, uint8_t* planes, uint8_t* pool,
@@ -218,13 +390,16 @@ int jpeg_reconstruct_slots_u8(const int16_t* coef, const uint16_t* quant, int m,
     TSTAR_REQUIRE((uintptr_t)slots % 4 == 0, "jpeg_reconstruct_slots_u8: misaligned slot list");
     ColorArgs a;
     if (const int rc = jpeg_idct_planes(coef, quant, m, g, planes, &a, s, "jpeg_reconstruct_slots_u8")) return rc;
-    const size_t per = (size_t)g.W * g.H;
-    const dim3 grid((unsigned)((per + 1023) / 1024), (unsigned)m);
-    if ((uintptr_t)pool % 4 == 0 && per * 3 % 4 == 0)
-        hipLaunchKernelGGL(jpeg_color_slots_kernel<true>, grid, dim3(256), 0, s, planes, a, pool, pool_frames, slots);
-    else hipLaunchKernelGGL(jpeg_color_slots_kernel<false>, grid, dim3(256), 0, s, planes, a, pool, pool_frames, slots);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    return TSTAR_OK;
+    return jpeg_color_slots(planes, a, m, pool, pool_frames, slots, s);
+}
+
+int jpeg_reconstruct_slots_scaled_u8(const int16_t* coef, const uint16_t* quant, int m, const JpegScaledGeom& sg, uint8_t* planes,
+                                     uint8_t* pool, int pool_frames, const int32_t* slots, hipStream_t s) {
+    TSTAR_REQUIRE(pool_frames > 0 && m <= 65535, "jpeg_reconstruct_slots_scaled_u8: pool_frames <= 0 or more than 65535 frames");
+    TSTAR_REQUIRE((uintptr_t)slots % 4 == 0, "jpeg_reconstruct_slots_scaled_u8: misaligned slot list");
+    ColorArgs a;
+    if (const int rc = jpeg_idct_scaled_planes(coef, quant, m, sg, planes, &a, s, "jpeg_reconstruct_slots_scaled_u8")) return rc;
+    return jpeg_color_slots(planes, a, m, pool, pool_frames, slots, s);
 }
 
 }  // namespace tstar

@@ -725,37 +725,57 @@ bool jpeg_entropy_split_host(const uint8_t* bytes, size_t total_bytes, const Jpe
     return true;
 }
 
+namespace {
+
+// dequantise + inverse DCT of output size k x k (8, 4, 2, 1) + range limit of one block -> k rows of k pixels at dst
+void idct_block(const int16_t* b, const uint16_t* q, int k, uint8_t* dst, int pitch) {
+    using namespace jpegmath;
+    if (k == 1) {
+        dst[0] = range_limit(idct1((uint32_t)((int32_t)b[0] * (int32_t)q[0])));
+        return;
+    }
+    const int shift1 = k == 8 ? 11 : (k == 4 ? 12 : 13), shift2 = shift1 + 7;
+    const auto pass = [k](const uint32_t* x, int32_t* o, int shift) {
+        if (k == 8) idct8(x, o, shift);
+        else if (k == 4) idct4(x, o, shift);
+        else idct2(x, o, shift);
+    };
+    int32_t ws[64];
+    for (int col = 0; col < 8; ++col) {
+        if (!idct_reads(k, col)) continue;
+        uint32_t x[8];
+        int32_t o[8];
+        for (int i = 0; i < 8; ++i) x[i] = (uint32_t)((int32_t)b[8 * i + col] * (int32_t)q[8 * i + col]);
+        pass(x, o, shift1);
+        for (int i = 0; i < k; ++i) ws[8 * i + col] = o[i];
+    }
+    for (int row = 0; row < k; ++row) {
+        uint32_t x[8];
+        int32_t o[8];
+        for (int i = 0; i < 8; ++i) x[i] = idct_reads(k, i) ? (uint32_t)ws[8 * row + i] : 0u;
+        pass(x, o, shift2);
+        for (int i = 0; i < k; ++i) dst[(size_t)row * pitch + i] = range_limit(o[i]);
+    }
+}
+
+// every block of a component -> its plane (whole blocks of k x k pixels, rows of `pitch` bytes)
+void idct_plane(const int16_t* blocks, const uint16_t* q, int bw, int bh, int k, uint8_t* out, int pitch) {
+    for (int by = 0; by < bh; ++by)
+        for (int bx = 0; bx < bw; ++bx)
+            idct_block(blocks + ((size_t)by * bw + bx) * 64, q, k, out + (size_t)by * k * pitch + bx * k, pitch);
+}
+
+}  // namespace
+
 void jpeg_reconstruct_host(const JpegGeom& g, const int16_t* coef, const uint16_t* quant, uint8_t* scratch, uint8_t* rgb) {
     using namespace jpegmath;
     const uint8_t* plane[3] = {nullptr, nullptr, nullptr};
     int pitch[3] = {0, 0, 0};
     for (int c = 0; c < g.ncomp; ++c) {
-        const int bw = g.bw(c), bh = g.bh(c);
         uint8_t* out = scratch + g.block_offset(c) * 64;
         plane[c] = out;
-        pitch[c] = bw * 8;
-        const uint16_t* q = quant + 64 * c;
-        const int16_t* blocks = coef + g.block_offset(c) * 64;
-        for (int by = 0; by < bh; ++by)
-            for (int bx = 0; bx < bw; ++bx) {
-                const int16_t* b = blocks + ((size_t)by * bw + bx) * 64;
-                int32_t ws[64];
-                for (int col = 0; col < 8; ++col) {
-                    uint32_t x[8];
-                    int32_t o[8];
-                    for (int k = 0; k < 8; ++k) x[k] = (uint32_t)((int32_t)b[8 * k + col] * (int32_t)q[8 * k + col]);
-                    idct8(x, o, 11);
-                    for (int k = 0; k < 8; ++k) ws[8 * k + col] = o[k];
-                }
-                for (int row = 0; row < 8; ++row) {
-                    uint32_t x[8];
-                    int32_t o[8];
-                    for (int k = 0; k < 8; ++k) x[k] = (uint32_t)ws[8 * row + k];
-                    idct8(x, o, 18);
-                    uint8_t* dst = out + (size_t)(by * 8 + row) * pitch[c] + bx * 8;
-                    for (int k = 0; k < 8; ++k) dst[k] = range_limit(o[k]);
-                }
-            }
+        pitch[c] = g.bw(c) * 8;
+        idct_plane(coef + g.block_offset(c) * 64, quant + 64 * c, g.bw(c), g.bh(c), 8, out, pitch[c]);
     }
     for (int y = 0; y < g.H; ++y) {
         uint8_t* dst = rgb + (size_t)y * g.W * 3;
@@ -767,6 +787,31 @@ void jpeg_reconstruct_host(const JpegGeom& g, const int16_t* coef, const uint16_
         for (int x = 0; x < g.W; ++x) {
             const int cb = upsample_at(plane[1], pitch[1], g.cw(1), g.ch(1), g.hs, g.vs, x, y);
             const int cr = upsample_at(plane[2], pitch[2], g.cw(2), g.ch(2), g.hs, g.vs, x, y);
+            ycc_to_rgb(yr[x], cb, cr, dst + 3 * x);
+        }
+    }
+}
+
+void jpeg_reconstruct_scaled_host(const JpegScaledGeom& sg, const int16_t* coef, const uint16_t* quant, uint8_t* scratch, uint8_t* rgb) {
+    using namespace jpegmath;
+    const JpegGeom& g = sg.g;
+    const uint8_t* plane[3] = {nullptr, nullptr, nullptr};
+    for (int c = 0; c < g.ncomp; ++c) {
+        uint8_t* out = scratch + sg.plane_offset(c);
+        plane[c] = out;
+        idct_plane(coef + g.block_offset(c) * 64, quant + 64 * c, g.bw(c), g.bh(c), sg.kc(c), out, sg.pitch(c));
+    }
+    const int ow = sg.ow(), oh = sg.oh(), mode = sg.chroma_mode();
+    for (int y = 0; y < oh; ++y) {
+        uint8_t* dst = rgb + (size_t)y * ow * 3;
+        const uint8_t* yr = plane[0] + (size_t)y * sg.pitch(0);
+        if (g.ncomp == 1) {
+            for (int x = 0; x < ow; ++x) dst[3 * x] = dst[3 * x + 1] = dst[3 * x + 2] = yr[x];
+            continue;
+        }
+        for (int x = 0; x < ow; ++x) {
+            const int cb = chroma_at(plane[1], sg.pitch(1), sg.cw(1), sg.ch(1), mode, x, y);
+            const int cr = chroma_at(plane[2], sg.pitch(2), sg.cw(2), sg.ch(2), mode, x, y);
             ycc_to_rgb(yr[x], cb, cr, dst + 3 * x);
         }
     }
@@ -837,6 +882,19 @@ int tstar_jpeg_sizes(int W, int H, int ncomp, int hs, int vs, size_t* out2) {
 }
 
 int tstar_jpeg_threads(int asked) { return jpeg_thread_allowance(asked); }
+
+int tstar_jpeg_sizes_scaled(int W, int H, int ncomp, int hs, int vs, int scale, size_t* out4) {
+    const JpegScaledGeom sg{JpegGeom{W, H, ncomp, hs, vs}, scale};
+    if (!out4 || !sg.scale_ok() || !sg.g.valid()) {
+        set_error("tstar_jpeg_sizes_scaled: null argument, unsupported geometry or a scale other than 1, 2, 4, 8");
+        return 1;
+    }
+    out4[0] = (size_t)sg.ow();
+    out4[1] = (size_t)sg.oh();
+    out4[2] = scale == 1 ? sg.g.plane_bytes() : sg.plane_bytes();
+    out4[3] = sg.covered() ? 1 : 0;
+    return 0;
+}
 
 int tstar_jpeg_entropy_batch(const uint8_t* const* datas, const size_t* lens, int n, int W, int H, int ncomp, int hs, int vs,
                              int16_t* coef, uint16_t* quant, int threads, int32_t* status) {
@@ -934,6 +992,23 @@ int tstar_jpeg_reconstruct_host(const int16_t* coef, const uint16_t* quant, int 
     parallel_frames(n, threads, [&](int i) {
         std::vector<uint8_t> scratch(g.plane_bytes());
         jpeg_reconstruct_host(g, coef + per * (size_t)i, quant + 192 * (size_t)i, scratch.data(), rgb + frame * (size_t)i);
+    });
+    return 0;
+}
+
+int tstar_jpeg_reconstruct_scaled_host(const int16_t* coef, const uint16_t* quant, int n, int W, int H, int ncomp, int hs, int vs,
+                                       int scale, uint8_t* rgb, int threads) {
+    if (scale == 1) return tstar_jpeg_reconstruct_host(coef, quant, n, W, H, ncomp, hs, vs, rgb, threads);
+    const JpegScaledGeom sg{JpegGeom{W, H, ncomp, hs, vs}, scale};
+    if (!coef || !quant || !rgb || n <= 0 || !sg.covered()) {
+        set_error("tstar_jpeg_reconstruct_scaled_host: null argument, n <= 0, a scale other than 1, 2, 4, 8 or a geometry that is not "
+                  "covered at this scale");
+        return 1;
+    }
+    const size_t per = sg.g.blocks() * 64, frame = (size_t)sg.ow() * sg.oh() * 3;
+    parallel_frames(n, threads, [&](int i) {
+        std::vector<uint8_t> scratch(sg.plane_bytes());
+        jpeg_reconstruct_scaled_host(sg, coef + per * (size_t)i, quant + 192 * (size_t)i, scratch.data(), rgb + frame * (size_t)i);
     });
     return 0;
 }

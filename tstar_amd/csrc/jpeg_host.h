@@ -50,6 +50,50 @@ struct JpegGeom {
     }
 };
 
+// How the colour stage of a scaled decode reads chroma
+enum {
+    JPEG_CHROMA_FULL = 0,            // the chroma planes are as large as the picture (grayscale, 4:4:4, scaled 4:2:0)
+    JPEG_CHROMA_FANCY_H2V1 = 1,      // half width, libjpeg's triangle filter (upsample_at with hs 2, vs 1)
+    JPEG_CHROMA_REPLICATE_H2V1 = 2,  // half width, every sample twice
+};
+
+// A decode of geometry g at 1/scale size (scale 1, 2, 4, 8), as libjpeg-turbo does it: every block of component c goes through
+// an inverse DCT of output size kc(c) x kc(c) on its low-frequency corner.  Luma takes k = 8 / scale.  4:2:0 chroma takes 2k
+// (libjpeg scales it up in the IDCT instead of upsampling: at scale 2 that is the full 8 x 8 transform), so its plane is as
+// large as the picture and nothing is upsampled; 4:2:2 chroma stays at k (the vertical condition fails) and is upsampled
+// horizontally, by the triangle filter for k >= 2 and by replication for k = 1, where libjpeg turns fancy upsampling off.
+// Planes: component after component, whole blocks, rows of pitch(c) bytes (a multiple of 4), each plane a multiple of 8 bytes.
+// Scale 1 is the full-size decode: its entries delegate to JpegGeom's own code, and kc / chroma_mode below describe scales 2, 4, 8.
+struct JpegScaledGeom {
+    JpegGeom g;
+    int scale;
+    bool scale_ok() const { return scale == 1 || scale == 2 || scale == 4 || scale == 8; }
+    int k() const { return 8 / scale; }
+    int kc(int c) const { return (c > 0 && g.hs == 2 && g.vs == 2 && scale > 1) ? 2 * k() : k(); }
+    int ow() const { return (g.W + scale - 1) / scale; }
+    int oh() const { return (g.H + scale - 1) / scale; }
+    // true sample size of component c at this scale: ceil(W * h_c * kc / (hmax * 8))
+    int cw(int c) const { return c == 0 ? ow() : (g.W * kc(c) + 8 * g.hs - 1) / (8 * g.hs); }
+    int ch(int c) const { return c == 0 ? oh() : (g.H * kc(c) + 8 * g.vs - 1) / (8 * g.vs); }
+    int pitch(int c) const { return (g.bw(c) * kc(c) + 3) & ~3; }
+    size_t plane_size(int c) const { return ((size_t)pitch(c) * g.bh(c) * kc(c) + 7) & ~(size_t)7; }
+    size_t plane_offset(int c) const {
+        size_t b = 0;
+        for (int j = 0; j < c; ++j) b += plane_size(j);
+        return b;
+    }
+    size_t plane_bytes() const { return plane_offset(g.ncomp); }
+    int chroma_mode() const {
+        if (g.ncomp == 1 || g.hs == 1 || kc(1) != k()) return JPEG_CHROMA_FULL;
+        return k() >= 2 ? JPEG_CHROMA_FANCY_H2V1 : JPEG_CHROMA_REPLICATE_H2V1;
+    }
+    // Not covered at this scale (the frame goes to the general decoder): the triangle filter over a chroma row of at most 2
+    // samples, the libjpeg quirk JpegGeom::valid() excludes at full size.
+    bool covered() const {
+        return scale_ok() && g.valid() && (scale == 1 || chroma_mode() != JPEG_CHROMA_FANCY_H2V1 || cw(1) > 2);
+    }
+};
+
 // Header walk only.  JPEG_OK: *g filled.  JPEG_UNCOVERED: g->W, g->H filled when a frame header was seen (else 0).
 int jpeg_probe(const uint8_t* data, size_t len, JpegGeom* g, char* err, size_t errlen);
 
@@ -99,6 +143,9 @@ bool jpeg_entropy_split_host(const uint8_t* bytes, size_t total_bytes, const Jpe
 
 // Scalar reference of the device stage: coefficients + tables -> RGB u8 [H][W][3].  scratch: g.plane_bytes() bytes.
 void jpeg_reconstruct_host(const JpegGeom& g, const int16_t* coef, const uint16_t* quant, uint8_t* scratch, uint8_t* rgb);
+// The same at 1/scale size (scale 2, 4, 8; sg.covered()): RGB u8 [sg.oh()][sg.ow()][3], byte-equal to libjpeg-turbo's scaled
+// decode (Pillow's Image.draft).  scratch: sg.plane_bytes() bytes.
+void jpeg_reconstruct_scaled_host(const JpegScaledGeom& sg, const int16_t* coef, const uint16_t* quant, uint8_t* scratch, uint8_t* rgb);
 
 // threads a batch may use: min(16, CPUs this process is allowed to run on); `asked` > 0 lowers it further
 int jpeg_thread_allowance(int asked);

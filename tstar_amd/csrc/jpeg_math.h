@@ -40,6 +40,34 @@ TSTAR_JHD void idct8(const uint32_t x[8], int32_t out[8], int shift) {
     out[3] = descale(t13 + t0, shift); out[4] = descale(t13 - t0, shift);
 }
 
+// The reduced-size passes of a decode at 1/2, 1/4 and 1/8 scale (libjpeg's jidctred.c, constants x 2^13): the same 1-D routine
+// over the columns (pass 1), then over the rows (pass 2) of the low-frequency corner of the block, x = the eight values of the
+// column / row.  Unread elements may hold anything.
+// 4 outputs; x[4] is never read, and pass 1 leaves column 4 out.  shift 12 after the column pass, 19 after the row pass.
+TSTAR_JHD void idct4(const uint32_t x[8], int32_t out[4], int shift) {
+    const uint32_t t0 = x[0] << 14;
+    const uint32_t t2 = x[2] * 15137u - x[6] * 6270u;
+    const uint32_t t10 = t0 + t2, t12 = t0 - t2;
+    const uint32_t a = x[7] * (uint32_t)-1730 + x[5] * 11893u + x[3] * (uint32_t)-17799 + x[1] * 8697u;
+    const uint32_t b = x[7] * (uint32_t)-4176 + x[5] * (uint32_t)-4926 + x[3] * 7373u + x[1] * 20995u;
+    out[0] = descale(t10 + b, shift); out[3] = descale(t10 - b, shift);
+    out[1] = descale(t12 + a, shift); out[2] = descale(t12 - a, shift);
+}
+
+// 2 outputs; reads x[0], x[1], x[3], x[5], x[7], and pass 1 runs over those columns only.  shift 13 after the column pass, 20
+// after the row pass.
+TSTAR_JHD void idct2(const uint32_t x[8], int32_t out[2], int shift) {
+    const uint32_t t10 = x[0] << 15;
+    const uint32_t t = x[7] * (uint32_t)-5906 + x[5] * 6967u + x[3] * (uint32_t)-10426 + x[1] * 29692u;
+    out[0] = descale(t10 + t, shift); out[1] = descale(t10 - t, shift);
+}
+
+// 1 output: the dequantised DC term alone
+TSTAR_JHD int32_t idct1(uint32_t dc) { return descale(dc, 3); }
+
+// does a pass of output size k (8, 4, 2) read element / column i of the block?
+TSTAR_JHD bool idct_reads(int k, int i) { return k == 8 || (k == 4 ? i != 4 : (i < 2 || (i & 1))); }
+
 TSTAR_JHD int clamp255(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 TSTAR_JHD uint8_t range_limit(int32_t v) { return (uint8_t)clamp255(v + 128); }
 TSTAR_JHD int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -60,6 +88,13 @@ TSTAR_JHD int upsample_at(const uint8_t* p, int pitch, int cw, int ch, int hs, i
     const uint8_t* r1 = p + (size_t)jn * pitch;
     const int a = 3 * r0[i] + r1[i], b = 3 * r0[in] + r1[in];
     return (3 * a + b + ((x & 1) ? 7 : 8)) >> 4;
+}
+
+// Chroma sample for output pixel (x, y) of a scaled decode (jpeg_host.h JpegScaledGeom): mode 0 the plane is as large as the
+// picture, 1 half width through the triangle filter above, 2 half width, every sample twice.
+TSTAR_JHD int chroma_at(const uint8_t* p, int pitch, int cw, int ch, int mode, int x, int y) {
+    if (mode == 2) return p[(size_t)y * pitch + (x >> 1)];
+    return upsample_at(p, pitch, cw, ch, mode == 1 ? 2 : 1, 1, x, y);
 }
 
 // F(x) = int(x * 65536 + 0.5)

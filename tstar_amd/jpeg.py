@@ -14,6 +14,10 @@ coefficients, and a frame the device does not vouch for is run through the host 
 A frame without restart markers is one segment; the device mode cuts segments of at least TSTAR_JPEG_SPLIT_BYTES bytes into
 sub-sequences of SPLIT_SUB_BYTES bytes, one lane each (tstar_jpeg_entropy_split_device: self-synchronising parallel Huffman
 decoding), and ``FrameStore.entropy_split_stats`` says how many segments went that way.
+
+``scale`` 2, 4 or 8 (``open_video(..., jpeg_scale=)``, TSTAR_JPEG_SCALE) decodes every frame at 1/2, 1/4 or 1/8 size, byte for byte
+Pillow's ``Image.draft``: the entropy stages are the same, the reconstruction runs reduced inverse DCTs
+(tstar_jpeg_reconstruct_scaled, tstar_jpeg_reconstruct_scaled_host), and frames that go to Pillow are drafted to the same scale.
 """
 from __future__ import annotations
 
@@ -286,6 +290,29 @@ def _sizes(geom):
     return int(out[0]), int(out[1])
 
 
+SCALES = (1, 2, 4, 8)
+
+
+def scale_mode(jpeg_scale: Optional[int] = None) -> int:
+    """The keyword when given, else TSTAR_JPEG_SCALE, else 1: the factor 1, 2, 4 or 8 a JPEG source is decoded down by."""
+    v = jpeg_scale if jpeg_scale is not None else (os.environ.get("TSTAR_JPEG_SCALE") or 1)
+    try:
+        s = int(v) if not isinstance(v, (bool, float)) else 0
+    except (TypeError, ValueError):
+        s = 0
+    if s not in SCALES:
+        raise ValueError(f"jpeg_scale={v!r}: expected one of {SCALES}")
+    return s
+
+
+def scaled_sizes(geom, scale: int):
+    """(ow, oh, bytes of the per-frame plane workspace, covered) of a decode of ``geom`` at 1/scale size (tstar_jpeg_sizes_scaled)."""
+    from . import _lib
+    out = (C.c_size_t * 4)()
+    _lib.check(_lib.load().tstar_jpeg_sizes_scaled(*geom, scale, out), "tstar_jpeg_sizes_scaled")
+    return int(out[0]), int(out[1]), int(out[2]), bool(out[3])
+
+
 def entropy_batch(datas: Sequence[bytes], geom, coef: np.ndarray, quant: np.ndarray, threads: int = 0):
     """Entropy-decode ``datas`` into coef int16 [>= n, blocks * 64] / quant uint16 [>= n, 192] -> (status int32 [n], message)."""
     from . import _lib
@@ -551,14 +578,29 @@ class DeviceBatch:
                      stream, sub_bytes)
 
 
-def _pillow_rgb(data: bytes, label: str) -> np.ndarray:
+def _pillow_rgb(data: bytes, label: str, scale: int = 1, check_size=None) -> np.ndarray:
+    """Pillow's pixels of one JPEG, at 1/scale size through ``Image.draft`` (libjpeg's scaled decode).  ``check_size(w, h)`` sees the
+    file's own size before anything is decoded."""
     import io
     from PIL import Image
     try:
         with Image.open(io.BytesIO(data)) as im:
+            w, h = im.size
+            if check_size is not None:
+                check_size(w, h)
+            if scale > 1:
+                im.draft(im.mode, (w // scale, h // scale))
+                if im.size != (-(-w // scale), -(-h // scale)):
+                    raise ValueError(f"Pillow decodes it at {im.size[0]}x{im.size[1]}, not at 1/{scale} of {w}x{h}")
             return np.array(im.convert("RGB"), dtype=np.uint8)
+    except _SizeError:
+        raise
     except Exception as e:
         raise ValueError(f"Cannot open video file: {label} ({e})")
+
+
+class _SizeError(ValueError):
+    """A frame whose size the open refuses: the message names the file already."""
 
 
 def decode_host(datas: Sequence[bytes], threads: int = 0) -> np.ndarray:
@@ -593,12 +635,14 @@ class JpegOpen:
     """What an open of a JPEG source knows before its first chunk, and what every mode does with ONE frame: ``raw`` is the raw frame
     behind every frame k the open decodes, the first of them fixes the picture size (W, H), the first one the kernels cover fixes the
     geometry.  The three counter dicts of the store live here; ``seconds`` [len(raw)] says how many logical seconds frame k serves
-    (default one each), and every count is in seconds."""
+    (default one each), and every count is in seconds.  ``scale``: every frame is decoded at 1/scale size, ow x oh = ceil(W / scale) x
+    ceil(H / scale) (the kernels' reduced inverse DCTs, Pillow's ``draft`` for the frames that go to Pillow); W, H and every message
+    keep speaking of the file's own size."""
 
-    def __init__(self, src: JpegFrames, raw: Sequence[int], device, seconds: Optional[np.ndarray] = None):
-        self.src, self.raw, self.device = src, raw, device
+    def __init__(self, src: JpegFrames, raw: Sequence[int], device, seconds: Optional[np.ndarray] = None, scale: int = 1):
+        self.src, self.raw, self.device, self.scale = src, raw, device, int(scale)
         self.first = src.read(raw[0])
-        self.W = self.H = self.geom = None
+        self.W = self.H = self.ow = self.oh = self.geom = None
         self.blocks = self.plane_bytes = 0
         self.seconds = np.ones(len(raw), dtype=np.int64) if seconds is None else seconds
         self.reconstructs = "host" if str(device).startswith("cpu") else "device"       # who turns coefficients into pixels
@@ -608,6 +652,7 @@ class JpegOpen:
 
     def attach(self, store):
         store.decode_stats, store.entropy_stats, store.entropy_split_stats = self.stats, self.estats, self.sstats
+        store.jpeg_scale, store.source_size = self.scale, (self.W, self.H)
         return store
 
     def count(self, frames, decode: Optional[str] = None, entropy: Optional[str] = None) -> None:
@@ -624,30 +669,38 @@ class JpegOpen:
         return ValueError(f"Cannot open video file: {self.src.label(self.raw[k])} ({why})")
 
     def check_size(self, k: int, w: int, h: int) -> None:
-        """The first frame's size is the picture size; ValueError for a later frame of another."""
+        """The first frame's size is the picture size; ValueError for a later frame of another, or for a picture with a side shorter than
+        the scale (Pillow's draft, the yardstick, cannot be held to the scale there)."""
         if self.W is None:
+            if min(w, h) < self.scale:
+                raise _SizeError(f"Cannot open video file: {self.src.label(self.raw[k])} is {w}x{h}: jpeg_scale={self.scale} needs a picture "
+                                 f"of at least {self.scale}x{self.scale}")
             self.W, self.H = int(w), int(h)
+            self.ow, self.oh = -(-self.W // self.scale), -(-self.H // self.scale)
         elif (w, h) != (self.W, self.H):
-            raise ValueError(f"Cannot open video file: {self.src.label(self.raw[k])} is {w}x{h}, the first frame is {self.W}x{self.H}")
+            raise _SizeError(f"Cannot open video file: {self.src.label(self.raw[k])} is {w}x{h}, the first frame is {self.W}x{self.H}")
 
     def pillow(self, k: int, data: bytes) -> np.ndarray:
-        """Frame k as Pillow decodes it (exact, on the host), size-checked and counted."""
-        arr = _pillow_rgb(data, self.src.label(self.raw[k]))
-        self.check_size(k, arr.shape[1], arr.shape[0])
+        """Frame k as Pillow decodes it at the open's scale (exact, on the host), size-checked and counted."""
+        arr = _pillow_rgb(data, self.src.label(self.raw[k]), self.scale, lambda w, h: self.check_size(k, w, h))
         self.count([k], "pillow")
         return arr
 
     def prelude(self, k: int, data: bytes) -> Optional[np.ndarray]:
-        """One step while no covered frame has been seen: frame k is probed alone -> None when the kernels cover it (its geometry is
-        the open's from here on), else Pillow's pixels; ValueError when it is broken or of another size."""
+        """One step while no covered frame has been seen: frame k is probed alone -> None when the kernels cover it at the open's scale
+        (its geometry is the open's from here on), else Pillow's pixels; ValueError when it is broken or of another size."""
         rc, info, msg = probe(data)
         if rc == MALFORMED:
             raise self.error(k, msg)
         if rc != OK:
             return self.pillow(k, data)
         self.check_size(k, info[0], info[1])
-        self.geom = info
-        self.blocks, self.plane_bytes = _sizes(info)
+        blocks, plane_bytes = _sizes(info)
+        if self.scale > 1:
+            _, _, plane_bytes, covered = scaled_sizes(info, self.scale)
+            if not covered:                               # 4:2:2 whose scaled chroma rows are at most 2 samples long
+                return self.pillow(k, data)
+        self.geom, self.blocks, self.plane_bytes = info, blocks, plane_bytes
         return None
 
     def host_verdict(self, k: int, data: bytes):
@@ -668,15 +721,35 @@ class JpegOpen:
             self.check_size(k, info[0], info[1])
         return self.pillow(k, data)
 
+    def reconstruct(self, coef_ptr: int, quant_ptr: int, n: int, planes_ptr: int, out_ptr: int, stream: int) -> None:
+        """n frames of device coefficients -> u8 [n,oh,ow,3] at ``out_ptr`` on ``stream``: the one place an open calls the device stage.
+        Scale 1 is tstar_jpeg_reconstruct as it always was."""
+        from . import _lib
+        lib = _lib.load()
+        if self.scale == 1:
+            _lib.check(lib.tstar_jpeg_reconstruct(coef_ptr, quant_ptr, n, *self.geom, planes_ptr, out_ptr, stream), "tstar_jpeg_reconstruct")
+        else:
+            _lib.check(lib.tstar_jpeg_reconstruct_scaled(coef_ptr, quant_ptr, n, *self.geom, self.scale, planes_ptr, out_ptr, stream),
+                       "tstar_jpeg_reconstruct_scaled")
+
+    def reconstruct_host(self, coef_ptr: int, quant_ptr: int, n: int, out_ptr: int, threads: int) -> None:
+        """The same through the host twin, for a CPU store."""
+        from . import _lib
+        lib = _lib.load()
+        if self.scale == 1:
+            _lib.check(lib.tstar_jpeg_reconstruct_host(coef_ptr, quant_ptr, n, *self.geom, out_ptr, threads), "tstar_jpeg_reconstruct_host")
+        else:
+            _lib.check(lib.tstar_jpeg_reconstruct_scaled_host(coef_ptr, quant_ptr, n, *self.geom, self.scale, out_ptr, threads),
+                       "tstar_jpeg_reconstruct_scaled_host")
+
     def reconstruct_one(self, coef1, quant1, out, planes=None) -> None:
-        """One frame from host_verdict's coefficients into ``out`` (u8 [1,H,W,3] on the device), on the current stream."""
+        """One frame from host_verdict's coefficients into ``out`` (u8 [1,oh,ow,3] on the device), on the current stream."""
         import torch
         from . import _lib
         if planes is None:
             planes = torch.empty(self.plane_bytes, dtype=torch.uint8, device=self.device)
         dc, dq = coef1.to(self.device), quant1.to(self.device)
-        _lib.check(_lib.load().tstar_jpeg_reconstruct(dc.data_ptr(), dq.data_ptr(), 1, *self.geom, planes.data_ptr(), out.data_ptr(),
-                                                      _lib.stream_ptr()), "tstar_jpeg_reconstruct")
+        self.reconstruct(dc.data_ptr(), dq.data_ptr(), 1, planes.data_ptr(), out.data_ptr(), _lib.stream_ptr())
 
 
 class EntropyRunner:
@@ -750,8 +823,6 @@ def _device_entropy_chunks(ctx: JpegOpen, store, s0: int, chunk: Optional[int], 
     collected one chunk later (the host plans the next chunk while this one runs); a frame the device did not return OK for gets the
     host decoder's verdict."""
     import torch
-    from . import _lib
-    lib = _lib.load()
     run = EntropyRunner(ctx, chunk, min_split_bytes)
     planes = torch.empty((run.chunk, ctx.plane_bytes), dtype=torch.uint8, device=ctx.device)
 
@@ -771,9 +842,8 @@ def _device_entropy_chunks(ctx: JpegOpen, store, s0: int, chunk: Optional[int], 
         ticket = run.submit(s0, datas, side)
         batch = ticket[1]
         if len(batch.plan.segments):
-            _lib.check(lib.tstar_jpeg_reconstruct(run.d_coef.data_ptr(), run.d_buf.data_ptr() + batch.parts["quant"][0], len(datas), *ctx.geom,
-                                                  planes.data_ptr(), store[s0:s0 + len(datas)].data_ptr(), side.cuda_stream),
-                       "tstar_jpeg_reconstruct")
+            ctx.reconstruct(run.d_coef.data_ptr(), run.d_buf.data_ptr() + batch.parts["quant"][0], len(datas), planes.data_ptr(),
+                            store[s0:s0 + len(datas)].data_ptr(), side.cuda_stream)
         if before is not None:
             finish(before)
         before = ticket
@@ -786,8 +856,6 @@ def _host_entropy_chunks(ctx: JpegOpen, store, s0: int, chunk: Optional[int], th
     """load_jpeg from frame s0 on with the entropy stage on the host thread pool: coefficients into (on a GPU: two sets of pinned)
     buffers, reconstruction by the HIP kernels on the side stream while the next chunk is entropy-decoded, or by their host mirror."""
     import torch
-    from . import _lib
-    lib = _lib.load()
     n_sec, geom, on_gpu = len(ctx.raw), ctx.geom, side is not None
     c = min(chunk if chunk else max(1, min(64, (48 << 20) // (ctx.blocks * 128))), n_sec)
     coefs = [torch.empty((c, ctx.blocks * 64), dtype=torch.int16, pin_memory=on_gpu) for _ in range(1 + on_gpu)]
@@ -818,24 +886,24 @@ def _host_entropy_chunks(ctx: JpegOpen, store, s0: int, chunk: Optional[int], th
             with torch.cuda.stream(side):
                 d_coef[b][:n].copy_(coef[:n], non_blocking=True)
                 d_quant[b][:n].copy_(quant[:n], non_blocking=True)
-                _lib.check(lib.tstar_jpeg_reconstruct(d_coef[b].data_ptr(), d_quant[b].data_ptr(), n, *geom, planes.data_ptr(),
-                                                      store[s0:s0 + n].data_ptr(), side.cuda_stream), "tstar_jpeg_reconstruct")
+                ctx.reconstruct(d_coef[b].data_ptr(), d_quant[b].data_ptr(), n, planes.data_ptr(), store[s0:s0 + n].data_ptr(), side.cuda_stream)
                 done[b] = torch.cuda.Event()
                 done[b].record(side)
                 for j, arr in fallback:                   # after the kernels, which wrote whatever the stale coefficients gave into these slots
                     store[s0 + j].copy_(torch.from_numpy(arr))
         else:
             out = store[s0:s0 + n].numpy()
-            _lib.check(lib.tstar_jpeg_reconstruct_host(coef.data_ptr(), quant.data_ptr(), n, *geom, out.ctypes.data, threads),
-                       "tstar_jpeg_reconstruct_host")
+            ctx.reconstruct_host(coef.data_ptr(), quant.data_ptr(), n, out.ctypes.data, threads)
             for j, arr in fallback:
                 out[j] = arr
         s0 += n
         ci += 1
 
 
-def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None, threads: int = 0, entropy: Optional[str] = None):
-    """Decode the wanted frames of ``src`` into a FrameStore (RGB u8 [N,H,W,3] on ``device``).  ``entropy``: "host" (the
+def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None, threads: int = 0, entropy: Optional[str] = None,
+              scale: int = 1):
+    """Decode the wanted frames of ``src`` into a FrameStore (RGB u8 [N,H,W,3] on ``device``; at ``scale`` 2, 4 or 8 the frames are
+    decoded at 1/scale size, [N, ceil(H / scale), ceil(W / scale), 3], byte for byte Pillow's ``draft``).  ``entropy``: "host" (the
     default; TSTAR_JPEG_ENTROPY when absent) or "device", where the Huffman decode runs on the GPU too and the store's
     ``entropy_stats`` says how many frames each side entropy-decoded.  The device mode works on larger chunks (a frame without
     restart markers is one segment): next to the store it holds up to 512 MiB of coefficients plus half as much of planes on the
@@ -855,14 +923,14 @@ def load_jpeg(src: JpegFrames, device: str = "cuda", chunk: Optional[int] = None
         raise ValueError("load_jpeg: entropy='device' needs a GPU store (device='cpu' was asked for)")
     dev_entropy = entropy_mode(entropy) == "device" and on_gpu       # TSTAR_JPEG_ENTROPY=device leaves a CPU store on the host path
     min_split = split_min_bytes() if dev_entropy else 0
-    ctx = JpegOpen(src, want, device)
+    ctx = JpegOpen(src, want, device, scale=scale)
     side = torch.cuda.Stream(device=device) if on_gpu else None
     store, s0 = None, 0
     try:
         while s0 < len(want) and ctx.geom is None:
             arr = ctx.prelude(s0, ctx.read(s0))
             if store is None:                             # the first frame has fixed the picture size
-                store = torch.empty((len(want), ctx.H, ctx.W, 3), dtype=torch.uint8, device=device)
+                store = torch.empty((len(want), ctx.oh, ctx.ow, 3), dtype=torch.uint8, device=device)
             if arr is not None:
                 store[s0].copy_(torch.from_numpy(arr))
                 s0 += 1

@@ -246,11 +246,13 @@ def _entry_keys(src, want):
     return np.asarray(sec_entry, dtype=np.int64), raw
 
 
-def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optional[int] = None, chunk: Optional[int] = None):
+def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optional[int] = None, chunk: Optional[int] = None,
+                  scale: int = 1):
     """Open ``src`` as a ``video.JpegFrameStore`` (see the module text).  The open is ``load_jpeg``'s device mode with another
     destination: the same ``jpeg.JpegOpen`` (prelude, host verdict, counters, messages) and the same ``jpeg.EntropyRunner`` (one upload
     per chunk carries the bytes and the records, the entropy kernels check every frame); here the bytes move on into the arena, and a
-    frame the device did not return OK for becomes an exception: RGB in a permanent slot."""
+    frame the device did not return OK for becomes an exception: RGB in a permanent slot.  ``scale`` 2, 4, 8: pool slots and permanent
+    slots hold the frames at 1/scale size; the arena and the gather are those of the full-size store."""
     import torch
     from .video import JpegFrameStore
     if str(device).startswith("cpu"):
@@ -262,7 +264,7 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
     sec_entry, raw = _entry_keys(src, want)
     E = len(raw)
     # the counters are per logical second, as load_jpeg's: an entry counts once for every second that shares it
-    ctx = jpeg.JpegOpen(src, raw, device, seconds=np.bincount(sec_entry, minlength=E))
+    ctx = jpeg.JpegOpen(src, raw, device, seconds=np.bincount(sec_entry, minlength=E), scale=scale)
     min_split = jpeg.split_min_bytes()
     sizes = [src.ranges[fi][1] for fi in raw] if getattr(src, "ranges", None) is not None else None
     builder = ArenaBuilder()
@@ -300,7 +302,7 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
         for j in run.collect(ticket):                    # waits for the chunk: the statuses decide what the arena may serve
             verdict = ctx.host_verdict(e0 + j, datas[j])
             if isinstance(verdict, tuple):
-                rgb = torch.empty((1, ctx.H, ctx.W, 3), dtype=torch.uint8, device=device)
+                rgb = torch.empty((1, ctx.oh, ctx.ow, 3), dtype=torch.uint8, device=device)
                 ctx.reconstruct_one(*verdict, rgb)
                 stream.synchronize()
                 verdict = rgb[0]
@@ -313,6 +315,6 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
         del d_parts
     arena = builder.finish()
     assert arena.n_entries == E and builder.total == d_arena.numel()
-    st = JpegFrameStore(arena, d_arena, sec_entry, ctx.geom, (ctx.H, ctx.W), exceptions, P, src.fps, src.n_frames, name=src.name,
-                        min_split_bytes=min_split, max_rounds=ctx.sstats["rounds_max"])
+    st = JpegFrameStore(arena, d_arena, sec_entry, ctx.geom, (ctx.oh, ctx.ow), exceptions, P, src.fps, src.n_frames, name=src.name,
+                        min_split_bytes=min_split, max_rounds=ctx.sstats["rounds_max"], jpeg_scale=ctx.scale)
     return ctx.attach(st)

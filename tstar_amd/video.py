@@ -101,6 +101,8 @@ class FrameStore:
         self.decode_stats = None      # JPEG sources: {"device": n, "host": n, "pillow": n} frames decoded by each path
         self.entropy_stats = None     # JPEG sources: {"device": n, "host": n} frames run through each side's entropy decoder
         self.entropy_split_stats = None   # JPEG sources: {"split": n, "abandoned": n, "rounds_max": r} segments cut into sub-sequences
+        self.jpeg_scale = 1               # JPEG sources: the frames are the file's pictures decoded at 1/jpeg_scale size ...
+        self.source_size = None           # ... and (W, H) is the file's own picture size
 
     @property
     def num_seconds(self) -> int:
@@ -176,10 +178,11 @@ class JpegFrameStore(FrameStore):
 
     def __init__(self, arena, d_arena, sec_entry, geom, hw, exceptions, pool_frames: int, raw_fps: float,
                  raw_total_frames: Optional[int] = None, name: str = "<jpeg frames>", min_split_bytes: Optional[int] = None,
-                 max_rounds: Optional[int] = None):
+                 max_rounds: Optional[int] = None, jpeg_scale: int = 1):
         """``max_rounds``: rounds of the split path a fetch queues (default jpeg.SPLIT_MAX_ROUNDS).  Sub-sequences are cut from a
         segment's own first byte, so a segment converges in the round it converged in at open, wherever a fetch puts it: an open
-        passes the most rounds any segment took, and a fetch queues that many launches instead of 48 (same coefficients)."""
+        passes the most rounds any segment took, and a fetch queues that many launches instead of 48 (same coefficients).
+        ``jpeg_scale``: the slots hold the frames decoded at 1/jpeg_scale size, ``hw`` is that size."""
         import torch
         from . import jpeg, jpeg_resident as JR
         self.fmt = "rgb"
@@ -187,6 +190,7 @@ class JpegFrameStore(FrameStore):
         self.raw_total_frames = int(raw_total_frames if raw_total_frames is not None else round(len(sec_entry) * self.raw_fps))
         self.name = name
         self.decode_stats = self.entropy_stats = self.entropy_split_stats = None
+        self.jpeg_scale, self.source_size = int(jpeg_scale), None
         self.arena, self.d_arena = arena, d_arena
         self._sec_entry = np.asarray(sec_entry, dtype=np.int64)
         self._geom = tuple(int(v) for v in geom) if geom is not None else None
@@ -220,6 +224,8 @@ class JpegFrameStore(FrameStore):
         # a fetch's workspace, sized once for the largest piece a fetch can be (never reallocated: fetches on several streams share
         # it, ordered by events)
         blocks, plane_bytes = jpeg._sizes(self._geom)
+        if self.jpeg_scale > 1:
+            plane_bytes = jpeg.scaled_sizes(self._geom, self.jpeg_scale)[2]
         c = self._piece = max(1, min(self.pool_frames, JR.FETCH_COEF_BUDGET // (blocks * 128)))
         keep = np.ones(arena.n_entries, dtype=bool)
         keep[exc] = False
@@ -337,9 +343,14 @@ class JpegFrameStore(FrameStore):
         jpeg.split_launch((base, total, base + s_at, self._d_sets.data_ptr(), len(a.table_sets), base + f_at, m, nseg, *self._geom), longest,
                           self._min_split, self._max_rounds, self._d_ws.data_ptr(), self._ws_bytes, self._d_coef.data_ptr(), st.data_ptr(),
                           st.data_ptr() + 4 * self._cap_segments, sp)
-        _lib.check(lib.tstar_jpeg_reconstruct_slots(self._d_coef.data_ptr(), base + q_at, m, *self._geom, self._d_planes.data_ptr(),
-                                                    self._slots.data_ptr(), self.pool_frames, d.data_ptr() + 4 * (at + 6 * m), sp),
-                   "tstar_jpeg_reconstruct_slots")
+        if self.jpeg_scale == 1:
+            _lib.check(lib.tstar_jpeg_reconstruct_slots(self._d_coef.data_ptr(), base + q_at, m, *self._geom, self._d_planes.data_ptr(),
+                                                        self._slots.data_ptr(), self.pool_frames, d.data_ptr() + 4 * (at + 6 * m), sp),
+                       "tstar_jpeg_reconstruct_slots")
+        else:
+            _lib.check(lib.tstar_jpeg_reconstruct_slots_scaled(self._d_coef.data_ptr(), base + q_at, m, *self._geom, self.jpeg_scale,
+                                                               self._d_planes.data_ptr(), self._slots.data_ptr(), self.pool_frames,
+                                                               d.data_ptr() + 4 * (at + 6 * m), sp), "tstar_jpeg_reconstruct_slots_scaled")
         self._err.bitwise_or_(st[:nseg].max())
 
     def fetch_errors(self) -> int:
@@ -594,7 +605,7 @@ _SYN = re.compile(r"^synthetic://")
 
 
 def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_entropy: Optional[str] = None,
-               resident: Optional[str] = None, pool_frames: Optional[int] = None) -> FrameStore:
+               resident: Optional[str] = None, pool_frames: Optional[int] = None, jpeg_scale: Optional[int] = None) -> FrameStore:
     """``video``: a FrameStore, a ``synthetic://n=..,h=..,w=..,seed=..,fps=..`` URL, a folder of .jpg / .jpeg frames or a
     list of JPEG paths / bytes (``fps`` frames per second, default 1), a .mjpeg / .mjpg stream (``fps`` default 25), a
     Motion-JPEG .avi, or another file path (.y4m, the Pillow sequences; else decoded at native rate through decord, else
@@ -602,14 +613,18 @@ def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_en
     ``jpeg_entropy``: where JPEG sources are entropy-decoded, "host" (default; TSTAR_JPEG_ENTROPY when absent) or "device".
     ``resident="jpeg"`` (TSTAR_JPEG_RESIDENT=1 when absent): a JPEG source stays compressed in HBM and its frames are decoded on
     demand into a pool of ``pool_frames`` slots (default 512; TSTAR_JPEG_POOL) -> a ``JpegFrameStore``.  The keyword on a source
-    that is not JPEG is a ValueError; the variable alone leaves such a source as it is."""
+    that is not JPEG is a ValueError; the variable alone leaves such a source as it is.
+    ``jpeg_scale`` 2, 4 or 8 (TSTAR_JPEG_SCALE when absent; default 1): a JPEG source is decoded at 1/2, 1/4 or 1/8 size, byte for
+    byte what Pillow's ``Image.draft`` gives, so the store -- decoded or compressed-resident -- holds [N, ceil(H / s), ceil(W / s), 3]
+    and records ``jpeg_scale`` and ``source_size``.  Boxes of a search on it are in pixels of the stored frame.  The keyword on a
+    source that is not JPEG, and any other value, is a ValueError; the variable alone leaves a source that is not JPEG as it is."""
     if isinstance(video, FrameStore):
         return video
-    from . import jpeg_resident
+    from . import jpeg, jpeg_resident
     mode = jpeg_resident.resident_mode(resident)
+    scale = jpeg.scale_mode(jpeg_scale)
     other_codec = None
     if not (isinstance(video, str) and _SYN.match(video)):
-        from . import jpeg
         try:
             src = jpeg.open_source(video, fps)
         except jpeg.NotMotionJpeg as e:               # an AVI with another codec: decord / cv2 below, where a host has them
@@ -617,12 +632,14 @@ def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_en
         if src is not None:
             try:
                 if mode == "jpeg" and (resident is not None or not str(device).startswith("cpu")):
-                    return jpeg_resident.load_resident(src, device, pool_frames)
-                return jpeg.load_jpeg(src, device, entropy=jpeg_entropy)
+                    return jpeg_resident.load_resident(src, device, pool_frames, scale=scale)
+                return jpeg.load_jpeg(src, device, entropy=jpeg_entropy, scale=scale)
             finally:
                 src.close()
     if resident is not None:
         raise ValueError(f"open_video: resident={resident!r} needs a Motion-JPEG .avi, a .mjpeg stream or JPEG frames; {video!r} is none of them")
+    if jpeg_scale is not None:
+        raise ValueError(f"open_video: jpeg_scale={jpeg_scale!r} needs a Motion-JPEG .avi, a .mjpeg stream or JPEG frames; {video!r} is none of them")
     if fps is not None:
         raise ValueError("open_video: fps= applies to JPEG frame folders / lists and .mjpeg streams only")
     if isinstance(video, str) and _SYN.match(video):
