@@ -516,6 +516,31 @@ int tstar_jpeg_encode_scan(const int16_t* d_coef, int n, int W, int H, int hs, i
 int tstar_jpeg_encode(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
                       int16_t* d_coef, uint8_t* d_out, size_t slot_bytes, uint32_t* d_lengths, int32_t* d_status, void* d_workspace,
                       size_t workspace_bytes, void* stream);
+/* ---- The same encoder with RESTART INTERVALS: what Pillow writes with restart_marker_blocks= / restart_marker_rows=.  restart is
+ * the interval in MCUs, 0..65535 (0: none; the entries above are these with 0: the same bytes from the same launches).  With an
+ * interval the header carries DRI (FF DD 00 04 hi lo) directly before SOS (629 bytes), and behind every full interval but the
+ * last the scan fills the current byte with one-bits (a byte that becomes 0xFF is stuffed like any other), holds RSTn (FF D0 +
+ * n mod 8, never stuffed) and starts every DC predictor from 0; an interval of at least the frame's MCUs writes DRI and no
+ * marker.  Restart counters of their own (optional, added to; u64 [3] on the host, u32 [n][3] per frame on the device, zeroed by
+ * the call): markers, intervals in front of a marker that ended byte-aligned, padded bytes that came out as 0xFF (on the device
+ * the last is counted by the stuffing pass, so it stays 0 for a frame that pass never visits: one far too large for its slot). */
+/* out8 as tstar_jpeg_encode_plan with the bound on a scan grown by 4 bytes per marker (the padding adds less than one data
+ * byte, which stuffing can double; the marker's two bytes are never stuffed) and the workspace by the interval tables;
+ * out2 (optional) = {interval, markers per frame = (MCUs - 1) / interval}. */
+int tstar_jpeg_encode_plan_rst(int W, int H, int hs, int vs, int n, size_t slot_bytes, int restart, size_t* out8, size_t* out2);
+int tstar_jpeg_encode_header_rst(int W, int H, int quality, int hs, int vs, int restart, uint8_t* out, size_t cap, size_t* len);
+int tstar_jpeg_encode_scan_host_rst(const int16_t* coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* out, size_t slot_bytes,
+                                    uint32_t* lengths, int32_t* status, int threads, uint64_t* counters, uint64_t* rst_counters);
+int tstar_jpeg_encode_host_rst(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
+                               int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status, int threads,
+                               uint64_t* counters, uint64_t* rst_counters);
+/* d_workspace: the bytes tstar_jpeg_encode_plan_rst names for this interval; d_rst_counters: optional device u32 [n][3]. */
+int tstar_jpeg_encode_scan_rst(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* d_out, size_t slot_bytes,
+                               uint32_t* d_lengths, int32_t* d_status, void* d_workspace, size_t workspace_bytes,
+                               uint32_t* d_rst_counters, void* stream);
+int tstar_jpeg_encode_rst(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
+                          int restart, int16_t* d_coef, uint8_t* d_out, size_t slot_bytes, uint32_t* d_lengths, int32_t* d_status,
+                          void* d_workspace, size_t workspace_bytes, uint32_t* d_rst_counters, void* stream);
 /* Entropy stage on the device.  The unit of parallel work is a SEGMENT: a run of MCUs that starts at a byte boundary with
  * zero DC predictors (one restart interval; a frame without DRI is one segment).  The planner below cuts frames into
  * segments on the host, the kernel decodes one segment per lane into the coefficient layout above, and

@@ -93,6 +93,12 @@ SIGNATURES = {
     "tstar_jpeg_encode_blocks": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tstar_jpeg_encode_scan": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "tstar_jpeg_encode": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "tstar_jpeg_encode_plan_rst": (_i, [_i, _i, _i, _i, _i, _sz, _i, _vp, _vp]),
+    "tstar_jpeg_encode_header_rst": (_i, [_i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "tstar_jpeg_encode_scan_host_rst": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp]),
+    "tstar_jpeg_encode_host_rst": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp]),
+    "tstar_jpeg_encode_scan_rst": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tstar_jpeg_encode_rst": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp]),
     "tstar_jpeg_plan_segments": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "tstar_jpeg_entropy_device": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tstar_jpeg_entropy_segments_host": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -27,17 +27,26 @@ bool jpeg_enc_geom_ok(const JpegGeom& g) {
 
 size_t jpeg_enc_max_scan_bytes(const JpegGeom& g) { return 2 * ((g.blocks() * (size_t)jpegenc::kMaxBlockBits + 7) / 8) + 2; }
 
-JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes) {
+size_t jpeg_enc_restart_markers(const JpegGeom& g, int restart) {
+    return restart > 0 ? ((size_t)g.mcux() * g.mcuy() - 1) / (size_t)restart : 0;
+}
+size_t jpeg_enc_max_scan_bytes(const JpegGeom& g, int restart) { return jpeg_enc_max_scan_bytes(g) + 4 * jpeg_enc_restart_markers(g, restart); }
+
+JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes, int restart) {
     JpegEncPlan p = {};
+    if (!jpeg_enc_restart_ok(restart)) { p.error = "restart interval must be in 0..65535 MCUs (DRI holds 16 bits)"; return p; }
     if (!jpeg_enc_geom_ok(g)) { p.error = "unsupported geometry (3 components, sampling 2x2 / 2x1 / 1x1, sides 1..16384)"; return p; }
     if (n < 1 || n > 65535) { p.error = "n must be in 1..65535"; return p; }
     p.blocks = g.blocks();
-    if (p.blocks * (size_t)jpegenc::kMaxBlockBits >= (1ull << 32)) { p.error = "frame too large: a scan's bit offsets would not fit 32 bits"; return p; }
+    p.restart = restart;
+    p.markers = jpeg_enc_restart_markers(g, restart);
+    if (p.blocks * (size_t)jpegenc::kMaxBlockBits + p.markers * (size_t)jpegenc::kRestartBits >= (1ull << 32)) { p.error = "frame too large: a scan's bit offsets would not fit 32 bits"; return p; }
     if (slot_bytes < 2 || slot_bytes >= (1ull << 31)) { p.error = "slot_bytes must be in 2..2^31-1"; return p; }
     p.coef_bytes = p.blocks * 128;
-    p.max_scan_bytes = jpeg_enc_max_scan_bytes(g);
-    p.header_bytes = kJpegEncHeaderBytes;
-    const size_t max_raw = (p.blocks * (size_t)jpegenc::kMaxBlockBits + 7) / 8;
+    p.max_scan_bytes = jpeg_enc_max_scan_bytes(g, restart);
+    p.header_bytes = (size_t)jpeg_enc_header_bytes(restart);
+    // with markers the unstuffed stream holds them and the padding in front of them: 3 bytes more per marker at most
+    const size_t max_raw = (p.blocks * (size_t)jpegenc::kMaxBlockBits + 7) / 8 + 3 * p.markers;
     const size_t raw_cap = slot_bytes < max_raw ? slot_bytes : max_raw;      // unstuffed bytes never exceed the stuffed ones
     p.raw_words = raw_cap / 4 + 1;
     p.ff_chunks = (p.raw_words * 4 + kJpegEncStuffChunk - 1) / kJpegEncStuffChunk;
@@ -47,6 +56,11 @@ JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes) {
     p.off_raw = p.off_bits + up((size_t)n * p.blocks * sizeof(uint32_t));
     p.off_ff = p.off_raw + up((size_t)n * p.raw_words * sizeof(uint32_t));
     p.workspace_bytes = p.off_ff + up((size_t)n * p.ff_chunks * sizeof(uint32_t));
+    if (restart > 0) {
+        p.off_seg = p.workspace_bytes;
+        p.off_mark = p.off_seg + up((size_t)n * (p.markers + 1) * sizeof(uint32_t));
+        p.workspace_bytes = p.off_mark + up((size_t)n * p.markers * sizeof(uint32_t));
+    }
     const size_t total_blocks = (size_t)n * p.blocks;
     if (total_blocks / 32 + 1 >= 0x7fffffffull) { p.error = "chunk too large for one launch"; return p; }
     p.block_wgs = (unsigned)((total_blocks + 31) / 32);
@@ -61,7 +75,9 @@ void jpeg_enc_quant(int quality, uint16_t* quant) {
         for (int k = 0; k < 64; ++k) quant[c * 64 + k] = (uint16_t)jpegenc::quant_entry(jpegenc::kStd.q[c ? 1 : 0][k], scale);
 }
 
-void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out) {
+void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out) { jpeg_enc_header(g, quality, 0, out); }
+
+void jpeg_enc_header(const JpegGeom& g, int quality, int restart, uint8_t* out) {
     uint8_t* p = out;
     auto put = [&](std::initializer_list<int> v) { for (int b : v) *p++ = (uint8_t)b; };
     uint16_t quant[192];
@@ -81,6 +97,7 @@ void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out) {
         for (int i = 0; i < 16; ++i) *p++ = s.bits[i];
         for (int i = 0; i < s.nvals; ++i) *p++ = s.vals[i];
     }
+    if (restart > 0) put({0xFF, 0xDD, 0, 4, restart >> 8, restart & 255});
     put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
 }
 
@@ -144,26 +161,43 @@ struct ByteSink {                        // MSB-first bit writer with FF -> FF 0
             nb -= 8;
         }
     }
-    void finish() {
-        if (nb) byte((uint8_t)((acc << (8 - nb)) | ((1u << (8 - nb)) - 1u)));
+    // fills the current byte with one-bits (stuffed like any byte when that makes 0xFF); 1 when there was a byte to fill
+    int pad(bool* ff) {
+        if (!nb) return 0;
+        const uint8_t b = (uint8_t)((acc << (8 - nb)) | ((1u << (8 - nb)) - 1u));
+        if (ff) *ff = b == 0xFF;
+        byte(b);
         nb = 0;
+        return 1;
+    }
+    void marker(int m) {                 // never stuffed
         bytes.push_back(0xFF);
-        bytes.push_back(0xD9);
+        bytes.push_back((uint8_t)m);
+    }
+    void finish() {
+        pad(nullptr);
+        marker(0xD9);
     }
 };
 
 }  // namespace
 
 // the whole scan of one frame into sink.bytes; JPEG_ENC_OK or JPEG_ENC_BAD_COEF
-static int scan_frame(const int16_t* coef, const JpegGeom& g, ByteSink& sink, uint64_t* counters) {
+static int scan_frame(const int16_t* coef, const JpegGeom& g, int restart, ByteSink& sink, uint64_t* counters, uint64_t* rst_counters) {
     const jpegenc::ScanGeom sg = scan_geom(g);
     sink.bytes.reserve(g.blocks() * 16);
-    uint64_t zrl = 0, no_eob = 0;
+    uint64_t zrl = 0, no_eob = 0, rst = 0, pad_free = 0, pad_ff = 0;
     int bad = 0;
-    const int nb = sg.blocks();
+    const int nb = sg.blocks(), per = sg.per_mcu();
     for (int k = 0; k < nb; ++k) {
+        if (restart > 0 && k > 0 && k % per == 0 && (k / per) % restart == 0) {
+            bool ff = false;
+            if (!sink.pad(&ff)) ++pad_free;
+            pad_ff += ff;
+            sink.marker(0xD0 + (int)(rst++ & 7));
+        }
         int c, b, pb;
-        jpegenc::scan_block(sg, k, &c, &b, &pb);
+        jpegenc::scan_block_rst(sg, k, restart, &c, &b, &pb);
         const int pred = pb < 0 ? 0 : coef[(size_t)pb * 64];
         const jpegenc::BlockEvents ev = jpegenc::encode_block(coef + (size_t)b * 64, pred, kTables.codes[c ? 2 : 0], kTables.codes[c ? 3 : 1],
                                                               jpegenc::kStd.zigzag, sink);
@@ -177,13 +211,23 @@ static int scan_frame(const int16_t* coef, const JpegGeom& g, ByteSink& sink, ui
         counters[JPEG_ENC_N_NO_EOB] += no_eob;
         counters[JPEG_ENC_N_STUFFED] += sink.stuffed;
     }
+    if (rst_counters) {
+        rst_counters[JPEG_ENC_R_RST] += rst;
+        rst_counters[JPEG_ENC_R_PAD_FREE] += pad_free;
+        rst_counters[JPEG_ENC_R_PAD_FF] += pad_ff;
+    }
     return bad ? JPEG_ENC_BAD_COEF : JPEG_ENC_OK;
 }
 
 int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, uint8_t* out, size_t cap, size_t* len, uint64_t* counters) {
+    return jpeg_enc_scan(coef, g, 0, out, cap, len, counters, nullptr);
+}
+
+int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, uint64_t* counters,
+                  uint64_t* rst_counters) {
     ByteSink sink;
     *len = 0;
-    if (scan_frame(coef, g, sink, counters) != JPEG_ENC_OK) return JPEG_ENC_BAD_COEF;
+    if (scan_frame(coef, g, restart, sink, counters, rst_counters) != JPEG_ENC_OK) return JPEG_ENC_BAD_COEF;
     *len = sink.bytes.size();
     if (sink.bytes.size() > cap) return JPEG_ENC_SHORT;
     memcpy(out, sink.bytes.data(), sink.bytes.size());
@@ -192,12 +236,14 @@ int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, uint8_t* out, size_t c
 
 namespace {
 
-// run fn(i, counters of the worker) for i in [0, n) on up to `threads` workers; the workers' counters are summed into `counters`
+// run fn(i, counters of the worker) for i in [0, n) on up to `threads` workers; a worker's counters are the JPEG_ENC_N_* block
+// with the JPEG_ENC_R_* block behind it; the workers' counters are summed into `counters` and `rst_counters`
+constexpr int kWorkerCounters = JPEG_ENC_N_COUNTERS + JPEG_ENC_R_COUNTERS;
 template <class F>
-void parallel_frames(int n, int threads, uint64_t* counters, F fn) {
+void parallel_frames(int n, int threads, uint64_t* counters, uint64_t* rst_counters, F fn) {
     const int allow = jpeg_thread_allowance(threads);
     const int t = allow < n ? allow : n;
-    std::vector<uint64_t> local((size_t)(t < 1 ? 1 : t) * JPEG_ENC_N_COUNTERS, 0);
+    std::vector<uint64_t> local((size_t)(t < 1 ? 1 : t) * kWorkerCounters, 0);
     if (t <= 1) {
         for (int i = 0; i < n; ++i) fn(i, local.data());
     } else {
@@ -206,12 +252,15 @@ void parallel_frames(int n, int threads, uint64_t* counters, F fn) {
         pool.reserve((size_t)t);
         for (int w = 0; w < t; ++w)
             pool.emplace_back([&, w] {
-                for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i, local.data() + (size_t)w * JPEG_ENC_N_COUNTERS);
+                for (int i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i, local.data() + (size_t)w * kWorkerCounters);
             });
         for (auto& th : pool) th.join();
     }
-    if (counters)
-        for (size_t k = 0; k < local.size(); ++k) counters[k % JPEG_ENC_N_COUNTERS] += local[k];
+    for (size_t k = 0; k < local.size(); ++k) {
+        const size_t j = k % kWorkerCounters;
+        if (j < JPEG_ENC_N_COUNTERS ? counters != nullptr : rst_counters != nullptr)
+            (j < JPEG_ENC_N_COUNTERS ? counters[j] : rst_counters[j - JPEG_ENC_N_COUNTERS]) += local[k];
+    }
 }
 
 bool frames_args_ok(const char* fn, const void* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs, JpegGeom* g) {
@@ -236,24 +285,42 @@ using namespace tstar;
 
 extern "C" {
 
+// the entries without an interval forward to these with interval 0
+int tstar_jpeg_encode_plan_rst(int W, int H, int hs, int vs, int n, size_t slot_bytes, int restart, size_t* out8, size_t* out2);
+int tstar_jpeg_encode_header_rst(int W, int H, int quality, int hs, int vs, int restart, uint8_t* out, size_t cap, size_t* len);
+int tstar_jpeg_encode_scan_host_rst(const int16_t* coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* out, size_t slot_bytes,
+                                    uint32_t* lengths, int32_t* status, int threads, uint64_t* counters, uint64_t* rst_counters);
+int tstar_jpeg_encode_host_rst(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
+                               int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status, int threads,
+                               uint64_t* counters, uint64_t* rst_counters);
+
 int tstar_jpeg_encode_plan(int W, int H, int hs, int vs, int n, size_t slot_bytes, size_t* out8) {
+    return tstar_jpeg_encode_plan_rst(W, H, hs, vs, n, slot_bytes, 0, out8, nullptr);
+}
+
+int tstar_jpeg_encode_plan_rst(int W, int H, int hs, int vs, int n, size_t slot_bytes, int restart, size_t* out8, size_t* out2) {
     if (!out8) { set_error("tstar_jpeg_encode_plan: null argument"); return 1; }
-    const JpegEncPlan p = plan_jpeg_encode(JpegGeom{W, H, 3, hs, vs}, n, slot_bytes);
+    const JpegEncPlan p = plan_jpeg_encode(JpegGeom{W, H, 3, hs, vs}, n, slot_bytes, restart);
     if (p.error) { set_error(std::string("tstar_jpeg_encode_plan: ") + p.error); return 1; }
+    if (out2) { out2[0] = (size_t)p.restart; out2[1] = p.markers; }
     out8[0] = p.blocks; out8[1] = p.coef_bytes; out8[2] = p.max_scan_bytes; out8[3] = p.header_bytes; out8[4] = p.workspace_bytes;
     out8[5] = p.block_wgs; out8[6] = p.entropy_wgs_x; out8[7] = p.stuff_wgs_x;
     return 0;
 }
 
 int tstar_jpeg_encode_header(int W, int H, int quality, int hs, int vs, uint8_t* out, size_t cap, size_t* len) {
+    return tstar_jpeg_encode_header_rst(W, H, quality, hs, vs, 0, out, cap, len);
+}
+
+int tstar_jpeg_encode_header_rst(int W, int H, int quality, int hs, int vs, int restart, uint8_t* out, size_t cap, size_t* len) {
     const JpegGeom g{W, H, 3, hs, vs};
-    if (!out || !len || quality < 1 || quality > 100 || !jpeg_enc_geom_ok(g)) {
-        set_error("tstar_jpeg_encode_header: null argument, quality outside 1..100 or unsupported geometry");
+    if (!out || !len || quality < 1 || quality > 100 || !jpeg_enc_geom_ok(g) || !jpeg_enc_restart_ok(restart)) {
+        set_error("tstar_jpeg_encode_header: null argument, quality outside 1..100, unsupported geometry or restart interval outside 0..65535");
         return 1;
     }
-    *len = kJpegEncHeaderBytes;
-    if (cap < (size_t)kJpegEncHeaderBytes) { set_error("tstar_jpeg_encode_header: the buffer is shorter than the header"); return 4; }
-    jpeg_enc_header(g, quality, out);
+    *len = (size_t)jpeg_enc_header_bytes(restart);
+    if (cap < *len) { set_error("tstar_jpeg_encode_header: the buffer is shorter than the header"); return 4; }
+    jpeg_enc_header(g, quality, restart, out);
     return 0;
 }
 
@@ -266,7 +333,7 @@ int tstar_jpeg_encode_blocks_host(const uint8_t* frames, int N, int H, int W, co
     jpeg_enc_quant(quality, q);
     if (quant) memcpy(quant, q, sizeof(q));
     const size_t per = g.blocks() * 64, frame = (size_t)W * H * 3;
-    parallel_frames(n, threads, counters, [&](int i, uint64_t* cnt) {
+    parallel_frames(n, threads, counters, nullptr, [&](int i, uint64_t* cnt) {
         jpeg_enc_blocks(frames + frame * (size_t)idx[i], g, q, coef + per * (size_t)i, cnt + JPEG_ENC_N_DUMMY_RIGHT);
     });
     return 0;
@@ -274,15 +341,21 @@ int tstar_jpeg_encode_blocks_host(const uint8_t* frames, int N, int H, int W, co
 
 int tstar_jpeg_encode_scan_host(const int16_t* coef, int n, int W, int H, int hs, int vs, uint8_t* out, size_t slot_bytes,
                                 uint32_t* lengths, int32_t* status, int threads, uint64_t* counters) {
+    return tstar_jpeg_encode_scan_host_rst(coef, n, W, H, hs, vs, 0, out, slot_bytes, lengths, status, threads, counters, nullptr);
+}
+
+int tstar_jpeg_encode_scan_host_rst(const int16_t* coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* out, size_t slot_bytes,
+                                    uint32_t* lengths, int32_t* status, int threads, uint64_t* counters, uint64_t* rst_counters) {
     const JpegGeom g{W, H, 3, hs, vs};
-    if (!coef || !lengths || !status || (!out && slot_bytes) || n < 1 || !jpeg_enc_geom_ok(g)) {
-        set_error("tstar_jpeg_encode_scan_host: null argument, empty batch or unsupported geometry");
+    if (!coef || !lengths || !status || (!out && slot_bytes) || n < 1 || !jpeg_enc_geom_ok(g) || !jpeg_enc_restart_ok(restart)) {
+        set_error("tstar_jpeg_encode_scan_host: null argument, empty batch, unsupported geometry or restart interval outside 0..65535");
         return 1;
     }
     const size_t per = g.blocks() * 64;
-    parallel_frames(n, threads, counters, [&](int i, uint64_t* cnt) {
+    parallel_frames(n, threads, counters, rst_counters, [&](int i, uint64_t* cnt) {
         size_t len = 0;
-        status[i] = jpeg_enc_scan(coef + per * (size_t)i, g, out + slot_bytes * (size_t)i, slot_bytes, &len, cnt);
+        status[i] = jpeg_enc_scan(coef + per * (size_t)i, g, restart, out + slot_bytes * (size_t)i, slot_bytes, &len, cnt,
+                                  cnt + JPEG_ENC_N_COUNTERS);
         lengths[i] = (uint32_t)len;
     });
     return 0;
@@ -290,28 +363,36 @@ int tstar_jpeg_encode_scan_host(const int16_t* coef, int n, int W, int H, int hs
 
 int tstar_jpeg_encode_host(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
                            uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status, int threads, uint64_t* counters) {
+    return tstar_jpeg_encode_host_rst(frames, N, H, W, idx, n, quality, hs, vs, 0, out, slot_bytes, lengths, status, threads, counters, nullptr);
+}
+
+int tstar_jpeg_encode_host_rst(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
+                               int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status, int threads,
+                               uint64_t* counters, uint64_t* rst_counters) {
     JpegGeom g;
     if (!frames_args_ok("tstar_jpeg_encode_host", frames, N, H, W, idx, n, quality, hs, vs, &g)) return 1;
     if (!lengths || !status || (!out && slot_bytes)) { set_error("tstar_jpeg_encode_host: null argument"); return 1; }
+    if (!jpeg_enc_restart_ok(restart)) { set_error("tstar_jpeg_encode_host: restart interval outside 0..65535 MCUs"); return 1; }
     uint16_t q[192];
     jpeg_enc_quant(quality, q);
-    uint8_t header[kJpegEncHeaderBytes];
-    jpeg_enc_header(g, quality, header);
+    uint8_t header[kJpegEncHeaderBytes + kJpegEncDriBytes];
+    const size_t head = (size_t)jpeg_enc_header_bytes(restart);
+    jpeg_enc_header(g, quality, restart, header);
     const size_t per = g.blocks() * 64, frame = (size_t)W * H * 3;
-    parallel_frames(n, threads, counters, [&](int i, uint64_t* cnt) {
+    parallel_frames(n, threads, counters, rst_counters, [&](int i, uint64_t* cnt) {
         std::vector<int16_t> coef(per);
         jpeg_enc_blocks(frames + frame * (size_t)idx[i], g, q, coef.data(), cnt + JPEG_ENC_N_DUMMY_RIGHT);
         uint8_t* slot = out + slot_bytes * (size_t)i;
         // the scan goes behind the header only when the whole file fits: a short slot is left as it was
         ByteSink sink;
-        const int rc = scan_frame(coef.data(), g, sink, cnt);
+        const int rc = scan_frame(coef.data(), g, restart, sink, cnt, cnt + JPEG_ENC_N_COUNTERS);
         const size_t len = sink.bytes.size();
-        lengths[i] = (uint32_t)(kJpegEncHeaderBytes + len);
+        lengths[i] = (uint32_t)(head + len);
         status[i] = rc;
         if (rc != JPEG_ENC_OK) return;
-        if (kJpegEncHeaderBytes + len > slot_bytes) { status[i] = JPEG_ENC_SHORT; return; }
-        memcpy(slot, header, kJpegEncHeaderBytes);
-        memcpy(slot + kJpegEncHeaderBytes, sink.bytes.data(), len);
+        if (head + len > slot_bytes) { status[i] = JPEG_ENC_SHORT; return; }
+        memcpy(slot, header, head);
+        memcpy(slot + head, sink.bytes.data(), len);
     });
     return 0;
 }

@@ -28,11 +28,25 @@ enum {
 enum { JPEG_ENC_N_ZRL = 0, JPEG_ENC_N_NO_EOB = 1, JPEG_ENC_N_STUFFED = 2, JPEG_ENC_N_DUMMY_RIGHT = 3, JPEG_ENC_N_DUMMY_BOTTOM = 4, JPEG_ENC_N_COUNTERS = 5 };
 
 constexpr int kJpegEncHeaderBytes = 623;      // 2 + 18 + 2 * 69 + 19 + 2 * 33 + 2 * 183 + 14
+constexpr int kJpegEncDriBytes = 6;           // FF DD 00 04 hi lo, directly before SOS when the scan has a restart interval
+
+// Restart intervals (every entry below that takes `restart`: MCUs per interval, 0 = none, at most kJpegEncMaxRestart -- the
+// DRI segment holds 16 bits).  What a scan with an interval holds: jpeg_enc_math.h, "restart intervals".  Counters of their
+// own (optional, added to): markers written; intervals in front of a marker that ended on a byte boundary (no padding);
+// padded bytes in front of a marker that came out as 0xFF (and were stuffed like any data byte).
+constexpr int kJpegEncMaxRestart = 65535;
+enum { JPEG_ENC_R_RST = 0, JPEG_ENC_R_PAD_FREE = 1, JPEG_ENC_R_PAD_FF = 2, JPEG_ENC_R_COUNTERS = 3 };
+inline bool jpeg_enc_restart_ok(int restart) { return restart >= 0 && restart <= kJpegEncMaxRestart; }
+inline int jpeg_enc_header_bytes(int restart) { return kJpegEncHeaderBytes + (restart > 0 ? kJpegEncDriBytes : 0); }
 
 // what the encoder covers: 3 components, luma sampling 2x2 / 2x1 / 1x1, 1 <= W, H <= 16384 (JpegGeom::valid() is the DECODER's
 // coverage and is narrower: it leaves pictures with subsampled chroma at most 2 samples wide to Pillow)
 bool jpeg_enc_geom_ok(const JpegGeom& g);
 size_t jpeg_enc_max_scan_bytes(const JpegGeom& g);
+// With a restart interval the bound grows by 4 bytes per marker: the padding in front of a marker adds less than one data byte
+// (which stuffing can double), the marker itself two bytes that are never stuffed.
+size_t jpeg_enc_restart_markers(const JpegGeom& g, int restart);
+size_t jpeg_enc_max_scan_bytes(const JpegGeom& g, int restart);
 
 // Launch plan of the device encoder (jpeg_enc.hip), pure: no HIP call, no global state; integers in, integers out.  The
 // workspace of a chunk of n frames whose scans go into slots of slot_bytes bytes holds, 16-byte aligned one after another:
@@ -41,6 +55,9 @@ size_t jpeg_enc_max_scan_bytes(const JpegGeom& g);
 //   raw   u32 [n][raw_words]  the unstuffed stream, big-endian words; min(slot_bytes, the bound) bytes: unstuffed bytes never
 //                             exceed stuffed ones, so a frame that does not fit here does not fit its slot either
 //   ff    u32 [n][ff_chunks]  0xFF bytes per chunk of kJpegEncStuffChunk raw bytes, then (scanned in place) the count before it
+// and, with a restart interval only (the unstuffed stream then holds the padding and the markers too):
+//   seg   u32 [n][markers + 1]  padded bits of every interval with its marker, then (scanned in place) its first bit
+//   mark  u32 [n][markers]      byte offset of every marker in the unstuffed stream; bit 31: the byte in front of it is padded
 constexpr int kJpegEncStuffChunk = 64;
 struct JpegEncPlan {
     const char* error;          // non-null: the launchers refuse these arguments
@@ -50,18 +67,26 @@ struct JpegEncPlan {
     unsigned block_wgs;         // block stage: workgroups of 32 blocks over all frames
     unsigned entropy_wgs_x;     // entropy stage: workgroups of 256 blocks per frame (grid y = n)
     unsigned stuff_wgs_x;       // stuffing passes: workgroups of 256 chunks per frame (grid y = n)
+    int restart;                // MCUs per restart interval, 0: none (then markers, off_seg and off_mark are 0)
+    size_t markers;             // per frame
+    size_t off_seg, off_mark;
 };
-JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes);
+JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes, int restart = 0);
 
 // quant u16 [3][64], natural order, rows Y / Cb / Cr (the decoder's table layout); quality 1..100
 void jpeg_enc_quant(int quality, uint16_t* quant);
 // the header of every frame of geometry g at this quality: exactly kJpegEncHeaderBytes bytes
 void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out);
+// the same with DRI in front of SOS when restart > 0: jpeg_enc_header_bytes(restart) bytes
+void jpeg_enc_header(const JpegGeom& g, int quality, int restart, uint8_t* out);
 
 // stage 1, one frame: rgb u8 [H][W][3] -> coef int16 [g.blocks()][64]; dummy2 (optional) += {right-edge, bottom-edge} dummy blocks
 void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2);
 // stage 2, one frame: -> *len = the bytes the scan takes (with EOI), written to out only when they fit cap.  counters
 // (optional, JPEG_ENC_N_*) are added to, for frames that fit and frames that do not alike.
 int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, uint8_t* out, size_t cap, size_t* len, uint64_t* counters);
+// the same with a restart interval; rst_counters (optional, JPEG_ENC_R_*) are added to likewise
+int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, uint64_t* counters,
+                  uint64_t* rst_counters);
 
 }  // namespace tstar

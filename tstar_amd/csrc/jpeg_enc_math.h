@@ -245,6 +245,21 @@ TSTAR_JHD void scan_block(const ScanGeom& g, int k, int* comp, int* block, int* 
     }
 }
 
+// ---------------------------------------------------------------------------------------------- restart intervals
+// A scan with a restart interval of R MCUs (R >= 1) is cut behind every R-th MCU but the last: the entropy coder fills the
+// current byte with one-bits, RSTn follows (FF D0 + n mod 8, n counting the markers of the scan from 0) and every component's
+// DC predictor starts from 0 again.  The scan then holds (MCUs - 1) / R markers and one interval more.
+// scan_block under a restart interval (0: none): the first block of a component in an interval has no predecessor
+TSTAR_JHD void scan_block_rst(const ScanGeom& g, int k, int interval, int* comp, int* block, int* pred_block) {
+    scan_block(g, k, comp, block, pred_block);
+    if (interval > 0) {
+        const int per = g.per_mcu(), m = k / per, j = k % per;
+        if (m % interval == 0 && (j == 0 || j >= per - 2)) *pred_block = -1;
+    }
+}
+// Bits an interval's end adds to the scan at most: 7 pad bits and the 16 of the marker
+constexpr int kRestartBits = 7 + 16;
+
 // Dummy luma blocks (beyond the real ceil(W / 8) x ceil(H / 8) blocks, inside the last MCU column / row): AC zero, DC that of
 // a REAL block in the same MCU.  A right-edge dummy takes the block to its left.  Every block of a bottom-edge dummy row takes
 // the block that precedes the row in the MCU's order, the last block of the row above, which may be a right-edge dummy itself

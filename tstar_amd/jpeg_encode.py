@@ -1,6 +1,8 @@
 """Baseline JPEG encode of resident frames: the bytes ``PIL.Image.fromarray(frame).save(buf, "JPEG", quality=q,
 subsampling=s)`` writes, for quality 1..100 and subsampling 4:2:0 / 4:2:2 / 4:4:4 (csrc/jpeg_enc.hip on the device,
-csrc/jpeg_enc_host.cpp on the host).
+csrc/jpeg_enc_host.cpp on the host).  ``restart_rows=`` / ``restart_blocks=`` on every entry are Pillow's
+``restart_marker_rows=`` / ``restart_marker_blocks=``: a DRI segment and RSTn markers, which cut a scan into pieces the device
+decoder takes one lane each.
 
 The reference's exits are JPEG: ``encode_image_to_base64`` (TStar/utilites.py:15-37) for the grounding frames and the QA
 keyframes, ``.jpg`` files for the keyframes (TStarFramework.py:136-146).  Here the frames never leave HBM as pixels: the
@@ -12,6 +14,7 @@ from __future__ import annotations
 
 import base64
 import ctypes as C
+import operator
 import os
 import struct
 from typing import List, Optional, Sequence
@@ -22,6 +25,8 @@ SUBSAMPLINGS = {"4:2:0": (2, 2), "4:2:2": (2, 1), "4:4:4": (1, 1)}
 _PIL_SUBSAMPLING = {0: "4:4:4", 1: "4:2:2", 2: "4:2:0"}
 STATUS_OK, STATUS_SHORT, STATUS_BAD_COEF = 0, 1, 2
 COUNTERS = ("zrl", "no_eob", "stuffed", "dummy_right", "dummy_bottom")
+RESTART_COUNTERS = ("rst", "pad_free", "pad_ff")        # markers; intervals that ended byte-aligned; padded bytes that became 0xFF
+RESTART_LIMIT = 65535          # MCUs per interval: what the 16 bits of DRI hold
 AVI_LIMIT = 1 << 30            # a RIFF AVI of this size or more needs OpenDML index segments, which nobody here writes or reads
 
 
@@ -40,26 +45,73 @@ def _quality(quality) -> int:
     return q
 
 
+def restart_interval(W: int, H: int, subsampling="4:2:0", restart_rows=None, restart_blocks=None) -> int:
+    """Pillow's ``restart_marker_rows`` / ``restart_marker_blocks`` -> MCUs per restart interval (0: no DRI, no markers).  Rows
+    count MCU rows and win over blocks (MCUs) when both are given; 0 / None mean "not given".  A negative or non-integer value,
+    and an interval above 65535 MCUs, raise ValueError: DRI holds 16 bits (libjpeg itself clamps rows to 65535 MCUs and writes
+    the low 16 bits of a larger block count into DRI while it places the markers by the full count, a file no decoder follows)."""
+    rows, blocks = _restart_values(restart_rows, restart_blocks)
+    hs, _ = sampling(subsampling)
+    interval = rows * ((int(W) + 8 * hs - 1) // (8 * hs)) if rows else blocks
+    if interval > RESTART_LIMIT:
+        raise ValueError(f"JPEG restart interval of {interval} MCUs: DRI holds at most {RESTART_LIMIT}")
+    return interval
+
+
+def _restart_values(restart_rows, restart_blocks) -> tuple:
+    """The two keywords as non-negative ints (None -> 0); what can be refused without knowing the picture is refused here."""
+    vals = []
+    for name, v in (("restart_rows", restart_rows), ("restart_blocks", restart_blocks)):
+        if v is None:
+            v = 0
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            v = operator.index(v)
+        except TypeError:
+            raise ValueError(f"JPEG {name} {v!r}: expected a non-negative integer") from None
+        if v < 0:
+            raise ValueError(f"JPEG {name} {v!r}: expected a non-negative integer")
+        vals.append(v)
+    rows, blocks = vals
+    if (rows or blocks) > RESTART_LIMIT:               # a row is at least one MCU
+        raise ValueError(f"JPEG restart interval of {rows or blocks} MCUs or more: DRI holds at most {RESTART_LIMIT}")
+    return rows, blocks
+
+
 class Plan:
-    """tstar_jpeg_encode_plan: sizes and launch shape for n frames of W x H whose scans go into slots of slot_bytes."""
+    """tstar_jpeg_encode_plan: sizes and launch shape for n frames of W x H whose scans go into slots of slot_bytes.  With
+    ``restart`` (MCUs per interval) tstar_jpeg_encode_plan_rst: the bounds hold the markers and the padding, and ``markers`` is
+    their number per frame."""
     FIELDS = ("blocks", "coef_bytes", "max_scan_bytes", "header_bytes", "workspace_bytes", "block_wgs", "entropy_wgs_x", "stuff_wgs_x")
 
-    def __init__(self, W: int, H: int, hs: int, vs: int, n: int = 1, slot_bytes: int = 2):
+    def __init__(self, W: int, H: int, hs: int, vs: int, n: int = 1, slot_bytes: int = 2, restart: int = 0):
         from . import _lib
         out = (C.c_size_t * 8)()
-        _lib.check(_lib.load().tstar_jpeg_encode_plan(W, H, hs, vs, n, slot_bytes, out), "tstar_jpeg_encode_plan")
+        self.restart, self.markers = int(restart), 0
+        if restart:
+            out2 = (C.c_size_t * 2)()
+            _lib.check(_lib.load().tstar_jpeg_encode_plan_rst(W, H, hs, vs, n, slot_bytes, restart, out, out2), "tstar_jpeg_encode_plan_rst")
+            self.markers = int(out2[1])
+        else:
+            _lib.check(_lib.load().tstar_jpeg_encode_plan(W, H, hs, vs, n, slot_bytes, out), "tstar_jpeg_encode_plan")
         for k, v in zip(self.FIELDS, out):
             setattr(self, k, int(v))
 
 
-def header(W: int, H: int, quality: int = 75, subsampling="4:2:0") -> bytes:
-    """SOI .. SOS as Pillow writes them from an array."""
+def header(W: int, H: int, quality: int = 75, subsampling="4:2:0", restart_rows=None, restart_blocks=None) -> bytes:
+    """SOI .. SOS as Pillow writes them from an array (with a restart interval: DRI directly before SOS)."""
     from . import _lib
     hs, vs = sampling(subsampling)
+    restart = restart_interval(W, H, subsampling, restart_rows, restart_blocks)
     buf = np.empty(1024, dtype=np.uint8)
     n = C.c_size_t(0)
-    _lib.check(_lib.load().tstar_jpeg_encode_header(W, H, _quality(quality), hs, vs, buf.ctypes.data, buf.size, C.byref(n)),
-               "tstar_jpeg_encode_header")
+    if restart:
+        _lib.check(_lib.load().tstar_jpeg_encode_header_rst(W, H, _quality(quality), hs, vs, restart, buf.ctypes.data, buf.size, C.byref(n)),
+                   "tstar_jpeg_encode_header_rst")
+    else:
+        _lib.check(_lib.load().tstar_jpeg_encode_header(W, H, _quality(quality), hs, vs, buf.ctypes.data, buf.size, C.byref(n)),
+                   "tstar_jpeg_encode_header")
     return buf[:n.value].tobytes()
 
 
@@ -88,50 +140,67 @@ def blocks_host(frames, quality: int = 75, subsampling="4:2:0", idx: Optional[Se
     return coef, quant
 
 
-def scan_host(coef: np.ndarray, W: int, H: int, subsampling="4:2:0", slot_bytes: Optional[int] = None, threads: int = 0, counters=None):
-    """Scan stage of the host twin: coef int16 [n, blocks * 64] -> (list of scans (None where the status is not 0), lengths, status)."""
+def scan_host(coef: np.ndarray, W: int, H: int, subsampling="4:2:0", slot_bytes: Optional[int] = None, threads: int = 0, counters=None,
+              restart_rows=None, restart_blocks=None, restart_counters=None):
+    """Scan stage of the host twin: coef int16 [n, blocks * 64] -> (list of scans (None where the status is not 0), lengths, status).
+    ``restart_counters``: uint64 [3] (RESTART_COUNTERS), added to."""
     from . import _lib
     hs, vs = sampling(subsampling)
+    restart = restart_interval(W, H, subsampling, restart_rows, restart_blocks)
     coef = np.ascontiguousarray(coef, dtype=np.int16)
     n = coef.shape[0]
-    p = Plan(W, H, hs, vs, n)
+    p = Plan(W, H, hs, vs, n, restart=restart)
     assert coef.size == n * p.blocks * 64, "coefficients do not match the geometry"
     slot = p.max_scan_bytes if slot_bytes is None else int(slot_bytes)
     out = np.empty((n, slot), dtype=np.uint8)
     lengths = np.zeros(n, dtype=np.uint32)
     status = np.full(n, -1, dtype=np.int32)
-    _lib.check(_lib.load().tstar_jpeg_encode_scan_host(coef.ctypes.data, n, W, H, hs, vs, out.ctypes.data, slot, lengths.ctypes.data,
-                                                       status.ctypes.data, threads, _counter_ptr(counters)), "tstar_jpeg_encode_scan_host")
+    if restart or restart_counters is not None:
+        _lib.check(_lib.load().tstar_jpeg_encode_scan_host_rst(coef.ctypes.data, n, W, H, hs, vs, restart, out.ctypes.data, slot,
+                                                               lengths.ctypes.data, status.ctypes.data, threads, _counter_ptr(counters),
+                                                               _counter_ptr(restart_counters, RESTART_COUNTERS)),
+                   "tstar_jpeg_encode_scan_host_rst")
+    else:
+        _lib.check(_lib.load().tstar_jpeg_encode_scan_host(coef.ctypes.data, n, W, H, hs, vs, out.ctypes.data, slot, lengths.ctypes.data,
+                                                           status.ctypes.data, threads, _counter_ptr(counters)), "tstar_jpeg_encode_scan_host")
     return [out[i, :lengths[i]].tobytes() if status[i] == 0 else None for i in range(n)], lengths, status
 
 
-def _counter_ptr(counters):
+def _counter_ptr(counters, names=COUNTERS):
     if counters is None:
         return None
-    assert isinstance(counters, np.ndarray) and counters.dtype == np.uint64 and counters.size == len(COUNTERS)
+    assert isinstance(counters, np.ndarray) and counters.dtype == np.uint64 and counters.size == len(names)
     return counters.ctypes.data
 
 
 def encode_host(frames, quality: int = 75, subsampling="4:2:0", idx: Optional[Sequence[int]] = None, slot_bytes: Optional[int] = None,
-                threads: int = 0, counters=None, out: Optional[np.ndarray] = None):
+                threads: int = 0, counters=None, out: Optional[np.ndarray] = None, restart_rows=None, restart_blocks=None,
+                restart_counters=None):
     """Whole files from the host twin -> (out uint8 [n, slot_bytes], lengths, status).  ``slot_bytes`` defaults to what holds any
     file of the geometry; ``out`` may be a caller's buffer of at least n * slot_bytes bytes (the capacity tests pass one)."""
     from . import _lib
     a = _host_array(frames)
     hs, vs = sampling(subsampling)
     N, H, W, _ = a.shape
+    restart = restart_interval(W, H, subsampling, restart_rows, restart_blocks)
     ii = np.ascontiguousarray(np.arange(N) if idx is None else idx, dtype=np.int32)
     n = len(ii)
-    p = Plan(W, H, hs, vs, n)
+    p = Plan(W, H, hs, vs, n, restart=restart)
     slot = p.header_bytes + p.max_scan_bytes if slot_bytes is None else int(slot_bytes)
     if out is None:
         out = np.empty((n, slot), dtype=np.uint8)
     assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= n * slot
     lengths = np.zeros(n, dtype=np.uint32)
     status = np.full(n, -1, dtype=np.int32)
-    _lib.check(_lib.load().tstar_jpeg_encode_host(a.ctypes.data, N, H, W, ii.ctypes.data, n, _quality(quality), hs, vs, out.ctypes.data,
-                                                  slot, lengths.ctypes.data, status.ctypes.data, threads, _counter_ptr(counters)),
-               "tstar_jpeg_encode_host")
+    if restart or restart_counters is not None:
+        _lib.check(_lib.load().tstar_jpeg_encode_host_rst(a.ctypes.data, N, H, W, ii.ctypes.data, n, _quality(quality), hs, vs, restart,
+                                                          out.ctypes.data, slot, lengths.ctypes.data, status.ctypes.data, threads,
+                                                          _counter_ptr(counters), _counter_ptr(restart_counters, RESTART_COUNTERS)),
+                   "tstar_jpeg_encode_host_rst")
+    else:
+        _lib.check(_lib.load().tstar_jpeg_encode_host(a.ctypes.data, N, H, W, ii.ctypes.data, n, _quality(quality), hs, vs, out.ctypes.data,
+                                                      slot, lengths.ctypes.data, status.ctypes.data, threads, _counter_ptr(counters)),
+                   "tstar_jpeg_encode_host")
     return out, lengths, status
 
 
@@ -144,14 +213,16 @@ def _typical_slot(W: int, H: int, p: Plan) -> int:
 class DeviceEncoder:
     """Buffers and launches of the device path for frames of one geometry, reused chunk after chunk."""
 
-    def __init__(self, W: int, H: int, quality: int, subsampling, chunk: int, slot_bytes: Optional[int] = None, device=None):
+    def __init__(self, W: int, H: int, quality: int, subsampling, chunk: int, slot_bytes: Optional[int] = None, device=None,
+                 restart: int = 0):
         import torch
         self.W, self.H, self.quality = W, H, _quality(quality)
         self.hs, self.vs = sampling(subsampling)
         self.chunk = int(chunk)
-        one = Plan(W, H, self.hs, self.vs, 1)
+        self.restart = int(restart)                    # MCUs per restart interval; 0: the launches of a scan without markers
+        one = Plan(W, H, self.hs, self.vs, 1, restart=self.restart)
         self.slot = int(slot_bytes) if slot_bytes else _typical_slot(W, H, one)
-        self.plan = Plan(W, H, self.hs, self.vs, self.chunk, self.slot)
+        self.plan = Plan(W, H, self.hs, self.vs, self.chunk, self.slot, self.restart)
         self.max_scan_bytes = one.max_scan_bytes
         self.device = device
         u8 = dict(dtype=torch.uint8, device=device)
@@ -159,6 +230,8 @@ class DeviceEncoder:
         self.work = torch.empty(self.plan.workspace_bytes, **u8)
         self.out = torch.empty((self.chunk, self.slot), **u8)
         self.meta = torch.empty((2, self.chunk), dtype=torch.int32, device=device)      # lengths (u32 bits), status
+        self.rst = torch.zeros((self.chunk, len(RESTART_COUNTERS)), dtype=torch.int32, device=device) if self.restart else None
+        self.restart_counts = np.zeros(len(RESTART_COUNTERS), dtype=np.int64)           # summed by collect()
         self.block_ms = self.entropy_ms = 0.0
         self.timed = False
 
@@ -177,9 +250,15 @@ class DeviceEncoder:
                                                 self.coef.data_ptr(), None, s), "tstar_jpeg_encode_blocks")
         if ev:
             ev[1].record()
-        _lib.check(lib.tstar_jpeg_encode_scan(self.coef.data_ptr(), n, self.W, self.H, self.hs, self.vs, self.out.data_ptr(), self.slot,
-                                              self.meta[0].data_ptr(), self.meta[1].data_ptr(), self.work.data_ptr(), self.work.numel(), s),
-                   "tstar_jpeg_encode_scan")
+        if self.restart:
+            _lib.check(lib.tstar_jpeg_encode_scan_rst(self.coef.data_ptr(), n, self.W, self.H, self.hs, self.vs, self.restart,
+                                                      self.out.data_ptr(), self.slot, self.meta[0].data_ptr(), self.meta[1].data_ptr(),
+                                                      self.work.data_ptr(), self.work.numel(), self.rst.data_ptr(), s),
+                       "tstar_jpeg_encode_scan_rst")
+        else:
+            _lib.check(lib.tstar_jpeg_encode_scan(self.coef.data_ptr(), n, self.W, self.H, self.hs, self.vs, self.out.data_ptr(), self.slot,
+                                                  self.meta[0].data_ptr(), self.meta[1].data_ptr(), self.work.data_ptr(), self.work.numel(), s),
+                       "tstar_jpeg_encode_scan")
         if ev:
             ev[2].record()
             ev[2].synchronize()
@@ -187,13 +266,15 @@ class DeviceEncoder:
             self.entropy_ms += ev[1].elapsed_time(ev[2])
 
     def collect(self, n: int):
-        """ONE device -> host read of lengths and status, then the used bytes of the slots in one copy -> (list of scans (None where
-        the slot was short), status)."""
+        """ONE device -> host read of lengths and status (with a restart interval a second one, of the counters), then the used bytes
+        of the slots in one copy -> (list of scans (None where the slot was short), status)."""
         import torch
         meta = self.meta[:, :n].cpu().numpy()
         lengths, status = meta[0].view(np.uint32).astype(np.int64), meta[1]
         if (status == STATUS_BAD_COEF).any():
             raise ValueError("JPEG encode: a coefficient outside 8-bit baseline JPEG")
+        if self.rst is not None:                       # the frames that were written: a short frame is counted when it is encoded again
+            self.restart_counts += self.rst[:n].cpu().numpy().astype(np.int64)[status == STATUS_OK].sum(axis=0)
         take = np.where(status == STATUS_OK, lengths, 0)
         cols = torch.arange(self.slot, device=self.out.device)[None, :]
         used = self.out[:n][cols < torch.as_tensor(take, device=self.out.device)[:, None]].cpu().numpy()
@@ -207,18 +288,19 @@ def encode_chunk_size(blocks: int, n_frames: int, chunk: Optional[int] = None) -
     return jpeg.device_entropy_chunk(blocks, n_frames, chunk)
 
 
-def _encode_device(frames, idx, quality, subsampling, chunk=None, slot_bytes=None, stats=None) -> List[bytes]:
-    """frames: cuda uint8 [N,H,W,3]; idx: int32 cuda tensor of frame numbers -> the JPEG files."""
+def _encode_device(frames, idx, quality, subsampling, chunk=None, slot_bytes=None, stats=None, restart: int = 0) -> List[bytes]:
+    """frames: cuda uint8 [N,H,W,3]; idx: int32 cuda tensor of frame numbers -> the JPEG files.  restart: MCUs per interval."""
     import torch
     N, H, W, _ = (int(v) for v in frames.shape)
     hs, vs = sampling(subsampling)
     n = int(idx.numel())
     if n == 0:
         return []
-    head = header(W, H, quality, subsampling)
-    one = Plan(W, H, hs, vs, 1)
+    head = header(W, H, quality, subsampling, restart_blocks=restart)
+    one = Plan(W, H, hs, vs, 1, restart=restart)
+    counts = np.zeros(len(RESTART_COUNTERS), dtype=np.int64)
     with torch.cuda.device(frames.device):
-        enc = DeviceEncoder(W, H, quality, subsampling, encode_chunk_size(one.blocks, n, chunk), slot_bytes, frames.device)
+        enc = DeviceEncoder(W, H, quality, subsampling, encode_chunk_size(one.blocks, n, chunk), slot_bytes, frames.device, restart)
         enc.timed = stats is not None
         out: List[Optional[bytes]] = []
         short: List[int] = []
@@ -232,13 +314,14 @@ def _encode_device(frames, idx, quality, subsampling, chunk=None, slot_bytes=Non
             stats["block_ms"] = stats.get("block_ms", 0.0) + enc.block_ms
             stats["entropy_ms"] = stats.get("entropy_ms", 0.0) + enc.entropy_ms
             stats["retried"] = stats.get("retried", 0) + len(short)
+        counts += enc.restart_counts
         if short:
             if enc.slot >= enc.max_scan_bytes:
                 raise RuntimeError("JPEG encode: a scan did not fit the bound of its geometry")
             del enc
             # frames the typical slot was short of: once more into slots that hold any scan, a few at a time
             step = max(1, min(len(short), (256 << 20) // one.max_scan_bytes))
-            big = DeviceEncoder(W, H, quality, subsampling, step, one.max_scan_bytes, frames.device)
+            big = DeviceEncoder(W, H, quality, subsampling, step, one.max_scan_bytes, frames.device, restart)
             for s0 in range(0, len(short), step):
                 ids = short[s0:s0 + step]
                 big.launch(frames, idx[torch.as_tensor(ids, device=idx.device, dtype=torch.long)])
@@ -247,27 +330,37 @@ def _encode_device(frames, idx, quality, subsampling, chunk=None, slot_bytes=Non
                     raise RuntimeError("JPEG encode: a scan did not fit the bound of its geometry")
                 for i, sc in zip(ids, scans):
                     out[i] = sc
+            counts += big.restart_counts
+    if stats is not None and restart:
+        for k, v in zip(RESTART_COUNTERS, counts):
+            stats[k] = stats.get(k, 0) + int(v)
     return [head + sc for sc in out]
 
 
 def encode_frames(frames, quality: int = 75, subsampling="4:2:0", device: bool = True, chunk: Optional[int] = None,
-                  slot_bytes: Optional[int] = None, stats: Optional[dict] = None, threads: int = 0) -> List[bytes]:
-    """One JPEG file per frame, byte for byte Pillow's ``Image.fromarray(frame).save(buf, "JPEG", quality=, subsampling=)``.
+                  slot_bytes: Optional[int] = None, stats: Optional[dict] = None, threads: int = 0, restart_rows=None,
+                  restart_blocks=None) -> List[bytes]:
+    """One JPEG file per frame, byte for byte Pillow's ``Image.fromarray(frame).save(buf, "JPEG", quality=, subsampling=,
+    restart_marker_rows=restart_rows, restart_marker_blocks=restart_blocks)``.
 
     ``frames``: a cuda uint8 tensor [n,H,W,3], or ``(store, secs)`` -- a FrameStore (RGB or NV12) and the logical seconds wanted,
     read straight from the store through the index list.  ``device=False``: the host twin on a numpy array [n,H,W,3] (the
     fallback a caller without a device can choose; there is no silent one).  ``chunk`` / ``slot_bytes`` override the device
-    path's frames per chunk and per-frame scan capacity (frames a slot is short of are encoded again at the bound)."""
+    path's frames per chunk and per-frame scan capacity (frames a slot is short of are encoded again at the bound).
+    ``restart_rows`` / ``restart_blocks``: a restart interval of that many MCU rows / MCUs (``restart_interval``; default none);
+    with ``stats`` the device path adds the RESTART_COUNTERS of the files it wrote."""
     quality = _quality(quality)
     sampling(subsampling)
+    _restart_values(restart_rows, restart_blocks)      # the values themselves, before anything is touched
     if isinstance(frames, tuple) and len(frames) == 2 and hasattr(frames[0], "fmt"):
         store, secs = frames
+        restart = restart_interval(store.shape[2], store.shape[1], subsampling, restart_rows, restart_blocks)
         if not device:
-            return encode_frames(store.host_frames(secs), quality, subsampling, device=False, threads=threads)
-        return _encode_store(store, secs, quality, subsampling, chunk, slot_bytes, stats)
+            return encode_frames(store.host_frames(secs), quality, subsampling, device=False, threads=threads, restart_blocks=restart)
+        return _encode_store(store, secs, quality, subsampling, chunk, slot_bytes, stats, restart)
     if not device:
         a = _host_array(frames)
-        out, lengths, status = encode_host(a, quality, subsampling, threads=threads)
+        out, lengths, status = encode_host(a, quality, subsampling, threads=threads, restart_rows=restart_rows, restart_blocks=restart_blocks)
         if (status != STATUS_OK).any():
             raise RuntimeError(f"JPEG encode (host): status {status.tolist()}")
         return [out[i, :lengths[i]].tobytes() for i in range(len(a))]
@@ -277,12 +370,13 @@ def encode_frames(frames, quality: int = 75, subsampling="4:2:0", device: bool =
         raise ValueError("encode_frames: expected a cuda uint8 tensor [n,H,W,3] or (store, secs); pass device=False for numpy frames")
     if 0 in frames.shape[1:]:
         raise ValueError("encode_frames: empty frames")
+    restart = restart_interval(int(frames.shape[2]), int(frames.shape[1]), subsampling, restart_rows, restart_blocks)
     frames = frames.contiguous()
     idx = torch.arange(frames.shape[0], dtype=torch.int32, device=frames.device)
-    return _encode_device(frames, idx, quality, subsampling, chunk, slot_bytes, stats)
+    return _encode_device(frames, idx, quality, subsampling, chunk, slot_bytes, stats, restart)
 
 
-def _encode_store(store, secs, quality, subsampling, chunk, slot_bytes, stats) -> List[bytes]:
+def _encode_store(store, secs, quality, subsampling, chunk, slot_bytes, stats, restart: int = 0) -> List[bytes]:
     import torch
     from . import _lib
     N, H, W, _ = store.shape
@@ -298,7 +392,7 @@ def _encode_store(store, secs, quality, subsampling, chunk, slot_bytes, stats) -
         for s0 in range(0, len(secs), step):
             lease = store.lease(secs[s0:s0 + step])
             try:
-                out += _encode_device(lease.frames, lease.idx, quality, subsampling, chunk, slot_bytes, stats)
+                out += _encode_device(lease.frames, lease.idx, quality, subsampling, chunk, slot_bytes, stats, restart)
             finally:
                 lease.done()
         return out
@@ -313,20 +407,21 @@ def _encode_store(store, secs, quality, subsampling, chunk, slot_bytes, stats) -
             m = int(part.numel())
             _lib.check(_lib.load().tstar_nv12_to_rgb(store.frames.data_ptr(), N, H, W, part.data_ptr(), m, rgb.data_ptr(),
                                                       _lib.stream_ptr()), "tstar_nv12_to_rgb")
-            out += _encode_device(rgb, torch.arange(m, dtype=torch.int32, device=dev), quality, subsampling, chunk, slot_bytes, stats)
+            out += _encode_device(rgb, torch.arange(m, dtype=torch.int32, device=dev), quality, subsampling, chunk, slot_bytes, stats, restart)
     return out
 
 
-def frames_to_base64(store, secs=None, quality: int = 75, subsampling="4:2:0") -> List[str]:
+def frames_to_base64(store, secs=None, quality: int = 75, subsampling="4:2:0", restart_rows=None, restart_blocks=None) -> List[str]:
     """The reference's ``encode_image_to_base64`` (TStar/utilites.py:15-37: Pillow's default JPEG, base64, utf-8) for frames that
     never left HBM as pixels.  ``store``: a FrameStore with ``secs``, or frames as ``encode_frames`` takes them (a numpy array
     goes through the host twin)."""
+    rst = dict(restart_rows=restart_rows, restart_blocks=restart_blocks)
     if secs is not None:
-        files = encode_frames((store, secs), quality, subsampling)
+        files = encode_frames((store, secs), quality, subsampling, **rst)
     elif isinstance(store, np.ndarray):
-        files = encode_frames(store, quality, subsampling, device=False)
+        files = encode_frames(store, quality, subsampling, device=False, **rst)
     else:
-        files = encode_frames(store, quality, subsampling)
+        files = encode_frames(store, quality, subsampling, **rst)
     return [base64.b64encode(f).decode("utf-8") for f in files]
 
 
@@ -401,18 +496,20 @@ def write_mjpeg_file(path: str, files: Sequence[bytes], W: int, H: int, fps: flo
 
 
 def save_mjpeg(store, path: str, quality: int = 90, subsampling="4:2:0", fps: Optional[float] = None, device: bool = True,
-               piece: int = 1024) -> int:
+               piece: int = 1024, restart_rows=None, restart_blocks=None) -> int:
     """Write a FrameStore (or, with ``device=False``, a numpy array [n,H,W,3]) as Motion-JPEG at its LOGICAL rate (1 frame per
     second unless ``fps`` is given), so that ``open_video(path)`` gives back a store of the same seconds.  Returns the frames
-    written."""
+    written.  ``restart_rows`` / ``restart_blocks`` (default: none) cut every frame's scan into restart intervals, which the
+    device entropy decoder of ``open_video`` takes one lane each instead of splitting one long scan."""
+    rst = dict(restart_rows=restart_rows, restart_blocks=restart_blocks)
     if hasattr(store, "fmt"):
         N, H, W, _ = store.shape
         files: List[bytes] = []
         for s0 in range(0, N, piece):
-            files += encode_frames((store, range(s0, min(N, s0 + piece))), quality, subsampling, device=device)
+            files += encode_frames((store, range(s0, min(N, s0 + piece))), quality, subsampling, device=device, **rst)
     else:
         a = _host_array(store)
         N, H, W, _ = a.shape
-        files = encode_frames(a, quality, subsampling, device=False) if not device else encode_frames(store, quality, subsampling)
+        files = encode_frames(a, quality, subsampling, device=False, **rst) if not device else encode_frames(store, quality, subsampling, **rst)
     write_mjpeg_file(path, files, W, H, 1.0 if fps is None else float(fps))
     return len(files)
