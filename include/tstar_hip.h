@@ -374,11 +374,30 @@ int tstar_image_guided_postprocess_host(const float* scores, const float* boxes_
  * The network is handed over as data (tstar_amd/yolo_world.py build_program): a float32 blob (BatchNorm folded), a
  * table of ops [n_ops][24] int32 over NHWC buffers [n_bufs][3] = (H, W, C), the max-sigmoid attention layers
  * [n_guides][5] = (embed, heads, guide_fc weight / bias offsets, per-head bias offset) and the head levels
- * [n_levels][8] = (embedding buffer, DFL buffer, map size, stride, offset of (exp(logit_scale), bias), 0, 0, 0). */
+ * [n_levels][8] = (embedding buffer, DFL buffer, map size, stride, offset of (exp(logit_scale), bias), 0, 0, 0).
+ *
+ * The words of an op (csrc/yolo_program.h is the definition, W_* in tstar_amd/yolo_world.py the mirror; unused words are 0):
+ *   word        0  1    2        3      4    5        6       7      8       9    10     11     12    13   14
+ *   conv        0  src  src_off  cin    dst  dst_off  cout    ks     stride  act  w_off  b_off  mode  aux  aux_off
+ *   pool 5x5    1  buf  src_off  C      buf  dst_off
+ *   up-copy     2  src  src_off  C      dst  dst_off  factor
+ *   attention   3  src  src_off  embed  dst  0        heads   guide
+ * src / dst / buf / aux are buffer indices, the offsets channel offsets inside them (channel concatenation is free), w_off / b_off float
+ * offsets into the blob (weights [cout][ks][ks][cin]; b_off < 0: no bias).  conv: ks 1 | 3, stride 1 | 2, pad ks / 2, act 0 none | 1 SiLU,
+ * mode 0 plain | 1 + residual read at channel aux_off of buffer aux | 2 * gate, buffer aux being [.., heads] (aux_off 0).  pool: 5 x 5 /
+ * stride 1 max pool in place.  up-copy: factor 1 copies, 2 upsamples (nearest).  attention: the max-sigmoid gate of attention layer
+ * `guide` (whose embed and heads words 3 and 6 repeat), one row of heads per source pixel into buffer dst.
+ * tstar_yolo_create refuses, as "malformed op N" plus the reason, every op the kernels cannot serve; a buffer must hold fewer than 2^31
+ * pixels at max_batch images. */
 typedef struct tstar_yolo tstar_yolo;
 int tstar_yolo_create(tstar_yolo** out, const float* h_blob, size_t n_blob, const int32_t* h_ops, int n_ops, int op_words,
                       const int32_t* h_bufs, int n_bufs, const int32_t* h_guides, int n_guides, const int32_t* h_levels,
                       int n_levels, int input_buf, int max_batch);
+/* Diagnostic (an added entry; tstar_abi_version() stays 3): every check tstar_yolo_create makes of its arguments, without a GPU and
+ * without creating anything.  TSTAR_OK, or TSTAR_ERR_ARG with the message tstar_yolo_create would give. */
+int tstar_yolo_check_program(const float* h_blob, size_t n_blob, const int32_t* h_ops, int n_ops, int op_words, const int32_t* h_bufs,
+                             int n_bufs, const int32_t* h_guides, int n_guides, const int32_t* h_levels, int n_levels, int input_buf,
+                             int max_batch);
 int tstar_yolo_destroy(tstar_yolo* h);
 int tstar_yolo_num_anchors(tstar_yolo* h);
 /* model.reparameterize(texts) (interface_heuristic.py:93): the cached CLIP text features float32 [Q,512] of query set

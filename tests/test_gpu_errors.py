@@ -389,65 +389,17 @@ def test_yolo_layer_op_entries_validate_their_arguments(env):
     det.close()
 
 
-def _crafted(mutate):
-    """A one-op program from yolo_ops_util, with ``mutate(ops, bufs)`` applied to the raw tables."""
-    import yolo_ops_util as OU
-    prog, _ = OU.conv_program([c for c in OU.CONV_CASES if c.name in ("t_res_silu", "t_gate2_silu", "d_stem_9x7")])
-    prog = dict(prog, ops=prog["ops"].copy(), bufs=prog["bufs"].copy())
-    mutate(prog["ops"], prog["bufs"])
-    return prog
-
-
 def test_yolo_create_refuses_ops_the_kernels_cannot_serve(env):
-    """Shapes that used to fail at the first forward (in the launcher) or not at all are refused by tstar_yolo_create.  Ops 0 / 1 / 2 of
-    the crafted program: a residual conv, a gated conv (20 channels, 10 heads), a direct-form conv (cin = 3, cout = 16)."""
+    """Shapes that used to fail at the first forward (in the launcher) or not at all are refused by tstar_yolo_create: the table of
+    yolo_ops_util.refused_programs (which tests/test_yolo_program_host.py runs through tstar_yolo_check_program without a GPU)."""
     L, lib, _ = env
     import yolo_ops_util as OU
-    from tstar_amd import yolo_world as Y
     from tstar_amd.yolo import YoloDetector
-    YoloDetector.from_program(_crafted(lambda ops, bufs: None), max_batch=1).close()          # the unmutated program is accepted
-
-    def cout_6(ops, bufs): ops[0, 6] = 6                                   # cout % 4
-    def dst_off_2(ops, bufs): ops[0, 5] = 2                                # dst_off % 4
-    def mode_3(ops, bufs): ops[0, 12] = 3
-    def res_off_2(ops, bufs): ops[0, 14] = 42                              # residual offset % 4
-    def res_past_end(ops, bufs): ops[0, 14] = 80                           # 80 + 20 > 96
-    def gate_heads(ops, bufs): bufs[ops[1, 13], 2] = 8                     # 20 channels over 8 heads
-    def gate_off(ops, bufs): ops[1, 14] = 4
-    def gate_map(ops, bufs): bufs[ops[1, 13], 0] += 1                      # gate buffer of another map size
-    def direct_res(ops, bufs): ops[2, 12] = 1; ops[2, 13] = ops[2, 4]; ops[2, 14] = 32
-    def direct_cout(ops, bufs): ops[2, 6] = 12                             # direct form needs cout % 16 (12 keeps the blob ranges valid)
-    for mut, op, msg in ((cout_6, 0, "multiples of 4"), (dst_off_2, 0, "multiples of 4"), (mode_3, 0, "unknown conv mode"),
-                         (res_off_2, 0, "residual channels"), (res_past_end, 0, "residual channels"), (gate_heads, 1, "divide evenly among the heads"),
-                         (gate_off, 1, "divide evenly among the heads"), (gate_map, 1, "output's map size"), (direct_res, 2, "no fused residual"),
-                         (direct_cout, 2, "cout % 16 == 0")):
-        with pytest.raises(L.TStarHipError, match=f"malformed op {op}.*{msg}"):
-            YoloDetector.from_program(_crafted(mut), max_batch=1)
-    # the direct form's 64 KB of weights: cin = 8, k = 3, cout = 256 is 72 KB
-    b, levels, x = OU._new_builder()
-    s, d = b.buf(4, 4, 8), b.buf(4, 4, 256)
-    b.conv(None, s, 0, d, 0, act=Y.ACT_NONE, raw=(np.zeros((256, 8, 3, 3), np.float32), None))
-    with pytest.raises(L.TStarHipError, match="malformed op 0.*64 KB of LDS"):
-        YoloDetector.from_program(Y.program_from_builder(b, levels, x), max_batch=1)
-    # attention op: embed / heads must be the guide's, the gate buffer the source's map
-    gprog, _ = OU.gate_program()
-    for col, val, msg in ((3, 16, "differ from the op's attention layer"), (6, 2, "malformed op 0")):
-        ops = gprog["ops"].copy()
-        ops[0, col] = val
+    YoloDetector.from_program(OU.crafted_program(), max_batch=1).close()                      # the unmutated program is accepted
+    for name, prog, msg in OU.refused_programs():
         with pytest.raises(L.TStarHipError, match=msg):
-            YoloDetector.from_program(dict(gprog, ops=ops), max_batch=1)
-    bufs = gprog["bufs"].copy()
-    bufs[gprog["ops"][0, 4], 1] += 1
-    with pytest.raises(L.TStarHipError, match="gate buffer must have the source's map size"):
-        YoloDetector.from_program(dict(gprog, bufs=bufs), max_batch=1)
-    # pool / up-copy of no channels
-    mprog, _, _ = OU.move_program()
-    for i in (0, len(OU.POOL_CASES)):
-        ops = mprog["ops"].copy()
-        ops[i, 3] = 0
-        with pytest.raises(L.TStarHipError, match=f"malformed op {i}"):
-            YoloDetector.from_program(dict(mprog, ops=ops), max_batch=1)
+            YoloDetector.from_program(prog, max_batch=1)
     # and the library is healthy afterwards
-    det = YoloDetector.from_program(_crafted(lambda ops, bufs: None), max_batch=1)
+    det = YoloDetector.from_program(OU.crafted_program(), max_batch=1)
     assert (det.run_ops(1)[:3] >= 0).all()
     det.close()

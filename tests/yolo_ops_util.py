@@ -1,6 +1,7 @@
-"""Crafted single-op programs for the YOLO-World layer ops (csrc/yolo.hip), their float64 references, the per-output error
+"""Crafted single-op programs for the YOLO-World layer ops (csrc/yolo.hip, csrc/yolo_conv.hip), their float64 references, the per-output error
 bound and the poison rules.  Used by tests/test_yolo_ops_reference.py (no GPU), tests/test_gpu_yolo_ops.py and
-tests/yolo_ops_probe.py.  numpy only at import time.
+tests/yolo_ops_probe.py; the programs tstar_yolo_create must refuse (REFUSED, below) by tests/test_yolo_program_host.py (no GPU)
+and tests/test_gpu_errors.py.  numpy only at import time.
 
 References
 ----------
@@ -495,11 +496,11 @@ def move_program():
     pools, ups = [], []
     for c in POOL_CASES:
         buf = b.buf(c.H, c.W, c.ld)
-        b.ops.append([Y.OP_POOL5, buf, c.soff, c.C, buf, c.doff])
+        b.pool5(buf, c.soff, c.C, c.doff)
         pools.append(buf)
     for c in UP_CASES:
         s, d = b.buf(c.Hs, c.Ws, c.sld), b.buf(c.Hs * c.f, c.Ws * c.f, c.dld)
-        b.ops.append([Y.OP_UPCOPY, s, c.soff, c.C, d, c.doff, c.f])
+        b.upcopy(s, c.soff, c.C, d, c.doff, c.f)
         ups.append((s, d))
     return Y.program_from_builder(b, levels, x), pools, ups
 
@@ -576,6 +577,69 @@ def gate_program():
         src, dst = b.buf(c.H, c.W, c.ld), b.buf(c.H, c.W, c.heads)
         gid = len(b.guides)
         b.guides.append(dict(embed=embed, heads=c.heads, w_off=b.put(d.W), b_off=b.put(d.b), bias_off=b.put(d.bias)))
-        b.ops.append([Y.OP_ATTN, src, c.off, embed, dst, 0, c.heads, gid])
+        b.attn(src, c.off, embed, dst, c.heads, gid)
         where.append((src, dst))
     return Y.program_from_builder(b, levels, x), where
+
+
+# ------------------------------------------------------------------------------------------ programs the checker refuses
+def crafted_program(mutate=None):
+    """Ops 0 / 1 / 2: a residual conv, a gated conv (20 channels, 10 heads), a direct-form conv (cin = 3, cout = 16), with
+    ``mutate(ops, bufs)`` applied to copies of the raw tables."""
+    prog, _ = conv_program([c for c in CONV_CASES if c.name in ("t_res_silu", "t_gate2_silu", "d_stem_9x7")])
+    prog = dict(prog, ops=prog["ops"].copy(), bufs=prog["bufs"].copy())
+    if mutate:
+        mutate(prog["ops"], prog["bufs"])
+    return prog
+
+
+def _mutated(prog, op_words=(), buf_words=()):
+    """``prog`` with ops[i, word] = value for every (i, word, value) and bufs[ops[i, which], word] += delta for every
+    (i, which, word, delta)."""
+    ops, bufs = prog["ops"].copy(), prog["bufs"].copy()
+    for i, word, value in op_words:
+        ops[i, word] = value
+    for i, which, word, delta in buf_words:
+        bufs[ops[i, which], word] += delta
+    return dict(prog, ops=ops, bufs=bufs)
+
+
+def _lds_72k_program():
+    """The direct form's 64 KB of weights: cin = 8, k = 3, cout = 256 is 72 KB."""
+    b, levels, x = _new_builder()
+    s, d = b.buf(4, 4, 8), b.buf(4, 4, 256)
+    b.conv(None, s, 0, d, 0, act=Y.ACT_NONE, raw=(np.zeros((256, 8, 3, 3), np.float32), None))
+    return Y.program_from_builder(b, levels, x)
+
+
+def refused_programs():
+    """[(name, program, regex the error must match)]: shapes that used to fail at the first forward (in the launcher) or not at
+    all.  The regexes are those tests/test_gpu_errors.py has always asserted."""
+    crafted = crafted_program()
+    rows = []
+
+    def conv_row(name, op, msg, op_words=(), buf_words=()):
+        rows.append((name, _mutated(crafted, op_words, buf_words), f"malformed op {op}.*{msg}"))
+
+    conv_row("cout_6", 0, "multiples of 4", [(0, Y.W_COUT, 6)])                                        # cout % 4
+    conv_row("dst_off_2", 0, "multiples of 4", [(0, Y.W_DST_OFF, 2)])                                  # dst_off % 4
+    conv_row("mode_3", 0, "unknown conv mode", [(0, Y.W_MODE, 3)])
+    conv_row("res_off_2", 0, "residual channels", [(0, Y.W_AUX_OFF, 42)])                              # residual offset % 4
+    conv_row("res_past_end", 0, "residual channels", [(0, Y.W_AUX_OFF, 80)])                           # 80 + 20 > 96
+    conv_row("gate_heads", 1, "divide evenly among the heads", buf_words=[(1, Y.W_AUX, Y.BUF_C, -2)]) # 20 channels over 8 heads
+    conv_row("gate_off", 1, "divide evenly among the heads", [(1, Y.W_AUX_OFF, 4)])
+    conv_row("gate_map", 1, "output's map size", buf_words=[(1, Y.W_AUX, Y.BUF_H, 1)])                # gate buffer of another map size
+    conv_row("direct_res", 2, "no fused residual",
+             [(2, Y.W_MODE, Y.MODE_RESIDUAL), (2, Y.W_AUX, int(crafted["ops"][2, Y.W_DST])), (2, Y.W_AUX_OFF, 32)])
+    conv_row("direct_cout", 2, "cout % 16 == 0", [(2, Y.W_COUT, 12)])      # direct form needs cout % 16 (12 keeps the blob ranges valid)
+    rows.append(("direct_72k", _lds_72k_program(), "malformed op 0.*64 KB of LDS"))
+    # attention op: embed / heads must be the guide's, the gate buffer the source's map
+    gprog, _ = gate_program()
+    rows.append(("attn_embed", _mutated(gprog, [(0, Y.W_EMBED, 16)]), "differ from the op's attention layer"))
+    rows.append(("attn_heads", _mutated(gprog, [(0, Y.W_HEADS, 2)]), "malformed op 0"))
+    rows.append(("attn_map", _mutated(gprog, buf_words=[(0, Y.W_DST, Y.BUF_W, 1)]), "gate buffer must have the source's map size"))
+    # pool / up-copy of no channels
+    mprog, _, _ = move_program()
+    for i in (0, len(POOL_CASES)):
+        rows.append((f"move_{i}_no_channels", _mutated(mprog, [(i, Y.W_C, 0)]), f"malformed op {i}"))
+    return rows

@@ -16,9 +16,9 @@ scale = sys.argv[4] if len(sys.argv) > 4 else "l"
 prog = Y.build_program(Y.synthetic_state_dict(0, scale), scale)
 convs = []
 for o in prog["ops"]:
-    if o[0] != Y.OP_CONV:
+    if o[Y.W_KIND] != Y.OP_CONV:
         continue
-    _, src, so, cin, dst, do, cout, ks, st = [int(v) for v in o[:9]]
+    src, cin, dst, cout, ks, st = (int(o[w]) for w in (Y.W_SRC, Y.W_CIN, Y.W_DST, Y.W_COUT, Y.W_KS, Y.W_STRIDE))
     H, W, _ = prog["bufs"][src]
     Ho, Wo, _ = prog["bufs"][dst]
     convs.append((H, W, cin, cout, ks, st, Ho, Wo, 2.0 * B * Ho * Wo * cout * ks * ks * cin))

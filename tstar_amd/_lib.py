@@ -65,6 +65,7 @@ SIGNATURES = {
     "tstar_image_guided_postprocess": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tstar_image_guided_postprocess_host": (_i, [_vp, _vp, _i, _i, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "tstar_yolo_create": (_i, [C.POINTER(_vp), _vp, _sz, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i]),
+    "tstar_yolo_check_program": (_i, [_vp, _sz, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i]),
     "tstar_yolo_destroy": (_i, [_vp]),
     "tstar_yolo_num_anchors": (_i, [_vp]),
     "tstar_yolo_set_text_feats": (_i, [_vp, _i, _vp, _vp, _i, _vp]),

@@ -1,5 +1,5 @@
 // C ABI of libtstar_hip.so (include/tstar_hip.h): the error plumbing and the stateless entry points (GEMM, attention, ingest, JPEG,
-// cell_reduce, draw_boxes, plans).  The detector handles live beside their kernels: owl.hip, yolo.hip, searcher.hip.
+// cell_reduce, draw_boxes, plans).  The detector handles live beside their kernels: owl.hip, yolo.hip (+ yolo_conv.hip), searcher.hip.
 #include "../../include/tstar_hip.h"
 #include "common.h"
 #include "heads.h"

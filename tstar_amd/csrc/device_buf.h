@@ -1,4 +1,5 @@
-// One grow-on-demand device buffer (internal): the staging areas of the detector handles whose size follows the largest call so far.
+// One owned device buffer (internal): the staging areas of the detector handles whose size follows the largest call so far (grown on
+// demand), and the YOLO handle's fixed-size arrays (reserved once at create).  Move-only; the destructor frees.
 #pragma once
 #include "common.h"
 
@@ -8,6 +9,16 @@ template <class T>
 struct DeviceBuf {
     T* p = nullptr;
     size_t cap = 0;          // elements
+
+    DeviceBuf() = default;
+    DeviceBuf(const DeviceBuf&) = delete;
+    DeviceBuf& operator=(const DeviceBuf&) = delete;
+    DeviceBuf(DeviceBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DeviceBuf& operator=(DeviceBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DeviceBuf() { release(); }
 
     // Room for n elements.  n <= cap does nothing.  Otherwise stream s -- the one whose launches read the buffer -- is drained
     // before a live allocation is freed, and the new one holds exactly n elements (no doubling: the HBM budgets count on it).

@@ -1,7 +1,7 @@
 """Host wrapper of the HIP YOLO-World detector (tstar_yolo_* in include/tstar_hip.h).
 
 PyTorch is used for device memory and streams only; the network is executed by the hand-written f32 VALU kernels of
-csrc/yolo.hip from the layer program tstar_amd.yolo_world.build_program emits.
+csrc/yolo.hip and csrc/yolo_conv.hip from the layer program tstar_amd.yolo_world.build_program emits.
 """
 from __future__ import annotations
 
@@ -29,6 +29,21 @@ def conv_plan(cin, src_ld, src_off, H, W, cout, dst_ld, dst_off, ks, stride, mod
     return FORM_NAMES[out[0]], out[1], out[2]
 
 
+def _program_args(prog, max_batch):
+    """(arrays to keep alive, the arguments of tstar_yolo_create behind ``out``) of a program dict."""
+    keep = [np.ascontiguousarray(prog[k], dtype=np.float32 if k == "blob" else np.int32) for k in ("blob", "ops", "bufs", "guides", "levels")]
+    blob, ops, bufs, guides, levels = keep
+    return keep, (blob.ctypes.data, blob.size, ops.ctypes.data, ops.shape[0], ops.shape[1], bufs.ctypes.data, bufs.shape[0], guides.ctypes.data,
+                  guides.shape[0], levels.ctypes.data, levels.shape[0], int(prog["input_buf"]), int(max_batch))
+
+
+def check_program(prog, max_batch: int = 16) -> None:
+    """Every check tstar_yolo_create makes of a layer program (tstar_yolo_check_program; pure, needs no GPU).  Raises
+    ``TStarHipError`` with the message create would give."""
+    keep, args = _program_args(prog, max_batch)
+    _lib.check(_lib.load().tstar_yolo_check_program(*args), "tstar_yolo_check_program")
+
+
 @dataclass
 class YoloResult:
     """Device tensors of one tstar_yolo_detect call (detections are sorted by descending score, padded to max_dets)."""
@@ -54,16 +69,10 @@ class YoloDetector:
         prog = state_dict if scale is None else Y.build_program(state_dict, scale)
         self.arch = prog.get("arch")
         self.conv_flops_per_image = Y.conv_flops(prog)
-        blob = np.ascontiguousarray(prog["blob"], dtype=np.float32)
-        ops = np.ascontiguousarray(prog["ops"], dtype=np.int32)
-        bufs = np.ascontiguousarray(prog["bufs"], dtype=np.int32)
-        guides = np.ascontiguousarray(prog["guides"], dtype=np.int32)
-        levels = np.ascontiguousarray(prog["levels"], dtype=np.int32)
+        keep, args = _program_args(prog, max_batch)                  # keep: the arrays args points into, alive across the call
+        ops, bufs = keep[1], keep[2]
         h = C.c_void_p()
-        rc = self._lib.tstar_yolo_create(C.byref(h), blob.ctypes.data, blob.size, ops.ctypes.data, ops.shape[0], ops.shape[1],
-                                         bufs.ctypes.data, bufs.shape[0], guides.ctypes.data, guides.shape[0], levels.ctypes.data,
-                                         levels.shape[0], int(prog["input_buf"]), int(max_batch))
-        _lib.check(rc, "tstar_yolo_create")
+        _lib.check(self._lib.tstar_yolo_create(C.byref(h), *args), "tstar_yolo_create")
         self._h = h
         self.max_batch = int(max_batch)
         self.n_anchor = int(self._lib.tstar_yolo_num_anchors(h))

@@ -42,11 +42,30 @@ NUM_TRAINING_CLASSES = 80           # head_module.num_classes of the pretrain co
 # yolov8_x base "from X to XL": deepen 1.0, widen 1.5 (96-channel stem, 192/384/768/768 stages, 6/12/12 attention heads)
 SCALES = {"s": (0.33, 0.5, 1024), "m": (0.67, 0.75, 768), "l": (1.0, 1.0, 512), "x": (1.0, 1.25, 512), "xl": (1.0, 1.5, 512)}
 
-# op codes of the layer program (mirrored in csrc/yolo.hip)
+# the layer program's op codes and word positions (mirror of csrc/yolo_program.h, which defines them)
 OP_CONV, OP_POOL5, OP_UPCOPY, OP_ATTN = 0, 1, 2, 3
 ACT_NONE, ACT_SILU = 0, 1
 MODE_PLAIN, MODE_RESIDUAL, MODE_ATTN_MUL = 0, 1, 2
 OP_WORDS = 24
+(W_KIND, W_SRC, W_SRC_OFF, W_CIN, W_DST, W_DST_OFF, W_COUT, W_KS, W_STRIDE, W_ACT, W_W_OFF, W_B_OFF, W_MODE, W_AUX, W_AUX_OFF) = range(15)
+W_C = W_EMBED = W_CIN                     # word 3 of the pool / up-copy and of the attention op
+W_FACTOR = W_HEADS = W_COUT               # word 6 of the up-copy and of the attention op
+W_GUIDE = W_KS                            # word 7 of the attention op
+BUF_H, BUF_W, BUF_C = range(3)            # the words of a buffer row
+WORD_OF = dict(src=W_SRC, src_off=W_SRC_OFF, cin=W_CIN, dst=W_DST, dst_off=W_DST_OFF, cout=W_COUT, ks=W_KS, stride=W_STRIDE, act=W_ACT,
+               w_off=W_W_OFF, b_off=W_B_OFF, mode=W_MODE, aux=W_AUX, aux_off=W_AUX_OFF, c=W_C, embed=W_EMBED, factor=W_FACTOR,
+               heads=W_HEADS, guide=W_GUIDE)
+
+
+def pack_op(kind: int, **words) -> List[int]:
+    """One op row from named words: ``pack_op(OP_UPCOPY, src=.., src_off=.., c=.., dst=.., dst_off=.., factor=..)``."""
+    row = [0] * OP_WORDS
+    row[W_KIND] = kind
+    for name, v in words.items():
+        if name not in WORD_OF:
+            raise ValueError(f"pack_op: no op word named {name!r} (one of {sorted(WORD_OF)})")
+        row[WORD_OF[name]] = int(v)
+    return row
 
 
 def make_divisible(x: float, widen: float, divisor: int = 8) -> int:
@@ -202,7 +221,17 @@ class _Builder:
                 f"buffer: the state dict is not a YOLO-World-v2-{self.A['scale'].upper()} model (wrong scale= / config name?)")
         w_off = self.put(w)
         b_off = self.put(b) if b is not None else -1
-        self.ops.append([OP_CONV, src, src_off, cin, dst, dst_off, cout, ks, stride, act, w_off, b_off, mode, aux, aux_off])
+        self.ops.append(pack_op(OP_CONV, src=src, src_off=src_off, cin=cin, dst=dst, dst_off=dst_off, cout=cout, ks=ks, stride=stride, act=act,
+                                w_off=w_off, b_off=b_off, mode=mode, aux=aux, aux_off=aux_off))
+
+    def pool5(self, buf, src_off, c, dst_off):
+        self.ops.append(pack_op(OP_POOL5, src=buf, src_off=src_off, c=c, dst=buf, dst_off=dst_off))
+
+    def upcopy(self, src, src_off, c, dst, dst_off, factor):
+        self.ops.append(pack_op(OP_UPCOPY, src=src, src_off=src_off, c=c, dst=dst, dst_off=dst_off, factor=factor))
+
+    def attn(self, src, src_off, embed, dst, heads, guide):
+        self.ops.append(pack_op(OP_ATTN, src=src, src_off=src_off, embed=embed, dst=dst, heads=heads, guide=guide))
 
     def c2f(self, name, src, cin, cout, n, add, attn_id=None):
         """CSPLayerWithTwoConv / MaxSigmoidCSPLayerWithTwoConv: every branch writes into ONE concat buffer."""
@@ -230,7 +259,7 @@ class _Builder:
             gid = len(self.guides)
             self.guides.append(dict(embed=embed, heads=heads, w_off=self.put(gw), b_off=self.put(gb), bias_off=self.put(self.sd[a + ".bias"])))
             ab = self.buf(H, W, heads)
-            self.ops.append([OP_ATTN, esrc, eoff, embed, ab, 0, heads, gid])
+            self.attn(esrc, eoff, embed, ab, heads, gid)
             self.conv(a + ".project_conv", cat, last_off, cat, (2 + n) * mid, act=ACT_NONE, mode=MODE_ATTN_MUL, aux=ab, aux_off=0)
         out = self.buf(H, W, cout)
         self.conv(name + ".final_conv", cat, 0, out, 0)
@@ -266,7 +295,7 @@ def build_program(state_dict, scale: str = "l") -> Dict:
             cat = B.buf(size, size, c // 2 * 4)
             B.conv(f"{b}stage{si}.2.conv1", cur, 0, cat, 0)
             for j in range(3):
-                B.ops.append([OP_POOL5, cat, j * (c // 2), c // 2, cat, (j + 1) * (c // 2)])
+                B.pool5(cat, j * (c // 2), c // 2, (j + 1) * (c // 2))
             o = B.buf(size, size, c)
             B.conv(f"{b}stage{si}.2.conv2", cat, 0, o, 0)
             cur = o
@@ -278,8 +307,8 @@ def build_program(state_dict, scale: str = "l") -> Dict:
     def cat2(first, c_first, factor, second, c_second, size):
         """torch.cat([first (optionally upsampled x2), second], dim=1) as two copies into one buffer."""
         cb = B.buf(size, size, c_first + c_second)
-        B.ops.append([OP_UPCOPY, first, 0, c_first, cb, 0, factor])
-        B.ops.append([OP_UPCOPY, second, 0, c_second, cb, c_first, 1])
+        B.upcopy(first, 0, c_first, cb, 0, factor)
+        B.upcopy(second, 0, c_second, cb, c_first, 1)
         return cb
 
     inner = [None, None, feats[2]]
@@ -322,7 +351,7 @@ def build_program(state_dict, scale: str = "l") -> Dict:
 def program_from_builder(B: "_Builder", levels, input_buf: int, A=None) -> Dict:
     """The program dict the library takes, from a builder's blob / ops / buffers / attention layers."""
     ops = np.zeros((len(B.ops), OP_WORDS), dtype=np.int32)
-    for i, o in enumerate(B.ops):
+    for i, o in enumerate(B.ops):                             # a row may be given short: the words it leaves out are 0
         ops[i, :len(o)] = o
     guides = np.array([[g["embed"], g["heads"], g["w_off"], g["b_off"], g["bias_off"]] for g in B.guides], dtype=np.int32).reshape(-1, 5)
     return dict(blob=np.concatenate(B.blob).astype(np.float32), ops=ops, bufs=np.array(B.bufs, dtype=np.int32), guides=guides,
@@ -333,10 +362,9 @@ def conv_flops(prog) -> float:
     """Algorithmic multiply-add flops (x2) of every conv of one 640x640 image."""
     total = 0.0
     for o in prog["ops"]:
-        if o[0] == OP_CONV:
-            _, _, _, cin, dst, _, cout, ks, *_ = o
-            H, W, _ = prog["bufs"][dst]
-            total += 2.0 * H * W * cout * cin * ks * ks
+        if o[W_KIND] == OP_CONV:
+            buf = prog["bufs"][o[W_DST]]
+            total += 2.0 * buf[BUF_H] * buf[BUF_W] * o[W_COUT] * o[W_CIN] * o[W_KS] * o[W_KS]
     return total
 
 
