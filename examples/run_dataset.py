@@ -56,6 +56,9 @@ def main():
     ap.add_argument("--jpeg-scale", type=int, choices=(1, 2, 4, 8), default=None, metavar="N",
                     help="decode Motion-JPEG / JPEG-folder videos at 1/N size (2, 4 or 8; sets TSTAR_JPEG_SCALE), byte for byte Pillow's "
                          "draft: the store shrinks by N * N, and the search sees the smaller frames (boxes are in their pixels)")
+    ap.add_argument("--jpeg-recode", type=int, default=None, metavar="N",
+                    help="with --jpeg-resident: re-code the compressed videos losslessly at open with a restart interval of N MCUs "
+                         "(1..65535; sets TSTAR_JPEG_RECODE), so that fetches decode one lane per interval: same pixels, same results")
     ap.add_argument("--query-image", action="append", default=[], metavar="NAME=PATH[@x0,y0,x1,y1]",
                     help="example image of an object (repeatable): every target / cue object called NAME is searched for by the "
                          "image-guided query embedded from PATH instead of by its text; @x0,y0,x1,y1 (pixels of that image) "
@@ -99,6 +102,10 @@ def main():
             os.environ["TSTAR_JPEG_POOL"] = str(args.jpeg_resident)
     if args.jpeg_scale is not None:
         os.environ["TSTAR_JPEG_SCALE"] = str(args.jpeg_scale)
+    if args.jpeg_recode is not None:
+        if args.jpeg_resident is None:
+            ap.error("--jpeg-recode re-codes the arena of a compressed-resident store: it needs --jpeg-resident")
+        os.environ["TSTAR_JPEG_RECODE"] = str(args.jpeg_recode)
     per_video = max(1, args.questions_per_video)
     paths = args.videos if args.videos else [f"synthetic://n={args.nframes},seed={100 + i // per_video}" for i in range(args.items * per_video)]
     items = [{"video_path": p, "targets": QUESTIONS[i % 4][0], "cues": QUESTIONS[i % 4][1]} for i, p in enumerate(paths)]

@@ -676,6 +676,43 @@ int tstar_jpeg_reconstruct_scaled(const int16_t* d_coef, const uint16_t* d_quant
 int tstar_jpeg_reconstruct_slots_scaled(const int16_t* d_coef, const uint16_t* d_quant, int m, int W, int H, int ncomp, int hs, int vs,
                                         int scale, uint8_t* d_planes, uint8_t* d_pool, int pool_frames, const int32_t* d_slots,
                                         void* stream);
+/* Lossless RE-CODING with a restart interval (added entries; tstar_abi_version() stays 3): the JPEG counterpart of
+ * `jpegtran -restart`.  A batch of baseline frames of one geometry goes through the device entropy runner (coefficients in HBM),
+ * through tstar_jpeg_encode_scan_rst (scans with the standard Huffman tables in fixed-size slots, per-frame length and status) and
+ * through the assembly below, which builds a PIECE of a new arena and its records on the device.  Not a pixel changes: the
+ * coefficients and the quantisation tables are the source's.
+ * Header of a re-coded frame: the layout of tstar_jpeg_encode_header_rst with the DQT entries given (quant u16 [3][64], natural
+ * order, rows Y / Cb / Cr, values 1..65535).  Equal chroma rows share table 1, else Cr takes table 2; a table with a value above
+ * 255 is written with 16-bit entries and the frame header becomes SOF1, as libjpeg writes it.  At most 890 bytes; for the rows of
+ * a quality the bytes are tstar_jpeg_encode_header_rst's.  TSTAR_ERR_ARG / 4 (cap short, nothing written). */
+int tstar_jpeg_encode_header_tables(int W, int H, const uint16_t* quant, int hs, int vs, int restart, uint8_t* out, size_t cap, size_t* len);
+/* Assembly.  Descriptor, 8 x u32 per frame j of the piece, written by the host once lengths and statuses are known:
+ * {kind (0 re-coded: header row + the scan in slot j; 1 kept: the source bytes as they are), header row, frame of the source batch
+ * (its quant row; for a kept frame its records), kept: byte offset and bytes in the source batch, table set of the output's frame
+ * record (i32; -1: a kept frame without one), first segment in the output's list, segments (re-coded: ceil(n_mcu / restart);
+ * kept: the source frame record's count)}.  Headers: u8 [n_headers][1024] with their lengths.  Slots: 16-byte aligned, slot_bytes a
+ * multiple of 16.  The source batch is what the entropy launchers took: bytes, quant rows (16-byte aligned), frame records,
+ * segments.  Output: the frames end to end from d_out[0] (no padding, as an arena packs them; out_bytes is the capacity, below
+ * 2^32) and ONE record buffer, 16-byte aligned, of the size the layout query returns (0: not a piece; out5 = byte offsets of)
+ *   off u64 [m + 1] (off[m]: the piece's bytes) | len u32 [m] | quant u16 [m][192] | frame records [m] | segments [n_segments]
+ * which hold what tstar_jpeg_plan_segments says about the output bytes, field for field (begin / end from d_out[0], frame = j).
+ * The launcher checks the HOST copy of the descriptor before any launch and refuses what fails; the kernels read the DEVICE copy
+ * and check every frame against device memory again: a frame that fails takes no bytes and gets a record without a table set and
+ * segments that name no frame.  No load leaves a slot, a header row or a kept frame's source range, no store the frame's range
+ * below out_bytes or the record buffer.  longest: the most bytes a frame takes (it sizes the grid only).  Three launches, no
+ * synchronisation.  The host mirror takes everything in host memory and gives the same bytes and records word for word. */
+size_t tstar_jpeg_recode_layout(int m, int n_segments, size_t* out5);
+int tstar_jpeg_recode_assemble(const void* h_desc, const void* d_desc, int m, int n_segments, const uint8_t* d_headers,
+                               const uint32_t* d_header_len, int n_headers, const uint8_t* d_slots, size_t slot_bytes,
+                               const uint32_t* d_scan_len, int restart, int n_mcu, const uint8_t* d_src_bytes, size_t src_total,
+                               const uint16_t* d_src_quant, const void* d_src_frames, const void* d_src_segments, int n_src_frames,
+                               int n_src_segments, uint8_t* d_rec, size_t rec_bytes, uint8_t* d_out, size_t out_bytes, size_t longest,
+                               void* stream);
+int tstar_jpeg_recode_assemble_host(const void* desc, int m, int n_segments, const uint8_t* headers, const uint32_t* header_len,
+                                    int n_headers, const uint8_t* slots, size_t slot_bytes, const uint32_t* scan_len, int restart,
+                                    int n_mcu, const uint8_t* src_bytes, size_t src_total, const uint16_t* src_quant,
+                                    const void* src_frames, const void* src_segments, int n_src_frames, int n_src_segments, uint8_t* rec,
+                                    size_t rec_bytes, uint8_t* out, size_t out_bytes);
 /* Native-resolution RGB u8 [n,H,W,3] of NV12 frames (the keyframes pop_frames hands back, :379-380). */
 int tstar_nv12_to_rgb(const uint8_t* d_video, int N, int H, int W, const int32_t* d_frame_idx, int n,
                       uint8_t* d_out, void* stream);

@@ -106,6 +106,12 @@ SIGNATURES = {
     "tstar_jpeg_split_workspace_bytes": (_sz, [_sz, _i, _i]),
     "tstar_jpeg_entropy_split_device": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "tstar_jpeg_entropy_split_host": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "tstar_jpeg_encode_header_tables": (_i, [_i, _i, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "tstar_jpeg_recode_layout": (_sz, [_i, _i, _vp]),
+    "tstar_jpeg_recode_assemble": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp, _sz,
+                                        _sz, _vp]),
+    "tstar_jpeg_recode_assemble_host": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp,
+                                             _sz]),
     "tstar_jpeg_gather_bytes": (_sz, [_sz, _i, _i, _vp]),
     "tstar_jpeg_gather": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _sz, _i, _vp, _sz, _vp]),
     "tstar_jpeg_gather_host": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _sz, _i, _vp, _sz]),

@@ -47,7 +47,7 @@ def _hipcc() -> str:
 
 
 # HIP-free host sources that are part of libtstar_hip.so (hipcc compiles them as plain C++)
-HOST_SOURCES = ("jpeg_host.cpp", "jpeg_enc_host.cpp", "jpeg_resident_host.cpp", "image_guided_post_host.cpp")
+HOST_SOURCES = ("jpeg_host.cpp", "jpeg_enc_host.cpp", "jpeg_resident_host.cpp", "jpeg_recode_host.cpp", "image_guided_post_host.cpp")
 HOST_FLAGS = ["-x", "c++", "-O3", "-std=c++20", "-fPIC", "-Wall", "-pthread"]
 
 

@@ -78,17 +78,33 @@ void jpeg_enc_quant(int quality, uint16_t* quant) {
 void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out) { jpeg_enc_header(g, quality, 0, out); }
 
 void jpeg_enc_header(const JpegGeom& g, int quality, int restart, uint8_t* out) {
-    uint8_t* p = out;
-    auto put = [&](std::initializer_list<int> v) { for (int b : v) *p++ = (uint8_t)b; };
     uint16_t quant[192];
     jpeg_enc_quant(quality, quant);
+    jpeg_enc_header_tables(g, quant, restart, out);
+}
+
+size_t jpeg_enc_header_tables(const JpegGeom& g, const uint16_t* quant, int restart, uint8_t* out) {
+    uint8_t* p = out;
+    auto put = [&](std::initializer_list<int> v) { for (int b : v) *p++ = (uint8_t)b; };
+    const int n_tables = memcmp(quant + 64, quant + 128, 128) == 0 ? 2 : 3;       // Cb and Cr share table 1 when their rows are equal
+    bool wide = false;
     put({0xFF, 0xD8});
     put({0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
-    for (int t = 0; t < 2; ++t) {
-        put({0xFF, 0xDB, 0, 67, t});
-        for (int k = 0; k < 64; ++k) *p++ = (uint8_t)quant[t * 64 + jpegenc::kStd.zigzag[k]];
+    for (int t = 0; t < n_tables; ++t) {
+        const uint16_t* q = quant + t * 64;
+        int prec = 0;
+        for (int k = 0; k < 64; ++k) prec |= q[k] > 255;
+        wide |= prec != 0;
+        put({0xFF, 0xDB, 0, 67 + 64 * prec, (prec << 4) | t});
+        for (int k = 0; k < 64; ++k) {
+            const uint16_t v = q[jpegenc::kStd.zigzag[k]];
+            if (prec) *p++ = (uint8_t)(v >> 8);
+            *p++ = (uint8_t)v;
+        }
     }
-    put({0xFF, 0xC0, 0, 17, 8, g.H >> 8, g.H & 255, g.W >> 8, g.W & 255, 3, 1, (g.hs << 4) | g.vs, 0, 2, 0x11, 1, 3, 0x11, 1});
+    // a 16-bit table is not baseline: libjpeg then writes SOF1 (extended sequential, Huffman)
+    put({0xFF, wide ? 0xC1 : 0xC0, 0, 17, 8, g.H >> 8, g.H & 255, g.W >> 8, g.W & 255, 3, 1, (g.hs << 4) | g.vs, 0, 2, 0x11, 1, 3, 0x11,
+         n_tables - 1});
     const int ids[4] = {0x00, 0x10, 0x01, 0x11};                // DC 0, AC 0, DC 1, AC 1
     for (int t = 0; t < 4; ++t) {
         const jpegenc::HuffSpec& s = kTables.spec[t];
@@ -99,6 +115,7 @@ void jpeg_enc_header(const JpegGeom& g, int quality, int restart, uint8_t* out) 
     }
     if (restart > 0) put({0xFF, 0xDD, 0, 4, restart >> 8, restart & 255});
     put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
+    return (size_t)(p - out);
 }
 
 void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2) {
@@ -321,6 +338,21 @@ int tstar_jpeg_encode_header_rst(int W, int H, int quality, int hs, int vs, int 
     *len = (size_t)jpeg_enc_header_bytes(restart);
     if (cap < *len) { set_error("tstar_jpeg_encode_header: the buffer is shorter than the header"); return 4; }
     jpeg_enc_header(g, quality, restart, out);
+    return 0;
+}
+
+int tstar_jpeg_encode_header_tables(int W, int H, const uint16_t* quant, int hs, int vs, int restart, uint8_t* out, size_t cap, size_t* len) {
+    const JpegGeom g{W, H, 3, hs, vs};
+    if (!out || !len || !quant || !jpeg_enc_geom_ok(g) || !jpeg_enc_restart_ok(restart)) {
+        set_error("tstar_jpeg_encode_header_tables: null argument, unsupported geometry or restart interval outside 0..65535");
+        return 1;
+    }
+    for (int k = 0; k < 192; ++k)
+        if (quant[k] == 0) { set_error("tstar_jpeg_encode_header_tables: a quantisation value of 0"); return 1; }
+    uint8_t buf[kJpegEncHeaderTablesMax];
+    *len = jpeg_enc_header_tables(g, quant, restart, buf);
+    if (cap < *len) { set_error("tstar_jpeg_encode_header_tables: the buffer is shorter than the header"); return 4; }
+    memcpy(out, buf, *len);
     return 0;
 }
 

@@ -79,6 +79,12 @@ void jpeg_enc_quant(int quality, uint16_t* quant);
 void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out);
 // the same with DRI in front of SOS when restart > 0: jpeg_enc_header_bytes(restart) bytes
 void jpeg_enc_header(const JpegGeom& g, int quality, int restart, uint8_t* out);
+// the same layout with the DQT entries given (quant u16 [3][64], natural order, rows Y / Cb / Cr, every value 1..65535), for a
+// file that is re-coded losslessly: two tables when the chroma rows are equal (what the header above writes), else three; a table
+// with a value above 255 takes 16-bit entries and turns SOF0 into SOF1, as libjpeg writes it.  -> the bytes written, at most
+// kJpegEncHeaderTablesMax.  For jpeg_enc_quant(quality)'s rows the bytes are jpeg_enc_header's.
+constexpr int kJpegEncHeaderTablesMax = kJpegEncHeaderBytes + kJpegEncDriBytes + 69 + 3 * 64;       // a third table, 16-bit entries
+size_t jpeg_enc_header_tables(const JpegGeom& g, const uint16_t* quant, int restart, uint8_t* out);
 
 // stage 1, one frame: rgb u8 [H][W][3] -> coef int16 [g.blocks()][64]; dummy2 (optional) += {right-edge, bottom-edge} dummy blocks
 void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2);

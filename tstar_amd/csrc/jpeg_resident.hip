@@ -8,31 +8,17 @@
 // leaves the frame's padded range of the batch; the padding is written as zeros, so that the buffer is the mirror's word for word.
 #include "common.h"
 #include "jpeg_resident_core.h"
+#include "jpeg_vec_copy.h"
 
 namespace tstar {
 
 namespace {
 
 using namespace jpegres;
+using jpegvec::funnel;
 
 constexpr int kThreads = 256;
 constexpr uint32_t kVecPerWg = 1024;          // 16 KiB of a frame per workgroup: a 22 KB 360x640 frame takes two
-
-// bytes [a, a + 16) of the 32 bytes lo | hi, 0 < a < 16
-__device__ inline uint4 funnel(const uint4& lo, const uint4& hi, uint32_t a) {
-    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-    const uint32_t q = a >> 2, r = (a & 3) * 8;
-    uint32_t o[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        uint32_t x = 0, y = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)                  // q is uniform over the frame: selects, no indexed registers
-            if (q == (uint32_t)k) { x = w[k + i]; y = w[k + i + 1]; }
-        o[i] = (uint32_t)((((uint64_t)y << 32) | x) >> r);
-    }
-    return make_uint4(o[0], o[1], o[2], o[3]);
-}
 
 __global__ __launch_bounds__(kThreads) void jpeg_gather_kernel(Arena a, Batch b, const GatherDesc* __restrict__ desc) {
     const uint32_t j = blockIdx.y, t = threadIdx.x;

@@ -650,6 +650,18 @@ class JpegOpen:
         self.estats = {"device": 0, "host": 0}
         self.sstats = {"split": 0, "abandoned": 0, "rounds_max": 0}
 
+    @classmethod
+    def for_geometry(cls, src: JpegFrames, raw: Sequence[int], device, geom, scale: int = 1) -> "JpegOpen":
+        """An open whose geometry is known up front (every frame of ``raw`` was probed by the caller): what ``prelude`` leaves behind
+        after the first covered frame, without decoding anything.  An EntropyRunner can be driven over it outside ``load_jpeg``."""
+        ctx = cls(src, raw, device, scale=scale)
+        ctx.check_size(0, int(geom[0]), int(geom[1]))
+        ctx.geom = tuple(int(v) for v in geom)
+        ctx.blocks, ctx.plane_bytes = _sizes(ctx.geom)
+        if ctx.scale > 1:
+            ctx.plane_bytes = scaled_sizes(ctx.geom, ctx.scale)[2]
+        return ctx
+
     def attach(self, store):
         store.decode_stats, store.entropy_stats, store.entropy_split_stats = self.stats, self.estats, self.sstats
         store.jpeg_scale, store.source_size = self.scale, (self.W, self.H)
@@ -805,17 +817,26 @@ class EntropyRunner:
             self.done[b].record(stream)
         return k0, batch, b
 
-    def collect(self, ticket):
+    def collect(self, ticket, split_stats: bool = True):
         """Wait for a chunk's statuses -> the frames (positions in the chunk) the device did not return OK for, host-routed ones
-        included; the others are counted as the device's, and the split counters are updated."""
+        included; the others are counted as the device's, and the split counters are updated (``split_stats=False``: left alone, for
+        a caller that counts ``seg_info`` itself)."""
         k0, batch, b = ticket
         self.done[b].synchronize()
         nseg = len(batch.plan.segments)
         status = self.status[b][:2 * nseg].numpy()
         fstat = batch.plan.frame_status(status[:nseg])
-        count_split(self.ctx.sstats, status[nseg:])
+        if split_stats:
+            count_split(self.ctx.sstats, status[nseg:])
         self.ctx.count(k0 + np.flatnonzero(fstat == OK), "device", "device")
         return [int(j) for j in np.nonzero(fstat)[0]]
+
+    def seg_info(self, ticket) -> np.ndarray:
+        """The split path's word on every segment of a collected chunk (int32 [n_segments]: 0 one lane, r > 0 converged in round r,
+        -1 abandoned), valid until the second submit after the chunk's."""
+        _, batch, b = ticket
+        nseg = len(batch.plan.segments)
+        return self.status[b][nseg:2 * nseg].numpy().copy()
 
 
 def _device_entropy_chunks(ctx: JpegOpen, store, s0: int, chunk: Optional[int], min_split_bytes: int, side) -> None:

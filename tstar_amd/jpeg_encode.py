@@ -115,6 +115,26 @@ def header(W: int, H: int, quality: int = 75, subsampling="4:2:0", restart_rows=
     return buf[:n.value].tobytes()
 
 
+def header_from_tables(W: int, H: int, quant, subsampling="4:2:0", restart: int = 0) -> bytes:
+    """SOI .. SOS in the layout of ``header`` with the DQT entries given: ``quant`` [3][64] in natural order (rows Y / Cb / Cr, as
+    the decoder reports a file's tables), values 1..65535.  Equal chroma rows share table 1 (what ``header`` writes), else Cr takes a
+    table 2 of its own; a table with a value above 255 is written with 16-bit entries and the frame header becomes SOF1, as libjpeg
+    writes it.  ``restart``: MCUs per interval (0: no DRI).  For the tables of a Pillow quality q the bytes are ``header(W, H, q,
+    subsampling, restart_blocks=restart)``'s: a file re-coded under it keeps its own quantisation, so not a pixel changes."""
+    from . import _lib
+    hs, vs = sampling(subsampling)
+    _, restart = _restart_values(None, restart)
+    q = np.ascontiguousarray(quant, dtype=np.int64).reshape(-1)
+    if q.size != 192 or q.min() < 1 or q.max() > 65535:
+        raise ValueError("header_from_tables: expected quantisation tables [3][64] of values 1..65535")
+    q = q.astype(np.uint16)
+    buf = np.empty(1024, dtype=np.uint8)
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().tstar_jpeg_encode_header_tables(W, H, q.ctypes.data, hs, vs, restart, buf.ctypes.data, buf.size, C.byref(n)),
+               "tstar_jpeg_encode_header_tables")
+    return buf[:n.value].tobytes()
+
+
 def _host_array(frames) -> np.ndarray:
     a = np.ascontiguousarray(frames)
     if a.ndim == 3:
@@ -512,4 +532,53 @@ def save_mjpeg(store, path: str, quality: int = 90, subsampling="4:2:0", fps: Op
         N, H, W, _ = a.shape
         files = encode_frames(a, quality, subsampling, device=False, **rst) if not device else encode_frames(store, quality, subsampling, **rst)
     write_mjpeg_file(path, files, W, H, 1.0 if fps is None else float(fps))
+    return len(files)
+
+
+# ------------------------------------------------------------------------------------------------ lossless re-coding
+def recode_frames(files: Sequence, restart_blocks: int = 8, device: bool = True, stats: Optional[dict] = None,
+                  chunk: Optional[int] = None) -> List[bytes]:
+    """Every JPEG of ``files`` (bytes or paths) with a restart interval of ``restart_blocks`` MCUs (1..65535), LOSSLESSLY: the
+    quantised coefficients and the quantisation tables are the file's own, only the entropy coding is new (the standard Huffman
+    tables, DRI / RSTn), so every decoder gives the pixels it gave before.  A file that is not re-coded comes back as it is:
+    grayscale, progressive, arithmetic, CMYK, a sampling the kernels do not cover, a file the decoder does not return OK for, or a
+    coefficient beyond the standard tables' size categories.  ``stats`` (optional dict) is added to: ``recoded``, ``kept``,
+    ``bytes_in``, ``bytes_out``.  A source with optimised Huffman tables grows by what the optimisation had saved.
+    ``device=False``: the host twin, which needs no GPU and gives the same bytes."""
+    from . import jpeg_recode
+    restart = jpeg_recode.recode_interval(restart_blocks)
+    datas = []
+    for f in files:
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            datas.append(bytes(f))
+        else:
+            with open(f, "rb") as fh:
+                datas.append(fh.read())
+    if not device:
+        return jpeg_recode.recode_host(datas, restart, stats)
+    return jpeg_recode.recode_device(datas, restart, chunk=chunk, stats=stats)
+
+
+def recode_mjpeg(src, dst: str, restart_blocks: int = 8, device: bool = True, stats: Optional[dict] = None, piece: int = 1024) -> int:
+    """``src`` (a Motion-JPEG .avi, a .mjpeg / .mjpg stream or a folder of JPEG frames) re-coded losslessly (``recode_frames``) into
+    ``dst`` (.avi, .mjpeg or .mjpg; an AVI of 1 GiB or more is refused, as ``save_mjpeg`` refuses it).  EVERY raw frame is carried
+    over, at the source's frame rate.  Returns the frames written."""
+    from . import jpeg
+    s = jpeg.open_source(src)
+    if s is None:
+        raise ValueError(f"recode_mjpeg: {src!r}: expected a Motion-JPEG .avi, a .mjpeg / .mjpg stream or a folder of JPEG frames")
+    try:
+        if s.n_frames < 1:
+            raise ValueError(f"recode_mjpeg: {src!r} holds no frame")
+        rc, info, msg = jpeg.probe(s.read(0))              # a container wants the picture size: the first frame's own header says it
+        if rc == jpeg.MALFORMED:
+            raise ValueError(f"recode_mjpeg: {s.label(0)}: {msg}")
+        W, H = int(info[0]), int(info[1])
+        files: List[bytes] = []
+        for k0 in range(0, s.n_frames, piece):
+            files += recode_frames([s.read(i) for i in range(k0, min(s.n_frames, k0 + piece))], restart_blocks, device, stats)
+        fps = s.fps
+    finally:
+        s.close()
+    write_mjpeg_file(dst, files, W, H, fps)
     return len(files)

@@ -247,14 +247,19 @@ def _entry_keys(src, want):
 
 
 def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optional[int] = None, chunk: Optional[int] = None,
-                  scale: int = 1):
+                  scale: int = 1, recode_blocks: Optional[int] = None):
     """Open ``src`` as a ``video.JpegFrameStore`` (see the module text).  The open is ``load_jpeg``'s device mode with another
     destination: the same ``jpeg.JpegOpen`` (prelude, host verdict, counters, messages) and the same ``jpeg.EntropyRunner`` (one upload
     per chunk carries the bytes and the records, the entropy kernels check every frame); here the bytes move on into the arena, and a
     frame the device did not return OK for becomes an exception: RGB in a permanent slot.  ``scale`` 2, 4, 8: pool slots and permanent
-    slots hold the frames at 1/scale size; the arena and the gather are those of the full-size store."""
+    slots hold the frames at 1/scale size; the arena and the gather are those of the full-size store.  ``recode_blocks`` (MCUs, 1..65535;
+    default: none): every chunk is re-coded losslessly with that restart interval while its coefficients are in HBM
+    (``jpeg_recode.DeviceRecoder``), and the arena holds the re-coded bytes only: a fetch then decodes one lane per interval and
+    cuts nothing, whatever the file on disk looks like.  The store's ``recode_stats`` says how many frames were re-coded and kept."""
     import torch
+    from . import jpeg_recode
     from .video import JpegFrameStore
+    restart = jpeg_recode.recode_interval(recode_blocks) if recode_blocks else 0
     if str(device).startswith("cpu"):
         raise ValueError("resident='jpeg' needs a GPU store (device='cpu' was asked for)")
     P = pool_size(pool_frames)
@@ -266,7 +271,9 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
     # the counters are per logical second, as load_jpeg's: an entry counts once for every second that shares it
     ctx = jpeg.JpegOpen(src, raw, device, seconds=np.bincount(sec_entry, minlength=E), scale=scale)
     min_split = jpeg.split_min_bytes()
-    sizes = [src.ranges[fi][1] for fi in raw] if getattr(src, "ranges", None) is not None else None
+    sizes = [src.ranges[fi][1] for fi in raw] if getattr(src, "ranges", None) is not None and not restart else None
+    rstats = jpeg_recode.new_stats() if restart else None
+    rec, long_segments = None, False                    # long_segments: a fetch will cut intervals whose rounds no open has counted
     builder = ArenaBuilder()
     d_parts = []                                        # the arena's bytes, chunk by chunk, when the sizes are not known up front
     d_arena = torch.empty(sum(sizes), dtype=torch.uint8, device=device) if sizes is not None else None
@@ -286,20 +293,44 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
         if arr is None:
             break
         exceptions[e0] = arr
+        jpeg_recode._count(rstats, True, len(data), len(data))
         place(torch.from_numpy(np.frombuffer(data, dtype=np.uint8).copy()))
         builder.add(jpeg.SegmentPlan(np.ones(1, np.int32), np.array([(-1, 0, 0, 0)], dtype=jpeg.FRAME_DTYPE), np.zeros((1, 192), np.uint16),
                                      np.zeros((0, jpeg.TABLE_SET_BYTES), np.uint8), np.zeros(0, jpeg.SEGMENT_DTYPE),
                                      np.zeros(1, np.uint64), len(data)), [len(data)])
         e0 += 1
     run = jpeg.EntropyRunner(ctx, chunk, min_split) if e0 < E else None
+    # a clip whose covered frames are grayscale (or of a sampling the scan stage does not code) is kept whole: its chunks take the
+    # plain open's way and are counted
+    recoding = bool(restart) and jpeg_recode.recodable(ctx.geom)
+    if recoding:
+        rec = jpeg_recode.DeviceRecoder(ctx.geom, device, restart, rstats)
     stream = torch.cuda.current_stream()
     while e0 < E:
         datas = run.read(e0)
         ticket = run.submit(e0, datas, stream)
         batch = ticket[1]
-        place(run.d_buf[:batch.total])
-        builder.add(batch.plan, [len(d) for d in datas])
-        for j in run.collect(ticket):                    # waits for the chunk: the statuses decide what the arena may serve
+        if not recoding:
+            place(run.d_buf[:batch.total])
+            builder.add(batch.plan, [len(d) for d in datas])
+            for d in datas:
+                jpeg_recode._count(rstats, True, len(d), len(d))
+        bad = run.collect(ticket, split_stats=not recoding)     # waits for the chunk: the statuses decide what the arena may serve
+        if recoding:
+            kept, n_cut = np.zeros(len(datas), dtype=bool), 0
+            for p in rec.recode_chunk(batch, run.d_buf, run.d_coef, bad):
+                d_parts.append(p.d_bytes)
+                builder.add(p.plan, p.lens)
+                kept[p.first:p.first + len(p.lens)] = p.kept
+                seg = p.plan.segments
+                if min_split:                            # intervals long enough for a fetch to cut: none at a sensible interval
+                    n_cut += int(((seg["end"].astype(np.int64) - seg["begin"] >= min_split) & ~p.kept[seg["frame"]]).sum())
+            # the split counters describe the arena the store serves: a kept frame's segments as this open decoded them, and the
+            # intervals of re-coded frames a fetch will cut; the open's own rounds on a frame that was re-coded are not the store's
+            jpeg.count_split(ctx.sstats, run.seg_info(ticket)[kept[batch.plan.segments["frame"]]])
+            ctx.sstats["split"] += n_cut
+            long_segments |= n_cut > 0
+        for j in bad:
             verdict = ctx.host_verdict(e0 + j, datas[j])
             if isinstance(verdict, tuple):
                 rgb = torch.empty((1, ctx.oh, ctx.ow, 3), dtype=torch.uint8, device=device)
@@ -316,5 +347,6 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
     arena = builder.finish()
     assert arena.n_entries == E and builder.total == d_arena.numel()
     st = JpegFrameStore(arena, d_arena, sec_entry, ctx.geom, (ctx.oh, ctx.ow), exceptions, P, src.fps, src.n_frames, name=src.name,
-                        min_split_bytes=min_split, max_rounds=ctx.sstats["rounds_max"], jpeg_scale=ctx.scale)
+                        min_split_bytes=min_split, max_rounds=None if long_segments else ctx.sstats["rounds_max"], jpeg_scale=ctx.scale)
+    st.recode_stats = rstats
     return ctx.attach(st)

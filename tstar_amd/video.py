@@ -609,7 +609,8 @@ _SYN = re.compile(r"^synthetic://")
 
 
 def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_entropy: Optional[str] = None,
-               resident: Optional[str] = None, pool_frames: Optional[int] = None, jpeg_scale: Optional[int] = None) -> FrameStore:
+               resident: Optional[str] = None, pool_frames: Optional[int] = None, jpeg_scale: Optional[int] = None,
+               recode_blocks: Optional[int] = None) -> FrameStore:
     """``video``: a FrameStore, a ``synthetic://n=..,h=..,w=..,seed=..,fps=..`` URL, a folder of .jpg / .jpeg frames or a
     list of JPEG paths / bytes (``fps`` frames per second, default 1), a .mjpeg / .mjpg stream (``fps`` default 25), a
     Motion-JPEG .avi, or another file path (.y4m, the Pillow sequences; else decoded at native rate through decord, else
@@ -621,12 +622,19 @@ def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_en
     ``jpeg_scale`` 2, 4 or 8 (TSTAR_JPEG_SCALE when absent; default 1): a JPEG source is decoded at 1/2, 1/4 or 1/8 size, byte for
     byte what Pillow's ``Image.draft`` gives, so the store -- decoded or compressed-resident -- holds [N, ceil(H / s), ceil(W / s), 3]
     and records ``jpeg_scale`` and ``source_size``.  Boxes of a search on it are in pixels of the stored frame.  The keyword on a
-    source that is not JPEG, and any other value, is a ValueError; the variable alone leaves a source that is not JPEG as it is."""
+    source that is not JPEG, and any other value, is a ValueError; the variable alone leaves a source that is not JPEG as it is.
+    ``recode_blocks`` N (1..65535 MCUs; TSTAR_JPEG_RECODE when absent; default: none) with ``resident="jpeg"``: the arena is re-coded
+    losslessly at open with a restart interval of N MCUs (``jpeg_recode``), so that a fetch decodes one lane per interval instead of
+    cutting one long scan; pixels, ``jpeg_scale`` and every reader are unchanged, ``store.recode_stats`` counts the frames.  The
+    keyword without ``resident="jpeg"`` is a ValueError; the variable alone leaves a store that is not compressed-resident as it is."""
     if isinstance(video, FrameStore):
         return video
-    from . import jpeg, jpeg_resident
+    from . import jpeg, jpeg_recode, jpeg_resident
     mode = jpeg_resident.resident_mode(resident)
     scale = jpeg.scale_mode(jpeg_scale)
+    if recode_blocks is not None and mode != "jpeg":
+        raise ValueError(f"open_video: recode_blocks={recode_blocks!r} re-codes the arena of a compressed-resident store: it needs resident=\"jpeg\"")
+    recode = jpeg_recode.recode_mode(recode_blocks) if mode == "jpeg" else 0
     other_codec = None
     if not (isinstance(video, str) and _SYN.match(video)):
         try:
@@ -636,10 +644,12 @@ def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_en
         if src is not None:
             try:
                 if mode == "jpeg" and (resident is not None or not str(device).startswith("cpu")):
-                    return jpeg_resident.load_resident(src, device, pool_frames, scale=scale)
+                    return jpeg_resident.load_resident(src, device, pool_frames, scale=scale, recode_blocks=recode or None)
                 return jpeg.load_jpeg(src, device, entropy=jpeg_entropy, scale=scale)
             finally:
                 src.close()
+    if recode_blocks is not None:
+        raise ValueError(f"open_video: recode_blocks={recode_blocks!r} needs a Motion-JPEG .avi, a .mjpeg stream or JPEG frames; {video!r} is none of them")
     if resident is not None:
         raise ValueError(f"open_video: resident={resident!r} needs a Motion-JPEG .avi, a .mjpeg stream or JPEG frames; {video!r} is none of them")
     if jpeg_scale is not None:
