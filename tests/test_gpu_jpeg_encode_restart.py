@@ -1,7 +1,7 @@
 """Restart intervals in the JPEG encoder's kernels (csrc/jpeg_enc.hip) against the host twin and against Pillow.
 
-tests/test_jpeg_encode_restart_host.py pins the twin against Pillow on the CPU over the same matrix; here the interval kernels
-(jpeg_enc_rst_*) must give the twin's bytes, lengths, statuses and counters, keep to their slots, carry frames out of RGB and
+tests/test_jpeg_encode_restart_host.py pins the twin against Pillow on the CPU over the same matrix; here the scan stage's kernels
+with an interval (their RST = true forms) must give the twin's bytes, lengths, statuses and counters, keep to their slots, carry frames out of RGB and
 NV12 stores, and write Motion-JPEG that the ingest reads back one lane per restart segment.
 """
 import io
@@ -86,25 +86,39 @@ def test_device_scan_equals_the_host_twin(geom):
 
 
 def test_interval_zero_on_the_device_is_the_marker_free_encode():
-    """tstar_jpeg_encode_scan_rst with interval 0 == tstar_jpeg_encode_scan, and the keywords at 0 / None == encode_frames without them."""
+    """tstar_jpeg_encode_scan_rst with interval 0 == tstar_jpeg_encode_scan, and the keywords at 0 / None == encode_frames without
+    them == tstar_jpeg_encode.  jpeg_encode reaches the _rst entries alone, so the entries without an interval are called here as
+    the ABI has them."""
     import torch
     from tstar_amd import _lib
     from tstar_amd import jpeg_encode as JE
     for H, W, s in GEOMETRIES:
         hs, vs = JE.sampling(s)
         batch = mixed_batch(H, W, s, 5)
-        want = JE.encode_frames(cuda(batch), 100, s)
-        assert want == [pillow_bytes(a, 100, s) for a in batch]
-        assert JE.encode_frames(cuda(batch), 100, s, restart_rows=0, restart_blocks=0) == want
-        assert JE.encode_frames(cuda(batch), 100, s, restart_rows=None, restart_blocks=None) == want
-        coef, _ = JE.blocks_host(batch, 100, s)
         slot = JE.Plan(W, H, hs, vs).max_scan_bytes
-        out, d_len, d_st, d_cnt = device_scan(coef, W, H, s, 0, slot)
         p = JE.Plan(W, H, hs, vs, 5, slot)
         d_out = torch.full((5 * slot + 64,), 0xA5, dtype=torch.uint8, device="cuda")
         o_len = torch.zeros(5, dtype=torch.int32, device="cuda")
         o_st = torch.full((5,), -1, dtype=torch.int32, device="cuda")
         d_work = torch.empty(p.workspace_bytes, dtype=torch.uint8, device="cuda")
+        d_coef = torch.empty(5 * p.coef_bytes, dtype=torch.uint8, device="cuda")
+        d_frames, d_idx = cuda(batch), cuda(np.arange(5, dtype=np.int32))
+        _lib.check(_lib.load().tstar_jpeg_encode(d_frames.data_ptr(), 5, H, W, d_idx.data_ptr(), 5, 100, hs, vs, d_coef.data_ptr(),
+                                                 d_out.data_ptr(), slot, o_len.data_ptr(), o_st.data_ptr(), d_work.data_ptr(),
+                                                 p.workspace_bytes, _lib.stream_ptr()))
+        torch.cuda.synchronize()
+        o_out, lens = d_out.cpu().numpy(), o_len.cpu().numpy().view(np.uint32)
+        assert o_st.cpu().tolist() == [0] * 5
+        want = [JE.header(W, H, 100, s) + o_out[i * slot:i * slot + lens[i]].tobytes() for i in range(5)]
+        assert want == [pillow_bytes(a, 100, s) for a in batch]
+        assert JE.encode_frames(cuda(batch), 100, s) == want
+        assert JE.encode_frames(cuda(batch), 100, s, restart_rows=0, restart_blocks=0) == want
+        assert JE.encode_frames(cuda(batch), 100, s, restart_rows=None, restart_blocks=None) == want
+        coef, _ = JE.blocks_host(batch, 100, s)
+        out, d_len, d_st, d_cnt = device_scan(coef, W, H, s, 0, slot)
+        d_out.fill_(0xA5)
+        o_len.zero_()
+        o_st.fill_(-1)
         d_coef = cuda(coef)
         _lib.check(_lib.load().tstar_jpeg_encode_scan(d_coef.data_ptr(), 5, W, H, hs, vs, d_out.data_ptr(), slot, o_len.data_ptr(),
                                                       o_st.data_ptr(), d_work.data_ptr(), p.workspace_bytes, _lib.stream_ptr()))

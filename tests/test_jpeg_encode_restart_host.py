@@ -61,7 +61,8 @@ def test_rows_win_and_zero_means_none():
 
 
 def test_interval_zero_through_the_new_entries_is_the_existing_entries():
-    """tstar_jpeg_encode_*_rst with interval 0 == the entries without an interval: files, scans, lengths, header, plan, counters."""
+    """tstar_jpeg_encode_*_rst with interval 0 == the entries without an interval: files, scans, lengths, header, plan, counters.
+    jpeg_encode reaches the _rst entries alone, so the entries without an interval are called here as the ABI has them."""
     import ctypes as C
     from tstar_amd import _lib
     from tstar_amd import jpeg_encode as JE
@@ -69,21 +70,31 @@ def test_interval_zero_through_the_new_entries_is_the_existing_entries():
     for H, W, s in GEOMETRIES:
         hs, vs = JE.sampling(s)
         batch = np.stack([rst_picture("noise", H, W, s), rst_picture("smooth", H, W, s)])
+        idx = np.arange(2, dtype=np.int32)
         for q in (30, 100):
             c_old, c_new, r_new = new_counters(), new_counters(), new_restart_counters()
-            old = JE.encode_host(batch, q, s, counters=c_old)
+            p = JE.Plan(W, H, hs, vs, 2)
+            slot = p.header_bytes + p.max_scan_bytes
+            old = (np.empty((2, slot), dtype=np.uint8), np.zeros(2, dtype=np.uint32), np.full(2, -1, dtype=np.int32))
+            _lib.check(lib.tstar_jpeg_encode_host(batch.ctypes.data, 2, H, W, idx.ctypes.data, 2, q, hs, vs, old[0].ctypes.data, slot,
+                                                  old[1].ctypes.data, old[2].ctypes.data, 0, c_old.ctypes.data))
             new = JE.encode_host(batch, q, s, counters=c_new, restart_counters=r_new)          # goes through tstar_jpeg_encode_host_rst
             assert np.array_equal(old[1], new[1]) and np.array_equal(old[2], new[2]) and np.array_equal(c_old, c_new)
             assert all(old[0][i, :old[1][i]].tobytes() == new[0][i, :new[1][i]].tobytes() == pillow_bytes(batch[i], q, s) for i in range(2))
             assert r_new.tolist() == [0, 0, 0]
             coef, _ = JE.blocks_host(batch, q, s)
             r2 = new_restart_counters()
-            a, b = JE.scan_host(coef, W, H, s), JE.scan_host(coef, W, H, s, restart_counters=r2)
+            a_out, a_len, a_st = np.empty((2, p.max_scan_bytes), dtype=np.uint8), np.zeros(2, dtype=np.uint32), np.full(2, -1, dtype=np.int32)
+            _lib.check(lib.tstar_jpeg_encode_scan_host(coef.ctypes.data, 2, W, H, hs, vs, a_out.ctypes.data, p.max_scan_bytes, a_len.ctypes.data,
+                                                       a_st.ctypes.data, 0, None))
+            a = ([a_out[i, :a_len[i]].tobytes() if a_st[i] == 0 else None for i in range(2)], a_len, a_st)
+            b = JE.scan_host(coef, W, H, s, restart_counters=r2)
             assert a[0] == b[0] and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) and r2.tolist() == [0, 0, 0]
-            buf = np.zeros(1024, dtype=np.uint8)
-            n = C.c_size_t(0)
+            buf, plain = np.zeros(1024, dtype=np.uint8), np.zeros(1024, dtype=np.uint8)
+            n, n_plain = C.c_size_t(0), C.c_size_t(0)
             _lib.check(lib.tstar_jpeg_encode_header_rst(W, H, q, hs, vs, 0, buf.ctypes.data, buf.size, C.byref(n)))
-            assert buf[:n.value].tobytes() == JE.header(W, H, q, s) and n.value == 623
+            _lib.check(lib.tstar_jpeg_encode_header(W, H, q, hs, vs, plain.ctypes.data, plain.size, C.byref(n_plain)))
+            assert buf[:n.value].tobytes() == plain[:n_plain.value].tobytes() == JE.header(W, H, q, s) and n.value == n_plain.value == 623
         out8, new8, out2 = (C.c_size_t * 8)(), (C.c_size_t * 8)(), (C.c_size_t * 2)()
         _lib.check(lib.tstar_jpeg_encode_plan(W, H, hs, vs, 3, 4096, out8))
         _lib.check(lib.tstar_jpeg_encode_plan_rst(W, H, hs, vs, 3, 4096, 0, new8, out2))

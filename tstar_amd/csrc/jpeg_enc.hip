@@ -7,27 +7,31 @@
 //                                            -> int16 coefficients in the decoder's layout
 //                  jpeg_enc_dummy_dc_kernel  DC of the dummy luma blocks of the last MCU column / row (a lookup of a real block)
 //   entropy stage  jpeg_enc_bits_kernel<0>   bit length of every block's codes (one lane per block, scan order)
+//                                            [R] the DC predictor is cut at every interval
 //                  jpeg_enc_offsets_kernel   exclusive sum per frame -> bit offsets, the scan's size, whether it can fit
+//                                            [R] a second sum, of every interval's bits rounded up to a byte plus its marker's 16:
+//                                            a block starts at its interval's first bit plus the bits before it inside the
+//                                            interval; the byte offset of every marker goes into a sorted table
 //                  jpeg_enc_bits_kernel<1>   the same walk again, writing the bits into the zeroed unstuffed stream: whole words
 //                                            stored, the two boundary words of a block merged by atomicOr (commutative: the
 //                                            result does not depend on the order of arrival)
+//                                            [R] the lane of an interval's last block also writes the one-bits that fill its byte
+//                                            and the marker, so the unstuffed stream holds both
 //   stuffing       jpeg_enc_ff_kernel<0>     0xFF bytes per chunk of 64 unstuffed bytes
 //                  jpeg_enc_lengths_kernel   exclusive sum per frame -> where each chunk lands, the frame's length and status
 //                  jpeg_enc_ff_kernel<1>     scatter with FF 00, one-bits in the last byte, EOI; only into slots that fit
+//                                            [R] both passes: a chunk's lane finds its first marker in the table by bisection; the
+//                                            marker's FF is neither counted nor followed by 00 (its second byte, D0..D7, is no
+//                                            0xFF anyway)
 //
-// With a restart interval (jpeg_enc_math.h) the entropy stage and the stuffing passes are kernels of their own, launch for
-// launch in the places of the ones above, which stay what they are for scans without markers:
-//   jpeg_enc_rst_bits_kernel<0 / 1>   the DC predictor is cut at every interval; the lane of an interval's last block also writes
-//                                     the one-bits that fill its byte and the marker, so the unstuffed stream holds both
-//   jpeg_enc_rst_offsets_kernel       two sums: bits before every block, then the padded bits (with marker) before every interval;
-//                                     a block starts at its interval's first bit plus the bits before it inside the interval;
-//                                     the byte offset of every marker goes into a sorted table
-//   jpeg_enc_rst_ff_kernel<0 / 1>     a chunk's lane finds its first marker in that table by bisection: the marker's FF is
-//                                     neither counted nor followed by 00 (its second byte, D0..D7, is no 0xFF anyway)
+// [R]: only with a restart interval (jpeg_enc_math.h, "scan order").  The interval is an argument of the one scan launcher; the
+// kernels of the entropy stage and the stuffing passes take it as the compile-time parameter RST, so a scan without markers runs
+// none of the [R] steps and its kernels get no RestartArgs at all (RestartOf<false> is empty: there is nothing they could read).
+#include <type_traits>
+
 #include "../../include/tstar_hip.h"
 #include "common.h"
 #include "jpeg_enc_host.h"
-#include "jpeg_enc_math.h"
 
 namespace tstar {
 
@@ -234,23 +238,56 @@ struct WritePut {
     __device__ __forceinline__ int bits_in_byte() const { return nb & 7; }       // of the position behind the last put
 };
 
+constexpr uint32_t kMarkPadded = 0x80000000u;          // a byte offset is below 2^29: bit offsets fit 32 bits
+
+struct RestartArgs {
+    uint32_t* seg;              // [n][markers + 1]
+    uint32_t* mark;             // [n][markers]
+    uint32_t* counters;         // [n][3] (JPEG_ENC_R_*) or null
+    int interval;               // MCUs
+    int seg_blocks;             // blocks of a full interval
+    uint32_t markers;           // per frame
+};
+struct NoRestart {};            // what the RST = false forms get in its place: no member, so no read of one compiles
+template <bool RST>
+using RestartOf = std::conditional_t<RST, RestartArgs, NoRestart>;
+
 // grid (ceil(blocks / 256), n): lane k of frame f walks the k-th block of the scan.  The DC predictor is the quantised DC of the
-// previous block of the component, a lookup in the coefficients.
-template <int WRITE>
-__global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(EntropyArgs a) {
+// previous block of the component, a lookup in the coefficients.  RST, WRITE: block k of interval s starts at seg[s] + bits[k] -
+// bits[first block of s]; the lane of the last block of an interval that a marker follows appends up to 7 one-bits and the
+// marker's 16.
+template <int WRITE, bool RST>
+__global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(EntropyArgs a, RestartOf<RST> r) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
     if (k >= a.blocks) return;
     uint32_t* meta = a.meta + (size_t)f * 4;
     if (WRITE && meta[META_FLAGS]) return;
+    int interval = 0;
+    if constexpr (RST) interval = r.interval;
     int c, b, pb;
-    jpegenc::scan_block(a.sg, k, &c, &b, &pb);
+    jpegenc::scan_block(a.sg, k, interval, &c, &b, &pb);
     const int16_t* fc = a.coef + (size_t)f * a.blocks * 64;
     const int pred = pb < 0 ? 0 : fc[(size_t)pb * 64];
     const jpegenc::HuffCodes& dc = kDevTables.codes[c ? 2 : 0];
     const jpegenc::HuffCodes& ac = kDevTables.codes[c ? 3 : 1];
     if (WRITE) {
-        WritePut put(a.raw + (size_t)f * a.raw_words, a.bits[(size_t)f * a.blocks + k], a.raw_words);
+        const uint32_t* bits = a.bits + (size_t)f * a.blocks;
+        [[maybe_unused]] uint32_t s = 0, first = 0;
+        uint32_t pos = bits[k];
+        if constexpr (RST) {
+            s = (uint32_t)(k / r.seg_blocks);
+            first = s * (uint32_t)r.seg_blocks;
+            pos = r.seg[(size_t)f * (r.markers + 1) + s] + bits[k] - bits[first];
+        }
+        WritePut put(a.raw + (size_t)f * a.raw_words, pos, a.raw_words);
         jpegenc::encode_block(fc + (size_t)b * 64, pred, dc, ac, kDevZigzag, put);
+        if constexpr (RST) {
+            if (s < r.markers && (uint32_t)k + 1 == first + (uint32_t)r.seg_blocks) {
+                const int fill = (8 - put.bits_in_byte()) & 7;
+                if (fill) put((1u << fill) - 1u, fill);
+                put(0xFFD0u | (s & 7u), 16);
+            }
+        }
         put.finish();
     } else {
         CountPut put;
@@ -298,16 +335,55 @@ __device__ uint32_t workgroup_exclusive_scan(uint32_t* data, uint32_t count) {
 }
 
 // grid (n): block lengths -> bit offsets; the scan's bits and unstuffed bytes; frames whose unstuffed bytes and EOI alone
-// exceed the slot are marked and never written
-__global__ __launch_bounds__(256) void jpeg_enc_offsets_kernel(uint32_t* bits, uint32_t* meta, int blocks, uint32_t slot_bytes) {
-    const int f = blockIdx.x;
-    const uint32_t total = workgroup_exclusive_scan(bits + (size_t)f * blocks, (uint32_t)blocks);
-    if (threadIdx.x == 0) {
+// exceed the slot are marked and never written.
+// RST: after the first sum bits[k] is the bits in front of block k without any padding; an interval that a marker follows takes
+// its bits rounded up to a byte plus 16, the last one its bits alone; the second sum makes seg[s] the first bit of interval s.
+// Marker s sits 16 bits in front of seg[s + 1].
+template <bool RST>
+__global__ __launch_bounds__(256) void jpeg_enc_offsets_kernel(uint32_t* bits, uint32_t* meta, int blocks, uint32_t slot_bytes, RestartOf<RST> r) {
+    const int f = blockIdx.x, t = threadIdx.x;
+    uint32_t* fb = bits + (size_t)f * blocks;
+    uint32_t total = workgroup_exclusive_scan(fb, (uint32_t)blocks);              // < 2^32 by the plan's bound, padding and markers included
+    [[maybe_unused]] uint32_t pad_free = 0;
+    if constexpr (RST) {
+        __shared__ uint32_t pad_free_s;
+        uint32_t* seg = r.seg + (size_t)f * (r.markers + 1);
+        uint32_t* mark = r.mark + (size_t)f * r.markers;
+        const uint32_t data_bits = total;
+        if (t == 0) pad_free_s = 0;
+        __syncthreads();                               // every lane has the first total before the second sum starts its carry
+        auto interval_bits = [&](uint32_t s) {
+            const uint32_t first = s * (uint32_t)r.seg_blocks, next = first + (uint32_t)r.seg_blocks;
+            return (next < (uint32_t)blocks ? fb[next] : data_bits) - fb[first];
+        };
+        for (uint32_t s = (uint32_t)t; s <= r.markers; s += 256) {
+            const uint32_t d = interval_bits(s);
+            seg[s] = s < r.markers ? ((d + 7u) & ~7u) + 16u : d;
+        }
+        __syncthreads();
+        total = workgroup_exclusive_scan(seg, r.markers + 1);
+        uint32_t aligned = 0;
+        for (uint32_t s = (uint32_t)t; s < r.markers; s += 256) {
+            const uint32_t d = interval_bits(s);
+            mark[s] = ((seg[s + 1] - 16u) >> 3) | ((d & 7u) ? kMarkPadded : 0u);
+            aligned += (d & 7u) == 0;
+        }
+        if (aligned) atomicAdd(&pad_free_s, aligned);
+        __syncthreads();
+        pad_free = pad_free_s;
+    }
+    if (t == 0) {
         uint32_t* m = meta + (size_t)f * 4;
-        const uint32_t nbytes = (total >> 3) + ((total & 7u) ? 1u : 0u);          // total < 2^32 by the plan's bound
+        const uint32_t nbytes = (total >> 3) + ((total & 7u) ? 1u : 0u);
         m[META_BITS] = total;
         m[META_BYTES] = nbytes;
         if ((uint64_t)nbytes + 2 > slot_bytes) atomicOr(m + META_FLAGS, (uint32_t)FLAG_SKIP);
+        if constexpr (RST) {
+            if (r.counters) {
+                r.counters[(size_t)f * JPEG_ENC_R_COUNTERS + JPEG_ENC_R_RST] = r.markers;
+                r.counters[(size_t)f * JPEG_ENC_R_COUNTERS + JPEG_ENC_R_PAD_FREE] = pad_free;
+            }
+        }
     }
 }
 
@@ -331,8 +407,10 @@ __device__ __forceinline__ uint32_t raw_byte(const uint32_t* raw, uint32_t i, ui
 // grid (ceil(ff_chunks / 256), n): one lane per chunk of 64 unstuffed bytes.  SCATTER = 0 counts its 0xFF bytes; SCATTER = 1
 // writes the chunk at its place in the slot (its raw offset plus the 0xFF bytes before it) and, from the lane of the last
 // chunk, EOI.  A frame whose status is not 0 is left alone, so every write lands inside [0, length) <= slot_bytes.
-template <int SCATTER>
-__global__ __launch_bounds__(256) void jpeg_enc_ff_kernel(StuffArgs a) {
+// RST: the unstuffed stream holds the markers, and byte mark[i] of it is a marker's FF, which is neither counted nor stuffed; the
+// count pass also counts the padded bytes in front of a marker that came out as 0xFF.
+template <int SCATTER, bool RST>
+__global__ __launch_bounds__(256) void jpeg_enc_ff_kernel(StuffArgs a, RestartOf<RST> r) {
     const uint32_t chunk = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
     const uint32_t* m = a.meta + (size_t)f * 4;
     if (m[META_FLAGS]) return;
@@ -341,10 +419,37 @@ __global__ __launch_bounds__(256) void jpeg_enc_ff_kernel(StuffArgs a) {
     if (chunk >= a.ff_chunks || begin >= nbytes) return;
     const uint32_t end = begin + kJpegEncStuffChunk < nbytes ? begin + kJpegEncStuffChunk : nbytes;
     const uint32_t* raw = a.raw + (size_t)f * a.raw_words;
+    [[maybe_unused]] const uint32_t* mark = nullptr;
+    [[maybe_unused]] uint32_t mi = 0, next = 0xffffffffu;                          // the next marker and its table entry; no byte has offset 2^31 - 1
+    if constexpr (RST) {
+        mark = r.mark + (size_t)f * r.markers;
+        uint32_t lo = 0, hi = r.markers;               // the first marker at or behind `begin`
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if ((mark[mid] & ~kMarkPadded) < begin) lo = mid + 1;
+            else hi = mid;
+        }
+        mi = lo;
+        if (mi < r.markers) next = mark[mi];
+    }
     if (!SCATTER) {
         uint32_t n = 0;
-        for (uint32_t i = begin; i < end; ++i) n += raw_byte(raw, i, nbytes, total_bits) == 255u;
+        [[maybe_unused]] uint32_t pad_ff = 0;
+        for (uint32_t i = begin; i < end; ++i) {
+            if constexpr (RST) {
+                if (i == (next & ~kMarkPadded)) {
+                    if ((next & kMarkPadded) && raw_byte(raw, i - 1, nbytes, total_bits) == 255u) ++pad_ff;
+                    ++mi;
+                    next = mi < r.markers ? mark[mi] : 0xffffffffu;
+                    continue;
+                }
+            }
+            n += raw_byte(raw, i, nbytes, total_bits) == 255u;
+        }
         a.ff[(size_t)f * a.ff_chunks + chunk] = n;
+        if constexpr (RST) {
+            if (pad_ff && r.counters) atomicAdd(r.counters + (size_t)f * JPEG_ENC_R_COUNTERS + JPEG_ENC_R_PAD_FF, pad_ff);
+        }
     } else {
         if (a.status[f] != JPEG_ENC_OK) return;
         uint8_t* out = a.out + (size_t)f * a.slot_bytes;
@@ -354,6 +459,13 @@ __global__ __launch_bounds__(256) void jpeg_enc_ff_kernel(StuffArgs a) {
             const uint32_t b = raw_byte(raw, i, nbytes, total_bits);
             if (o < len) out[o] = (uint8_t)b;
             ++o;
+            if constexpr (RST) {
+                if (i == (next & ~kMarkPadded)) {
+                    ++mi;
+                    next = mi < r.markers ? mark[mi] : 0xffffffffu;
+                    continue;
+                }
+            }
             if (b == 255u) {
                 if (o < len) out[o] = 0;
                 ++o;
@@ -393,151 +505,6 @@ __global__ __launch_bounds__(256) void jpeg_enc_lengths_kernel(StuffArgs a) {
     }
 }
 
-// ------------------------------------------------------------------------------------------------ restart intervals
-constexpr uint32_t kMarkPadded = 0x80000000u;          // a byte offset is below 2^29: bit offsets fit 32 bits
-
-struct RestartArgs {
-    uint32_t* seg;              // [n][markers + 1]
-    uint32_t* mark;             // [n][markers]
-    uint32_t* counters;         // [n][3] (JPEG_ENC_R_*) or null
-    int interval;               // MCUs
-    int seg_blocks;             // blocks of a full interval
-    uint32_t markers;           // per frame
-};
-
-// jpeg_enc_bits_kernel with intervals.  WRITE: block k of interval s starts at seg[s] + bits[k] - bits[first block of s]; the
-// lane of the last block of an interval that a marker follows appends up to 7 one-bits and the marker's 16.
-template <int WRITE>
-__global__ __launch_bounds__(256) void jpeg_enc_rst_bits_kernel(EntropyArgs a, RestartArgs r) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
-    if (k >= a.blocks) return;
-    uint32_t* meta = a.meta + (size_t)f * 4;
-    if (WRITE && meta[META_FLAGS]) return;
-    int c, b, pb;
-    jpegenc::scan_block_rst(a.sg, k, r.interval, &c, &b, &pb);
-    const int16_t* fc = a.coef + (size_t)f * a.blocks * 64;
-    const int pred = pb < 0 ? 0 : fc[(size_t)pb * 64];
-    const jpegenc::HuffCodes& dc = kDevTables.codes[c ? 2 : 0];
-    const jpegenc::HuffCodes& ac = kDevTables.codes[c ? 3 : 1];
-    if (WRITE) {
-        const uint32_t* bits = a.bits + (size_t)f * a.blocks;
-        const uint32_t s = (uint32_t)(k / r.seg_blocks), first = s * (uint32_t)r.seg_blocks;
-        const uint32_t pos = r.seg[(size_t)f * (r.markers + 1) + s] + bits[k] - bits[first];
-        WritePut put(a.raw + (size_t)f * a.raw_words, pos, a.raw_words);
-        jpegenc::encode_block(fc + (size_t)b * 64, pred, dc, ac, kDevZigzag, put);
-        if (s < r.markers && (uint32_t)k + 1 == first + (uint32_t)r.seg_blocks) {
-            const int fill = (8 - put.bits_in_byte()) & 7;
-            if (fill) put((1u << fill) - 1u, fill);
-            put(0xFFD0u | (s & 7u), 16);
-        }
-        put.finish();
-    } else {
-        CountPut put;
-        const jpegenc::BlockEvents ev = jpegenc::encode_block(fc + (size_t)b * 64, pred, dc, ac, kDevZigzag, put);
-        a.bits[(size_t)f * a.blocks + k] = put.n;
-        if (ev.bad) atomicOr(meta + META_FLAGS, (uint32_t)FLAG_BAD_COEF);
-    }
-}
-
-// grid (n): jpeg_enc_offsets_kernel with intervals.  After the first sum bits[k] is the bits in front of block k without any
-// padding; an interval that a marker follows takes its bits rounded up to a byte plus 16, the last one its bits alone; the
-// second sum makes seg[s] the first bit of interval s.  Marker s sits 16 bits in front of seg[s + 1].
-__global__ __launch_bounds__(256) void jpeg_enc_rst_offsets_kernel(uint32_t* bits, uint32_t* meta, int blocks, uint32_t slot_bytes, RestartArgs r) {
-    __shared__ uint32_t pad_free_s;
-    const int f = blockIdx.x, t = threadIdx.x;
-    uint32_t* fb = bits + (size_t)f * blocks;
-    uint32_t* seg = r.seg + (size_t)f * (r.markers + 1);
-    uint32_t* mark = r.mark + (size_t)f * r.markers;
-    const uint32_t data_bits = workgroup_exclusive_scan(fb, (uint32_t)blocks);
-    if (t == 0) pad_free_s = 0;
-    __syncthreads();                                   // every lane has the first total before the second sum starts its carry
-    auto interval_bits = [&](uint32_t s) {
-        const uint32_t first = s * (uint32_t)r.seg_blocks, next = first + (uint32_t)r.seg_blocks;
-        return (next < (uint32_t)blocks ? fb[next] : data_bits) - fb[first];
-    };
-    for (uint32_t s = (uint32_t)t; s <= r.markers; s += 256) {
-        const uint32_t d = interval_bits(s);
-        seg[s] = s < r.markers ? ((d + 7u) & ~7u) + 16u : d;
-    }
-    __syncthreads();
-    const uint32_t total = workgroup_exclusive_scan(seg, r.markers + 1);          // < 2^32 by the plan's bound
-    uint32_t aligned = 0;
-    for (uint32_t s = (uint32_t)t; s < r.markers; s += 256) {
-        const uint32_t d = interval_bits(s);
-        mark[s] = ((seg[s + 1] - 16u) >> 3) | ((d & 7u) ? kMarkPadded : 0u);
-        aligned += (d & 7u) == 0;
-    }
-    if (aligned) atomicAdd(&pad_free_s, aligned);
-    __syncthreads();
-    if (t == 0) {
-        uint32_t* m = meta + (size_t)f * 4;
-        const uint32_t nbytes = (total >> 3) + ((total & 7u) ? 1u : 0u);
-        m[META_BITS] = total;
-        m[META_BYTES] = nbytes;
-        if ((uint64_t)nbytes + 2 > slot_bytes) atomicOr(m + META_FLAGS, (uint32_t)FLAG_SKIP);
-        if (r.counters) {
-            r.counters[(size_t)f * JPEG_ENC_R_COUNTERS + JPEG_ENC_R_RST] = r.markers;
-            r.counters[(size_t)f * JPEG_ENC_R_COUNTERS + JPEG_ENC_R_PAD_FREE] = pad_free_s;
-        }
-    }
-}
-
-// jpeg_enc_ff_kernel with intervals: the unstuffed stream holds the markers, and byte mark[i] of it is a marker's FF
-template <int SCATTER>
-__global__ __launch_bounds__(256) void jpeg_enc_rst_ff_kernel(StuffArgs a, RestartArgs r) {
-    const uint32_t chunk = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
-    const uint32_t* m = a.meta + (size_t)f * 4;
-    if (m[META_FLAGS]) return;
-    const uint32_t nbytes = m[META_BYTES], total_bits = m[META_BITS];
-    const uint32_t begin = chunk * (uint32_t)kJpegEncStuffChunk;
-    if (chunk >= a.ff_chunks || begin >= nbytes) return;
-    const uint32_t end = begin + kJpegEncStuffChunk < nbytes ? begin + kJpegEncStuffChunk : nbytes;
-    const uint32_t* raw = a.raw + (size_t)f * a.raw_words;
-    const uint32_t* mark = r.mark + (size_t)f * r.markers;
-    uint32_t lo = 0, hi = r.markers;                   // the first marker at or behind `begin`
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if ((mark[mid] & ~kMarkPadded) < begin) lo = mid + 1;
-        else hi = mid;
-    }
-    uint32_t mi = lo, next = mi < r.markers ? mark[mi] : 0xffffffffu;             // no byte has offset 2^31 - 1
-    if (!SCATTER) {
-        uint32_t n = 0, pad_ff = 0;
-        for (uint32_t i = begin; i < end; ++i) {
-            if (i == (next & ~kMarkPadded)) {
-                if ((next & kMarkPadded) && raw_byte(raw, i - 1, nbytes, total_bits) == 255u) ++pad_ff;
-                ++mi;
-                next = mi < r.markers ? mark[mi] : 0xffffffffu;
-                continue;
-            }
-            n += raw_byte(raw, i, nbytes, total_bits) == 255u;
-        }
-        a.ff[(size_t)f * a.ff_chunks + chunk] = n;
-        if (pad_ff && r.counters) atomicAdd(r.counters + (size_t)f * JPEG_ENC_R_COUNTERS + JPEG_ENC_R_PAD_FF, pad_ff);
-    } else {
-        if (a.status[f] != JPEG_ENC_OK) return;
-        uint8_t* out = a.out + (size_t)f * a.slot_bytes;
-        const uint32_t len = a.lengths[f];
-        uint32_t o = begin + a.ff[(size_t)f * a.ff_chunks + chunk];
-        for (uint32_t i = begin; i < end; ++i) {
-            const uint32_t b = raw_byte(raw, i, nbytes, total_bits);
-            if (o < len) out[o] = (uint8_t)b;
-            ++o;
-            if (i == (next & ~kMarkPadded)) {
-                ++mi;
-                next = mi < r.markers ? mark[mi] : 0xffffffffu;
-            } else if (b == 255u) {
-                if (o < len) out[o] = 0;
-                ++o;
-            }
-        }
-        if (end == nbytes && o + 2 == len) {
-            out[o] = 0xFF;
-            out[o + 1] = 0xD9;
-        }
-    }
-}
-
 }  // namespace
 
 int jpeg_encode_blocks_u8(const uint8_t* frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, const JpegGeom& g,
@@ -567,9 +534,33 @@ int jpeg_encode_blocks_u8(const uint8_t* frames, int N, int H, int W, const int3
     return TSTAR_OK;
 }
 
-int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status,
-                        void* workspace, size_t workspace_bytes, hipStream_t s) {
-    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes);
+namespace {
+
+// the six launches of the scan stage, with (RST) or without the interval-only steps
+template <bool RST>
+int launch_scan(const JpegEncPlan& p, int n, const EntropyArgs& e, const StuffArgs& a, const RestartOf<RST>& r, hipStream_t s) {
+    const dim3 egrid(p.entropy_wgs_x, (unsigned)n), sgrid(p.stuff_wgs_x, (unsigned)n);
+    hipLaunchKernelGGL((jpeg_enc_bits_kernel<0, RST>), egrid, dim3(256), 0, s, e, r);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_offsets_kernel<RST>, dim3((unsigned)n), dim3(256), 0, s, e.bits, e.meta, e.blocks, a.slot_bytes, r);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((jpeg_enc_bits_kernel<1, RST>), egrid, dim3(256), 0, s, e, r);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((jpeg_enc_ff_kernel<0, RST>), sgrid, dim3(256), 0, s, a, r);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(jpeg_enc_lengths_kernel, dim3((unsigned)n), dim3(256), 0, s, a);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((jpeg_enc_ff_kernel<1, RST>), sgrid, dim3(256), 0, s, a, r);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    return TSTAR_OK;
+}
+
+}  // namespace
+
+// the scan stage with a restart interval of `restart` MCUs (0: none).  d_rst_counters: optional u32 [n][3], zeroed here
+int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths,
+                        int32_t* status, void* workspace, size_t workspace_bytes, uint32_t* d_rst_counters, hipStream_t s) {
+    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart);
     TSTAR_REQUIRE(!p.error, std::string("jpeg_encode_scan_u8: ") + (p.error ? p.error : ""));
     TSTAR_REQUIRE((uintptr_t)workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
                   "jpeg_encode_scan_u8: the workspace is misaligned or smaller than the plan's workspace_bytes");
@@ -579,51 +570,19 @@ int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, uint8_t* 
     e.meta = (uint32_t*)(ws + p.off_meta);
     e.bits = (uint32_t*)(ws + p.off_bits);
     e.raw = (uint32_t*)(ws + p.off_raw);
-    e.sg = jpegenc::ScanGeom{g.hs, g.vs, g.mcux(), g.mcuy(), g.bw(0), (int)g.block_offset(1), (int)g.block_offset(2)};
+    e.sg = scan_geom(g);
     e.blocks = (int)p.blocks;
     e.raw_words = (uint32_t)p.raw_words;
-    // meta (flags) and the unstuffed stream start from zero: the stream is assembled by OR
-    TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), s));
-    TSTAR_HIP_CHECK(hipMemsetAsync(e.raw, 0, (size_t)n * p.raw_words * sizeof(uint32_t), s));
-    const dim3 egrid(p.entropy_wgs_x, (unsigned)n), sgrid(p.stuff_wgs_x, (unsigned)n);
-    hipLaunchKernelGGL(jpeg_enc_bits_kernel<0>, egrid, dim3(256), 0, s, e);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_enc_offsets_kernel, dim3((unsigned)n), dim3(256), 0, s, e.bits, e.meta, e.blocks, (uint32_t)slot_bytes);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_enc_bits_kernel<1>, egrid, dim3(256), 0, s, e);
-    TSTAR_HIP_CHECK(hipGetLastError());
     StuffArgs a;
     a.raw = e.raw; a.meta = e.meta;
     a.ff = (uint32_t*)(ws + p.off_ff);
     a.out = out; a.lengths = lengths; a.status = status;
     a.raw_words = (uint32_t)p.raw_words; a.ff_chunks = (uint32_t)p.ff_chunks; a.slot_bytes = (uint32_t)slot_bytes;
-    hipLaunchKernelGGL(jpeg_enc_ff_kernel<0>, sgrid, dim3(256), 0, s, a);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_enc_lengths_kernel, dim3((unsigned)n), dim3(256), 0, s, a);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_enc_ff_kernel<1>, sgrid, dim3(256), 0, s, a);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    return TSTAR_OK;
-}
-
-// the scan stage with a restart interval of `restart` MCUs; 0 is jpeg_encode_scan_u8 itself.  d_rst_counters: optional u32 [n][3]
-int jpeg_encode_scan_rst_u8(const int16_t* coef, int n, const JpegGeom& g, int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths,
-                            int32_t* status, void* workspace, size_t workspace_bytes, uint32_t* d_rst_counters, hipStream_t s) {
-    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart);
-    TSTAR_REQUIRE(!p.error, std::string("jpeg_encode_scan_rst_u8: ") + (p.error ? p.error : ""));
+    // meta (flags) and the unstuffed stream start from zero: the stream is assembled by OR
+    TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), s));
+    TSTAR_HIP_CHECK(hipMemsetAsync(e.raw, 0, (size_t)n * p.raw_words * sizeof(uint32_t), s));
     if (d_rst_counters) TSTAR_HIP_CHECK(hipMemsetAsync(d_rst_counters, 0, (size_t)n * JPEG_ENC_R_COUNTERS * sizeof(uint32_t), s));
-    if (restart == 0) return jpeg_encode_scan_u8(coef, n, g, out, slot_bytes, lengths, status, workspace, workspace_bytes, s);
-    TSTAR_REQUIRE((uintptr_t)workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
-                  "jpeg_encode_scan_rst_u8: the workspace is misaligned or smaller than the plan's workspace_bytes");
-    uint8_t* ws = (uint8_t*)workspace;
-    EntropyArgs e;
-    e.coef = coef;
-    e.meta = (uint32_t*)(ws + p.off_meta);
-    e.bits = (uint32_t*)(ws + p.off_bits);
-    e.raw = (uint32_t*)(ws + p.off_raw);
-    e.sg = jpegenc::ScanGeom{g.hs, g.vs, g.mcux(), g.mcuy(), g.bw(0), (int)g.block_offset(1), (int)g.block_offset(2)};
-    e.blocks = (int)p.blocks;
-    e.raw_words = (uint32_t)p.raw_words;
+    if (restart == 0) return launch_scan<false>(p, n, e, a, NoRestart{}, s);
     RestartArgs r;
     r.seg = (uint32_t*)(ws + p.off_seg);
     r.mark = (uint32_t*)(ws + p.off_mark);
@@ -631,27 +590,7 @@ int jpeg_encode_scan_rst_u8(const int16_t* coef, int n, const JpegGeom& g, int r
     r.interval = restart;
     r.seg_blocks = restart * e.sg.per_mcu();           // at most 65535 * 6; at least the frame's blocks when there is no marker
     r.markers = (uint32_t)p.markers;
-    TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), s));
-    TSTAR_HIP_CHECK(hipMemsetAsync(e.raw, 0, (size_t)n * p.raw_words * sizeof(uint32_t), s));
-    const dim3 egrid(p.entropy_wgs_x, (unsigned)n), sgrid(p.stuff_wgs_x, (unsigned)n);
-    hipLaunchKernelGGL(jpeg_enc_rst_bits_kernel<0>, egrid, dim3(256), 0, s, e, r);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_enc_rst_offsets_kernel, dim3((unsigned)n), dim3(256), 0, s, e.bits, e.meta, e.blocks, (uint32_t)slot_bytes, r);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_enc_rst_bits_kernel<1>, egrid, dim3(256), 0, s, e, r);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    StuffArgs a;
-    a.raw = e.raw; a.meta = e.meta;
-    a.ff = (uint32_t*)(ws + p.off_ff);
-    a.out = out; a.lengths = lengths; a.status = status;
-    a.raw_words = (uint32_t)p.raw_words; a.ff_chunks = (uint32_t)p.ff_chunks; a.slot_bytes = (uint32_t)slot_bytes;
-    hipLaunchKernelGGL(jpeg_enc_rst_ff_kernel<0>, sgrid, dim3(256), 0, s, a, r);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_enc_lengths_kernel, dim3((unsigned)n), dim3(256), 0, s, a);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(jpeg_enc_rst_ff_kernel<1>, sgrid, dim3(256), 0, s, a, r);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    return TSTAR_OK;
+    return launch_scan<true>(p, n, e, a, r, s);
 }
 
 }  // namespace tstar
@@ -669,28 +608,28 @@ int tstar_jpeg_encode_blocks(const uint8_t* d_frames, int N, int H, int W, const
     return TSTAR_OK;
 }
 
+// the two entries without an interval forward to the _rst entries with interval 0 and no counters, as on the host side
 int tstar_jpeg_encode_scan(const int16_t* d_coef, int n, int W, int H, int hs, int vs, uint8_t* d_out, size_t slot_bytes,
                            uint32_t* d_lengths, int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
     TSTAR_REQUIRE(d_coef && d_out && d_lengths && d_status && d_workspace, "tstar_jpeg_encode_scan: null argument");
-    return jpeg_encode_scan_u8(d_coef, n, JpegGeom{W, H, 3, hs, vs}, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes,
-                               (hipStream_t)stream);
+    return tstar_jpeg_encode_scan_rst(d_coef, n, W, H, hs, vs, 0, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes, nullptr,
+                                      stream);
 }
 
 int tstar_jpeg_encode(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
                       int16_t* d_coef, uint8_t* d_out, size_t slot_bytes, uint32_t* d_lengths, int32_t* d_status, void* d_workspace,
                       size_t workspace_bytes, void* stream) {
     TSTAR_REQUIRE(d_frames && d_idx && d_coef && d_out && d_lengths && d_status && d_workspace, "tstar_jpeg_encode: null argument");
-    const JpegGeom g{W, H, 3, hs, vs};
-    RC(jpeg_encode_blocks_u8(d_frames, N, H, W, d_idx, n, quality, g, d_coef, (hipStream_t)stream));
-    return jpeg_encode_scan_u8(d_coef, n, g, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes, (hipStream_t)stream);
+    return tstar_jpeg_encode_rst(d_frames, N, H, W, d_idx, n, quality, hs, vs, 0, d_coef, d_out, slot_bytes, d_lengths, d_status, d_workspace,
+                                 workspace_bytes, nullptr, stream);
 }
 
 int tstar_jpeg_encode_scan_rst(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* d_out, size_t slot_bytes,
                                uint32_t* d_lengths, int32_t* d_status, void* d_workspace, size_t workspace_bytes,
                                uint32_t* d_rst_counters, void* stream) {
     TSTAR_REQUIRE(d_coef && d_out && d_lengths && d_status && d_workspace, "tstar_jpeg_encode_scan_rst: null argument");
-    return jpeg_encode_scan_rst_u8(d_coef, n, JpegGeom{W, H, 3, hs, vs}, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace,
-                                   workspace_bytes, d_rst_counters, (hipStream_t)stream);
+    return jpeg_encode_scan_u8(d_coef, n, JpegGeom{W, H, 3, hs, vs}, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace,
+                               workspace_bytes, d_rst_counters, (hipStream_t)stream);
 }
 
 int tstar_jpeg_encode_rst(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
@@ -700,8 +639,8 @@ int tstar_jpeg_encode_rst(const uint8_t* d_frames, int N, int H, int W, const in
     const JpegGeom g{W, H, 3, hs, vs};
     TSTAR_REQUIRE(jpeg_enc_restart_ok(restart), "tstar_jpeg_encode_rst: restart interval outside 0..65535 MCUs");
     RC(jpeg_encode_blocks_u8(d_frames, N, H, W, d_idx, n, quality, g, d_coef, (hipStream_t)stream));
-    return jpeg_encode_scan_rst_u8(d_coef, n, g, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes,
-                                   d_rst_counters, (hipStream_t)stream);
+    return jpeg_encode_scan_u8(d_coef, n, g, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes,
+                               d_rst_counters, (hipStream_t)stream);
 }
 
 }  // extern "C"

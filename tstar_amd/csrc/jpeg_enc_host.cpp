@@ -10,8 +10,6 @@
 #include <thread>
 #include <vector>
 
-#include "jpeg_enc_math.h"
-
 namespace tstar {
 
 void set_error(const std::string& msg);          // capi.hip (or the stand-alone checker): thread-local last error
@@ -74,8 +72,6 @@ void jpeg_enc_quant(int quality, uint16_t* quant) {
     for (int c = 0; c < 3; ++c)
         for (int k = 0; k < 64; ++k) quant[c * 64 + k] = (uint16_t)jpegenc::quant_entry(jpegenc::kStd.q[c ? 1 : 0][k], scale);
 }
-
-void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out) { jpeg_enc_header(g, quality, 0, out); }
 
 void jpeg_enc_header(const JpegGeom& g, int quality, int restart, uint8_t* out) {
     uint16_t quant[192];
@@ -158,10 +154,6 @@ void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quan
 
 namespace {
 
-jpegenc::ScanGeom scan_geom(const JpegGeom& g) {
-    return jpegenc::ScanGeom{g.hs, g.vs, g.mcux(), g.mcuy(), g.bw(0), (int)g.block_offset(1), (int)g.block_offset(2)};
-}
-
 struct ByteSink {                        // MSB-first bit writer with FF -> FF 00
     std::vector<uint8_t> bytes;
     uint64_t acc = 0, stuffed = 0;
@@ -214,7 +206,7 @@ static int scan_frame(const int16_t* coef, const JpegGeom& g, int restart, ByteS
             sink.marker(0xD0 + (int)(rst++ & 7));
         }
         int c, b, pb;
-        jpegenc::scan_block_rst(sg, k, restart, &c, &b, &pb);
+        jpegenc::scan_block(sg, k, restart, &c, &b, &pb);
         const int pred = pb < 0 ? 0 : coef[(size_t)pb * 64];
         const jpegenc::BlockEvents ev = jpegenc::encode_block(coef + (size_t)b * 64, pred, kTables.codes[c ? 2 : 0], kTables.codes[c ? 3 : 1],
                                                               jpegenc::kStd.zigzag, sink);
@@ -234,10 +226,6 @@ static int scan_frame(const int16_t* coef, const JpegGeom& g, int restart, ByteS
         rst_counters[JPEG_ENC_R_PAD_FF] += pad_ff;
     }
     return bad ? JPEG_ENC_BAD_COEF : JPEG_ENC_OK;
-}
-
-int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, uint8_t* out, size_t cap, size_t* len, uint64_t* counters) {
-    return jpeg_enc_scan(coef, g, 0, out, cap, len, counters, nullptr);
 }
 
 int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, uint64_t* counters,

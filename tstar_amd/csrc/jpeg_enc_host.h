@@ -14,6 +14,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "jpeg_enc_math.h"
 #include "jpeg_host.h"
 
 namespace tstar {
@@ -31,7 +32,7 @@ constexpr int kJpegEncHeaderBytes = 623;      // 2 + 18 + 2 * 69 + 19 + 2 * 33 +
 constexpr int kJpegEncDriBytes = 6;           // FF DD 00 04 hi lo, directly before SOS when the scan has a restart interval
 
 // Restart intervals (every entry below that takes `restart`: MCUs per interval, 0 = none, at most kJpegEncMaxRestart -- the
-// DRI segment holds 16 bits).  What a scan with an interval holds: jpeg_enc_math.h, "restart intervals".  Counters of their
+// DRI segment holds 16 bits).  What a scan with an interval holds: jpeg_enc_math.h, "scan order".  Counters of their
 // own (optional, added to): markers written; intervals in front of a marker that ended on a byte boundary (no padding);
 // padded bytes in front of a marker that came out as 0xFF (and were stuffed like any data byte).
 constexpr int kJpegEncMaxRestart = 65535;
@@ -75,9 +76,8 @@ JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes, int re
 
 // quant u16 [3][64], natural order, rows Y / Cb / Cr (the decoder's table layout); quality 1..100
 void jpeg_enc_quant(int quality, uint16_t* quant);
-// the header of every frame of geometry g at this quality: exactly kJpegEncHeaderBytes bytes
-void jpeg_enc_header(const JpegGeom& g, int quality, uint8_t* out);
-// the same with DRI in front of SOS when restart > 0: jpeg_enc_header_bytes(restart) bytes
+// the header of every frame of geometry g at this quality, with DRI in front of SOS when restart > 0: exactly
+// jpeg_enc_header_bytes(restart) bytes
 void jpeg_enc_header(const JpegGeom& g, int quality, int restart, uint8_t* out);
 // the same layout with the DQT entries given (quant u16 [3][64], natural order, rows Y / Cb / Cr, every value 1..65535), for a
 // file that is re-coded losslessly: two tables when the chroma rows are equal (what the header above writes), else three; a table
@@ -88,10 +88,13 @@ size_t jpeg_enc_header_tables(const JpegGeom& g, const uint16_t* quant, int rest
 
 // stage 1, one frame: rgb u8 [H][W][3] -> coef int16 [g.blocks()][64]; dummy2 (optional) += {right-edge, bottom-edge} dummy blocks
 void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2);
-// stage 2, one frame: -> *len = the bytes the scan takes (with EOI), written to out only when they fit cap.  counters
-// (optional, JPEG_ENC_N_*) are added to, for frames that fit and frames that do not alike.
-int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, uint8_t* out, size_t cap, size_t* len, uint64_t* counters);
-// the same with a restart interval; rst_counters (optional, JPEG_ENC_R_*) are added to likewise
+// the scan order of g's coefficient layout, for the host twin and the kernels alike
+inline jpegenc::ScanGeom scan_geom(const JpegGeom& g) {
+    return jpegenc::ScanGeom{g.hs, g.vs, g.mcux(), g.mcuy(), g.bw(0), (int)g.block_offset(1), (int)g.block_offset(2)};
+}
+// stage 2, one frame, with a restart interval of `restart` MCUs: -> *len = the bytes the scan takes (with EOI), written to out
+// only when they fit cap.  counters (optional, JPEG_ENC_N_*) and rst_counters (optional, JPEG_ENC_R_*) are added to, for frames
+// that fit and frames that do not alike.
 int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, uint64_t* counters,
                   uint64_t* rst_counters);
 

@@ -221,6 +221,11 @@ TSTAR_JHD BlockEvents encode_block(const int16_t* coef, int pred, const HuffCode
 // ---------------------------------------------------------------------------------------------- scan order
 // The k-th block of a frame's interleaved scan (MCU after MCU; inside it the Y blocks row-major, then Cb, Cr): its component,
 // its index in the coefficient layout, and the index of the block whose DC it is predicted from (-1: none, predictor 0).
+//
+// A scan with a restart interval of R MCUs (R >= 1; 0: none) is cut behind every R-th MCU but the last: the entropy coder fills
+// the current byte with one-bits, RSTn follows (FF D0 + n mod 8, n counting the markers of the scan from 0) and every component's
+// DC predictor starts from 0 again: the first block of a component in an interval has no predecessor.  The scan then holds
+// (MCUs - 1) / R markers and one interval more.
 struct ScanGeom {
     int hs, vs, mcux, mcuy, bw0;           // bw0: luma blocks per row of the padded layout
     int off1, off2;                        // first Cb / Cr block of the layout
@@ -231,7 +236,7 @@ TSTAR_JHD int luma_block(const ScanGeom& g, int m, int j) {
     const int mx = m % g.mcux, my = m / g.mcux;
     return (my * g.vs + j / g.hs) * g.bw0 + mx * g.hs + j % g.hs;
 }
-TSTAR_JHD void scan_block(const ScanGeom& g, int k, int* comp, int* block, int* pred_block) {
+TSTAR_JHD void scan_block(const ScanGeom& g, int k, int interval, int* comp, int* block, int* pred_block) {
     const int ny = g.hs * g.vs, m = k / (ny + 2), j = k % (ny + 2);
     if (j < ny) {
         *comp = 0;
@@ -243,19 +248,7 @@ TSTAR_JHD void scan_block(const ScanGeom& g, int k, int* comp, int* block, int* 
         *block = off + m;
         *pred_block = m > 0 ? off + m - 1 : -1;
     }
-}
-
-// ---------------------------------------------------------------------------------------------- restart intervals
-// A scan with a restart interval of R MCUs (R >= 1) is cut behind every R-th MCU but the last: the entropy coder fills the
-// current byte with one-bits, RSTn follows (FF D0 + n mod 8, n counting the markers of the scan from 0) and every component's
-// DC predictor starts from 0 again.  The scan then holds (MCUs - 1) / R markers and one interval more.
-// scan_block under a restart interval (0: none): the first block of a component in an interval has no predecessor
-TSTAR_JHD void scan_block_rst(const ScanGeom& g, int k, int interval, int* comp, int* block, int* pred_block) {
-    scan_block(g, k, comp, block, pred_block);
-    if (interval > 0) {
-        const int per = g.per_mcu(), m = k / per, j = k % per;
-        if (m % interval == 0 && (j == 0 || j >= per - 2)) *pred_block = -1;
-    }
+    if (interval > 0 && m % interval == 0 && (j == 0 || j >= ny)) *pred_block = -1;
 }
 // Bits an interval's end adds to the scan at most: 7 pad bits and the 16 of the marker
 constexpr int kRestartBits = 7 + 16;

@@ -71,9 +71,9 @@ int run_case(const Case& cs, int restart) {
         for (uint8_t& v : rgb) v = (uint8_t)rnd();
         jpeg_enc_blocks(rgb.data(), g, quant, coef.data() + (size_t)i * blocks * 64, nullptr);
         std::vector<uint8_t> f(kJpegEncHeaderBytes + max_scan);
-        jpeg_enc_header(g, quality, f.data());
+        jpeg_enc_header(g, quality, 0, f.data());
         size_t len = 0;
-        if (jpeg_enc_scan(coef.data() + (size_t)i * blocks * 64, g, f.data() + kJpegEncHeaderBytes, max_scan, &len, nullptr) != JPEG_ENC_OK) return fail("source scan", cs, restart);
+        if (jpeg_enc_scan(coef.data() + (size_t)i * blocks * 64, g, 0, f.data() + kJpegEncHeaderBytes, max_scan, &len, nullptr, nullptr) != JPEG_ENC_OK) return fail("source scan", cs, restart);
         f.resize(kJpegEncHeaderBytes + len);
         files[i] = f;
     }

@@ -80,21 +80,16 @@ def _restart_values(restart_rows, restart_blocks) -> tuple:
 
 
 class Plan:
-    """tstar_jpeg_encode_plan: sizes and launch shape for n frames of W x H whose scans go into slots of slot_bytes.  With
-    ``restart`` (MCUs per interval) tstar_jpeg_encode_plan_rst: the bounds hold the markers and the padding, and ``markers`` is
-    their number per frame."""
+    """tstar_jpeg_encode_plan_rst: sizes and launch shape for n frames of W x H whose scans go into slots of slot_bytes.  With
+    ``restart`` (MCUs per interval; 0: none) the bounds hold the markers and the padding, and ``markers`` is their number per
+    frame."""
     FIELDS = ("blocks", "coef_bytes", "max_scan_bytes", "header_bytes", "workspace_bytes", "block_wgs", "entropy_wgs_x", "stuff_wgs_x")
 
     def __init__(self, W: int, H: int, hs: int, vs: int, n: int = 1, slot_bytes: int = 2, restart: int = 0):
         from . import _lib
-        out = (C.c_size_t * 8)()
-        self.restart, self.markers = int(restart), 0
-        if restart:
-            out2 = (C.c_size_t * 2)()
-            _lib.check(_lib.load().tstar_jpeg_encode_plan_rst(W, H, hs, vs, n, slot_bytes, restart, out, out2), "tstar_jpeg_encode_plan_rst")
-            self.markers = int(out2[1])
-        else:
-            _lib.check(_lib.load().tstar_jpeg_encode_plan(W, H, hs, vs, n, slot_bytes, out), "tstar_jpeg_encode_plan")
+        out, out2 = (C.c_size_t * 8)(), (C.c_size_t * 2)()
+        _lib.check(_lib.load().tstar_jpeg_encode_plan_rst(W, H, hs, vs, n, slot_bytes, restart, out, out2), "tstar_jpeg_encode_plan_rst")
+        self.restart, self.markers = int(restart), int(out2[1])
         for k, v in zip(self.FIELDS, out):
             setattr(self, k, int(v))
 
@@ -106,12 +101,8 @@ def header(W: int, H: int, quality: int = 75, subsampling="4:2:0", restart_rows=
     restart = restart_interval(W, H, subsampling, restart_rows, restart_blocks)
     buf = np.empty(1024, dtype=np.uint8)
     n = C.c_size_t(0)
-    if restart:
-        _lib.check(_lib.load().tstar_jpeg_encode_header_rst(W, H, _quality(quality), hs, vs, restart, buf.ctypes.data, buf.size, C.byref(n)),
-                   "tstar_jpeg_encode_header_rst")
-    else:
-        _lib.check(_lib.load().tstar_jpeg_encode_header(W, H, _quality(quality), hs, vs, buf.ctypes.data, buf.size, C.byref(n)),
-                   "tstar_jpeg_encode_header")
+    _lib.check(_lib.load().tstar_jpeg_encode_header_rst(W, H, _quality(quality), hs, vs, restart, buf.ctypes.data, buf.size, C.byref(n)),
+               "tstar_jpeg_encode_header_rst")
     return buf[:n.value].tobytes()
 
 
@@ -175,14 +166,10 @@ def scan_host(coef: np.ndarray, W: int, H: int, subsampling="4:2:0", slot_bytes:
     out = np.empty((n, slot), dtype=np.uint8)
     lengths = np.zeros(n, dtype=np.uint32)
     status = np.full(n, -1, dtype=np.int32)
-    if restart or restart_counters is not None:
-        _lib.check(_lib.load().tstar_jpeg_encode_scan_host_rst(coef.ctypes.data, n, W, H, hs, vs, restart, out.ctypes.data, slot,
-                                                               lengths.ctypes.data, status.ctypes.data, threads, _counter_ptr(counters),
-                                                               _counter_ptr(restart_counters, RESTART_COUNTERS)),
-                   "tstar_jpeg_encode_scan_host_rst")
-    else:
-        _lib.check(_lib.load().tstar_jpeg_encode_scan_host(coef.ctypes.data, n, W, H, hs, vs, out.ctypes.data, slot, lengths.ctypes.data,
-                                                           status.ctypes.data, threads, _counter_ptr(counters)), "tstar_jpeg_encode_scan_host")
+    _lib.check(_lib.load().tstar_jpeg_encode_scan_host_rst(coef.ctypes.data, n, W, H, hs, vs, restart, out.ctypes.data, slot,
+                                                           lengths.ctypes.data, status.ctypes.data, threads, _counter_ptr(counters),
+                                                           _counter_ptr(restart_counters, RESTART_COUNTERS)),
+               "tstar_jpeg_encode_scan_host_rst")
     return [out[i, :lengths[i]].tobytes() if status[i] == 0 else None for i in range(n)], lengths, status
 
 
@@ -212,15 +199,10 @@ def encode_host(frames, quality: int = 75, subsampling="4:2:0", idx: Optional[Se
     assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size >= n * slot
     lengths = np.zeros(n, dtype=np.uint32)
     status = np.full(n, -1, dtype=np.int32)
-    if restart or restart_counters is not None:
-        _lib.check(_lib.load().tstar_jpeg_encode_host_rst(a.ctypes.data, N, H, W, ii.ctypes.data, n, _quality(quality), hs, vs, restart,
-                                                          out.ctypes.data, slot, lengths.ctypes.data, status.ctypes.data, threads,
-                                                          _counter_ptr(counters), _counter_ptr(restart_counters, RESTART_COUNTERS)),
-                   "tstar_jpeg_encode_host_rst")
-    else:
-        _lib.check(_lib.load().tstar_jpeg_encode_host(a.ctypes.data, N, H, W, ii.ctypes.data, n, _quality(quality), hs, vs, out.ctypes.data,
-                                                      slot, lengths.ctypes.data, status.ctypes.data, threads, _counter_ptr(counters)),
-                   "tstar_jpeg_encode_host")
+    _lib.check(_lib.load().tstar_jpeg_encode_host_rst(a.ctypes.data, N, H, W, ii.ctypes.data, n, _quality(quality), hs, vs, restart,
+                                                      out.ctypes.data, slot, lengths.ctypes.data, status.ctypes.data, threads,
+                                                      _counter_ptr(counters), _counter_ptr(restart_counters, RESTART_COUNTERS)),
+               "tstar_jpeg_encode_host_rst")
     return out, lengths, status
 
 
@@ -270,15 +252,10 @@ class DeviceEncoder:
                                                 self.coef.data_ptr(), None, s), "tstar_jpeg_encode_blocks")
         if ev:
             ev[1].record()
-        if self.restart:
-            _lib.check(lib.tstar_jpeg_encode_scan_rst(self.coef.data_ptr(), n, self.W, self.H, self.hs, self.vs, self.restart,
-                                                      self.out.data_ptr(), self.slot, self.meta[0].data_ptr(), self.meta[1].data_ptr(),
-                                                      self.work.data_ptr(), self.work.numel(), self.rst.data_ptr(), s),
-                       "tstar_jpeg_encode_scan_rst")
-        else:
-            _lib.check(lib.tstar_jpeg_encode_scan(self.coef.data_ptr(), n, self.W, self.H, self.hs, self.vs, self.out.data_ptr(), self.slot,
-                                                  self.meta[0].data_ptr(), self.meta[1].data_ptr(), self.work.data_ptr(), self.work.numel(), s),
-                       "tstar_jpeg_encode_scan")
+        _lib.check(lib.tstar_jpeg_encode_scan_rst(self.coef.data_ptr(), n, self.W, self.H, self.hs, self.vs, self.restart,
+                                                  self.out.data_ptr(), self.slot, self.meta[0].data_ptr(), self.meta[1].data_ptr(),
+                                                  self.work.data_ptr(), self.work.numel(), _lib.ptr(self.rst), s),
+                   "tstar_jpeg_encode_scan_rst")
         if ev:
             ev[2].record()
             ev[2].synchronize()
