@@ -74,6 +74,9 @@ def main():
     ap.add_argument("--save-mjpeg", default=None, metavar="DIR",
                     help="write each opened video once as DIR/<name>.avi (Motion-JPEG, quality 90, 1 frame per second), skipped when the "
                          "file is there: a later run passes those files as --videos and opens them through the device decode path")
+    ap.add_argument("--jpeg-optimize", action="store_true",
+                    help="write the JPEGs of --keyframe-jpegs and --save-mjpeg with Huffman tables built from each frame's own statistics "
+                         "(Pillow's optimize=True, byte for byte): smaller files, the same pixels")
     args = ap.parse_args()
 
     import torch
@@ -126,7 +129,7 @@ def main():
                 os.makedirs(args.save_mjpeg, exist_ok=True)
                 out = os.path.join(args.save_mjpeg, re.sub(r"[^A-Za-z0-9._-]+", "_", os.path.splitext(os.path.basename(p.rstrip("/")))[0] or "video") + ".avi")
                 if not os.path.exists(out):
-                    stores[p].save_mjpeg(out, quality=90)
+                    stores[p].save_mjpeg(out, quality=90, optimize=args.jpeg_optimize)
         return stores[p]
 
     owl_kw = {}
@@ -175,7 +178,7 @@ def main():
                 if args.keyframe_jpegs:
                     d = os.path.join(args.keyframe_jpegs, f"{i:05d}")
                     os.makedirs(d, exist_ok=True)
-                    for t, data in zip(rows[-1], video_of(i).jpeg_frames(rows[-1])):
+                    for t, data in zip(rows[-1], video_of(i).jpeg_frames(rows[-1], optimize=args.jpeg_optimize)):
                         with open(os.path.join(d, f"{t}.jpg"), "wb") as f:
                             f.write(data)
                 dists[i] = s.P_history[-1] if s.P_history else []

@@ -560,6 +560,46 @@ int tstar_jpeg_encode_scan_rst(const int16_t* d_coef, int n, int W, int H, int h
 int tstar_jpeg_encode_rst(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
                           int restart, int16_t* d_coef, uint8_t* d_out, size_t slot_bytes, uint32_t* d_lengths, int32_t* d_status,
                           void* d_workspace, size_t workspace_bytes, uint32_t* d_rst_counters, void* stream);
+/* ---- The same encoder with OPTIMISED HUFFMAN TABLES: what Pillow writes with optimize=True (libjpeg's optimize_coding), with or
+ * without a restart interval.  Every frame is coded with four tables built from its own symbol counts (jchuff.c: the counts of
+ * encode_mcu_gather, the tables of jpeg_gen_optimal_table), so the header differs from frame to frame in content and in length:
+ * its four DHT segments (DC 0, AC 0, DC 1, AC 1, a segment each, all four always) carry the frame's tables.  A table travels as a
+ * SPEC of 276 bytes: bits u8 [16] (codes of length 1..16), vals u8 [256] (the first nvals are the symbols), nvals u16, status u16
+ * (0 ok; 1 a code longer than 32 bits before limiting, libjpeg's JERR_HUFF_CLEN_OVERFLOW; 2 no symbol).  Per-frame status 3: one of
+ * the frame's tables overflowed; nothing of the frame is written and its length is 0.  A block is bounded by 1665 bits (a DC code
+ * may be 16 bits long), which the plan's sizes hold.  The entries above are untouched: the same bytes from the same launches. */
+/* optimize 0 / 1.  out8, out2 as tstar_jpeg_encode_plan_rst (optimize = 1: the larger bound, the longest header 1299 / 1305, the
+ * workspace grown by the counts and the code tables); out3 (optional) = {optimize, byte offset in the workspace of the counts
+ * u32 [n][4][257] (tables in DHT order; [256] stays 0), byte offset of the code tables [n][4] {u16 code [256], u8 len [256]}}: both
+ * hold the last call's values when tstar_jpeg_encode_scan_opt returns. */
+int tstar_jpeg_encode_plan_opt(int W, int H, int hs, int vs, int n, size_t slot_bytes, int restart, int optimize, size_t* out8, size_t* out2,
+                               size_t* out3);
+/* The table procedure alone, pure: freq u32 [256] (sum at most 1000000000) -> spec (276 bytes, above), code u16 [256] and len u8 [256]
+ * (optional: the canonical codes; len 0 = no code), steps (optional: how often the limiting to 16 bits ran). */
+int tstar_jpeg_huff_optimal(const uint32_t* freq, uint8_t* spec, uint16_t* code, uint8_t* len, int32_t* steps);
+/* The header of one frame from its four specs (4 x 276 bytes, each with status 0) -> out, *len (at most 1299, 1305 with DRI). */
+int tstar_jpeg_encode_header_opt(int W, int H, int quality, int hs, int vs, int restart, const uint8_t* specs, uint8_t* out, size_t cap,
+                                 size_t* len);
+/* Scan stage on the host with optimised tables: as tstar_jpeg_encode_scan_host_rst; specs u8 [n][4][276] out; hist (optional) u32
+ * [n][4][257] out, the counts. */
+int tstar_jpeg_encode_scan_host_opt(const int16_t* coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* out, size_t slot_bytes,
+                                    uint32_t* lengths, int32_t* status, uint8_t* specs, uint32_t* hist, int threads, uint64_t* counters,
+                                    uint64_t* rst_counters);
+/* Whole files on the host with optimised tables (each frame's own header + scan), as tstar_jpeg_encode_host_rst. */
+int tstar_jpeg_encode_host_opt(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
+                               int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status, int threads,
+                               uint64_t* counters, uint64_t* rst_counters);
+/* Scan stage on the device with optimised tables: counts -> tables -> the launches of tstar_jpeg_encode_scan_rst coding with the
+ * frame's tables; nothing is read back in between.  d_specs: device u8 [n][4][276] out; d_workspace: the bytes
+ * tstar_jpeg_encode_plan_opt names with optimize = 1. */
+int tstar_jpeg_encode_scan_opt(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* d_out, size_t slot_bytes,
+                               uint32_t* d_lengths, int32_t* d_status, uint8_t* d_specs, void* d_workspace, size_t workspace_bytes,
+                               uint32_t* d_rst_counters, void* stream);
+/* The two stages in front of that scan alone, for tests and measurements: stages 1 the counts (zeroed, then gathered), 2 the tables
+ * from the counts as they lie in the workspace (so a caller may put counts of its own there), 3 both.  slot_bytes: the value the
+ * workspace was planned with (it places the counts and the code tables). */
+int tstar_jpeg_encode_tables(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, size_t slot_bytes, int stages,
+                             uint8_t* d_specs, void* d_workspace, size_t workspace_bytes, void* stream);
 /* Entropy stage on the device.  The unit of parallel work is a SEGMENT: a run of MCUs that starts at a byte boundary with
  * zero DC predictors (one restart interval; a frame without DRI is one segment).  The planner below cuts frames into
  * segments on the host, the kernel decodes one segment per lane into the coefficient layout above, and

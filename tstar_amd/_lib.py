@@ -100,6 +100,13 @@ SIGNATURES = {
     "tstar_jpeg_encode_host_rst": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp]),
     "tstar_jpeg_encode_scan_rst": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp]),
     "tstar_jpeg_encode_rst": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tstar_jpeg_encode_plan_opt": (_i, [_i, _i, _i, _i, _i, _sz, _i, _i, _vp, _vp, _vp]),
+    "tstar_jpeg_huff_optimal": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tstar_jpeg_encode_header_opt": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "tstar_jpeg_encode_scan_host_opt": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "tstar_jpeg_encode_host_opt": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp]),
+    "tstar_jpeg_encode_scan_opt": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "tstar_jpeg_encode_tables": (_i, [_vp, _i, _i, _i, _i, _i, _i, _sz, _i, _vp, _vp, _sz, _vp]),
     "tstar_jpeg_plan_segments": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "tstar_jpeg_entropy_device": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "tstar_jpeg_entropy_segments_host": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -27,6 +27,16 @@
 // [R]: only with a restart interval (jpeg_enc_math.h, "scan order").  The interval is an argument of the one scan launcher; the
 // kernels of the entropy stage and the stuffing passes take it as the compile-time parameter RST, so a scan without markers runs
 // none of the [R] steps and its kernels get no RestartArgs at all (RestartOf<false> is empty: there is nothing they could read).
+//
+// With optimised tables (Pillow's optimize=True; jpeg_enc_math.h, "optimised tables") two stages run in front of the entropy stage
+// and the two bits passes code with the frame's own tables; nothing is read back in between, and a scan with the standard tables
+// launches none of this:
+//   tables         jpeg_enc_hist_kernel      the symbols of the block walk counted into the frame's four histograms [4][257]
+//                  jpeg_enc_tables_kernel    one wave per (frame, table): histogram -> HuffSpecWide (what the DHT segment needs) and
+//                                            HuffCodes (what the bits kernel needs), or a status
+//   entropy stage  jpeg_enc_bits_opt_kernel  the lane body of jpeg_enc_bits_kernel behind a staging of the frame's four code tables
+//                                            into LDS
+//   status         jpeg_enc_opt_status_kernel  a frame with a table that has a status (never written) reports JPEG_ENC_HUFF_OVERFLOW
 #include <type_traits>
 
 #include "../../include/tstar_hip.h"
@@ -256,8 +266,9 @@ using RestartOf = std::conditional_t<RST, RestartArgs, NoRestart>;
 // previous block of the component, a lookup in the coefficients.  RST, WRITE: block k of interval s starts at seg[s] + bits[k] -
 // bits[first block of s]; the lane of the last block of an interval that a marker follows appends up to 7 one-bits and the
 // marker's 16.
+// codes: the four code tables of the frame (the Annex K ones in constant memory, or the frame's own, staged in LDS)
 template <int WRITE, bool RST>
-__global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(EntropyArgs a, RestartOf<RST> r) {
+__device__ __forceinline__ void bits_lane(const EntropyArgs& a, const RestartOf<RST>& r, const jpegenc::HuffCodes* codes) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
     if (k >= a.blocks) return;
     uint32_t* meta = a.meta + (size_t)f * 4;
@@ -268,8 +279,8 @@ __global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(EntropyArgs a, Resta
     jpegenc::scan_block(a.sg, k, interval, &c, &b, &pb);
     const int16_t* fc = a.coef + (size_t)f * a.blocks * 64;
     const int pred = pb < 0 ? 0 : fc[(size_t)pb * 64];
-    const jpegenc::HuffCodes& dc = kDevTables.codes[c ? 2 : 0];
-    const jpegenc::HuffCodes& ac = kDevTables.codes[c ? 3 : 1];
+    const jpegenc::HuffCodes& dc = codes[c ? 2 : 0];
+    const jpegenc::HuffCodes& ac = codes[c ? 3 : 1];
     if (WRITE) {
         const uint32_t* bits = a.bits + (size_t)f * a.blocks;
         [[maybe_unused]] uint32_t s = 0, first = 0;
@@ -294,6 +305,193 @@ __global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(EntropyArgs a, Resta
         const jpegenc::BlockEvents ev = jpegenc::encode_block(fc + (size_t)b * 64, pred, dc, ac, kDevZigzag, put);
         a.bits[(size_t)f * a.blocks + k] = put.n;
         if (ev.bad) atomicOr(meta + META_FLAGS, (uint32_t)FLAG_BAD_COEF);
+    }
+}
+
+template <int WRITE, bool RST>
+__global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(EntropyArgs a, RestartOf<RST> r) {
+    bits_lane<WRITE, RST>(a, r, kDevTables.codes);
+}
+
+// ------------------------------------------------------------------------------------------------ optimised tables
+// blocks -> histogram -> tables -> bits (count) -> offsets -> bits (write) -> stuffing; nothing is read back in between.
+constexpr int kHist = jpegenc::kHuffSymbols;           // 257 bins per table
+constexpr uint32_t kTableWords = 4 * sizeof(jpegenc::HuffCodes) / 4;       // 768 dwords: a frame's four code tables
+
+// The bits kernel coding with the frame's own tables: the workgroup stages them in LDS (4 x 768 bytes) once.
+template <int WRITE, bool RST>
+__global__ __launch_bounds__(256) void jpeg_enc_bits_opt_kernel(EntropyArgs a, RestartOf<RST> r, const jpegenc::HuffCodes* __restrict__ codes) {
+    __shared__ alignas(16) jpegenc::HuffCodes tab[4];
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(codes + (size_t)blockIdx.y * 4);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(tab);
+    for (uint32_t i = threadIdx.x; i < kTableWords; i += 256) dst[i] = src[i];
+    __syncthreads();
+    bits_lane<WRITE, RST>(a, r, tab);
+}
+
+// grid (ceil(blocks / 1024), n): a workgroup walks 1024 consecutive blocks of one frame's scan, four per lane, and counts their
+// symbols into histograms in LDS; the bins that are not zero are then added to the frame's (zeroed) hist [4][257].  Neighbouring
+// lanes meet on the same few bins (EOB, the small DC categories) at the same instruction, and LDS atomics on one address take
+// turns: the workgroup keeps kHistCopies copies of the four histograms, lane l counts into copy l mod kHistCopies (their bins lie
+// in different banks: a copy is 1028 dwords), and the flush sums them.
+constexpr int kHistCopies = 8;
+constexpr int kHistBlocksPerWg = 1024;
+__global__ __launch_bounds__(256) void jpeg_enc_hist_kernel(EntropyArgs a, int interval, uint32_t* __restrict__ hist) {
+    __shared__ uint32_t h[kHistCopies * 4 * kHist];
+    const int f = blockIdx.y;
+    for (int i = threadIdx.x; i < kHistCopies * 4 * kHist; i += 256) h[i] = 0;
+    __syncthreads();
+    const int16_t* fc = a.coef + (size_t)f * a.blocks * 64;
+    uint32_t* copy = h + (threadIdx.x % kHistCopies) * 4 * kHist;
+    for (int j = 0; j < kHistBlocksPerWg / 256; ++j) {
+        const int k = blockIdx.x * kHistBlocksPerWg + j * 256 + (int)threadIdx.x;
+        if (k >= a.blocks) break;
+        int c, b, pb;
+        jpegenc::scan_block(a.sg, k, interval, &c, &b, &pb);
+        const int pred = pb < 0 ? 0 : fc[(size_t)pb * 64];
+        uint32_t* mine = copy + (c ? 2 : 0) * kHist;
+        jpegenc::gather_block(fc + (size_t)b * 64, pred, kDevZigzag, [&](int ac, int sym) { atomicAdd(mine + ac * kHist + sym, 1u); });
+    }
+    __syncthreads();
+    uint32_t* fh = hist + (size_t)f * 4 * kHist;
+    for (int i = threadIdx.x; i < 4 * kHist; i += 256) {
+        uint32_t sum = 0;
+#pragma unroll
+        for (int r = 0; r < kHistCopies; ++r) sum += h[r * 4 * kHist + i];
+        if (sum) atomicAdd(fh + i, sum);
+    }
+}
+
+// smallest key of the wave (64 lanes), in every lane
+__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)v, d, 64), hi = __shfl_xor((uint32_t)(v >> 32), d, 64);
+        const uint64_t o = ((uint64_t)hi << 32) | lo;
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
+// grid (4, n), one wave: table t of frame f from its histogram (jpegenc::huff_optimal's result, found in parallel).
+//   merges  lane l holds the counts of symbols l, l + 64, ... (five registers; 256 is the reserved symbol, count 1).  The two
+//           smallest of a merge are wave minima of the key count << 9 | 511 - index (ties go to the LARGEST index, as libjpeg's
+//           upward scan with <= leaves them); every lane learns both and updates its own registers, lane 0 records the merge
+//           as a node with two parent links.
+//   depths  one leaf per lane walks its links to the root: the code size.  A size above 32 is the overflow status.
+//   table   lane 0 counts and limits the lengths (32 steps); every lane ranks its symbols for huffval (size, then value);
+//           lane 0 assigns the canonical codes.  Spec and codes leave LDS as dwords.
+__global__ __launch_bounds__(64) void jpeg_enc_tables_kernel(const uint32_t* __restrict__ hist, jpegenc::HuffSpecWide* __restrict__ specs,
+                                                             jpegenc::HuffCodes* __restrict__ codes, uint32_t* __restrict__ meta) {
+    __shared__ uint16_t node[kHist], parent[2 * kHist];
+    __shared__ uint8_t size[kHist + 3];
+    __shared__ int bits[jpegenc::kHuffMaxClen + 1];
+    __shared__ alignas(16) jpegenc::HuffSpecWide spec;
+    __shared__ alignas(16) jpegenc::HuffCodes tab;
+    const int lane = threadIdx.x, t = blockIdx.x, f = blockIdx.y;
+    const uint32_t* fh = hist + ((size_t)f * 4 + t) * kHist;
+    uint32_t cnt[5];
+    uint32_t present = 0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int i = lane + 64 * j;
+        cnt[j] = i < 256 ? fh[i] : (i == 256 ? 1u : 0u);
+        if (cnt[j]) present |= 1u << j;
+        if (i < kHist) node[i] = (uint16_t)i;
+    }
+    for (int i = lane; i < 2 * kHist; i += 64) parent[i] = 0xFFFF;
+    for (int i = lane; i < (int)(sizeof(spec) / 4); i += 64) reinterpret_cast<uint32_t*>(&spec)[i] = 0;
+    for (int i = lane; i < (int)(sizeof(tab) / 4); i += 64) reinterpret_cast<uint32_t*>(&tab)[i] = 0;
+    if (lane <= jpegenc::kHuffMaxClen) bits[lane] = 0;
+    __syncthreads();
+    constexpr uint64_t kNone = ~0ull;
+    for (int next = kHist;; ++next) {
+        uint64_t k1 = kNone;
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+            if (cnt[j]) {
+                const uint64_t key = ((uint64_t)cnt[j] << 9) | (uint64_t)(511 - (lane + 64 * j));
+                k1 = key < k1 ? key : k1;
+            }
+        k1 = wave_min_u64(k1);
+        const int c1 = 511 - (int)(k1 & 511u);
+        uint64_t k2 = kNone;
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+            if (cnt[j] && lane + 64 * j != c1) {
+                const uint64_t key = ((uint64_t)cnt[j] << 9) | (uint64_t)(511 - (lane + 64 * j));
+                k2 = key < k2 ? key : k2;
+            }
+        k2 = wave_min_u64(k2);
+        if (k2 == kNone) break;                        // one tree is left (wave-uniform)
+        const int c2 = 511 - (int)(k2 & 511u);
+        const uint32_t sum = (uint32_t)(k1 >> 9) + (uint32_t)(k2 >> 9);
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            if (lane + 64 * j == c1) cnt[j] = sum;
+            if (lane + 64 * j == c2) cnt[j] = 0;
+        }
+        if (lane == 0) {                               // at most 256 merges: next stays below 2 * 257
+            parent[node[c1]] = (uint16_t)next;
+            parent[node[c2]] = (uint16_t)next;
+            node[c1] = (uint16_t)next;
+        }
+    }
+    __syncthreads();
+    int deepest = 0, symbols = 0;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        const int i = lane + 64 * j;
+        int d = 0;
+        if (present & (1u << j))
+            for (int p = i; parent[p] != 0xFFFF; p = parent[p]) ++d;
+        if (i < kHist) size[i] = (uint8_t)d;           // at most 256
+        deepest = d > deepest ? d : deepest;
+        symbols += i < 256 && (present & (1u << j));
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int o = __shfl_xor(deepest, d, 64);
+        deepest = o > deepest ? o : deepest;
+        symbols += __shfl_xor(symbols, d, 64);
+    }
+    __syncthreads();
+    const int status = symbols == 0 ? jpegenc::HUFF_EMPTY : (deepest > jpegenc::kHuffMaxClen ? jpegenc::HUFF_CLEN_OVERFLOW : jpegenc::HUFF_OK);
+    if (status == jpegenc::HUFF_OK) {                  // wave-uniform
+        if (lane == 0) {
+            for (int i = 0; i < kHist; ++i)
+                if (size[i]) ++bits[size[i]];
+            jpegenc::huff_limit_bits(bits, nullptr);
+            for (int i = 0; i < 16; ++i) spec.bits[i] = (uint8_t)bits[i + 1];
+            spec.nvals = (uint16_t)symbols;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = lane + 64 * j;
+            if (present & (1u << j)) spec.vals[jpegenc::huff_rank(size, i)] = (uint8_t)i;
+        }
+        __syncthreads();
+        if (lane == 0) jpegenc::huff_assign_codes(spec, tab);
+    } else if (lane == 0) {
+        spec.status = (uint16_t)status;
+        atomicOr(meta + (size_t)f * 4 + META_FLAGS, (uint32_t)FLAG_SKIP);          // the frame is never written
+    }
+    __syncthreads();
+    uint32_t* so = reinterpret_cast<uint32_t*>(specs + (size_t)f * 4 + t);
+    uint32_t* co = reinterpret_cast<uint32_t*>(codes + (size_t)f * 4 + t);
+    for (int i = lane; i < (int)(sizeof(spec) / 4); i += 64) so[i] = reinterpret_cast<const uint32_t*>(&spec)[i];
+    for (int i = lane; i < (int)(sizeof(tab) / 4); i += 64) co[i] = reinterpret_cast<const uint32_t*>(&tab)[i];
+}
+
+// one lane per frame, behind the stuffing passes: a frame with a table that has a status reports it, with length 0
+__global__ __launch_bounds__(256) void jpeg_enc_opt_status_kernel(const jpegenc::HuffSpecWide* __restrict__ specs, uint32_t* lengths, int32_t* status, int n) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    bool bad = false;
+    for (int t = 0; t < 4; ++t) bad |= specs[(size_t)f * 4 + t].status != jpegenc::HUFF_OK;
+    if (bad && status[f] != JPEG_ENC_BAD_COEF) {
+        lengths[f] = 0;
+        status[f] = JPEG_ENC_HUFF_OVERFLOW;
     }
 }
 
@@ -536,15 +734,19 @@ int jpeg_encode_blocks_u8(const uint8_t* frames, int N, int H, int W, const int3
 
 namespace {
 
-// the six launches of the scan stage, with (RST) or without the interval-only steps
+// the six launches of the scan stage, with (RST) or without the interval-only steps; codes: the frames' own code tables
+// [n][4] (optimised tables), or null for the Annex K ones
 template <bool RST>
-int launch_scan(const JpegEncPlan& p, int n, const EntropyArgs& e, const StuffArgs& a, const RestartOf<RST>& r, hipStream_t s) {
+int launch_scan(const JpegEncPlan& p, int n, const EntropyArgs& e, const StuffArgs& a, const RestartOf<RST>& r, const jpegenc::HuffCodes* codes,
+                hipStream_t s) {
     const dim3 egrid(p.entropy_wgs_x, (unsigned)n), sgrid(p.stuff_wgs_x, (unsigned)n);
-    hipLaunchKernelGGL((jpeg_enc_bits_kernel<0, RST>), egrid, dim3(256), 0, s, e, r);
+    if (codes) hipLaunchKernelGGL((jpeg_enc_bits_opt_kernel<0, RST>), egrid, dim3(256), 0, s, e, r, codes);
+    else hipLaunchKernelGGL((jpeg_enc_bits_kernel<0, RST>), egrid, dim3(256), 0, s, e, r);
     TSTAR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(jpeg_enc_offsets_kernel<RST>, dim3((unsigned)n), dim3(256), 0, s, e.bits, e.meta, e.blocks, a.slot_bytes, r);
     TSTAR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL((jpeg_enc_bits_kernel<1, RST>), egrid, dim3(256), 0, s, e, r);
+    if (codes) hipLaunchKernelGGL((jpeg_enc_bits_opt_kernel<1, RST>), egrid, dim3(256), 0, s, e, r, codes);
+    else hipLaunchKernelGGL((jpeg_enc_bits_kernel<1, RST>), egrid, dim3(256), 0, s, e, r);
     TSTAR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((jpeg_enc_ff_kernel<0, RST>), sgrid, dim3(256), 0, s, a, r);
     TSTAR_HIP_CHECK(hipGetLastError());
@@ -557,10 +759,32 @@ int launch_scan(const JpegEncPlan& p, int n, const EntropyArgs& e, const StuffAr
 
 }  // namespace
 
-// the scan stage with a restart interval of `restart` MCUs (0: none).  d_rst_counters: optional u32 [n][3], zeroed here
+namespace {
+// the two stages in front of an optimised scan: 1 counts (into the zeroed histograms), 2 tables (from the histograms as they are)
+int launch_tables(const JpegEncPlan& p, int n, const EntropyArgs& e, int restart, jpegenc::HuffSpecWide* specs, uint8_t* ws, int stages,
+                  hipStream_t s) {
+    TSTAR_REQUIRE((uintptr_t)specs % 4 == 0, "jpeg encode: the specs need 4-byte alignment");
+    uint32_t* hist = (uint32_t*)(ws + p.off_hist);
+    if (stages & 1) {
+        TSTAR_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)n * 4 * kHist * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(jpeg_enc_hist_kernel, dim3((unsigned)((p.blocks + kHistBlocksPerWg - 1) / kHistBlocksPerWg), (unsigned)n), dim3(256), 0, s, e,
+                           restart, hist);
+        TSTAR_HIP_CHECK(hipGetLastError());
+    }
+    if (stages & 2) {
+        hipLaunchKernelGGL(jpeg_enc_tables_kernel, dim3(4, (unsigned)n), dim3(64), 0, s, hist, specs, (jpegenc::HuffCodes*)(ws + p.off_codes), e.meta);
+        TSTAR_HIP_CHECK(hipGetLastError());
+    }
+    return TSTAR_OK;
+}
+}  // namespace
+
+// the scan stage with a restart interval of `restart` MCUs (0: none).  d_rst_counters: optional u32 [n][3], zeroed here.
+// specs: null codes with the Annex K tables; else device HuffSpecWide [n][4] out, and every frame is coded with tables of its own
 int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths,
-                        int32_t* status, void* workspace, size_t workspace_bytes, uint32_t* d_rst_counters, hipStream_t s) {
-    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart);
+                        int32_t* status, void* workspace, size_t workspace_bytes, uint32_t* d_rst_counters, hipStream_t s,
+                        jpegenc::HuffSpecWide* specs = nullptr) {
+    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart, specs ? 1 : 0);
     TSTAR_REQUIRE(!p.error, std::string("jpeg_encode_scan_u8: ") + (p.error ? p.error : ""));
     TSTAR_REQUIRE((uintptr_t)workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
                   "jpeg_encode_scan_u8: the workspace is misaligned or smaller than the plan's workspace_bytes");
@@ -582,15 +806,28 @@ int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, int resta
     TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), s));
     TSTAR_HIP_CHECK(hipMemsetAsync(e.raw, 0, (size_t)n * p.raw_words * sizeof(uint32_t), s));
     if (d_rst_counters) TSTAR_HIP_CHECK(hipMemsetAsync(d_rst_counters, 0, (size_t)n * JPEG_ENC_R_COUNTERS * sizeof(uint32_t), s));
-    if (restart == 0) return launch_scan<false>(p, n, e, a, NoRestart{}, s);
-    RestartArgs r;
-    r.seg = (uint32_t*)(ws + p.off_seg);
-    r.mark = (uint32_t*)(ws + p.off_mark);
-    r.counters = d_rst_counters;
-    r.interval = restart;
-    r.seg_blocks = restart * e.sg.per_mcu();           // at most 65535 * 6; at least the frame's blocks when there is no marker
-    r.markers = (uint32_t)p.markers;
-    return launch_scan<true>(p, n, e, a, r, s);
+    jpegenc::HuffCodes* codes = nullptr;
+    if (specs) {
+        codes = (jpegenc::HuffCodes*)(ws + p.off_codes);
+        RC(launch_tables(p, n, e, restart, specs, ws, 3, s));
+    }
+    int rc;
+    if (restart == 0) {
+        rc = launch_scan<false>(p, n, e, a, NoRestart{}, codes, s);
+    } else {
+        RestartArgs r;
+        r.seg = (uint32_t*)(ws + p.off_seg);
+        r.mark = (uint32_t*)(ws + p.off_mark);
+        r.counters = d_rst_counters;
+        r.interval = restart;
+        r.seg_blocks = restart * e.sg.per_mcu();       // at most 65535 * 6; at least the frame's blocks when there is no marker
+        r.markers = (uint32_t)p.markers;
+        rc = launch_scan<true>(p, n, e, a, r, codes, s);
+    }
+    if (rc != TSTAR_OK || !specs) return rc;
+    hipLaunchKernelGGL(jpeg_enc_opt_status_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, lengths, status, n);
+    TSTAR_HIP_CHECK(hipGetLastError());
+    return TSTAR_OK;
 }
 
 }  // namespace tstar
@@ -630,6 +867,31 @@ int tstar_jpeg_encode_scan_rst(const int16_t* d_coef, int n, int W, int H, int h
     TSTAR_REQUIRE(d_coef && d_out && d_lengths && d_status && d_workspace, "tstar_jpeg_encode_scan_rst: null argument");
     return jpeg_encode_scan_u8(d_coef, n, JpegGeom{W, H, 3, hs, vs}, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace,
                                workspace_bytes, d_rst_counters, (hipStream_t)stream);
+}
+
+int tstar_jpeg_encode_scan_opt(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* d_out, size_t slot_bytes,
+                               uint32_t* d_lengths, int32_t* d_status, uint8_t* d_specs, void* d_workspace, size_t workspace_bytes,
+                               uint32_t* d_rst_counters, void* stream) {
+    TSTAR_REQUIRE(d_coef && d_out && d_lengths && d_status && d_specs && d_workspace, "tstar_jpeg_encode_scan_opt: null argument");
+    return jpeg_encode_scan_u8(d_coef, n, JpegGeom{W, H, 3, hs, vs}, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace,
+                               workspace_bytes, d_rst_counters, (hipStream_t)stream, (jpegenc::HuffSpecWide*)d_specs);
+}
+
+int tstar_jpeg_encode_tables(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, size_t slot_bytes, int stages,
+                             uint8_t* d_specs, void* d_workspace, size_t workspace_bytes, void* stream) {
+    TSTAR_REQUIRE(d_coef && d_specs && d_workspace && stages >= 1 && stages <= 3, "tstar_jpeg_encode_tables: null argument or stages outside 1..3");
+    const JpegGeom g{W, H, 3, hs, vs};
+    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart, 1);
+    TSTAR_REQUIRE(!p.error, std::string("tstar_jpeg_encode_tables: ") + (p.error ? p.error : ""));
+    TSTAR_REQUIRE((uintptr_t)d_workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
+                  "tstar_jpeg_encode_tables: the workspace is misaligned or smaller than the plan's workspace_bytes");
+    EntropyArgs e = {};
+    e.coef = d_coef;
+    e.meta = (uint32_t*)((uint8_t*)d_workspace + p.off_meta);
+    e.sg = scan_geom(g);
+    e.blocks = (int)p.blocks;
+    TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), (hipStream_t)stream));
+    return launch_tables(p, n, e, restart, (jpegenc::HuffSpecWide*)d_specs, (uint8_t*)d_workspace, stages, (hipStream_t)stream);
 }
 
 int tstar_jpeg_encode_rst(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,

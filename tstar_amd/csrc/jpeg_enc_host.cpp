@@ -29,22 +29,27 @@ size_t jpeg_enc_restart_markers(const JpegGeom& g, int restart) {
     return restart > 0 ? ((size_t)g.mcux() * g.mcuy() - 1) / (size_t)restart : 0;
 }
 size_t jpeg_enc_max_scan_bytes(const JpegGeom& g, int restart) { return jpeg_enc_max_scan_bytes(g) + 4 * jpeg_enc_restart_markers(g, restart); }
+size_t jpeg_enc_max_scan_bytes(const JpegGeom& g, int restart, int optimize) {
+    if (!optimize) return jpeg_enc_max_scan_bytes(g, restart);
+    return 2 * ((g.blocks() * (size_t)jpegenc::kMaxBlockBitsOpt + 7) / 8) + 2 + 4 * jpeg_enc_restart_markers(g, restart);
+}
 
-JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes, int restart) {
+JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes, int restart, int optimize) {
     JpegEncPlan p = {};
+    const size_t block_bits = optimize ? (size_t)jpegenc::kMaxBlockBitsOpt : (size_t)jpegenc::kMaxBlockBits;
     if (!jpeg_enc_restart_ok(restart)) { p.error = "restart interval must be in 0..65535 MCUs (DRI holds 16 bits)"; return p; }
     if (!jpeg_enc_geom_ok(g)) { p.error = "unsupported geometry (3 components, sampling 2x2 / 2x1 / 1x1, sides 1..16384)"; return p; }
     if (n < 1 || n > 65535) { p.error = "n must be in 1..65535"; return p; }
     p.blocks = g.blocks();
     p.restart = restart;
     p.markers = jpeg_enc_restart_markers(g, restart);
-    if (p.blocks * (size_t)jpegenc::kMaxBlockBits + p.markers * (size_t)jpegenc::kRestartBits >= (1ull << 32)) { p.error = "frame too large: a scan's bit offsets would not fit 32 bits"; return p; }
+    if (p.blocks * block_bits + p.markers * (size_t)jpegenc::kRestartBits >= (1ull << 32)) { p.error = "frame too large: a scan's bit offsets would not fit 32 bits"; return p; }
     if (slot_bytes < 2 || slot_bytes >= (1ull << 31)) { p.error = "slot_bytes must be in 2..2^31-1"; return p; }
     p.coef_bytes = p.blocks * 128;
-    p.max_scan_bytes = jpeg_enc_max_scan_bytes(g, restart);
-    p.header_bytes = (size_t)jpeg_enc_header_bytes(restart);
+    p.max_scan_bytes = jpeg_enc_max_scan_bytes(g, restart, optimize);
+    p.header_bytes = (size_t)jpeg_enc_header_bytes(restart, optimize);
     // with markers the unstuffed stream holds them and the padding in front of them: 3 bytes more per marker at most
-    const size_t max_raw = (p.blocks * (size_t)jpegenc::kMaxBlockBits + 7) / 8 + 3 * p.markers;
+    const size_t max_raw = (p.blocks * block_bits + 7) / 8 + 3 * p.markers;
     const size_t raw_cap = slot_bytes < max_raw ? slot_bytes : max_raw;      // unstuffed bytes never exceed the stuffed ones
     p.raw_words = raw_cap / 4 + 1;
     p.ff_chunks = (p.raw_words * 4 + kJpegEncStuffChunk - 1) / kJpegEncStuffChunk;
@@ -58,6 +63,12 @@ JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes, int re
         p.off_seg = p.workspace_bytes;
         p.off_mark = p.off_seg + up((size_t)n * (p.markers + 1) * sizeof(uint32_t));
         p.workspace_bytes = p.off_mark + up((size_t)n * p.markers * sizeof(uint32_t));
+    }
+    if (optimize) {
+        p.optimize = 1;
+        p.off_hist = p.workspace_bytes;
+        p.off_codes = p.off_hist + up((size_t)n * 4 * jpegenc::kHuffSymbols * sizeof(uint32_t));
+        p.workspace_bytes = p.off_codes + up((size_t)n * 4 * sizeof(jpegenc::HuffCodes));
     }
     const size_t total_blocks = (size_t)n * p.blocks;
     if (total_blocks / 32 + 1 >= 0x7fffffffull) { p.error = "chunk too large for one launch"; return p; }
@@ -79,7 +90,9 @@ void jpeg_enc_header(const JpegGeom& g, int quality, int restart, uint8_t* out) 
     jpeg_enc_header_tables(g, quant, restart, out);
 }
 
-size_t jpeg_enc_header_tables(const JpegGeom& g, const uint16_t* quant, int restart, uint8_t* out) {
+namespace {
+// SOI .. SOS; specs: the four tables of the DHT segments (null: the Annex K tables)
+size_t write_header(const JpegGeom& g, const uint16_t* quant, int restart, const jpegenc::HuffSpecWide* specs, uint8_t* out) {
     uint8_t* p = out;
     auto put = [&](std::initializer_list<int> v) { for (int b : v) *p++ = (uint8_t)b; };
     const int n_tables = memcmp(quant + 64, quant + 128, 128) == 0 ? 2 : 3;       // Cb and Cr share table 1 when their rows are equal
@@ -103,15 +116,26 @@ size_t jpeg_enc_header_tables(const JpegGeom& g, const uint16_t* quant, int rest
          n_tables - 1});
     const int ids[4] = {0x00, 0x10, 0x01, 0x11};                // DC 0, AC 0, DC 1, AC 1
     for (int t = 0; t < 4; ++t) {
-        const jpegenc::HuffSpec& s = kTables.spec[t];
-        const int len = 2 + 1 + 16 + s.nvals;
+        const uint8_t* bits = specs ? specs[t].bits : kTables.spec[t].bits;
+        const uint8_t* vals = specs ? specs[t].vals : kTables.spec[t].vals;
+        const int nvals = specs ? (int)specs[t].nvals : kTables.spec[t].nvals;
+        const int len = 2 + 1 + 16 + nvals;
         put({0xFF, 0xC4, len >> 8, len & 255, ids[t]});
-        for (int i = 0; i < 16; ++i) *p++ = s.bits[i];
-        for (int i = 0; i < s.nvals; ++i) *p++ = s.vals[i];
+        for (int i = 0; i < 16; ++i) *p++ = bits[i];
+        for (int i = 0; i < nvals; ++i) *p++ = vals[i];
     }
     if (restart > 0) put({0xFF, 0xDD, 0, 4, restart >> 8, restart & 255});
     put({0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
     return (size_t)(p - out);
+}
+}  // namespace
+
+size_t jpeg_enc_header_tables(const JpegGeom& g, const uint16_t* quant, int restart, uint8_t* out) { return write_header(g, quant, restart, nullptr, out); }
+
+size_t jpeg_enc_header_opt(const JpegGeom& g, int quality, int restart, const jpegenc::HuffSpecWide* specs, uint8_t* out) {
+    uint16_t quant[192];
+    jpeg_enc_quant(quality, quant);
+    return write_header(g, quant, restart, specs, out);
 }
 
 void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2) {
@@ -192,7 +216,8 @@ struct ByteSink {                        // MSB-first bit writer with FF -> FF 0
 }  // namespace
 
 // the whole scan of one frame into sink.bytes; JPEG_ENC_OK or JPEG_ENC_BAD_COEF
-static int scan_frame(const int16_t* coef, const JpegGeom& g, int restart, ByteSink& sink, uint64_t* counters, uint64_t* rst_counters) {
+static int scan_frame(const int16_t* coef, const JpegGeom& g, int restart, ByteSink& sink, uint64_t* counters, uint64_t* rst_counters,
+                      const jpegenc::HuffCodes* codes = kTables.codes) {
     const jpegenc::ScanGeom sg = scan_geom(g);
     sink.bytes.reserve(g.blocks() * 16);
     uint64_t zrl = 0, no_eob = 0, rst = 0, pad_free = 0, pad_ff = 0;
@@ -208,8 +233,7 @@ static int scan_frame(const int16_t* coef, const JpegGeom& g, int restart, ByteS
         int c, b, pb;
         jpegenc::scan_block(sg, k, restart, &c, &b, &pb);
         const int pred = pb < 0 ? 0 : coef[(size_t)pb * 64];
-        const jpegenc::BlockEvents ev = jpegenc::encode_block(coef + (size_t)b * 64, pred, kTables.codes[c ? 2 : 0], kTables.codes[c ? 3 : 1],
-                                                              jpegenc::kStd.zigzag, sink);
+        const jpegenc::BlockEvents ev = jpegenc::encode_block(coef + (size_t)b * 64, pred, codes[c ? 2 : 0], codes[c ? 3 : 1], jpegenc::kStd.zigzag, sink);
         zrl += (uint64_t)ev.zrl;
         no_eob += (uint64_t)ev.no_eob;
         bad |= ev.bad;
@@ -233,6 +257,44 @@ int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* 
     ByteSink sink;
     *len = 0;
     if (scan_frame(coef, g, restart, sink, counters, rst_counters) != JPEG_ENC_OK) return JPEG_ENC_BAD_COEF;
+    *len = sink.bytes.size();
+    if (sink.bytes.size() > cap) return JPEG_ENC_SHORT;
+    memcpy(out, sink.bytes.data(), sink.bytes.size());
+    return JPEG_ENC_OK;
+}
+
+int jpeg_enc_gather(const int16_t* coef, const JpegGeom& g, int restart, uint32_t* hist) {
+    const jpegenc::ScanGeom sg = scan_geom(g);
+    memset(hist, 0, 4 * jpegenc::kHuffSymbols * sizeof(uint32_t));
+    int bad = 0;
+    for (int k = 0, nb = sg.blocks(); k < nb; ++k) {
+        int c, b, pb;
+        jpegenc::scan_block(sg, k, restart, &c, &b, &pb);
+        const int pred = pb < 0 ? 0 : coef[(size_t)pb * 64];
+        uint32_t* h = hist + (c ? 2 : 0) * jpegenc::kHuffSymbols;
+        bad |= jpegenc::gather_block(coef + (size_t)b * 64, pred, jpegenc::kStd.zigzag, [&](int ac, int sym) { ++h[ac * jpegenc::kHuffSymbols + sym]; }).bad;
+    }
+    return bad ? JPEG_ENC_BAD_COEF : JPEG_ENC_OK;
+}
+
+// gather and the four tables of one frame -> JPEG_ENC_OK, JPEG_ENC_BAD_COEF or JPEG_ENC_HUFF_OVERFLOW
+static int frame_tables(const int16_t* coef, const JpegGeom& g, int restart, jpegenc::HuffSpecWide* specs, jpegenc::HuffCodes* codes, uint32_t* hist_out) {
+    uint32_t hist[4 * jpegenc::kHuffSymbols];
+    const int rc = jpeg_enc_gather(coef, g, restart, hist);
+    if (hist_out) memcpy(hist_out, hist, sizeof(hist));
+    int overflow = 0;
+    for (int t = 0; t < 4; ++t) overflow |= jpegenc::huff_optimal(hist + t * jpegenc::kHuffSymbols, specs[t], codes[t], nullptr) != jpegenc::HUFF_OK;
+    return rc != JPEG_ENC_OK ? rc : (overflow ? JPEG_ENC_HUFF_OVERFLOW : JPEG_ENC_OK);
+}
+
+int jpeg_enc_scan_opt(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, jpegenc::HuffSpecWide* specs,
+                      uint32_t* hist, uint64_t* counters, uint64_t* rst_counters) {
+    jpegenc::HuffCodes codes[4];
+    *len = 0;
+    const int rc = frame_tables(coef, g, restart, specs, codes, hist);
+    if (rc != JPEG_ENC_OK) return rc;
+    ByteSink sink;
+    if (scan_frame(coef, g, restart, sink, counters, rst_counters, codes) != JPEG_ENC_OK) return JPEG_ENC_BAD_COEF;
     *len = sink.bytes.size();
     if (sink.bytes.size() > cap) return JPEG_ENC_SHORT;
     memcpy(out, sink.bytes.data(), sink.bytes.size());
@@ -298,6 +360,110 @@ int tstar_jpeg_encode_scan_host_rst(const int16_t* coef, int n, int W, int H, in
 int tstar_jpeg_encode_host_rst(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
                                int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status, int threads,
                                uint64_t* counters, uint64_t* rst_counters);
+
+int tstar_jpeg_encode_plan_opt(int W, int H, int hs, int vs, int n, size_t slot_bytes, int restart, int optimize, size_t* out8, size_t* out2,
+                               size_t* out3) {
+    if (!out8 || (optimize != 0 && optimize != 1)) { set_error("tstar_jpeg_encode_plan_opt: null argument or optimize outside 0 / 1"); return 1; }
+    const JpegEncPlan p = plan_jpeg_encode(JpegGeom{W, H, 3, hs, vs}, n, slot_bytes, restart, optimize);
+    if (p.error) { set_error(std::string("tstar_jpeg_encode_plan_opt: ") + p.error); return 1; }
+    if (out2) { out2[0] = (size_t)p.restart; out2[1] = p.markers; }
+    if (out3) { out3[0] = (size_t)p.optimize; out3[1] = p.off_hist; out3[2] = p.off_codes; }
+    out8[0] = p.blocks; out8[1] = p.coef_bytes; out8[2] = p.max_scan_bytes; out8[3] = p.header_bytes; out8[4] = p.workspace_bytes;
+    out8[5] = p.block_wgs; out8[6] = p.entropy_wgs_x; out8[7] = p.stuff_wgs_x;
+    return 0;
+}
+
+int tstar_jpeg_huff_optimal(const uint32_t* freq, uint8_t* spec, uint16_t* code, uint8_t* len, int32_t* steps) {
+    if (!freq || !spec) { set_error("tstar_jpeg_huff_optimal: null argument"); return 1; }
+    uint64_t total = 0;
+    for (int i = 0; i < 256; ++i) total += freq[i];
+    if (total > jpegenc::kHuffMaxCount) { set_error("tstar_jpeg_huff_optimal: the counts sum to more than 1000000000"); return 1; }
+    jpegenc::HuffSpecWide s;
+    jpegenc::HuffCodes h;
+    int n = 0;
+    jpegenc::huff_optimal(freq, s, h, &n);
+    memcpy(spec, &s, sizeof(s));
+    if (code) memcpy(code, h.code, sizeof(h.code));
+    if (len) memcpy(len, h.len, sizeof(h.len));
+    if (steps) *steps = n;
+    return 0;
+}
+
+int tstar_jpeg_encode_header_opt(int W, int H, int quality, int hs, int vs, int restart, const uint8_t* specs, uint8_t* out, size_t cap,
+                                 size_t* len) {
+    const JpegGeom g{W, H, 3, hs, vs};
+    if (!out || !len || !specs || quality < 1 || quality > 100 || !jpeg_enc_geom_ok(g) || !jpeg_enc_restart_ok(restart)) {
+        set_error("tstar_jpeg_encode_header_opt: null argument, quality outside 1..100, unsupported geometry or restart interval outside 0..65535");
+        return 1;
+    }
+    jpegenc::HuffSpecWide s[4];
+    memcpy(s, specs, sizeof(s));
+    for (int t = 0; t < 4; ++t) {
+        int sum = 0;
+        for (int i = 0; i < 16; ++i) sum += s[t].bits[i];
+        if (s[t].status != jpegenc::HUFF_OK || s[t].nvals < 1 || s[t].nvals > 256 || sum != s[t].nvals) {
+            set_error("tstar_jpeg_encode_header_opt: a table without symbols, with a status, or whose lengths do not count its symbols");
+            return 1;
+        }
+    }
+    uint8_t buf[kJpegEncHeaderOptMax + kJpegEncDriBytes];
+    *len = jpeg_enc_header_opt(g, quality, restart, s, buf);
+    if (cap < *len) { set_error("tstar_jpeg_encode_header_opt: the buffer is shorter than the header"); return 4; }
+    memcpy(out, buf, *len);
+    return 0;
+}
+
+int tstar_jpeg_encode_scan_host_opt(const int16_t* coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* out, size_t slot_bytes,
+                                    uint32_t* lengths, int32_t* status, uint8_t* specs, uint32_t* hist, int threads, uint64_t* counters,
+                                    uint64_t* rst_counters) {
+    const JpegGeom g{W, H, 3, hs, vs};
+    if (!coef || !lengths || !status || !specs || (!out && slot_bytes) || n < 1 || !jpeg_enc_geom_ok(g) || !jpeg_enc_restart_ok(restart)) {
+        set_error("tstar_jpeg_encode_scan_host_opt: null argument, empty batch, unsupported geometry or restart interval outside 0..65535");
+        return 1;
+    }
+    const size_t per = g.blocks() * 64;
+    parallel_frames(n, threads, counters, rst_counters, [&](int i, uint64_t* cnt) {
+        size_t len = 0;
+        jpegenc::HuffSpecWide s[4];
+        status[i] = jpeg_enc_scan_opt(coef + per * (size_t)i, g, restart, out + slot_bytes * (size_t)i, slot_bytes, &len, s,
+                                      hist ? hist + (size_t)i * 4 * jpegenc::kHuffSymbols : nullptr, cnt, cnt + JPEG_ENC_N_COUNTERS);
+        memcpy(specs + (size_t)i * sizeof(s), s, sizeof(s));
+        lengths[i] = (uint32_t)len;
+    });
+    return 0;
+}
+
+int tstar_jpeg_encode_host_opt(const uint8_t* frames, int N, int H, int W, const int32_t* idx, int n, int quality, int hs, int vs,
+                               int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths, int32_t* status, int threads,
+                               uint64_t* counters, uint64_t* rst_counters) {
+    JpegGeom g;
+    if (!frames_args_ok("tstar_jpeg_encode_host_opt", frames, N, H, W, idx, n, quality, hs, vs, &g)) return 1;
+    if (!lengths || !status || (!out && slot_bytes)) { set_error("tstar_jpeg_encode_host_opt: null argument"); return 1; }
+    if (!jpeg_enc_restart_ok(restart)) { set_error("tstar_jpeg_encode_host_opt: restart interval outside 0..65535 MCUs"); return 1; }
+    uint16_t q[192];
+    jpeg_enc_quant(quality, q);
+    const size_t per = g.blocks() * 64, frame = (size_t)W * H * 3;
+    parallel_frames(n, threads, counters, rst_counters, [&](int i, uint64_t* cnt) {
+        std::vector<int16_t> coef(per);
+        jpeg_enc_blocks(frames + frame * (size_t)idx[i], g, q, coef.data(), cnt + JPEG_ENC_N_DUMMY_RIGHT);
+        jpegenc::HuffSpecWide specs[4];
+        jpegenc::HuffCodes codes[4];
+        lengths[i] = 0;
+        status[i] = frame_tables(coef.data(), g, restart, specs, codes, nullptr);
+        if (status[i] != JPEG_ENC_OK) return;
+        uint8_t header[kJpegEncHeaderOptMax + kJpegEncDriBytes];
+        const size_t head = write_header(g, q, restart, specs, header);
+        ByteSink sink;
+        status[i] = scan_frame(coef.data(), g, restart, sink, cnt, cnt + JPEG_ENC_N_COUNTERS, codes);
+        const size_t len = sink.bytes.size();
+        lengths[i] = (uint32_t)(head + len);
+        if (status[i] != JPEG_ENC_OK) return;
+        if (head + len > slot_bytes) { status[i] = JPEG_ENC_SHORT; return; }
+        memcpy(out + slot_bytes * (size_t)i, header, head);
+        memcpy(out + slot_bytes * (size_t)i + head, sink.bytes.data(), len);
+    });
+    return 0;
+}
 
 int tstar_jpeg_encode_plan(int W, int H, int hs, int vs, int n, size_t slot_bytes, size_t* out8) {
     return tstar_jpeg_encode_plan_rst(W, H, hs, vs, n, slot_bytes, 0, out8, nullptr);

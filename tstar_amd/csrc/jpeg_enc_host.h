@@ -23,6 +23,8 @@ enum {
     JPEG_ENC_OK = 0,
     JPEG_ENC_SHORT = 1,          // the buffer's capacity is short of this frame: nothing of the frame was written
     JPEG_ENC_BAD_COEF = 2,       // a coefficient outside what 8-bit baseline JPEG can code (scan stage fed foreign data)
+    JPEG_ENC_HUFF_OVERFLOW = 3,  // optimised tables only: a code would be longer than 32 bits before limiting (libjpeg's
+                                 // JERR_HUFF_CLEN_OVERFLOW); nothing of the frame is written
 };
 
 // counters of the scan stage (optional out-array of the host entries)
@@ -40,6 +42,18 @@ enum { JPEG_ENC_R_RST = 0, JPEG_ENC_R_PAD_FREE = 1, JPEG_ENC_R_PAD_FF = 2, JPEG_
 inline bool jpeg_enc_restart_ok(int restart) { return restart >= 0 && restart <= kJpegEncMaxRestart; }
 inline int jpeg_enc_header_bytes(int restart) { return kJpegEncHeaderBytes + (restart > 0 ? kJpegEncDriBytes : 0); }
 
+// Optimised tables (every entry below that takes `optimize`: 0 the four Annex K tables, 1 tables built from each frame's own symbol
+// counts, Pillow's optimize=True; the procedure: jpeg_enc_math.h, "optimised tables").  The header then differs from frame to frame,
+// in content and in length: its four DHT segments carry the frame's tables, each 2 + 2 + 17 + symbols bytes.
+constexpr int kJpegEncHeaderDhtAt = 177;      // SOI, APP0, DQT x 2, SOF0: the bytes in front of the first DHT
+constexpr int kJpegEncDhtMax = 2 + 2 + 17 + 256;
+constexpr int kJpegEncHeaderOptMax = kJpegEncHeaderDhtAt + 4 * kJpegEncDhtMax + 14;        // without DRI
+constexpr int kJpegEncSpecBytes = (int)sizeof(jpegenc::HuffSpecWide);                        // 276
+static_assert(kJpegEncSpecBytes == 276, "HuffSpecWide is handed out as 276 bytes");
+inline int jpeg_enc_header_bytes(int restart, int optimize) {
+    return optimize ? kJpegEncHeaderOptMax + (restart > 0 ? kJpegEncDriBytes : 0) : jpeg_enc_header_bytes(restart);
+}
+
 // what the encoder covers: 3 components, luma sampling 2x2 / 2x1 / 1x1, 1 <= W, H <= 16384 (JpegGeom::valid() is the DECODER's
 // coverage and is narrower: it leaves pictures with subsampled chroma at most 2 samples wide to Pillow)
 bool jpeg_enc_geom_ok(const JpegGeom& g);
@@ -48,6 +62,8 @@ size_t jpeg_enc_max_scan_bytes(const JpegGeom& g);
 // (which stuffing can double), the marker itself two bytes that are never stuffed.
 size_t jpeg_enc_restart_markers(const JpegGeom& g, int restart);
 size_t jpeg_enc_max_scan_bytes(const JpegGeom& g, int restart);
+// With optimised tables a block's bound is kMaxBlockBitsOpt: a DC code may then be 16 bits long.
+size_t jpeg_enc_max_scan_bytes(const JpegGeom& g, int restart, int optimize);
 
 // Launch plan of the device encoder (jpeg_enc.hip), pure: no HIP call, no global state; integers in, integers out.  The
 // workspace of a chunk of n frames whose scans go into slots of slot_bytes bytes holds, 16-byte aligned one after another:
@@ -59,6 +75,9 @@ size_t jpeg_enc_max_scan_bytes(const JpegGeom& g, int restart);
 // and, with a restart interval only (the unstuffed stream then holds the padding and the markers too):
 //   seg   u32 [n][markers + 1]  padded bits of every interval with its marker, then (scanned in place) its first bit
 //   mark  u32 [n][markers]      byte offset of every marker in the unstuffed stream; bit 31: the byte in front of it is padded
+// and, with optimised tables only:
+//   hist   u32 [n][4][257]      symbol counts of the frame's four tables (DC luma, AC luma, DC chroma, AC chroma); [256] stays 0
+//   codes  HuffCodes [n][4]     the code / length arrays the two passes of the bits kernel code with
 constexpr int kJpegEncStuffChunk = 64;
 struct JpegEncPlan {
     const char* error;          // non-null: the launchers refuse these arguments
@@ -71,8 +90,10 @@ struct JpegEncPlan {
     int restart;                // MCUs per restart interval, 0: none (then markers, off_seg and off_mark are 0)
     size_t markers;             // per frame
     size_t off_seg, off_mark;
+    int optimize;               // 1: optimised tables (else off_hist and off_codes are 0)
+    size_t off_hist, off_codes;
 };
-JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes, int restart = 0);
+JpegEncPlan plan_jpeg_encode(const JpegGeom& g, int n, size_t slot_bytes, int restart = 0, int optimize = 0);
 
 // quant u16 [3][64], natural order, rows Y / Cb / Cr (the decoder's table layout); quality 1..100
 void jpeg_enc_quant(int quality, uint16_t* quant);
@@ -85,6 +106,9 @@ void jpeg_enc_header(const JpegGeom& g, int quality, int restart, uint8_t* out);
 // kJpegEncHeaderTablesMax.  For jpeg_enc_quant(quality)'s rows the bytes are jpeg_enc_header's.
 constexpr int kJpegEncHeaderTablesMax = kJpegEncHeaderBytes + kJpegEncDriBytes + 69 + 3 * 64;       // a third table, 16-bit entries
 size_t jpeg_enc_header_tables(const JpegGeom& g, const uint16_t* quant, int restart, uint8_t* out);
+// the header of ONE frame coded with the four tables of `specs` (DC luma, AC luma, DC chroma, AC chroma): the layout above with
+// these tables in the DHT segments -> the bytes written, at most jpeg_enc_header_bytes(restart, 1)
+size_t jpeg_enc_header_opt(const JpegGeom& g, int quality, int restart, const jpegenc::HuffSpecWide* specs, uint8_t* out);
 
 // stage 1, one frame: rgb u8 [H][W][3] -> coef int16 [g.blocks()][64]; dummy2 (optional) += {right-edge, bottom-edge} dummy blocks
 void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2);
@@ -97,5 +121,13 @@ inline jpegenc::ScanGeom scan_geom(const JpegGeom& g) {
 // that fit and frames that do not alike.
 int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, uint64_t* counters,
                   uint64_t* rst_counters);
+
+// Optimised tables, one frame.  The counts of the symbols the scan's walk emits, in its order (so the DC counts depend on the
+// interval): hist u32 [4][257], overwritten.  -> JPEG_ENC_OK or JPEG_ENC_BAD_COEF.
+int jpeg_enc_gather(const int16_t* coef, const JpegGeom& g, int restart, uint32_t* hist);
+// gather, the four tables, the scan coded with them.  specs [4] out (always written; a spec's status names an overflow);
+// hist (optional) u32 [4][257] out.  -> JPEG_ENC_*; with JPEG_ENC_HUFF_OVERFLOW *len is 0 and nothing is written.
+int jpeg_enc_scan_opt(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, jpegenc::HuffSpecWide* specs,
+                      uint32_t* hist, uint64_t* counters, uint64_t* rst_counters);
 
 }  // namespace tstar

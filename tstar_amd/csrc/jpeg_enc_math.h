@@ -2,7 +2,8 @@
 // (jpeg_enc.hip): libjpeg-turbo as Pillow drives it -- 16-bit fixed-point RGB -> YCbCr, the h2v2 / h2v1 box downsamplers with
 // their alternating bias, libjpeg's accurate integer forward DCT (Loeffler-Ligtenberg-Moschytz, the twelve constants x 2^13
 // that jpeg_math.h::idct8 uses), the rounding quantiser, the quality -> table rule, the four Annex K Huffman tables as
-// code / length arrays, and the symbol walk of one block.  Geometry and coefficient layout are JpegGeom's (jpeg_host.h).
+// code / length arrays, the symbol walk of one block, and the tables Pillow's optimize=True builds from a frame's own symbol
+// counts.  Geometry and coefficient layout are JpegGeom's (jpeg_host.h).
 #pragma once
 #include <stdint.h>
 
@@ -216,6 +217,153 @@ TSTAR_JHD BlockEvents encode_block(const int16_t* coef, int pred, const HuffCode
     if (run > 0) put((unsigned)ac.code[0], (int)ac.len[0]);
     else ev.no_eob = 1;
     return ev;
+}
+
+// ---------------------------------------------------------------------------------------------- optimised tables
+// Pillow's optimize=True (libjpeg's optimize_coding): every frame is coded with four tables built from its own symbol counts.
+// The procedure is jchuff.c's: encode_mcu_gather / htest_one_block for the counts, jpeg_gen_optimal_table for the tables.
+
+// The gathering form of encode_block's walk: count(ac, symbol) for every code the walk above would put (ac: 0 the DC table of
+// the component, 1 its AC table); magnitude bits have no symbol.  Out-of-range values are clamped as above.
+template <class Count>
+TSTAR_JHD BlockEvents gather_block(const int16_t* coef, int pred, const uint8_t* zigzag, Count&& count) {
+    BlockEvents ev = {0, 0, 0};
+    int n = category((int)coef[0] - pred);
+    if (n > 11) { ev.bad = 1; n = 11; }
+    count(0, n);
+    int run = 0;
+    for (int k = 1; k < 64; ++k) {
+        const int v = coef[zigzag[k]];
+        if (v == 0) { ++run; continue; }
+        while (run > 15) {
+            count(1, 0xF0);
+            run -= 16;
+            ++ev.zrl;
+        }
+        int s = category(v);
+        if (s > 10) { ev.bad = 1; s = 10; }
+        count(1, (run << 4) | s);
+        run = 0;
+    }
+    if (run > 0) count(1, 0);
+    else ev.no_eob = 1;
+    return ev;
+}
+
+// A table as the DHT segment carries it, for any alphabet of up to 256 symbols (the standard tables' HuffSpec stops at 162).
+// 276 bytes, no padding: the layout the C ABI hands out.
+struct HuffSpecWide {
+    uint8_t bits[16];            // codes of length 1..16
+    uint8_t vals[256];           // the first nvals are the symbols, by code length and then by value
+    uint16_t nvals;
+    uint16_t status;             // HUFF_*
+};
+enum { HUFF_OK = 0, HUFF_CLEN_OVERFLOW = 1, HUFF_EMPTY = 2 };        // libjpeg's JERR_HUFF_CLEN_OVERFLOW; a histogram without a symbol
+constexpr int kHuffSymbols = 257;                    // 256 symbols and the reserved one, which keeps the all-ones code unused
+constexpr int kHuffMaxClen = 32;                     // libjpeg's MAX_CLEN
+constexpr uint32_t kHuffMaxCount = 1000000000u;      // libjpeg's search starts from this value: larger counts are never found
+
+// With a 16-bit DC code a block takes at most (16 + 11) + 63 * (16 + 10) bits.
+constexpr int kMaxBlockBitsOpt = 27 + 63 * 26;
+
+// Code sizes as jpeg_gen_optimal_table finds them: repeat { c1 = the smallest non-zero count, ties to the LARGEST index; c2 the
+// same among the others; count[c1] += count[c2], count[c2] = 0 } until one tree is left; a symbol's size is its depth in the
+// tree of merges.  libjpeg bumps the sizes of both chains at every merge; here every merge makes a node with two parent links
+// and the depth is read by walking them, which is what the table kernel does with one leaf per lane.
+// freq [256] (their sum at most kHuffMaxCount); size [257] out (0: absent; [256] the reserved symbol's) -> the largest size.
+TSTAR_JHD int huff_code_sizes(const uint32_t* freq, uint8_t* size) {
+    uint32_t f[kHuffSymbols];
+    uint16_t node[kHuffSymbols], parent[2 * kHuffSymbols];
+    for (int i = 0; i < kHuffSymbols; ++i) { f[i] = i < 256 ? freq[i] : 1u; node[i] = (uint16_t)i; }
+    for (int i = 0; i < 2 * kHuffSymbols; ++i) parent[i] = 0xFFFF;
+    for (int next = kHuffSymbols;; ++next) {
+        int c1 = -1, c2 = -1;
+        for (int i = 0; i < kHuffSymbols; ++i)
+            if (f[i] && (c1 < 0 || f[i] <= f[c1])) c1 = i;
+        for (int i = 0; i < kHuffSymbols; ++i)
+            if (f[i] && i != c1 && (c2 < 0 || f[i] <= f[c2])) c2 = i;
+        if (c2 < 0) break;
+        f[c1] += f[c2];
+        f[c2] = 0;
+        parent[node[c1]] = parent[node[c2]] = (uint16_t)next;
+        node[c1] = (uint16_t)next;
+    }
+    int deepest = 0;
+    for (int i = 0; i < kHuffSymbols; ++i) {
+        int d = 0;
+        if (i == 256 || freq[i])
+            for (int p = i; parent[p] != 0xFFFF; p = parent[p]) ++d;
+        size[i] = (uint8_t)d;                         // at most 256
+        if (d > deepest) deepest = d;
+    }
+    return deepest;
+}
+
+// bits [33] (index = code length, [0] unused) counted from sizes of at most 32 -> limited to 16 as libjpeg does it: a pair of
+// the longest codes gives one code a bit shorter, and the longest shorter code becomes the prefix of two; then the reserved
+// symbol's code, one of the longest, is taken out.
+TSTAR_JHD void huff_limit_bits(int* bits, int* steps) {
+    int n = 0;
+    for (int i = kHuffMaxClen; i > 16; --i)
+        while (bits[i] > 0) {
+            int j = i - 2;
+            while (j > 0 && bits[j] == 0) --j;
+            bits[i] -= 2; bits[i - 1] += 1; bits[j + 1] += 2; bits[j] -= 1;
+            ++n;
+        }
+    int i = 16;
+    while (i > 0 && bits[i] == 0) --i;
+    bits[i] -= 1;
+    if (steps) *steps = n;
+}
+
+// rank of symbol j (size[j] > 0) in the order of huffval: symbols by unlimited code size, then by value
+TSTAR_JHD int huff_rank(const uint8_t* size, int j) {
+    int r = 0;
+    for (int i = 0; i < 256; ++i) r += size[i] && (size[i] < size[j] || (size[i] == size[j] && i < j));
+    return r;
+}
+
+// canonical codes of a wide spec (make_codes' rule); every symbol without a code gets length 0
+TSTAR_JHD void huff_assign_codes(const HuffSpecWide& s, HuffCodes& h) {
+    for (int i = 0; i < 256; ++i) { h.code[i] = 0; h.len[i] = 0; }
+    unsigned code = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        for (int i = 0; i < s.bits[l - 1]; ++i, ++k) {
+            h.code[s.vals[k]] = (uint16_t)code++;
+            h.len[s.vals[k]] = (uint8_t)l;
+        }
+        code <<= 1;
+    }
+}
+
+// The whole procedure, pure: freq [256] -> spec (bits, huffval, status) and codes.  A status other than HUFF_OK leaves an empty
+// spec and no code.  steps (optional): how often the limiting loop ran.
+TSTAR_JHD int huff_optimal(const uint32_t* freq, HuffSpecWide& spec, HuffCodes& codes, int* steps) {
+    for (int i = 0; i < 16; ++i) spec.bits[i] = 0;
+    for (int i = 0; i < 256; ++i) spec.vals[i] = 0;
+    spec.nvals = 0;
+    spec.status = HUFF_OK;
+    if (steps) *steps = 0;
+    uint8_t size[kHuffSymbols];
+    int present = 0;
+    for (int i = 0; i < 256; ++i) present += freq[i] != 0;
+    if (!present) spec.status = HUFF_EMPTY;
+    else if (huff_code_sizes(freq, size) > kHuffMaxClen) spec.status = HUFF_CLEN_OVERFLOW;
+    if (spec.status == HUFF_OK) {
+        int bits[kHuffMaxClen + 1];
+        for (int i = 0; i <= kHuffMaxClen; ++i) bits[i] = 0;
+        for (int i = 0; i < kHuffSymbols; ++i)
+            if (size[i]) ++bits[size[i]];
+        huff_limit_bits(bits, steps);
+        for (int i = 0; i < 16; ++i) spec.bits[i] = (uint8_t)bits[i + 1];
+        for (int j = 0; j < 256; ++j)
+            if (size[j]) spec.vals[huff_rank(size, j)] = (uint8_t)j;
+        spec.nvals = (uint16_t)present;
+    }
+    huff_assign_codes(spec, codes);
+    return spec.status;
 }
 
 // ---------------------------------------------------------------------------------------------- scan order

@@ -155,22 +155,26 @@ class FrameStore:
         _, H, W, _ = self.shape
         return torch.cat(parts).cpu().numpy() if parts else np.empty((0, H, W, 3), dtype=np.uint8)
 
-    def jpeg_frames(self, secs, quality: int = 75, subsampling: str = "4:2:0", restart_rows=None, restart_blocks=None):
+    def jpeg_frames(self, secs, quality: int = 75, subsampling: str = "4:2:0", restart_rows=None, restart_blocks=None,
+                    optimize: bool = False):
         """The given logical seconds as JPEG files (list of bytes), encoded on the device straight from the store: byte for
         byte Pillow's ``Image.fromarray(frame).save(buf, "JPEG", quality=, subsampling=)`` of ``host_frames(secs)``;
-        ``restart_rows`` / ``restart_blocks`` are Pillow's ``restart_marker_rows`` / ``restart_marker_blocks``."""
+        ``restart_rows`` / ``restart_blocks`` are Pillow's ``restart_marker_rows`` / ``restart_marker_blocks``, ``optimize`` its
+        ``optimize`` (Huffman tables built from each frame's own statistics: smaller files, the same pixels)."""
         from . import jpeg_encode
-        return jpeg_encode.encode_frames((self, secs), quality, subsampling, restart_rows=restart_rows, restart_blocks=restart_blocks)
+        return jpeg_encode.encode_frames((self, secs), quality, subsampling, restart_rows=restart_rows, restart_blocks=restart_blocks,
+                                         optimize=optimize)
 
     def save_mjpeg(self, path: str, quality: int = 90, subsampling: str = "4:2:0", fps: Optional[float] = None, restart_rows=None,
-                   restart_blocks=None) -> int:
+                   restart_blocks=None, optimize: bool = False) -> int:
         """Write the store as Motion-JPEG (.avi: RIFF with one MJPG stream; .mjpeg / .mjpg: concatenated frames) at its logical
         rate, 1 frame per second unless ``fps`` is given, so that ``open_video(path)`` returns a store of the same seconds.  A
         file that would need OpenDML (1 GiB and above) is refused with a ValueError that names .mjpeg as the way out.
         ``restart_rows`` / ``restart_blocks`` (default: no markers) write every frame with restart intervals of that many MCU
-        rows / MCUs."""
+        rows / MCUs; ``optimize=True`` writes every frame with optimised Huffman tables."""
         from . import jpeg_encode
-        return jpeg_encode.save_mjpeg(self, path, quality, subsampling, fps, restart_rows=restart_rows, restart_blocks=restart_blocks)
+        return jpeg_encode.save_mjpeg(self, path, quality, subsampling, fps, restart_rows=restart_rows, restart_blocks=restart_blocks,
+                                      optimize=optimize)
 
 
 class JpegFrameStore(FrameStore):
