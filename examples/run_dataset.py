@@ -59,6 +59,9 @@ def main():
     ap.add_argument("--jpeg-recode", type=int, default=None, metavar="N",
                     help="with --jpeg-resident: re-code the compressed videos losslessly at open with a restart interval of N MCUs "
                          "(1..65535; sets TSTAR_JPEG_RECODE), so that fetches decode one lane per interval: same pixels, same results")
+    ap.add_argument("--jpeg-recode-optimize", action="store_true",
+                    help="with --jpeg-recode: write the re-coded frames with optimised Huffman tables, one set per group of frames "
+                         "(sets TSTAR_JPEG_RECODE_OPTIMIZE): a smaller arena, same pixels, same results")
     ap.add_argument("--query-image", action="append", default=[], metavar="NAME=PATH[@x0,y0,x1,y1]",
                     help="example image of an object (repeatable): every target / cue object called NAME is searched for by the "
                          "image-guided query embedded from PATH instead of by its text; @x0,y0,x1,y1 (pixels of that image) "
@@ -109,6 +112,10 @@ def main():
         if args.jpeg_resident is None:
             ap.error("--jpeg-recode re-codes the arena of a compressed-resident store: it needs --jpeg-resident")
         os.environ["TSTAR_JPEG_RECODE"] = str(args.jpeg_recode)
+    if args.jpeg_recode_optimize:
+        if args.jpeg_recode is None:
+            ap.error("--jpeg-recode-optimize optimises the tables of a re-coded arena: it needs --jpeg-recode")
+        os.environ["TSTAR_JPEG_RECODE_OPTIMIZE"] = "1"
     per_video = max(1, args.questions_per_video)
     paths = args.videos if args.videos else [f"synthetic://n={args.nframes},seed={100 + i // per_video}" for i in range(args.items * per_video)]
     items = [{"video_path": p, "targets": QUESTIONS[i % 4][0], "cues": QUESTIONS[i % 4][1]} for i, p in enumerate(paths)]

@@ -753,6 +753,53 @@ int tstar_jpeg_recode_assemble_host(const void* desc, int m, int n_segments, con
                                     int n_mcu, const uint8_t* src_bytes, size_t src_total, const uint16_t* src_quant,
                                     const void* src_frames, const void* src_segments, int n_src_frames, int n_src_segments, uint8_t* rec,
                                     size_t rec_bytes, uint8_t* out, size_t out_bytes);
+/* ---- Re-coding with OPTIMISED HUFFMAN TABLES (added entries; tstar_abi_version() stays 3): the counterpart of
+ * `jpegtran -optimize -restart N`.  Two modes.  PER FRAME: tstar_jpeg_encode_scan_opt on the decoder's coefficients, every frame
+ * under a header of its own.  SHARED: the frames of a GROUP are coded with ONE set of four tables, built by the same procedure from
+ * the SUM of their symbol counts (the DC predictors restart with every frame, so the sum over frames is exact); a compressed-resident
+ * arena then needs one decoder table set per group and quantisation set instead of one per frame.
+ * Header: the layout of tstar_jpeg_encode_header_tables (the source's DQT entries, SOF0 or SOF1) with the four tables of `specs`
+ * (4 x 276 bytes, each with status 0) in the DHT segments.  At most 1566 bytes; for the rows of a quality the bytes are
+ * tstar_jpeg_encode_header_opt's.  restart 0: no DRI. */
+int tstar_jpeg_encode_header_tables_opt(int W, int H, const uint16_t* quant, int hs, int vs, int restart, const uint8_t* specs, uint8_t* out,
+                                        size_t cap, size_t* len);
+/* Groups.  group i32 [n]: the group of every frame of the batch, -1 for a frame that is not coded (status 3, length 0); group
+ * numbers start at 0 and rise by one in frame order, so a group's frames are consecutive but for such frames.  A group holds at
+ * most 1000000000 / (64 * blocks) frames, at least 1 (the first entry returns that number; 0: unsupported geometry): a block emits
+ * at most 64 symbols, so a group's counts stay within what tstar_jpeg_huff_optimal is defined for and the u32 bins cannot wrap.
+ * The second entry checks the groups and writes span i32 [n_groups][2], the first frame of every group and the frame behind its
+ * last, which the device entry wants next to the groups. */
+int tstar_jpeg_encode_group_frames(int W, int H, int hs, int vs);
+int tstar_jpeg_encode_group_spans(const int32_t* group, int n, int n_groups, int W, int H, int hs, int vs, int32_t* span);
+/* Scan stage with shared tables.  stages, a sum of: 1 the frames' counts (tstar_jpeg_encode_scan_opt's histogram launch) and their
+ * sums per group into group_hist u32 [n_groups][4][257], added in frame order by a kernel that stores every bin once (no atomics);
+ * 2 the groups' tables from group_hist AS IT IS (so a caller may put counts of its own there) into specs u8 [n_groups][4][276] and,
+ * on the device, the code tables of the workspace; 4 the scans, coded with the tables stage 2 left (host: rebuilt from specs).  A
+ * frame of a group one of whose tables has a status reports 3 with length 0, unless its walk met a coefficient without a code (2).
+ * The device entry takes the groups and spans twice, in host memory (checked before any launch) and in device memory (read by the
+ * kernels, which treat a group outside 0 .. n_groups - 1 as -1 and clip a span to the n frames).  Workspace: the bytes
+ * tstar_jpeg_encode_plan_opt names with optimize = 1 for these n and slot_bytes.  No synchronisation. */
+int tstar_jpeg_encode_scan_host_grp(const int16_t* coef, int n, int W, int H, int hs, int vs, int restart, const int32_t* group,
+                                    int n_groups, int stages, uint32_t* group_hist, uint8_t* specs, uint8_t* out, size_t slot_bytes,
+                                    uint32_t* lengths, int32_t* status, int threads);
+int tstar_jpeg_encode_scan_grp(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, const int32_t* h_group,
+                               const int32_t* h_span, const int32_t* d_group, const int32_t* d_span, int n_groups, int stages,
+                               uint32_t* d_group_hist, uint8_t* d_specs, uint8_t* d_out, size_t slot_bytes, uint32_t* d_lengths,
+                               int32_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream);
+/* The assembly with header rows of header_pitch bytes (a multiple of 16 in 16..65536 that holds the piece's longest header; rows 16-byte
+ * aligned) and restart 0..65535 (0: no interval, a re-coded frame is one segment; so is one whose interval is not shorter than the
+ * frame).  Everything else, bytes and records included, is tstar_jpeg_recode_assemble's. */
+int tstar_jpeg_recode_assemble_opt(const void* h_desc, const void* d_desc, int m, int n_segments, const uint8_t* d_headers,
+                                   size_t header_pitch, const uint32_t* d_header_len, int n_headers, const uint8_t* d_slots,
+                                   size_t slot_bytes, const uint32_t* d_scan_len, int restart, int n_mcu, const uint8_t* d_src_bytes,
+                                   size_t src_total, const uint16_t* d_src_quant, const void* d_src_frames, const void* d_src_segments,
+                                   int n_src_frames, int n_src_segments, uint8_t* d_rec, size_t rec_bytes, uint8_t* d_out,
+                                   size_t out_bytes, size_t longest, void* stream);
+int tstar_jpeg_recode_assemble_host_opt(const void* desc, int m, int n_segments, const uint8_t* headers, size_t header_pitch,
+                                        const uint32_t* header_len, int n_headers, const uint8_t* slots, size_t slot_bytes,
+                                        const uint32_t* scan_len, int restart, int n_mcu, const uint8_t* src_bytes, size_t src_total,
+                                        const uint16_t* src_quant, const void* src_frames, const void* src_segments, int n_src_frames,
+                                        int n_src_segments, uint8_t* rec, size_t rec_bytes, uint8_t* out, size_t out_bytes);
 /* Native-resolution RGB u8 [n,H,W,3] of NV12 frames (the keyframes pop_frames hands back, :379-380). */
 int tstar_nv12_to_rgb(const uint8_t* d_video, int N, int H, int W, const int32_t* d_frame_idx, int n,
                       uint8_t* d_out, void* stream);

@@ -119,6 +119,15 @@ SIGNATURES = {
                                         _sz, _vp]),
     "tstar_jpeg_recode_assemble_host": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp,
                                              _sz]),
+    "tstar_jpeg_encode_header_tables_opt": (_i, [_i, _i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "tstar_jpeg_encode_group_frames": (_i, [_i, _i, _i, _i]),
+    "tstar_jpeg_encode_group_spans": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "tstar_jpeg_encode_scan_host_grp": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _i]),
+    "tstar_jpeg_encode_scan_grp": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "tstar_jpeg_recode_assemble_opt": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp, _i, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _sz,
+                                            _vp, _sz, _sz, _vp]),
+    "tstar_jpeg_recode_assemble_host_opt": (_i, [_vp, _i, _i, _vp, _sz, _vp, _i, _vp, _sz, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp, _i, _i, _vp, _sz,
+                                                 _vp, _sz]),
     "tstar_jpeg_gather_bytes": (_sz, [_sz, _i, _i, _vp]),
     "tstar_jpeg_gather": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _sz, _i, _vp, _sz, _vp]),
     "tstar_jpeg_gather_host": (_i, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _sz, _i, _vp, _sz]),

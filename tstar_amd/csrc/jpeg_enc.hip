@@ -37,7 +37,19 @@
 //   entropy stage  jpeg_enc_bits_opt_kernel  the lane body of jpeg_enc_bits_kernel behind a staging of the frame's four code tables
 //                                            into LDS
 //   status         jpeg_enc_opt_status_kernel  a frame with a table that has a status (never written) reports JPEG_ENC_HUFF_OVERFLOW
+//
+// With SHARED tables (tstar_jpeg_encode_scan_grp: the re-coding of a compressed-resident arena) the frames of a GROUP are coded with one
+// set of tables built from the sum of their counts; the launches above with
+//   tables         jpeg_enc_group_sum_kernel   behind the histogram launch: one lane per bin adds the group's frames in frame order and
+//                                              stores the sum once (no atomics)
+//                  jpeg_enc_tables_kernel      one wave per (GROUP, table), on the sums
+//                  jpeg_enc_group_flag_kernel  the frames of a group with a status, and the frames without a group, are never written
+//   entropy stage  jpeg_enc_bits_grp_kernel    jpeg_enc_bits_opt_kernel with the tables of the frame's group (frame -> table-slot indirection)
+//   status         jpeg_enc_group_status_kernel
+#include <string.h>
+
 #include <type_traits>
+#include <vector>
 
 #include "../../include/tstar_hip.h"
 #include "common.h"
@@ -474,7 +486,7 @@ __global__ __launch_bounds__(64) void jpeg_enc_tables_kernel(const uint32_t* __r
         if (lane == 0) jpegenc::huff_assign_codes(spec, tab);
     } else if (lane == 0) {
         spec.status = (uint16_t)status;
-        atomicOr(meta + (size_t)f * 4 + META_FLAGS, (uint32_t)FLAG_SKIP);          // the frame is never written
+        if (meta) atomicOr(meta + (size_t)f * 4 + META_FLAGS, (uint32_t)FLAG_SKIP);        // the frame is never written (null: f is a group)
     }
     __syncthreads();
     uint32_t* so = reinterpret_cast<uint32_t*>(specs + (size_t)f * 4 + t);
@@ -490,6 +502,85 @@ __global__ __launch_bounds__(256) void jpeg_enc_opt_status_kernel(const jpegenc:
     bool bad = false;
     for (int t = 0; t < 4; ++t) bad |= specs[(size_t)f * 4 + t].status != jpegenc::HUFF_OK;
     if (bad && status[f] != JPEG_ENC_BAD_COEF) {
+        lengths[f] = 0;
+        status[f] = JPEG_ENC_HUFF_OVERFLOW;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ shared tables (groups of frames)
+// The frames of a group are coded with ONE set of four tables, built from the sum of their counts.  group i32 [n]: a frame's group
+// (-1: not coded); span i32 [n_groups][2]: the first frame of a group and the frame behind its last.  Both come from the host, which
+// has checked its copy (jpeg_enc_groups_check); the kernels still trust neither: a group outside 0 .. n_groups - 1 counts as -1, a
+// span is clipped to the n frames.
+struct GroupArgs {
+    const int32_t* group;       // [n]
+    const int32_t* span;        // [n_groups][2]
+    uint32_t* hist;             // [n_groups][4][257]
+    int n_groups;
+};
+__device__ __forceinline__ int group_of(const GroupArgs& ga, int f) {
+    const int g = ga.group[f];
+    return g >= 0 && g < ga.n_groups ? g : -1;
+}
+
+// grid (ceil(4 * 257 / 256), n_groups): lane i adds bin i of the group's frames IN FRAME ORDER into a register and stores the sum once:
+// no atomic, no bin that two workgroups share (a video's EOB bin would otherwise take tens of thousands of atomics on one word),
+// and the integer sum is the same in every run.  Four loads are in flight per lane; neighbouring lanes read neighbouring words.
+__global__ __launch_bounds__(256) void jpeg_enc_group_sum_kernel(const uint32_t* __restrict__ hist, GroupArgs ga, int n) {
+    const int i = blockIdx.x * 256 + (int)threadIdx.x, g = blockIdx.y;
+    if (i >= 4 * kHist) return;
+    int f0 = ga.span[2 * g], f1 = ga.span[2 * g + 1];
+    f0 = f0 < 0 ? 0 : f0;
+    f1 = f1 > n ? n : f1;
+    uint32_t sum = 0;
+    int f = f0;
+    for (; f + 4 <= f1; f += 4) {
+        uint32_t v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = ga.group[f + j] == g ? hist[(size_t)(f + j) * 4 * kHist + i] : 0u;
+        sum += v[0]; sum += v[1]; sum += v[2]; sum += v[3];
+    }
+    for (; f < f1; ++f)
+        if (ga.group[f] == g) sum += hist[(size_t)f * 4 * kHist + i];
+    ga.hist[(size_t)g * 4 * kHist + i] = sum;
+}
+
+// one lane per frame, behind the tables: a frame without a group, or of a group one of whose tables has a status, is never written
+__global__ __launch_bounds__(256) void jpeg_enc_group_flag_kernel(const jpegenc::HuffSpecWide* __restrict__ specs, GroupArgs ga, uint32_t* meta, int n) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    const int g = group_of(ga, f);
+    bool bad = g < 0;
+    if (!bad)
+        for (int t = 0; t < 4; ++t) bad |= specs[(size_t)g * 4 + t].status != jpegenc::HUFF_OK;
+    if (bad) atomicOr(meta + (size_t)f * 4 + META_FLAGS, (uint32_t)FLAG_SKIP);
+}
+
+// jpeg_enc_bits_opt_kernel with the tables of the frame's GROUP: a frame -> table-slot indirection in place of blockIdx.y * 4.  A
+// frame without a group stages tables without a code (every length 0); it is flagged and never written.
+template <int WRITE, bool RST>
+__global__ __launch_bounds__(256) void jpeg_enc_bits_grp_kernel(EntropyArgs a, RestartOf<RST> r, const jpegenc::HuffCodes* __restrict__ codes,
+                                                                GroupArgs ga) {
+    __shared__ alignas(16) jpegenc::HuffCodes tab[4];
+    const int g = group_of(ga, blockIdx.y);                 // uniform over the workgroup
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(codes + (size_t)(g < 0 ? 0 : g) * 4);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(tab);
+    for (uint32_t i = threadIdx.x; i < kTableWords; i += 256) dst[i] = g < 0 ? 0u : src[i];
+    __syncthreads();
+    bits_lane<WRITE, RST>(a, r, tab);
+}
+
+// one lane per frame, behind the stuffing passes: jpeg_enc_opt_status_kernel with the group's tables; a frame without a group
+// reports JPEG_ENC_HUFF_OVERFLOW whatever lies in its coefficients
+__global__ __launch_bounds__(256) void jpeg_enc_group_status_kernel(const jpegenc::HuffSpecWide* __restrict__ specs, GroupArgs ga, uint32_t* lengths,
+                                                                    int32_t* status, int n) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n) return;
+    const int g = group_of(ga, f);
+    bool bad = false;
+    if (g >= 0)
+        for (int t = 0; t < 4; ++t) bad |= specs[(size_t)g * 4 + t].status != jpegenc::HUFF_OK;
+    if (g < 0 || (bad && status[f] != JPEG_ENC_BAD_COEF)) {
         lengths[f] = 0;
         status[f] = JPEG_ENC_HUFF_OVERFLOW;
     }
@@ -735,17 +826,19 @@ int jpeg_encode_blocks_u8(const uint8_t* frames, int N, int H, int W, const int3
 namespace {
 
 // the six launches of the scan stage, with (RST) or without the interval-only steps; codes: the frames' own code tables
-// [n][4] (optimised tables), or null for the Annex K ones
+// [n][4] (optimised tables), or null for the Annex K ones; ga: codes holds the GROUPS' tables [n_groups][4]
 template <bool RST>
 int launch_scan(const JpegEncPlan& p, int n, const EntropyArgs& e, const StuffArgs& a, const RestartOf<RST>& r, const jpegenc::HuffCodes* codes,
-                hipStream_t s) {
+                hipStream_t s, const GroupArgs* ga = nullptr) {
     const dim3 egrid(p.entropy_wgs_x, (unsigned)n), sgrid(p.stuff_wgs_x, (unsigned)n);
-    if (codes) hipLaunchKernelGGL((jpeg_enc_bits_opt_kernel<0, RST>), egrid, dim3(256), 0, s, e, r, codes);
+    if (ga) hipLaunchKernelGGL((jpeg_enc_bits_grp_kernel<0, RST>), egrid, dim3(256), 0, s, e, r, codes, *ga);
+    else if (codes) hipLaunchKernelGGL((jpeg_enc_bits_opt_kernel<0, RST>), egrid, dim3(256), 0, s, e, r, codes);
     else hipLaunchKernelGGL((jpeg_enc_bits_kernel<0, RST>), egrid, dim3(256), 0, s, e, r);
     TSTAR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(jpeg_enc_offsets_kernel<RST>, dim3((unsigned)n), dim3(256), 0, s, e.bits, e.meta, e.blocks, a.slot_bytes, r);
     TSTAR_HIP_CHECK(hipGetLastError());
-    if (codes) hipLaunchKernelGGL((jpeg_enc_bits_opt_kernel<1, RST>), egrid, dim3(256), 0, s, e, r, codes);
+    if (ga) hipLaunchKernelGGL((jpeg_enc_bits_grp_kernel<1, RST>), egrid, dim3(256), 0, s, e, r, codes, *ga);
+    else if (codes) hipLaunchKernelGGL((jpeg_enc_bits_opt_kernel<1, RST>), egrid, dim3(256), 0, s, e, r, codes);
     else hipLaunchKernelGGL((jpeg_enc_bits_kernel<1, RST>), egrid, dim3(256), 0, s, e, r);
     TSTAR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((jpeg_enc_ff_kernel<0, RST>), sgrid, dim3(256), 0, s, a, r);
@@ -761,8 +854,9 @@ int launch_scan(const JpegEncPlan& p, int n, const EntropyArgs& e, const StuffAr
 
 namespace {
 // the two stages in front of an optimised scan: 1 counts (into the zeroed histograms), 2 tables (from the histograms as they are)
+// ga: stage 1 also sums the counts of every group's frames, stage 2 makes the tables of the GROUPS from those sums and flags the frames
 int launch_tables(const JpegEncPlan& p, int n, const EntropyArgs& e, int restart, jpegenc::HuffSpecWide* specs, uint8_t* ws, int stages,
-                  hipStream_t s) {
+                  hipStream_t s, const GroupArgs* ga = nullptr) {
     TSTAR_REQUIRE((uintptr_t)specs % 4 == 0, "jpeg encode: the specs need 4-byte alignment");
     uint32_t* hist = (uint32_t*)(ws + p.off_hist);
     if (stages & 1) {
@@ -770,8 +864,18 @@ int launch_tables(const JpegEncPlan& p, int n, const EntropyArgs& e, int restart
         hipLaunchKernelGGL(jpeg_enc_hist_kernel, dim3((unsigned)((p.blocks + kHistBlocksPerWg - 1) / kHistBlocksPerWg), (unsigned)n), dim3(256), 0, s, e,
                            restart, hist);
         TSTAR_HIP_CHECK(hipGetLastError());
+        if (ga) {
+            hipLaunchKernelGGL(jpeg_enc_group_sum_kernel, dim3((4 * kHist + 255) / 256, (unsigned)ga->n_groups), dim3(256), 0, s, hist, *ga, n);
+            TSTAR_HIP_CHECK(hipGetLastError());
+        }
     }
-    if (stages & 2) {
+    if ((stages & 2) && ga) {
+        hipLaunchKernelGGL(jpeg_enc_tables_kernel, dim3(4, (unsigned)ga->n_groups), dim3(64), 0, s, ga->hist, specs,
+                           (jpegenc::HuffCodes*)(ws + p.off_codes), (uint32_t*)nullptr);
+        TSTAR_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(jpeg_enc_group_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, *ga, e.meta, n);
+        TSTAR_HIP_CHECK(hipGetLastError());
+    } else if (stages & 2) {
         hipLaunchKernelGGL(jpeg_enc_tables_kernel, dim3(4, (unsigned)n), dim3(64), 0, s, hist, specs, (jpegenc::HuffCodes*)(ws + p.off_codes), e.meta);
         TSTAR_HIP_CHECK(hipGetLastError());
     }
@@ -781,9 +885,11 @@ int launch_tables(const JpegEncPlan& p, int n, const EntropyArgs& e, int restart
 
 // the scan stage with a restart interval of `restart` MCUs (0: none).  d_rst_counters: optional u32 [n][3], zeroed here.
 // specs: null codes with the Annex K tables; else device HuffSpecWide [n][4] out, and every frame is coded with tables of its own
+// ga: specs is [n_groups][4] and every frame is coded with the tables of its group; stages (1 counts, 2 tables, 4 scans) then says
+// which steps run: the tables are made from ga->hist as it is, the scans with the codes the workspace holds
 int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths,
                         int32_t* status, void* workspace, size_t workspace_bytes, uint32_t* d_rst_counters, hipStream_t s,
-                        jpegenc::HuffSpecWide* specs = nullptr) {
+                        jpegenc::HuffSpecWide* specs = nullptr, const GroupArgs* ga = nullptr, int stages = 7) {
     const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart, specs ? 1 : 0);
     TSTAR_REQUIRE(!p.error, std::string("jpeg_encode_scan_u8: ") + (p.error ? p.error : ""));
     TSTAR_REQUIRE((uintptr_t)workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
@@ -809,11 +915,16 @@ int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, int resta
     jpegenc::HuffCodes* codes = nullptr;
     if (specs) {
         codes = (jpegenc::HuffCodes*)(ws + p.off_codes);
-        RC(launch_tables(p, n, e, restart, specs, ws, 3, s));
+        if (stages & 3) RC(launch_tables(p, n, e, restart, specs, ws, stages & 3, s, ga));
+        if (ga && !(stages & 2)) {                         // the scans alone: the flags are those of the tables that were kept
+            hipLaunchKernelGGL(jpeg_enc_group_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, *ga, e.meta, n);
+            TSTAR_HIP_CHECK(hipGetLastError());
+        }
     }
+    if (!(stages & 4)) return TSTAR_OK;
     int rc;
     if (restart == 0) {
-        rc = launch_scan<false>(p, n, e, a, NoRestart{}, codes, s);
+        rc = launch_scan<false>(p, n, e, a, NoRestart{}, codes, s, ga);
     } else {
         RestartArgs r;
         r.seg = (uint32_t*)(ws + p.off_seg);
@@ -822,10 +933,11 @@ int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, int resta
         r.interval = restart;
         r.seg_blocks = restart * e.sg.per_mcu();       // at most 65535 * 6; at least the frame's blocks when there is no marker
         r.markers = (uint32_t)p.markers;
-        rc = launch_scan<true>(p, n, e, a, r, codes, s);
+        rc = launch_scan<true>(p, n, e, a, r, codes, s, ga);
     }
     if (rc != TSTAR_OK || !specs) return rc;
-    hipLaunchKernelGGL(jpeg_enc_opt_status_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, lengths, status, n);
+    if (ga) hipLaunchKernelGGL(jpeg_enc_group_status_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, *ga, lengths, status, n);
+    else hipLaunchKernelGGL(jpeg_enc_opt_status_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, lengths, status, n);
     TSTAR_HIP_CHECK(hipGetLastError());
     return TSTAR_OK;
 }
@@ -892,6 +1004,44 @@ int tstar_jpeg_encode_tables(const int16_t* d_coef, int n, int W, int H, int hs,
     e.blocks = (int)p.blocks;
     TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), (hipStream_t)stream));
     return launch_tables(p, n, e, restart, (jpegenc::HuffSpecWide*)d_specs, (uint8_t*)d_workspace, stages, (hipStream_t)stream);
+}
+
+// Shared tables: frame f is coded with the four tables of group h_group[f] (d_group: the same array on the device; -1: the frame is
+// not coded), built from the sum of the group's counts.  h_span / d_span: i32 [n_groups][2] from tstar_jpeg_encode_group_spans.  stages: 1 counts the frames' symbols and sums them per group into
+// d_group_hist; 2 makes the groups' tables from d_group_hist as it is (d_specs, and the codes in the workspace); 4 codes the scans
+// with the codes the workspace holds.  The workspace is tstar_jpeg_encode_plan_opt's (optimize 1) for these n and slot_bytes.
+int tstar_jpeg_encode_scan_grp(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, const int32_t* h_group,
+                               const int32_t* h_span, const int32_t* d_group, const int32_t* d_span, int n_groups, int stages, uint32_t* d_group_hist, uint8_t* d_specs,
+                               uint8_t* d_out, size_t slot_bytes, uint32_t* d_lengths, int32_t* d_status, void* d_workspace,
+                               size_t workspace_bytes, void* stream) {
+    TSTAR_REQUIRE(d_coef && h_group && h_span && d_group && d_span && d_group_hist && d_specs && d_workspace && stages >= 1 && stages <= 7,
+                  "tstar_jpeg_encode_scan_grp: null argument or stages outside 1..7");
+    TSTAR_REQUIRE(!(stages & 4) || (d_out && d_lengths && d_status), "tstar_jpeg_encode_scan_grp: null argument");
+    TSTAR_REQUIRE((uintptr_t)d_group % 4 == 0 && (uintptr_t)d_span % 4 == 0 && (uintptr_t)d_group_hist % 4 == 0,
+                  "tstar_jpeg_encode_scan_grp: misaligned group arrays");
+    const JpegGeom g{W, H, 3, hs, vs};
+    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart, 1);
+    TSTAR_REQUIRE(!p.error, std::string("tstar_jpeg_encode_scan_grp: ") + (p.error ? p.error : ""));
+    std::vector<int32_t> span((size_t)2 * (n_groups > 0 ? n_groups : 1));
+    const char* bad = jpeg_enc_groups_check(h_group, n, n_groups, p.blocks, span.data());
+    TSTAR_REQUIRE(!bad, std::string("tstar_jpeg_encode_scan_grp: ") + (bad ? bad : ""));
+    TSTAR_REQUIRE(memcmp(span.data(), h_span, span.size() * sizeof(int32_t)) == 0,
+                  "tstar_jpeg_encode_scan_grp: the spans are not those of the groups (tstar_jpeg_encode_group_spans)");
+    GroupArgs ga;
+    ga.group = d_group; ga.span = d_span; ga.hist = d_group_hist; ga.n_groups = n_groups;
+    if (!(stages & 4)) {                                   // counts and tables alone: tstar_jpeg_encode_tables' way
+        TSTAR_REQUIRE((uintptr_t)d_workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
+                      "tstar_jpeg_encode_scan_grp: the workspace is misaligned or smaller than the plan's workspace_bytes");
+        EntropyArgs e = {};
+        e.coef = d_coef;
+        e.meta = (uint32_t*)((uint8_t*)d_workspace + p.off_meta);
+        e.sg = scan_geom(g);
+        e.blocks = (int)p.blocks;
+        TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), (hipStream_t)stream));
+        return launch_tables(p, n, e, restart, (jpegenc::HuffSpecWide*)d_specs, (uint8_t*)d_workspace, stages & 3, (hipStream_t)stream, &ga);
+    }
+    return jpeg_encode_scan_u8(d_coef, n, g, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes, nullptr,
+                               (hipStream_t)stream, (jpegenc::HuffSpecWide*)d_specs, &ga, stages);
 }
 
 int tstar_jpeg_encode_rst(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,

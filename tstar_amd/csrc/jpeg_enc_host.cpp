@@ -138,6 +138,28 @@ size_t jpeg_enc_header_opt(const JpegGeom& g, int quality, int restart, const jp
     return write_header(g, quant, restart, specs, out);
 }
 
+size_t jpeg_enc_header_tables_opt(const JpegGeom& g, const uint16_t* quant, int restart, const jpegenc::HuffSpecWide* specs, uint8_t* out) {
+    return write_header(g, quant, restart, specs, out);
+}
+
+const char* jpeg_enc_groups_check(const int32_t* group, int n, int n_groups, size_t blocks, int32_t* span) {
+    if (!group || n < 1 || n_groups < 1 || n_groups > n) return "no group, or more groups than frames";
+    const int most = jpeg_enc_group_frames(blocks);
+    int last = -1, members = 0;
+    for (int f = 0; f < n; ++f) {
+        const int g = group[f];
+        if (g == -1) continue;
+        if (g < 0 || g >= n_groups) return "a frame's group outside -1 .. n_groups - 1";
+        if (g != last && g != last + 1) return "the groups are not numbered in frame order without a gap";
+        if (g != last) { members = 0; if (span) span[2 * g] = f; }
+        if (++members > most) return "a group holds more frames than keep its counts within 1000000000";
+        if (span) span[2 * g + 1] = f + 1;
+        last = g;
+    }
+    if (last != n_groups - 1) return "a group without a frame";
+    return nullptr;
+}
+
 void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2) {
     const int real_bw = (g.W + 7) / 8, real_bh = (g.H + 7) / 8;
     for (int c = 0; c < 3; ++c) {
@@ -430,6 +452,107 @@ int tstar_jpeg_encode_scan_host_opt(const int16_t* coef, int n, int W, int H, in
         memcpy(specs + (size_t)i * sizeof(s), s, sizeof(s));
         lengths[i] = (uint32_t)len;
     });
+    return 0;
+}
+
+// Shared tables, host twin of tstar_jpeg_encode_scan_grp.  stages as there: 1 the frames' counts and their sums per group (into
+// group_hist), 2 the groups' tables from group_hist AS IT IS (a caller may have put counts of its own there), 4 the scans.
+int tstar_jpeg_encode_scan_host_grp(const int16_t* coef, int n, int W, int H, int hs, int vs, int restart, const int32_t* group,
+                                    int n_groups, int stages, uint32_t* group_hist, uint8_t* specs, uint8_t* out, size_t slot_bytes,
+                                    uint32_t* lengths, int32_t* status, int threads) {
+    const JpegGeom g{W, H, 3, hs, vs};
+    if (!coef || !group || !group_hist || !specs || n < 1 || stages < 1 || stages > 7 || !jpeg_enc_geom_ok(g) || !jpeg_enc_restart_ok(restart) ||
+        ((stages & 4) && (!lengths || !status || (!out && slot_bytes)))) {
+        set_error("tstar_jpeg_encode_scan_host_grp: null argument, empty batch, stages outside 1..7, unsupported geometry or restart interval outside 0..65535");
+        return 1;
+    }
+    std::vector<int32_t> span((size_t)2 * (n_groups > 0 ? n_groups : 1));
+    const char* bad = jpeg_enc_groups_check(group, n, n_groups, g.blocks(), span.data());
+    if (bad) { set_error(std::string("tstar_jpeg_encode_scan_host_grp: ") + bad); return 1; }
+    constexpr size_t kH = 4 * jpegenc::kHuffSymbols;
+    const size_t per = g.blocks() * 64;
+    if (stages & 1) {
+        std::vector<uint32_t> hist((size_t)n * kH, 0);
+        parallel_frames(n, threads, nullptr, nullptr, [&](int i, uint64_t*) {
+            if (group[i] >= 0) jpeg_enc_gather(coef + per * (size_t)i, g, restart, hist.data() + (size_t)i * kH);
+        });
+        for (int q = 0; q < n_groups; ++q) {                          // the frames of a group in order: the sums are exact
+            uint32_t* gh = group_hist + (size_t)q * kH;
+            memset(gh, 0, kH * sizeof(uint32_t));
+            for (int f = span[2 * q]; f < span[2 * q + 1]; ++f)
+                if (group[f] == q)
+                    for (size_t i = 0; i < kH; ++i) gh[i] += hist[(size_t)f * kH + i];
+        }
+    }
+    if (!(stages & 6)) return 0;
+    std::vector<jpegenc::HuffCodes> codes((size_t)4 * n_groups);
+    std::vector<jpegenc::HuffSpecWide> sp((size_t)4 * n_groups);
+    if (stages & 2) {
+        for (int q = 0; q < 4 * n_groups; ++q)
+            jpegenc::huff_optimal(group_hist + (size_t)(q / 4) * kH + (size_t)(q % 4) * jpegenc::kHuffSymbols, sp[q], codes[q], nullptr);
+        memcpy(specs, sp.data(), sp.size() * sizeof(jpegenc::HuffSpecWide));
+    } else {                                                          // the scans alone: with the tables the caller kept
+        memcpy(sp.data(), specs, sp.size() * sizeof(jpegenc::HuffSpecWide));
+        for (int q = 0; q < 4 * n_groups; ++q) jpegenc::huff_assign_codes(sp[q], codes[q]);
+    }
+    if (!(stages & 4)) return 0;
+    parallel_frames(n, threads, nullptr, nullptr, [&](int i, uint64_t*) {
+        lengths[i] = 0;
+        status[i] = JPEG_ENC_HUFF_OVERFLOW;
+        const int q = group[i];
+        if (q < 0) return;
+        bool overflow = false;
+        for (int t = 0; t < 4; ++t) overflow |= sp[(size_t)4 * q + t].status != jpegenc::HUFF_OK;
+        ByteSink sink;
+        const int rc = scan_frame(coef + per * (size_t)i, g, restart, sink, nullptr, nullptr, codes.data() + (size_t)4 * q);
+        if (rc != JPEG_ENC_OK) { status[i] = rc; return; }            // a coefficient without a code: before the tables' word, as per frame
+        if (overflow) return;
+        lengths[i] = (uint32_t)(sink.bytes.size() > 0xffffffffull ? 0xffffffffull : sink.bytes.size());
+        if (sink.bytes.size() > slot_bytes) { status[i] = JPEG_ENC_SHORT; return; }
+        memcpy(out + slot_bytes * (size_t)i, sink.bytes.data(), sink.bytes.size());
+        status[i] = JPEG_ENC_OK;
+    });
+    return 0;
+}
+
+// group i32 [n] -> span i32 [n_groups][2]: what the device entry wants next to the groups (and checks)
+int tstar_jpeg_encode_group_spans(const int32_t* group, int n, int n_groups, int W, int H, int hs, int vs, int32_t* span) {
+    const JpegGeom g{W, H, 3, hs, vs};
+    if (!span || !jpeg_enc_geom_ok(g)) { set_error("tstar_jpeg_encode_group_spans: null argument or unsupported geometry"); return 1; }
+    const char* bad = jpeg_enc_groups_check(group, n, n_groups, g.blocks(), span);
+    if (bad) { set_error(std::string("tstar_jpeg_encode_group_spans: ") + bad); return 1; }
+    return 0;
+}
+
+int tstar_jpeg_encode_group_frames(int W, int H, int hs, int vs) {
+    const JpegGeom g{W, H, 3, hs, vs};
+    if (!jpeg_enc_geom_ok(g)) { set_error("tstar_jpeg_encode_group_frames: unsupported geometry"); return 0; }
+    return jpeg_enc_group_frames(g.blocks());
+}
+
+int tstar_jpeg_encode_header_tables_opt(int W, int H, const uint16_t* quant, int hs, int vs, int restart, const uint8_t* specs, uint8_t* out,
+                                        size_t cap, size_t* len) {
+    const JpegGeom g{W, H, 3, hs, vs};
+    if (!out || !len || !quant || !specs || !jpeg_enc_geom_ok(g) || !jpeg_enc_restart_ok(restart)) {
+        set_error("tstar_jpeg_encode_header_tables_opt: null argument, unsupported geometry or restart interval outside 0..65535");
+        return 1;
+    }
+    for (int k = 0; k < 192; ++k)
+        if (quant[k] < 1) { set_error("tstar_jpeg_encode_header_tables_opt: a quantisation value of 0"); return 1; }
+    jpegenc::HuffSpecWide s[4];
+    memcpy(s, specs, sizeof(s));
+    for (int t = 0; t < 4; ++t) {
+        int sum = 0;
+        for (int i = 0; i < 16; ++i) sum += s[t].bits[i];
+        if (s[t].status != jpegenc::HUFF_OK || s[t].nvals < 1 || s[t].nvals > 256 || sum != s[t].nvals) {
+            set_error("tstar_jpeg_encode_header_tables_opt: a table without symbols, with a status, or whose lengths do not count its symbols");
+            return 1;
+        }
+    }
+    uint8_t buf[kJpegEncHeaderTablesOptMax];
+    *len = jpeg_enc_header_tables_opt(g, quant, restart, s, buf);
+    if (cap < *len) { set_error("tstar_jpeg_encode_header_tables_opt: the buffer is shorter than the header"); return 4; }
+    memcpy(out, buf, *len);
     return 0;
 }
 

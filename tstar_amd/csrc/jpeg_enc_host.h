@@ -109,6 +109,10 @@ size_t jpeg_enc_header_tables(const JpegGeom& g, const uint16_t* quant, int rest
 // the header of ONE frame coded with the four tables of `specs` (DC luma, AC luma, DC chroma, AC chroma): the layout above with
 // these tables in the DHT segments -> the bytes written, at most jpeg_enc_header_bytes(restart, 1)
 size_t jpeg_enc_header_opt(const JpegGeom& g, int quality, int restart, const jpegenc::HuffSpecWide* specs, uint8_t* out);
+// both: the DQT entries of jpeg_enc_header_tables AND the four tables of jpeg_enc_header_opt, for a file that is re-coded losslessly
+// with tables of its own -> the bytes written, at most kJpegEncHeaderTablesOptMax
+constexpr int kJpegEncHeaderTablesOptMax = kJpegEncHeaderOptMax + kJpegEncDriBytes + 69 + 3 * 64;
+size_t jpeg_enc_header_tables_opt(const JpegGeom& g, const uint16_t* quant, int restart, const jpegenc::HuffSpecWide* specs, uint8_t* out);
 
 // stage 1, one frame: rgb u8 [H][W][3] -> coef int16 [g.blocks()][64]; dummy2 (optional) += {right-edge, bottom-edge} dummy blocks
 void jpeg_enc_blocks(const uint8_t* rgb, const JpegGeom& g, const uint16_t* quant, int16_t* coef, uint64_t* dummy2);
@@ -129,5 +133,17 @@ int jpeg_enc_gather(const int16_t* coef, const JpegGeom& g, int restart, uint32_
 // hist (optional) u32 [4][257] out.  -> JPEG_ENC_*; with JPEG_ENC_HUFF_OVERFLOW *len is 0 and nothing is written.
 int jpeg_enc_scan_opt(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, jpegenc::HuffSpecWide* specs,
                       uint32_t* hist, uint64_t* counters, uint64_t* rst_counters);
+
+// Shared tables: the frames of a GROUP are coded with ONE set of four tables, built from the sum of their symbol counts (the DC
+// predictors restart with every frame, so the sum over frames is exact).  A group holds at most jpeg_enc_group_frames(blocks)
+// frames: a block emits at most 64 symbols, so the sums stay within kHuffMaxCount and the u32 bins cannot wrap.
+inline int jpeg_enc_group_frames(size_t blocks) {
+    const size_t n = (size_t)jpegenc::kHuffMaxCount / (blocks * 64);
+    return n < 1 ? 1 : (n > 0x7fffffff ? 0x7fffffff : (int)n);
+}
+// group i32 [n]: the group of every frame, -1 for a frame that is not coded (status JPEG_ENC_HUFF_OVERFLOW, length 0); the frames
+// of a group are consecutive but for such frames, and group numbers do not decrease.  -> nullptr, or what is wrong; span i32
+// [n_groups][2] out (optional): first frame and the frame behind the last of every group.
+const char* jpeg_enc_groups_check(const int32_t* group, int n, int n_groups, size_t blocks, int32_t* span);
 
 }  // namespace tstar

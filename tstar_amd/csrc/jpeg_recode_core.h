@@ -22,6 +22,9 @@ namespace jpegrec {
 
 enum { RECODE_NEW = 0, RECODE_KEPT = 1 };
 constexpr uint32_t kHeaderPitch = 1024;      // bytes of a row of the header table (the longest header: three 16-bit tables, DRI: 890)
+// Rows of the _opt entries: a header with tables of its own is up to 177 + 4 * 277 + 14 + 6 = 1305 bytes, a third quantisation table
+// and 16-bit entries add 69 + 3 * 64.  Their pitch is an argument: a multiple of 16 that holds the longest header of the piece.
+constexpr uint32_t kHeaderPitchOpt = 1568;
 
 // One frame of a piece, written by the host once the scan stage's lengths and statuses are known.
 struct RecodeDesc {
@@ -45,13 +48,14 @@ struct Source {                  // the batch the frames were decoded from
 };
 
 struct Scans {                   // what the scan stage wrote
-    const uint8_t* headers;      // [n_headers][kHeaderPitch]
+    const uint8_t* headers;      // [n_headers][header_pitch]
     const uint32_t* header_len;  // [n_headers]
     uint32_t n_headers;
+    uint32_t header_pitch;       // kHeaderPitch for the entries without an argument for it
     const uint8_t* slots;        // [m][slot_bytes], 16-byte aligned, slot_bytes a multiple of 16
     uint64_t slot_bytes;
     const uint32_t* scan_len;    // [m]
-    uint32_t restart, n_mcu;     // MCUs per interval, MCUs per frame
+    uint32_t restart, n_mcu;     // MCUs per interval (0, _opt entries only: none, the frame is one segment), MCUs per frame
 };
 
 struct Records {                 // views into the record buffer
@@ -91,7 +95,7 @@ inline void recode_views(uint8_t* buf, Records* r) {
     r->segments = reinterpret_cast<JpegSegment*>(buf + r->segments_at);
 }
 
-TSTAR_JPEG_HD inline uint32_t recode_intervals(uint32_t n_mcu, uint32_t restart) { return (n_mcu + restart - 1) / restart; }
+TSTAR_JPEG_HD inline uint32_t recode_intervals(uint32_t n_mcu, uint32_t restart) { return restart ? (n_mcu + restart - 1) / restart : 1u; }
 
 // What the host checks before any launch, on ITS copy of the descriptor: kinds, rows, source frames, segment counts and the exact
 // segment prefix.  nullptr, or what is wrong.
@@ -121,13 +125,15 @@ inline const char* recode_args(const void* h_desc, int m, int n_segments, const 
                                const uint8_t* slots, size_t slot_bytes, const uint32_t* scan_len, int restart, int n_mcu,
                                const uint8_t* src_bytes, size_t src_total, const uint16_t* src_quant, const void* src_frames,
                                const void* src_segments, int n_src_frames, int n_src_segments, uint8_t* rec, size_t rec_bytes, uint8_t* out,
-                               size_t out_bytes, Source* s, Scans* c, Records* r, Output* o) {
+                               size_t out_bytes, Source* s, Scans* c, Records* r, Output* o, size_t header_pitch = kHeaderPitch,
+                               int min_restart = 1) {
     if (!h_desc || !headers || !header_len || !slots || !scan_len || !src_bytes || !src_quant || !src_frames || !src_segments || !rec || !out)
         return "null argument";
     if (!recode_layout(m, n_segments, r)) return "m outside 1..65535 or n_segments < 0";
     if (rec_bytes < r->nbytes) return "the record buffer is shorter than tstar_jpeg_recode_layout says";
     if (n_headers <= 0 || n_src_frames <= 0 || n_src_segments < 0) return "no header or an empty source batch";
-    if (restart < 1 || restart > 65535 || n_mcu < 1) return "restart interval outside 1..65535 or no MCU";
+    if (restart < min_restart || restart > 65535 || n_mcu < 1) return "restart interval outside 1..65535 or no MCU";
+    if (header_pitch < 16 || header_pitch % 16 || header_pitch > 65536) return "header_pitch must be a multiple of 16 in 16..65536";
     if (slot_bytes < 16 || slot_bytes % 16 || slot_bytes >= (1ull << 31)) return "slot_bytes must be a multiple of 16 in 16..2^31-1";
     if (src_total >= (1ull << 32) || out_bytes >= (1ull << 32)) return "a piece addresses its bytes with 32 bits";
     if ((uintptr_t)rec % 16 || (uintptr_t)slots % 16 || (uintptr_t)headers % 16 || (uintptr_t)src_quant % 16 || (uintptr_t)h_desc % 4 ||
@@ -135,7 +141,7 @@ inline const char* recode_args(const void* h_desc, int m, int n_segments, const 
         return "misaligned buffer";
     s->bytes = src_bytes; s->total_bytes = src_total; s->quant = src_quant; s->frames = (const JpegFrameDesc*)src_frames;
     s->segments = (const JpegSegment*)src_segments; s->n_frames = (uint32_t)n_src_frames; s->n_segments = (uint32_t)n_src_segments;
-    c->headers = headers; c->header_len = header_len; c->n_headers = (uint32_t)n_headers; c->slots = slots; c->slot_bytes = slot_bytes;
+    c->headers = headers; c->header_len = header_len; c->n_headers = (uint32_t)n_headers; c->header_pitch = (uint32_t)header_pitch; c->slots = slots; c->slot_bytes = slot_bytes;
     c->scan_len = scan_len; c->restart = (uint32_t)restart; c->n_mcu = (uint32_t)n_mcu;
     recode_views(rec, r);
     o->bytes = out; o->cap = out_bytes;
@@ -147,7 +153,7 @@ inline const char* recode_args(const void* h_desc, int m, int n_segments, const 
 TSTAR_JPEG_HD inline bool recode_frame_ok(const RecodeDesc& d, uint32_t j, const Source& s, const Scans& c, const Records& r) {
     if (d.src >= s.n_frames || (uint64_t)d.first_segment + d.n_segments > r.n_segments) return false;
     if (d.kind == RECODE_NEW) {
-        if (d.hdr >= c.n_headers || c.header_len[d.hdr] > kHeaderPitch) return false;
+        if (d.hdr >= c.n_headers || c.header_len[d.hdr] > c.header_pitch) return false;
         const uint32_t n = c.scan_len[j];
         return n >= 2 && n <= c.slot_bytes && d.n_segments == recode_intervals(c.n_mcu, c.restart);
     }

@@ -37,7 +37,7 @@ void jpeg_recode_assemble_host(const RecodeDesc* desc, const Source& s, const Sc
         }
         const uint32_t hlen = c.header_len[d.hdr], n = c.scan_len[j];
         const uint8_t* scan = c.slots + (size_t)j * c.slot_bytes;
-        memcpy(o.bytes + r.off[j], c.headers + (size_t)d.hdr * kHeaderPitch, hlen);
+        memcpy(o.bytes + r.off[j], c.headers + (size_t)d.hdr * c.header_pitch, hlen);
         memcpy(o.bytes + r.off[j] + hlen, scan, n);
         for (uint32_t i = 0; i < d.n_segments; ++i) segs[i] = recode_new_segment(c, j, i, d.n_segments);
         segs[0].begin = base + hlen;
@@ -80,6 +80,22 @@ int tstar_jpeg_recode_assemble_host(const void* desc, int m, int n_segments, con
                                   src_total, src_quant, src_frames, src_segments, n_src_frames, n_src_segments, rec, rec_bytes, out, out_bytes,
                                   &s, &c, &r, &o);
     if (bad) { set_error(std::string("tstar_jpeg_recode_assemble_host: ") + bad); return 1; }
+    jpeg_recode_assemble_host((const RecodeDesc*)desc, s, c, r, o);
+    return 0;
+}
+
+// added entry: rows of header_pitch bytes (a multiple of 16; headers with tables of their own are longer than 1024 bytes), one row
+// per frame or per group of frames, and restart 0 (no DRI, no marker: a frame is one segment)
+int tstar_jpeg_recode_assemble_host_opt(const void* desc, int m, int n_segments, const uint8_t* headers, size_t header_pitch,
+                                        const uint32_t* header_len, int n_headers, const uint8_t* slots, size_t slot_bytes,
+                                        const uint32_t* scan_len, int restart, int n_mcu, const uint8_t* src_bytes, size_t src_total,
+                                        const uint16_t* src_quant, const void* src_frames, const void* src_segments, int n_src_frames,
+                                        int n_src_segments, uint8_t* rec, size_t rec_bytes, uint8_t* out, size_t out_bytes) {
+    Source s; Scans c; Records r; Output o;
+    const char* bad = recode_args(desc, m, n_segments, headers, header_len, n_headers, slots, slot_bytes, scan_len, restart, n_mcu, src_bytes,
+                                  src_total, src_quant, src_frames, src_segments, n_src_frames, n_src_segments, rec, rec_bytes, out, out_bytes,
+                                  &s, &c, &r, &o, header_pitch, 0);
+    if (bad) { set_error(std::string("tstar_jpeg_recode_assemble_host_opt: ") + bad); return 1; }
     jpeg_recode_assemble_host((const RecodeDesc*)desc, s, c, r, o);
     return 0;
 }

@@ -178,6 +178,26 @@ def header_from_specs(W: int, H: int, specs, quality: int = 75, subsampling="4:2
     return buf[:n.value].tobytes()
 
 
+def header_from_tables_specs(W: int, H: int, quant, specs, subsampling="4:2:0", restart: int = 0) -> bytes:
+    """tstar_jpeg_encode_header_tables_opt: SOI .. SOS of a file that is RE-CODED with tables of its own: ``header_from_tables``'s
+    layout (the source's DQT entries ``quant`` [3][64], SOF0 or SOF1, DRI when ``restart`` > 0) with the four tables of ``specs``
+    (SPEC_DTYPE [4]) in its DHT segments.  For the tables of a Pillow quality q the bytes are ``header_from_specs(W, H, specs, q,
+    subsampling, restart)``'s."""
+    from . import _lib
+    hs, vs = sampling(subsampling)
+    _, restart = _restart_values(None, restart)
+    q = np.ascontiguousarray(quant, dtype=np.int64).reshape(-1)
+    if q.size != 192 or q.min() < 1 or q.max() > 65535:
+        raise ValueError("header_from_tables_specs: expected quantisation tables [3][64] of values 1..65535")
+    q = q.astype(np.uint16)
+    sp = np.ascontiguousarray(specs, dtype=SPEC_DTYPE).reshape(4)
+    buf = np.empty(2048, dtype=np.uint8)
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().tstar_jpeg_encode_header_tables_opt(W, H, q.ctypes.data, hs, vs, restart, sp.ctypes.data, buf.ctypes.data, buf.size,
+                                                               C.byref(n)), "tstar_jpeg_encode_header_tables_opt")
+    return buf[:n.value].tobytes()
+
+
 def _check_tables(specs) -> None:
     """A table whose code sizes overflow is an error, never a fall-back to the standard tables."""
     if (np.asarray(specs["status"]) != HUFF_OK).any():
@@ -620,17 +640,23 @@ def save_mjpeg(store, path: str, quality: int = 90, subsampling="4:2:0", fps: Op
 
 # ------------------------------------------------------------------------------------------------ lossless re-coding
 def recode_frames(files: Sequence, restart_blocks: int = 8, device: bool = True, stats: Optional[dict] = None,
-                  chunk: Optional[int] = None) -> List[bytes]:
+                  chunk: Optional[int] = None, optimize: bool = False) -> List[bytes]:
     """Every JPEG of ``files`` (bytes or paths) with a restart interval of ``restart_blocks`` MCUs (1..65535), LOSSLESSLY: the
-    quantised coefficients and the quantisation tables are the file's own, only the entropy coding is new (the standard Huffman
-    tables, DRI / RSTn), so every decoder gives the pixels it gave before.  A file that is not re-coded comes back as it is:
-    grayscale, progressive, arithmetic, CMYK, a sampling the kernels do not cover, a file the decoder does not return OK for, or a
-    coefficient beyond the standard tables' size categories.  ``stats`` (optional dict) is added to: ``recoded``, ``kept``,
-    ``bytes_in``, ``bytes_out``.  A source with optimised Huffman tables grows by what the optimisation had saved: re-coding still
-    writes the standard tables (``encode_frames(optimize=True)`` builds per-frame tables from pixels, not from a file's coefficients).
-    ``device=False``: the host twin, which needs no GPU and gives the same bytes."""
+    quantised coefficients and the quantisation tables are the file's own, only the entropy coding is new (DRI / RSTn), so every
+    decoder gives the pixels it gave before.  A file that is not re-coded comes back as it is: grayscale, progressive, arithmetic,
+    CMYK, a sampling the kernels do not cover, a file the decoder does not return OK for, or a coefficient beyond the standard
+    tables' size categories.  ``stats`` (optional dict) is added to: ``recoded``, ``kept``, ``bytes_in``, ``bytes_out``.
+    ``optimize=False`` writes the standard Huffman tables: a source with optimised tables grows by what the optimisation had saved.
+    ``optimize=True`` is ``jpegtran -optimize -restart N``: every re-coded frame is coded with four tables built from ITS OWN symbol
+    counts (the procedure of ``encode_frames(optimize=True)`` on the file's coefficients) and carries them in its header; for a
+    Pillow-written source the result is byte for byte Pillow's ``optimize=True, restart_marker_blocks=N`` file.  ``restart_blocks=0``
+    is then allowed and means no DRI and no markers (``jpegtran -optimize``).  A frame whose optimal table would need a code longer
+    than 32 bits is kept and counted, as a lossless tool returns its input.  ``stats`` then gains ``optimized`` (frames coded with
+    tables of their own) and ``table_bytes`` (bytes of their DHT segments).  ``device=False``: the host twin, which needs no GPU and
+    gives the same bytes."""
     from . import jpeg_recode
-    restart = jpeg_recode.recode_interval(restart_blocks)
+    optimize = bool(optimize)
+    restart = jpeg_recode.recode_restart(restart_blocks, optimize)
     datas = []
     for f in files:
         if isinstance(f, (bytes, bytearray, memoryview)):
@@ -638,19 +664,28 @@ def recode_frames(files: Sequence, restart_blocks: int = 8, device: bool = True,
         else:
             with open(f, "rb") as fh:
                 datas.append(fh.read())
+    if not optimize:
+        if not device:
+            return jpeg_recode.recode_host(datas, restart, stats)
+        return jpeg_recode.recode_device(datas, restart, chunk=chunk, stats=stats)
     if not device:
-        return jpeg_recode.recode_host(datas, restart, stats)
-    return jpeg_recode.recode_device(datas, restart, chunk=chunk, stats=stats)
+        return jpeg_recode.recode_host(datas, restart, stats, optimize=True)
+    return jpeg_recode.recode_device(datas, restart, chunk=chunk, stats=stats, optimize=True)
 
 
-def recode_mjpeg(src, dst: str, restart_blocks: int = 8, device: bool = True, stats: Optional[dict] = None, piece: int = 1024) -> int:
+def recode_mjpeg(src, dst: str, restart_blocks: int = 8, device: bool = True, stats: Optional[dict] = None, piece: int = 1024,
+                 optimize: bool = False) -> int:
     """``src`` (a Motion-JPEG .avi, a .mjpeg / .mjpg stream or a folder of JPEG frames) re-coded losslessly (``recode_frames``) into
     ``dst`` (.avi, .mjpeg or .mjpg; an AVI of 1 GiB or more is refused, as ``save_mjpeg`` refuses it).  EVERY raw frame is carried
-    over, at the source's frame rate.  Returns the frames written."""
-    from . import jpeg
+    over, at the source's frame rate.  ``optimize``: ``recode_frames``' (per-frame tables; the output does not depend on ``piece``).
+    Returns the frames written."""
+    from . import jpeg, jpeg_recode
+    optimize = bool(optimize)
+    jpeg_recode.recode_restart(restart_blocks, optimize)
     s = jpeg.open_source(src)
     if s is None:
         raise ValueError(f"recode_mjpeg: {src!r}: expected a Motion-JPEG .avi, a .mjpeg / .mjpg stream or a folder of JPEG frames")
+    more = dict(optimize=True) if optimize else {}
     try:
         if s.n_frames < 1:
             raise ValueError(f"recode_mjpeg: {src!r} holds no frame")
@@ -660,7 +695,7 @@ def recode_mjpeg(src, dst: str, restart_blocks: int = 8, device: bool = True, st
         W, H = int(info[0]), int(info[1])
         files: List[bytes] = []
         for k0 in range(0, s.n_frames, piece):
-            files += recode_frames([s.read(i) for i in range(k0, min(s.n_frames, k0 + piece))], restart_blocks, device, stats)
+            files += recode_frames([s.read(i) for i in range(k0, min(s.n_frames, k0 + piece))], restart_blocks, device, stats, **more)
         fps = s.fps
     finally:
         s.close()

@@ -15,7 +15,17 @@ the lengths and statuses, then tstar_jpeg_recode_assemble builds the piece of th
 A frame is KEPT (its source bytes, not re-coded) and counted when the decoder routes it to the host or to Pillow (grayscale,
 progressive, arithmetic, CMYK, uncovered sampling, a device status that is not OK) or when the encoder's walk meets a coefficient or
 DC difference beyond the standard tables' categories.  A scan that does not fit its slot is coded again into the plan's worst-case
-slot: never dropped, never truncated.  The output always carries the standard Huffman tables, so a source with optimised tables grows.
+slot: never dropped, never truncated.  By default the output carries the standard Huffman tables, so a source with optimised tables
+grows.
+
+``optimize=True`` is the counterpart of ``jpegtran -optimize``: the output is coded with tables built from its own symbol counts by the
+procedure of ``jpeg_encode``.  PER FRAME (the file-to-file entries): tstar_jpeg_encode_scan_opt on the decoder's
+coefficients, every frame under a header with its own four DHT segments; an interval of 0 (no DRI, no marker) is then allowed.  SHARED
+(the compressed-resident arena, ``shared=True``): the OK frames of a chunk are cut, in order, into GROUPS of at most ``group_frames``
+frames; a group's counts are the sum of its frames' counts, its four tables come from that sum, and every frame of the group is coded
+with them and carries them (tstar_jpeg_encode_scan_grp) -- a decoder table set is 9016 bytes, more than tables of its own save a
+20 KB frame, and the arena needs one per group and quantisation set only.  A frame, or every frame of a group, whose optimal table
+would need a code longer than 32 bits is kept.
 """
 from __future__ import annotations
 
@@ -32,7 +42,9 @@ RECODE_DESC_DTYPE = np.dtype([("kind", "<u4"), ("hdr", "<u4"), ("src", "<u4"), (
                               ("first_segment", "<u4"), ("n_segments", "<u4")])
 NEW, KEPT = 0, 1
 HEADER_PITCH = 1024
+HEADER_PITCH_OPT = 1568            # rows of headers with tables of their own: at most 1566 bytes (csrc/jpeg_recode_core.h)
 STATS = ("recoded", "kept", "bytes_in", "bytes_out")
+GROUP_COUNT_LIMIT = 1_000_000_000  # what tstar_jpeg_huff_optimal and libjpeg's procedure are defined for
 PIECE_LIMIT = (1 << 32) - 16       # a piece addresses its bytes with 32 bits, like every batch of the entropy launchers
 RETRY_BYTES = 256 << 20            # slots of the worst case a retry holds at a time
 _SUBSAMPLING = {(2, 2): "4:2:0", (2, 1): "4:2:2", (1, 1): "4:4:4"}
@@ -45,6 +57,49 @@ def recode_interval(recode_blocks) -> int:
     if blocks < 1:
         raise ValueError(f"JPEG re-code interval {recode_blocks!r}: expected 1..{JE.RESTART_LIMIT} MCUs")
     return blocks
+
+
+def recode_restart(restart_blocks, optimize: bool = False) -> int:
+    """The interval of a file-to-file re-code: 1..65535 MCUs; 0 (no DRI, no marker) only together with ``optimize``."""
+    _, blocks = JE._restart_values(None, restart_blocks)
+    if blocks == 0 and optimize:
+        return 0
+    return recode_interval(restart_blocks)
+
+
+def recode_optimize_mode(recode_optimize=None) -> bool:
+    """The keyword when given, else TSTAR_JPEG_RECODE_OPTIMIZE ("1": on; "", "0": off)."""
+    if recode_optimize is not None:
+        return bool(recode_optimize)
+    v = os.environ.get("TSTAR_JPEG_RECODE_OPTIMIZE", "")
+    if v not in ("", "0", "1"):
+        raise ValueError(f"TSTAR_JPEG_RECODE_OPTIMIZE={v!r}: expected 0 or 1")
+    return v == "1"
+
+
+def group_limit(blocks: int) -> int:
+    """Frames a group holds at most: a block emits at most 64 symbols, so the group's counts stay within 10^9 (and within u32)."""
+    return max(1, GROUP_COUNT_LIMIT // (int(blocks) * 64))
+
+
+def make_groups(ok: np.ndarray, group_frames: int):
+    """The frames of a chunk with ``ok`` set, in order, cut into consecutive groups of at most ``group_frames`` -> (group int32 [n],
+    -1 where ``ok`` is not set; the number of groups)."""
+    ok = np.asarray(ok, dtype=bool)
+    group = np.full(len(ok), -1, dtype=np.int32)
+    rank = np.cumsum(ok) - 1
+    group[ok] = (rank[ok] // int(group_frames)).astype(np.int32)
+    return group, int(group.max()) + 1 if ok.any() else 0
+
+
+def _group_frames(group_frames, blocks: int) -> int:
+    limit = group_limit(blocks)
+    if group_frames is None:
+        return limit
+    g = int(group_frames)
+    if not 1 <= g <= limit:
+        raise ValueError(f"JPEG re-code: group_frames={group_frames!r}: expected 1..{limit} frames of {blocks} blocks")
+    return g
 
 
 def recode_mode(recode_blocks=None) -> int:
@@ -60,15 +115,21 @@ def recode_mode(recode_blocks=None) -> int:
     return recode_interval(recode_blocks)
 
 
-def new_stats() -> dict:
-    return {k: 0 for k in STATS}
+def new_stats(optimize: bool = False) -> dict:
+    """The counters of a re-code; ``optimize`` (the shared mode of an arena): ``optimized`` and ``table_sets`` too."""
+    return {k: 0 for k in STATS + (("optimized", "table_sets") if optimize else ())}
 
 
-def _count(stats: Optional[dict], kept: bool, n_in: int, n_out: int) -> None:
+def _count(stats: Optional[dict], kept: bool, n_in: int, n_out: int, table_bytes: Optional[int] = None) -> None:
+    """table_bytes: None without ``optimize`` (no key is added); else the bytes of the frame's DHT segments (0 for a kept frame)."""
     if stats is not None:
         stats["kept" if kept else "recoded"] = stats.get("kept" if kept else "recoded", 0) + 1
         stats["bytes_in"] = stats.get("bytes_in", 0) + int(n_in)
         stats["bytes_out"] = stats.get("bytes_out", 0) + int(n_out)
+        if table_bytes is not None:
+            stats["optimized"] = stats.get("optimized", 0) + (0 if kept else 1)
+            if "table_sets" not in stats:                   # the file-to-file entries; an arena counts its table sets instead
+                stats["table_bytes"] = stats.get("table_bytes", 0) + int(table_bytes)
 
 
 def recodable(geom) -> bool:
@@ -87,43 +148,163 @@ def covered(data: bytes):
 
 
 # ------------------------------------------------------------------------------------------------ host twin
-def recode_host(datas: Sequence[bytes], restart: int, stats: Optional[dict] = None) -> List[bytes]:
-    """Every file of ``datas`` re-coded with an interval of ``restart`` MCUs, or kept; files may differ in geometry."""
-    restart = recode_interval(restart)
-    out = []
-    for data in datas:
-        data = bytes(data)
-        new = _recode_one_host(data, restart)
-        _count(stats, new is None, len(data), len(data if new is None else new))
-        out.append(data if new is None else new)
+def recode_host(datas: Sequence[bytes], restart: int, stats: Optional[dict] = None, optimize: bool = False, shared: bool = False,
+                group_frames: Optional[int] = None, chunk: Optional[int] = None) -> List[bytes]:
+    """Every file of ``datas`` re-coded with an interval of ``restart`` MCUs, or kept; files may differ in geometry.  ``optimize``:
+    tables of the frame's own.  ``shared`` (with ``optimize``): the tables of its group, as the device path forms the groups -- the
+    files of one geometry, in order, in chunks of ``chunk`` frames (default: the entropy runner's), each chunk through
+    ``recode_host_chunk``."""
+    restart = recode_restart(restart, optimize)
+    if shared and not optimize:
+        raise ValueError("JPEG re-code: shared tables are optimised tables: shared=True needs optimize=True")
+    datas = [bytes(d) for d in datas]
+    if not shared:
+        out = []
+        for data in datas:
+            new = _recode_one_host(data, restart, optimize)
+            _count(stats, new is None, len(data), len(data if new is None else new), _table_bytes(new) if optimize else None)
+            out.append(data if new is None else new)
+        return out
+    if stats is not None:
+        stats.setdefault("table_sets", 0)
+    out: List[Optional[bytes]] = [None] * len(datas)
+    by_geom = {}
+    for i, d in enumerate(datas):
+        geom = covered(d)
+        if geom is None:
+            out[i] = d
+            _count(stats, True, len(d), len(d), 0)
+        else:
+            by_geom.setdefault(geom, []).append(i)
+    for geom, ids in by_geom.items():
+        blocks, _ = jpeg._sizes(geom)
+        step = jpeg.device_entropy_chunk(blocks, len(ids), chunk)
+        k0 = 0
+        while k0 < len(ids):
+            part = ids[k0:k0 + step]
+            part = part[:jpeg.device_entropy_take([len(datas[i]) for i in part])]
+            for i, f in zip(part, recode_host_chunk([datas[i] for i in part], geom, restart, group_frames, stats)):
+                out[i] = f
+            k0 += len(part)
     return out
 
 
-def _recode_one_host(data: bytes, restart: int) -> Optional[bytes]:
-    geom = covered(data)
-    if geom is None:
-        return None
+def _table_bytes(new: Optional[bytes]) -> int:
+    """Bytes of the four DHT segments of a file this module wrote (they follow each other in front of DRI / SOS); 0 for a kept frame."""
+    if new is None:
+        return 0
+    at = new.index(b"\xff\xc4")
+    n = 0
+    for _ in range(4):
+        n += 2 + int.from_bytes(new[at + n + 2:at + n + 4], "big")
+    return n
+
+
+def _decode_one_host(data: bytes, geom):
+    """(coef int16 [1, blocks * 64], quant uint16 [1, 192]) of a covered file, or None when the decoder does not return OK."""
     blocks, _ = jpeg._sizes(geom)
     coef = np.empty((1, blocks * 64), dtype=np.int16)
     quant = np.empty((1, 192), dtype=np.uint16)
     status, _ = jpeg.entropy_batch([data], geom, coef, quant, 1)
-    if status[0] != jpeg.OK:
+    return (coef, quant) if status[0] == jpeg.OK else None
+
+
+def _recode_one_host(data: bytes, restart: int, optimize: bool = False) -> Optional[bytes]:
+    geom = covered(data)
+    if geom is None:
         return None
-    return code_host(coef, quant, geom, restart)
+    dec = _decode_one_host(data, geom)
+    if dec is None:
+        return None
+    return code_host(dec[0], dec[1], geom, restart, optimize)
 
 
-def code_host(coef: np.ndarray, quant: np.ndarray, geom, restart: int) -> Optional[bytes]:
+def code_host(coef: np.ndarray, quant: np.ndarray, geom, restart: int, optimize: bool = False) -> Optional[bytes]:
     """The second half of the host twin: one frame's quantised coefficients (int16 [1, blocks * 64], the decoder's layout) and its
     quant rows (uint16 [192]) -> the file with the interval, or None when the encoder's walk meets a coefficient or DC difference of
-    a size category the standard tables have no code for (the frame is then kept)."""
+    a size category the standard tables have no code for, or (``optimize``) when a table of the frame's own overflows: the frame is
+    then kept."""
     W, H, _, hs, vs = geom
     sub = _SUBSAMPLING[(hs, vs)]
-    scans, _, st = JE.scan_host(coef, W, H, sub, threads=1, restart_blocks=restart)
-    if st[0] == JE.STATUS_BAD_COEF:
+    tables = {}
+    scans, _, st = JE.scan_host(coef, W, H, sub, threads=1, restart_blocks=restart, optimize=optimize, tables=tables)
+    if st[0] == JE.STATUS_BAD_COEF or (optimize and st[0] == JE.STATUS_HUFF_OVERFLOW):
         return None
     if st[0] != JE.STATUS_OK:
         raise RuntimeError("JPEG re-code (host): a scan did not fit the bound of its geometry")
-    return JE.header_from_tables(W, H, np.asarray(quant).reshape(3, 64), sub, restart) + scans[0]
+    q = np.asarray(quant).reshape(3, 64)
+    if optimize:
+        return JE.header_from_tables_specs(W, H, q, tables["specs"][0], sub, restart) + scans[0]
+    return JE.header_from_tables(W, H, q, sub, restart) + scans[0]
+
+
+def code_host_shared(coef: np.ndarray, geom, restart: int, group: np.ndarray, n_groups: int, counts: Optional[np.ndarray] = None):
+    """The group-coding step of the host twin (tstar_jpeg_encode_scan_host_grp): coef int16 [m, blocks * 64], ``group`` int32 [m]
+    (-1: not coded) -> (scans: bytes, or None for a frame that is kept; status int32 [m]; specs SPEC_DTYPE [n_groups, 4]; the groups'
+    counts uint32 [n_groups, 4, 257]).  ``counts``: counts to build the tables from INSTEAD of the frames' own sums (a seam for
+    tests: the overflow needs counts no picture of a testable size has)."""
+    from . import _lib
+    W, H, _, hs, vs = geom
+    coef = np.ascontiguousarray(coef, dtype=np.int16)
+    m = coef.shape[0]
+    p = JE.Plan(W, H, hs, vs, m, restart=restart, optimize=True)
+    assert coef.size == m * p.blocks * 64, "coefficients do not match the geometry"
+    group = np.ascontiguousarray(group, dtype=np.int32)
+    slot = p.max_scan_bytes
+    out = np.empty((m, slot), dtype=np.uint8)
+    lengths, status = np.zeros(m, dtype=np.uint32), np.full(m, -1, dtype=np.int32)
+    specs = np.zeros((n_groups, 4), dtype=JE.SPEC_DTYPE)
+    hist = np.zeros((n_groups, 4, JE.HIST_BINS), dtype=np.uint32)
+    stages = 7
+    if counts is not None:
+        hist[...] = np.asarray(counts, dtype=np.uint32).reshape(n_groups, 4, JE.HIST_BINS)
+        stages = 6
+    _lib.check(_lib.load().tstar_jpeg_encode_scan_host_grp(coef.ctypes.data, m, W, H, hs, vs, restart, group.ctypes.data, n_groups, stages,
+                                                           hist.ctypes.data, specs.ctypes.data, out.ctypes.data, slot, lengths.ctypes.data,
+                                                           status.ctypes.data, 1), "tstar_jpeg_encode_scan_host_grp")
+    if (status == JE.STATUS_SHORT).any():
+        raise RuntimeError("JPEG re-code (host): a scan did not fit the bound of its geometry")
+    return [out[i, :lengths[i]].tobytes() if status[i] == JE.STATUS_OK else None for i in range(m)], status, specs, hist
+
+
+def recode_host_chunk(datas: Sequence[bytes], geom, restart: int, group_frames: Optional[int] = None, stats: Optional[dict] = None,
+                      counts: Optional[np.ndarray] = None, info: Optional[dict] = None) -> List[bytes]:
+    """ONE chunk of the shared mode on the host: ``datas`` are the chunk's files (those of another geometry, or that the decoder does
+    not return OK for, are kept and belong to no group); the others, in order, form groups of at most ``group_frames`` (default: the
+    most the count bound allows).  ``info`` (optional dict) receives ``group``, ``specs``, ``hist`` and ``kept``."""
+    geom = tuple(int(v) for v in geom)
+    restart = recode_restart(restart, True)
+    W, H, _, hs, vs = geom
+    blocks, _ = jpeg._sizes(geom)
+    gf = _group_frames(group_frames, blocks)
+    if stats is not None:
+        stats.setdefault("table_sets", 0)
+    m = len(datas)
+    coef = np.zeros((m, blocks * 64), dtype=np.int16)
+    quant = np.zeros((m, 192), dtype=np.uint16)
+    ok = np.zeros(m, dtype=bool)
+    for j, d in enumerate(datas):
+        dec = _decode_one_host(d, geom) if covered(d) == geom else None
+        if dec is not None:
+            coef[j], quant[j], ok[j] = dec[0][0], dec[1][0], True
+    group, n_groups = make_groups(ok, gf)
+    out = [bytes(d) for d in datas]
+    kept = np.ones(m, dtype=bool)
+    specs = np.zeros((0, 4), dtype=JE.SPEC_DTYPE)
+    hist = np.zeros((0, 4, JE.HIST_BINS), dtype=np.uint32)
+    if n_groups:
+        scans, _, specs, hist = code_host_shared(coef, geom, restart, group, n_groups, counts)
+        for j, sc in enumerate(scans):
+            if sc is not None:
+                out[j] = JE.header_from_tables_specs(W, H, quant[j].reshape(3, 64), specs[group[j]], _SUBSAMPLING[(hs, vs)], restart) + sc
+                kept[j] = False
+    for j, d in enumerate(datas):
+        _count(stats, bool(kept[j]), len(d), len(out[j]), 0)
+    if stats is not None and "table_sets" in stats:
+        stats["table_sets"] += len({(int(group[j]), quant[j].tobytes()) for j in range(m) if not kept[j]})
+    if info is not None:
+        info.update(group=group, specs=specs, hist=hist, kept=kept)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ table sets
@@ -146,6 +327,32 @@ def recoded_table_set(src_set: np.ndarray) -> np.ndarray:
     double by the planner) are the source frame's."""
     ts = np.array(src_set, dtype=np.uint8).reshape(jpeg.TABLE_SET_BYTES)
     ts[:_HUFF_BYTES] = _std_huffman()
+    return ts
+
+
+_huffman_cache: dict = {}
+
+
+def huffman_of_specs(specs) -> np.ndarray:
+    """The six flat Huffman tables the planner makes of a file whose four DHT segments carry ``specs`` (SPEC_DTYPE [4]): planned from
+    a smallest file with exactly those segments, so they are ``jpeg.plan_segments``' of any output file that carries them."""
+    sp = np.ascontiguousarray(specs, dtype=JE.SPEC_DTYPE).reshape(4)
+    key = sp.tobytes()
+    if key not in _huffman_cache:
+        if len(_huffman_cache) >= 4096:
+            _huffman_cache.clear()
+        f = JE.header_from_specs(8, 8, sp, 75, "4:4:4") + b"\x00\xff\xd9"
+        plan = jpeg.plan_segments([f], (8, 8, 3, 1, 1))
+        if plan.route[0] != jpeg.ROUTE_DEVICE or plan.table_sets.shape != (1, jpeg.TABLE_SET_BYTES):
+            raise RuntimeError("JPEG re-code: the planner does not take the optimised tables of a group")
+        _huffman_cache[key] = plan.table_sets[0, :_HUFF_BYTES].copy()
+    return _huffman_cache[key]
+
+
+def optimized_table_set(src_set: np.ndarray, specs) -> np.ndarray:
+    """``recoded_table_set`` for a frame coded with the tables of ``specs``."""
+    ts = np.array(src_set, dtype=np.uint8).reshape(jpeg.TABLE_SET_BYTES)
+    ts[:_HUFF_BYTES] = huffman_of_specs(specs)
     return ts
 
 
@@ -172,12 +379,18 @@ class PieceDesc:
     (RECODE_DESC_DTYPE [m]), the header table, the output's table sets (in the planner's order: first appearance) and every frame's
     output length."""
 
-    def __init__(self, plan: jpeg.SegmentPlan, src_lens, a: int, b: int, kept: np.ndarray, scan_len: np.ndarray, geom, restart: int):
+    def __init__(self, plan: jpeg.SegmentPlan, src_lens, a: int, b: int, kept: np.ndarray, scan_len: np.ndarray, geom, restart: int,
+                 specs: Optional[np.ndarray] = None, spec_of: Optional[np.ndarray] = None):
+        """specs (SPEC_DTYPE [k, 4]) and spec_of (int [m]: the row of ``specs`` frame j is coded with): optimised tables; a header
+        row is then one per (tables, quantisation set), and rows are HEADER_PITCH_OPT bytes."""
         W, H, _, hs, vs = geom
         m = b - a
         self.m, self.restart = m, restart
         self.n_mcu = ((W + 8 * hs - 1) // (8 * hs)) * ((H + 8 * vs - 1) // (8 * vs))
-        n_int = (self.n_mcu + restart - 1) // restart
+        n_int = (self.n_mcu + restart - 1) // restart if restart else 1
+        self.pitch = HEADER_PITCH if specs is None else HEADER_PITCH_OPT
+        self.table_bytes = np.zeros(m, dtype=np.int64)
+        self.table_keys = set()                             # (tables, quantisation set) of the re-coded frames
         desc = np.zeros(m, dtype=RECODE_DESC_DTYPE)
         headers, sets, out_len = {}, {}, np.zeros(m, dtype=np.int64)
         self.header_bytes = []
@@ -193,11 +406,18 @@ class PieceDesc:
                 out_len[j] = int(src_lens[s])
             else:
                 qkey = plan.quant[s].tobytes()
+                if specs is not None:
+                    sp = specs[int(spec_of[j])]
+                    qkey = (int(spec_of[j]), qkey)
+                    self.table_keys.add(qkey)
+                    self.table_bytes[j] = 4 * 21 + int(sp["nvals"].sum())
                 if qkey not in headers:
                     headers[qkey] = len(self.header_bytes)
-                    self.header_bytes.append(JE.header_from_tables(W, H, plan.quant[s].reshape(3, 64), _SUBSAMPLING[(hs, vs)], restart))
+                    q = plan.quant[s].reshape(3, 64)
+                    self.header_bytes.append(JE.header_from_tables(W, H, q, _SUBSAMPLING[(hs, vs)], restart) if specs is None
+                                             else JE.header_from_tables_specs(W, H, q, sp, _SUBSAMPLING[(hs, vs)], restart))
                 d["kind"], d["hdr"], d["n_segments"] = NEW, headers[qkey], n_int
-                key = recoded_table_set(plan.table_sets[ts]).tobytes()
+                key = (recoded_table_set(plan.table_sets[ts]) if specs is None else optimized_table_set(plan.table_sets[ts], sp)).tobytes()
                 out_len[j] = len(self.header_bytes[d["hdr"]]) + int(scan_len[j])
             d["table_set"] = -1 if key is None else sets.setdefault(key, len(sets))
         desc["first_segment"] = np.cumsum(desc["n_segments"], dtype=np.int64) - desc["n_segments"]
@@ -206,7 +426,7 @@ class PieceDesc:
         self.table_sets = (np.stack([np.frombuffer(k, dtype=np.uint8) for k in sets]) if sets
                            else np.zeros((0, jpeg.TABLE_SET_BYTES), dtype=np.uint8))
         nh = max(1, len(self.header_bytes))
-        self.headers = np.zeros((nh, HEADER_PITCH), dtype=np.uint8)
+        self.headers = np.zeros((nh, self.pitch), dtype=np.uint8)
         self.header_len = np.zeros(nh, dtype=np.uint32)
         for k, h in enumerate(self.header_bytes):
             self.headers[k, :len(h)] = np.frombuffer(h, dtype=np.uint8)
@@ -237,11 +457,17 @@ def assemble_host(pd: PieceDesc, slots: np.ndarray, scan_len: np.ndarray, src_by
     scan_len = np.ascontiguousarray(scan_len, dtype=np.uint32)
     segs = plan.segments if len(plan.segments) else np.zeros(1, dtype=jpeg.SEGMENT_DTYPE)
     quant = _aligned16(plan.quant)
-    _lib.check(_lib.load().tstar_jpeg_recode_assemble_host(
-        pd.desc.ctypes.data, pd.m, pd.n_segments, _aligned16(pd.headers).ctypes.data, pd.header_len.ctypes.data, len(pd.header_len),
-        _aligned16(slots).ctypes.data, slots.shape[1], scan_len.ctypes.data, pd.restart, pd.n_mcu, src_bytes.ctypes.data, plan.total_bytes,
-        quant.ctypes.data, plan.frames.ctypes.data, segs.ctypes.data, len(plan.frames), len(plan.segments), rec.ctypes.data, rec.size,
-        out.ctypes.data, pd.total), "tstar_jpeg_recode_assemble_host")
+    tail = (_aligned16(slots).ctypes.data, slots.shape[1], scan_len.ctypes.data, pd.restart, pd.n_mcu, src_bytes.ctypes.data, plan.total_bytes,
+            quant.ctypes.data, plan.frames.ctypes.data, segs.ctypes.data, len(plan.frames), len(plan.segments), rec.ctypes.data, rec.size,
+            out.ctypes.data, pd.total)
+    if pd.pitch == HEADER_PITCH:
+        _lib.check(_lib.load().tstar_jpeg_recode_assemble_host(
+            pd.desc.ctypes.data, pd.m, pd.n_segments, _aligned16(pd.headers).ctypes.data, pd.header_len.ctypes.data, len(pd.header_len),
+            *tail), "tstar_jpeg_recode_assemble_host")
+    else:
+        _lib.check(_lib.load().tstar_jpeg_recode_assemble_host_opt(
+            pd.desc.ctypes.data, pd.m, pd.n_segments, _aligned16(pd.headers).ctypes.data, pd.pitch, pd.header_len.ctypes.data,
+            len(pd.header_len), *tail), "tstar_jpeg_recode_assemble_host_opt")
     return out[:pd.total], rec
 
 
@@ -269,21 +495,33 @@ class Piece:
 class DeviceRecoder:
     """Re-codes the chunks of one ``jpeg.EntropyRunner`` (frames of one geometry) on the current stream.  Owns the scan stage's
     buffers, reused chunk after chunk.  ``alloc(nbytes)`` hands out the output and record buffers (uint8 cuda tensors at 16-byte-
-    aligned addresses); the default is torch.empty."""
+    aligned addresses); the default is torch.empty.  ``optimize``: every frame coded with tables of its own
+    (tstar_jpeg_encode_scan_opt); with ``shared`` with the tables of its group of at most ``group_frames`` frames
+    (tstar_jpeg_encode_scan_grp).  Without ``optimize`` the launches, reads and bytes are those of the standard tables."""
 
-    def __init__(self, geom, device, restart: int, stats: Optional[dict] = None, alloc=None, slot_bytes: Optional[int] = None):
-        self.geom, self.device, self.restart = tuple(int(v) for v in geom), device, recode_interval(restart)
+    def __init__(self, geom, device, restart: int, stats: Optional[dict] = None, alloc=None, slot_bytes: Optional[int] = None,
+                 optimize: bool = False, shared: bool = False, group_frames: Optional[int] = None):
+        self.optimize, self.shared = bool(optimize), bool(shared)
+        if self.shared and not self.optimize:
+            raise ValueError("JPEG re-code: shared tables are optimised tables: shared=True needs optimize=True")
+        self.geom, self.device, self.restart = tuple(int(v) for v in geom), device, recode_restart(restart, self.optimize)
         if not recodable(self.geom):
             raise ValueError(f"JPEG re-code: geometry {self.geom} is not re-coded (three components at 4:2:0, 4:2:2 or 4:4:4 are); its frames are kept")
         self.stats = stats
         W, H, _, hs, vs = self.geom
-        one = JE.Plan(W, H, hs, vs, 1, restart=self.restart)
+        one = JE.Plan(W, H, hs, vs, 1, restart=self.restart, optimize=self.optimize)
         self.blocks = one.blocks
         self.max_slot = (one.max_scan_bytes + 15) // 16 * 16
         self.first_slot = None if slot_bytes is None else min(self.max_slot, max(16, (int(slot_bytes) + 15) // 16 * 16))
         self.alloc = alloc if alloc is not None else self._alloc
         self.bufs = None
         self.retried = 0
+        self.group_frames = _group_frames(group_frames, self.blocks) if self.shared else None
+        self.groups = None                                  # shared: (group int32 [n], n_groups, d_hist, d_specs) of the chunk in work
+        self.last_specs = None                              # optimize: the specs of the last piece (per frame) or chunk (per group)
+        self.table_keys = set()
+        if self.shared and stats is not None:
+            stats.setdefault("table_sets", 0)
 
     def _alloc(self, nbytes: int):
         import torch
@@ -294,15 +532,18 @@ class DeviceRecoder:
         if self.bufs is None or self.bufs[0] < m or self.bufs[1] != slot:
             self.bufs = None
             W, H, _, hs, vs = self.geom
-            p = JE.Plan(W, H, hs, vs, m, slot, self.restart)
+            p = JE.Plan(W, H, hs, vs, m, slot, self.restart, self.optimize)
             self.bufs = (m, slot, torch.empty(p.workspace_bytes, dtype=torch.uint8, device=self.device),
                          torch.empty((m, slot), dtype=torch.uint8, device=self.device),
-                         torch.empty((2, m), dtype=torch.int32, device=self.device))
+                         torch.empty((2, m), dtype=torch.int32, device=self.device),
+                         torch.empty((m, 4 * JE.SPEC_BYTES), dtype=torch.uint8, device=self.device) if self.optimize and not self.shared
+                         else None)
         return self.bufs[2:]
 
     def recode_chunk(self, batch: jpeg.DeviceBatch, d_buf, d_coef, bad) -> List[Piece]:
         """The chunk ``batch`` (uploaded into ``d_buf``, its coefficients in ``d_coef``; ``bad``: the frames the device did not
         return OK for) -> the pieces of the new arena, in order."""
+        import torch
         n = len(batch.datas)
         src_lens = np.fromiter((len(d) for d in batch.datas), dtype=np.int64, count=n)
         bad_mask = np.zeros(n, dtype=bool)
@@ -310,22 +551,69 @@ class DeviceRecoder:
         # the first pass: twice the longest source file (the standard tables cost a source with optimised ones a few per cent, a
         # marker with its padding at most 3 bytes per interval); frames it is short of are coded again at the bound
         slot = self.first_slot or min(self.max_slot, (2 * int(src_lens.max()) + 4096 + 15) // 16 * 16)
-        return self._pieces(batch, d_buf, d_coef, bad_mask, src_lens, 0, n, slot)
+        if self.shared:
+            group, n_groups = make_groups(~bad_mask, self.group_frames)
+            k = max(1, n_groups)
+            self.groups = (group, n_groups, torch.empty((k, 4 * JE.HIST_BINS), dtype=torch.int32, device=self.device),
+                           torch.empty((k, 4 * JE.SPEC_BYTES), dtype=torch.uint8, device=self.device))
+            self.last_specs = None
+        self.table_keys = set()                             # (group, quantisation set) of the chunk's re-coded frames, counted once
+        return self._pieces(batch, d_buf, d_coef, bad_mask, src_lens, 0, n, slot, True)
 
-    def _pieces(self, batch, d_buf, d_coef, bad_mask, src_lens, a: int, b: int, slot: int) -> List[Piece]:
+    def _scan(self, d_coef, a: int, m: int, slot: int, work, out, meta, d_specs, first: bool):
+        """The scan stage for frames [a, a + m) of the chunk -> (specs SPEC_DTYPE [k, 4] or None, spec_of int [m] or None)."""
         import torch
         from . import _lib
         lib = _lib.load()
         W, H, _, hs, vs = self.geom
-        m = b - a
-        work, out, meta = self._buffers(m, slot)
         s = _lib.stream_ptr()
-        _lib.check(lib.tstar_jpeg_encode_scan_rst(d_coef.data_ptr() + a * self.blocks * 128, m, W, H, hs, vs, self.restart, out.data_ptr(), slot,
-                                                  meta[0].data_ptr(), meta[1].data_ptr(), work.data_ptr(), work.numel(), None, s),
-                   "tstar_jpeg_encode_scan_rst")
-        meta_h = meta[:, :m].cpu().numpy()               # ONE read: lengths (u32 bits) and statuses
-        scan_len, status = meta_h[0].view(np.uint32).astype(np.int64), meta_h[1]
+        coef = d_coef.data_ptr() + a * self.blocks * 128
+        if not self.optimize:
+            _lib.check(lib.tstar_jpeg_encode_scan_rst(coef, m, W, H, hs, vs, self.restart, out.data_ptr(), slot, meta[0].data_ptr(),
+                                                      meta[1].data_ptr(), work.data_ptr(), work.numel(), None, s),
+                       "tstar_jpeg_encode_scan_rst")
+            return None, None
+        if not self.shared:
+            _lib.check(lib.tstar_jpeg_encode_scan_opt(coef, m, W, H, hs, vs, self.restart, out.data_ptr(), slot, meta[0].data_ptr(),
+                                                      meta[1].data_ptr(), d_specs.data_ptr(), work.data_ptr(), work.numel(), None, s),
+                       "tstar_jpeg_encode_scan_opt")
+            return None, np.arange(m)
+        group, n_groups, d_hist, d_gspecs = self.groups
+        sub = group[a:a + m]
+        if not (sub >= 0).any():
+            return None, sub                                # no frame of these has a group: all are kept, nothing is coded
+        g0, g1 = int(sub[sub >= 0].min()), int(sub.max()) + 1
+        local = np.where(sub >= 0, sub - g0, -1).astype(np.int32)
+        span = np.zeros((g1 - g0, 2), dtype=np.int32)
+        _lib.check(lib.tstar_jpeg_encode_group_spans(local.ctypes.data, m, g1 - g0, W, H, hs, vs, span.ctypes.data),
+                   "tstar_jpeg_encode_group_spans")
+        d_gs = torch.from_numpy(np.concatenate([local, span.reshape(-1)])).to(self.device)
+        # the first pass covers the whole chunk: counts, sums, tables, scans.  A later pass (a larger slot, or a part of the chunk)
+        # keeps the sums of the first: a group's tables do not depend on how the chunk is cut
+        stages = 7 if first else 6
+        _lib.check(lib.tstar_jpeg_encode_scan_grp(coef, m, W, H, hs, vs, self.restart, local.ctypes.data, span.ctypes.data, d_gs.data_ptr(),
+                                                  d_gs.data_ptr() + 4 * m, g1 - g0, stages, d_hist.data_ptr() + g0 * 16 * JE.HIST_BINS,
+                                                  d_gspecs.data_ptr() + g0 * 4 * JE.SPEC_BYTES, out.data_ptr(), slot, meta[0].data_ptr(),
+                                                  meta[1].data_ptr(), work.data_ptr(), work.numel(), s), "tstar_jpeg_encode_scan_grp")
+        return None, sub
+
+    def _pieces(self, batch, d_buf, d_coef, bad_mask, src_lens, a: int, b: int, slot: int, first: bool = False) -> List[Piece]:
+        import torch
+        from . import _lib
+        lib = _lib.load()
+        m = b - a
+        work, out, meta, d_specs = self._buffers(m, slot)
+        s = _lib.stream_ptr()
+        _, spec_of = self._scan(d_coef, a, m, slot, work, out, meta, d_specs, first)
+        coded = not self.shared or bool((spec_of >= 0).any())
+        if coded:
+            meta_h = meta[:, :m].cpu().numpy()           # ONE read: lengths (u32 bits) and statuses
+            scan_len, status = meta_h[0].view(np.uint32).astype(np.int64), meta_h[1]
+        else:
+            scan_len, status = np.zeros(m, dtype=np.int64), np.full(m, JE.STATUS_HUFF_OVERFLOW, dtype=np.int32)
         kept = bad_mask[a:b] | (status == JE.STATUS_BAD_COEF)
+        if self.optimize:
+            kept |= status == JE.STATUS_HUFF_OVERFLOW
         short = (status == JE.STATUS_SHORT) & ~kept
         if short.any():
             if slot >= self.max_slot:
@@ -334,7 +622,14 @@ class DeviceRecoder:
             step = max(1, min(m, RETRY_BYTES // self.max_slot))
             return [p for s0 in range(a, b, step)
                     for p in self._pieces(batch, d_buf, d_coef, bad_mask, src_lens, s0, min(b, s0 + step), self.max_slot)]
-        pd = PieceDesc(batch.plan, src_lens, a, b, kept, scan_len, self.geom, self.restart)
+        specs = None
+        if self.optimize and not self.shared:               # one more small read: the frames' tables
+            specs = self.last_specs = d_specs[:m].cpu().numpy().view(JE.SPEC_DTYPE).reshape(m, 4)
+        elif self.shared and coded:
+            if self.last_specs is None:                     # one more small read per chunk: the groups' tables
+                self.last_specs = self.groups[3][:self.groups[1]].cpu().numpy().view(JE.SPEC_DTYPE).reshape(self.groups[1], 4)
+            specs = self.last_specs
+        pd = PieceDesc(batch.plan, src_lens, a, b, kept, scan_len, self.geom, self.restart, specs, spec_of if specs is not None else None)
         if pd.total >= PIECE_LIMIT:
             if m == 1:
                 raise RuntimeError("JPEG re-code: one frame of 4 GiB")
@@ -346,14 +641,23 @@ class DeviceRecoder:
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).to(self.device)      # noqa: E731
         d_desc, d_headers, d_hlen = up(pd.desc), up(pd.headers), up(pd.header_len)
         base, parts, plan = d_buf.data_ptr(), batch.parts, batch.plan
-        _lib.check(lib.tstar_jpeg_recode_assemble(
-            pd.desc.ctypes.data, d_desc.data_ptr(), m, pd.n_segments, d_headers.data_ptr(), d_hlen.data_ptr(), len(pd.header_len),
-            out.data_ptr(), slot, meta[0].data_ptr(), self.restart, pd.n_mcu, base, batch.total, base + parts["quant"][0],
-            base + parts["frames"][0], base + parts["segments"][0], len(plan.frames), len(plan.segments), d_rec.data_ptr(), nrec,
-            d_out.data_ptr(), pd.total, int(pd.out_len.max()), s), "tstar_jpeg_recode_assemble")
+        tail = (out.data_ptr(), slot, meta[0].data_ptr(), self.restart, pd.n_mcu, base, batch.total, base + parts["quant"][0],
+                base + parts["frames"][0], base + parts["segments"][0], len(plan.frames), len(plan.segments), d_rec.data_ptr(), nrec,
+                d_out.data_ptr(), pd.total, int(pd.out_len.max()), s)
+        if not self.optimize:
+            _lib.check(lib.tstar_jpeg_recode_assemble(
+                pd.desc.ctypes.data, d_desc.data_ptr(), m, pd.n_segments, d_headers.data_ptr(), d_hlen.data_ptr(), len(pd.header_len), *tail),
+                "tstar_jpeg_recode_assemble")
+        else:
+            _lib.check(lib.tstar_jpeg_recode_assemble_opt(
+                pd.desc.ctypes.data, d_desc.data_ptr(), m, pd.n_segments, d_headers.data_ptr(), pd.headers.shape[1], d_hlen.data_ptr(),
+                len(pd.header_len), *tail), "tstar_jpeg_recode_assemble_opt")
         rec = d_rec[:nrec].cpu().numpy()                 # the records only: the bytes stay on the device
         for j in range(m):
-            _count(self.stats, bool(kept[j]), src_lens[a + j], pd.out_len[j])
+            _count(self.stats, bool(kept[j]), src_lens[a + j], pd.out_len[j], int(pd.table_bytes[j]) if self.optimize else None)
+        if self.shared and self.stats is not None:
+            self.stats["table_sets"] += len(pd.table_keys - self.table_keys)
+            self.table_keys |= pd.table_keys
         return [Piece(d_out[:pd.total], pd.plan_of(rec), pd.out_len.astype(np.uint32), kept, a)]
 
 
@@ -364,11 +668,15 @@ def runner_for(datas: Sequence[bytes], geom, device, chunk: Optional[int] = None
 
 
 def recode_device(datas: Sequence[bytes], restart: int, device="cuda", chunk: Optional[int] = None, stats: Optional[dict] = None,
-                  alloc=None, slot_bytes: Optional[int] = None, pieces_out: Optional[list] = None) -> List[bytes]:
+                  alloc=None, slot_bytes: Optional[int] = None, pieces_out: Optional[list] = None, optimize: bool = False,
+                  shared: bool = False, group_frames: Optional[int] = None) -> List[bytes]:
     """``recode_host`` through the device path: files of one geometry are entropy-decoded, re-coded and assembled together, chunk by
-    chunk, and only the finished pieces are read back.  ``pieces_out``: a list that receives (source files, Piece) of every piece."""
+    chunk, and only the finished pieces are read back.  ``pieces_out``: a list that receives (source files, Piece) of every piece.
+    ``optimize`` / ``shared`` / ``group_frames``: ``recode_host``'s."""
     import torch
-    restart = recode_interval(restart)
+    restart = recode_restart(restart, optimize)
+    if shared and stats is not None:
+        stats.setdefault("table_sets", 0)
     datas = [bytes(d) for d in datas]
     out: List[Optional[bytes]] = [None] * len(datas)
     groups = {}
@@ -376,7 +684,7 @@ def recode_device(datas: Sequence[bytes], restart: int, device="cuda", chunk: Op
         geom = covered(d)
         if geom is None:
             out[i] = d
-            _count(stats, True, len(d), len(d))
+            _count(stats, True, len(d), len(d), 0 if optimize else None)
         else:
             groups.setdefault(geom, []).append(i)
     with torch.cuda.device(device):
@@ -384,7 +692,7 @@ def recode_device(datas: Sequence[bytes], restart: int, device="cuda", chunk: Op
         for geom, ids in groups.items():
             files = [datas[i] for i in ids]
             run = runner_for(files, geom, device, chunk)
-            rec = DeviceRecoder(geom, device, restart, stats, alloc, slot_bytes)
+            rec = DeviceRecoder(geom, device, restart, stats, alloc, slot_bytes, optimize, shared, group_frames)
             k0 = 0
             while k0 < len(files):
                 part = run.read(k0)

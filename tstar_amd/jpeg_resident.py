@@ -247,7 +247,7 @@ def _entry_keys(src, want):
 
 
 def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optional[int] = None, chunk: Optional[int] = None,
-                  scale: int = 1, recode_blocks: Optional[int] = None):
+                  scale: int = 1, recode_blocks: Optional[int] = None, recode_optimize: bool = False, group_frames: Optional[int] = None):
     """Open ``src`` as a ``video.JpegFrameStore`` (see the module text).  The open is ``load_jpeg``'s device mode with another
     destination: the same ``jpeg.JpegOpen`` (prelude, host verdict, counters, messages) and the same ``jpeg.EntropyRunner`` (one upload
     per chunk carries the bytes and the records, the entropy kernels check every frame); here the bytes move on into the arena, and a
@@ -255,11 +255,18 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
     slots hold the frames at 1/scale size; the arena and the gather are those of the full-size store.  ``recode_blocks`` (MCUs, 1..65535;
     default: none): every chunk is re-coded losslessly with that restart interval while its coefficients are in HBM
     (``jpeg_recode.DeviceRecoder``), and the arena holds the re-coded bytes only: a fetch then decodes one lane per interval and
-    cuts nothing, whatever the file on disk looks like.  The store's ``recode_stats`` says how many frames were re-coded and kept."""
+    cuts nothing, whatever the file on disk looks like.  The store's ``recode_stats`` says how many frames were re-coded and kept.
+    ``recode_optimize`` (with ``recode_blocks``): the re-coded frames carry optimised Huffman tables, ONE set per group of the OK frames of
+    a chunk (``jpeg_recode``, shared mode; ``group_frames``: frames per group, default the most the count bound allows), so the arena
+    is smaller than the standard-table one and holds one decoder table set per group and quantisation set; ``recode_stats`` gains
+    ``optimized`` and ``table_sets``."""
     import torch
     from . import jpeg_recode
     from .video import JpegFrameStore
     restart = jpeg_recode.recode_interval(recode_blocks) if recode_blocks else 0
+    optimize = bool(recode_optimize)
+    if optimize and not restart:
+        raise ValueError("load_resident: recode_optimize optimises the tables of a re-coded arena: it needs recode_blocks")
     if str(device).startswith("cpu"):
         raise ValueError("resident='jpeg' needs a GPU store (device='cpu' was asked for)")
     P = pool_size(pool_frames)
@@ -272,7 +279,7 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
     ctx = jpeg.JpegOpen(src, raw, device, seconds=np.bincount(sec_entry, minlength=E), scale=scale)
     min_split = jpeg.split_min_bytes()
     sizes = [src.ranges[fi][1] for fi in raw] if getattr(src, "ranges", None) is not None and not restart else None
-    rstats = jpeg_recode.new_stats() if restart else None
+    rstats = (jpeg_recode.new_stats(True) if optimize else jpeg_recode.new_stats()) if restart else None
     rec, long_segments = None, False                    # long_segments: a fetch will cut intervals whose rounds no open has counted
     builder = ArenaBuilder()
     d_parts = []                                        # the arena's bytes, chunk by chunk, when the sizes are not known up front
@@ -304,7 +311,8 @@ def load_resident(src: jpeg.JpegFrames, device: str = "cuda", pool_frames: Optio
     # plain open's way and are counted
     recoding = bool(restart) and jpeg_recode.recodable(ctx.geom)
     if recoding:
-        rec = jpeg_recode.DeviceRecoder(ctx.geom, device, restart, rstats)
+        rec = (jpeg_recode.DeviceRecoder(ctx.geom, device, restart, rstats, optimize=True, shared=True, group_frames=group_frames) if optimize
+               else jpeg_recode.DeviceRecoder(ctx.geom, device, restart, rstats))
     stream = torch.cuda.current_stream()
     while e0 < E:
         datas = run.read(e0)

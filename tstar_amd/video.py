@@ -614,7 +614,7 @@ _SYN = re.compile(r"^synthetic://")
 
 def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_entropy: Optional[str] = None,
                resident: Optional[str] = None, pool_frames: Optional[int] = None, jpeg_scale: Optional[int] = None,
-               recode_blocks: Optional[int] = None) -> FrameStore:
+               recode_blocks: Optional[int] = None, recode_optimize: Optional[bool] = None) -> FrameStore:
     """``video``: a FrameStore, a ``synthetic://n=..,h=..,w=..,seed=..,fps=..`` URL, a folder of .jpg / .jpeg frames or a
     list of JPEG paths / bytes (``fps`` frames per second, default 1), a .mjpeg / .mjpg stream (``fps`` default 25), a
     Motion-JPEG .avi, or another file path (.y4m, the Pillow sequences; else decoded at native rate through decord, else
@@ -630,7 +630,11 @@ def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_en
     ``recode_blocks`` N (1..65535 MCUs; TSTAR_JPEG_RECODE when absent; default: none) with ``resident="jpeg"``: the arena is re-coded
     losslessly at open with a restart interval of N MCUs (``jpeg_recode``), so that a fetch decodes one lane per interval instead of
     cutting one long scan; pixels, ``jpeg_scale`` and every reader are unchanged, ``store.recode_stats`` counts the frames.  The
-    keyword without ``resident="jpeg"`` is a ValueError; the variable alone leaves a store that is not compressed-resident as it is."""
+    keyword without ``resident="jpeg"`` is a ValueError; the variable alone leaves a store that is not compressed-resident as it is.
+    ``recode_optimize=True`` (TSTAR_JPEG_RECODE_OPTIMIZE=1 when absent) with a re-coding open: the re-coded frames carry optimised
+    Huffman tables, one set per group of frames, so the arena shrinks instead of growing; ``store.recode_stats`` gains ``optimized``
+    and ``table_sets``.  The keyword without a re-coding open (``recode_blocks`` or TSTAR_JPEG_RECODE) is a ValueError; the variable
+    alone is then ignored."""
     if isinstance(video, FrameStore):
         return video
     from . import jpeg, jpeg_recode, jpeg_resident
@@ -639,6 +643,10 @@ def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_en
     if recode_blocks is not None and mode != "jpeg":
         raise ValueError(f"open_video: recode_blocks={recode_blocks!r} re-codes the arena of a compressed-resident store: it needs resident=\"jpeg\"")
     recode = jpeg_recode.recode_mode(recode_blocks) if mode == "jpeg" else 0
+    if recode_optimize and not recode:
+        raise ValueError(f"open_video: recode_optimize={recode_optimize!r} optimises the tables of a re-coded arena: it needs recode_blocks "
+                         "(or TSTAR_JPEG_RECODE) with resident=\"jpeg\"")
+    optimize = bool(recode) and jpeg_recode.recode_optimize_mode(recode_optimize)
     other_codec = None
     if not (isinstance(video, str) and _SYN.match(video)):
         try:
@@ -648,6 +656,8 @@ def open_video(video, device: str = "cuda", fps: Optional[float] = None, jpeg_en
         if src is not None:
             try:
                 if mode == "jpeg" and (resident is not None or not str(device).startswith("cpu")):
+                    if optimize:
+                        return jpeg_resident.load_resident(src, device, pool_frames, scale=scale, recode_blocks=recode, recode_optimize=True)
                     return jpeg_resident.load_resident(src, device, pool_frames, scale=scale, recode_blocks=recode or None)
                 return jpeg.load_jpeg(src, device, entropy=jpeg_entropy, scale=scale)
             finally:
