@@ -3,6 +3,7 @@ per-frame mode, a small DHT parser, and the groups' tables worked out from per-f
 
 Every JPEG is made at test time (``jpeg_recode_util``); nothing binary is committed.
 """
+import functools
 import io
 import os
 import sys
@@ -24,6 +25,25 @@ def pillow_optimized(rgb, sampling, quality, interval=0):
     if interval:
         kw["restart_marker_blocks"] = interval
     return U._save(Image.fromarray(rgb), **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def groups_of_one_cases():
+    """The smallest inputs on which tables per frame and tables shared by groups of ONE frame take every branch -> ((files, interval,
+    the per-frame files of the host twin, its stats), ...), worked out once: three different 48x48 4:2:0 frames at an interval of 2
+    (9 MCUs: 5 intervals, the last one short) with a grayscale file, which is kept and belongs to no group, among them; and one
+    24x16 4:4:4 frame without an interval (no DRI)."""
+    from tstar_amd import jpeg_recode as JR
+    cases = []
+    for files, n in (([U.source(48, 48, "420", "q75")[1], U.source(48, 48, "420", "gray")[1], U.source(48, 48, "420", "noise100")[1],
+                       U.source(48, 48, "420", "qtables", 1)[1]], 2), ([U.source(24, 16, "444", "q75")[1]], 0)):
+        stats = {}
+        cases.append((files, n, JR.recode_host(files, n, stats, optimize=True), stats))
+    return tuple(cases)
+
+
+def without(stats, key):
+    return {k: v for k, v in stats.items() if k != key}
 
 
 def pixels(data):

@@ -145,6 +145,47 @@ def test_a_coefficient_the_standard_tables_cannot_code_keeps_the_frame_on_the_de
     _assert_records_are_the_planners([(files, p)])
 
 
+def test_the_plain_assemble_entry_is_the_pitch_taking_one_at_1024():
+    """tstar_jpeg_recode_assemble forwards to tstar_jpeg_recode_assemble_opt with rows of 1024 bytes: a one-frame piece through both,
+    called directly, gives the same bytes (the host twin's file) and records; its own condition, an interval of at least 1, keeps
+    its name and launches nothing."""
+    from tstar_amd import _lib, jpeg_recode as JR
+    files = [U.source(24, 40, "444", "q75")[1]]
+    geom = JR.covered(files[0])
+    run = JR.runner_for(files, geom, "cuda")
+    ticket = run.submit(0, run.read(0), torch.cuda.current_stream())
+    assert run.collect(ticket) == []
+    batch, rec = ticket[1], JR.DeviceRecoder(geom, "cuda", 2)
+    slot = rec.max_slot
+    bufs = rec._buffers(1, slot)
+    assert rec._scan(run.d_coef, 0, 1, slot, bufs, True) is None
+    meta = bufs.meta[:, :1].cpu().numpy()
+    assert meta[1, 0] == 0
+    pd = JR.PieceDesc(batch.plan, [len(files[0])], 0, 1, np.zeros(1, bool), meta[0].view(np.uint32).astype(np.int64), geom, 2)
+    assert pd.pitch == JR.HEADER_PITCH == 1024
+    nrec, _ = JR.recode_layout(1, pd.n_segments)
+    up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).cuda()      # noqa: E731
+    d_desc, d_headers, d_hlen = up(pd.desc), up(pd.headers), up(pd.header_len)
+    base, parts, plan = run.d_buf.data_ptr(), batch.parts, batch.plan
+
+    def call(entry, pitch, restart):
+        alloc = GuardedAlloc()
+        d_out, d_rec = alloc(max(16, pd.total)), alloc(nrec)
+        _lib.check(getattr(_lib.load(), entry)(
+            pd.desc.ctypes.data, d_desc.data_ptr(), 1, pd.n_segments, d_headers.data_ptr(), *pitch, d_hlen.data_ptr(), len(pd.header_len),
+            bufs.out.data_ptr(), slot, bufs.meta[0].data_ptr(), restart, pd.n_mcu, base, batch.total, base + parts["quant"][0],
+            base + parts["frames"][0], base + parts["segments"][0], len(plan.frames), len(plan.segments), d_rec.data_ptr(), nrec,
+            d_out.data_ptr(), pd.total, int(pd.out_len.max()), _lib.stream_ptr()), entry)
+        alloc.check()
+        return d_out[:pd.total].cpu().numpy().tobytes(), d_rec.cpu().numpy().tobytes()
+
+    plain = call("tstar_jpeg_recode_assemble", (), 2)
+    assert plain == call("tstar_jpeg_recode_assemble_opt", (1024,), 2)
+    assert plain[0] == _host(files, 2)[0][0]
+    with pytest.raises(_lib.TStarHipError, match="tstar_jpeg_recode_assemble: restart interval outside 1..65535"):
+        call("tstar_jpeg_recode_assemble", (), 0)
+
+
 def test_the_recoder_refuses_a_geometry_it_does_not_code():
     from tstar_amd import jpeg_recode as JR
     for geom in ((64, 48, 1, 1, 1), (64, 48, 3, 4, 1)):

@@ -97,6 +97,19 @@ def test_device_recode_equals_the_host_twin_in_both_modes(case):
         assert np.array_equal(OU.pixels(a), OU.pixels(b))
 
 
+def test_the_per_frame_mode_is_the_shared_mode_with_groups_of_one():
+    """The device half of the host test of this name: tables per frame and tables shared by groups of one frame give the same
+    files, each other's and the host twin's, and the same stats but for the two keys that count tables."""
+    for files, n, want, want_stats in OU.groups_of_one_cases():
+        own, own_stats, pieces = _device(files, n)
+        _assert_records_are_the_planners(pieces)
+        shared, shared_stats, pieces = _device(files, n, shared=True, group_frames=1)
+        _assert_records_are_the_planners(pieces)
+        assert own == shared == want and own_stats == want_stats
+        assert OU.without(shared_stats, "table_sets") == OU.without(own_stats, "table_bytes")
+        assert shared_stats["table_sets"] == own_stats["optimized"] and "table_bytes" not in shared_stats and "table_sets" not in own_stats
+
+
 def test_files_of_two_geometries_in_one_call():
     files = U.batch(48, 48, "420") + U.batch(40, 24, "422") + [b"no jpeg at all"] + U.batch(48, 48, "420", with_kept=False)
     for kw in (dict(chunk=4), dict(shared=True, group_frames=5, chunk=7), dict(shared=True)):

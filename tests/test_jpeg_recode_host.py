@@ -192,6 +192,40 @@ def test_assembly_refuses_a_descriptor_that_does_not_tile():
             JR.assemble_host(pd, slots, lengths, buf, batch.plan)
 
 
+def test_the_plain_assembly_entry_is_the_pitch_taking_one_at_1024():
+    """tstar_jpeg_recode_assemble_host forwards to tstar_jpeg_recode_assemble_host_opt with rows of 1024 bytes: a one-frame piece
+    through both, called directly, gives the same bytes and records; its own condition, an interval of at least 1, keeps its name."""
+    from tstar_amd import _lib, jpeg, jpeg_encode as JE, jpeg_recode as JR
+    files = [U.source(24, 40, "444", "q75")[1]]
+    geom = JR.covered(files[0])
+    batch = jpeg.DeviceBatch(files, geom)
+    buf = np.zeros(batch.nbytes, dtype=np.uint8)
+    batch.fill(buf)
+    coef, _ = jpeg.entropy_segments_host(buf, batch.plan, geom)
+    scans, lengths, _ = JE.scan_host(coef, 24, 40, "4:4:4", slot_bytes=8192, restart_blocks=2)
+    slots = JR._aligned16(np.zeros((1, 8192), dtype=np.uint8))
+    slots[0, :len(scans[0])] = np.frombuffer(scans[0], dtype=np.uint8)
+    pd = JR.PieceDesc(batch.plan, [len(files[0])], 0, 1, np.zeros(1, bool), lengths, geom, 2)
+    assert pd.pitch == JR.HEADER_PITCH == 1024
+    nrec, _ = JR.recode_layout(1, pd.n_segments)
+    headers, quant, plan = JR._aligned16(pd.headers), JR._aligned16(batch.plan.quant), batch.plan
+
+    def call(entry, pitch, restart):
+        rec, out = JR._aligned16(np.zeros(nrec, dtype=np.uint8)), np.zeros(max(16, pd.total), dtype=np.uint8)
+        _lib.check(getattr(_lib.load(), entry)(
+            pd.desc.ctypes.data, 1, pd.n_segments, headers.ctypes.data, *pitch, pd.header_len.ctypes.data, len(pd.header_len),
+            slots.ctypes.data, slots.shape[1], lengths.ctypes.data, restart, pd.n_mcu, buf.ctypes.data, plan.total_bytes, quant.ctypes.data,
+            plan.frames.ctypes.data, plan.segments.ctypes.data, len(plan.frames), len(plan.segments), rec.ctypes.data, rec.size,
+            out.ctypes.data, pd.total), entry)
+        return out.tobytes(), rec.tobytes()
+
+    plain = call("tstar_jpeg_recode_assemble_host", (), 2)
+    assert plain == call("tstar_jpeg_recode_assemble_host_opt", (1024,), 2)
+    assert plain[0][:pd.total] == _recode(files, 2)[0][0]
+    with pytest.raises(_lib.TStarHipError, match="tstar_jpeg_recode_assemble_host: restart interval outside 1..65535"):
+        call("tstar_jpeg_recode_assemble_host", (), 0)
+
+
 def test_recode_mjpeg_carries_every_frame_and_the_rate(tmp_path, monkeypatch):
     from tstar_amd import jpeg, jpeg_encode as JE
     files = [U.source(48, 48, "420", name, seed)[1] for seed in (0, 1) for name in ("q75", "noise100", "gray")]

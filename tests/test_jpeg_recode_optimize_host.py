@@ -130,6 +130,23 @@ def test_shared_tables_are_the_optimal_tables_of_the_summed_counts(group_frames)
         assert out == _recode(files, n, optimize=True)[0]                 # groups of one frame: the per-frame files
 
 
+def test_the_per_frame_mode_is_the_shared_mode_with_groups_of_one():
+    """What the one scan stage rests on: a frame's own tables are the tables of a group that holds the frame alone.  File for file,
+    and every stats key but the two that say how tables are counted (bytes per frame, sets per arena)."""
+    from tstar_amd import jpeg_recode as JR
+    for files, n, want, want_stats in OU.groups_of_one_cases():
+        stats = {}
+        assert JR.recode_host(files, n, stats, optimize=True, shared=True, group_frames=1) == want
+        assert set(want_stats) - set(stats) == {"table_bytes"} and set(stats) - set(want_stats) == {"table_sets"}
+        assert OU.without(stats, "table_sets") == OU.without(want_stats, "table_bytes")
+        bare = {}                                                           # the chunk entry alone, from an empty dict: the same keys
+        assert JR.recode_host_chunk(files, JR.covered(files[0]), n, 1, bare) == want and bare == stats
+        gray = [JR.covered(f) is None for f in files]
+        assert want_stats.get("kept", 0) == sum(gray) and want_stats["optimized"] == stats["table_sets"] == len(files) - sum(gray)
+        assert [a == b for a, b in zip(want, files)] == gray                # the grayscale file alone comes back as it was
+        assert all(OU.markers(o) == (n, [k % 8 for k in range(4 if n else 0)]) for o, g in zip(want, gray) if not g)
+
+
 # ------------------------------------------------------------------------------------------------ 4. guards
 def test_a_group_whose_table_overflows_is_kept_whole():
     from tstar_amd import jpeg_encode as JE, jpeg_recode as JR

@@ -28,6 +28,7 @@ import sys
 import tempfile
 import time
 from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -117,21 +118,22 @@ def scan_times(path, reps=5):
 
     std = JR.DeviceRecoder(geom, "cuda", INTERVAL)
     bufs = std._buffers(n, slot)
-    out["standard"] = ms(lambda: std._scan(run.d_coef, 0, n, slot, *bufs, True))
+    out["standard"] = ms(lambda: std._scan(run.d_coef, 0, n, slot, bufs, True))
     rec = JR.DeviceRecoder(geom, "cuda", INTERVAL, optimize=True, shared=True)
     group, k = JR.make_groups(np.ones(n, dtype=bool), rec.group_frames)
-    rec.groups = (group, k, torch.empty((k, 4 * 257), dtype=torch.int32, device="cuda"), torch.empty((k, 4 * 276), dtype=torch.uint8, device="cuda"))
+    rec.groups = SimpleNamespace(group=group, n=k, d_hist=torch.empty((k, 4 * 257), dtype=torch.int32, device="cuda"),
+                                 d_specs=torch.empty((k, 4 * 276), dtype=torch.uint8, device="cuda"))
     bufs = rec._buffers(n, slot)
-    out["shared"] = ms(lambda: rec._scan(run.d_coef, 0, n, slot, *bufs, True))
+    out["shared"] = ms(lambda: rec._scan(run.d_coef, 0, n, slot, bufs, True))
     lib, W, H, hs, vs = _lib.load(), *geom[:2], *geom[3:]
     span = np.zeros((k, 2), dtype=np.int32)
     _lib.check(lib.tstar_jpeg_encode_group_spans(group.ctypes.data, n, k, W, H, hs, vs, span.ctypes.data), "tstar_jpeg_encode_group_spans")
     d_gs = torch.from_numpy(np.concatenate([group, span.reshape(-1)])).cuda()
-    work = bufs[0]
+    work = bufs.work
 
     def stage(stages):
         _lib.check(lib.tstar_jpeg_encode_scan_grp(run.d_coef.data_ptr(), n, W, H, hs, vs, INTERVAL, group.ctypes.data, span.ctypes.data, d_gs.data_ptr(),
-                                                  d_gs.data_ptr() + 4 * n, k, stages, rec.groups[2].data_ptr(), rec.groups[3].data_ptr(), None, slot, None,
+                                                  d_gs.data_ptr() + 4 * n, k, stages, rec.groups.d_hist.data_ptr(), rec.groups.d_specs.data_ptr(), None, slot, None,
                                                   None, work.data_ptr(), work.numel(), _lib.stream_ptr()), "tstar_jpeg_encode_scan_grp")
 
     out["counts_and_group_sums"] = ms(lambda: stage(1))

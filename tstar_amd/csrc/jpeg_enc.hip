@@ -27,6 +27,8 @@
 // [R]: only with a restart interval (jpeg_enc_math.h, "scan order").  The interval is an argument of the one scan launcher; the
 // kernels of the entropy stage and the stuffing passes take it as the compile-time parameter RST, so a scan without markers runs
 // none of the [R] steps and its kernels get no RestartArgs at all (RestartOf<false> is empty: there is nothing they could read).
+// Where the four code tables of a frame come from is the bits kernel's third compile-time parameter TAB, handled the same way:
+// TAB_STD reads the Annex K tables in constant memory and gets an empty StdTables.
 //
 // With optimised tables (Pillow's optimize=True; jpeg_enc_math.h, "optimised tables") two stages run in front of the entropy stage
 // and the two bits passes code with the frame's own tables; nothing is read back in between, and a scan with the standard tables
@@ -34,9 +36,10 @@
 //   tables         jpeg_enc_hist_kernel      the symbols of the block walk counted into the frame's four histograms [4][257]
 //                  jpeg_enc_tables_kernel    one wave per (frame, table): histogram -> HuffSpecWide (what the DHT segment needs) and
 //                                            HuffCodes (what the bits kernel needs), or a status
-//   entropy stage  jpeg_enc_bits_opt_kernel  the lane body of jpeg_enc_bits_kernel behind a staging of the frame's four code tables
+//   entropy stage  jpeg_enc_bits_kernel<WRITE, RST, TAB_FRAME>  the same lane body behind a staging of the frame's four code tables
 //                                            into LDS
-//   status         jpeg_enc_opt_status_kernel  a frame with a table that has a status (never written) reports JPEG_ENC_HUFF_OVERFLOW
+//   status         jpeg_enc_table_status_kernel<TAB_FRAME>  a frame with a table that has a status (never written) reports
+//                                            JPEG_ENC_HUFF_OVERFLOW
 //
 // With SHARED tables (tstar_jpeg_encode_scan_grp: the re-coding of a compressed-resident arena) the frames of a GROUP are coded with one
 // set of tables built from the sum of their counts; the launches above with
@@ -44,8 +47,8 @@
 //                                              stores the sum once (no atomics)
 //                  jpeg_enc_tables_kernel      one wave per (GROUP, table), on the sums
 //                  jpeg_enc_group_flag_kernel  the frames of a group with a status, and the frames without a group, are never written
-//   entropy stage  jpeg_enc_bits_grp_kernel    jpeg_enc_bits_opt_kernel with the tables of the frame's group (frame -> table-slot indirection)
-//   status         jpeg_enc_group_status_kernel
+//   entropy stage  jpeg_enc_bits_kernel<WRITE, RST, TAB_GROUP>  stages the tables of the frame's group (frame -> table-row indirection)
+//   status         jpeg_enc_table_status_kernel<TAB_GROUP>
 #include <string.h>
 
 #include <type_traits>
@@ -320,26 +323,63 @@ __device__ __forceinline__ void bits_lane(const EntropyArgs& a, const RestartOf<
     }
 }
 
-template <int WRITE, bool RST>
-__global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(EntropyArgs a, RestartOf<RST> r) {
-    bits_lane<WRITE, RST>(a, r, kDevTables.codes);
+// ------------------------------------------------------------------------------------------------ table source
+// The frames of a group are coded with ONE set of four tables, built from the sum of their counts.  group i32 [n]: a frame's group
+// (-1: not coded); span i32 [n_groups][2]: the first frame of a group and the frame behind its last.  Both come from the host, which
+// has checked its copy (jpeg_enc_groups_check); the kernels still trust neither: a group outside 0 .. n_groups - 1 counts as -1, a
+// span is clipped to the n frames.
+struct GroupArgs {
+    const int32_t* group;       // [n]
+    const int32_t* span;        // [n_groups][2]
+    uint32_t* hist;             // [n_groups][4][257]
+    int n_groups;
+};
+struct OwnRow {};               // what TAB_FRAME gets in its place: row f of a table array belongs to frame f
+
+// Where the four code tables of a frame come from: the Annex K ones in constant memory, row f of an array in HBM (the frame's own), or
+// the row of the frame's group.  RowsOf<TAB> maps a frame to its row (-1: none, only with groups); TablesOf<TAB> is what the bits
+// kernel gets: nothing at all, the codes pointer, or the codes pointer and the groups.
+constexpr int TAB_STD = 0, TAB_FRAME = 1, TAB_GROUP = 2;
+template <int TAB>
+using RowsOf = std::conditional_t<TAB == TAB_GROUP, GroupArgs, OwnRow>;
+template <class F>
+__device__ __forceinline__ F table_row(const OwnRow&, F f) { return f; }        // as it is: an unsigned index stays one
+__device__ __forceinline__ int table_row(const GroupArgs& ga, int f) {
+    const int g = ga.group[f];
+    return g >= 0 && g < ga.n_groups ? g : -1;
+}
+struct StdTables {};            // no member, as NoRestart
+template <int TAB>
+struct RowTables {
+    const jpegenc::HuffCodes* codes;                    // [rows][4]
+    [[no_unique_address]] RowsOf<TAB> rows;
+};
+template <int TAB>
+using TablesOf = std::conditional_t<TAB == TAB_STD, StdTables, RowTables<TAB>>;
+
+constexpr int kHist = jpegenc::kHuffSymbols;           // 257 bins per table
+constexpr uint32_t kTableWords = 4 * sizeof(jpegenc::HuffCodes) / 4;       // 768 dwords: a frame's four code tables
+
+// TAB_FRAME, TAB_GROUP: the workgroup stages the four tables of its frame's row in LDS (4 x 768 bytes) once.  A frame without a group
+// stages tables without a code (every length 0); it is flagged and never written.
+template <int WRITE, bool RST, int TAB>
+__global__ __launch_bounds__(256) void jpeg_enc_bits_kernel(EntropyArgs a, RestartOf<RST> r, TablesOf<TAB> t) {
+    if constexpr (TAB == TAB_STD) {
+        bits_lane<WRITE, RST>(a, r, kDevTables.codes);
+    } else {
+        __shared__ alignas(16) jpegenc::HuffCodes tab[4];
+        const auto row = table_row(t.rows, blockIdx.y);         // uniform over the workgroup
+        const bool none = TAB == TAB_GROUP && (int)row < 0;
+        const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(t.codes + (size_t)(none ? 0 : row) * 4);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(tab);
+        for (uint32_t i = threadIdx.x; i < kTableWords; i += 256) dst[i] = none ? 0u : src[i];
+        __syncthreads();
+        bits_lane<WRITE, RST>(a, r, tab);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ optimised tables
 // blocks -> histogram -> tables -> bits (count) -> offsets -> bits (write) -> stuffing; nothing is read back in between.
-constexpr int kHist = jpegenc::kHuffSymbols;           // 257 bins per table
-constexpr uint32_t kTableWords = 4 * sizeof(jpegenc::HuffCodes) / 4;       // 768 dwords: a frame's four code tables
-
-// The bits kernel coding with the frame's own tables: the workgroup stages them in LDS (4 x 768 bytes) once.
-template <int WRITE, bool RST>
-__global__ __launch_bounds__(256) void jpeg_enc_bits_opt_kernel(EntropyArgs a, RestartOf<RST> r, const jpegenc::HuffCodes* __restrict__ codes) {
-    __shared__ alignas(16) jpegenc::HuffCodes tab[4];
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(codes + (size_t)blockIdx.y * 4);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(tab);
-    for (uint32_t i = threadIdx.x; i < kTableWords; i += 256) dst[i] = src[i];
-    __syncthreads();
-    bits_lane<WRITE, RST>(a, r, tab);
-}
 
 // grid (ceil(blocks / 1024), n): a workgroup walks 1024 consecutive blocks of one frame's scan, four per lane, and counts their
 // symbols into histograms in LDS; the bins that are not zero are then added to the frame's (zeroed) hist [4][257].  Neighbouring
@@ -495,34 +535,25 @@ __global__ __launch_bounds__(64) void jpeg_enc_tables_kernel(const uint32_t* __r
     for (int i = lane; i < (int)(sizeof(tab) / 4); i += 64) co[i] = reinterpret_cast<const uint32_t*>(&tab)[i];
 }
 
-// one lane per frame, behind the stuffing passes: a frame with a table that has a status reports it, with length 0
-__global__ __launch_bounds__(256) void jpeg_enc_opt_status_kernel(const jpegenc::HuffSpecWide* __restrict__ specs, uint32_t* lengths, int32_t* status, int n) {
+// one lane per frame, behind the stuffing passes: a frame with a table that has a status reports it, with length 0; a frame without
+// a group reports JPEG_ENC_HUFF_OVERFLOW whatever lies in its coefficients
+template <int TAB>
+__global__ __launch_bounds__(256) void jpeg_enc_table_status_kernel(const jpegenc::HuffSpecWide* __restrict__ specs, RowsOf<TAB> rows, uint32_t* lengths,
+                                                                    int32_t* status, int n) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
+    const int row = table_row(rows, f);
+    const bool none = TAB == TAB_GROUP && row < 0;
     bool bad = false;
-    for (int t = 0; t < 4; ++t) bad |= specs[(size_t)f * 4 + t].status != jpegenc::HUFF_OK;
-    if (bad && status[f] != JPEG_ENC_BAD_COEF) {
+    if (!none)
+        for (int t = 0; t < 4; ++t) bad |= specs[(size_t)row * 4 + t].status != jpegenc::HUFF_OK;
+    if (none || (bad && status[f] != JPEG_ENC_BAD_COEF)) {
         lengths[f] = 0;
         status[f] = JPEG_ENC_HUFF_OVERFLOW;
     }
 }
 
 // ------------------------------------------------------------------------------------------------ shared tables (groups of frames)
-// The frames of a group are coded with ONE set of four tables, built from the sum of their counts.  group i32 [n]: a frame's group
-// (-1: not coded); span i32 [n_groups][2]: the first frame of a group and the frame behind its last.  Both come from the host, which
-// has checked its copy (jpeg_enc_groups_check); the kernels still trust neither: a group outside 0 .. n_groups - 1 counts as -1, a
-// span is clipped to the n frames.
-struct GroupArgs {
-    const int32_t* group;       // [n]
-    const int32_t* span;        // [n_groups][2]
-    uint32_t* hist;             // [n_groups][4][257]
-    int n_groups;
-};
-__device__ __forceinline__ int group_of(const GroupArgs& ga, int f) {
-    const int g = ga.group[f];
-    return g >= 0 && g < ga.n_groups ? g : -1;
-}
-
 // grid (ceil(4 * 257 / 256), n_groups): lane i adds bin i of the group's frames IN FRAME ORDER into a register and stores the sum once:
 // no atomic, no bin that two workgroups share (a video's EOB bin would otherwise take tens of thousands of atomics on one word),
 // and the integer sum is the same in every run.  Four loads are in flight per lane; neighbouring lanes read neighbouring words.
@@ -549,41 +580,11 @@ __global__ __launch_bounds__(256) void jpeg_enc_group_sum_kernel(const uint32_t*
 __global__ __launch_bounds__(256) void jpeg_enc_group_flag_kernel(const jpegenc::HuffSpecWide* __restrict__ specs, GroupArgs ga, uint32_t* meta, int n) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= n) return;
-    const int g = group_of(ga, f);
+    const int g = table_row(ga, f);
     bool bad = g < 0;
     if (!bad)
         for (int t = 0; t < 4; ++t) bad |= specs[(size_t)g * 4 + t].status != jpegenc::HUFF_OK;
     if (bad) atomicOr(meta + (size_t)f * 4 + META_FLAGS, (uint32_t)FLAG_SKIP);
-}
-
-// jpeg_enc_bits_opt_kernel with the tables of the frame's GROUP: a frame -> table-slot indirection in place of blockIdx.y * 4.  A
-// frame without a group stages tables without a code (every length 0); it is flagged and never written.
-template <int WRITE, bool RST>
-__global__ __launch_bounds__(256) void jpeg_enc_bits_grp_kernel(EntropyArgs a, RestartOf<RST> r, const jpegenc::HuffCodes* __restrict__ codes,
-                                                                GroupArgs ga) {
-    __shared__ alignas(16) jpegenc::HuffCodes tab[4];
-    const int g = group_of(ga, blockIdx.y);                 // uniform over the workgroup
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(codes + (size_t)(g < 0 ? 0 : g) * 4);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(tab);
-    for (uint32_t i = threadIdx.x; i < kTableWords; i += 256) dst[i] = g < 0 ? 0u : src[i];
-    __syncthreads();
-    bits_lane<WRITE, RST>(a, r, tab);
-}
-
-// one lane per frame, behind the stuffing passes: jpeg_enc_opt_status_kernel with the group's tables; a frame without a group
-// reports JPEG_ENC_HUFF_OVERFLOW whatever lies in its coefficients
-__global__ __launch_bounds__(256) void jpeg_enc_group_status_kernel(const jpegenc::HuffSpecWide* __restrict__ specs, GroupArgs ga, uint32_t* lengths,
-                                                                    int32_t* status, int n) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n) return;
-    const int g = group_of(ga, f);
-    bool bad = false;
-    if (g >= 0)
-        for (int t = 0; t < 4; ++t) bad |= specs[(size_t)g * 4 + t].status != jpegenc::HUFF_OK;
-    if (g < 0 || (bad && status[f] != JPEG_ENC_BAD_COEF)) {
-        lengths[f] = 0;
-        status[f] = JPEG_ENC_HUFF_OVERFLOW;
-    }
 }
 
 // In-place exclusive sum of data[0 .. count) by one workgroup of 256 lanes, tiles of 1024 with a running carry; every lane
@@ -825,21 +826,17 @@ int jpeg_encode_blocks_u8(const uint8_t* frames, int N, int H, int W, const int3
 
 namespace {
 
-// the six launches of the scan stage, with (RST) or without the interval-only steps; codes: the frames' own code tables
-// [n][4] (optimised tables), or null for the Annex K ones; ga: codes holds the GROUPS' tables [n_groups][4]
-template <bool RST>
-int launch_scan(const JpegEncPlan& p, int n, const EntropyArgs& e, const StuffArgs& a, const RestartOf<RST>& r, const jpegenc::HuffCodes* codes,
-                hipStream_t s, const GroupArgs* ga = nullptr) {
+// the six launches of the scan stage, with (RST) or without the interval-only steps, coding with the tables of TAB; tables that
+// can have a status (specs: theirs) get the status launch behind them
+template <bool RST, int TAB>
+int launch_scan(const JpegEncPlan& p, int n, const EntropyArgs& e, const StuffArgs& a, const RestartOf<RST>& r, const TablesOf<TAB>& t,
+                const jpegenc::HuffSpecWide* specs, hipStream_t s) {
     const dim3 egrid(p.entropy_wgs_x, (unsigned)n), sgrid(p.stuff_wgs_x, (unsigned)n);
-    if (ga) hipLaunchKernelGGL((jpeg_enc_bits_grp_kernel<0, RST>), egrid, dim3(256), 0, s, e, r, codes, *ga);
-    else if (codes) hipLaunchKernelGGL((jpeg_enc_bits_opt_kernel<0, RST>), egrid, dim3(256), 0, s, e, r, codes);
-    else hipLaunchKernelGGL((jpeg_enc_bits_kernel<0, RST>), egrid, dim3(256), 0, s, e, r);
+    hipLaunchKernelGGL((jpeg_enc_bits_kernel<0, RST, TAB>), egrid, dim3(256), 0, s, e, r, t);
     TSTAR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(jpeg_enc_offsets_kernel<RST>, dim3((unsigned)n), dim3(256), 0, s, e.bits, e.meta, e.blocks, a.slot_bytes, r);
     TSTAR_HIP_CHECK(hipGetLastError());
-    if (ga) hipLaunchKernelGGL((jpeg_enc_bits_grp_kernel<1, RST>), egrid, dim3(256), 0, s, e, r, codes, *ga);
-    else if (codes) hipLaunchKernelGGL((jpeg_enc_bits_opt_kernel<1, RST>), egrid, dim3(256), 0, s, e, r, codes);
-    else hipLaunchKernelGGL((jpeg_enc_bits_kernel<1, RST>), egrid, dim3(256), 0, s, e, r);
+    hipLaunchKernelGGL((jpeg_enc_bits_kernel<1, RST, TAB>), egrid, dim3(256), 0, s, e, r, t);
     TSTAR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((jpeg_enc_ff_kernel<0, RST>), sgrid, dim3(256), 0, s, a, r);
     TSTAR_HIP_CHECK(hipGetLastError());
@@ -847,12 +844,13 @@ int launch_scan(const JpegEncPlan& p, int n, const EntropyArgs& e, const StuffAr
     TSTAR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL((jpeg_enc_ff_kernel<1, RST>), sgrid, dim3(256), 0, s, a, r);
     TSTAR_HIP_CHECK(hipGetLastError());
+    if constexpr (TAB != TAB_STD) {
+        hipLaunchKernelGGL(jpeg_enc_table_status_kernel<TAB>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, t.rows, a.lengths, a.status, n);
+        TSTAR_HIP_CHECK(hipGetLastError());
+    }
     return TSTAR_OK;
 }
 
-}  // namespace
-
-namespace {
 // the two stages in front of an optimised scan: 1 counts (into the zeroed histograms), 2 tables (from the histograms as they are)
 // ga: stage 1 also sums the counts of every group's frames, stage 2 makes the tables of the GROUPS from those sums and flags the frames
 int launch_tables(const JpegEncPlan& p, int n, const EntropyArgs& e, int restart, jpegenc::HuffSpecWide* specs, uint8_t* ws, int stages,
@@ -881,19 +879,26 @@ int launch_tables(const JpegEncPlan& p, int n, const EntropyArgs& e, int restart
     }
     return TSTAR_OK;
 }
+// Where the code tables of a scan come from and which of its steps run.  specs null: the Annex K tables.  Else device HuffSpecWide out:
+// [n][4], every frame coded with tables of its own; with ga [n_groups][4], every frame with the tables of its group.  stages: 1 counts,
+// 2 tables (made from the histograms as they are), 4 scans (with the codes the workspace holds); the Annex K tables have the scans only.
+struct TableSource {
+    jpegenc::HuffSpecWide* specs = nullptr;
+    const GroupArgs* ga = nullptr;
+    int stages = 4;
+};
 }  // namespace
 
-// the scan stage with a restart interval of `restart` MCUs (0: none).  d_rst_counters: optional u32 [n][3], zeroed here.
-// specs: null codes with the Annex K tables; else device HuffSpecWide [n][4] out, and every frame is coded with tables of its own
-// ga: specs is [n_groups][4] and every frame is coded with the tables of its group; stages (1 counts, 2 tables, 4 scans) then says
-// which steps run: the tables are made from ga->hist as it is, the scans with the codes the workspace holds
-int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, int restart, uint8_t* out, size_t slot_bytes, uint32_t* lengths,
-                        int32_t* status, void* workspace, size_t workspace_bytes, uint32_t* d_rst_counters, hipStream_t s,
-                        jpegenc::HuffSpecWide* specs = nullptr, const GroupArgs* ga = nullptr, int stages = 7) {
-    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart, specs ? 1 : 0);
-    TSTAR_REQUIRE(!p.error, std::string("jpeg_encode_scan_u8: ") + (p.error ? p.error : ""));
+// The scan stage with a restart interval of `restart` MCUs (0: none), for the entry `who`: the one place that checks the plan and the
+// workspace and fills the kernels' arguments.  d_rst_counters: optional u32 [n][3], zeroed here.  Without stage 4 nothing of out,
+// lengths and status is used, and of the workspace only the flags are zeroed.
+int jpeg_encode_scan_u8(const char* who, const int16_t* coef, int n, const JpegGeom& g, int restart, uint8_t* out, size_t slot_bytes,
+                        uint32_t* lengths, int32_t* status, void* workspace, size_t workspace_bytes, uint32_t* d_rst_counters, hipStream_t s,
+                        const TableSource& t = {}) {
+    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart, t.specs ? 1 : 0);
+    TSTAR_REQUIRE(!p.error, std::string(who) + ": " + (p.error ? p.error : ""));
     TSTAR_REQUIRE((uintptr_t)workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
-                  "jpeg_encode_scan_u8: the workspace is misaligned or smaller than the plan's workspace_bytes");
+                  std::string(who) + ": the workspace is misaligned or smaller than the plan's workspace_bytes");
     uint8_t* ws = (uint8_t*)workspace;
     EntropyArgs e;
     e.coef = coef;
@@ -908,38 +913,33 @@ int jpeg_encode_scan_u8(const int16_t* coef, int n, const JpegGeom& g, int resta
     a.ff = (uint32_t*)(ws + p.off_ff);
     a.out = out; a.lengths = lengths; a.status = status;
     a.raw_words = (uint32_t)p.raw_words; a.ff_chunks = (uint32_t)p.ff_chunks; a.slot_bytes = (uint32_t)slot_bytes;
+    const bool scans = (t.stages & 4) != 0;
     // meta (flags) and the unstuffed stream start from zero: the stream is assembled by OR
     TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), s));
-    TSTAR_HIP_CHECK(hipMemsetAsync(e.raw, 0, (size_t)n * p.raw_words * sizeof(uint32_t), s));
-    if (d_rst_counters) TSTAR_HIP_CHECK(hipMemsetAsync(d_rst_counters, 0, (size_t)n * JPEG_ENC_R_COUNTERS * sizeof(uint32_t), s));
-    jpegenc::HuffCodes* codes = nullptr;
-    if (specs) {
-        codes = (jpegenc::HuffCodes*)(ws + p.off_codes);
-        if (stages & 3) RC(launch_tables(p, n, e, restart, specs, ws, stages & 3, s, ga));
-        if (ga && !(stages & 2)) {                         // the scans alone: the flags are those of the tables that were kept
-            hipLaunchKernelGGL(jpeg_enc_group_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, *ga, e.meta, n);
-            TSTAR_HIP_CHECK(hipGetLastError());
-        }
+    if (scans) TSTAR_HIP_CHECK(hipMemsetAsync(e.raw, 0, (size_t)n * p.raw_words * sizeof(uint32_t), s));
+    if (scans && d_rst_counters) TSTAR_HIP_CHECK(hipMemsetAsync(d_rst_counters, 0, (size_t)n * JPEG_ENC_R_COUNTERS * sizeof(uint32_t), s));
+    if (t.specs && (t.stages & 3)) RC(launch_tables(p, n, e, restart, t.specs, ws, t.stages & 3, s, t.ga));
+    if (!scans) return TSTAR_OK;
+    if (t.ga && !(t.stages & 2)) {                         // the scans alone: the flags are those of the tables that were kept
+        hipLaunchKernelGGL(jpeg_enc_group_flag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t.specs, *t.ga, e.meta, n);
+        TSTAR_HIP_CHECK(hipGetLastError());
     }
-    if (!(stages & 4)) return TSTAR_OK;
-    int rc;
-    if (restart == 0) {
-        rc = launch_scan<false>(p, n, e, a, NoRestart{}, codes, s, ga);
-    } else {
-        RestartArgs r;
-        r.seg = (uint32_t*)(ws + p.off_seg);
-        r.mark = (uint32_t*)(ws + p.off_mark);
-        r.counters = d_rst_counters;
-        r.interval = restart;
-        r.seg_blocks = restart * e.sg.per_mcu();       // at most 65535 * 6; at least the frame's blocks when there is no marker
-        r.markers = (uint32_t)p.markers;
-        rc = launch_scan<true>(p, n, e, a, r, codes, s, ga);
-    }
-    if (rc != TSTAR_OK || !specs) return rc;
-    if (ga) hipLaunchKernelGGL(jpeg_enc_group_status_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, *ga, lengths, status, n);
-    else hipLaunchKernelGGL(jpeg_enc_opt_status_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, specs, lengths, status, n);
-    TSTAR_HIP_CHECK(hipGetLastError());
-    return TSTAR_OK;
+    const jpegenc::HuffCodes* codes = (const jpegenc::HuffCodes*)(ws + p.off_codes);        // read with specs only
+    auto launch = [&](auto rst, const auto& r) {
+        constexpr bool RST = decltype(rst)::value;
+        if (t.ga) return launch_scan<RST, TAB_GROUP>(p, n, e, a, r, {codes, *t.ga}, t.specs, s);
+        if (t.specs) return launch_scan<RST, TAB_FRAME>(p, n, e, a, r, {codes, {}}, t.specs, s);
+        return launch_scan<RST, TAB_STD>(p, n, e, a, r, {}, nullptr, s);
+    };
+    if (restart == 0) return launch(std::false_type{}, NoRestart{});
+    RestartArgs r;
+    r.seg = (uint32_t*)(ws + p.off_seg);
+    r.mark = (uint32_t*)(ws + p.off_mark);
+    r.counters = d_rst_counters;
+    r.interval = restart;
+    r.seg_blocks = restart * e.sg.per_mcu();           // at most 65535 * 6; at least the frame's blocks when there is no marker
+    r.markers = (uint32_t)p.markers;
+    return launch(std::true_type{}, r);
 }
 
 }  // namespace tstar
@@ -977,33 +977,23 @@ int tstar_jpeg_encode_scan_rst(const int16_t* d_coef, int n, int W, int H, int h
                                uint32_t* d_lengths, int32_t* d_status, void* d_workspace, size_t workspace_bytes,
                                uint32_t* d_rst_counters, void* stream) {
     TSTAR_REQUIRE(d_coef && d_out && d_lengths && d_status && d_workspace, "tstar_jpeg_encode_scan_rst: null argument");
-    return jpeg_encode_scan_u8(d_coef, n, JpegGeom{W, H, 3, hs, vs}, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace,
-                               workspace_bytes, d_rst_counters, (hipStream_t)stream);
+    return jpeg_encode_scan_u8("tstar_jpeg_encode_scan_rst", d_coef, n, JpegGeom{W, H, 3, hs, vs}, restart, d_out, slot_bytes, d_lengths, d_status,
+                               d_workspace, workspace_bytes, d_rst_counters, (hipStream_t)stream);
 }
 
 int tstar_jpeg_encode_scan_opt(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, uint8_t* d_out, size_t slot_bytes,
                                uint32_t* d_lengths, int32_t* d_status, uint8_t* d_specs, void* d_workspace, size_t workspace_bytes,
                                uint32_t* d_rst_counters, void* stream) {
     TSTAR_REQUIRE(d_coef && d_out && d_lengths && d_status && d_specs && d_workspace, "tstar_jpeg_encode_scan_opt: null argument");
-    return jpeg_encode_scan_u8(d_coef, n, JpegGeom{W, H, 3, hs, vs}, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace,
-                               workspace_bytes, d_rst_counters, (hipStream_t)stream, (jpegenc::HuffSpecWide*)d_specs);
+    return jpeg_encode_scan_u8("tstar_jpeg_encode_scan_opt", d_coef, n, JpegGeom{W, H, 3, hs, vs}, restart, d_out, slot_bytes, d_lengths, d_status,
+                               d_workspace, workspace_bytes, d_rst_counters, (hipStream_t)stream, {(jpegenc::HuffSpecWide*)d_specs, nullptr, 7});
 }
 
 int tstar_jpeg_encode_tables(const int16_t* d_coef, int n, int W, int H, int hs, int vs, int restart, size_t slot_bytes, int stages,
                              uint8_t* d_specs, void* d_workspace, size_t workspace_bytes, void* stream) {
     TSTAR_REQUIRE(d_coef && d_specs && d_workspace && stages >= 1 && stages <= 3, "tstar_jpeg_encode_tables: null argument or stages outside 1..3");
-    const JpegGeom g{W, H, 3, hs, vs};
-    const JpegEncPlan p = plan_jpeg_encode(g, n, slot_bytes, restart, 1);
-    TSTAR_REQUIRE(!p.error, std::string("tstar_jpeg_encode_tables: ") + (p.error ? p.error : ""));
-    TSTAR_REQUIRE((uintptr_t)d_workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
-                  "tstar_jpeg_encode_tables: the workspace is misaligned or smaller than the plan's workspace_bytes");
-    EntropyArgs e = {};
-    e.coef = d_coef;
-    e.meta = (uint32_t*)((uint8_t*)d_workspace + p.off_meta);
-    e.sg = scan_geom(g);
-    e.blocks = (int)p.blocks;
-    TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), (hipStream_t)stream));
-    return launch_tables(p, n, e, restart, (jpegenc::HuffSpecWide*)d_specs, (uint8_t*)d_workspace, stages, (hipStream_t)stream);
+    return jpeg_encode_scan_u8("tstar_jpeg_encode_tables", d_coef, n, JpegGeom{W, H, 3, hs, vs}, restart, nullptr, slot_bytes, nullptr, nullptr,
+                               d_workspace, workspace_bytes, nullptr, (hipStream_t)stream, {(jpegenc::HuffSpecWide*)d_specs, nullptr, stages});
 }
 
 // Shared tables: frame f is coded with the four tables of group h_group[f] (d_group: the same array on the device; -1: the frame is
@@ -1029,19 +1019,8 @@ int tstar_jpeg_encode_scan_grp(const int16_t* d_coef, int n, int W, int H, int h
                   "tstar_jpeg_encode_scan_grp: the spans are not those of the groups (tstar_jpeg_encode_group_spans)");
     GroupArgs ga;
     ga.group = d_group; ga.span = d_span; ga.hist = d_group_hist; ga.n_groups = n_groups;
-    if (!(stages & 4)) {                                   // counts and tables alone: tstar_jpeg_encode_tables' way
-        TSTAR_REQUIRE((uintptr_t)d_workspace % 16 == 0 && workspace_bytes >= p.workspace_bytes,
-                      "tstar_jpeg_encode_scan_grp: the workspace is misaligned or smaller than the plan's workspace_bytes");
-        EntropyArgs e = {};
-        e.coef = d_coef;
-        e.meta = (uint32_t*)((uint8_t*)d_workspace + p.off_meta);
-        e.sg = scan_geom(g);
-        e.blocks = (int)p.blocks;
-        TSTAR_HIP_CHECK(hipMemsetAsync(e.meta, 0, (size_t)n * 4 * sizeof(uint32_t), (hipStream_t)stream));
-        return launch_tables(p, n, e, restart, (jpegenc::HuffSpecWide*)d_specs, (uint8_t*)d_workspace, stages & 3, (hipStream_t)stream, &ga);
-    }
-    return jpeg_encode_scan_u8(d_coef, n, g, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes, nullptr,
-                               (hipStream_t)stream, (jpegenc::HuffSpecWide*)d_specs, &ga, stages);
+    return jpeg_encode_scan_u8("tstar_jpeg_encode_scan_grp", d_coef, n, g, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace,
+                               workspace_bytes, nullptr, (hipStream_t)stream, {(jpegenc::HuffSpecWide*)d_specs, &ga, stages});
 }
 
 int tstar_jpeg_encode_rst(const uint8_t* d_frames, int N, int H, int W, const int32_t* d_idx, int n, int quality, int hs, int vs,
@@ -1051,7 +1030,7 @@ int tstar_jpeg_encode_rst(const uint8_t* d_frames, int N, int H, int W, const in
     const JpegGeom g{W, H, 3, hs, vs};
     TSTAR_REQUIRE(jpeg_enc_restart_ok(restart), "tstar_jpeg_encode_rst: restart interval outside 0..65535 MCUs");
     RC(jpeg_encode_blocks_u8(d_frames, N, H, W, d_idx, n, quality, g, d_coef, (hipStream_t)stream));
-    return jpeg_encode_scan_u8(d_coef, n, g, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes,
+    return jpeg_encode_scan_u8("tstar_jpeg_encode_rst", d_coef, n, g, restart, d_out, slot_bytes, d_lengths, d_status, d_workspace, workspace_bytes,
                                d_rst_counters, (hipStream_t)stream);
 }
 

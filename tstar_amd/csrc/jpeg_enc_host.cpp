@@ -239,7 +239,7 @@ struct ByteSink {                        // MSB-first bit writer with FF -> FF 0
 
 // the whole scan of one frame into sink.bytes; JPEG_ENC_OK or JPEG_ENC_BAD_COEF
 static int scan_frame(const int16_t* coef, const JpegGeom& g, int restart, ByteSink& sink, uint64_t* counters, uint64_t* rst_counters,
-                      const jpegenc::HuffCodes* codes = kTables.codes) {
+                      const jpegenc::HuffCodes* codes) {
     const jpegenc::ScanGeom sg = scan_geom(g);
     sink.bytes.reserve(g.blocks() * 16);
     uint64_t zrl = 0, no_eob = 0, rst = 0, pad_free = 0, pad_ff = 0;
@@ -274,15 +274,35 @@ static int scan_frame(const int16_t* coef, const JpegGeom& g, int restart, ByteS
     return bad ? JPEG_ENC_BAD_COEF : JPEG_ENC_OK;
 }
 
-int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, uint64_t* counters,
-                  uint64_t* rst_counters) {
+// One frame's scan, coded with `codes`, into `out` when it fits `cap` (out is not touched otherwise) -> the status; *len: the scan's
+// bytes; with JPEG_ENC_BAD_COEF 0 (the scan entries) or, `walked`, the bytes the walk made (the whole-file entries).  Every caller's
+// tail: what it adds is its own precedence of the tables' status.
+static int emit_scan(const int16_t* coef, const JpegGeom& g, int restart, const jpegenc::HuffCodes* codes, uint8_t* out, size_t cap, size_t* len,
+                     uint64_t* counters, uint64_t* rst_counters, bool walked = false) {
     ByteSink sink;
-    *len = 0;
-    if (scan_frame(coef, g, restart, sink, counters, rst_counters) != JPEG_ENC_OK) return JPEG_ENC_BAD_COEF;
-    *len = sink.bytes.size();
+    const int rc = scan_frame(coef, g, restart, sink, counters, rst_counters, codes);
+    *len = rc == JPEG_ENC_OK || walked ? sink.bytes.size() : 0;
+    if (rc != JPEG_ENC_OK) return JPEG_ENC_BAD_COEF;
     if (sink.bytes.size() > cap) return JPEG_ENC_SHORT;
     memcpy(out, sink.bytes.data(), sink.bytes.size());
     return JPEG_ENC_OK;
+}
+
+// emit_scan behind the `head` bytes of `header`, for the whole-file entries: the scan goes behind the header only when the whole file
+// fits, so a short slot is left as it was.  *length: header and walked bytes, whatever the status.  cnt: a worker's counters.
+static int emit_file(const int16_t* coef, const JpegGeom& g, int restart, const jpegenc::HuffCodes* codes, const uint8_t* header, size_t head,
+                     uint8_t* slot, size_t slot_bytes, uint32_t* length, uint64_t* cnt) {
+    const bool room = slot_bytes >= head;
+    size_t len = 0;
+    const int rc = emit_scan(coef, g, restart, codes, room ? slot + head : nullptr, room ? slot_bytes - head : 0, &len, cnt, cnt + JPEG_ENC_N_COUNTERS, true);
+    *length = (uint32_t)(head + len);
+    if (rc == JPEG_ENC_OK) memcpy(slot, header, head);     // OK means room: without it cap is 0, and a scan holds its EOI at least
+    return rc;
+}
+
+int jpeg_enc_scan(const int16_t* coef, const JpegGeom& g, int restart, uint8_t* out, size_t cap, size_t* len, uint64_t* counters,
+                  uint64_t* rst_counters) {
+    return emit_scan(coef, g, restart, kTables.codes, out, cap, len, counters, rst_counters);
 }
 
 int jpeg_enc_gather(const int16_t* coef, const JpegGeom& g, int restart, uint32_t* hist) {
@@ -314,13 +334,17 @@ int jpeg_enc_scan_opt(const int16_t* coef, const JpegGeom& g, int restart, uint8
     jpegenc::HuffCodes codes[4];
     *len = 0;
     const int rc = frame_tables(coef, g, restart, specs, codes, hist);
-    if (rc != JPEG_ENC_OK) return rc;
-    ByteSink sink;
-    if (scan_frame(coef, g, restart, sink, counters, rst_counters, codes) != JPEG_ENC_OK) return JPEG_ENC_BAD_COEF;
-    *len = sink.bytes.size();
-    if (sink.bytes.size() > cap) return JPEG_ENC_SHORT;
-    memcpy(out, sink.bytes.data(), sink.bytes.size());
-    return JPEG_ENC_OK;
+    return rc != JPEG_ENC_OK ? rc : emit_scan(coef, g, restart, codes, out, cap, len, counters, rst_counters);
+}
+
+// the four tables of a DHT-carrying header: no status, 1..256 symbols, lengths that count them
+static bool specs_ok(const jpegenc::HuffSpecWide s[4]) {
+    for (int t = 0; t < 4; ++t) {
+        int sum = 0;
+        for (int i = 0; i < 16; ++i) sum += s[t].bits[i];
+        if (s[t].status != jpegenc::HUFF_OK || s[t].nvals < 1 || s[t].nvals > 256 || sum != s[t].nvals) return false;
+    }
+    return true;
 }
 
 namespace {
@@ -420,13 +444,9 @@ int tstar_jpeg_encode_header_opt(int W, int H, int quality, int hs, int vs, int 
     }
     jpegenc::HuffSpecWide s[4];
     memcpy(s, specs, sizeof(s));
-    for (int t = 0; t < 4; ++t) {
-        int sum = 0;
-        for (int i = 0; i < 16; ++i) sum += s[t].bits[i];
-        if (s[t].status != jpegenc::HUFF_OK || s[t].nvals < 1 || s[t].nvals > 256 || sum != s[t].nvals) {
-            set_error("tstar_jpeg_encode_header_opt: a table without symbols, with a status, or whose lengths do not count its symbols");
-            return 1;
-        }
+    if (!specs_ok(s)) {
+        set_error("tstar_jpeg_encode_header_opt: a table without symbols, with a status, or whose lengths do not count its symbols");
+        return 1;
     }
     uint8_t buf[kJpegEncHeaderOptMax + kJpegEncDriBytes];
     *len = jpeg_enc_header_opt(g, quality, restart, s, buf);
@@ -503,14 +523,14 @@ int tstar_jpeg_encode_scan_host_grp(const int16_t* coef, int n, int W, int H, in
         if (q < 0) return;
         bool overflow = false;
         for (int t = 0; t < 4; ++t) overflow |= sp[(size_t)4 * q + t].status != jpegenc::HUFF_OK;
-        ByteSink sink;
-        const int rc = scan_frame(coef + per * (size_t)i, g, restart, sink, nullptr, nullptr, codes.data() + (size_t)4 * q);
-        if (rc != JPEG_ENC_OK) { status[i] = rc; return; }            // a coefficient without a code: before the tables' word, as per frame
-        if (overflow) return;
-        lengths[i] = (uint32_t)(sink.bytes.size() > 0xffffffffull ? 0xffffffffull : sink.bytes.size());
-        if (sink.bytes.size() > slot_bytes) { status[i] = JPEG_ENC_SHORT; return; }
-        memcpy(out + slot_bytes * (size_t)i, sink.bytes.data(), sink.bytes.size());
-        status[i] = JPEG_ENC_OK;
+        // a group whose tables have a status is walked too, into no slot: a coefficient without a code comes before the tables' word,
+        // as per frame
+        size_t len = 0;
+        const int rc = emit_scan(coef + per * (size_t)i, g, restart, codes.data() + (size_t)4 * q, overflow ? nullptr : out + slot_bytes * (size_t)i,
+                                 overflow ? 0 : slot_bytes, &len, nullptr, nullptr);
+        if (overflow && rc != JPEG_ENC_BAD_COEF) return;
+        lengths[i] = (uint32_t)(len > 0xffffffffull ? 0xffffffffull : len);
+        status[i] = rc;
     });
     return 0;
 }
@@ -541,13 +561,9 @@ int tstar_jpeg_encode_header_tables_opt(int W, int H, const uint16_t* quant, int
         if (quant[k] < 1) { set_error("tstar_jpeg_encode_header_tables_opt: a quantisation value of 0"); return 1; }
     jpegenc::HuffSpecWide s[4];
     memcpy(s, specs, sizeof(s));
-    for (int t = 0; t < 4; ++t) {
-        int sum = 0;
-        for (int i = 0; i < 16; ++i) sum += s[t].bits[i];
-        if (s[t].status != jpegenc::HUFF_OK || s[t].nvals < 1 || s[t].nvals > 256 || sum != s[t].nvals) {
-            set_error("tstar_jpeg_encode_header_tables_opt: a table without symbols, with a status, or whose lengths do not count its symbols");
-            return 1;
-        }
+    if (!specs_ok(s)) {
+        set_error("tstar_jpeg_encode_header_tables_opt: a table without symbols, with a status, or whose lengths do not count its symbols");
+        return 1;
     }
     uint8_t buf[kJpegEncHeaderTablesOptMax];
     *len = jpeg_enc_header_tables_opt(g, quant, restart, s, buf);
@@ -576,14 +592,7 @@ int tstar_jpeg_encode_host_opt(const uint8_t* frames, int N, int H, int W, const
         if (status[i] != JPEG_ENC_OK) return;
         uint8_t header[kJpegEncHeaderOptMax + kJpegEncDriBytes];
         const size_t head = write_header(g, q, restart, specs, header);
-        ByteSink sink;
-        status[i] = scan_frame(coef.data(), g, restart, sink, cnt, cnt + JPEG_ENC_N_COUNTERS, codes);
-        const size_t len = sink.bytes.size();
-        lengths[i] = (uint32_t)(head + len);
-        if (status[i] != JPEG_ENC_OK) return;
-        if (head + len > slot_bytes) { status[i] = JPEG_ENC_SHORT; return; }
-        memcpy(out + slot_bytes * (size_t)i, header, head);
-        memcpy(out + slot_bytes * (size_t)i + head, sink.bytes.data(), len);
+        status[i] = emit_file(coef.data(), g, restart, codes, header, head, out + slot_bytes * (size_t)i, slot_bytes, &lengths[i], cnt);
     });
     return 0;
 }
@@ -691,17 +700,7 @@ int tstar_jpeg_encode_host_rst(const uint8_t* frames, int N, int H, int W, const
     parallel_frames(n, threads, counters, rst_counters, [&](int i, uint64_t* cnt) {
         std::vector<int16_t> coef(per);
         jpeg_enc_blocks(frames + frame * (size_t)idx[i], g, q, coef.data(), cnt + JPEG_ENC_N_DUMMY_RIGHT);
-        uint8_t* slot = out + slot_bytes * (size_t)i;
-        // the scan goes behind the header only when the whole file fits: a short slot is left as it was
-        ByteSink sink;
-        const int rc = scan_frame(coef.data(), g, restart, sink, cnt, cnt + JPEG_ENC_N_COUNTERS);
-        const size_t len = sink.bytes.size();
-        lengths[i] = (uint32_t)(head + len);
-        status[i] = rc;
-        if (rc != JPEG_ENC_OK) return;
-        if (head + len > slot_bytes) { status[i] = JPEG_ENC_SHORT; return; }
-        memcpy(slot, header, head);
-        memcpy(slot + head, sink.bytes.data(), len);
+        status[i] = emit_file(coef.data(), g, restart, kTables.codes, header, head, out + slot_bytes * (size_t)i, slot_bytes, &lengths[i], cnt);
     });
     return 0;
 }

@@ -13,9 +13,9 @@
 //                               order, which ends interval k at its FF and starts interval k + 1 behind it
 // No load leaves the slot, the header row or the source frame it reads; no store leaves [off[j], off[j] + len[j]) below the
 // output's capacity, or the record buffer.  Plain vector stores only; nothing synchronises.
-// tstar_jpeg_recode_assemble_opt (frames coded with optimised tables) runs the same three kernels with header rows of a pitch the caller
-// gives (a header with tables of its own exceeds 1024 bytes; a row per frame, or per group of frames and quantisation set) and takes an
-// interval of 0: no marker, one segment, which the marker pass finds by finding nothing.
+// tstar_jpeg_recode_assemble_opt is the one launcher: header rows of a pitch the caller gives (a header with tables of its own exceeds
+// 1024 bytes; a row per frame, or per group of frames and quantisation set) and any interval, 0 among them: no marker, one segment,
+// which the marker pass finds by finding nothing.  tstar_jpeg_recode_assemble forwards to it with rows of 1024 bytes and an interval.
 #include "common.h"
 #include "jpeg_recode_core.h"
 #include "jpeg_vec_copy.h"
@@ -175,16 +175,14 @@ extern "C" int tstar_jpeg_recode_assemble(const void* h_desc, const void* d_desc
                                           const uint16_t* d_src_quant, const void* d_src_frames, const void* d_src_segments, int n_src_frames,
                                           int n_src_segments, uint8_t* d_rec, size_t rec_bytes, uint8_t* d_out, size_t out_bytes,
                                           size_t longest, void* stream) {
-    jpegrec::Source s; jpegrec::Scans c; jpegrec::Records r; jpegrec::Output o;
-    const char* bad = jpegrec::recode_args(h_desc, m, n_segments, d_headers, d_header_len, n_headers, d_slots, slot_bytes, d_scan_len, restart,
-                                           n_mcu, d_src_bytes, src_total, d_src_quant, d_src_frames, d_src_segments, n_src_frames,
-                                           n_src_segments, d_rec, rec_bytes, d_out, out_bytes, &s, &c, &r, &o);
-    TSTAR_REQUIRE(!bad, std::string("tstar_jpeg_recode_assemble: ") + bad);
-    TSTAR_REQUIRE(d_desc && (uintptr_t)d_desc % 4 == 0, "tstar_jpeg_recode_assemble: null or misaligned device descriptor");
-    return jpeg_recode_assemble((const jpegrec::RecodeDesc*)d_desc, s, c, r, o, longest, (hipStream_t)stream);
+    // the entry of the standard tables: rows of kHeaderPitch bytes and always an interval; the rest is the _opt entry's
+    TSTAR_REQUIRE(restart >= 1, "tstar_jpeg_recode_assemble: restart interval outside 1..65535 or no MCU");
+    return tstar_jpeg_recode_assemble_opt(h_desc, d_desc, m, n_segments, d_headers, jpegrec::kHeaderPitch, d_header_len, n_headers, d_slots, slot_bytes,
+                                          d_scan_len, restart, n_mcu, d_src_bytes, src_total, d_src_quant, d_src_frames, d_src_segments, n_src_frames,
+                                          n_src_segments, d_rec, rec_bytes, d_out, out_bytes, longest, stream);
 }
 
-// added entry: rows of header_pitch bytes and restart 0, as tstar_jpeg_recode_assemble_host_opt
+// rows of header_pitch bytes and restart 0 allowed, as tstar_jpeg_recode_assemble_host_opt
 extern "C" int tstar_jpeg_recode_assemble_opt(const void* h_desc, const void* d_desc, int m, int n_segments, const uint8_t* d_headers,
                                               size_t header_pitch, const uint32_t* d_header_len, int n_headers, const uint8_t* d_slots,
                                               size_t slot_bytes, const uint32_t* d_scan_len, int restart, int n_mcu,
@@ -195,7 +193,7 @@ extern "C" int tstar_jpeg_recode_assemble_opt(const void* h_desc, const void* d_
     jpegrec::Source s; jpegrec::Scans c; jpegrec::Records r; jpegrec::Output o;
     const char* bad = jpegrec::recode_args(h_desc, m, n_segments, d_headers, d_header_len, n_headers, d_slots, slot_bytes, d_scan_len, restart,
                                            n_mcu, d_src_bytes, src_total, d_src_quant, d_src_frames, d_src_segments, n_src_frames,
-                                           n_src_segments, d_rec, rec_bytes, d_out, out_bytes, &s, &c, &r, &o, header_pitch, 0);
+                                           n_src_segments, d_rec, rec_bytes, d_out, out_bytes, &s, &c, &r, &o, header_pitch);
     TSTAR_REQUIRE(!bad, std::string("tstar_jpeg_recode_assemble_opt: ") + bad);
     TSTAR_REQUIRE(d_desc && (uintptr_t)d_desc % 4 == 0, "tstar_jpeg_recode_assemble_opt: null or misaligned device descriptor");
     return jpeg_recode_assemble((const jpegrec::RecodeDesc*)d_desc, s, c, r, o, longest, (hipStream_t)stream);

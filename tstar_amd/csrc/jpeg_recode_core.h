@@ -125,14 +125,13 @@ inline const char* recode_args(const void* h_desc, int m, int n_segments, const 
                                const uint8_t* slots, size_t slot_bytes, const uint32_t* scan_len, int restart, int n_mcu,
                                const uint8_t* src_bytes, size_t src_total, const uint16_t* src_quant, const void* src_frames,
                                const void* src_segments, int n_src_frames, int n_src_segments, uint8_t* rec, size_t rec_bytes, uint8_t* out,
-                               size_t out_bytes, Source* s, Scans* c, Records* r, Output* o, size_t header_pitch = kHeaderPitch,
-                               int min_restart = 1) {
+                               size_t out_bytes, Source* s, Scans* c, Records* r, Output* o, size_t header_pitch) {
     if (!h_desc || !headers || !header_len || !slots || !scan_len || !src_bytes || !src_quant || !src_frames || !src_segments || !rec || !out)
         return "null argument";
     if (!recode_layout(m, n_segments, r)) return "m outside 1..65535 or n_segments < 0";
     if (rec_bytes < r->nbytes) return "the record buffer is shorter than tstar_jpeg_recode_layout says";
     if (n_headers <= 0 || n_src_frames <= 0 || n_src_segments < 0) return "no header or an empty source batch";
-    if (restart < min_restart || restart > 65535 || n_mcu < 1) return "restart interval outside 1..65535 or no MCU";
+    if (restart < 0 || restart > 65535 || n_mcu < 1) return "restart interval outside 0..65535 or no MCU";
     if (header_pitch < 16 || header_pitch % 16 || header_pitch > 65536) return "header_pitch must be a multiple of 16 in 16..65536";
     if (slot_bytes < 16 || slot_bytes % 16 || slot_bytes >= (1ull << 31)) return "slot_bytes must be a multiple of 16 in 16..2^31-1";
     if (src_total >= (1ull << 32) || out_bytes >= (1ull << 32)) return "a piece addresses its bytes with 32 bits";

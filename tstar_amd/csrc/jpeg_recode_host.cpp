@@ -70,22 +70,8 @@ size_t tstar_jpeg_recode_layout(int m, int n_segments, size_t* out5) {
     return (size_t)r.nbytes;
 }
 
-int tstar_jpeg_recode_assemble_host(const void* desc, int m, int n_segments, const uint8_t* headers, const uint32_t* header_len, int n_headers,
-                                    const uint8_t* slots, size_t slot_bytes, const uint32_t* scan_len, int restart, int n_mcu,
-                                    const uint8_t* src_bytes, size_t src_total, const uint16_t* src_quant, const void* src_frames,
-                                    const void* src_segments, int n_src_frames, int n_src_segments, uint8_t* rec, size_t rec_bytes,
-                                    uint8_t* out, size_t out_bytes) {
-    Source s; Scans c; Records r; Output o;
-    const char* bad = recode_args(desc, m, n_segments, headers, header_len, n_headers, slots, slot_bytes, scan_len, restart, n_mcu, src_bytes,
-                                  src_total, src_quant, src_frames, src_segments, n_src_frames, n_src_segments, rec, rec_bytes, out, out_bytes,
-                                  &s, &c, &r, &o);
-    if (bad) { set_error(std::string("tstar_jpeg_recode_assemble_host: ") + bad); return 1; }
-    jpeg_recode_assemble_host((const RecodeDesc*)desc, s, c, r, o);
-    return 0;
-}
-
-// added entry: rows of header_pitch bytes (a multiple of 16; headers with tables of their own are longer than 1024 bytes), one row
-// per frame or per group of frames, and restart 0 (no DRI, no marker: a frame is one segment)
+// rows of header_pitch bytes (a multiple of 16; headers with tables of their own are longer than 1024 bytes), one row per frame or
+// per group of frames, and restart 0 allowed (no DRI, no marker: a frame is one segment)
 int tstar_jpeg_recode_assemble_host_opt(const void* desc, int m, int n_segments, const uint8_t* headers, size_t header_pitch,
                                         const uint32_t* header_len, int n_headers, const uint8_t* slots, size_t slot_bytes,
                                         const uint32_t* scan_len, int restart, int n_mcu, const uint8_t* src_bytes, size_t src_total,
@@ -94,10 +80,22 @@ int tstar_jpeg_recode_assemble_host_opt(const void* desc, int m, int n_segments,
     Source s; Scans c; Records r; Output o;
     const char* bad = recode_args(desc, m, n_segments, headers, header_len, n_headers, slots, slot_bytes, scan_len, restart, n_mcu, src_bytes,
                                   src_total, src_quant, src_frames, src_segments, n_src_frames, n_src_segments, rec, rec_bytes, out, out_bytes,
-                                  &s, &c, &r, &o, header_pitch, 0);
+                                  &s, &c, &r, &o, header_pitch);
     if (bad) { set_error(std::string("tstar_jpeg_recode_assemble_host_opt: ") + bad); return 1; }
     jpeg_recode_assemble_host((const RecodeDesc*)desc, s, c, r, o);
     return 0;
+}
+
+int tstar_jpeg_recode_assemble_host(const void* desc, int m, int n_segments, const uint8_t* headers, const uint32_t* header_len, int n_headers,
+                                    const uint8_t* slots, size_t slot_bytes, const uint32_t* scan_len, int restart, int n_mcu,
+                                    const uint8_t* src_bytes, size_t src_total, const uint16_t* src_quant, const void* src_frames,
+                                    const void* src_segments, int n_src_frames, int n_src_segments, uint8_t* rec, size_t rec_bytes,
+                                    uint8_t* out, size_t out_bytes) {
+    // the entry of the standard tables: rows of kHeaderPitch bytes and always an interval; the rest is the _opt entry's
+    if (restart < 1) { set_error("tstar_jpeg_recode_assemble_host: restart interval outside 1..65535 or no MCU"); return 1; }
+    return tstar_jpeg_recode_assemble_host_opt(desc, m, n_segments, headers, kHeaderPitch, header_len, n_headers, slots, slot_bytes, scan_len, restart,
+                                               n_mcu, src_bytes, src_total, src_quant, src_frames, src_segments, n_src_frames, n_src_segments, rec,
+                                               rec_bytes, out, out_bytes);
 }
 
 }  // extern "C"

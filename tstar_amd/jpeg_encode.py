@@ -87,20 +87,17 @@ def _restart_values(restart_rows, restart_blocks) -> tuple:
 
 
 class Plan:
-    """tstar_jpeg_encode_plan_rst: sizes and launch shape for n frames of W x H whose scans go into slots of slot_bytes.  With
+    """tstar_jpeg_encode_plan_opt: sizes and launch shape for n frames of W x H whose scans go into slots of slot_bytes.  With
     ``restart`` (MCUs per interval; 0: none) the bounds hold the markers and the padding, and ``markers`` is their number per
-    frame.  With ``optimize`` (tstar_jpeg_encode_plan_opt) a block's bound is 1665 bits, ``header_bytes`` is the LONGEST header and
-    the workspace holds the symbol counts (at ``off_hist``) and the code tables (at ``off_codes``)."""
+    frame.  With ``optimize`` a block's bound is 1665 bits, ``header_bytes`` is the LONGEST header and the workspace holds the symbol
+    counts (at ``off_hist``) and the code tables (at ``off_codes``); without it the values are tstar_jpeg_encode_plan_rst's."""
     FIELDS = ("blocks", "coef_bytes", "max_scan_bytes", "header_bytes", "workspace_bytes", "block_wgs", "entropy_wgs_x", "stuff_wgs_x")
 
     def __init__(self, W: int, H: int, hs: int, vs: int, n: int = 1, slot_bytes: int = 2, restart: int = 0, optimize: bool = False):
         from . import _lib
         out, out2, out3 = (C.c_size_t * 8)(), (C.c_size_t * 2)(), (C.c_size_t * 3)()
-        if optimize:
-            _lib.check(_lib.load().tstar_jpeg_encode_plan_opt(W, H, hs, vs, n, slot_bytes, restart, 1, out, out2, out3),
-                       "tstar_jpeg_encode_plan_opt")
-        else:
-            _lib.check(_lib.load().tstar_jpeg_encode_plan_rst(W, H, hs, vs, n, slot_bytes, restart, out, out2), "tstar_jpeg_encode_plan_rst")
+        _lib.check(_lib.load().tstar_jpeg_encode_plan_opt(W, H, hs, vs, n, slot_bytes, restart, 1 if optimize else 0, out, out2, out3),
+                   "tstar_jpeg_encode_plan_opt")
         self.optimize, self.off_hist, self.off_codes = bool(optimize), int(out3[1]), int(out3[2])
         self.restart, self.markers = int(restart), int(out2[1])
         for k, v in zip(self.FIELDS, out):
@@ -245,20 +242,16 @@ def scan_host(coef: np.ndarray, W: int, H: int, subsampling="4:2:0", slot_bytes:
     out = np.empty((n, slot), dtype=np.uint8)
     lengths = np.zeros(n, dtype=np.uint32)
     status = np.full(n, -1, dtype=np.int32)
-    if optimize:
+    entry, own = "tstar_jpeg_encode_scan_host_rst", ()
+    if optimize:                                        # the _opt entry takes the frames' tables and counts behind the statuses
         specs = np.zeros((n, 4), dtype=SPEC_DTYPE)
         hist = np.zeros((n, 4, HIST_BINS), dtype=np.uint32)
-        _lib.check(_lib.load().tstar_jpeg_encode_scan_host_opt(coef.ctypes.data, n, W, H, hs, vs, restart, out.ctypes.data, slot,
-                                                               lengths.ctypes.data, status.ctypes.data, specs.ctypes.data, hist.ctypes.data,
-                                                               threads, _counter_ptr(counters), _counter_ptr(restart_counters, RESTART_COUNTERS)),
-                   "tstar_jpeg_encode_scan_host_opt")
-        if tables is not None:
-            tables.update(specs=specs, hist=hist)
-        return [out[i, :lengths[i]].tobytes() if status[i] == 0 else None for i in range(n)], lengths, status
-    _lib.check(_lib.load().tstar_jpeg_encode_scan_host_rst(coef.ctypes.data, n, W, H, hs, vs, restart, out.ctypes.data, slot,
-                                                           lengths.ctypes.data, status.ctypes.data, threads, _counter_ptr(counters),
-                                                           _counter_ptr(restart_counters, RESTART_COUNTERS)),
-               "tstar_jpeg_encode_scan_host_rst")
+        entry, own = "tstar_jpeg_encode_scan_host_opt", (specs.ctypes.data, hist.ctypes.data)
+    _lib.check(getattr(_lib.load(), entry)(coef.ctypes.data, n, W, H, hs, vs, restart, out.ctypes.data, slot, lengths.ctypes.data,
+                                           status.ctypes.data, *own, threads, _counter_ptr(counters),
+                                           _counter_ptr(restart_counters, RESTART_COUNTERS)), entry)
+    if optimize and tables is not None:
+        tables.update(specs=specs, hist=hist)
     return [out[i, :lengths[i]].tobytes() if status[i] == 0 else None for i in range(n)], lengths, status
 
 

@@ -8,7 +8,7 @@ RSTn every ``restart`` MCUs) under a header that carries the SOURCE's quantisati
 
 ``recode_host`` is the host twin (``jpeg.entropy_batch`` + ``jpeg_encode.scan_host``; no GPU).  ``DeviceRecoder`` is the device
 path for one chunk of an ``jpeg.EntropyRunner``: tstar_jpeg_encode_scan_rst on the coefficients the runner left in HBM, one read of
-the lengths and statuses, then tstar_jpeg_recode_assemble builds the piece of the new arena and its records on the device
+the lengths and statuses, then tstar_jpeg_recode_assemble_opt builds the piece of the new arena and its records on the device
 (csrc/jpeg_recode.hip) -- no compressed byte goes to the host.  ``jpeg_resident.load_resident(recode_blocks=)`` drives it at open;
 ``jpeg_encode.recode_frames`` / ``recode_mjpeg`` drive it file to file.
 
@@ -31,6 +31,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -120,16 +121,17 @@ def new_stats(optimize: bool = False) -> dict:
     return {k: 0 for k in STATS + (("optimized", "table_sets") if optimize else ())}
 
 
-def _count(stats: Optional[dict], kept: bool, n_in: int, n_out: int, table_bytes: Optional[int] = None) -> None:
-    """table_bytes: None without ``optimize`` (no key is added); else the bytes of the frame's DHT segments (0 for a kept frame)."""
+def _count(stats: Optional[dict], kept: bool, n_in: int, n_out: int, optimize: bool = False, table_bytes: Optional[int] = None) -> None:
+    """One frame into ``stats``.  ``optimize``: ``optimized`` counts the re-coded frames too.  ``table_bytes`` (the per-frame mode
+    alone; the shared mode counts its ``table_sets`` instead): the bytes of the frame's DHT segments, 0 for a kept frame."""
     if stats is not None:
         stats["kept" if kept else "recoded"] = stats.get("kept" if kept else "recoded", 0) + 1
         stats["bytes_in"] = stats.get("bytes_in", 0) + int(n_in)
         stats["bytes_out"] = stats.get("bytes_out", 0) + int(n_out)
-        if table_bytes is not None:
+        if optimize:
             stats["optimized"] = stats.get("optimized", 0) + (0 if kept else 1)
-            if "table_sets" not in stats:                   # the file-to-file entries; an arena counts its table sets instead
-                stats["table_bytes"] = stats.get("table_bytes", 0) + int(table_bytes)
+        if table_bytes is not None:
+            stats["table_bytes"] = stats.get("table_bytes", 0) + int(table_bytes)
 
 
 def recodable(geom) -> bool:
@@ -162,21 +164,11 @@ def recode_host(datas: Sequence[bytes], restart: int, stats: Optional[dict] = No
         out = []
         for data in datas:
             new = _recode_one_host(data, restart, optimize)
-            _count(stats, new is None, len(data), len(data if new is None else new), _table_bytes(new) if optimize else None)
+            _count(stats, new is None, len(data), len(data if new is None else new), optimize, _table_bytes(new) if optimize else None)
             out.append(data if new is None else new)
         return out
-    if stats is not None:
-        stats.setdefault("table_sets", 0)
     out: List[Optional[bytes]] = [None] * len(datas)
-    by_geom = {}
-    for i, d in enumerate(datas):
-        geom = covered(d)
-        if geom is None:
-            out[i] = d
-            _count(stats, True, len(d), len(d), 0)
-        else:
-            by_geom.setdefault(geom, []).append(i)
-    for geom, ids in by_geom.items():
+    for geom, ids in _by_geometry(datas, out, stats, True, True).items():
         blocks, _ = jpeg._sizes(geom)
         step = jpeg.device_entropy_chunk(blocks, len(ids), chunk)
         k0 = 0
@@ -187,6 +179,22 @@ def recode_host(datas: Sequence[bytes], restart: int, stats: Optional[dict] = No
                 out[i] = f
             k0 += len(part)
     return out
+
+
+def _by_geometry(datas: Sequence[bytes], out: list, stats: Optional[dict], optimize: bool, shared: bool) -> dict:
+    """The files the re-coder takes -> {geometry: their indices, in order}.  The others go into ``out`` as they are and are counted as
+    kept, with the keys of the mode: ``table_sets`` (shared) or ``table_bytes`` (optimised tables per frame)."""
+    if shared and stats is not None:
+        stats.setdefault("table_sets", 0)
+    by_geom: dict = {}
+    for i, d in enumerate(datas):
+        geom = covered(d)
+        if geom is None:
+            out[i] = d
+            _count(stats, True, len(d), len(d), optimize, 0 if optimize and not shared else None)
+        else:
+            by_geom.setdefault(geom, []).append(i)
+    return by_geom
 
 
 def _table_bytes(new: Optional[bytes]) -> int:
@@ -232,10 +240,15 @@ def code_host(coef: np.ndarray, quant: np.ndarray, geom, restart: int, optimize:
         return None
     if st[0] != JE.STATUS_OK:
         raise RuntimeError("JPEG re-code (host): a scan did not fit the bound of its geometry")
-    q = np.asarray(quant).reshape(3, 64)
-    if optimize:
-        return JE.header_from_tables_specs(W, H, q, tables["specs"][0], sub, restart) + scans[0]
-    return JE.header_from_tables(W, H, q, sub, restart) + scans[0]
+    return _header(geom, quant, restart, tables["specs"][0] if optimize else None) + scans[0]
+
+
+def _header(geom, quant, restart: int, sp=None) -> bytes:
+    """SOI .. SOS of a re-coded frame: the source's quantisation rows and the tables the frame is coded with -- ``sp`` (SPEC_DTYPE
+    [4]) in its four DHT segments, or the standard ones (None)."""
+    W, H, _, hs, vs = geom
+    q, sub = np.asarray(quant).reshape(3, 64), _SUBSAMPLING[(hs, vs)]
+    return JE.header_from_tables(W, H, q, sub, restart) if sp is None else JE.header_from_tables_specs(W, H, q, sp, sub, restart)
 
 
 def code_host_shared(coef: np.ndarray, geom, restart: int, group: np.ndarray, n_groups: int, counts: Optional[np.ndarray] = None):
@@ -296,11 +309,11 @@ def recode_host_chunk(datas: Sequence[bytes], geom, restart: int, group_frames: 
         scans, _, specs, hist = code_host_shared(coef, geom, restart, group, n_groups, counts)
         for j, sc in enumerate(scans):
             if sc is not None:
-                out[j] = JE.header_from_tables_specs(W, H, quant[j].reshape(3, 64), specs[group[j]], _SUBSAMPLING[(hs, vs)], restart) + sc
+                out[j] = _header(geom, quant[j], restart, specs[group[j]]) + sc
                 kept[j] = False
     for j, d in enumerate(datas):
-        _count(stats, bool(kept[j]), len(d), len(out[j]), 0)
-    if stats is not None and "table_sets" in stats:
+        _count(stats, bool(kept[j]), len(d), len(out[j]), True)
+    if stats is not None:
         stats["table_sets"] += len({(int(group[j]), quant[j].tobytes()) for j in range(m) if not kept[j]})
     if info is not None:
         info.update(group=group, specs=specs, hist=hist, kept=kept)
@@ -325,9 +338,7 @@ def _std_huffman() -> np.ndarray:
 def recoded_table_set(src_set: np.ndarray) -> np.ndarray:
     """The table set of a re-coded frame: the standard Huffman tables; quantisation rows, zigzag order and energy limits (computed in
     double by the planner) are the source frame's."""
-    ts = np.array(src_set, dtype=np.uint8).reshape(jpeg.TABLE_SET_BYTES)
-    ts[:_HUFF_BYTES] = _std_huffman()
-    return ts
+    return optimized_table_set(src_set, None)
 
 
 _huffman_cache: dict = {}
@@ -350,9 +361,9 @@ def huffman_of_specs(specs) -> np.ndarray:
 
 
 def optimized_table_set(src_set: np.ndarray, specs) -> np.ndarray:
-    """``recoded_table_set`` for a frame coded with the tables of ``specs``."""
+    """``recoded_table_set`` for a frame coded with the tables of ``specs`` (None: the standard ones)."""
     ts = np.array(src_set, dtype=np.uint8).reshape(jpeg.TABLE_SET_BYTES)
-    ts[:_HUFF_BYTES] = huffman_of_specs(specs)
+    ts[:_HUFF_BYTES] = _std_huffman() if specs is None else huffman_of_specs(specs)
     return ts
 
 
@@ -388,7 +399,9 @@ class PieceDesc:
         self.m, self.restart = m, restart
         self.n_mcu = ((W + 8 * hs - 1) // (8 * hs)) * ((H + 8 * vs - 1) // (8 * vs))
         n_int = (self.n_mcu + restart - 1) // restart if restart else 1
-        self.pitch = HEADER_PITCH if specs is None else HEADER_PITCH_OPT
+        self.pitch = HEADER_PITCH_OPT
+        if specs is None:                                   # the standard tables: one row, None, that every frame is coded with
+            specs, spec_of, self.pitch = [None], np.zeros(m, dtype=np.int64), HEADER_PITCH
         self.table_bytes = np.zeros(m, dtype=np.int64)
         self.table_keys = set()                             # (tables, quantisation set) of the re-coded frames
         desc = np.zeros(m, dtype=RECODE_DESC_DTYPE)
@@ -405,19 +418,16 @@ class PieceDesc:
                 d["n_segments"] = int(plan.frames["n_segments"][s]) if ts >= 0 else 0
                 out_len[j] = int(src_lens[s])
             else:
-                qkey = plan.quant[s].tobytes()
-                if specs is not None:
-                    sp = specs[int(spec_of[j])]
-                    qkey = (int(spec_of[j]), qkey)
+                sp = specs[int(spec_of[j])]
+                qkey = (int(spec_of[j]), plan.quant[s].tobytes())
+                if sp is not None:
                     self.table_keys.add(qkey)
                     self.table_bytes[j] = 4 * 21 + int(sp["nvals"].sum())
                 if qkey not in headers:
                     headers[qkey] = len(self.header_bytes)
-                    q = plan.quant[s].reshape(3, 64)
-                    self.header_bytes.append(JE.header_from_tables(W, H, q, _SUBSAMPLING[(hs, vs)], restart) if specs is None
-                                             else JE.header_from_tables_specs(W, H, q, sp, _SUBSAMPLING[(hs, vs)], restart))
+                    self.header_bytes.append(_header(geom, plan.quant[s], restart, sp))
                 d["kind"], d["hdr"], d["n_segments"] = NEW, headers[qkey], n_int
-                key = (recoded_table_set(plan.table_sets[ts]) if specs is None else optimized_table_set(plan.table_sets[ts], sp)).tobytes()
+                key = optimized_table_set(plan.table_sets[ts], sp).tobytes()
                 out_len[j] = len(self.header_bytes[d["hdr"]]) + int(scan_len[j])
             d["table_set"] = -1 if key is None else sets.setdefault(key, len(sets))
         desc["first_segment"] = np.cumsum(desc["n_segments"], dtype=np.int64) - desc["n_segments"]
@@ -448,7 +458,7 @@ class PieceDesc:
 
 
 def assemble_host(pd: PieceDesc, slots: np.ndarray, scan_len: np.ndarray, src_bytes: np.ndarray, plan: jpeg.SegmentPlan):
-    """The host mirror of the assembly (tstar_jpeg_recode_assemble_host) -> (output bytes uint8 [total], record buffer uint8)."""
+    """The host mirror of the assembly (tstar_jpeg_recode_assemble_host_opt) -> (output bytes uint8 [total], record buffer uint8)."""
     from . import _lib
     nrec, _ = recode_layout(pd.m, pd.n_segments)
     rec = _aligned16(np.zeros(nrec, dtype=np.uint8))
@@ -457,17 +467,11 @@ def assemble_host(pd: PieceDesc, slots: np.ndarray, scan_len: np.ndarray, src_by
     scan_len = np.ascontiguousarray(scan_len, dtype=np.uint32)
     segs = plan.segments if len(plan.segments) else np.zeros(1, dtype=jpeg.SEGMENT_DTYPE)
     quant = _aligned16(plan.quant)
-    tail = (_aligned16(slots).ctypes.data, slots.shape[1], scan_len.ctypes.data, pd.restart, pd.n_mcu, src_bytes.ctypes.data, plan.total_bytes,
-            quant.ctypes.data, plan.frames.ctypes.data, segs.ctypes.data, len(plan.frames), len(plan.segments), rec.ctypes.data, rec.size,
-            out.ctypes.data, pd.total)
-    if pd.pitch == HEADER_PITCH:
-        _lib.check(_lib.load().tstar_jpeg_recode_assemble_host(
-            pd.desc.ctypes.data, pd.m, pd.n_segments, _aligned16(pd.headers).ctypes.data, pd.header_len.ctypes.data, len(pd.header_len),
-            *tail), "tstar_jpeg_recode_assemble_host")
-    else:
-        _lib.check(_lib.load().tstar_jpeg_recode_assemble_host_opt(
-            pd.desc.ctypes.data, pd.m, pd.n_segments, _aligned16(pd.headers).ctypes.data, pd.pitch, pd.header_len.ctypes.data,
-            len(pd.header_len), *tail), "tstar_jpeg_recode_assemble_host_opt")
+    _lib.check(_lib.load().tstar_jpeg_recode_assemble_host_opt(
+        pd.desc.ctypes.data, pd.m, pd.n_segments, _aligned16(pd.headers).ctypes.data, pd.pitch, pd.header_len.ctypes.data, len(pd.header_len),
+        _aligned16(slots).ctypes.data, slots.shape[1], scan_len.ctypes.data, pd.restart, pd.n_mcu, src_bytes.ctypes.data, plan.total_bytes,
+        quant.ctypes.data, plan.frames.ctypes.data, segs.ctypes.data, len(plan.frames), len(plan.segments), rec.ctypes.data, rec.size,
+        out.ctypes.data, pd.total), "tstar_jpeg_recode_assemble_host_opt")
     return out[:pd.total], rec
 
 
@@ -514,10 +518,10 @@ class DeviceRecoder:
         self.max_slot = (one.max_scan_bytes + 15) // 16 * 16
         self.first_slot = None if slot_bytes is None else min(self.max_slot, max(16, (int(slot_bytes) + 15) // 16 * 16))
         self.alloc = alloc if alloc is not None else self._alloc
-        self.bufs = None
+        self.bufs = None                                    # m, slot, work, out, meta, specs (per-frame tables only)
         self.retried = 0
         self.group_frames = _group_frames(group_frames, self.blocks) if self.shared else None
-        self.groups = None                                  # shared: (group int32 [n], n_groups, d_hist, d_specs) of the chunk in work
+        self.groups = None                                  # shared: group (int32 [n]), n, d_hist, d_specs of the chunk in work
         self.last_specs = None                              # optimize: the specs of the last piece (per frame) or chunk (per group)
         self.table_keys = set()
         if self.shared and stats is not None:
@@ -529,16 +533,14 @@ class DeviceRecoder:
 
     def _buffers(self, m: int, slot: int):
         import torch
-        if self.bufs is None or self.bufs[0] < m or self.bufs[1] != slot:
+        if self.bufs is None or self.bufs.m < m or self.bufs.slot != slot:
             self.bufs = None
             W, H, _, hs, vs = self.geom
             p = JE.Plan(W, H, hs, vs, m, slot, self.restart, self.optimize)
-            self.bufs = (m, slot, torch.empty(p.workspace_bytes, dtype=torch.uint8, device=self.device),
-                         torch.empty((m, slot), dtype=torch.uint8, device=self.device),
-                         torch.empty((2, m), dtype=torch.int32, device=self.device),
-                         torch.empty((m, 4 * JE.SPEC_BYTES), dtype=torch.uint8, device=self.device) if self.optimize and not self.shared
-                         else None)
-        return self.bufs[2:]
+            new = lambda *shape, dtype=torch.uint8: torch.empty(shape, dtype=dtype, device=self.device)          # noqa: E731
+            self.bufs = SimpleNamespace(m=m, slot=slot, work=new(p.workspace_bytes), out=new(m, slot), meta=new(2, m, dtype=torch.int32),
+                                        specs=new(m, 4 * JE.SPEC_BYTES) if self.optimize and not self.shared else None)
+        return self.bufs
 
     def recode_chunk(self, batch: jpeg.DeviceBatch, d_buf, d_coef, bad) -> List[Piece]:
         """The chunk ``batch`` (uploaded into ``d_buf``, its coefficients in ``d_coef``; ``bad``: the frames the device did not
@@ -554,34 +556,34 @@ class DeviceRecoder:
         if self.shared:
             group, n_groups = make_groups(~bad_mask, self.group_frames)
             k = max(1, n_groups)
-            self.groups = (group, n_groups, torch.empty((k, 4 * JE.HIST_BINS), dtype=torch.int32, device=self.device),
-                           torch.empty((k, 4 * JE.SPEC_BYTES), dtype=torch.uint8, device=self.device))
+            self.groups = SimpleNamespace(group=group, n=n_groups,
+                                          d_hist=torch.empty((k, 4 * JE.HIST_BINS), dtype=torch.int32, device=self.device),
+                                          d_specs=torch.empty((k, 4 * JE.SPEC_BYTES), dtype=torch.uint8, device=self.device))
             self.last_specs = None
         self.table_keys = set()                             # (group, quantisation set) of the chunk's re-coded frames, counted once
         return self._pieces(batch, d_buf, d_coef, bad_mask, src_lens, 0, n, slot, True)
 
-    def _scan(self, d_coef, a: int, m: int, slot: int, work, out, meta, d_specs, first: bool):
-        """The scan stage for frames [a, a + m) of the chunk -> (specs SPEC_DTYPE [k, 4] or None, spec_of int [m] or None)."""
+    def _scan(self, d_coef, a: int, m: int, slot: int, bufs, first: bool):
+        """The scan stage of the mode for frames [a, a + m) of the chunk, into ``bufs`` -> spec_of: the row of the mode's specs
+        (``_specs``) every frame is coded with (int [m], -1: none; None with the standard tables)."""
         import torch
         from . import _lib
         lib = _lib.load()
         W, H, _, hs, vs = self.geom
+        head = (d_coef.data_ptr() + a * self.blocks * 128, m, W, H, hs, vs, self.restart)
+        tail = (bufs.out.data_ptr(), slot, bufs.meta[0].data_ptr(), bufs.meta[1].data_ptr())
+        work = (bufs.work.data_ptr(), bufs.work.numel())
         s = _lib.stream_ptr()
-        coef = d_coef.data_ptr() + a * self.blocks * 128
         if not self.optimize:
-            _lib.check(lib.tstar_jpeg_encode_scan_rst(coef, m, W, H, hs, vs, self.restart, out.data_ptr(), slot, meta[0].data_ptr(),
-                                                      meta[1].data_ptr(), work.data_ptr(), work.numel(), None, s),
-                       "tstar_jpeg_encode_scan_rst")
-            return None, None
+            _lib.check(lib.tstar_jpeg_encode_scan_rst(*head, *tail, *work, None, s), "tstar_jpeg_encode_scan_rst")
+            return None
         if not self.shared:
-            _lib.check(lib.tstar_jpeg_encode_scan_opt(coef, m, W, H, hs, vs, self.restart, out.data_ptr(), slot, meta[0].data_ptr(),
-                                                      meta[1].data_ptr(), d_specs.data_ptr(), work.data_ptr(), work.numel(), None, s),
-                       "tstar_jpeg_encode_scan_opt")
-            return None, np.arange(m)
-        group, n_groups, d_hist, d_gspecs = self.groups
-        sub = group[a:a + m]
+            _lib.check(lib.tstar_jpeg_encode_scan_opt(*head, *tail, bufs.specs.data_ptr(), *work, None, s), "tstar_jpeg_encode_scan_opt")
+            return np.arange(m)
+        g = self.groups
+        sub = g.group[a:a + m]
         if not (sub >= 0).any():
-            return None, sub                                # no frame of these has a group: all are kept, nothing is coded
+            return sub                                      # no frame of these has a group: all are kept, nothing is coded
         g0, g1 = int(sub[sub >= 0].min()), int(sub.max()) + 1
         local = np.where(sub >= 0, sub - g0, -1).astype(np.int32)
         span = np.zeros((g1 - g0, 2), dtype=np.int32)
@@ -591,23 +593,29 @@ class DeviceRecoder:
         # the first pass covers the whole chunk: counts, sums, tables, scans.  A later pass (a larger slot, or a part of the chunk)
         # keeps the sums of the first: a group's tables do not depend on how the chunk is cut
         stages = 7 if first else 6
-        _lib.check(lib.tstar_jpeg_encode_scan_grp(coef, m, W, H, hs, vs, self.restart, local.ctypes.data, span.ctypes.data, d_gs.data_ptr(),
-                                                  d_gs.data_ptr() + 4 * m, g1 - g0, stages, d_hist.data_ptr() + g0 * 16 * JE.HIST_BINS,
-                                                  d_gspecs.data_ptr() + g0 * 4 * JE.SPEC_BYTES, out.data_ptr(), slot, meta[0].data_ptr(),
-                                                  meta[1].data_ptr(), work.data_ptr(), work.numel(), s), "tstar_jpeg_encode_scan_grp")
-        return None, sub
+        _lib.check(lib.tstar_jpeg_encode_scan_grp(*head, local.ctypes.data, span.ctypes.data, d_gs.data_ptr(), d_gs.data_ptr() + 4 * m, g1 - g0,
+                                                  stages, g.d_hist.data_ptr() + g0 * 16 * JE.HIST_BINS,
+                                                  g.d_specs.data_ptr() + g0 * 4 * JE.SPEC_BYTES, *tail, *work, s), "tstar_jpeg_encode_scan_grp")
+        return sub
+
+    def _specs(self, bufs, m: int):
+        """The tables of the mode, read back behind a scan stage that coded something (SPEC_DTYPE [k, 4]; None: the standard ones):
+        one more small read per piece for the frames' own, one per chunk for the groups'."""
+        if self.optimize and not self.shared:
+            self.last_specs = bufs.specs[:m].cpu().numpy().view(JE.SPEC_DTYPE).reshape(m, 4)
+        elif self.shared and self.last_specs is None:
+            self.last_specs = self.groups.d_specs[:self.groups.n].cpu().numpy().view(JE.SPEC_DTYPE).reshape(self.groups.n, 4)
+        return self.last_specs
 
     def _pieces(self, batch, d_buf, d_coef, bad_mask, src_lens, a: int, b: int, slot: int, first: bool = False) -> List[Piece]:
         import torch
         from . import _lib
-        lib = _lib.load()
         m = b - a
-        work, out, meta, d_specs = self._buffers(m, slot)
-        s = _lib.stream_ptr()
-        _, spec_of = self._scan(d_coef, a, m, slot, work, out, meta, d_specs, first)
+        bufs = self._buffers(m, slot)
+        spec_of = self._scan(d_coef, a, m, slot, bufs, first)
         coded = not self.shared or bool((spec_of >= 0).any())
         if coded:
-            meta_h = meta[:, :m].cpu().numpy()           # ONE read: lengths (u32 bits) and statuses
+            meta_h = bufs.meta[:, :m].cpu().numpy()      # ONE read: lengths (u32 bits) and statuses
             scan_len, status = meta_h[0].view(np.uint32).astype(np.int64), meta_h[1]
         else:
             scan_len, status = np.zeros(m, dtype=np.int64), np.full(m, JE.STATUS_HUFF_OVERFLOW, dtype=np.int32)
@@ -622,13 +630,7 @@ class DeviceRecoder:
             step = max(1, min(m, RETRY_BYTES // self.max_slot))
             return [p for s0 in range(a, b, step)
                     for p in self._pieces(batch, d_buf, d_coef, bad_mask, src_lens, s0, min(b, s0 + step), self.max_slot)]
-        specs = None
-        if self.optimize and not self.shared:               # one more small read: the frames' tables
-            specs = self.last_specs = d_specs[:m].cpu().numpy().view(JE.SPEC_DTYPE).reshape(m, 4)
-        elif self.shared and coded:
-            if self.last_specs is None:                     # one more small read per chunk: the groups' tables
-                self.last_specs = self.groups[3][:self.groups[1]].cpu().numpy().view(JE.SPEC_DTYPE).reshape(self.groups[1], 4)
-            specs = self.last_specs
+        specs = self._specs(bufs, m) if coded else None
         pd = PieceDesc(batch.plan, src_lens, a, b, kept, scan_len, self.geom, self.restart, specs, spec_of if specs is not None else None)
         if pd.total >= PIECE_LIMIT:
             if m == 1:
@@ -641,20 +643,15 @@ class DeviceRecoder:
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).to(self.device)      # noqa: E731
         d_desc, d_headers, d_hlen = up(pd.desc), up(pd.headers), up(pd.header_len)
         base, parts, plan = d_buf.data_ptr(), batch.parts, batch.plan
-        tail = (out.data_ptr(), slot, meta[0].data_ptr(), self.restart, pd.n_mcu, base, batch.total, base + parts["quant"][0],
-                base + parts["frames"][0], base + parts["segments"][0], len(plan.frames), len(plan.segments), d_rec.data_ptr(), nrec,
-                d_out.data_ptr(), pd.total, int(pd.out_len.max()), s)
-        if not self.optimize:
-            _lib.check(lib.tstar_jpeg_recode_assemble(
-                pd.desc.ctypes.data, d_desc.data_ptr(), m, pd.n_segments, d_headers.data_ptr(), d_hlen.data_ptr(), len(pd.header_len), *tail),
-                "tstar_jpeg_recode_assemble")
-        else:
-            _lib.check(lib.tstar_jpeg_recode_assemble_opt(
-                pd.desc.ctypes.data, d_desc.data_ptr(), m, pd.n_segments, d_headers.data_ptr(), pd.headers.shape[1], d_hlen.data_ptr(),
-                len(pd.header_len), *tail), "tstar_jpeg_recode_assemble_opt")
+        _lib.check(_lib.load().tstar_jpeg_recode_assemble_opt(
+            pd.desc.ctypes.data, d_desc.data_ptr(), m, pd.n_segments, d_headers.data_ptr(), pd.pitch, d_hlen.data_ptr(), len(pd.header_len),
+            bufs.out.data_ptr(), slot, bufs.meta[0].data_ptr(), self.restart, pd.n_mcu, base, batch.total, base + parts["quant"][0],
+            base + parts["frames"][0], base + parts["segments"][0], len(plan.frames), len(plan.segments), d_rec.data_ptr(), nrec,
+            d_out.data_ptr(), pd.total, int(pd.out_len.max()), _lib.stream_ptr()), "tstar_jpeg_recode_assemble_opt")
         rec = d_rec[:nrec].cpu().numpy()                 # the records only: the bytes stay on the device
+        per_frame = self.optimize and not self.shared       # tables of the frames' own are counted in bytes, shared ones in sets
         for j in range(m):
-            _count(self.stats, bool(kept[j]), src_lens[a + j], pd.out_len[j], int(pd.table_bytes[j]) if self.optimize else None)
+            _count(self.stats, bool(kept[j]), src_lens[a + j], pd.out_len[j], self.optimize, int(pd.table_bytes[j]) if per_frame else None)
         if self.shared and self.stats is not None:
             self.stats["table_sets"] += len(pd.table_keys - self.table_keys)
             self.table_keys |= pd.table_keys
@@ -675,21 +672,12 @@ def recode_device(datas: Sequence[bytes], restart: int, device="cuda", chunk: Op
     ``optimize`` / ``shared`` / ``group_frames``: ``recode_host``'s."""
     import torch
     restart = recode_restart(restart, optimize)
-    if shared and stats is not None:
-        stats.setdefault("table_sets", 0)
     datas = [bytes(d) for d in datas]
     out: List[Optional[bytes]] = [None] * len(datas)
-    groups = {}
-    for i, d in enumerate(datas):
-        geom = covered(d)
-        if geom is None:
-            out[i] = d
-            _count(stats, True, len(d), len(d), 0 if optimize else None)
-        else:
-            groups.setdefault(geom, []).append(i)
+    by_geom = _by_geometry(datas, out, stats, optimize, shared)
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream()
-        for geom, ids in groups.items():
+        for geom, ids in by_geom.items():
             files = [datas[i] for i in ids]
             run = runner_for(files, geom, device, chunk)
             rec = DeviceRecoder(geom, device, restart, stats, alloc, slot_bytes, optimize, shared, group_frames)
